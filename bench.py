@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- walk-generation throughput of the MI355X engine (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config headline|C2|C3|C4|C5] [--scale S]
+    python bench.py --gpus N --steps K --warmup W [--config headline|C2|C3|C4|C5] [--scale S] [--dump-outputs DIR] [--full]
 
 One "step" = one full pass of the hot path (MT19937 stream expansion + all walk kernels + for N > 1 the one
 gather of the walk shards on rank 0) over the whole job array of the workload.  Default workload = the
@@ -15,6 +15,10 @@ per GPU; when WORLD_SIZE is not set the script launches the N ranks itself (torc
 Graph replicated, job array sharded, strong scaling (total work fixed); the walk shards are gathered once on rank 0
 over RCCL/xGMI inside the timed region (--no-gather leaves every shard on the GPU that produced it).  Rank 0 prints
 ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does not
+need: the roofline of the dominant kernel, the CPU baseline (--no-cpu-baseline drops it) and one call on host pointers
+(--no-host-call drops it).  --dump-outputs DIR writes the walk matrix of the last timed step as DIR/walks.npy (float64;
+a fixed, seeded sample of its rows when the whole matrix exceeds DUMP_BYTES).
 """
 import argparse
 import json
@@ -30,6 +34,7 @@ sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 RANDOM_SECTOR_GBS = 3100.0     # measured: scattered 64-byte sectors, profiles/r02_fetch_calibration.txt
+DUMP_BYTES = 48 << 20          # --dump-outputs: at most this many bytes of walk rows (float64)
 
 CONFIGS = {
     "headline": dict(graph="rmat", scale=22, p=0.5, q=2.0, mode="SparseOTF", weighted=False, extend=False),
@@ -57,8 +62,12 @@ def parse():
     ap.add_argument("--extend", action="store_true", help="node2vec+ (weighted graphs)")
     ap.add_argument("--self-loops", type=int, default=0, help="add this many random self loops to the RMAT graph (the reference "
                     "accepts them, graph.py:238-268; round 6: they keep the lane kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-call", action="store_true", help="skip the host-pointer call (config.host_call)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the roofline, the CPU baseline and the host-pointer call (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the walk matrix of the last timed step (rank 0's) as DIR/walks.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-call", action="store_true", help="--full: skip the host-pointer call (config.host_call)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--gather-chunks", default="auto",
                     help="N > 1: chunks per shard whose gathers overlap the next chunk's walk kernel; 'auto' = 2 / 3 / 4 for "
@@ -69,7 +78,10 @@ def parse():
                          "DESIGN.md section 6 (0.5 at 8 GPUs), 1 = uniform")
     ap.add_argument("--no-gather", action="store_true",
                     help="N > 1: leave the walk shards on their GPUs (skip the gather on rank 0)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(n):
@@ -136,6 +148,20 @@ def er_bits_gpu(n, density, dev, seed=1):
     bits = w32[:, 0::2] | (w32[:, 1::2] << 32)
     deg = adj[:, :n].sum(1)
     return bits.contiguous(), deg
+
+
+def dump_walks(mat, out_dir):
+    """--dump-outputs: the walk matrix (uint32 cells in int32 storage) as out_dir/walks.npy in float64 -- every row, or a
+    fixed sample (seed 0, ascending row order) of DUMP_BYTES worth of rows: the same rows for the same arguments."""
+    import torch
+
+    n, cols = mat.shape
+    k = max(1, min(n, DUMP_BYTES // (cols * 8)))
+    if k < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        mat = mat[torch.from_numpy(rows).to(mat.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "walks.npy"), mat.cpu().numpy().view(np.uint32).astype(np.float64))
 
 
 def load_pmc(key):
@@ -387,137 +413,142 @@ def main():
         assert torch.equal(gathered, whole), "gathered shards differ from the single-stream matrix"
         print("bench.py: gathered shards verified against a whole-array run", file=sys.stderr)
 
-    # ---- roofline of the dominant kernel (rank 0's shard) ------------------------------------------------------
-    lane = int(st["lane_kernel"]) in (1, 2)          # (3 = the weighted lane form: its own accounting below)
-    wlane = int(st["lane_kernel"]) == 3
-    k_ms = float(np.mean(acc["lane_kernel_ms"] if (lane or wlane) else acc["walk_kernel_ms"]))
-    steps0 = int(acc["total_steps"][-1])
-    walks0 = int(has_nbr[starts[lo:hi]].sum())
-    ref_bytes = None
-    if cfg["graph"] == "rmat":
-        deg_t = torch.from_numpy(np.diff(indptr.astype(np.int64))).to(dev)
-        common = None
-        if extend:   # section 8(d)'s node2vec+ formula needs |N(cur) & N(prev)| of every step: the lane index's per-entry counts
-            try:
-                cnt, _, _, _ = eng.lane_index()
-                rows_np = np.repeat(np.arange(n_nodes, dtype=np.int64), np.diff(indptr.astype(np.int64)))
-                common = (torch.from_numpy(rows_np * n_nodes + indices.astype(np.int64)).to(dev),
-                          torch.from_numpy(cnt.astype(np.int64)).to(dev), n_nodes)
-            except Exception:   # noqa: BLE001 (no lane index: the counts are left out, the figure says so)
-                common = None
-        ref_bytes = reference_format_bytes(d_out, deg_t, L, common)
-    if lane:
-        # declared format of the lane kernel: per sampled step one 64-byte edge line (the record
-        # of the edge the walk arrives by and -- for lists of up to 20 entries -- the list itself), one 8-byte draw, one
-        # 4-byte output cell, 2 bytes per common-neighbour list entry read (counted in the kernel; uint16 positions;
-        # entries read inside the edge line are counted twice, rows beyond 65536 entries use 4 bytes); per walk: start
-        # 4 + stream offset 8 + vertex record 16 + header/length cells 8
-        entries = int(acc["list_entries_read"][-1])
-        # ... and 128 bytes per step that needs the float32 chain (the walk's queue record, written and read back)
-        chain_steps = int(acc["wave_chain_steps"][-1])
-        floats_form = int(st["lane_kernel"]) == 2
-        declared = (steps0 * (64 + 8 + 4 + (4 if floats_form else 0)) + entries * 2 + (0 if floats_form else chain_steps * 128) +
-                    (hi - lo) * (4 + 8) + walks0 * (16 + 8) + (hi - lo - walks0) * 8)
-        kernel = ("walk_lanes_kernel (QUAD form: every round of a pass) + lanes_chain_kernel" if int(st["lane_kernel"]) == 1 else
-                  "walk_lanes_kernel<FLOATS> (1/p or 1/q not a power of two: float64-bounded decision from per-line row totals, "
-                  "float32 chains for the steps it leaves open, per lane)")
-        fmt = ("per step ONE 64 B edge line (record + inline list or pivots; fetched whole by a quad of lanes into LDS) + 8 B draw "
-               "+ 4 B output; 64 B per overflow-list sector a search visits (in-kernel counter, 32 two-byte entries' worth each) "
-               "and 2 B per list entry the float chains probe; 128 B per parked step (queue record out and back); 36 B per walk"
-               if int(st["lane_kernel"]) == 1 else
-               "64 B edge line + 8 B draw + 4 B output + 4 B row total per step, 2 B per common-neighbour list entry probed "
-               "(in-kernel counter), 36 B per walk")
-    elif cfg["graph"] == "er":
-        wpr = (n_nodes + 63) // 64
-        if wpr <= 2048:
-            # rows of up to 131 072 columns: the row of cur stays in registers and serves as prev's row one step later
-            declared = steps0 * (wpr * 8 + 12)
-            fmt = "packed adjacency: ONE row per step (the row of cur is kept in registers for the next step) + draw + output"
+    if args.dump_outputs:
+        dump_walks(gather.full if do_gather else d_out, args.dump_outputs)
+
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel (rank 0's shard) ------------------------------------------------------
+        lane = int(st["lane_kernel"]) in (1, 2)          # (3 = the weighted lane form: its own accounting below)
+        wlane = int(st["lane_kernel"]) == 3
+        k_ms = float(np.mean(acc["lane_kernel_ms"] if (lane or wlane) else acc["walk_kernel_ms"]))
+        steps0 = int(acc["total_steps"][-1])
+        walks0 = int(has_nbr[starts[lo:hi]].sum())
+        ref_bytes = None
+        if cfg["graph"] == "rmat":
+            deg_t = torch.from_numpy(np.diff(indptr.astype(np.int64))).to(dev)
+            common = None
+            if extend:   # section 8(d)'s node2vec+ formula needs |N(cur) & N(prev)| of every step: the lane index's per-entry counts
+                try:
+                    cnt, _, _, _ = eng.lane_index()
+                    rows_np = np.repeat(np.arange(n_nodes, dtype=np.int64), np.diff(indptr.astype(np.int64)))
+                    common = (torch.from_numpy(rows_np * n_nodes + indices.astype(np.int64)).to(dev),
+                              torch.from_numpy(cnt.astype(np.int64)).to(dev), n_nodes)
+                except Exception:   # noqa: BLE001 (no lane index: the counts are left out, the figure says so)
+                    common = None
+            ref_bytes = reference_format_bytes(d_out, deg_t, L, common)
+        if lane:
+            # declared format of the lane kernel: per sampled step one 64-byte edge line (the record
+            # of the edge the walk arrives by and -- for lists of up to 20 entries -- the list itself), one 8-byte draw, one
+            # 4-byte output cell, 2 bytes per common-neighbour list entry read (counted in the kernel; uint16 positions;
+            # entries read inside the edge line are counted twice, rows beyond 65536 entries use 4 bytes); per walk: start
+            # 4 + stream offset 8 + vertex record 16 + header/length cells 8
+            entries = int(acc["list_entries_read"][-1])
+            # ... and 128 bytes per step that needs the float32 chain (the walk's queue record, written and read back)
+            chain_steps = int(acc["wave_chain_steps"][-1])
+            floats_form = int(st["lane_kernel"]) == 2
+            declared = (steps0 * (64 + 8 + 4 + (4 if floats_form else 0)) + entries * 2 + (0 if floats_form else chain_steps * 128) +
+                        (hi - lo) * (4 + 8) + walks0 * (16 + 8) + (hi - lo - walks0) * 8)
+            kernel = ("walk_lanes_kernel (QUAD form: every round of a pass) + lanes_chain_kernel" if int(st["lane_kernel"]) == 1 else
+                      "walk_lanes_kernel<FLOATS> (1/p or 1/q not a power of two: float64-bounded decision from per-line row totals, "
+                      "float32 chains for the steps it leaves open, per lane)")
+            fmt = ("per step ONE 64 B edge line (record + inline list or pivots; fetched whole by a quad of lanes into LDS) + 8 B draw "
+                   "+ 4 B output; 64 B per overflow-list sector a search visits (in-kernel counter, 32 two-byte entries' worth each) "
+                   "and 2 B per list entry the float chains probe; 128 B per parked step (queue record out and back); 36 B per walk"
+                   if int(st["lane_kernel"]) == 1 else
+                   "64 B edge line + 8 B draw + 4 B output + 4 B row total per step, 2 B per common-neighbour list entry probed "
+                   "(in-kernel counter), 36 B per walk")
+        elif cfg["graph"] == "er":
+            wpr = (n_nodes + 63) // 64
+            if wpr <= 2048:
+                # rows of up to 131 072 columns: the row of cur stays in registers and serves as prev's row one step later
+                declared = steps0 * (wpr * 8 + 12)
+                fmt = "packed adjacency: ONE row per step (the row of cur is kept in registers for the next step) + draw + output"
+            else:
+                declared = steps0 * (3 * wpr * 8 + 12)
+                fmt = "packed adjacency: rows of cur and prev (count pass) + cur's row again (search segment) + draw + output"
+            # which kernel ran (launch_dense_bits' own conditions): the register-only kernel needs dyadic 1/p, 1/q, rows of at most
+            # 131 072 columns and no PECANPY_AMD_DENSE_NO_FAST
+            def _pow2(x):
+                m, _ = np.frexp(np.float32(1.0 / x))
+                return float(m) == 0.5
+            fast = wpr <= 2048 and _pow2(p) and _pow2(q) and not os.environ.get("PECANPY_AMD_DENSE_NO_FAST")
+            kernel = "walk_dense_fast_kernel" if fast else "walk_dense_bits_kernel"
+            if not fast:
+                declared = steps0 * (3 * wpr * 8 + 12)
+                fmt = "packed adjacency: rows of cur and prev (count pass) + cur's row again (search segment) + draw + output"
         else:
-            declared = steps0 * (3 * wpr * 8 + 12)
-            fmt = "packed adjacency: rows of cur and prev (count pass) + cur's row again (search segment) + draw + output"
-        # which kernel ran (launch_dense_bits' own conditions): the register-only kernel needs dyadic 1/p, 1/q, rows of at most
-        # 131 072 columns and no PECANPY_AMD_DENSE_NO_FAST
-        def _pow2(x):
-            m, _ = np.frexp(np.float32(1.0 / x))
-            return float(m) == 0.5
-        fast = wpr <= 2048 and _pow2(p) and _pow2(q) and not os.environ.get("PECANPY_AMD_DENSE_NO_FAST")
-        kernel = "walk_dense_fast_kernel" if fast else "walk_dense_bits_kernel"
-        if not fast:
-            declared = steps0 * (3 * wpr * 8 + 12)
-            fmt = "packed adjacency: rows of cur and prev (count pass) + cur's row again (search segment) + draw + output"
-    else:
-        # the wave-per-walk kernel streams rows (keys of the shorter row, weights of cur's row): SURVEY 8(d)'s
-        # figure in the reference's element sizes is its declared format
-        declared = ref_bytes
-        kernel = "walk_kernel<float,false,%s,%s>" % ("true" if not cfg["weighted"] else "false", "true" if extend else "false")
+            # the wave-per-walk kernel streams rows (keys of the shorter row, weights of cur's row): SURVEY 8(d)'s
+            # figure in the reference's element sizes is its declared format
+            declared = ref_bytes
+            kernel = "walk_kernel<float,false,%s,%s>" % ("true" if not cfg["weighted"] else "false", "true" if extend else "false")
+            if wlane:
+                kernel = ("walk_lanes_kernel<WEIGHTED> (float64-bounded decision per lane) + lanes_eager_weighted_kernel (wave scan of the "
+                          "steps the bound leaves open, from recorded chain values), every round of a pass")
+                # declared format of the weighted lane form: per step the 64-byte edge line, the draw and the
+                # output cell; per search probe a list entry and two float64 table values (18 B: an upper bound, probes inside a run
+                # read one value); per parked step its 64-byte queue record out and back and the scan window of the wave scan
+                # (at most 2 x 1024 elements from the last recorded chain value: 4-byte weights + 4-byte neighbour ids); 36 B per walk
+                probes = int(acc["list_entries_read"][-1])
+                eager = int(st["eager_steps"])
+                declared = (steps0 * (64 + 8 + 4) + probes * 18 + eager * (128 + 2048 * 8) + (hi - lo) * (4 + 8) + walks0 * (16 + 8) +
+                            (hi - lo - walks0) * 8)
+                fmt = ("64 B edge line + 8 B draw + 4 B output per step, 18 B per search probe (list entry + two float64 prefix values), "
+                       "per parked step 128 B of queue record + a scan window of at most 2048 elements x 8 B; 36 B per walk")
+            fmt_ref = ("SURVEY 8(d): 8*d_cur + 4*d_prev + 28 per step" +
+                   (" + 4*d_prev + 4*|N(cur)&N(prev)| + 4 (node2vec+)" if extend else "") +
+                   " -- the REFERENCE's row traffic, which this kernel's rows mostly take from L2 / Infinity Cache: `frac` here is an "
+                   "algorithmic-byte rate, NOT an HBM utilisation (that is traffic_frac_of_peak, from the PMC passes); the kernel is "
+                   "instruction bound (issue_bound)")
+            if not wlane:
+                fmt = fmt_ref
+        achieved = declared / (k_ms * 1e-3) / 1e9
+        key = f"{key_graph}_{mode}_p{p:g}_q{q:g}{'_ext' if extend else ''}_w{W}_l{L}_seed{args.seed}"
+        pmc = load_pmc(key) if world == 1 else None
+        traffic = int(pmc["fetch_bytes"] + pmc["write_bytes"]) if pmc else None
+        wide_note = ""
+        if pmc and mode == "DenseOTF" and cfg["graph"] == "er":
+            # on gfx950 FETCH_SIZE reports exactly half the bytes of a wide coalesced streaming
+            # read (128-byte requests tallied at 64 B) -- the packed rows are read that way (8 B per lane, 512 B per wavefront load)
+            traffic = int(2 * pmc["fetch_bytes"] + pmc["write_bytes"])
+            wide_note = (" FETCH_SIZE doubled: wide coalesced row reads are tallied at half their bytes on gfx950; "
+                         "raw counter value in traffic_raw_counter_bytes.")
+        roofline = {
+            "bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "declared_bytes_per_launch": int(declared), "declared_format": fmt,
+            "avg_launch_ms": round(k_ms, 3), "rng_jump_and_expand_ms": round(float(np.mean(acc["rng_kernel_ms"])), 3),
+            "traffic_note": ((pmc["note"] + wide_note) if pmc else "no PMC pass committed for this workload (profiles/r06_traffic.json)"),
+            "random_sector_peak_GBps": RANDOM_SECTOR_GBS,
+            "reference_format_bytes": ref_bytes,
+        }
+        if pmc and wide_note:
+            roofline["traffic_raw_counter_bytes"] = int(pmc["fetch_bytes"] + pmc["write_bytes"])
+        if traffic:
+            roofline["traffic_GBps"] = round(traffic / (k_ms * 1e-3) / 1e9, 1)
+            roofline["traffic_frac_of_peak"] = round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+            roofline["traffic_frac_of_random_sector_peak"] = round(traffic / (k_ms * 1e-3) / 1e9 / RANDOM_SECTOR_GBS, 4)
+        if pmc and "issue" in pmc:
+            roofline["issue_bound"] = pmc["issue"]
         if wlane:
-            kernel = ("walk_lanes_kernel<WEIGHTED> (float64-bounded decision per lane) + lanes_eager_weighted_kernel (wave scan of the "
-                      "steps the bound leaves open, from recorded chain values), every round of a pass")
-            # declared format of the weighted lane form: per step the 64-byte edge line, the draw and the
-            # output cell; per search probe a list entry and two float64 table values (18 B: an upper bound, probes inside a run
-            # read one value); per parked step its 64-byte queue record out and back and the scan window of the wave scan
-            # (at most 2 x 1024 elements from the last recorded chain value: 4-byte weights + 4-byte neighbour ids); 36 B per walk
-            probes = int(acc["list_entries_read"][-1])
-            eager = int(st["eager_steps"])
-            declared = (steps0 * (64 + 8 + 4) + probes * 18 + eager * (128 + 2048 * 8) + (hi - lo) * (4 + 8) + walks0 * (16 + 8) +
-                        (hi - lo - walks0) * 8)
-            fmt = ("64 B edge line + 8 B draw + 4 B output per step, 18 B per search probe (list entry + two float64 prefix values), "
-                   "per parked step 128 B of queue record + a scan window of at most 2048 elements x 8 B; 36 B per walk")
-        fmt_ref = ("SURVEY 8(d): 8*d_cur + 4*d_prev + 28 per step" +
-               (" + 4*d_prev + 4*|N(cur)&N(prev)| + 4 (node2vec+)" if extend else "") +
-               " -- the REFERENCE's row traffic, which this kernel's rows mostly take from L2 / Infinity Cache: `frac` here is an "
-               "algorithmic-byte rate, NOT an HBM utilisation (that is traffic_frac_of_peak, from the PMC passes); the kernel is "
-               "instruction bound (issue_bound)")
-        if not wlane:
-            fmt = fmt_ref
-    achieved = declared / (k_ms * 1e-3) / 1e9
-    key = f"{key_graph}_{mode}_p{p:g}_q{q:g}{'_ext' if extend else ''}_w{W}_l{L}_seed{args.seed}"
-    pmc = load_pmc(key) if world == 1 else None
-    traffic = int(pmc["fetch_bytes"] + pmc["write_bytes"]) if pmc else None
-    wide_note = ""
-    if pmc and mode == "DenseOTF" and cfg["graph"] == "er":
-        # MI355X_MICROARCH.md (HBM): on gfx950 FETCH_SIZE reports exactly half the bytes of a wide coalesced streaming
-        # read (128-byte requests tallied at 64 B) -- the packed rows are read that way (8 B per lane, 512 B per wavefront load)
-        traffic = int(2 * pmc["fetch_bytes"] + pmc["write_bytes"])
-        wide_note = (" FETCH_SIZE doubled: wide coalesced row reads are tallied at half their bytes on gfx950 (the build image's "
-                     "/opt/skills/guides/MI355X_MICROARCH.md, HBM section); raw counter value in traffic_raw_counter_bytes.")
-    roofline = {
-        "bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-        "declared_bytes_per_launch": int(declared), "declared_format": fmt,
-        "avg_launch_ms": round(k_ms, 3), "rng_jump_and_expand_ms": round(float(np.mean(acc["rng_kernel_ms"])), 3),
-        "traffic_note": ((pmc["note"] + wide_note) if pmc else "no PMC pass committed for this workload (profiles/r06_traffic.json)"),
-        "random_sector_peak_GBps": RANDOM_SECTOR_GBS,
-        "reference_format_bytes": ref_bytes,
-    }
-    if pmc and wide_note:
-        roofline["traffic_raw_counter_bytes"] = int(pmc["fetch_bytes"] + pmc["write_bytes"])
-    if traffic:
-        roofline["traffic_GBps"] = round(traffic / (k_ms * 1e-3) / 1e9, 1)
-        roofline["traffic_frac_of_peak"] = round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        roofline["traffic_frac_of_random_sector_peak"] = round(traffic / (k_ms * 1e-3) / 1e9 / RANDOM_SECTOR_GBS, 4)
-    if pmc and "issue" in pmc:
-        roofline["issue_bound"] = pmc["issue"]
-    if wlane:
-        roofline["eager_step_frac"] = round(st["eager_steps"] / max(steps0, 1), 5)
-        roofline["lane_rounds"] = int(st["lane_rounds"])
-    if lane:
-        roofline["ambiguous_step_frac"] = round(acc["ambiguous_steps"][-1] / max(steps0, 1), 5)
-        roofline["float_chain_step_frac"] = round(acc["wave_chain_steps"][-1] / max(steps0, 1), 5)
-        roofline["list_entries_per_step"] = round(acc["list_entries_read"][-1] / max(steps0, 1), 2)
-        roofline["redo_walks"] = int(acc["redo_walks"][-1])
-        roofline["lane_rounds"] = int(st["lane_rounds"])
-        # the safety net under the argued bounds of the interval decision: 1/1024 of the steps it settles are
-        # re-decided by the float chain inside every call -- summed over the timed passes
-        roofline["verify_sampled_decisions"] = int(sum(acc["verify_checked"][-args.steps:]))
-        roofline["verify_mismatches"] = int(sum(acc["verify_mismatch"][-args.steps:]))
-        roofline["launch_note"] = ("one pass = lane_rounds launches of walk_lanes_kernel (walks whose step needs the float32 chain "
-                                   "are parked and resumed by the next round) + one lanes_chain_kernel launch per queue; "
-                                   "avg_launch_ms and declared_bytes_per_launch are per PASS (sum over these launches)")
+            roofline["eager_step_frac"] = round(st["eager_steps"] / max(steps0, 1), 5)
+            roofline["lane_rounds"] = int(st["lane_rounds"])
+        if lane:
+            roofline["ambiguous_step_frac"] = round(acc["ambiguous_steps"][-1] / max(steps0, 1), 5)
+            roofline["float_chain_step_frac"] = round(acc["wave_chain_steps"][-1] / max(steps0, 1), 5)
+            roofline["list_entries_per_step"] = round(acc["list_entries_read"][-1] / max(steps0, 1), 2)
+            roofline["redo_walks"] = int(acc["redo_walks"][-1])
+            roofline["lane_rounds"] = int(st["lane_rounds"])
+            # the safety net under the argued bounds of the interval decision: 1/1024 of the steps it settles are
+            # re-decided by the float chain inside every call -- summed over the timed passes
+            roofline["verify_sampled_decisions"] = int(sum(acc["verify_checked"][-args.steps:]))
+            roofline["verify_mismatches"] = int(sum(acc["verify_mismatch"][-args.steps:]))
+            roofline["launch_note"] = ("one pass = lane_rounds launches of walk_lanes_kernel (walks whose step needs the float32 chain "
+                                       "are parked and resumed by the next round) + one lanes_chain_kernel launch per queue; "
+                                       "avg_launch_ms and declared_bytes_per_launch are per PASS (sum over these launches)")
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and cfg["graph"] == "rmat" and not extend:
+    if args.full and not args.no_cpu_baseline and world == 1 and cfg["graph"] == "rmat" and not extend:
         from oracle import pyoracle as orc
 
         # thread count: the box may expose more logical CPUs than the container can run on (affinity mask,
@@ -579,7 +610,7 @@ def main():
     # ---- the call Base.simulate_walks actually makes: host pointers in, the walk matrix out into pageable NumPy memory ----
     # (pw_simulate: parts walked while the finished ones leave over PCIe through a ring of pinned buffers; never `value`)
     host_call = None
-    if world == 1 and not args.no_host_call and cfg["graph"] == "rmat":
+    if args.full and world == 1 and not args.no_host_call and cfg["graph"] == "rmat":
         try:
             eng.simulate(mode, p, q, extend, starts[: max(1, n_jobs // 64)], L, seed=args.seed + 1000)   # (staging buffers exist)
             t = time.perf_counter()

@@ -187,7 +187,7 @@ def test_bench_self_launches_two_ranks_and_gathers():
     env = dict(os.environ, PECANPY_BENCH_BACKEND="gloo", PECANPY_BENCH_ONE_GPU="1", PECANPY_BENCH_VERIFY="1")
     env.pop("WORLD_SIZE", None)
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scale", "16", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "gathered shards verified" in res.stderr
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -195,6 +195,26 @@ def test_bench_self_launches_two_ranks_and_gathers():
     assert rec["n_gpus"] == 2 and rec["config"]["gather_on_rank0"] is True
     assert len(rec["config"]["per_rank_walk_kernel_ms"]) == 2
     assert rec["roofline"]["frac"] <= 1.0
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run prints the headline line only, times exactly --steps passes, and --dump-outputs writes
+    the walk matrix of the last timed pass (seed + warmup + steps - 1), equal to the oracle's walks."""
+    steps, warmup, L = 2, 1, 20
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--scale", "12", "--steps", str(steps),
+                          "--warmup", str(warmup), "--walk-length", str(L), "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == steps and rec["warmup"] == warmup and rec["ms_per_step"] > 0
+    assert rec["value"] > 0 and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["config"]["host_call"] is None
+    got = np.load(tmp_path / "walks.npy")
+    assert got.dtype == np.float64
+    indptr, indices, data = rmat_csr(12, seed=1)
+    starts = orc.shuffled_starts(indptr.size - 1, 10, 0)
+    want = orc.walks_sparse_otf(indptr, indices, data, 0.5, 2, starts, L, warmup + steps - 1)
+    assert np.array_equal(got, want.astype(np.float64))
 
 
 def test_weighted_normaliser_table_equals_the_two_pass_step(monkeypatch):

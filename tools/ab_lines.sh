@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/ab_lines.sh <out dir under gpurun_out> -- headline A/B lines of round 6 (sampled verification on / off, self loops)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/$1; mkdir -p $OUT; cd $R
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-call"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-call"
 timeout 300 $B > $OUT/headline_sample_on.json 2> $OUT/err1.txt
 PECANPY_AMD_VERIFY_SAMPLE=0 timeout 300 $B > $OUT/headline_sample_off.json 2> $OUT/err2.txt
 timeout 400 $B --self-loops 1000 > $OUT/headline_loops1000.json 2> $OUT/err3.txt
