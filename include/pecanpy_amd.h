@@ -50,8 +50,19 @@ typedef enum {
     PW_MODE_DENSE_OTF = 1,             /* DenseOTF.move_forward,  pecanpy.py:597-612 */
     PW_MODE_PRECOMP = 2,               /* PreComp.move_forward,   pecanpy.py:409-438 */
     PW_MODE_FIRST_ORDER_UNWEIGHTED = 3,/* FirstOrderUnweighted,   pecanpy.py:299-309 */
-    PW_MODE_PRECOMP_FIRST_ORDER = 4    /* PreCompFirstOrder,      pecanpy.py:319-334 */
+    PW_MODE_PRECOMP_FIRST_ORDER = 4,   /* PreCompFirstOrder,      pecanpy.py:319-334 */
+    PW_MODE_NODE2VEC_PLUSPLUS = 5      /* experimental.Node2vecPlusPlus, experimental.py:31-102 (see below) */
 } pw_mode;
+
+/* PW_MODE_NODE2VEC_PLUSPLUS: node2vec++, the reference's continuous form of node2vec+, on dense handles.  A column x of cur's
+ * row with data[prev, x] < thr[x], x != prev, is weighted by ((t * b) / (1 + (b - 1))) * |1 - 1/q| + min(1, 1/q), with
+ * t = data[prev, x] / thr[x] (1 - t when q < 1) and b = data[cur, x] / thr[x]; prev's weight is divided by p; the first step is
+ * unbiased.  Like DenseOTF it draws one double per step (stream_skip, shards and pw_count_stream_draws apply unchanged).
+ *   - the thresholds of pw_graph_set_thresholds() are always used (extend is ignored); without them: PW_ERR_INVALID.
+ *   - PW_ERR_UNSUPPORTED for CSR handles, pw_dense_create_bits handles and matrices with negative or non-finite weights.
+ *   - legal weights can make the reference's probabilities NaN (b < 2^-54 and q > 1) or inf / NaN (q < 1); the step then
+ *     follows NumPy's searchsorted (the first k with !(cdf[k] < r)); a draw no partial sum reaches takes the last neighbour
+ *     and counts as an overflow + clamped read.  pw_stats.ambiguous_steps counts the steps the reference's loops decided. */
 
 typedef struct {
     uint64_t total_steps;     /* sampled transitions = sum_i (len_i - 1) */

@@ -50,6 +50,7 @@ MODE_IDS = {
     "PreComp": 2,
     "FirstOrderUnweighted": 3,
     "PreCompFirstOrder": 4,
+    "Node2vecPlusPlus": 5,   # experimental.Node2vecPlusPlus (dense handles)
 }
 
 # every symbol include/pecanpy_amd.h declares: (restype, argtypes)

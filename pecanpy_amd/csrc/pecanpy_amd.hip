@@ -140,6 +140,7 @@ struct pw_graph {
     uint64_t wl_thr_version = 0;
     bool wl_failed = false;
     bool wl_active = false;                             // the current call may run the weighted lane form (tables are there)
+    bool call_n2vpp = false;                            // the current call walks node2vec++ (walk_dense_w.hip.h)
     bool wl_used = false;                               // ... and did
     double tot_p = 0, tot_q = 0;                        // ... built for these parameters
     int tot_extend = -1;                                // -1: none yet
@@ -1338,6 +1339,15 @@ PW_EXPORT int pw_precomp_export(pw_graph *g, uint64_t *alias_indptr, uint32_t *a
     return PW_OK;
 }
 
+// How a mode uses the random stream.  On-the-fly modes draw one double per step: a job array splits anywhere (stream_skip,
+// shards, parts).  The alias / first-order modes consume a variable number of words per step: one sequential stream.
+static bool mode_on_the_fly(int mode) {
+    return mode == PW_MODE_SPARSE_OTF || mode == PW_MODE_DENSE_OTF || mode == PW_MODE_NODE2VEC_PLUSPLUS;
+}
+static bool mode_sequential_stream(int mode) {
+    return mode == PW_MODE_PRECOMP || mode == PW_MODE_FIRST_ORDER_UNWEIGHTED || mode == PW_MODE_PRECOMP_FIRST_ORDER;
+}
+
 // Sequential-stream modes (variable word consumption): one lane walks every job in order.
 static int simulate_sequential(pw_graph *g, int mode, double p, double q, int extend, const uint32_t *d_starts,
                                uint64_t n_jobs, uint32_t L, int has_seed, uint32_t seed, uint32_t *d_out,
@@ -1647,16 +1657,33 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, bool extend,
 
 // weighted dense graphs: the float64-bounded decision, one row stream per step (walk_dense_w.hip.h); the walks it hands
 // over (a partial sum inside the bound's interval: ~10^-11 of the steps) are walked again by the complete kernel
-static bool dense_weighted_eligible(const pw_graph *g, const pw::WalkArgs &wa, bool extend) {
-    if (g->kind != 1 || g->unit || g->bits_only || !g->dense_nonneg || !g->d_adjbits || !g->d_data) return false;
-    if (extend && !g->d_thr) return false;
-    if (wa.resume || getenv("PECANPY_AMD_DENSE_NO_WFAST")) return false;
-    // LDS of one wavefront: prev's packed row + its prefix popcounts + the block prefixes
+// LDS of one wavefront: prev's packed row + its prefix popcounts + the block prefixes
+static bool dense_weighted_lds_ok(const pw_graph *g) {
     const uint64_t lds = (uint64_t)g->words_per_row * 12u + ((uint64_t)g->max_degree / pw::DWBLK_MIN + 2u) * 8u;
     return lds <= 60u * 1024u;
 }
 
-static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, bool extend, uint64_t *redo_total) {
+static bool dense_weighted_eligible(const pw_graph *g, const pw::WalkArgs &wa, bool extend) {
+    if (g->kind != 1 || g->unit || g->bits_only || !g->dense_nonneg || !g->d_adjbits || !g->d_data) return false;
+    if (extend && !g->d_thr) return false;
+    if (wa.resume || getenv("PECANPY_AMD_DENSE_NO_WFAST")) return false;
+    return dense_weighted_lds_ok(g);
+}
+
+// node2vec++ has no other kernel: what it cannot walk is refused before the call starts (simulate_device_impl, run_probe)
+static int n2vpp_check(const pw_graph *g) {
+    if (g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs a dense graph handle");
+    if (g->bits_only) return fail(PW_ERR_UNSUPPORTED, "node2vec++: a dense graph created from packed bits has no compressed rows");
+    if (!g->dense_nonneg) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights");
+    if (!g->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
+    if (!g->d_adjbits || (!g->unit && !g->d_data)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: the handle has no dense rows");
+    if (!dense_weighted_lds_ok(g)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: prev's packed row does not fit one wavefront's LDS");
+    return PW_OK;
+}
+
+// bias: pw::DW_N2V / DW_N2VPLUS (DenseOTF) or DW_N2VPP / DW_N2VPP_UNIT (node2vec++)
+static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, int bias, uint64_t *redo_total) {
+    const bool extend = bias == pw::DW_N2VPLUS;
     uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
     if (!n_work) return 0;
     pw::DenseWArgs da;
@@ -1690,7 +1717,10 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, bool exten
     da.lds_blocks = g->max_degree / pw::DWBLK_MIN + 2u;
     const size_t lds = (size_t)da.wpr * 8u + (size_t)da.lds_blocks * 8u + (size_t)da.wpr * 4u;
     typedef void (*dw_fn)(pw::DenseWArgs);
-    dw_fn fn = extend ? pw::walk_dense_weighted_kernel<true> : pw::walk_dense_weighted_kernel<false>;
+    dw_fn fn = bias == pw::DW_N2VPLUS ? pw::walk_dense_weighted_kernel<pw::DW_N2VPLUS>
+               : bias == pw::DW_N2VPP ? pw::walk_dense_weighted_kernel<pw::DW_N2VPP>
+               : bias == pw::DW_N2VPP_UNIT ? pw::walk_dense_weighted_kernel<pw::DW_N2VPP_UNIT>
+               : pw::walk_dense_weighted_kernel<pw::DW_N2V>;
     int occ = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, pw::WAVE, lds));
     if (occ < 1) occ = 1;
@@ -1705,6 +1735,8 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, bool exten
     HIP_TRY(hipMemcpyAsync(&nr, g->counters.p + 6, sizeof(nr), hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     if (!nr) return 0;
+    if (bias == pw::DW_N2VPP || bias == pw::DW_N2VPP_UNIT)   // (the kernel decides every node2vec++ step itself)
+        return fail(PW_ERR_HIP, "node2vec++: the walk kernel handed over " + std::to_string(nr) + " walks");
     if (redo_total) *redo_total += nr;
     pw::WalkArgs wr = wa;
     wr.job_list = g->redo.p;
@@ -1727,9 +1759,10 @@ static int launch_wave_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_
     // unweighted dense graphs: the column-space kernels at every size (round 6: with prev's row in LDS and DPP sums the packed rows
     // beat the compressed ones from N = 1 000 on -- ER-1k 364 -> 682, ER-8k 207 -> 1 135, ER-12k 158 -> 1 145 M steps/s; rounds 2-5
     // sent matrices of up to 12 000 rows through their compressed rows; PECANPY_AMD_DENSE_SMALL_ROWS=1: that rule)
+    if (g->call_n2vpp) return launch_dense_weighted(g, wa, g->unit ? pw::DW_N2VPP_UNIT : pw::DW_N2VPP, redo_total);
     const bool small_rows = env_on("PECANPY_AMD_DENSE_SMALL_ROWS");
     if (g->kind == 1 && g->unit && g->d_deg && (g->bits_only || g->n_nodes > 12000 || !small_rows)) return launch_dense_bits(g, wa, redo_total);
-    if (dense_weighted_eligible(g, wa, extend)) return launch_dense_weighted(g, wa, extend, redo_total);
+    if (dense_weighted_eligible(g, wa, extend)) return launch_dense_weighted(g, wa, extend ? pw::DW_N2VPLUS : pw::DW_N2V, redo_total);
     int occ = 0;
     walk_kernel_fn fn = pick_kernel(g, extend);
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
@@ -2457,9 +2490,11 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
                                 int has_seed, uint32_t seed, uint64_t stream_skip, uint32_t *d_out,
                                 pw_stats *stats) {
     if (!g || (n_jobs && (!d_starts || !d_out))) return fail(PW_ERR_INVALID, "null pointer");
-    if (mode < PW_MODE_SPARSE_OTF || mode > PW_MODE_PRECOMP_FIRST_ORDER) return fail(PW_ERR_INVALID, "unknown mode");
+    if (!mode_on_the_fly(mode) && !mode_sequential_stream(mode)) return fail(PW_ERR_INVALID, "unknown mode");
     if (mode == PW_MODE_SPARSE_OTF && g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
     if (mode == PW_MODE_DENSE_OTF && g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
+    const bool n2vpp = mode == PW_MODE_NODE2VEC_PLUSPLUS;
+    if (n2vpp) { int rcn = n2vpp_check(g); if (rcn) return rcn; extend = 0; }   // (node2vec++ ignores extend)
     if (extend && !g->unit && !g->d_thr)
         return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
@@ -2472,7 +2507,8 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
     if (!has_seed) seed = os_seed();
     if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
     { int rcs = check_starts(g, d_starts, n_jobs); if (rcs) return rcs; }
-    if (mode >= PW_MODE_PRECOMP) {
+    g->call_n2vpp = n2vpp;
+    if (mode_sequential_stream(mode)) {
         if (stream_skip) return fail(PW_ERR_UNSUPPORTED, "alias / first-order modes consume a variable number of "
                                                          "words per step: the stream cannot be sharded");
         int rcs = simulate_sequential(g, mode, p, q, extend, d_starts, n_jobs, walk_length, has_seed, seed, d_out, &st);
@@ -2987,9 +3023,9 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
     int n_parts = 1;
     // (the first part's walks are the only ones the copy does not hide: more parts while a part stays a launch worth making --
     //  RMAT-18, 0.86 GB: 4 / 8 / 16 parts -> 22.7 / 21.5 / 29.0 ms per call)
-    if (mode < PW_MODE_PRECOMP && (size_t)n_jobs * row_bytes >= ((size_t)128 << 20) && !getenv("PECANPY_AMD_NO_PARTS"))
+    if (mode_on_the_fly(mode) && (size_t)n_jobs * row_bytes >= ((size_t)128 << 20) && !getenv("PECANPY_AMD_NO_PARTS"))
         n_parts = (size_t)n_jobs * row_bytes >= ((size_t)800 << 20) ? 8 : 4;
-    if (const char *pe = getenv("PECANPY_AMD_PARTS")) { n_parts = atoi(pe); if (n_parts < 1 || mode >= PW_MODE_PRECOMP) n_parts = 1; }
+    if (const char *pe = getenv("PECANPY_AMD_PARTS")) { n_parts = atoi(pe); if (n_parts < 1 || mode_sequential_stream(mode)) n_parts = 1; }
     // (nominal addressing -- the opt-in fallback of the dead-end repair -- must be decided ONCE for the whole array: a part that
     //  fell back would own slots up to skip + nominal while the next part started at skip + actual; exact addressing, the
     //  default, makes the walks those of one call whatever the split)
@@ -3126,7 +3162,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
     if (!has_seed) { seed = os_seed(); has_seed = 1; }   // (every shard walks the same stream)
     const size_t W = (size_t)walk_length + 2;
     int n_sh = n_handles;
-    if (mode >= PW_MODE_PRECOMP || n_jobs < (uint64_t)n_handles * 64) n_sh = 1;   // (alias modes: a sequential stream; tiny arrays: one device)
+    if (mode_sequential_stream(mode) || n_jobs < (uint64_t)n_handles * 64) n_sh = 1;   // (alias modes: a sequential stream; tiny arrays: one device)
     if (n_sh == 1 && !out_on_device) return pw_simulate(handles[0], mode, p, q, extend, starts, n_jobs, walk_length, has_seed, seed, stream_skip, out, stats);
     struct Shard {
         uint64_t lo = 0, hi = 0, skip = 0, nominal = 0;
@@ -3155,7 +3191,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
         Shard &S = sh[i];
         pw_graph *g = handles[i];
         if (S.hi == S.lo) return;
-        if (mode >= PW_MODE_PRECOMP) return;
+        if (mode_sequential_stream(mode)) return;
         S.rc = pw_count_stream_draws(g, starts + S.lo, S.hi - S.lo, walk_length, &S.nominal);
         if (S.rc) S.err = g_err;
     }, 0);
@@ -3196,7 +3232,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
             uint64_t a = 0, acc = 0, skip_c = S.skip;
             pw_stats tot;
             memset(&tot, 0, sizeof(tot));
-            if (n_ch > 1 && mode < PW_MODE_PRECOMP) {   // one jump-ahead tree for the shard, not one per chunk
+            if (n_ch > 1 && mode_on_the_fly(mode)) {   // one jump-ahead tree for the shard, not one per chunk
                 S.rc = pw_stream_hold(g, seed, S.skip, S.nominal);
                 if (S.rc) { S.err = g_err; return; }
             }
@@ -3290,15 +3326,67 @@ PW_EXPORT int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, do
 // ---- single-step probe (Base.get_move_forward of the drop-in API; probability vectors for the parity tests) --------
 typedef void (*probe_kernel_fn)(pw::WalkArgs, const pw::ProbeArgs *);
 
+// node2vec++: the walk kernel's value() and two loops on one wavefront (walk_dense_w.hip.h, dense_w_probe_kernel)
+static int run_probe_n2vpp(pw_graph *g, double p, double q, uint32_t cur, int has_prev, uint32_t prev, double r,
+                           void *probs_host, uint32_t *out_host) {
+    if (set_device(g)) return PW_ERR_HIP;
+    pw::ProbeArgs *d_pa = nullptr;
+    uint32_t *d_out = nullptr;
+    double *d_probs = nullptr;
+    auto cleanup = [&]() {
+        if (d_pa) (void)hipFree(d_pa);
+        if (d_out) (void)hipFree(d_out);
+        if (d_probs) (void)hipFree(d_probs);
+    };
+    hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
+    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->max_degree + 1));
+    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
+    pw::ProbeArgs pa;
+    pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
+    pa.r = r; pa.probs = d_probs; pa.out = d_out;
+    pw::DenseWArgs da;
+    memset(&da, 0, sizeof(da));
+    da.indptr = g->d_indptr;
+    da.indices = g->d_indices;
+    da.data = (const double *)g->d_data;
+    da.adjbits = g->d_adjbits;
+    da.thr = g->d_thr;
+    da.n = g->n_nodes;
+    da.wpr = g->words_per_row;
+    da.p = p;
+    da.q = q;
+    const size_t lds = (size_t)da.wpr * 12u;
+    typedef void (*dwp_fn)(pw::DenseWArgs, const pw::ProbeArgs *);
+    dwp_fn fn = g->unit ? pw::dense_w_probe_kernel<pw::DW_N2VPP_UNIT> : pw::dense_w_probe_kernel<pw::DW_N2VPP>;
+    uint32_t zero[4] = {0, 0, 0, 0};
+    e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), lds, g->stream, da, (const pw::ProbeArgs *)d_pa);
+        e = hipGetLastError();
+    }
+    uint32_t out[4] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    if (e == hipSuccess && probs_host && out[2]) e = hipMemcpy(probs_host, d_probs, sizeof(double) * out[2], hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("node2vec++ single-step probe: ") + hipGetErrorString(e));
+    out_host[0] = out[0]; out_host[1] = out[1]; out_host[2] = out[2];
+    return PW_OK;
+}
+
 static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint32_t cur, int has_prev, uint32_t prev, double r,
                      void *probs_host, uint32_t *out_host) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
     if (mode == PW_MODE_SPARSE_OTF && g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
     if (mode == PW_MODE_DENSE_OTF && g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
-    if (mode != PW_MODE_SPARSE_OTF && mode != PW_MODE_DENSE_OTF) return fail(PW_ERR_UNSUPPORTED, "single steps are provided for the on-the-fly modes");
+    if (!mode_on_the_fly(mode)) return fail(PW_ERR_UNSUPPORTED, "single steps are provided for the on-the-fly modes");
+    if (mode == PW_MODE_NODE2VEC_PLUSPLUS) { int rcn = n2vpp_check(g); if (rcn) return rcn; }
     if (g->bits_only) return fail(PW_ERR_UNSUPPORTED, "dense graph created from packed bits has no compressed rows");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
     if (cur >= g->n_nodes || (has_prev && prev >= g->n_nodes)) return fail(PW_ERR_INVALID, "vertex out of range");
+    if (mode == PW_MODE_NODE2VEC_PLUSPLUS) return run_probe_n2vpp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
     if (extend && !g->unit && !g->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (set_device(g)) return PW_ERR_HIP;
     const bool ext = extend && !g->unit;

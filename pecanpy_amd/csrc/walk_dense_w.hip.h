@@ -31,7 +31,19 @@
 //     non-finite values and the read past the row still go to the redo list.
 //   * the block that holds k1 (256 elements, 3 KB) is read a second time and scanned; nothing else is read twice.
 //
-// Declared bytes per step: 12 d(cur) + N / 8 (+ 8 d(prev) for node2vec+) + 8 (draw) + 4 (output).
+// node2vec++ (PW_MODE_NODE2VEC_PLUSPLUS; the reference's experimental.py:31-102) is a third bias form of the same step: for a
+// column x of cur's row with data[prev, x] < thr[x], x != prev,
+//   t = data[prev, x] / thr[x]   (t = 1 - t when q < 1),   b = w / thr[x],   w *= ((t * b) / (1 + (b - 1))) * scale + offset,
+// scale = |1 - 1/q|, offset = min(1, 1/q); / p for prev.  It reads what node2vec+ reads (prev's packed row, its prefix popcounts,
+// data[prev, x] gathered by rank); DW_N2VPP_UNIT is its form for unit-weight handles, which keep no values (every weight 1.0).
+// Every finite value is again >= 0 (t in [0, 1), b > 0, the quotient >= 0 or non-finite, offset > 0), so the bound E and the
+// block-prefix decision hold as stated above.  What is new: legal weights reach NON-FINITE values (b < 2^-54 makes 1 + (b - 1)
+// zero: 0/0 = NaN for q > 1, +inf for q < 1), and the reference then samples from NaN probabilities.  Such steps never go to
+// the redo list (walk_kernel knows no node2vec++): the reference's two loops decide them in place with NumPy's NaN-last
+// searchsorted rule -- the first k with !(c_k < r) --, and a draw no partial sum reaches is clamped to the last neighbour and
+// counted as an overflow + clamped read, as the complete kernel does for DenseOTF.
+//
+// Declared bytes per step: 12 d(cur) + N / 8 (+ 8 d(prev) for node2vec+ / node2vec++) + 8 (draw) + 4 (output).
 #pragma once
 #include "walk_sparse.hip.h"
 
@@ -41,16 +53,26 @@ namespace pw {
 #define PW_DWB 4       // 64-element iterations per block, node2vec (HBM bound at 2 .. 8: ER-20k 149.0 / 149.5 / 151.3 ms per pass)
 #endif
 #ifndef PW_DWB_EXT
-#define PW_DWB_EXT 2   // ... node2vec+ (the gathers behind the column load make it latency bound: 70 VGPRs and seven wavefronts per
+#define PW_DWB_EXT 2   // ... node2vec+ and node2vec++ (the gathers behind the column load make it latency bound: 70 VGPRs and seven wavefronts per
 #endif                 // SIMD at 2, 84 / five at 4, 112 / four at 8: ER-20k 274 / 286 / 321 ms per pass)
 constexpr uint32_t DWBLK_MIN = WAVE;          // smallest block any instantiation uses (host: capacity of the block-prefix array)
+
+// bias kinds of the step
+enum DenseWBias : int {
+    DW_N2V = 0,          // node2vec (DenseOTF)
+    DW_N2VPLUS = 1,      // node2vec+ (DenseOTF, extend)
+    DW_N2VPP = 2,        // node2vec++ (Node2vecPlusPlus)
+    DW_N2VPP_UNIT = 3,   // node2vec++ on a unit-weight handle (no values stored: every weight is 1.0)
+};
+__host__ __device__ constexpr bool dw_gathers(int bias) { return bias == DW_N2VPLUS || bias == DW_N2VPP; }   // data[prev, x] by rank
+__host__ __device__ constexpr bool dw_pp(int bias) { return bias == DW_N2VPP || bias == DW_N2VPP_UNIT; }
 
 struct DenseWArgs {
     const uint32_t *__restrict__ indptr;
     const uint32_t *__restrict__ indices;
-    const double *__restrict__ data;
+    const double *__restrict__ data;          // (nullptr: DW_N2VPP_UNIT)
     const uint64_t *__restrict__ adjbits;     // [n][wpr]
-    const float *__restrict__ thr;            // node2vec+ thresholds (EXTEND)
+    const float *__restrict__ thr;            // thresholds (node2vec+, node2vec++)
     uint32_t n, wpr;
     double p, q;
     uint32_t L;
@@ -76,16 +98,18 @@ __device__ __forceinline__ double dw_wave_sum(double v) {
 }
 
 // The biased value of one non-zero of cur's row, statement by statement the reference's arithmetic.
-template <bool EXTEND> struct DenseWStep {
+template <int BIAS> struct DenseWStep {
+    static constexpr bool EXTEND = BIAS != DW_N2V;
     bool has_prev;
     uint32_t prev;
     const uint64_t *pb;              // LDS: prev's packed row
-    const uint32_t *pr;              // LDS: set bits before each word of it (EXTEND)
-    const double *__restrict__ pdata;   // prev's compressed weights (EXTEND)
+    const uint32_t *pr;              // LDS: set bits before each word of it (dw_gathers)
+    const double *__restrict__ pdata;   // prev's compressed weights (dw_gathers)
     const float *__restrict__ thr;
     double thr_cur;
     double p, q, inv_p, inv_q, one_minus_inv_q, alpha_noisy;
-    bool p_pow2, q_pow2;
+    double pp_scale, pp_offset;      // node2vec++: |1 - 1/q|, min(1, 1/q) (experimental.py:88-89)
+    bool p_pow2, q_pow2, q_lt_one;
 
     __device__ __forceinline__ double div_p(double w) const { return p_pow2 ? w * inv_p : w / p; }
     __device__ __forceinline__ double div_q(double w) const { return q_pow2 ? w * inv_q : w / q; }
@@ -95,10 +119,10 @@ template <bool EXTEND> struct DenseWStep {
         if (!has_prev) return w;
         const uint64_t word = pb[col >> 6];
         const bool bit = (word >> (col & 63u)) & 1ull;
-        if (!EXTEND) {
+        if constexpr (!EXTEND) {
             if (col == prev) return div_p(w);                 // dense_rw.py:64
             return bit ? w : div_q(w);                        // dense_rw.py:60-63
-        } else {
+        } else if constexpr (BIAS == DW_N2VPLUS) {
             double w_px = 0.0;                                // data[prev, col]: zero for a non-neighbour (dense_rw.py:89)
             if (bit) w_px = pdata[pr[col >> 6] + (uint32_t)__popcll(word & ((1ull << (col & 63u)) - 1ull))];
             const double thx = (double)thr[col];
@@ -110,26 +134,85 @@ template <bool EXTEND> struct DenseWStep {
                 return w * alpha;
             }
             return w;
+        } else {                                              // node2vec++
+            double w_px = 0.0;                                // data[prev, col] (experimental.py:77)
+            if (bit) {
+                if constexpr (BIAS == DW_N2VPP_UNIT) w_px = 1.0;
+                else w_px = pdata[pr[col >> 6] + (uint32_t)__popcll(word & ((1ull << (col & 63u)) - 1ull))];
+            }
+            const double thx = (double)thr[col];
+            if (col == prev) return div_p(w);                 // experimental.py:80, 94
+            if (w_px < thx && w != 0.0) {                     // out edge (experimental.py:79; NaN thresholds: never); w == 0: past the row
+                double t = w_px / thx;                        // experimental.py:82
+                if (q_lt_one) t = 1.0 - t;                    // experimental.py:86 (clip(0, 1): t is in [0, 1) already)
+                const double b = w / thx;                     // experimental.py:87
+                const double alpha = t * b / (1.0 + (b - 1.0)) * pp_scale + pp_offset;   // experimental.py:90, in its order
+                return w * alpha;                             // experimental.py:92
+            }
+            return w;
         }
     }
 };
 
-template <bool EXTEND>
-__global__ void __launch_bounds__(WAVE)
-walk_dense_weighted_kernel(DenseWArgs a) {
-    constexpr int DWB = EXTEND ? PW_DWB_EXT : PW_DWB;
-    constexpr uint32_t DWBLK = DWB * WAVE;        // elements per block
-    extern __shared__ uint64_t dw_lds[];
-    uint64_t *pb = dw_lds;                               // [wpr]
-    double *P = (double *)(pb + a.wpr);                  // [lds_blocks]
-    uint32_t *pr = (uint32_t *)(P + a.lds_blocks);       // [wpr] (EXTEND)
+// The reference's two loops themselves, in their order (dense_rw.py:116 + pecanpy.py:609-610; experimental.py:97-98 + 52-53):
+// tot = w.sum(), then the partial sums of w / tot one after the other until one is not below r.  Values 64 at a time in
+// parallel, the additions sequential.  DenseOTF keeps `c >= r`; node2vec++ takes NumPy's NaN-last order, !(c < r), because
+// its probabilities can be NaN.  Returns the column (NOT_FOUND: no partial sum reaches r), *pos its position in the row;
+// `probs` (one wavefront's probe) receives every normalised value.
+template <int BIAS>
+__device__ __forceinline__ uint32_t dw_two_loops(const DenseWStep<BIAS> &sv, const uint32_t *__restrict__ cols,
+                                                 const double *__restrict__ wts, uint32_t d, double r, uint32_t *pos,
+                                                 double *probs) {
     const int lane = lane_id();
-    const uint32_t L = a.L, n = a.n, wpr = a.wpr;
-    const uint64_t W = (uint64_t)L + 2;
-    const uint64_t n_work = a.job_list ? a.n_list : a.n_jobs;
-    unsigned long long st_steps = 0, st_dead = 0, st_exact = 0;
+    auto wt = [&](uint32_t k) -> double {
+        if constexpr (BIAS == DW_N2VPP_UNIT) return k < d ? 1.0 : 0.0;
+        else return k < d ? wts[k] : 0.0;
+    };
+    double tot = 0.0;
+    for (uint32_t k0 = 0; k0 < d; k0 += WAVE) {                       // tot = w.sum()
+        const uint32_t k = k0 + (uint32_t)lane;
+        const double e = sv.value(k < d ? cols[k] : 0u, wt(k));
+        const uint32_t m = d - k0 < (uint32_t)WAVE ? d - k0 : (uint32_t)WAVE;
+        for (uint32_t l = 0; l < m; l++) tot = tot + readlane_f64(e, (int)l);
+    }
+    uint32_t nxt = NOT_FOUND;
+    double c = 0.0;
+    for (uint32_t k0 = 0; k0 < d && (nxt == NOT_FOUND || probs); k0 += WAVE) {   // cdf = np.cumsum(w / tot); searchsorted
+        const uint32_t k = k0 + (uint32_t)lane;
+        const uint32_t col = k < d ? cols[k] : 0u;
+        const double v = sv.value(col, wt(k)) / tot;
+        if (probs && k < d) probs[k] = v;
+        const uint32_t m = d - k0 < (uint32_t)WAVE ? d - k0 : (uint32_t)WAVE;
+        for (uint32_t l = 0; l < m && nxt == NOT_FOUND; l++) {
+            c = c + readlane_f64(v, (int)l);
+            const bool hit = dw_pp(BIAS) ? !(c < r) : c >= r;
+            if (hit) { nxt = readlane_u32(col, (int)l); *pos = k0 + l; }
+        }
+    }
+    return nxt;
+}
 
-    DenseWStep<EXTEND> sv;
+// prev's packed row into LDS (and, for the gathers, the set bits before each of its words)
+template <int BIAS>
+__device__ __forceinline__ void dw_stage_prev(const uint64_t *__restrict__ prow, uint32_t wpr, uint64_t *pb, uint32_t *pr) {
+    const int lane = lane_id();
+    uint32_t carry = 0;
+    for (uint32_t w0 = 0; w0 < wpr; w0 += WAVE) {
+        const uint32_t w = w0 + (uint32_t)lane;
+        const uint64_t v = w < wpr ? prow[w] : 0ull;
+        if (w < wpr) pb[w] = v;
+        if (dw_gathers(BIAS)) {
+            const uint32_t own = (uint32_t)__popcll(v);
+            const uint32_t incl = wave_incl_scan_u32(own);
+            if (w < wpr) pr[w] = carry + incl - own;
+            carry += readlane_u32(incl, WAVE - 1);
+        }
+    }
+}
+
+// the per-launch constants of the step, computed with the reference's operations
+template <int BIAS>
+__device__ __forceinline__ void dw_setup(DenseWStep<BIAS> &sv, const DenseWArgs &a, uint64_t *pb, uint32_t *pr) {
     sv.pb = pb;
     sv.pr = pr;
     sv.thr = a.thr;
@@ -139,11 +222,38 @@ walk_dense_weighted_kernel(DenseWArgs a) {
     sv.inv_q = 1.0 / a.q;
     sv.one_minus_inv_q = 1.0 - sv.inv_q;
     sv.alpha_noisy = sv.inv_q < 1.0 ? sv.inv_q : 1.0;
+    if constexpr (dw_pp(BIAS)) {
+        const double d1 = 1.0 - sv.inv_q;
+        sv.pp_scale = d1 < 0.0 ? -d1 : d1;               // np.abs(1 - 1 / q)
+        sv.pp_offset = sv.inv_q < 1.0 ? sv.inv_q : 1.0;  // np.minimum(1, 1 / q)
+        sv.q_lt_one = a.q < 1.0;
+    }
     {
         const uint64_t qb = (uint64_t)__double_as_longlong(a.q), pbits = (uint64_t)__double_as_longlong(a.p);
         sv.q_pow2 = (qb & 0xfffffffffffffull) == 0 && a.q > 0x1p-100 && a.q < 0x1p100;
         sv.p_pow2 = (pbits & 0xfffffffffffffull) == 0 && a.p > 0x1p-100 && a.p < 0x1p100;
     }
+}
+
+template <int BIAS>
+__global__ void __launch_bounds__(WAVE)
+walk_dense_weighted_kernel(DenseWArgs a) {
+    constexpr bool EXTEND = BIAS != DW_N2V;
+    constexpr bool UNIT = BIAS == DW_N2VPP_UNIT;
+    constexpr int DWB = EXTEND ? PW_DWB_EXT : PW_DWB;
+    constexpr uint32_t DWBLK = DWB * WAVE;        // elements per block
+    extern __shared__ uint64_t dw_lds[];
+    uint64_t *pb = dw_lds;                               // [wpr]
+    double *P = (double *)(pb + a.wpr);                  // [lds_blocks]
+    uint32_t *pr = (uint32_t *)(P + a.lds_blocks);       // [wpr] (dw_gathers)
+    const int lane = lane_id();
+    const uint32_t L = a.L, n = a.n, wpr = a.wpr;
+    const uint64_t W = (uint64_t)L + 2;
+    const uint64_t n_work = a.job_list ? a.n_list : a.n_jobs;
+    unsigned long long st_steps = 0, st_dead = 0, st_exact = 0, st_clamp = 0;
+
+    DenseWStep<BIAS> sv;
+    dw_setup<BIAS>(sv, a, pb, pr);
 
     for (;;) {
         unsigned long long widx = 0;
@@ -171,7 +281,11 @@ walk_dense_weighted_kernel(DenseWArgs a) {
             const double r = readlane_f64(rbuf, (int)jr);
             const bool has_prev = j >= 2;
             const uint32_t *__restrict__ cols = a.indices + rs;
-            const double *__restrict__ wts = a.data + rs;
+            const double *__restrict__ wts = UNIT ? nullptr : a.data + rs;
+            auto wt = [&](uint32_t k) -> double {   // (unit handles keep no values: every weight is 1.0)
+                if constexpr (UNIT) return k < d ? 1.0 : 0.0;
+                else return k < d ? wts[k] : 0.0;
+            };
             const uint32_t nblk = (d + DWBLK - 1) / DWBLK;
 
             // first block's loads in flight while prev's packed row is staged
@@ -181,29 +295,15 @@ walk_dense_weighted_kernel(DenseWArgs a) {
             for (int i = 0; i < DWB; i++) {
                 const uint32_t k = (uint32_t)i * WAVE + (uint32_t)lane;
                 c_nx[i] = k < d ? cols[k] : 0u;
-                w_nx[i] = k < d ? wts[k] : 0.0;
+                w_nx[i] = wt(k);
             }
             sv.has_prev = has_prev;
             sv.prev = prev;
             if (has_prev) {
                 wave_lds_fence();   // (the previous step's readers of pb / pr / P are done)
-                const uint64_t *__restrict__ prow = a.adjbits + (uint64_t)prev * wpr;
-                uint32_t carry = 0;
-                for (uint32_t w0 = 0; w0 < wpr; w0 += WAVE) {
-                    const uint32_t w = w0 + (uint32_t)lane;
-                    const uint64_t v = w < wpr ? prow[w] : 0ull;
-                    if (w < wpr) pb[w] = v;
-                    if (EXTEND) {
-                        const uint32_t own = (uint32_t)__popcll(v);
-                        const uint32_t incl = wave_incl_scan_u32(own);
-                        if (w < wpr) pr[w] = carry + incl - own;
-                        carry += readlane_u32(incl, WAVE - 1);
-                    }
-                }
-                if (EXTEND) {
-                    sv.pdata = a.data + uni(a.indptr[prev]);
-                    sv.thr_cur = (double)uni(a.thr[cur]);
-                }
+                dw_stage_prev<BIAS>(a.adjbits + (uint64_t)prev * wpr, wpr, pb, pr);
+                if (dw_gathers(BIAS)) sv.pdata = a.data + uni(a.indptr[prev]);
+                if (BIAS == DW_N2VPLUS) sv.thr_cur = (double)uni(a.thr[cur]);
             } else {
                 wave_lds_fence();
             }
@@ -223,7 +323,7 @@ walk_dense_weighted_kernel(DenseWArgs a) {
                     for (int i = 0; i < DWB; i++) {
                         const uint32_t k = (blk + 1) * DWBLK + (uint32_t)i * WAVE + (uint32_t)lane;
                         c_nx[i] = k < d ? cols[k] : 0u;
-                        w_nx[i] = k < d ? wts[k] : 0.0;
+                        w_nx[i] = wt(k);
                     }
                 }
                 double acc = 0.0;
@@ -259,7 +359,7 @@ walk_dense_weighted_kernel(DenseWArgs a) {
                     for (int i = 0; i < DWB; i++) {
                         const uint32_t k = tb * DWBLK + (uint32_t)i * WAVE + (uint32_t)lane;
                         const uint32_t col = k < d ? cols[k] : 0u;
-                        const double w = k < d ? wts[k] : 0.0;
+                        const double w = wt(k);
                         const double sc = wave_incl_scan_f64(sv.value(col, w));
                         const double S = base + sc;
                         const uint64_t m = ballot(k < d && S >= Tl);
@@ -275,32 +375,20 @@ walk_dense_weighted_kernel(DenseWArgs a) {
                     }
                 }
             }
-            if (nxt == NOT_FOUND && ok) {
-                // ---- a partial sum inside the bound's interval: the reference's two loops themselves, in their order ----
-                // (values 64 at a time in parallel, the additions one after the other: ~40 us of one wavefront, once per ~10^8
-                //  steps; the complete kernel would walk the whole walk again: ~10 ms)
-                double tot = 0.0;
-                for (uint32_t k0 = 0; k0 < d; k0 += WAVE) {                       // tot = w.sum()  (dense_rw.py:69 / 116)
-                    const uint32_t k = k0 + (uint32_t)lane;
-                    const double e = sv.value(k < d ? cols[k] : 0u, k < d ? wts[k] : 0.0);
-                    const uint32_t m = d - k0 < (uint32_t)WAVE ? d - k0 : (uint32_t)WAVE;
-                    for (uint32_t l = 0; l < m; l++) tot = tot + readlane_f64(e, (int)l);
-                }
-                double c = 0.0;
-                for (uint32_t k0 = 0; k0 < d && nxt == NOT_FOUND; k0 += WAVE) {   // cdf = np.cumsum(w / tot); searchsorted (pecanpy.py:609-610)
-                    const uint32_t k = k0 + (uint32_t)lane;
-                    const uint32_t col = k < d ? cols[k] : 0u;
-                    const double v = sv.value(col, k < d ? wts[k] : 0.0) / tot;
-                    const uint32_t m = d - k0 < (uint32_t)WAVE ? d - k0 : (uint32_t)WAVE;
-                    for (uint32_t l = 0; l < m; l++) {
-                        c = c + readlane_f64(v, (int)l);
-                        if (c >= r) { nxt = readlane_u32(col, (int)l); break; }
-                    }
-                }
+            if (nxt == NOT_FOUND && (ok || dw_pp(BIAS))) {
+                // ---- a partial sum inside the bound's interval (node2vec++: also non-finite values): the reference's two
+                //      loops themselves, in their order (~40 us of one wavefront, once per ~10^8 steps; the complete kernel
+                //      would walk the whole walk again: ~10 ms)
+                uint32_t pos_unused = 0;
+                nxt = dw_two_loops<BIAS>(sv, cols, wts, d, r, &pos_unused, nullptr);
                 st_exact++;
             }
+            if (dw_pp(BIAS) && nxt == NOT_FOUND) {   // no partial sum reaches r: the reference reads past the row -- clamped
+                nxt = uni(cols[d - 1]);
+                st_clamp++;
+            }
             if (nxt == NOT_FOUND || nxt >= n) { redo = true; break; }   // (no partial sum reaches r: the reference reads past the row)
-            if (a.redo_every && j == 3 && job % a.redo_every == 0) { redo = true; break; }
+            if (!dw_pp(BIAS) && a.redo_every && j == 3 && job % a.redo_every == 0) { redo = true; break; }
             if (lane == 0) row[j] = nxt;
             prev = cur;
             cur = nxt;
@@ -318,6 +406,42 @@ walk_dense_weighted_kernel(DenseWArgs a) {
         if (st_steps) atomicAdd(&a.stats[0], st_steps);
         if (st_dead) atomicAdd(&a.stats[3], st_dead);
         if (st_exact) atomicAdd(&a.stats[7], st_exact);   // (pw_stats.ambiguous_steps: steps decided by the float64 chain itself)
+        if (st_clamp) { atomicAdd(&a.stats[1], st_clamp); atomicAdd(&a.stats[2], st_clamp); }   // (overflow + clamped reads)
+    }
+}
+
+// ---- one node2vec++ step of one (cur, prev) for pw_step / pw_probs: ONE wavefront, the walk kernel's value() and its two loops
+// (the probabilities are exactly the values the walk samples from).  Dynamic LDS: prev's packed row and its prefix popcounts.
+template <int BIAS>
+__global__ void __launch_bounds__(WAVE)
+dense_w_probe_kernel(DenseWArgs a, const ProbeArgs *pa) {
+    extern __shared__ uint64_t dw_lds[];
+    uint64_t *pb = dw_lds;                               // [wpr]
+    uint32_t *pr = (uint32_t *)(pb + a.wpr);             // [wpr]
+    const int lane = lane_id();
+    const uint32_t cur = uni(pa->cur), prev = uni(pa->prev);
+    const bool has_prev = uni(pa->has_prev) != 0u;
+    const uint32_t rs = uni(a.indptr[cur]), d = uni(a.indptr[cur + 1]) - rs;
+    if (lane == 0) pa->out[2] = d;
+    if (d == 0) return;
+    DenseWStep<BIAS> sv;
+    dw_setup<BIAS>(sv, a, pb, pr);
+    sv.has_prev = has_prev;
+    sv.prev = prev;
+    if (has_prev) {
+        dw_stage_prev<BIAS>(a.adjbits + (uint64_t)prev * a.wpr, a.wpr, pb, pr);
+        if (dw_gathers(BIAS)) sv.pdata = a.data + uni(a.indptr[prev]);
+        if (BIAS == DW_N2VPLUS) sv.thr_cur = (double)uni(a.thr[cur]);
+    }
+    wave_lds_fence();
+    const uint32_t *__restrict__ cols = a.indices + rs;
+    const double *__restrict__ wts = BIAS == DW_N2VPP_UNIT ? nullptr : a.data + rs;
+    uint32_t pos = d;
+    uint32_t nxt = dw_two_loops<BIAS>(sv, cols, wts, d, uni(pa->r), &pos, uni(pa->want_probs) ? (double *)pa->probs : nullptr);
+    if (nxt == NOT_FOUND) nxt = uni(cols[d - 1]);   // (clamped, as the walk kernel does)
+    if (lane == 0) {
+        pa->out[0] = pos;
+        pa->out[1] = nxt;
     }
 }
 

@@ -59,6 +59,7 @@ class Base(BaseGraph):
     """
 
     _mode = None  # name understood by the C ABI (pw_mode)
+    _always_thresholds = False  # the mode's step uses the noise thresholds whatever `extend` says (node2vec++)
 
     def __init__(self, p=1, q=1, workers=1, verbose=False, extend=False, gamma=0, random_state=None):
         super().__init__()
@@ -112,7 +113,7 @@ class Base(BaseGraph):
             self._engine = self._make_engine(self._device_index())
             self._engine_key = key
             self._thr_key = None
-        if self.extend and self._thr_key != (self.gamma,):   # gamma may change between calls
+        if (self.extend or self._always_thresholds) and self._thr_key != (self.gamma,):   # gamma may change between calls
             thr = self.get_noise_thresholds()
             self._engine.set_thresholds(thr)
             if self._multi is not None:
@@ -240,7 +241,7 @@ class Base(BaseGraph):
         eng = self._get_engine()
         seed = self._run_seed if self.random_state is None else self.random_state
         if self._dist() is not None:
-            if self._mode not in ("SparseOTF", "DenseOTF"):
+            if self._mode not in ("SparseOTF", "DenseOTF", "Node2vecPlusPlus"):
                 raise NotImplementedError(
                     f"{self._mode} draws a variable number of random words per step; its seeded "
                     "stream cannot be sharded across GPUs -- run it in a single process")
@@ -284,7 +285,7 @@ class Base(BaseGraph):
         evaluated on the GPU by the walk kernels' own step code (``pw_step``); the uniform draw comes from
         ``np.random.random()`` as in the reference.  One kernel launch per call: for API compatibility and
         inspection -- ``simulate_walks`` is the throughput path."""
-        if self._mode not in ("SparseOTF", "DenseOTF"):
+        if self._mode not in ("SparseOTF", "DenseOTF", "Node2vecPlusPlus"):
             raise NotImplementedError(f"{self._mode}: single steps are provided for the on-the-fly modes")
         eng = self._get_engine()
         mode, p, q, extend = self._mode, self.p, self.q, self.extend
@@ -440,10 +441,8 @@ class PreComp(_SparseBase):
         self.alias_dim = self.indptr[1:] - self.indptr[:-1]
 
 
-class DenseOTF(Base, DenseGraph):
-    """Dense graph, transition probabilities on the fly (reference pecanpy.py:564-614)."""
-
-    _mode = "DenseOTF"
+class _DenseBase(Base, DenseGraph):
+    """Dense-matrix-backed modes (reference ``DenseRWGraph`` mixin, rw/dense_rw.py:8-31)."""
 
     def __init__(self, *args, **kwargs):
         Base.__init__(self, *args, **kwargs)
@@ -479,3 +478,9 @@ class DenseOTF(Base, DenseGraph):
             w = self.data[i, self.nonzero[i]]
             thr[i] = w.mean() + self.gamma * w.std()
         return np.maximum(thr, 0)
+
+
+class DenseOTF(_DenseBase):
+    """Dense graph, transition probabilities on the fly (reference pecanpy.py:564-614)."""
+
+    _mode = "DenseOTF"
