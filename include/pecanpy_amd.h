@@ -51,7 +51,8 @@ typedef enum {
     PW_MODE_PRECOMP = 2,               /* PreComp.move_forward,   pecanpy.py:409-438 */
     PW_MODE_FIRST_ORDER_UNWEIGHTED = 3,/* FirstOrderUnweighted,   pecanpy.py:299-309 */
     PW_MODE_PRECOMP_FIRST_ORDER = 4,   /* PreCompFirstOrder,      pecanpy.py:319-334 */
-    PW_MODE_NODE2VEC_PLUSPLUS = 5      /* experimental.Node2vecPlusPlus, experimental.py:31-102 (see below) */
+    PW_MODE_NODE2VEC_PLUSPLUS = 5,     /* experimental.Node2vecPlusPlus, experimental.py:31-102 (see below) */
+    PW_MODE_SPARSE_NODE2VEC_PLUSPLUS = 6 /* experimental.SparseNode2vecPlusPlus: node2vec++ on CSR handles (see below) */
 } pw_mode;
 
 /* PW_MODE_NODE2VEC_PLUSPLUS: node2vec++, the reference's continuous form of node2vec+, on dense handles.  A column x of cur's
@@ -63,6 +64,12 @@ typedef enum {
  *   - legal weights can make the reference's probabilities NaN (b < 2^-54 and q > 1) or inf / NaN (q < 1); the step then
  *     follows NumPy's searchsorted (the first k with !(cdf[k] < r)); a draw no partial sum reaches takes the last neighbour
  *     and counts as an overflow + clamped read.  pw_stats.ambiguous_steps counts the steps the reference's loops decided. */
+
+/* PW_MODE_SPARSE_NODE2VEC_PLUSPLUS: node2vec++ on CSR handles.  Walks, steps and probabilities equal mode 5 on the dense
+ * float64 form of the graph (A.toarray().astype(np.float64)), bit for bit, for any number of nodes; no row length limit.
+ *   - the thresholds must be the DENSE formula's (pw_noise_thresholds_csr_f64); without any: PW_ERR_INVALID.
+ *   - PW_ERR_UNSUPPORTED for dense handles and for CSR handles with a stored weight of 0 (the dense form has no such entry).
+ *   - pw_probs writes float64[degree(cur)]; one double per step, so stream_skip, shards and pw_count_stream_draws apply. */
 
 typedef struct {
     uint64_t total_steps;     /* sampled transitions = sum_i (len_i - 1) */
@@ -215,7 +222,7 @@ int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mode, double 
  * (rw/sparse_rw.py:51-130, rw/dense_rw.py:34-118).  has_prev = 0: first step of a walk (prev ignored).
  *   pw_step : *next = sampled neighbour, *position (may be NULL) = its index in cur's row (== degree when the float
  *             CDF never reached r: the reference's overflow read, mirrored)
- *   pw_probs: probs = float32[degree(cur)] for CSR handles, float64[degree(cur)] for dense handles (room for the
+ *   pw_probs: probs = float32[degree(cur)] for CSR handles, float64[degree(cur)] for dense handles and mode 6 (room for the
  *             maximum degree of the graph), *n = degree(cur)
  * The same device code as the walk kernels' eager step; one launch per call (API compatibility and tests, not a
  * throughput path). */
@@ -282,6 +289,9 @@ int pw_stream_sample_device(pw_graph *g, uint32_t seed, uint64_t offset, uint64_
  * The result is what pw_graph_set_thresholds() expects. */
 int pw_noise_thresholds_csr(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr);
 int pw_noise_thresholds_dense(const double *data, uint32_t n_nodes, double gamma, float *thr);
+/* The dense formula over a float32 CSR (data NULL: every weight 1.0): what pw_noise_thresholds_dense gives for its float64
+ * dense form -- the row's non-zeros widened to float64 in column order.  The thresholds of PW_MODE_SPARSE_NODE2VEC_PLUSPLUS. */
+int pw_noise_thresholds_csr_f64(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr);
 /* pw_noise_thresholds_csr evaluates mean + gamma * std as NumPy >= 2 does (float32 throughout); this variant as NumPy
  * 1.x does (the reference pins numpy==1.23.2: float32 scalar * Python float -> float64, one rounding on store).  They
  * differ by an ulp when gamma * std is not exact in float32 (gamma = 0.1, ...); the Python layer picks the one that

@@ -51,6 +51,7 @@ MODE_IDS = {
     "FirstOrderUnweighted": 3,
     "PreCompFirstOrder": 4,
     "Node2vecPlusPlus": 5,   # experimental.Node2vecPlusPlus (dense handles)
+    "SparseNode2vecPlusPlus": 6,   # experimental.SparseNode2vecPlusPlus (CSR handles)
 }
 
 # every symbol include/pecanpy_amd.h declares: (restype, argtypes)
@@ -97,6 +98,7 @@ SYMBOLS = {
     "pw_noise_thresholds_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_noise_thresholds_csr_numpy1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_noise_thresholds_dense": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
+    "pw_noise_thresholds_csr_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_edgelist_read": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
     "pw_edgelist_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4),
     "pw_edgelist_export": (C.c_int, [C.c_void_p] * 7),

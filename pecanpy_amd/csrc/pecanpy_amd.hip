@@ -30,6 +30,7 @@
 #include "seqscan.h"
 #include "walk_dense.hip.h"
 #include "walk_dense_w.hip.h"
+#include "walk_sparse_pp.hip.h"
 #include "walk_seq.hip.h"
 #include "walk_sparse.hip.h"
 #include "walk_lanes.hip.h"
@@ -141,6 +142,8 @@ struct pw_graph {
     bool wl_failed = false;
     bool wl_active = false;                             // the current call may run the weighted lane form (tables are there)
     bool call_n2vpp = false;                            // the current call walks node2vec++ (walk_dense_w.hip.h)
+    bool call_spp = false;                              // ... node2vec++ on this CSR handle (walk_sparse_pp.hip.h)
+    int spp_zero = -1;                                  // CSR: some stored weight is 0.0f (-1: not checked yet)
     bool wl_used = false;                               // ... and did
     double tot_p = 0, tot_q = 0;                        // ... built for these parameters
     int tot_extend = -1;                                // -1: none yet
@@ -1342,7 +1345,8 @@ PW_EXPORT int pw_precomp_export(pw_graph *g, uint64_t *alias_indptr, uint32_t *a
 // How a mode uses the random stream.  On-the-fly modes draw one double per step: a job array splits anywhere (stream_skip,
 // shards, parts).  The alias / first-order modes consume a variable number of words per step: one sequential stream.
 static bool mode_on_the_fly(int mode) {
-    return mode == PW_MODE_SPARSE_OTF || mode == PW_MODE_DENSE_OTF || mode == PW_MODE_NODE2VEC_PLUSPLUS;
+    return mode == PW_MODE_SPARSE_OTF || mode == PW_MODE_DENSE_OTF || mode == PW_MODE_NODE2VEC_PLUSPLUS ||
+           mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
 }
 static bool mode_sequential_stream(int mode) {
     return mode == PW_MODE_PRECOMP || mode == PW_MODE_FIRST_ORDER_UNWEIGHTED || mode == PW_MODE_PRECOMP_FIRST_ORDER;
@@ -1679,6 +1683,77 @@ static int n2vpp_check(const pw_graph *g) {
     if (!g->d_adjbits || (!g->unit && !g->d_data)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: the handle has no dense rows");
     if (!dense_weighted_lds_ok(g)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: prev's packed row does not fit one wavefront's LDS");
     return PW_OK;
+}
+
+// node2vec++ on CSR handles (walk_sparse_pp.hip.h): likewise no other kernel
+static int spp_check(pw_graph *g) {
+    if (g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++ needs a CSR graph handle");
+    if (!g->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
+    if (g->nnz && (!g->d_vrec || !g->d_kf || !g->d_fbits || !g->d_slots))
+        return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++: the handle has no membership index");
+    if (g->spp_zero < 0) {   // a stored 0.0f is a neighbour here but not in the dense reference (its b = 0 gives 0 / 0)
+        g->spp_zero = 0;
+        if (!g->unit && g->d_data && g->nnz) {
+            if (set_device(g)) return PW_ERR_HIP;
+            if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
+            unsigned long long flag = 0;
+            HIP_TRY(hipMemsetAsync(g->counters.p, 0, sizeof(flag), g->stream));
+            hipLaunchKernelGGL(pw::csr_zero_weight_kernel, dim3((unsigned)(((uint64_t)g->nnz + 255) / 256)), dim3(256), 0, g->stream,
+                               (const float *)g->d_data, (uint64_t)g->nnz, g->counters.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&flag, g->counters.p, sizeof(flag), hipMemcpyDeviceToHost, g->stream));
+            HIP_TRY(hipStreamSynchronize(g->stream));
+            g->spp_zero = flag ? 1 : 0;
+        }
+    }
+    if (g->spp_zero) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights (a stored weight is 0)");
+    return PW_OK;
+}
+
+static pw::SparsePPArgs spp_args(const pw_graph *g, double p, double q) {
+    pw::SparsePPArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.vrec = g->d_vrec;
+    sa.kf = g->d_kf;
+    sa.data = g->unit ? nullptr : (const float *)g->d_data;
+    sa.fbits = g->d_fbits;
+    sa.slots = g->d_slots;
+    sa.thr = g->d_thr;
+    sa.n = g->n_nodes;
+    sa.p = p;
+    sa.q = q;
+    return sa;
+}
+
+// node2vec++ walks on a CSR handle: one wavefront per walk, every step decided in the kernel (no redo list)
+static int launch_sparse_pp(pw_graph *g, const pw::WalkArgs &wa) {
+    const uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
+    if (!n_work) return 0;
+    pw::SparsePPArgs sa = spp_args(g, wa.p, wa.q);
+    sa.L = wa.L;
+    sa.n_jobs = wa.n_jobs;
+    sa.starts = wa.starts;
+    sa.stream_off = wa.stream_off;
+    sa.job_list = wa.job_list;
+    sa.n_list = wa.n_list;
+    sa.rng = wa.rng;
+    sa.rng_base = wa.rng_base;
+    sa.out = wa.out;
+    sa.job_counter = wa.job_counter;
+    sa.stats = wa.stats;
+    const char *xt = getenv("PECANPY_AMD_DENSE_EXACT_TEST");  // tests: steps with (job + step) % k == 0 are decided by the in-kernel chain
+    sa.exact_every = xt ? (uint32_t)strtoul(xt, nullptr, 10) : 0u;
+    typedef void (*spp_fn)(pw::SparsePPArgs);
+    spp_fn fn = g->unit ? pw::walk_sparse_pp_kernel<true> : pw::walk_sparse_pp_kernel<false>;
+    int occ = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, pw::WAVE, 0));
+    if (occ < 1) occ = 1;
+    uint64_t grid = (uint64_t)g->n_cu * (uint64_t)occ;
+    if (grid > n_work) grid = n_work;
+    HIP_TRY(hipMemsetAsync(g->counters.p, 0, sizeof(unsigned long long), g->stream));
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(pw::WAVE), 0, g->stream, sa);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // bias: pw::DW_N2V / DW_N2VPLUS (DenseOTF) or DW_N2VPP / DW_N2VPP_UNIT (node2vec++)
@@ -2303,6 +2378,7 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_re
 }
 
 static int launch_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_t *redo_total) {
+    if (g->call_spp) return launch_sparse_pp(g, wa);   // (node2vec++ on CSR: never the lane kernels)
     const bool floats = lanes_float_eligible(g, wa);
     // weighted lane form: whole job arrays only (repair passes of a directed graph run on job lists: the wave kernel), and
     // only when the rounds have a queue -- the in-place form can do nothing with a step it cannot decide (first steps
@@ -2495,6 +2571,8 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
     if (mode == PW_MODE_DENSE_OTF && g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
     const bool n2vpp = mode == PW_MODE_NODE2VEC_PLUSPLUS;
     if (n2vpp) { int rcn = n2vpp_check(g); if (rcn) return rcn; extend = 0; }   // (node2vec++ ignores extend)
+    const bool spp = mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
+    if (spp) { int rcn = spp_check(g); if (rcn) return rcn; extend = 0; }
     if (extend && !g->unit && !g->d_thr)
         return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
@@ -2508,6 +2586,7 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
     if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
     { int rcs = check_starts(g, d_starts, n_jobs); if (rcs) return rcs; }
     g->call_n2vpp = n2vpp;
+    g->call_spp = spp;
     if (mode_sequential_stream(mode)) {
         if (stream_skip) return fail(PW_ERR_UNSUPPORTED, "alias / first-order modes consume a variable number of "
                                                          "words per step: the stream cannot be sharded");
@@ -2571,7 +2650,7 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
         wa.lazy_ok = (pow2_ok(wa.w_out) && pow2_ok(wa.w_prev)) ? 1u : 0u;
     }
     g->param_ms_call = 0;
-    rc = ensure_tot_table(g, wa, extend != 0);   // (before the timed walk region: a per-(p, q) index, reported apart)
+    if (!spp) rc = ensure_tot_table(g, wa, extend != 0);   // (before the timed walk region: a per-(p, q) index, reported apart)
     if (rc) return rc;
     if (mode == PW_MODE_SPARSE_OTF && lanes_float_eligible(g, wa)) { rc = ensure_unit_tot(g, wa); if (rc) return rc; }
     g->wl_active = false;
@@ -2587,7 +2666,7 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
     }
     if (g->on_tables_ready) { auto cb = g->on_tables_ready; g->on_tables_ready = nullptr; cb(); }
     uint64_t redo_total = 0;
-    const bool lanes = lanes_eligible(g, wa) || lanes_float_eligible(g, wa);
+    const bool lanes = !spp && (lanes_eligible(g, wa) || lanes_float_eligible(g, wa));
     g->lane_ms = 0;
     g->lane_rounds = 0;
     g->ver_checked = g->ver_mismatch = g->ver_dropped = g->ver_ties = 0;
@@ -3376,6 +3455,45 @@ static int run_probe_n2vpp(pw_graph *g, double p, double q, uint32_t cur, int ha
     return PW_OK;
 }
 
+// node2vec++ on CSR: the walk kernel's value() and two loops on one wavefront (walk_sparse_pp.hip.h, sparse_pp_probe_kernel)
+static int run_probe_spp(pw_graph *g, double p, double q, uint32_t cur, int has_prev, uint32_t prev, double r,
+                         void *probs_host, uint32_t *out_host) {
+    if (set_device(g)) return PW_ERR_HIP;
+    pw::ProbeArgs *d_pa = nullptr;
+    uint32_t *d_out = nullptr;
+    double *d_probs = nullptr;
+    auto cleanup = [&]() {
+        if (d_pa) (void)hipFree(d_pa);
+        if (d_out) (void)hipFree(d_out);
+        if (d_probs) (void)hipFree(d_probs);
+    };
+    hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
+    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->max_degree + 1));
+    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
+    pw::ProbeArgs pa;
+    pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
+    pa.r = r; pa.probs = d_probs; pa.out = d_out;
+    const pw::SparsePPArgs sa = spp_args(g, p, q);
+    typedef void (*spp_probe_fn)(pw::SparsePPArgs, const pw::ProbeArgs *);
+    spp_probe_fn fn = g->unit ? pw::sparse_pp_probe_kernel<true> : pw::sparse_pp_probe_kernel<false>;
+    uint32_t zero[4] = {0, 0, 0, 0};
+    e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), 0, g->stream, sa, (const pw::ProbeArgs *)d_pa);
+        e = hipGetLastError();
+    }
+    uint32_t out[4] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    if (e == hipSuccess && probs_host && out[2]) e = hipMemcpy(probs_host, d_probs, sizeof(double) * out[2], hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("node2vec++ single-step probe: ") + hipGetErrorString(e));
+    out_host[0] = out[0]; out_host[1] = out[1]; out_host[2] = out[2];
+    return PW_OK;
+}
+
 static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint32_t cur, int has_prev, uint32_t prev, double r,
                      void *probs_host, uint32_t *out_host) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
@@ -3383,10 +3501,12 @@ static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint
     if (mode == PW_MODE_DENSE_OTF && g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
     if (!mode_on_the_fly(mode)) return fail(PW_ERR_UNSUPPORTED, "single steps are provided for the on-the-fly modes");
     if (mode == PW_MODE_NODE2VEC_PLUSPLUS) { int rcn = n2vpp_check(g); if (rcn) return rcn; }
+    if (mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS) { int rcn = spp_check(g); if (rcn) return rcn; }
     if (g->bits_only) return fail(PW_ERR_UNSUPPORTED, "dense graph created from packed bits has no compressed rows");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
     if (cur >= g->n_nodes || (has_prev && prev >= g->n_nodes)) return fail(PW_ERR_INVALID, "vertex out of range");
     if (mode == PW_MODE_NODE2VEC_PLUSPLUS) return run_probe_n2vpp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
+    if (mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS) return run_probe_spp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
     if (extend && !g->unit && !g->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (set_device(g)) return PW_ERR_HIP;
     const bool ext = extend && !g->unit;
@@ -4055,6 +4175,12 @@ PW_EXPORT int pw_noise_thresholds_csr(const uint32_t *indptr, const float *data,
 PW_EXPORT int pw_noise_thresholds_csr_numpy1(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr) {
     if (!indptr || !thr || (!data && indptr[n_nodes] != 0)) return fail(PW_ERR_INVALID, "null pointer");
     pw::noise_thresholds_csr(indptr, data, n_nodes, gamma, thr, true);
+    return PW_OK;
+}
+
+PW_EXPORT int pw_noise_thresholds_csr_f64(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr) {
+    if (!indptr || !thr) return fail(PW_ERR_INVALID, "null pointer");
+    pw::noise_thresholds_csr_f64(indptr, data, n_nodes, gamma, thr);
     return PW_OK;
 }
 

@@ -91,4 +91,22 @@ inline void noise_thresholds_dense(const double *mat, uint32_t n, double gamma, 
     }
 }
 
+// CSR rows of float32 weights (nullptr: every weight 1.0) under the DENSE formula: what noise_thresholds_dense gives for
+// A.toarray().astype(np.float64) -- the row's non-zeros widened to float64 in column order (= CSR order), float64 arithmetic,
+// stored as float32; NaN for a row without non-zeros (node2vec++ on CSR handles, PW_MODE_SPARSE_NODE2VEC_PLUSPLUS)
+inline void noise_thresholds_csr_f64(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr) {
+    std::vector<double> row, scratch;
+    for (uint32_t i = 0; i < n_nodes; i++) {
+        row.clear();
+        for (uint32_t e = indptr[i]; e < indptr[i + 1]; e++) {
+            const double w = data ? (double)data[e] : 1.0;
+            if (w != 0.0) row.push_back(w);
+        }
+        double m, s;
+        numpy_mean_std<double>(row.data(), row.size(), scratch, m, s);
+        const float t = (float)(m + gamma * s);
+        thr[i] = (t != t) ? t : (t > 0.0f ? t : 0.0f);
+    }
+}
+
 }  // namespace pw

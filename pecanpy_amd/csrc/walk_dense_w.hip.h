@@ -142,36 +142,38 @@ template <int BIAS> struct DenseWStep {
             }
             const double thx = (double)thr[col];
             if (col == prev) return div_p(w);                 // experimental.py:80, 94
-            if (w_px < thx && w != 0.0) {                     // out edge (experimental.py:79; NaN thresholds: never); w == 0: past the row
-                double t = w_px / thx;                        // experimental.py:82
-                if (q_lt_one) t = 1.0 - t;                    // experimental.py:86 (clip(0, 1): t is in [0, 1) already)
-                const double b = w / thx;                     // experimental.py:87
-                const double alpha = t * b / (1.0 + (b - 1.0)) * pp_scale + pp_offset;   // experimental.py:90, in its order
-                return w * alpha;                             // experimental.py:92
-            }
-            return w;
+            return pp_value(w, w_px, thx);
         }
+    }
+
+    // node2vec++ value of a column x != prev of cur's row: w = data[cur, x], w_px = data[prev, x] (zero for a non-neighbour of
+    // prev), thx = thr[x].  Shared with the sparse form (walk_sparse_pp.hip.h).
+    __device__ __forceinline__ double pp_value(double w, double w_px, double thx) const {
+        if (w_px < thx && w != 0.0) {                         // out edge (experimental.py:79; NaN thresholds: never); w == 0: past the row
+            double t = w_px / thx;                            // experimental.py:82
+            if (q_lt_one) t = 1.0 - t;                        // experimental.py:86 (clip(0, 1): t is in [0, 1) already)
+            const double b = w / thx;                         // experimental.py:87
+            const double alpha = t * b / (1.0 + (b - 1.0)) * pp_scale + pp_offset;   // experimental.py:90, in its order
+            return w * alpha;                                 // experimental.py:92
+        }
+        return w;
     }
 };
 
 // The reference's two loops themselves, in their order (dense_rw.py:116 + pecanpy.py:609-610; experimental.py:97-98 + 52-53):
 // tot = w.sum(), then the partial sums of w / tot one after the other until one is not below r.  Values 64 at a time in
-// parallel, the additions sequential.  DenseOTF keeps `c >= r`; node2vec++ takes NumPy's NaN-last order, !(c < r), because
-// its probabilities can be NaN.  Returns the column (NOT_FOUND: no partial sum reaches r), *pos its position in the row;
-// `probs` (one wavefront's probe) receives every normalised value.
-template <int BIAS>
-__device__ __forceinline__ uint32_t dw_two_loops(const DenseWStep<BIAS> &sv, const uint32_t *__restrict__ cols,
-                                                 const double *__restrict__ wts, uint32_t d, double r, uint32_t *pos,
-                                                 double *probs) {
+// parallel, the additions sequential.  DenseOTF keeps `c >= r`; node2vec++ (NAN_LAST) takes NumPy's NaN-last order, !(c < r),
+// because its probabilities can be NaN.  `at(k, col)` returns the biased value of element k of the row (0.0 for k >= d) and
+// sets col to its column.  Returns the column (NOT_FOUND: no partial sum reaches r), *pos its position in the row; `probs`
+// (one wavefront's probe) receives every normalised value.
+template <bool NAN_LAST, class At>
+__device__ __forceinline__ uint32_t dw_chain_decide(const At &at, uint32_t d, double r, uint32_t *pos, double *probs) {
     const int lane = lane_id();
-    auto wt = [&](uint32_t k) -> double {
-        if constexpr (BIAS == DW_N2VPP_UNIT) return k < d ? 1.0 : 0.0;
-        else return k < d ? wts[k] : 0.0;
-    };
     double tot = 0.0;
     for (uint32_t k0 = 0; k0 < d; k0 += WAVE) {                       // tot = w.sum()
         const uint32_t k = k0 + (uint32_t)lane;
-        const double e = sv.value(k < d ? cols[k] : 0u, wt(k));
+        uint32_t col;
+        const double e = at(k, col);
         const uint32_t m = d - k0 < (uint32_t)WAVE ? d - k0 : (uint32_t)WAVE;
         for (uint32_t l = 0; l < m; l++) tot = tot + readlane_f64(e, (int)l);
     }
@@ -179,17 +181,29 @@ __device__ __forceinline__ uint32_t dw_two_loops(const DenseWStep<BIAS> &sv, con
     double c = 0.0;
     for (uint32_t k0 = 0; k0 < d && (nxt == NOT_FOUND || probs); k0 += WAVE) {   // cdf = np.cumsum(w / tot); searchsorted
         const uint32_t k = k0 + (uint32_t)lane;
-        const uint32_t col = k < d ? cols[k] : 0u;
-        const double v = sv.value(col, wt(k)) / tot;
+        uint32_t col;
+        const double v = at(k, col) / tot;
         if (probs && k < d) probs[k] = v;
         const uint32_t m = d - k0 < (uint32_t)WAVE ? d - k0 : (uint32_t)WAVE;
         for (uint32_t l = 0; l < m && nxt == NOT_FOUND; l++) {
             c = c + readlane_f64(v, (int)l);
-            const bool hit = dw_pp(BIAS) ? !(c < r) : c >= r;
+            const bool hit = NAN_LAST ? !(c < r) : c >= r;
             if (hit) { nxt = readlane_u32(col, (int)l); *pos = k0 + l; }
         }
     }
     return nxt;
+}
+
+template <int BIAS>
+__device__ __forceinline__ uint32_t dw_two_loops(const DenseWStep<BIAS> &sv, const uint32_t *__restrict__ cols,
+                                                 const double *__restrict__ wts, uint32_t d, double r, uint32_t *pos,
+                                                 double *probs) {
+    auto at = [&](uint32_t k, uint32_t &col) -> double {
+        col = k < d ? cols[k] : 0u;
+        if constexpr (BIAS == DW_N2VPP_UNIT) return sv.value(col, k < d ? 1.0 : 0.0);
+        else return sv.value(col, k < d ? wts[k] : 0.0);
+    };
+    return dw_chain_decide<dw_pp(BIAS)>(at, d, r, pos, probs);
 }
 
 // prev's packed row into LDS (and, for the gathers, the set bits before each of its words)
@@ -211,8 +225,8 @@ __device__ __forceinline__ void dw_stage_prev(const uint64_t *__restrict__ prow,
 }
 
 // the per-launch constants of the step, computed with the reference's operations
-template <int BIAS>
-__device__ __forceinline__ void dw_setup(DenseWStep<BIAS> &sv, const DenseWArgs &a, uint64_t *pb, uint32_t *pr) {
+template <int BIAS, class Args>
+__device__ __forceinline__ void dw_setup(DenseWStep<BIAS> &sv, const Args &a, uint64_t *pb, uint32_t *pr) {
     sv.pb = pb;
     sv.pr = pr;
     sv.thr = a.thr;

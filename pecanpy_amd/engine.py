@@ -201,8 +201,8 @@ class WalkEngine:
 
     def probs(self, mode, p, q, extend, cur, prev=None):
         """``get_normalized_probs(cur, prev)`` computed by the walk kernels' own step code: float32 (CSR) or
-        float64 (dense) vector over ``cur``'s neighbours."""
-        dt = np.float32 if self.kind == "csr" else np.float64
+        float64 (dense, node2vec++) vector over ``cur``'s neighbours."""
+        dt = np.float32 if self.kind == "csr" and mode != "SparseNode2vecPlusPlus" else np.float64
         buf = np.zeros(self.max_degree() + 1, dtype=dt)
         n = C.c_uint32(0)
         _lib.check(self._lib.pw_probs(self._h, MODE_IDS[mode], float(p), float(q), int(bool(extend)), int(cur),

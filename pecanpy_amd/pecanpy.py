@@ -241,7 +241,7 @@ class Base(BaseGraph):
         eng = self._get_engine()
         seed = self._run_seed if self.random_state is None else self.random_state
         if self._dist() is not None:
-            if self._mode not in ("SparseOTF", "DenseOTF", "Node2vecPlusPlus"):
+            if self._mode not in ("SparseOTF", "DenseOTF", "Node2vecPlusPlus", "SparseNode2vecPlusPlus"):
                 raise NotImplementedError(
                     f"{self._mode} draws a variable number of random words per step; its seeded "
                     "stream cannot be sharded across GPUs -- run it in a single process")
@@ -285,7 +285,7 @@ class Base(BaseGraph):
         evaluated on the GPU by the walk kernels' own step code (``pw_step``); the uniform draw comes from
         ``np.random.random()`` as in the reference.  One kernel launch per call: for API compatibility and
         inspection -- ``simulate_walks`` is the throughput path."""
-        if self._mode not in ("SparseOTF", "DenseOTF", "Node2vecPlusPlus"):
+        if self._mode not in ("SparseOTF", "DenseOTF", "Node2vecPlusPlus", "SparseNode2vecPlusPlus"):
             raise NotImplementedError(f"{self._mode}: single steps are provided for the on-the-fly modes")
         eng = self._get_engine()
         mode, p, q, extend = self._mode, self.p, self.q, self.extend
