@@ -87,7 +87,7 @@ constexpr int MT_POLY_WORDS = 312;
 // into place.  parts == 1: the result is written directly.
 // Round 6: the taps of g are first unpacked into a LIST of sequence offsets in LDS (uint16, ascending, padded to a multiple of
 // 16 with the offset of a zeroed block behind the sequence), then every output word folds 16 taps per trip: sixteen independent
-// LDS reads in flight instead of one bit-scan + one dependent read per tap (mt_jump_v1_kernel below: ~87 cycles per tap at 2.5
+// LDS reads in flight instead of one bit-scan + one dependent read per tap (rounds 1-5: ~87 cycles per tap at 2.5
 // wavefronts per SIMD -- the LDS round trip -- i.e. ~0.36 ms per jump, 3.3 ms for the eleven tree levels of an RMAT-22 pass).
 // `parts` > 1 slices the tap LIST (16-tap granules), not the polynomial's words.
 constexpr int MT_TAP_CAP = 19968 + 16;               // >= 19937 taps rounded up to 16, + one granule read ahead
@@ -161,49 +161,6 @@ mt_jump_kernel(uint32_t *__restrict__ states, const uint64_t *__restrict__ poly,
             qa = na; qb = nb;
         }
         const uint32_t acc = acc0 ^ acc1;
-        if (parts == 1) states[(src + dst_offset) * 624 + t] = acc;
-        else if (acc) atomicXor(&tmp[(uint64_t)jump * 624 + t], acc);
-    }
-}
-
-// (the first form: one bit scan and one dependent LDS read per tap; PECANPY_AMD_MT_JUMP_V1=1, kept for same-box comparisons)
-__global__ void __launch_bounds__(640)
-mt_jump_v1_kernel(uint32_t *__restrict__ states, const uint64_t *__restrict__ poly, uint32_t src_stride,
-               uint32_t dst_offset, uint32_t parts, uint32_t *tmp) {
-    __shared__ uint32_t seq[MT_SEQ_BLOCKS * 624];
-    __shared__ uint64_t spoly[MT_POLY_WORDS];
-    const int t = threadIdx.x;
-    const uint32_t jump = blockIdx.x / parts, part = blockIdx.x % parts;
-    const uint64_t src = (uint64_t)jump * src_stride;
-    const int per = (MT_POLY_WORDS + (int)parts - 1) / (int)parts;
-    const int jw0 = (int)part * per, jw1 = jw0 + per < MT_POLY_WORDS ? jw0 + per : MT_POLY_WORDS;
-    if (t < 624) seq[t] = states[src * 624 + t];
-    if (t < MT_POLY_WORDS) spoly[t] = poly[t];
-    __syncthreads();
-    // this part reads sequence words up to index (jw1 - 1) * 64 + 63 + 623
-    int need = jw1 > jw0 ? ((jw1 - 1) * 64 + 63 + 623) / 624 + 1 : 1;
-    if (need > MT_SEQ_BLOCKS) need = MT_SEQ_BLOCKS;
-    for (int blk = 1; blk < need; blk++) {
-        uint32_t *nw = seq + blk * 624;
-        const uint32_t *od = nw - 624;
-        if (t < 227) nw[t] = mt_mix_dev(od[t], od[t + 1], od[t + 397]);
-        __syncthreads();
-        if (t >= 227 && t < 454) nw[t] = mt_mix_dev(od[t], od[t + 1], nw[t - 227]);
-        __syncthreads();
-        if (t >= 454 && t < 624) nw[t] = mt_mix_dev(od[t], (t < 623) ? od[t + 1] : nw[0], nw[t - 227]);
-        __syncthreads();
-    }
-    if (t < 624) {
-        uint32_t acc = 0;
-        for (int jw = jw0; jw < jw1; jw++) {
-            uint64_t word = spoly[jw];
-            const uint32_t *base = seq + t + jw * 64;
-            while (word) {
-                int b = __builtin_ctzll(word);
-                word &= word - 1;
-                acc ^= base[b];
-            }
-        }
         if (parts == 1) states[(src + dst_offset) * 624 + t] = acc;
         else if (acc) atomicXor(&tmp[(uint64_t)jump * 624 + t], acc);
     }

@@ -555,7 +555,7 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     uint64_t log_slots = 0;
     bool logged = false;
     const uint64_t nnz_tiles = ((uint64_t)nnz + pw::CL_TILE - 1) / pw::CL_TILE;
-    if (env_on("PECANPY_AMD_INDEX_LOGGED") && !getenv("PECANPY_AMD_INDEX_TWO_PASS") && !has_loop) {   // (self loops: the two-pass build)
+    if (env_on("PECANPY_AMD_INDEX_LOGGED") && !has_loop) {   // (self loops: the two-pass build)
         e = hipMalloc((void **)&d_logoff, sizeof(unsigned long long) * ((size_t)nnz + 1));
         if (e == hipSuccess) {
             hipLaunchKernelGGL(pw::log_tile_sums_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, g->d_indptr,
@@ -590,27 +590,15 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     }
     auto lists = [&](bool fill) {
         if (!large.empty()) {
-            // wavefronts per workgroup of the long rows' kernel (PECANPY_AMD_INDEX_THREADS = 256 / 512 / 1024 lanes): a workgroup holds
-            // 8192 row positions in LDS (33 KB: four workgroups per CU) and its wavefronts wait for the 13 dependent LDS reads of
-            // a search most of the time (SQ_WAIT_ANY 74 % of the wave cycles at 3.7 wavefronts per SIMD, profiles/r06_pmc_headline.txt)
-            // -- with 512 lanes the same LDS serves EIGHT wavefronts per SIMD instead of four (26-32 VGPRs: the registers allow
-            // it).  RMAT-22, same box: index kernels 170.6 -> 117.0 ms with 512 (the default since round 6's fourth session),
-            // 122.7 with 1024; COUNT + FILL of the long rows 130 -> ~77 ms.
-            static const int ith = getenv("PECANPY_AMD_INDEX_THREADS") ? atoi(getenv("PECANPY_AMD_INDEX_THREADS")) : 512;
+            // 512 lanes per workgroup for the long rows: a workgroup holds 8192 row positions in LDS (33 KB: four workgroups
+            // per CU) and its wavefronts wait for the 13 dependent LDS reads of a search most of the time (SQ_WAIT_ANY 74 % of
+            // the wave cycles at 3.7 wavefronts per SIMD with 256 lanes, profiles/r06_pmc_headline.txt) -- with 512 lanes the same
+            // LDS serves EIGHT wavefronts per SIMD instead of four (26-32 VGPRs: the registers allow it).  RMAT-22, same box:
+            // index kernels 170.6 -> 117.0 ms with 512 lanes, 122.7 with 1024; COUNT + FILL of the long rows 130 -> ~77 ms.
             const dim3 lg((unsigned)large.size());
-            if (ith == 512) {
-                if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, true>), lg, dim3(512), 0, g->stream, ba, d_large);
-                else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false, true>), lg, dim3(512), 0, g->stream, ba, d_large);
-                else hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false>), lg, dim3(512), 0, g->stream, ba, d_large);
-            } else if (ith == 1024) {
-                if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<1024, pw::LB_SEG, true>), lg, dim3(1024), 0, g->stream, ba, d_large);
-                else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<1024, pw::LB_SEG, false, true>), lg, dim3(1024), 0, g->stream, ba, d_large);
-                else hipLaunchKernelGGL((pw::lane_lists_kernel<1024, pw::LB_SEG, false>), lg, dim3(1024), 0, g->stream, ba, d_large);
-            } else {
-                if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<256, pw::LB_SEG, true>), lg, dim3(256), 0, g->stream, ba, d_large);
-                else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<256, pw::LB_SEG, false, true>), lg, dim3(256), 0, g->stream, ba, d_large);
-                else hipLaunchKernelGGL((pw::lane_lists_kernel<256, pw::LB_SEG, false>), lg, dim3(256), 0, g->stream, ba, d_large);
-            }
+            if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, true>), lg, dim3(512), 0, g->stream, ba, d_large);
+            else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false, true>), lg, dim3(512), 0, g->stream, ba, d_large);
+            else hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false>), lg, dim3(512), 0, g->stream, ba, d_large);
         }
         if (!small.empty()) {
             if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, true>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, d_small);
@@ -1442,33 +1430,24 @@ static int launch_dense_bits(pw_graph *g, const pw::WalkArgs &wa, uint64_t *redo
     // rows of up to 131 072 columns: the row of `cur` is kept in registers for the next step (WPL words per lane)
     typedef void (*dense_fn)(pw::DenseArgs);
     dense_fn fn = pw::walk_dense_bits_kernel<0>;
-    if (!getenv("PECANPY_AMD_DENSE_NO_KEEP")) {
-        if (da.wpr <= 64 * 8) fn = pw::walk_dense_bits_kernel<8>;
-        else if (da.wpr <= 64 * 16) fn = pw::walk_dense_bits_kernel<16>;
-        else if (da.wpr <= 64 * 25) fn = pw::walk_dense_bits_kernel<25>;
-        else if (da.wpr <= 64 * 32) fn = pw::walk_dense_bits_kernel<32>;
-    }
+    if (da.wpr <= 64 * 8) fn = pw::walk_dense_bits_kernel<8>;
+    else if (da.wpr <= 64 * 16) fn = pw::walk_dense_bits_kernel<16>;
+    else if (da.wpr <= 64 * 25) fn = pw::walk_dense_bits_kernel<25>;
+    else if (da.wpr <= 64 * 32) fn = pw::walk_dense_bits_kernel<32>;
     uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
     // dyadic 1/p, 1/q: the decisive path alone, in registers (walk_dense_fast_kernel); what it leaves (a handful of
-    // walks per 10^8 steps) is walked again by the complete kernel
+    // walks per 10^8 steps) is walked again by the complete kernel.  Rows of up to 25 words per lane keep prev's row in
+    // LDS (LDSK, round 6: three wavefronts per SIMD instead of two).  1/p or 1/q not a power of two: the same kernel with float64
+    // masses and the float64-bounded decision (round 6; before: walk_dense_bits_kernel alone: 22.7 against 467 M steps/s
+    // at ER-100k)
     typedef void (*fast_fn)(pw::DenseArgs, uint32_t *, unsigned long long *, uint32_t);
     fast_fn ff = nullptr;
     const bool dyadic = is_pow2_double(1.0 / wa.p) && is_pow2_double(1.0 / wa.q);
-    if (fn != pw::walk_dense_bits_kernel<0> && dyadic && !getenv("PECANPY_AMD_DENSE_NO_FAST")) {
-        // (round 6: prev's row in LDS instead of registers -- three wavefronts per SIMD instead of two; PECANPY_AMD_DENSE_KEEP_REGS=1:
-        //  the register form, rounds 3-5)
-        const bool ldsk = getenv("PECANPY_AMD_DENSE_KEEP_REGS") == nullptr;
-        if (da.wpr <= 64 * 8) ff = ldsk ? pw::walk_dense_fast_kernel<8, 0, true> : pw::walk_dense_fast_kernel<8, 0>;
-        else if (da.wpr <= 64 * 16) ff = ldsk ? pw::walk_dense_fast_kernel<16, 8, true> : pw::walk_dense_fast_kernel<16, 8>;
-        else if (da.wpr <= 64 * 25) ff = ldsk ? pw::walk_dense_fast_kernel<25, 16, true> : pw::walk_dense_fast_kernel<25, 16>;
-        else ff = pw::walk_dense_fast_kernel<32, 25>;
-    } else if (fn != pw::walk_dense_bits_kernel<0> && !dyadic && !getenv("PECANPY_AMD_DENSE_NO_FAST") && !getenv("PECANPY_AMD_DENSE_NO_BOUNDED")) {
-        // 1/p or 1/q not a power of two: the same kernel with float64 masses and the float64-bounded decision (round 6; before:
-        // walk_dense_bits_kernel alone: 22.7 against 467 M steps/s at ER-100k)
-        if (da.wpr <= 64 * 8) ff = pw::walk_dense_fast_kernel<8, 0, true, true>;
-        else if (da.wpr <= 64 * 16) ff = pw::walk_dense_fast_kernel<16, 8, true, true>;
-        else if (da.wpr <= 64 * 25) ff = pw::walk_dense_fast_kernel<25, 16, true, true>;
-        else ff = pw::walk_dense_fast_kernel<32, 25, false, true>;
+    if (fn != pw::walk_dense_bits_kernel<0> && !getenv("PECANPY_AMD_DENSE_NO_FAST")) {
+        if (da.wpr <= 64 * 8) ff = dyadic ? pw::walk_dense_fast_kernel<8, 0, true> : pw::walk_dense_fast_kernel<8, 0, true, true>;
+        else if (da.wpr <= 64 * 16) ff = dyadic ? pw::walk_dense_fast_kernel<16, 8, true> : pw::walk_dense_fast_kernel<16, 8, true, true>;
+        else if (da.wpr <= 64 * 25) ff = dyadic ? pw::walk_dense_fast_kernel<25, 16, true> : pw::walk_dense_fast_kernel<25, 16, true, true>;
+        else ff = dyadic ? pw::walk_dense_fast_kernel<32, 25> : pw::walk_dense_fast_kernel<32, 25, false, true>;
     }
     auto grid_for = [&](const void *f, uint64_t work, unsigned *out) -> int {
         int occ = 0;
@@ -1799,7 +1778,6 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, int bias, 
     int occ = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, pw::WAVE, lds));
     if (occ < 1) occ = 1;
-    if (const char *oe = getenv("PECANPY_AMD_DENSE_W_OCC")) { const int cap = atoi(oe); if (cap >= 1 && cap < occ) occ = cap; }
     uint64_t grid = (uint64_t)g->n_cu * (uint64_t)occ;
     if (grid > n_work) grid = n_work;
     HIP_TRY(hipMemsetAsync(g->counters.p, 0, sizeof(unsigned long long), g->stream));
@@ -1890,34 +1868,21 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     la.wl_off = g->d_wl_off;
     la.wl_dprev = g->d_wl_dprev;
     la.tot_e = wa.tot_e;
-    la.wp1 = getenv("PECANPY_AMD_NO_WFIRST") ? nullptr : g->d_wp1;
+    la.wp1 = g->d_wp1;
     la.wl_pos = wa.q >= 1.0 ? 1u : 0u;
     la.tot_v = wa.tot_v;
-    // TAILS form (round 4: the rest of the edge line staged in LDS by the lane itself; picked for graphs whose lines stay cache
-    // resident): superseded by the QUAD form, which fetches the whole line by a quad of lanes -- RMAT-20, 10.5 M jobs: 34.1 ms
-    // (TAILS) vs 32.1 (QUAD); kept behind PECANPY_AMD_LANE_TAILS=1 for A/B runs.
-    bool tails = false;
-    if (const char *te = getenv("PECANPY_AMD_LANE_TAILS")) tails = atoi(te) != 0;
-    if (getenv("PECANPY_AMD_VERIFY_TIGHT") || weighted) tails = false;
     int occ = 0;
-    if (weighted) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::walk_lanes_kernel<false, false, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
-    else if (tails) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::walk_lanes_kernel<false, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
+    if (weighted) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::walk_lanes_kernel<false, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
     else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::walk_lanes_kernel<false, false>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
     if (occ < 1) occ = 1;
     int occ_in = 0;
-    if (weighted) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_in, (const void *)pw::walk_lanes_kernel<true, false, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
-    else if (tails) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_in, (const void *)pw::walk_lanes_kernel<true, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
+    if (weighted) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_in, (const void *)pw::walk_lanes_kernel<true, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
     else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_in, (const void *)pw::walk_lanes_kernel<true, false>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
     if (occ_in < 1) occ_in = 1;
     // twin contexts (weighted halves side by side): a persistent lane kernel sized for the whole GPU would keep the other half's
     // eager kernel waiting for its workgroups to retire -- four of the six resident workgroups per CU here, six of eight for the
     // eager kernel: C5 341 -> 311 ms per pass (sweep: 3..5 x 4..12, profiles/r06_c5_twin_sweep.txt)
     if (weighted && g->twin_active) { if (occ > 4) occ = 4; if (occ_in > 4) occ_in = 4; }
-    if (const char *oe = getenv("PECANPY_AMD_LANE_OCC")) {   // (experiments: fewer resident workgroups per CU than fit)
-        const int cap = atoi(oe);
-        if (cap >= 1 && cap < occ) occ = cap;
-        if (cap >= 1 && cap < occ_in) occ_in = cap;
-    }
     const uint64_t lanes_resident = (uint64_t)g->n_cu * (uint64_t)occ * pw::WAVES_PER_BLOCK * pw::WAVE;
     // Steps that need the float32 chain (~1 % on RMAT-22 after lane_tight) are not run in place -- a chain with a few
     // of the wavefront's 64 lanes enabled costs the other lanes ~300 us -- their walks are PARKED in a queue, a
@@ -1952,7 +1917,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     // against 9.4, one in-place launch) -- so the form takes job arrays of up to 16 jobs per resident lane (rounds 5-6: 32).
     // PECANPY_AMD_LANE_CHAINS=0/1 overrides.
     int occ_c = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, (const void *)pw::walk_lanes_kernel<false, false, false, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, (const void *)pw::walk_lanes_kernel<false, false, false, false, true>, pw::WAVES_PER_BLOCK * pw::WAVE, 0));
     if (occ_c < 1) occ_c = 1;
     const uint64_t lanes_resident_c = (uint64_t)g->n_cu * (uint64_t)occ_c * pw::WAVES_PER_BLOCK * pw::WAVE;
     bool chains_form = !weighted && !getenv("PECANPY_AMD_VERIFY_TIGHT") && !tail_env && !getenv("PECANPY_AMD_NO_CHAIN_QUEUE") &&
@@ -1983,7 +1948,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     uint32_t sample_n = 1024;
     if (const char *se = getenv("PECANPY_AMD_VERIFY_SAMPLE")) sample_n = (uint32_t)strtoul(se, nullptr, 10);
     if (sample_n & (sample_n - 1)) { uint32_t pw2 = 1; while (pw2 * 2 <= sample_n) pw2 *= 2; sample_n = pw2; }
-    const bool verify_sample = !verify_full && !weighted && !tails && sample_n > 0;
+    const bool verify_sample = !verify_full && !weighted && sample_n > 0;
     const bool verify = verify_full || verify_sample;
     la.ver_poison = ((verify_full && strcmp(ver_env, "poison") == 0) || (verify_sample && getenv("PECANPY_AMD_VERIFY_SAMPLE_POISON"))) ? 1u : 0u;
     la.ver_mask = verify_full ? 0u : sample_n - 1u;
@@ -2025,7 +1990,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
         // default 16).  RMAT-22 pass, same box, same walks: the rounds behind the second, 1.43 M + 0.32 M walks, 2.96 + 2.09 ms ->
         // one round of 3.7 ms; the pass 103.4 -> 102.3 ms.  32 (the second round too: 5.2 M walks): 12.9 ms against 7.7 + 3.0 + 2.1;
         // 64 (every round behind the first): 44.6 against 36.1 (profiles/r06_late_chains.txt).
-        const bool chains_late = late_chains > 0 && round >= 1 && !weighted && !tails && use_queue && !verify_full && !tail_env &&
+        const bool chains_late = late_chains > 0 && round >= 1 && !weighted && use_queue && !verify_full && !tail_env &&
                                  g->list_max_len == 0xffffffffu && todo >= lanes_resident_c && todo <= late_chains * lanes_resident_c;
         const bool chains_now = (chains_form && round == 0) || chains_late;
         bool queue_out = chains_now || (use_queue && todo > tail && round < (weighted ? 512 : 64));
@@ -2059,15 +2024,13 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
         HIP_TRY(hipEventRecord(g->round_ev[2 * (size_t)round], g->stream));
         if (verify_full || (verify_sample && round == 0)) HIP_TRY(hipMemsetAsync(g->counters.p + 40, 0, 4 * sizeof(unsigned long long), g->stream));
         const dim3 lgrid((unsigned)grid), lblock(pw::WAVES_PER_BLOCK * pw::WAVE);
-        if (chains_now && verify) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, true, false, false, false, true>), lgrid, lblock, 0, g->stream, la);
-        else if (chains_now) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, false, false, false, false, true>), lgrid, lblock, 0, g->stream, la);
-        else if (weighted && queue_out) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, false, false, false, true>), lgrid, lblock, 0, g->stream, la);
-        else if (weighted) hipLaunchKernelGGL((pw::walk_lanes_kernel<true, false, false, false, true>), lgrid, lblock, 0, g->stream, la);
+        if (chains_now && verify) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, true, false, false, true>), lgrid, lblock, 0, g->stream, la);
+        else if (chains_now) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, false, false, false, true>), lgrid, lblock, 0, g->stream, la);
+        else if (weighted && queue_out) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, false, false, true>), lgrid, lblock, 0, g->stream, la);
+        else if (weighted) hipLaunchKernelGGL((pw::walk_lanes_kernel<true, false, false, true>), lgrid, lblock, 0, g->stream, la);
         else if (queue_out && verify) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, true>), lgrid, lblock, 0, g->stream, la);
-        else if (queue_out && tails) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, false, false, true>), lgrid, lblock, 0, g->stream, la);
         else if (queue_out) hipLaunchKernelGGL((pw::walk_lanes_kernel<false, false>), lgrid, lblock, 0, g->stream, la);
         else if (verify) hipLaunchKernelGGL((pw::walk_lanes_kernel<true, true>), lgrid, lblock, 0, g->stream, la);
-        else if (tails) hipLaunchKernelGGL((pw::walk_lanes_kernel<true, false, false, true>), lgrid, lblock, 0, g->stream, la);
         else hipLaunchKernelGGL((pw::walk_lanes_kernel<true, false>), lgrid, lblock, 0, g->stream, la);
         HIP_TRY(hipGetLastError());
         if (verify_full) {   // the chain decides this round's recorded steps again
@@ -2102,15 +2065,14 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
         if (parked && weighted) {   // the parked steps of the weighted form: one wavefront each, the wave-per-walk scan
             HIP_TRY(hipMemsetAsync(g->counters.p + 13, 0, sizeof(unsigned long long), g->stream));   // (record counter of the persistent grid)
             const uint64_t want_e = (parked + pw::WAVES_PER_BLOCK - 1) / pw::WAVES_PER_BLOCK;
-            static const int eager_env = getenv("PECANPY_AMD_EAGER_WGS") ? atoi(getenv("PECANPY_AMD_EAGER_WGS")) : 0;   // (workgroups per CU; experiments)
-            const int eager_wgs = eager_env > 0 ? eager_env : (g->twin_active ? 6 : 8);
+            const int eager_wgs = g->twin_active ? 6 : 8;   // (workgroups per CU)
             const unsigned egrid_e = (unsigned)std::min<uint64_t>(want_e, (uint64_t)g->n_cu * (uint64_t)eager_wgs);
             if (extend) hipLaunchKernelGGL(pw::lanes_eager_weighted_kernel<true>, dim3(egrid_e), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa,
                                            g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12, (const uint32_t *)g->d_wedge_row,
-                                           (const unsigned long long *)g->d_wck_off, (const float *)(getenv("PECANPY_AMD_NO_WCKPT") ? nullptr : g->d_wck));
+                                           (const unsigned long long *)g->d_wck_off, (const float *)g->d_wck);
             else hipLaunchKernelGGL(pw::lanes_eager_weighted_kernel<false>, dim3(egrid_e), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa,
                                     g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12, (const uint32_t *)g->d_wedge_row,
-                                    (const unsigned long long *)g->d_wck_off, (const float *)(getenv("PECANPY_AMD_NO_WCKPT") ? nullptr : g->d_wck));
+                                    (const unsigned long long *)g->d_wck_off, (const float *)g->d_wck);
             HIP_TRY(hipGetLastError());
         } else if (parked) {   // settle the queue just filled
             hipLaunchKernelGGL(pw::lanes_chain_kernel, dim3((unsigned)((parked + 255) / 256)), dim3(256), 0, g->stream,
@@ -2233,7 +2195,7 @@ static bool lanes_float_eligible(const pw_graph *g, const pw::WalkArgs &wa) {
 // handle, reported as param_index_ms): the step then is ONE bounded decision instead of two float chains.  A call that
 // samples fewer steps than the graph has lines runs the two-chain step (an existing table is used whatever the call's size).
 static int ensure_unit_tot(pw_graph *g, const pw::WalkArgs &wa) {
-    if (g->utot_failed || getenv("PECANPY_AMD_NO_UTOT")) return 0;
+    if (g->utot_failed) return 0;
     const uint64_t n_lines = (uint64_t)g->nnz + (g->vlines ? g->n_nodes : 0);
     const bool fresh = g->d_utot && g->utot_wo == wa.w_out && g->utot_wp == wa.w_prev;
     if (fresh || !(wa.n_jobs * (uint64_t)wa.L >= n_lines || getenv("PECANPY_AMD_FORCE_TOT"))) return 0;
@@ -2286,7 +2248,7 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_re
     la.susp_count = g->counters.p + 32;
     la.ver_count = g->counters.p + 40;
     la.susp_chunk = 1;
-    if (g->d_utot && g->utot_wo == wa.w_out && g->utot_wp == wa.w_prev && !getenv("PECANPY_AMD_NO_UTOT")) la.tot_e = g->d_utot;   // (ensure_unit_tot)
+    if (g->d_utot && g->utot_wo == wa.w_out && g->utot_wp == wa.w_prev) la.tot_e = g->d_utot;   // (ensure_unit_tot)
     // verification of the interval decision (round 6: lane_tight_values), as in launch_lane_walks: every settled step in test
     // mode (PECANPY_AMD_VERIFY_TIGHT=1), a sample of them in production (PECANPY_AMD_VERIFY_SAMPLE=N, default 1024, 0 = off)
     const char *ver_env = getenv("PECANPY_AMD_VERIFY_TIGHT");
@@ -2436,8 +2398,7 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
     // generators: each level of the jump tree is a launch or two, each generator expands its blocks one after the other --
     // short streams want fewer generators (RMAT-18, 381 k blocks: 256 / 512 / 1024 / 2048 / 4096 -> 1.72 / 1.62 / 2.06 /
     // 2.66 / 3.33 ms), long ones more (RMAT-22, 5.2 M blocks: 1024 / 2048 / 4096 -> 7.8 / 7.2 / 8.9 ms)
-    static const uint64_t gens_env = getenv("PECANPY_AMD_MT_GENS") ? (uint64_t)strtoull(getenv("PECANPY_AMD_MT_GENS"), nullptr, 10) : 0ull;
-    const uint64_t gens_target = gens_env ? gens_env : (n_blocks < (1ull << 21) ? 512ull : 2048ull);
+    const uint64_t gens_target = n_blocks < (1ull << 21) ? 512ull : 2048ull;
     while (per_gen * gens_target < n_blocks) { per_gen <<= 1; per_gen_log++; }
     const uint32_t n_gen = (uint32_t)((n_blocks + per_gen - 1) / per_gen);
     if (!g->jump_table_ready) {
@@ -2483,11 +2444,8 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
             uint32_t parts = jumps >= 128 ? 1u : (uint32_t)(g->n_cu > 0 ? g->n_cu : 256) / jumps;
             if (parts > 39) parts = 39;
             if (parts < 1) parts = 1;
-            static const bool v1 = env_on("PECANPY_AMD_MT_JUMP_V1");   // (the tap loop of rounds 1-5, for same-box comparisons)
-            if (v1) hipLaunchKernelGGL(pw::mt_jump_v1_kernel, dim3(jumps * parts), dim3(640), 0, g->stream, mt_states, poly, src_stride,
-                                       dst_offset, parts, g->jump_tmp.p);
-            else hipLaunchKernelGGL(pw::mt_jump_kernel, dim3(jumps * parts), dim3(640), 0, g->stream, mt_states, poly, src_stride,
-                                    dst_offset, parts, g->jump_tmp.p);
+            hipLaunchKernelGGL(pw::mt_jump_kernel, dim3(jumps * parts), dim3(640), 0, g->stream, mt_states, poly, src_stride,
+                               dst_offset, parts, g->jump_tmp.p);
             if (parts > 1)
                 hipLaunchKernelGGL(pw::mt_jump_store_kernel, dim3(jumps), dim3(640), 0, g->stream, mt_states, g->jump_tmp.p,
                                    src_stride, dst_offset);
@@ -3008,8 +2966,7 @@ static int copy_out_staged(pw_graph *g, void *dst, const void *d_src, size_t byt
         HIP_TRY(hipStreamSynchronize(g->copy_stream));
         return 0;
     }
-    static const int T_env = getenv("PECANPY_AMD_COPY_THREADS") ? atoi(getenv("PECANPY_AMD_COPY_THREADS")) : 0;
-    const int T_use = T_env > 0 ? (T_env > 32 ? 32 : T_env) : 8;
+    const int T_use = 8;                // host threads that copy out of the pinned buffers
     const size_t n_ch = (bytes + CH - 1) / CH;
     const bool dbg = getenv("PECANPY_AMD_COPY_DEBUG") != nullptr;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

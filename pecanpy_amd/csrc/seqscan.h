@@ -261,9 +261,9 @@ struct ListView {
     const void *piv = nullptr;   // pivots (same entry width), or nullptr
     uint32_t npiv = 0;           // their number (0: none)
     uint32_t step = 0;           // pivot k = entry (k + 1) * step
-    // Lane kernel (PW_LANES_LINE_LDS): bytes 16..63 of the edge line -- row start, list offset and the inline area: the list
-    // itself or its pivots -- were copied to LDS when the step that entered the edge was applied (three 16-byte pieces,
-    // 1024 bytes apart: global_load_lds writes piece c of lane t at base + 1024 c + 16 t).  `tail` = LDS address of this
+    // lanes_chain_kernel (walk_lanes.hip.h): bytes 16..63 of the edge line -- row start, list offset and the inline area: the
+    // list itself or its pivots -- were copied to LDS before the chain (three 16-byte pieces, 1024 bytes apart:
+    // global_load_lds writes piece c of lane t at base + 1024 c + 16 t).  `tail` = LDS address of this
     // lane's piece 0; what lives in the line is then read from there instead of from global memory.
     uint32_t tail = 0xffffffffu; // 0xffffffff: not staged
     uint32_t inl = 0;            // the list itself lives in the line (p points into it)

@@ -164,14 +164,8 @@ __device__ unsigned long long g_lprof[16];
 #ifndef PW_LANES_MIN_WAVES
 #define PW_LANES_MIN_WAVES 4   // 128 VGPRs: the in-place form needs ~130 (chain code); at 5-6 waves it spills in the hot loop and runs 1.6-2x slower
 #endif
-#ifndef PW_LANES_MIN_WAVES_Q
-#define PW_LANES_MIN_WAVES_Q 6   // ... of the queueing form (no chain code; statistics in scalar registers): 80 VGPRs, six waves without spilling
-#endif
-#ifndef PW_LANES_DEFER
-#define PW_LANES_DEFER 1         // queueing form: ambiguous steps wait in a per-wavefront LDS pool for a full-width interval decision
-#endif
 #ifndef PW_LANES_MIN_WAVES_D
-#define PW_LANES_MIN_WAVES_D 5   // ... its occupancy (96 VGPRs; 5 KB of pool + 2 KB of job window per wavefront: 5 x 4 x 7 KB = 140 KB of LDS per CU)
+#define PW_LANES_MIN_WAVES_D 5   // ... of the WEIGHTED queueing form
 #endif
 #ifndef PW_LANES_DEFER_TH
 #define PW_LANES_DEFER_TH 32     // deferred steps that trigger a pass of the interval decision (lanes enabled in it)
@@ -182,30 +176,14 @@ __device__ unsigned long long g_lprof[16];
 #ifndef PW_LANES_WIN
 #define PW_LANES_WIN 64          // jobs prefetched into the job window at a time
 #endif
-#ifndef PW_LANES_DRAW_LDS
-#define PW_LANES_DRAW_LDS 0      // 1: a walk's draws are fetched a 64-byte sector (8 draws) at a time, straight into LDS
-#endif
-#ifndef PW_LANES_LINE_LDS
-#define PW_LANES_LINE_LDS 0      // 1: the rest of the edge line a step enters (inline list / pivots) is copied to LDS with the record
-#endif
-#ifndef PW_LANES_QUAD
-#define PW_LANES_QUAD 1          // round 5: edge lines and list sectors are fetched WHOLE (64 bytes) by quads of lanes, straight into LDS
-#endif
 #ifndef PW_LANES_QPOOL
-#define PW_LANES_QPOOL 48        // ... pool slots / window jobs of that form (LDS: 4 KB of lines per wavefront on top)
+#define PW_LANES_QPOOL 48        // pool slots / window jobs of the QUAD form (LDS: 4 KB of lines per wavefront on top)
 #endif
 #ifndef PW_LANES_QWIN
 #define PW_LANES_QWIN 32
 #endif
 #ifndef PW_LANES_MIN_WAVES_QD
 #define PW_LANES_MIN_WAVES_QD 4  // ... its occupancy: 35 KB of LDS per workgroup = 4 per CU; the memory path, not the wave count, sets its pace
-#endif
-#ifndef PW_LANES_QPIPE
-#define PW_LANES_QPIPE 0         // 1: the line requested when a step is taken is applied at the top of the NEXT iteration, behind the pool's pass
-                                 // (measured: 122 vs 118 ms per RMAT-22 pass -- the wait then also covers the stores the pass has just issued)
-#endif
-#ifndef PW_LANES_QDRAW_EARLY
-#define PW_LANES_QDRAW_EARLY 1   // the next step's draw is requested together with the line, not after the record has arrived
 #endif
 #ifndef PW_LANES_CHAIN_TH
 #define PW_LANES_CHAIN_TH 20     // CHAINS form: steps waiting for their float chain that trigger a chain pass of the pool (28: the pool
@@ -297,8 +275,7 @@ __device__ unsigned long long g_lprof[16];
                     for (uint32_t z_ = A.j; z_ <= L; z_++) row_[z_] = 0;                        \
                 }                                                                               \
                 A.flags = 0;                                                                    \
-            } else if (PW_LANES_DRAW_LDS) { PW_DRAW_STAGE(A.soff + (A.j - 1)); }                \
-            else if (!(draw_prefetched_)) r = a.rng[A.soff + (A.j - 1)];   /* the next step's draw, asked for now */ \
+            } else if (!(draw_prefetched_)) r = a.rng[A.soff + (A.j - 1)];   /* the next step's draw, asked for now */ \
     } while (0)
 
 // ---- a binade with a ROUNDING TIE, walked by the whole wavefront (round 6) ------------------------------------------------------
@@ -394,29 +371,22 @@ __device__ __forceinline__ TieOut coop_tie_binade(const void *lp, uint32_t wide,
     return o;
 }
 
-#ifndef PW_CHAIN_COOP
-#define PW_CHAIN_COOP 1
-#endif
-#ifndef PW_CHAIN_STEP
-#define PW_CHAIN_STEP 1   // the wavefront's chains advance one binade at a time, in step (tying binades are walked between the steps)
-#endif
 // The float32 chains of the lanes with `active` set, by the wavefront: every chain advances one iteration of lane_chain's binade
-// loop at a time (PW_CHAIN_STEP), a lane that stops in front of a binade with a rounding tie has it walked by all 64 lanes
+// loop at a time, in step (tying binades are walked between the steps), a lane that stops in front of a binade with a rounding tie has it walked by all 64 lanes
 // (coop_tie_binade) and goes on.  CONVERGED code: every lane of the wavefront calls it.  list_p: the list in global memory
 // (cl.p before any staging).  Returns what lane_chain returns (position, LANE_CHAIN_END, LANE_TIE).
 __device__ __forceinline__ uint32_t lane_chain_wave(bool active, uint32_t kend, uint32_t n_in, uint32_t pp, double r, float x_in,
                                                     float x_out, float x_prev, const ListView &cl, const void *list_p, uint32_t &reads_total) {
     using B = Binade<float>;
     ChainResume rs;
-    rs.c = 0.0f; rs.k = 0u; rs.i0 = 0u; rs.started = 0u; rs.yield = PW_CHAIN_STEP ? 1u : 0u;
+    rs.c = 0.0f; rs.k = 0u; rs.i0 = 0u; rs.started = 0u; rs.yield = 1u;
     uint32_t res = 0u;
     reads_total = 0;
     if (active) {
         uint32_t reads = 0;
-        res = lane_chain(kend, n_in, pp, r, x_in, x_out, x_prev, cl, reads, nullptr, LANE_TIE_BUDGET, PW_CHAIN_COOP ? &rs : nullptr);
+        res = lane_chain(kend, n_in, pp, r, x_in, x_out, x_prev, cl, reads, nullptr, LANE_TIE_BUDGET, &rs);
         reads_total += reads;
     }
-#if PW_CHAIN_COOP
     for (;;) {
         uint64_t pend = ballot(active && res == LANE_TIE_PENDING);
         if (!pend && !ballot(active && res == LANE_YIELD)) break;
@@ -451,13 +421,12 @@ __device__ __forceinline__ uint32_t lane_chain_wave(bool active, uint32_t kend, 
                 }
             }
         }
-        if (active && res == LANE_YIELD) {   // (the chain goes on: behind its tying binade, or -- PW_CHAIN_STEP -- one iteration at a time)
+        if (active && res == LANE_YIELD) {   // (the chain goes on: behind its tying binade, or one iteration at a time)
             uint32_t reads = 0;
             res = lane_chain(kend, n_in, pp, r, x_in, x_out, x_prev, cl, reads, nullptr, LANE_TIE_BUDGET, &rs);
             reads_total += reads;
         }
     }
-#endif
     return res;
 }
 
@@ -475,7 +444,7 @@ struct __attribute__((packed, aligned(4))) OutCells {   // four staged output ce
 // form per binade (lane_chain): the row total w.sum() (sparse_rw.py:89), then cumsum / searchsorted over w / tot
 // (pecanpy.py:556-557).  ~6x fewer wave instructions per step than walk_kernel's eager step, which gives every walk a
 // whole wavefront.
-// DEFER (queueing form, !INPLACE, PW_LANES_DEFER): the interval decision (lane_tight, ~850 instructions, no memory access)
+// DEFER (queueing form, !INPLACE, dyadic): the interval decision (lane_tight, ~850 instructions, no memory access)
 // is NOT run where the ambiguity turns up -- 12 % of the lanes, so nearly every loop iteration would pay for it with an
 // eighth of its lanes enabled (round 3: ~40 % of the kernel's vector instructions).  The lane writes the walk's context
 // (80 bytes: walk state, draw, what lane_decide found, staged output cells) into a POOL of 64 slots in LDS, one pool per
@@ -485,11 +454,6 @@ struct __attribute__((packed, aligned(4))) OutCells {   // four staged output ce
 // decision leaves open go to the global queue of parked walks from there.  Slots are handed out by rank (r-th deferring
 // lane <- r-th free slot, through a 64-byte map in LDS); a step that finds no free slot is parked in the global queue
 // undecided (lanes_chain_kernel settles it by the float chain: any ambiguous step may go there).
-// TAILS: bytes 16..63 of the edge line a step enters (the inline list, or the pivots of a longer one) are copied to LDS with
-// the record's load (LDS-DMA, no registers) and the next step's searches read them there.  Chosen by the host for graphs
-// whose lines stay cache resident (RMAT-18: the probes it removes were L2 hits, 15.0 -> 13.4 ms per pass); at RMAT-22 the
-// dependent HBM probes of the long lists set the pace and it is neutral (139.7 vs 138.8 ms), so the plain form stays.
-// The LDS it takes comes out of the pool and the job window (32 slots / 32 jobs instead of 64 / 64: measured equal).
 // WEIGHTED (round 4): weighted CSR graphs, node2vec and node2vec+.  A step is decided by lane_decide_weighted (seqscan.h)
 // from the per-vertex float64 prefix sums of the base values + the arriving entry's delta prefix sums, with a rigorous
 // bound on the float32 chain; what the bound leaves open (RMAT-20 with hashed weights: 10 % of the steps), the first
@@ -503,13 +467,12 @@ struct __attribute__((packed, aligned(4))) OutCells {   // four staged output ce
 // resident lane (a shard of a multi-GPU run, RMAT-18..20 sized calls), where every round lasts as long as its slowest walks.
 // The chain code costs registers (3 waves per SIMD), so whole-array calls at RMAT-22 keep the rounds.  Only a step that finds
 // the pool full is parked (the host's round loop handles what is left, usually nothing).
-template <bool INPLACE, bool VERIFY, bool FLOATS = false, bool TAILS = false, bool WEIGHTED = false, bool CHAINS = false>
+template <bool INPLACE, bool VERIFY, bool FLOATS = false, bool WEIGHTED = false, bool CHAINS = false>
 __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE, CHAINS ? PW_LANES_MIN_WAVES_C : INPLACE ? PW_LANES_MIN_WAVES
-                                      : ((PW_LANES_QUAD && PW_LANES_DEFER && !FLOATS && !WEIGHTED) ? PW_LANES_MIN_WAVES_QD
-                                         : (PW_LANES_DEFER ? PW_LANES_MIN_WAVES_D : PW_LANES_MIN_WAVES_Q)))
+                                      : (!FLOATS && !WEIGHTED) ? PW_LANES_MIN_WAVES_QD : PW_LANES_MIN_WAVES_D)
 walk_lanes_kernel(LanesArgs a) {
-    constexpr bool DEFER = PW_LANES_DEFER && !INPLACE && !FLOATS && !WEIGHTED;
-    static_assert(!CHAINS || (DEFER && !TAILS), "the CHAINS form is the deferred queueing form plus in-kernel chain passes");
+    constexpr bool DEFER = !INPLACE && !FLOATS && !WEIGHTED;
+    static_assert(!CHAINS || DEFER, "the CHAINS form is the deferred queueing form plus in-kernel chain passes");
     // QUAD (round 5; the dyadic forms): what a step reads of the graph comes in WHOLE 64-byte sectors, fetched by quads of
     // lanes straight into LDS (global_load_lds, 16 bytes per lane: lane l moves piece l & 3 of the sector wanted by lane
     // 16 k + (l >> 2), k = 0..3 -- the 64 bytes of lane w's sector land contiguously at byte 64 w of the wavefront's buffer):
@@ -519,14 +482,9 @@ walk_lanes_kernel(LanesArgs a) {
     // 29.1 G/s; three dependent 2-byte probes of the same line on top of the record 15.7 G/s), so the record load, the
     // probes of the inline list / the pivots and the last five levels of every overflow-list bisection -- 5.7 requests per
     // step in round 4 -- become one request per line entered plus one per list sector visited.
-    constexpr bool QUAD = PW_LANES_QUAD && !FLOATS && !WEIGHTED && !TAILS;
-    constexpr bool LINE_LDS = (TAILS || PW_LANES_LINE_LDS) && !QUAD;
-    static_assert(!(QUAD && PW_LANES_DRAW_LDS), "the QUAD form fetches its draws with the lines");
-    constexpr int POOL_N = CHAINS ? PW_LANES_CPOOL : QUAD ? (PW_LANES_POOL < PW_LANES_QPOOL ? PW_LANES_POOL : PW_LANES_QPOOL)
-                                : (TAILS ? (PW_LANES_POOL < 32 ? PW_LANES_POOL : 32) : PW_LANES_POOL);
-    constexpr int WIN_N = CHAINS ? PW_LANES_CWIN : QUAD ? (PW_LANES_WIN < PW_LANES_QWIN ? PW_LANES_WIN : PW_LANES_QWIN)
-                               : (TAILS ? (PW_LANES_WIN < 32 ? PW_LANES_WIN : 32) : PW_LANES_WIN);
-    constexpr uint32_t DEFER_TH = TAILS ? (PW_LANES_DEFER_TH < 16 ? PW_LANES_DEFER_TH : 16) : PW_LANES_DEFER_TH;
+    constexpr bool QUAD = !FLOATS && !WEIGHTED;
+    constexpr int POOL_N = CHAINS ? PW_LANES_CPOOL : QUAD ? (PW_LANES_POOL < PW_LANES_QPOOL ? PW_LANES_POOL : PW_LANES_QPOOL) : PW_LANES_POOL;
+    constexpr int WIN_N = CHAINS ? PW_LANES_CWIN : QUAD ? (PW_LANES_WIN < PW_LANES_QWIN ? PW_LANES_WIN : PW_LANES_QWIN) : PW_LANES_WIN;
     const int lane = lane_id();
     const uint32_t L = a.L;
     const uint64_t W = (uint64_t)L + 2;
@@ -616,43 +574,11 @@ walk_lanes_kernel(LanesArgs a) {
     float tot = 1.0f, wo = 1.0f;
     uint32_t kmax = 0;
 
-    // DRAWS (PW_LANES_DRAW_LDS): the draws of a walk are consecutive doubles of the stream, but between two steps of a lane
-    // every other lane of the GPU touches its own sectors and the sector is gone from L2 -- one 64-byte fetch per 8-byte
-    // draw.  Instead the whole sector (8 draws) is fetched ONCE, straight into LDS (global_load_lds_dwordx4: lane t's
-    // 16-byte piece c lands at s_draw[c][t], no VGPRs), when the walk's stream position enters it.
     typedef __attribute__((address_space(3))) void *lds_ptr_t;
     typedef const __attribute__((address_space(1))) void *glb_ptr_t;
-    __shared__ uint4 s_draw[PW_LANES_DRAW_LDS ? WAVES_PER_BLOCK : 1][4][WAVE];
-    uint4 (*const dslot)[WAVE] = s_draw[PW_LANES_DRAW_LDS ? readfirst_u32(threadIdx.x / WAVE) : 0];
-    uint32_t dsec = 0xffffffffu;         // the sector (stream position / 8) this lane's slot holds
-#define PW_DRAW_STAGE(di)                                                                                              \
-    do {                                                                                                               \
-        const uint32_t sec_ = (uint32_t)((uint64_t)(di) >> 3);                                                         \
-        if (sec_ != dsec) {                                                                                            \
-            const double *src_ = a.rng + (uint64_t)sec_ * 8u;                                                          \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src_ + 0), (lds_ptr_t)&dslot[0][0], 16, 0, 0);               \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src_ + 2), (lds_ptr_t)&dslot[1][0], 16, 0, 0);               \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src_ + 4), (lds_ptr_t)&dslot[2][0], 16, 0, 0);               \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src_ + 6), (lds_ptr_t)&dslot[3][0], 16, 0, 0);               \
-            dsec = sec_;                                                                                               \
-        }                                                                                                              \
-    } while (0)
-    // LINE TAILS (PW_LANES_LINE_LDS): bytes 16..63 of the edge line a step enters -- the inline list or the pivots of a longer
-    // one -- go to LDS with the record's load; the next step's searches read them there (seqscan.h: ListView::tail)
-    __shared__ uint4 s_tail[LINE_LDS ? WAVES_PER_BLOCK : 1][3][WAVE];
-    uint4 (*const dtail)[WAVE] = s_tail[LINE_LDS ? readfirst_u32(threadIdx.x / WAVE) : 0];
-    const uint32_t tail_addr = LINE_LDS ? (uint32_t)(uintptr_t)(lds_ptr_t)&dtail[0][lane] : 0xffffffffu;
-#define PW_LINE_STAGE(rp)                                                                                              \
-    do {                                                                                                               \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)((rp) + 1), (lds_ptr_t)&dtail[0][0], 16, 0, 0);                   \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)((rp) + 2), (lds_ptr_t)&dtail[1][0], 16, 0, 0);                   \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)((rp) + 3), (lds_ptr_t)&dtail[2][0], 16, 0, 0);                   \
-    } while (0)
-    // the list view of the entry this lane's walk arrived by (staged: what lives in the line is read from LDS)
+    // the list view of the entry this lane's walk arrived by
     auto lane_list = [&](uint32_t e_, uint32_t d_, uint32_t n_in_, uint32_t coff_) -> ListView {
-        ListView v = edge_list(a.lines, a.clist, e_, d_, n_in_, coff_);
-        if (LINE_LDS) { v.tail = tail_addr; v.inl = (d_ <= 65536u && n_in_ <= EL_INLINE) ? 1u : 0u; }
-        return v;
+        return edge_list(a.lines, a.clist, e_, d_, n_in_, coff_);
     };
     // QUAD: one 64-byte slot per lane -- the edge line the walk entered, later the list sector its search looks into
     __shared__ uint4 s_quad[QUAD ? WAVES_PER_BLOCK : 1][4][WAVE];
@@ -685,12 +611,8 @@ walk_lanes_kernel(LanesArgs a) {
         quad_issue(want, base, sec);
         quad_wait();
     };
-    bool pending = false;   // QUAD: this lane's walk has taken an edge whose line is on its way (requested at the end of the last iteration)
     auto q_u32 = [&](uint32_t off) -> uint32_t { return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)(qslot + off); };
     auto q_u16 = [&](uint32_t off) -> uint32_t { return (uint32_t) * (const __attribute__((address_space(3))) uint16_t *)(uintptr_t)(qslot + off); };
-    // (the compiler does not order an LDS read behind the LDS-DMA that fills it: the wait is explicit)
-#define PW_DRAW_READ(di)                                                                                               \
-    (*(const double *)((const char *)&dslot[((uint32_t)(di) & 7u) >> 1][lane] + (((uint32_t)(di) & 1u) << 3)))
 
 #ifdef PW_LANES_WATCHDOG
     unsigned long long wd_main = 0, wd_refill = 0;
@@ -700,7 +622,7 @@ walk_lanes_kernel(LanesArgs a) {
         PW_WD(1, 2000000ull, wd_main);
         if (DEFER) {
             // ---- PASS: the interval decision of every deferred step, slot s by lane s ---------------------------------
-            if (m_def && (force_pass || (uint32_t)__popcll(m_def) >= (CHAINS ? 24u : DEFER_TH) || (uint32_t)__popcll(m_def | m_set | m_chn) >= (uint32_t)(POOL_N - POOL_N / 8))) {
+            if (m_def && (force_pass || (uint32_t)__popcll(m_def) >= (CHAINS ? 24u : (uint32_t)PW_LANES_DEFER_TH) || (uint32_t)__popcll(m_def | m_set | m_chn) >= (uint32_t)(POOL_N - POOL_N / 8))) {
                 force_pass = false;
                 LPROF_C(9, 1);
                 LPROF_C(10, __popcll(m_def));
@@ -819,20 +741,6 @@ walk_lanes_kernel(LanesArgs a) {
                 wave_lds_fence();
             }
         }
-        // ---- QUAD: the lines requested when the last iteration's steps were taken have had the pool's work to arrive in ----
-        if (QUAD && PW_LANES_QPIPE && ballot(pending)) {
-            quad_wait();
-            if (pending) {
-                typedef uint32_t __attribute__((ext_vector_type(4))) lds_u4;
-                typedef uint32_t __attribute__((ext_vector_type(2))) lds_u2;
-                const lds_u4 t0_ = *(const __attribute__((address_space(3))) lds_u4 *)(uintptr_t)qslot;
-                const lds_u2 t1_ = *(const __attribute__((address_space(3))) lds_u2 *)(uintptr_t)(qslot + 16u);
-                const uint4 r0_ = make_uint4(t0_.x, t0_.y, t0_.z, t0_.w);
-                const uint2 r1_ = make_uint2(t1_.x, t1_.y);
-                PW_LANE_APPLY_TAIL(r0_, r1_, PW_LANES_QDRAW_EARLY != 0);
-                pending = false;
-            }
-        }
         // ---- refill idle lanes from the job counter -------------------------------------------------------
         for (;;) {
             PW_WD(2, 2000000ull, wd_refill);
@@ -880,8 +788,7 @@ walk_lanes_kernel(LanesArgs a) {
                                 for (uint32_t z = 1; z <= L; z++) row[z] = 0;
                         } else {
                             const uint64_t so = LAP(const uint64_t *, stream_off)[job] - LA64(rng_base);
-                            double r0 = 0.0;
-                            if (!PW_LANES_DRAW_LDS) r0 = a.rng[so];
+                            const double r0 = a.rng[so];
                             w0 = make_uint4(job, start, vr.x, vr.y);
                             w1 = make_uint4((uint32_t)so, (uint32_t)(so >> 32), (uint32_t)__double_as_longlong(r0),
                                             (uint32_t)((unsigned long long)__double_as_longlong(r0) >> 32));
@@ -908,8 +815,7 @@ walk_lanes_kernel(LanesArgs a) {
                     A.job = j0.x;
                     A.soff = ((uint64_t)j1.y << 32) | j1.x;
                     A.s0 = j0.z; A.d = j0.w; A.n_in = 0; A.pp = NOT_FOUND; A.e = WEIGHTED ? j0.y : 0u; A.coff = 0; A.j = 1;
-                    if (PW_LANES_DRAW_LDS) { PW_DRAW_STAGE(A.soff); }
-                    else r = __longlong_as_double((long long)(((unsigned long long)j1.w << 32) | j1.z));
+                    r = __longlong_as_double((long long)(((unsigned long long)j1.w << 32) | j1.z));
                     A.flags = F_ACTIVE;
                 }
                 win_pos += take_w;
@@ -951,10 +857,6 @@ walk_lanes_kernel(LanesArgs a) {
         // their chains together once a few have gathered or nothing else can run.
         uint32_t choice = LANE_AMBIGUOUS;
         const bool runnable = A.flags == F_ACTIVE;
-        if (PW_LANES_DRAW_LDS || LINE_LDS) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (what was requested when the last steps were applied has landed in LDS)
-            if (PW_LANES_DRAW_LDS && runnable) r = PW_DRAW_READ(A.soff + (A.j - 1));
-        }
         if (FLOATS) {
             if (runnable && A.n_in != 0u && !edge_list_stored(A.d, A.n_in, A.coff)) choice = LANE_NEEDS_WAVE;   // (partial index)
             else if (runnable && a.tot_e) {
@@ -1081,7 +983,7 @@ walk_lanes_kernel(LanesArgs a) {
                     if (INPLACE && !a.susp) choice = LANE_NEEDS_WAVE;       // no queue: walk_kernel takes the walk over here
                 }
             }
-        } else if (QUAD) {
+        } else {   // (QUAD)
             // lane_decide with the search run here: the line the walk entered waits in this lane's LDS slot (record, inline list
             // or pivots); an overflow list is searched SECTOR by sector -- every lane that still needs one names it, the quads
             // fetch them all (one request per sector), and the lane looks at the sector's first and last entry of its range:
@@ -1176,12 +1078,6 @@ walk_lanes_kernel(LanesArgs a) {
                 }
             }
             if (go) choice = lane_decide_end(A.d, A.n_in, A.pp, dc, &sr, ls);
-            n_probes += ls.probes;
-        } else
-        if (runnable && !nolist) {
-            wo = A.j >= 2 ? w_out : 1.0f;   // first step of a walk: no bias (sparse_rw.py:66)
-            // (r = this step's draw: loaded when the previous step was applied / the walk was started)
-            choice = lane_decide(A.d, A.n_in, A.pp, r, wo, w_prev, lane_list(A.e, A.d, A.n_in, A.coff), ls);
             n_probes += ls.probes;
         }
         if (nolist && !WEIGHTED) {
@@ -1308,24 +1204,23 @@ walk_lanes_kernel(LanesArgs a) {
         n_steps += (unsigned long long)__popcll(ballot(A.flags == F_ACTIVE && choice < A.d));   // (LANE_* codes are >= any degree)
         if (QUAD) {
             // the lines of all lanes that move on: ONE request each, by the quads, into the lanes' slots -- and the next step's
-            // draw with them.  Nothing waits here: the record is applied at the top of the next iteration, behind the pool's
-            // pass (PW_LANE_APPLY_TAIL above), so the round trip runs under the interval decisions of the deferred steps.
+            // draw with them, not after the record has arrived -- then the records are applied.  (Applied at the top of the next
+            // iteration instead, behind the pool's pass: 122 vs 118 ms per RMAT-22 pass -- the wait then also covers the stores
+            // the pass has just issued.)
             bool fetch = false;
             if (A.flags == F_ACTIVE && choice != LANE_AMBIGUOUS) PW_LANE_APPLY_HEAD(fetch);
-            if (PW_LANES_QDRAW_EARLY && fetch && A.j < L) r = a.rng[A.soff + A.j];   // (step A.j + 1 samples with double #(soff + A.j); unused if the walk ends)
+            if (fetch && A.j < L) r = a.rng[A.soff + A.j];   // (step A.j + 1 samples with double #(soff + A.j); unused if the walk ends)
             quad_issue(fetch, (const uint8_t *)a.lines, A.e);
-            pending = fetch;
-            if (!PW_LANES_QPIPE && ballot(pending)) {
+            if (ballot(fetch)) {
                 quad_wait();
-                if (pending) {
+                if (fetch) {
                     typedef uint32_t __attribute__((ext_vector_type(4))) lds_u4;
                     typedef uint32_t __attribute__((ext_vector_type(2))) lds_u2;
                     const lds_u4 t0_ = *(const __attribute__((address_space(3))) lds_u4 *)(uintptr_t)qslot;
                     const lds_u2 t1_ = *(const __attribute__((address_space(3))) lds_u2 *)(uintptr_t)(qslot + 16u);
                     const uint4 r0_ = make_uint4(t0_.x, t0_.y, t0_.z, t0_.w);
                     const uint2 r1_ = make_uint2(t1_.x, t1_.y);
-                    PW_LANE_APPLY_TAIL(r0_, r1_, PW_LANES_QDRAW_EARLY != 0);
-                    pending = false;
+                    PW_LANE_APPLY_TAIL(r0_, r1_, true);
                 }
             }
         } else if (A.flags == F_ACTIVE && choice != LANE_AMBIGUOUS) {
@@ -1335,7 +1230,6 @@ walk_lanes_kernel(LanesArgs a) {
                 const uint4 *rp_ = (const uint4 *)(a.lines + A.e);
                 const uint4 r0_ = rp_[0];
                 const uint2 r1_ = *(const uint2 *)(rp_ + 1);
-                if (LINE_LDS) { PW_LINE_STAGE(rp_); }
                 PW_LANE_APPLY_TAIL(r0_, r1_, false);
             }
         }
@@ -1346,9 +1240,6 @@ walk_lanes_kernel(LanesArgs a) {
     }
 #undef PW_LANE_APPLY_HEAD
 #undef PW_LANE_APPLY_TAIL
-#undef PW_DRAW_STAGE
-#undef PW_DRAW_READ
-#undef PW_LINE_STAGE
     if (LA64(susp))
         for (uint64_t v = sp_lo + (uint64_t)lane; v < sp_hi; v += WAVE) LAP(SuspRec *, susp)[v].job = NOT_FOUND;   // reserved, unused
 #ifdef PW_PROF_LANES
@@ -1373,23 +1264,15 @@ walk_lanes_kernel(LanesArgs a) {
 #undef LAP
 
 // ---- the float32 chains of a whole queue of parked walks, one lane each, every lane busy ------------------------------
-#ifndef PW_CHAIN_TAILS
-#define PW_CHAIN_TAILS 1   // the chain's ~17 searches bisect the same pivots (or the same inline list): bytes 16..63 of the entry's
-                           // line are staged in LDS once per chain (seqscan.h: ListView::tail).  RMAT-22 pass 137.6 -> 134.3 ms
-#endif
 #ifndef PW_CHAIN_WAVES
 #define PW_CHAIN_WAVES 5   // 88 VGPRs; six waves (80) spill 44 bytes and gain 0.5 %
-#endif
-#ifndef PW_CHAIN_SORT
-#define PW_CHAIN_SORT 1    // the 256 records of a workgroup are dealt to its lanes in the order of their prefix bound kmax (the chain's
-                           // length): a wavefront lasts as long as its longest chain, so chains of similar length share one
 #endif
 __global__ void __launch_bounds__(256, PW_CHAIN_WAVES)
 lanes_chain_kernel(SuspRec *q, uint64_t n, const ELine *__restrict__ lines, const uint8_t *__restrict__ clist, float w_prev,
                    unsigned long long *stats) {
-    using B = Binade<float>;
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (PW_CHAIN_SORT) {
+    {   // the 256 records of a workgroup are dealt to its lanes in the order of their prefix bound kmax (the chain's length):
+        // a wavefront lasts as long as its longest chain, so chains of similar length share one
         __shared__ uint32_t s_key[256];
         __shared__ uint16_t s_ord[256];
         uint32_t key = 0u;                                  // (void slots / steps for lanes_eager_kernel: first, they cost nothing)
@@ -1408,8 +1291,8 @@ lanes_chain_kernel(SuspRec *q, uint64_t n, const ELine *__restrict__ lines, cons
     unsigned long long reads_l = 0, done = 0;
     typedef __attribute__((address_space(3))) void *lds_ptr_t;
     typedef const __attribute__((address_space(1))) void *glb_ptr_t;
-    __shared__ uint4 s_tail[PW_CHAIN_TAILS ? 4 : 1][3][WAVE];
-    uint4 (*const dtail)[WAVE] = s_tail[PW_CHAIN_TAILS ? readfirst_u32(threadIdx.x / WAVE) : 0];
+    __shared__ uint4 s_tail[4][3][WAVE];
+    uint4 (*const dtail)[WAVE] = s_tail[readfirst_u32(threadIdx.x / WAVE)];
     uint4 q0 = make_uint4(NOT_FOUND, 0u, 0u, 0u), q1 = make_uint4(0u, 0u, 0u, 0u), q2 = make_uint4(0u, 0u, 0u, 0u), q3 = make_uint4(0u, 0u, 0u, 0u);
     if (i < n) {
         const uint4 *qp = (const uint4 *)(q + i);
@@ -1421,7 +1304,9 @@ lanes_chain_kernel(SuspRec *q, uint64_t n, const ELine *__restrict__ lines, cons
     const float x_in = 1.0f / tot, x_out = x_in * wo, x_prev = x_in * w_prev;
     ListView cl = edge_list(lines, clist, q1.z, q0.w, q1.x, q1.w);
     const void *const list_p = cl.p;                       // (global memory: what the cooperative walk of a tying binade reads)
-    if (active && PW_CHAIN_TAILS && q1.x != 0u) {   // bytes 16..63 of the entry's line -> LDS (the inline list or the pivots)
+    // the chain's ~17 searches bisect the same pivots (or the same inline list): bytes 16..63 of the entry's line are staged
+    // in LDS once per chain (seqscan.h: ListView::tail).  RMAT-22 pass 137.6 -> 134.3 ms
+    if (active && q1.x != 0u) {
         const uint4 *rp = (const uint4 *)(lines + q1.z);
         __builtin_amdgcn_global_load_lds((glb_ptr_t)(rp + 1), (lds_ptr_t)&dtail[0][0], 16, 0, 0);
         __builtin_amdgcn_global_load_lds((glb_ptr_t)(rp + 2), (lds_ptr_t)&dtail[1][0], 16, 0, 0);
