@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include <functional>
 #include <future>
+#include <memory>
 #include <mutex>
 #include <cmath>
 #include <string>
@@ -87,20 +88,40 @@ template <typename T> struct DevBuf {
 
 }  // namespace
 
-struct pw_graph {
-    int device = 0;
+// The scalar description of a graph: pw_graph_replicate copies it in one assignment.
+struct GraphDesc {
     int kind = 0;  // 0 = CSR, 1 = dense
     uint32_t n_nodes = 0, nnz = 0;
     bool unit = false;  // all weights are 1.0f (data not stored)
     uint32_t max_degree = 0;
+    bool bits_only = false;          // dense graph created from packed bits: no compressed rows
+    bool dense_nonneg = false;       // weighted dense graph: every stored value is finite and > 0 (walk_dense_w.hip.h)
+    uint32_t words_per_row = 0;
+    bool has_loop = false;                              // the CSR has a self loop (unit graphs: lists fixed up, wave kernel's lazy step off)
+    bool lanes_off = false;                             // PECANPY_AMD_NO_LANES was set when the handle was created: the index is
+                                                        // built (the wave kernel's lazy step reads it) but the lane kernel is not used
+    bool vlines = false;                                // lines[nnz + v]: the line of vertex v's mirrored overflow read
+    uint64_t clist_bytes = 0, line_bytes = 0;
+    uint64_t fbits_words = 0, slot_words = 0;           // sizes of d_fbits / d_slots (pw_graph_replicate copies the buffers)
+    uint64_t n_clist = 0;
+    uint32_t list_max_len = 0xffffffffu;                // partial index: lists longer than this were left out (EL_NO_LIST)
+    uint64_t index_bytes = 0;                           // device bytes of the membership / lane index
+};
+
+// A graph on one device: its arrays, index and per-(p, q) tables, shared by the call contexts (pw_graph) that walk it.
+// Written only by handle creation (pw_csr_create, pw_dense_create*, pw_graph_replicate), pw_graph_set_thresholds,
+// pw_precomp_build and the lazy builders -- d_hasnbr in compute_offsets, ensure_tot_table, ensure_unit_tot,
+// ensure_wlane_tables, spp_check -- each of which writes nothing when its keys already match.  A twin context reads it
+// from another thread while the primary walks: its calls use the primary's (p, q, extend) and thresholds, so they find
+// every table in place.
+struct GraphData : GraphDesc {
+    int device = 0;
     uint32_t *d_indptr = nullptr, *d_indices = nullptr;
     uint32_t *d_hasnbr = nullptr;                       // bit v: vertex v has neighbours (stream offsets; built by the first call)
     void *d_data = nullptr;          // float32 (CSR graphs) or float64 (dense graphs); null when unit
     float *d_thr = nullptr;
     uint64_t *d_adjbits = nullptr;   // dense graphs: bit-packed adjacency rows
     uint32_t *d_deg = nullptr;       // dense graphs: row degrees
-    bool bits_only = false;          // dense graph created from packed bits: no compressed rows
-    bool dense_nonneg = false;       // weighted dense graph: every stored value is finite and > 0 (walk_dense_w.hip.h)
     uint32_t *d_foff = nullptr;      // CSR graphs: per-row membership filters (offsets, bits)
     uint64_t *d_fbits = nullptr;
     uint2 *d_kf = nullptr;           // CSR graphs: (neighbour id, filter word) per CSR entry
@@ -109,20 +130,15 @@ struct pw_graph {
     pw::ELine *d_lines = nullptr;                       // lane index (walk_lanes.hip.h): 64-byte edge line per CSR entry; its first 16 bytes
                                                         // {neighbour, common-neighbour count, reverse position, degree} also serve walk_kernel's lazy step
     uint8_t *d_clist = nullptr;                         // lane index: the lists too long for their edge line
-    uint64_t clist_bytes = 0, line_bytes = 0;
-    uint64_t fbits_words = 0, slot_words = 0;           // sizes of d_fbits / d_slots (pw_graph_replicate copies the buffers)
-    bool vlines = false;                                // lines[nnz + v]: the line of vertex v's mirrored overflow read
-    // TWIN (round 6): a second call context on the SAME device that aliases this handle's graph, index and per-(p, q) tables
-    // (own streams, counters, queues, stream buffers): the weighted lane form walks the two halves of a job array on the two
-    // contexts side by side, so that one half's eager kernel runs beside the other half's lane round (simulate_twin)
-    pw_graph *twin = nullptr;
-    bool alias = false;                                 // this handle IS such a twin: the shared buffers are not its to free
-    bool twin_active = false;                           // the current call runs on both contexts: each takes a share of the GPU
-    std::function<void()> on_tables_ready;              // simulate_twin: called once the call's per-(p, q) tables are in place
-    bool has_loop = false;                              // the CSR has a self loop (unit graphs: lists fixed up, wave kernel's lazy step off)
-    bool lanes_off = false;                             // PECANPY_AMD_NO_LANES was set when the handle was created: the index is
-                                                        // built (the wave kernel's lazy step reads it) but the lane kernel is not used
+    double index_build_ms = 0;                          // device time of all index KERNELS of pw_csr_create (event pairs around them)
+    double create_wall_ms = 0;                          // wall clock of pw_csr_create: runtime start-up, host passes, H2D, allocations, kernels
+    uint64_t thr_version = 0;                           // thresholds uploaded (pw_graph_set_thresholds calls)
     float *d_tot_e = nullptr, *d_tot_v = nullptr;       // weighted CSR graphs: per-edge / per-vertex normalisers
+    double tot_p = 0, tot_q = 0;                        // ... built for these parameters
+    int tot_extend = -1;                                // -1: none yet
+    uint64_t tot_thr_version = 0;                       // thresholds uploaded since the table was built?
+    bool tot_failed = false;
+    double tot_build_ms = 0;
     float *d_utot = nullptr;                            // unit graphs, 1/p or 1/q not a power of two: row total per arriving line
     float utot_wo = 0, utot_wp = 0;                     // ... built for these biases (0: none)
     bool utot_failed = false;
@@ -140,23 +156,52 @@ struct pw_graph {
     int wl_extend = -1;
     uint64_t wl_thr_version = 0;
     bool wl_failed = false;
+    int spp_zero = -1;                                  // CSR: some stored weight is 0.0f (-1: not checked yet)
+    // alias tables (PreComp modes)
+    DevBuf<uint64_t> alias_indptr;
+    DevBuf<uint32_t> alias_j, alias_s, alias_l, edge_row;
+    DevBuf<float> alias_q;
+    uint64_t n_alias = 0;
+    int alias_kind = -1;  // -1 none, 0 second order, 1 first order
+    double alias_p = 0, alias_q_param = 0;
+    int alias_extend = 0;
+
+    explicit GraphData(int dev) : device(dev) {}
+    GraphData(const GraphData &) = delete;
+    GraphData &operator=(const GraphData &) = delete;
+    ~GraphData() {
+        (void)hipSetDevice(device);
+        for (void *q : {(void *)d_indptr, (void *)d_indices, (void *)d_hasnbr, (void *)d_data, (void *)d_thr, (void *)d_adjbits,
+                        (void *)d_deg, (void *)d_foff, (void *)d_fbits, (void *)d_kf, (void *)d_tab_off, (void *)d_slots, (void *)d_vrec,
+                        (void *)d_lines, (void *)d_clist, (void *)d_tot_e, (void *)d_tot_v, (void *)d_utot, (void *)d_wb, (void *)d_wpq,
+                        (void *)d_wdl, (void *)d_wl_dprev, (void *)d_wl_off, (void *)d_wedge_row, (void *)d_wp1, (void *)d_wck_off,
+                        (void *)d_wck})
+            if (q) (void)hipFree(q);
+        alias_indptr.release();
+        alias_j.release();
+        alias_s.release();
+        alias_l.release();
+        edge_row.release();
+        alias_q.release();
+    }
+};
+
+// A call context over a graph: streams, events, counters, random stream and scratch buffers, and the flags of the
+// current call.  The graph itself (gd) may be shared with a twin context.
+struct pw_graph {
+    int device = 0;
+    std::shared_ptr<GraphData> gd;
+    // TWIN (round 6): a second call context on the SAME device over the same GraphData (own streams, counters, queues, stream
+    // buffers): the weighted lane form walks the two halves of a job array on the two contexts side by side, so that one half's
+    // eager kernel runs beside the other half's lane round (simulate_twin)
+    pw_graph *twin = nullptr;
+    bool twin_active = false;                           // the current call runs on both contexts: each takes a share of the GPU
+    std::function<void()> on_tables_ready;              // simulate_twin: called once the call's per-(p, q) tables are in place
     bool wl_active = false;                             // the current call may run the weighted lane form (tables are there)
     bool call_n2vpp = false;                            // the current call walks node2vec++ (walk_dense_w.hip.h)
     bool call_spp = false;                              // ... node2vec++ on this CSR handle (walk_sparse_pp.hip.h)
-    int spp_zero = -1;                                  // CSR: some stored weight is 0.0f (-1: not checked yet)
     bool wl_used = false;                               // ... and did
-    double tot_p = 0, tot_q = 0;                        // ... built for these parameters
-    int tot_extend = -1;                                // -1: none yet
-    uint64_t tot_thr_version = 0, thr_version = 0;      // thresholds uploaded since the table was built?
-    bool tot_failed = false;
-    double tot_build_ms = 0;
     double param_ms_call = 0;                           // (p, q)-dependent index time of the current call
-    uint64_t n_clist = 0;
-    uint32_t list_max_len = 0xffffffffu;                // partial index: lists longer than this were left out (EL_NO_LIST)
-    double index_build_ms = 0;                          // device time of all index KERNELS of pw_csr_create (event pairs around them)
-    double create_wall_ms = 0;                          // wall clock of pw_csr_create: runtime start-up, host passes, H2D, allocations, kernels
-    uint64_t index_bytes = 0;                           // device bytes of the membership / lane index
-    uint32_t words_per_row = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;   // side stream: the zero-fill of the walk matrix runs under the stream expansion
     hipEvent_t ev_side = nullptr;
@@ -192,14 +237,7 @@ struct pw_graph {
     DevBuf<uint32_t> jump_tmp;    // partial results of jumps whose taps are split over several workgroups (kept zeroed)
     bool jump_table_ready = false;
     DevBuf<unsigned long long> counters;  // [0] job counter [1..4] stats [5] changed count
-    // alias tables (PreComp modes)
-    DevBuf<uint64_t> alias_indptr;
-    DevBuf<uint32_t> alias_j, alias_s, alias_l, edge_row;
-    DevBuf<float> alias_q, probs_scratch;
-    uint64_t n_alias = 0;
-    int alias_kind = -1;  // -1 none, 0 second order, 1 first order
-    double alias_p = 0, alias_q_param = 0;
-    int alias_extend = 0;
+    DevBuf<float> probs_scratch;
 };
 
 namespace {
@@ -283,34 +321,6 @@ PW_EXPORT void pw_graph_destroy(pw_graph *g) {
     if (!g) return;
     if (g->twin) { pw_graph_destroy(g->twin); g->twin = nullptr; }
     (void)hipSetDevice(g->device);
-    if (g->alias) {   // the graph, its index and the per-(p, q) tables belong to the handle this one aliases
-        g->d_indptr = g->d_indices = nullptr; g->d_data = nullptr; g->d_thr = nullptr; g->d_adjbits = nullptr; g->d_deg = nullptr;
-        g->d_foff = nullptr; g->d_fbits = nullptr; g->d_kf = nullptr; g->d_tab_off = nullptr; g->d_slots = nullptr; g->d_vrec = nullptr;
-        g->d_lines = nullptr; g->d_clist = nullptr; g->d_tot_e = nullptr; g->d_tot_v = nullptr; g->d_utot = nullptr; g->d_hasnbr = nullptr;
-        g->d_wb = nullptr; g->d_wpq = nullptr; g->d_wdl = nullptr; g->d_wl_dprev = nullptr; g->d_wl_off = nullptr; g->d_wedge_row = nullptr;
-        g->d_wp1 = nullptr; g->d_wck_off = nullptr; g->d_wck = nullptr;
-    }
-    if (g->d_indptr) (void)hipFree(g->d_indptr);
-    if (g->d_indices) (void)hipFree(g->d_indices);
-    if (g->d_data) (void)hipFree(g->d_data);
-    if (g->d_thr) (void)hipFree(g->d_thr);
-    if (g->d_adjbits) (void)hipFree(g->d_adjbits);
-    if (g->d_deg) (void)hipFree(g->d_deg);
-    if (g->d_foff) (void)hipFree(g->d_foff);
-    if (g->d_fbits) (void)hipFree(g->d_fbits);
-    if (g->d_kf) (void)hipFree(g->d_kf);
-    if (g->d_tab_off) (void)hipFree(g->d_tab_off);
-    if (g->d_slots) (void)hipFree(g->d_slots);
-    if (g->d_vrec) (void)hipFree(g->d_vrec);
-    if (g->d_lines) (void)hipFree(g->d_lines);
-    if (g->d_clist) (void)hipFree(g->d_clist);
-    if (g->d_tot_e) (void)hipFree(g->d_tot_e);
-    if (g->d_utot) (void)hipFree(g->d_utot);
-    if (g->d_hasnbr) (void)hipFree(g->d_hasnbr);
-    if (g->d_tot_v) (void)hipFree(g->d_tot_v);
-    for (void *q : {(void *)g->d_wb, (void *)g->d_wpq, (void *)g->d_wdl, (void *)g->d_wl_dprev, (void *)g->d_wl_off, (void *)g->d_wedge_row, (void *)g->d_wp1,
-                    (void *)g->d_wck_off, (void *)g->d_wck})
-        if (q) (void)hipFree(q);
     g->redo.release();
     g->susp[0].release();
     g->susp[1].release();
@@ -326,12 +336,6 @@ PW_EXPORT void pw_graph_destroy(pw_graph *g) {
     g->jump_tmp.release();
     g->changed.release();
     g->counters.release();
-    g->alias_indptr.release();
-    g->alias_j.release();
-    g->alias_s.release();
-    g->alias_l.release();
-    g->edge_row.release();
-    g->alias_q.release();
     g->probs_scratch.release();
     for (auto &b : g->stage)
         if (b) (void)hipHostFree(b);
@@ -346,10 +350,12 @@ PW_EXPORT void pw_graph_destroy(pw_graph *g) {
     if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
     if (g->stream2) (void)hipStreamDestroy(g->stream2);
     if (g->stream) (void)hipStreamDestroy(g->stream);
+    g->gd.reset();   // (the graph goes with the last context that walks it)
     delete g;
 }
 
-static int graph_common_init(pw_graph *g, int device) {
+// a call context on `device` over `gd` (a twin's: the primary's graph) or over a new, empty graph
+static int graph_common_init(pw_graph *g, int device, std::shared_ptr<GraphData> gd = nullptr) {
     const bool dbg = getenv("PECANPY_AMD_CREATE_DEBUG") != nullptr;
     auto nowms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = nowms();
@@ -358,6 +364,7 @@ static int graph_common_init(pw_graph *g, int device) {
     if (n <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
     if (device < 0 || device >= n) return fail(PW_ERR_INVALID, "device index out of range");
     g->device = device;
+    g->gd = gd ? std::move(gd) : std::make_shared<GraphData>(device);
     HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -453,14 +460,14 @@ static void make_lane_work_items(const uint32_t *indptr, const uint32_t *indices
     });
 }
 
-// device time of a group of index kernels: g->ev[2] / g->ev[3] around it, added to g->index_build_ms once it has run
+// device time of a group of index kernels: g->ev[2] / g->ev[3] around it, added to g->gd->index_build_ms once it has run
 #define INDEX_KERNELS_BEGIN(g) (void)hipEventRecord((g)->ev[2], (g)->stream)
 #define INDEX_KERNELS_END(g)                                                                                     \
     do {                                                                                                         \
         (void)hipEventRecord((g)->ev[3], (g)->stream);                                                           \
         if (hipEventSynchronize((g)->ev[3]) == hipSuccess) {                                                     \
             float ms_ = 0;                                                                                       \
-            if (hipEventElapsedTime(&ms_, (g)->ev[2], (g)->ev[3]) == hipSuccess) (g)->index_build_ms += ms_;     \
+            if (hipEventElapsedTime(&ms_, (g)->ev[2], (g)->ev[3]) == hipSuccess) (g)->gd->index_build_ms += ms_; \
         }                                                                                                        \
     } while (0)
 
@@ -468,10 +475,10 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
                             uint64_t pre_bytes = 0) {
     // (pre_lines: the edge lines' memory, allocated by pw_csr_create's helper thread beside the host pass and the first kernels
     //  -- device memory a fresh box hands out for the first time costs up to ~25 ms per GB of hipMalloc; owned by g from here on)
-    if (pre_lines) g->d_lines = (pw::ELine *)pre_lines;
-    auto no_index = [&]() { if (g->d_lines) { (void)hipFree(g->d_lines); g->d_lines = nullptr; } return 0; };
-    if (!g->nnz) return no_index();
-    const uint32_t nnz = g->nnz, n_nodes = g->n_nodes;
+    if (pre_lines) g->gd->d_lines = (pw::ELine *)pre_lines;
+    auto no_index = [&]() { if (g->gd->d_lines) { (void)hipFree(g->gd->d_lines); g->gd->d_lines = nullptr; } return 0; };
+    if (!g->gd->nnz) return no_index();
+    const uint32_t nnz = g->gd->nnz, n_nodes = g->gd->n_nodes;
     const bool dbg = getenv("PECANPY_AMD_CREATE_DEBUG") != nullptr;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_last = now();
@@ -492,8 +499,8 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     (void)hipMemGetInfo(&free_b, &total_b);
     stamp("hipMemGetInfo");
     const uint64_t line_bytes = (uint64_t)n_lines * sizeof(pw::ELine) + 64;
-    if (g->d_lines && pre_bytes != line_bytes) no_index();   // (cannot happen: the same formula sized it)
-    if (!g->d_lines && line_bytes > free_b / 2) return 0;
+    if (g->gd->d_lines && pre_bytes != line_bytes) no_index();   // (cannot happen: the same formula sized it)
+    if (!g->gd->d_lines && line_bytes > free_b / 2) return 0;
     pw::LaneBuildItem *d_small = nullptr, *d_large = nullptr;
     uint32_t *d_segcnt = nullptr;
     uint64_t *d_tiles = nullptr, *d_etiles = nullptr;
@@ -507,14 +514,14 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     };
     auto drop = [&](int rc) {   // no lane index
         cleanup();
-        if (g->d_lines) (void)hipFree(g->d_lines);
-        if (g->d_clist) (void)hipFree(g->d_clist);
-        g->d_lines = nullptr;
-        g->d_clist = nullptr;
+        if (g->gd->d_lines) (void)hipFree(g->gd->d_lines);
+        if (g->gd->d_clist) (void)hipFree(g->gd->d_clist);
+        g->gd->d_lines = nullptr;
+        g->gd->d_clist = nullptr;
         (void)hipGetLastError();
         return rc;
     };
-    hipError_t e = g->d_lines ? hipSuccess : hipMalloc((void **)&g->d_lines, line_bytes);
+    hipError_t e = g->gd->d_lines ? hipSuccess : hipMalloc((void **)&g->gd->d_lines, line_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&d_small, sizeof(pw::LaneBuildItem) * (small.size() + 1));
     if (e == hipSuccess) e = hipMalloc((void **)&d_large, sizeof(pw::LaneBuildItem) * (large.size() + 1));
     if (e == hipSuccess) e = hipMalloc((void **)&d_segcnt, sizeof(uint32_t) * (size_t)(segcnt_total + 1));
@@ -528,9 +535,9 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     stamp("hipMalloc + item upload");
     pw::CsrDev c = csr_dev(g);
     pw::LaneBuildArgs ba;
-    ba.indptr = g->d_indptr;
-    ba.indices = g->d_indices;
-    ba.lines = g->d_lines;
+    ba.indptr = g->gd->d_indptr;
+    ba.indices = g->gd->d_indices;
+    ba.lines = g->gd->d_lines;
     ba.clist = nullptr;
     ba.segcnt = d_segcnt;
     ba.max_len = 0xffffffffu;
@@ -539,8 +546,8 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     ba.seglo = nullptr;
     ba.logged = 0;
     INDEX_KERNELS_BEGIN(g);
-    hipLaunchKernelGGL(pw::eline_init_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, c, d_edge_row, g->d_lines);
-    if (vlines) hipLaunchKernelGGL(pw::vline_init_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, c, g->d_lines);
+    hipLaunchKernelGGL(pw::eline_init_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, c, d_edge_row, g->gd->d_lines);
+    if (vlines) hipLaunchKernelGGL(pw::vline_init_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, c, g->gd->d_lines);
     const unsigned vgrid = (unsigned)(((uint64_t)n_nodes * pw::WAVE + 255) / 256);
     // LOGGED build (round 5; walk_lanes.hip.h: LaneBuildArgs): the COUNT pass keeps its matches in a log -- one block of d_k
     // four-byte slots per pair, the pair's upper bound: 50 GB of address space at RMAT-22 of which the matches touch 5 -- and
@@ -558,10 +565,10 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     if (env_on("PECANPY_AMD_INDEX_LOGGED") && !has_loop) {   // (self loops: the two-pass build)
         e = hipMalloc((void **)&d_logoff, sizeof(unsigned long long) * ((size_t)nnz + 1));
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pw::log_tile_sums_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, g->d_indptr,
+            hipLaunchKernelGGL(pw::log_tile_sums_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, g->gd->d_indptr,
                                d_edge_row, nnz, d_tiles);
             hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, nnz_tiles);
-            hipLaunchKernelGGL(pw::log_offsets_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, g->d_indptr,
+            hipLaunchKernelGGL(pw::log_offsets_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, g->gd->d_indptr,
                                d_edge_row, nnz, d_tiles, d_logoff);
             e = hipMemcpyAsync(&log_slots, d_tiles + nnz_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
         }
@@ -606,17 +613,17 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
             else hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, false>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, d_small);
         }
         if (vlines) {
-            if (fill) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->d_lines, g->d_clist);
-            else hipLaunchKernelGGL(pw::vline_lists_kernel<false>, dim3(vgrid), dim3(256), 0, g->stream, c, g->d_lines, (uint8_t *)nullptr);
+            if (fill) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines, g->gd->d_clist);
+            else hipLaunchKernelGGL(pw::vline_lists_kernel<false>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines, (uint8_t *)nullptr);
         }
     };
     lists(false);
     uint64_t units = 0, entries = 0;
     auto offsets = [&](uint32_t max_len) -> hipError_t {   // list offsets (16-byte units) of the lists of at most max_len entries
-        hipLaunchKernelGGL(pw::clist_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, n_lines, nnz, d_tiles, d_etiles, max_len);
+        hipLaunchKernelGGL(pw::clist_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, n_lines, nnz, d_tiles, d_etiles, max_len);
         hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
         hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_etiles, n_tiles);
-        hipLaunchKernelGGL(pw::clist_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, n_lines, d_tiles, max_len);
+        hipLaunchKernelGGL(pw::clist_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, n_lines, d_tiles, max_len);
         hipError_t e2 = hipGetLastError();
         if (e2 == hipSuccess) e2 = hipMemcpyAsync(&units, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
         if (e2 == hipSuccess) e2 = hipMemcpyAsync(&entries, d_etiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
@@ -645,7 +652,7 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
         if (e == hipSuccess) {
             INDEX_KERNELS_BEGIN(g);
             hipLaunchKernelGGL(pw::clist_length_hist_kernel, dim3((unsigned)(((uint64_t)n_lines + 255) / 256)), dim3(256), 0, g->stream,
-                               g->d_lines, n_lines, d_hist, HL);
+                               g->gd->d_lines, n_lines, d_hist, HL);
             e = hipGetLastError();
             INDEX_KERNELS_END(g);
         }
@@ -670,16 +677,16 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     const uint64_t list_bytes = units * 16 + 64;
     if (units >= 0xffffffffull || list_bytes > free_b - free_b / 8) return drop(0);
     if (has_loop && max_len != 0xffffffffu) return drop(0);   // (loop_fix_kernel edits stored lists: no partial index with self loops)
-    e = hipMalloc((void **)&g->d_clist, list_bytes);
+    e = hipMalloc((void **)&g->gd->d_clist, list_bytes);
     if (e != hipSuccess) return drop(e == hipErrorOutOfMemory ? 0 : fail(PW_ERR_HIP, std::string("lane index (lists): ") + hipGetErrorString(e)));
     stamp("hipMalloc of the lists");
-    ba.clist = g->d_clist;
+    ba.clist = g->gd->d_clist;
     ba.max_len = max_len;
     INDEX_KERNELS_BEGIN(g);
     if (logged) {   // the logged matches to their places; the FILL pass is left with the pairs of rows beyond 65536 entries
         hipLaunchKernelGGL(pw::lane_scatter_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, ba, d_edge_row, d_vm0, nnz);
         ba.logged = 1u;
-        if (vlines) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->d_lines, g->d_clist);
+        if (vlines) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines, g->gd->d_clist);
     } else
     lists(true);
     unsigned long long loop_removed = 0;
@@ -692,9 +699,9 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
         if (e == hipSuccess) e = hipMemsetAsync(d_self, 0, sizeof(uint32_t) * words, g->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, sizeof(unsigned long long), g->stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pw::self_loop_bits_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, g->d_indptr, g->d_indices, n_nodes, d_self);
+            hipLaunchKernelGGL(pw::self_loop_bits_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->d_indices, n_nodes, d_self);
             hipLaunchKernelGGL(pw::loop_fix_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, d_edge_row,
-                               (const uint32_t *)d_self, g->d_lines, g->d_clist, nnz, d_removed);
+                               (const uint32_t *)d_self, g->gd->d_lines, g->gd->d_clist, nnz, d_removed);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(&loop_removed, d_removed, sizeof(loop_removed), hipMemcpyDeviceToHost, g->stream);
@@ -707,7 +714,7 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
         const uint32_t first = logged ? nnz : 0u;
         if (n_lines > first)
             hipLaunchKernelGGL(pw::eline_pivots_kernel, dim3((unsigned)(((uint64_t)(n_lines - first) + 255) / 256)), dim3(256), 0, g->stream,
-                               g->d_lines, g->d_clist, n_lines, first);
+                               g->gd->d_lines, g->gd->d_clist, n_lines, first);
     }
     e = hipGetLastError();
     INDEX_KERNELS_END(g);
@@ -716,12 +723,12 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     stamp("fill pass + pivots");
     cleanup();
     stamp("hipFree of the scratch");
-    g->n_clist = entries - loop_removed;
-    g->list_max_len = max_len;
-    g->vlines = vlines;
-    g->clist_bytes = list_bytes;
-    g->line_bytes = line_bytes;
-    g->index_bytes += line_bytes + list_bytes;
+    g->gd->n_clist = entries - loop_removed;
+    g->gd->list_max_len = max_len;
+    g->gd->vlines = vlines;
+    g->gd->clist_bytes = list_bytes;
+    g->gd->line_bytes = line_bytes;
+    g->gd->index_bytes += line_bytes + list_bytes;
     return 0;
 }
 
@@ -797,9 +804,9 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
             });
         } catch (const std::system_error &) {}   // (thread limit: build_lane_index allocates)
     }
-    g->kind = 0;
-    g->n_nodes = n_nodes;
-    g->nnz = nnz;
+    g->gd->kind = 0;
+    g->gd->n_nodes = n_nodes;
+    g->gd->nnz = nnz;
     // O(n_nodes) host pass: monotone offsets, maximum degree, sizes of the per-row filters and index tables
     std::vector<uint32_t> foff((size_t)n_nodes + 1);
     std::vector<uint64_t> off((size_t)n_nodes + 1);
@@ -822,7 +829,7 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
     if ((trun >> 1) > 0xffffffffull) { pw_graph_destroy(g); return fail(PW_ERR_INVALID, "graph too large for 32-bit index offsets"); }
     foff[n_nodes] = (uint32_t)frun;
     off[n_nodes] = trun;
-    g->max_degree = md;
+    g->gd->max_degree = md;
     auto up = [&](void **dst, const void *src, size_t bytes) -> int {
         HIP_TRY(hipMalloc(dst, bytes ? bytes : 4));
         if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -831,7 +838,7 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
     // the CSR arrays, uploaded by the helper thread meanwhile (the lines' allocation may still be running: joined further down)
     if (pre.t_up.joinable()) pre.t_up.join();
     if (pre.err != hipSuccess) { pw_graph_destroy(g); return fail(pre.err == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("CSR upload: ") + hipGetErrorString(pre.err)); }
-    g->d_indptr = (uint32_t *)pre.indptr; g->d_indices = (uint32_t *)pre.indices; g->d_data = pre.data;
+    g->gd->d_indptr = (uint32_t *)pre.indptr; g->gd->d_indices = (uint32_t *)pre.indices; g->gd->d_data = pre.data;
     pre.csr_taken = true;
     stamp("host pass + H2D of the CSR");
 
@@ -849,12 +856,12 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
     if (e == hipSuccess) e = hipMalloc((void **)&d_flags, 5 * sizeof(unsigned long long));
     unsigned long long h_flags[5] = {~0ull, ~0ull, 0ull, 0ull, 0ull};
     if (e == hipSuccess) e = hipMemcpyAsync(d_flags, h_flags, sizeof(h_flags), hipMemcpyHostToDevice, g->stream);
-    g->index_build_ms = 0;
+    g->gd->index_build_ms = 0;
     INDEX_KERNELS_BEGIN(g);
     if (e == hipSuccess && nnz) {
-        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->d_indptr, n_nodes, d_edge_row);
+        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr, n_nodes, d_edge_row);
         hipLaunchKernelGGL(pw::csr_validate_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream,
-                           g->d_indptr, g->d_indices, (const float *)g->d_data, d_edge_row, n_nodes, nnz, d_flags);
+                           g->gd->d_indptr, g->gd->d_indices, (const float *)g->gd->d_data, d_edge_row, n_nodes, nnz, d_flags);
         e = hipGetLastError();
     }
     INDEX_KERNELS_END(g);
@@ -875,8 +882,8 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
                                         "as the reference's to_csr produces them (graph.py:336)");
     }
     stamp("validation kernels");
-    g->unit = !(data && h_flags[2]);
-    if (g->unit && g->d_data) { (void)hipFree(g->d_data); g->d_data = nullptr; }   // unit weights are never read
+    g->gd->unit = !(data && h_flags[2]);
+    if (g->gd->unit && g->gd->d_data) { (void)hipFree(g->gd->d_data); g->gd->d_data = nullptr; }   // unit weights are never read
     const bool has_loop = h_flags[3] != 0;
     // A negative, NaN or infinite weight: the reference turns it into meaningless "probabilities" (w / w.sum(), cumsum, searchsorted:
     // pecanpy.py:556-557) without complaint; the exact scans here (wave kernel: monotone partial sums; weighted lane form: a float64
@@ -886,39 +893,39 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
         return bail(PW_ERR_INVALID, "edge weights must be finite and >= 0 (a negative, NaN or infinite weight makes the reference's "
                                     "transition probabilities w / w.sum() meaningless; this library does not reproduce them)");
 
-    rc = up((void **)&g->d_foff, foff.data(), sizeof(uint32_t) * foff.size());
-    if (!rc) rc = up((void **)&g->d_tab_off, off.data(), sizeof(uint64_t) * off.size());
+    rc = up((void **)&g->gd->d_foff, foff.data(), sizeof(uint32_t) * foff.size());
+    if (!rc) rc = up((void **)&g->gd->d_tab_off, off.data(), sizeof(uint64_t) * off.size());
     if (rc) { if (d_edge_row) (void)hipFree(d_edge_row); (void)hipFree(d_flags); pw_graph_destroy(g); return rc; }
-    e = hipMalloc((void **)&g->d_fbits, sizeof(uint64_t) * (frun ? frun : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->d_kf, sizeof(uint2) * (size_t)(nnz ? nnz : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->d_slots, sizeof(uint64_t) * (trun ? trun : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->d_vrec, sizeof(uint4) * ((size_t)n_nodes + 1));
-    if (e == hipSuccess) e = hipMemsetAsync(g->d_fbits, 0, sizeof(uint64_t) * (frun ? frun : 1), g->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(g->d_slots, 0xff, sizeof(uint64_t) * (trun ? trun : 1), g->stream);
+    e = hipMalloc((void **)&g->gd->d_fbits, sizeof(uint64_t) * (frun ? frun : 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_kf, sizeof(uint2) * (size_t)(nnz ? nnz : 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_slots, sizeof(uint64_t) * (trun ? trun : 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_vrec, sizeof(uint4) * ((size_t)n_nodes + 1));
+    if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_fbits, 0, sizeof(uint64_t) * (frun ? frun : 1), g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_slots, 0xff, sizeof(uint64_t) * (trun ? trun : 1), g->stream);
     if (e != hipSuccess) return bail(PW_ERR_NOMEM, std::string("membership index: ") + hipGetErrorString(e));
-    g->index_bytes = sizeof(uint64_t) * (frun + trun) + sizeof(uint2) * (uint64_t)nnz + sizeof(uint4) * ((uint64_t)n_nodes + 1);
-    g->fbits_words = frun;
-    g->slot_words = trun;
+    g->gd->index_bytes = sizeof(uint64_t) * (frun + trun) + sizeof(uint2) * (uint64_t)nnz + sizeof(uint4) * ((uint64_t)n_nodes + 1);
+    g->gd->fbits_words = frun;
+    g->gd->slot_words = trun;
     INDEX_KERNELS_BEGIN(g);
-    hipLaunchKernelGGL(pw::vrec_build_kernel, dim3((n_nodes + 256) / 256), dim3(256), 0, g->stream, g->d_indptr, g->d_foff,
-                       g->d_tab_off, n_nodes, g->d_vrec);
+    hipLaunchKernelGGL(pw::vrec_build_kernel, dim3((n_nodes + 256) / 256), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->d_foff,
+                       g->gd->d_tab_off, n_nodes, g->gd->d_vrec);
     if (n_nodes && nnz)
         hipLaunchKernelGGL(pw::membership_build_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream,
-                           g->d_indptr, g->d_indices, d_edge_row, g->d_foff, g->d_tab_off, (unsigned long long *)g->d_fbits, g->d_kf,
-                           (unsigned long long *)g->d_slots, nnz, 4294967296.0 / (double)nnz);
+                           g->gd->d_indptr, g->gd->d_indices, d_edge_row, g->gd->d_foff, g->gd->d_tab_off, (unsigned long long *)g->gd->d_fbits, g->gd->d_kf,
+                           (unsigned long long *)g->gd->d_slots, nnz, 4294967296.0 / (double)nnz);
     e = hipGetLastError();
     INDEX_KERNELS_END(g);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("membership index build: ") + hipGetErrorString(e));
     stamp("membership index");
-    g->has_loop = has_loop;
-    if (nnz && (!has_loop || g->unit) && !getenv("PECANPY_AMD_NO_LAZY")) {   // (weighted graphs too: membership does not depend on the weights)
+    g->gd->has_loop = has_loop;
+    if (nnz && (!has_loop || g->gd->unit) && !getenv("PECANPY_AMD_NO_LAZY")) {   // (weighted graphs too: membership does not depend on the weights)
         // per-edge records and common-neighbour lists (lane kernel; lazy membership of the wave kernel).  SELF LOOPS (round 6):
         // unit-weight graphs keep the index -- prev's own position is taken out of the lists of the entries whose source has a
         // loop (loop_fix_kernel) -- and only the wave kernel's LAZY step, which counts common neighbours while it classifies
         // keys, stays off for them (launch_wave_walks); weighted graphs with self loops get no index, as before (the
         // node2vec+ tables pair the two directions' lists entry by entry, and the fix makes their lengths differ).
-        g->lanes_off = getenv("PECANPY_AMD_NO_LANES") != nullptr;
+        g->gd->lanes_off = getenv("PECANPY_AMD_NO_LANES") != nullptr;
         item_thread.join();
         if (pre.t_lines.joinable()) pre.t_lines.join();
         pre.lines_taken = pre.lines != nullptr;
@@ -927,10 +934,10 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
     }
     (void)hipStreamSynchronize(g->stream);
     stamp("lane index");
-    g->create_wall_ms = (now() - t_begin) * 1e3;
+    g->gd->create_wall_ms = (now() - t_begin) * 1e3;
     // a PARTIAL index keeps the source vertex of every CSR entry (4 bytes per entry): lanes_eager_kernel reads the vertex a
     // parked step came from there instead of bisecting indptr for it (22 dependent loads per step)
-    if (g->d_lines && g->list_max_len != 0xffffffffu && !g->d_wedge_row) g->d_wedge_row = d_edge_row;
+    if (g->gd->d_lines && g->gd->list_max_len != 0xffffffffu && !g->gd->d_wedge_row) g->gd->d_wedge_row = d_edge_row;
     else (void)hipFree(d_edge_row);
     (void)hipFree(d_flags);
     *out = g;
@@ -939,9 +946,9 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
 
 PW_EXPORT int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t *index_bytes, uint64_t *lane_list_entries) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    if (build_ms) *build_ms = g->index_build_ms;
-    if (index_bytes) *index_bytes = g->index_bytes;
-    if (lane_list_entries) *lane_list_entries = g->d_lines ? g->n_clist : 0;
+    if (build_ms) *build_ms = g->gd->index_build_ms;
+    if (index_bytes) *index_bytes = g->gd->index_bytes;
+    if (lane_list_entries) *lane_list_entries = g->gd->d_lines ? g->gd->n_clist : 0;
     return PW_OK;
 }
 
@@ -950,18 +957,18 @@ PW_EXPORT int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t 
 // in row v of the common neighbours.
 PW_EXPORT int pw_lane_index_export(pw_graph *g, uint32_t *n_in, uint32_t *rev_pos, uint32_t *entries) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    if (!g->d_lines) return fail(PW_ERR_UNSUPPORTED, "this graph has no lane index");
+    if (!g->gd->d_lines) return fail(PW_ERR_UNSUPPORTED, "this graph has no lane index");
     if (set_device(g)) return PW_ERR_HIP;
-    const uint32_t nnz = g->nnz;
+    const uint32_t nnz = g->gd->nnz;
     std::vector<pw::ELine> lines(nnz);
-    HIP_TRY(hipMemcpy(lines.data(), g->d_lines, sizeof(pw::ELine) * (size_t)nnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lines.data(), g->gd->d_lines, sizeof(pw::ELine) * (size_t)nnz, hipMemcpyDeviceToHost));
     std::vector<uint64_t> off((size_t)nnz + 1, 0);
     for (uint32_t e = 0; e < nnz; e++) {
         if (n_in) n_in[e] = lines[e].n_in;
         if (rev_pos) rev_pos[e] = lines[e].rev_pos;
         off[e + 1] = off[e] + lines[e].n_in;
     }
-    if (off[nnz] != g->n_clist) return fail(PW_ERR_HIP, "lane index: entry count mismatch");
+    if (off[nnz] != g->gd->n_clist) return fail(PW_ERR_HIP, "lane index: entry count mismatch");
     if (!entries || !off[nnz]) return PW_OK;
     uint64_t *d_off = nullptr;
     uint32_t *d_out = nullptr;
@@ -970,7 +977,7 @@ PW_EXPORT int pw_lane_index_export(pw_graph *g, uint32_t *n_in, uint32_t *rev_po
     if (e == hipSuccess) e = hipMemcpy(d_off, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pw::lane_index_export_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream,
-                           g->d_lines, g->d_clist, nnz, d_off, d_out);
+                           g->gd->d_lines, g->gd->d_clist, nnz, d_off, d_out);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
@@ -1013,28 +1020,28 @@ PW_EXPORT int pw_dense_create(const double *data, uint32_t n_nodes, int device, 
     pw_graph *g = new pw_graph();
     int rc = graph_common_init(g, device);
     if (rc) { pw_graph_destroy(g); return rc; }
-    g->kind = 1;
-    g->n_nodes = n_nodes;
-    g->nnz = (uint32_t)nnz;
-    g->unit = unit;
-    g->dense_nonneg = nonneg;
-    g->words_per_row = wpr;
+    g->gd->kind = 1;
+    g->gd->n_nodes = n_nodes;
+    g->gd->nnz = (uint32_t)nnz;
+    g->gd->unit = unit;
+    g->gd->dense_nonneg = nonneg;
+    g->gd->words_per_row = wpr;
     auto up = [&](void **dst, const void *src, size_t bytes) -> int {
         HIP_TRY(hipMalloc(dst, bytes ? bytes : 8));
         if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
         return 0;
     };
-    rc = up((void **)&g->d_indptr, indptr.data(), sizeof(uint32_t) * indptr.size());
-    if (!rc) rc = up((void **)&g->d_indices, cols.data(), sizeof(uint32_t) * cols.size());
-    if (!rc && !unit) rc = up((void **)&g->d_data, vals.data(), sizeof(double) * vals.size());
-    if (!rc) rc = up((void **)&g->d_adjbits, bits.data(), sizeof(uint64_t) * bits.size());
+    rc = up((void **)&g->gd->d_indptr, indptr.data(), sizeof(uint32_t) * indptr.size());
+    if (!rc) rc = up((void **)&g->gd->d_indices, cols.data(), sizeof(uint32_t) * cols.size());
+    if (!rc && !unit) rc = up((void **)&g->gd->d_data, vals.data(), sizeof(double) * vals.size());
+    if (!rc) rc = up((void **)&g->gd->d_adjbits, bits.data(), sizeof(uint64_t) * bits.size());
     if (!rc) {
         std::vector<uint32_t> deg(n);
         for (uint64_t i = 0; i < n; i++) {
             deg[i] = indptr[i + 1] - indptr[i];
-            if (deg[i] > g->max_degree) g->max_degree = deg[i];
+            if (deg[i] > g->gd->max_degree) g->gd->max_degree = deg[i];
         }
-        rc = up((void **)&g->d_deg, deg.data(), sizeof(uint32_t) * deg.size());
+        rc = up((void **)&g->gd->d_deg, deg.data(), sizeof(uint32_t) * deg.size());
     }
     if (rc) { pw_graph_destroy(g); return rc; }
     *out = g;
@@ -1049,35 +1056,35 @@ PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, in
     if (rc) { pw_graph_destroy(g); return rc; }
     const uint64_t n = n_nodes;
     const uint32_t wpr = (uint32_t)((n + 63) / 64);
-    g->kind = 1;
-    g->n_nodes = n_nodes;
-    g->unit = true;
-    g->bits_only = true;
-    g->words_per_row = wpr;
+    g->gd->kind = 1;
+    g->gd->n_nodes = n_nodes;
+    g->gd->unit = true;
+    g->gd->bits_only = true;
+    g->gd->words_per_row = wpr;
     const size_t bytes = sizeof(uint64_t) * (size_t)n * wpr;
-    hipError_t e = hipMalloc((void **)&g->d_adjbits, bytes);
+    hipError_t e = hipMalloc((void **)&g->gd->d_adjbits, bytes);
     // the copy must be ordered with the kernels of this handle's (non-blocking) stream
-    if (e == hipSuccess) e = hipMemcpyAsync(g->d_adjbits, adjbits, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->gd->d_adjbits, adjbits, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->d_deg, sizeof(uint32_t) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_deg, sizeof(uint32_t) * n);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::dense_degree_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->d_adjbits, n_nodes, wpr, g->d_deg);
+        hipLaunchKernelGGL(pw::dense_degree_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_adjbits, n_nodes, wpr, g->gd->d_deg);
         e = hipGetLastError();
     }
     std::vector<uint32_t> deg(n), indptr(n + 1, 0);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess) e = hipMemcpy(deg.data(), g->d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(deg.data(), g->gd->d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
     uint64_t nnz = 0;
     for (uint64_t i = 0; i < n; i++) {
         nnz += deg[i];
         if (nnz >= 0xffffffffull) { pw_graph_destroy(g); return fail(PW_ERR_INVALID, "dense graph has more than 2^32-1 edges"); }
         indptr[i + 1] = (uint32_t)nnz;
-        if (deg[i] > g->max_degree) g->max_degree = deg[i];
+        if (deg[i] > g->gd->max_degree) g->gd->max_degree = deg[i];
     }
-    g->nnz = (uint32_t)nnz;
-    e = hipMalloc((void **)&g->d_indptr, sizeof(uint32_t) * (n + 1));   // only used for stream offsets
-    if (e == hipSuccess) e = hipMemcpy(g->d_indptr, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice);
+    g->gd->nnz = (uint32_t)nnz;
+    e = hipMalloc((void **)&g->gd->d_indptr, sizeof(uint32_t) * (n + 1));   // only used for stream offsets
+    if (e == hipSuccess) e = hipMemcpy(g->gd->d_indptr, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice);
     if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
     *out = g;
     return PW_OK;
@@ -1086,9 +1093,9 @@ PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, in
 PW_EXPORT int pw_graph_set_thresholds(pw_graph *g, const float *thr) {
     if (!g || !thr) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
-    if (!g->d_thr) HIP_TRY(hipMalloc((void **)&g->d_thr, sizeof(float) * (size_t)g->n_nodes));
-    HIP_TRY(hipMemcpy(g->d_thr, thr, sizeof(float) * (size_t)g->n_nodes, hipMemcpyHostToDevice));
-    g->thr_version++;
+    if (!g->gd->d_thr) HIP_TRY(hipMalloc((void **)&g->gd->d_thr, sizeof(float) * (size_t)g->gd->n_nodes));
+    HIP_TRY(hipMemcpy(g->gd->d_thr, thr, sizeof(float) * (size_t)g->gd->n_nodes, hipMemcpyHostToDevice));
+    g->gd->thr_version++;
     return PW_OK;
 }
 
@@ -1101,29 +1108,26 @@ PW_EXPORT int pw_graph_replicate(const pw_graph *src, int device, pw_graph **out
     pw_graph *g = new pw_graph();
     int rc = graph_common_init(g, device);
     if (rc) { pw_graph_destroy(g); return rc; }
-    g->kind = src->kind; g->n_nodes = src->n_nodes; g->nnz = src->nnz; g->unit = src->unit; g->max_degree = src->max_degree;
-    g->bits_only = src->bits_only; g->dense_nonneg = src->dense_nonneg; g->words_per_row = src->words_per_row; g->has_loop = src->has_loop; g->lanes_off = src->lanes_off;
-    g->vlines = src->vlines; g->clist_bytes = src->clist_bytes; g->line_bytes = src->line_bytes; g->fbits_words = src->fbits_words;
-    g->slot_words = src->slot_words; g->n_clist = src->n_clist; g->list_max_len = src->list_max_len; g->index_bytes = src->index_bytes;
-    g->thr_version = src->d_thr ? 1 : 0;
-    const uint64_t n = src->n_nodes, nnz = src->nnz;
-    const bool rows = !src->bits_only;   // (dense graphs created from packed bits have no compressed rows)
+    static_cast<GraphDesc &>(*g->gd) = *src->gd;
+    g->gd->thr_version = src->gd->d_thr ? 1 : 0;
+    const uint64_t n = src->gd->n_nodes, nnz = src->gd->nnz;
+    const bool rows = !src->gd->bits_only;   // (dense graphs created from packed bits have no compressed rows)
     struct Buf { void **dst; const void *from; uint64_t bytes; };
     const Buf bufs[] = {
-        {(void **)&g->d_indptr, src->d_indptr, sizeof(uint32_t) * (n + 1)},
-        {(void **)&g->d_indices, src->d_indices, rows ? sizeof(uint32_t) * nnz : 0},
-        {(void **)&g->d_data, src->d_data, (src->kind == 0 ? sizeof(float) : sizeof(double)) * nnz},
-        {(void **)&g->d_thr, src->d_thr, sizeof(float) * n},
-        {(void **)&g->d_adjbits, src->d_adjbits, sizeof(uint64_t) * n * src->words_per_row},
-        {(void **)&g->d_deg, src->d_deg, sizeof(uint32_t) * n},
-        {(void **)&g->d_foff, src->d_foff, sizeof(uint32_t) * (n + 1)},
-        {(void **)&g->d_fbits, src->d_fbits, sizeof(uint64_t) * src->fbits_words},
-        {(void **)&g->d_kf, src->d_kf, sizeof(uint2) * nnz},
-        {(void **)&g->d_tab_off, src->d_tab_off, sizeof(uint64_t) * (n + 1)},
-        {(void **)&g->d_slots, src->d_slots, sizeof(uint64_t) * src->slot_words},
-        {(void **)&g->d_vrec, src->d_vrec, sizeof(uint4) * (n + 1)},
-        {(void **)&g->d_lines, src->d_lines, src->line_bytes},
-        {(void **)&g->d_clist, src->d_clist, src->clist_bytes},
+        {(void **)&g->gd->d_indptr, src->gd->d_indptr, sizeof(uint32_t) * (n + 1)},
+        {(void **)&g->gd->d_indices, src->gd->d_indices, rows ? sizeof(uint32_t) * nnz : 0},
+        {(void **)&g->gd->d_data, src->gd->d_data, (src->gd->kind == 0 ? sizeof(float) : sizeof(double)) * nnz},
+        {(void **)&g->gd->d_thr, src->gd->d_thr, sizeof(float) * n},
+        {(void **)&g->gd->d_adjbits, src->gd->d_adjbits, sizeof(uint64_t) * n * src->gd->words_per_row},
+        {(void **)&g->gd->d_deg, src->gd->d_deg, sizeof(uint32_t) * n},
+        {(void **)&g->gd->d_foff, src->gd->d_foff, sizeof(uint32_t) * (n + 1)},
+        {(void **)&g->gd->d_fbits, src->gd->d_fbits, sizeof(uint64_t) * src->gd->fbits_words},
+        {(void **)&g->gd->d_kf, src->gd->d_kf, sizeof(uint2) * nnz},
+        {(void **)&g->gd->d_tab_off, src->gd->d_tab_off, sizeof(uint64_t) * (n + 1)},
+        {(void **)&g->gd->d_slots, src->gd->d_slots, sizeof(uint64_t) * src->gd->slot_words},
+        {(void **)&g->gd->d_vrec, src->gd->d_vrec, sizeof(uint4) * (n + 1)},
+        {(void **)&g->gd->d_lines, src->gd->d_lines, src->gd->line_bytes},
+        {(void **)&g->gd->d_clist, src->gd->d_clist, src->gd->clist_bytes},
     };
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e = hipSuccess;
@@ -1138,8 +1142,8 @@ PW_EXPORT int pw_graph_replicate(const pw_graph *src, int device, pw_graph **out
         pw_graph_destroy(g);
         return fail(e == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("pw_graph_replicate: ") + hipGetErrorString(e));
     }
-    g->create_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g->index_build_ms = 0;     // (nothing was built here)
+    g->gd->create_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g->gd->index_build_ms = 0;     // (nothing was built here)
     *out = g;
     return PW_OK;
 }
@@ -1191,10 +1195,10 @@ static int compute_offsets(pw_graph *g, const uint32_t *d_starts, const uint32_t
     if (g->stream_off.ensure(n_all + 1)) return PW_ERR_NOMEM;
     if (g->tile_sums.ensure((n_all + pw::SCAN_TILE - 1) / pw::SCAN_TILE + 1)) return PW_ERR_NOMEM;
     if (track_changes && g->changed.ensure(n_all)) return PW_ERR_NOMEM;
-    if (!g->d_hasnbr) {
-        const uint32_t words = (g->n_nodes + 31u) / 32u;
-        HIP_TRY(hipMalloc((void **)&g->d_hasnbr, sizeof(uint32_t) * (size_t)(words ? words : 1)));
-        hipLaunchKernelGGL(pw::has_nbr_bits_kernel, dim3((words + 255) / 256 ? (words + 255) / 256 : 1), dim3(256), 0, g->stream, g->d_indptr, g->n_nodes, g->d_hasnbr);
+    if (!g->gd->d_hasnbr) {
+        const uint32_t words = (g->gd->n_nodes + 31u) / 32u;
+        HIP_TRY(hipMalloc((void **)&g->gd->d_hasnbr, sizeof(uint32_t) * (size_t)(words ? words : 1)));
+        hipLaunchKernelGGL(pw::has_nbr_bits_kernel, dim3((words + 255) / 256 ? (words + 255) / 256 : 1), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->n_nodes, g->gd->d_hasnbr);
     }
     const uint32_t *w_starts = d_starts + j0;
     const uint32_t *w_walks = d_walks ? d_walks + j0 * ((uint64_t)L + 2) : nullptr;
@@ -1203,10 +1207,10 @@ static int compute_offsets(pw_graph *g, const uint32_t *d_starts, const uint32_t
     unsigned long long *fm = first_mismatch ? g->counters.p + 14 : nullptr;
     if (fm) HIP_TRY(hipMemsetAsync(fm, 0xff, sizeof(unsigned long long), g->stream));
     hipLaunchKernelGGL(pw::draws_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream,
-                       g->d_hasnbr, w_starts, w_walks, L, n_jobs, g->tile_sums.p);
+                       g->gd->d_hasnbr, w_starts, w_walks, L, n_jobs, g->tile_sums.p);
     hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, g->tile_sums.p, n_tiles);
     hipLaunchKernelGGL(pw::draws_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream,
-                       g->d_hasnbr, w_starts, w_walks, L, n_jobs, g->tile_sums.p, skip, g->stream_off.p + j0,
+                       g->gd->d_hasnbr, w_starts, w_walks, L, n_jobs, g->tile_sums.p, skip, g->stream_off.p + j0,
                        track_changes ? g->changed.p : nullptr, cc, j0, fm);
     HIP_TRY(hipGetLastError());
     uint64_t tot = 0;
@@ -1227,7 +1231,7 @@ static int check_starts(pw_graph *g, const uint32_t *d_starts, uint64_t n_jobs) 
     unsigned long long bad = ~0ull;
     HIP_TRY(hipMemcpyAsync(g->counters.p + 9, &bad, sizeof(bad), hipMemcpyHostToDevice, g->stream));
     hipLaunchKernelGGL(pw::starts_check_kernel, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, g->stream, d_starts,
-                       n_jobs, g->n_nodes, g->counters.p + 9);
+                       n_jobs, g->gd->n_nodes, g->counters.p + 9);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&bad, g->counters.p + 9, sizeof(bad), hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -1255,38 +1259,38 @@ PW_EXPORT int pw_count_stream_draws(pw_graph *g, const uint32_t *starts, uint64_
 
 static pw::CsrDev csr_dev(const pw_graph *g) {
     pw::CsrDev c;
-    c.indptr = g->d_indptr;
-    c.indices = g->d_indices;
-    c.data = g->d_data;
-    c.thr = g->d_thr;
-    c.adjbits = g->d_adjbits;
-    c.foff = g->d_foff;
-    c.fbits = g->d_fbits;
-    c.kf = g->d_kf;
-    c.tab_off = g->d_tab_off;
-    c.slots = g->d_slots;
-    c.tri = (const uint4 *)g->d_lines;   // (stride: one 64-byte line per CSR entry)
-    c.clist = g->d_clist;
+    c.indptr = g->gd->d_indptr;
+    c.indices = g->gd->d_indices;
+    c.data = g->gd->d_data;
+    c.thr = g->gd->d_thr;
+    c.adjbits = g->gd->d_adjbits;
+    c.foff = g->gd->d_foff;
+    c.fbits = g->gd->d_fbits;
+    c.kf = g->gd->d_kf;
+    c.tab_off = g->gd->d_tab_off;
+    c.slots = g->gd->d_slots;
+    c.tri = (const uint4 *)g->gd->d_lines;   // (stride: one 64-byte line per CSR entry)
+    c.clist = g->gd->d_clist;
     c.step_edge = 0xffffffffu;
-    c.vrec = g->d_vrec;
-    c.words_per_row = g->words_per_row;
-    c.n_nodes = g->n_nodes;
-    c.nnz = g->nnz;
+    c.vrec = g->gd->d_vrec;
+    c.words_per_row = g->gd->words_per_row;
+    c.n_nodes = g->gd->n_nodes;
+    c.nnz = g->gd->nnz;
     return c;
 }
 
 PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int first_order) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    if (g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "alias tables need a CSR graph handle");
+    if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "alias tables need a CSR graph handle");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
-    if (extend && !g->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
+    if (extend && !g->gd->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (set_device(g)) return PW_ERR_HIP;
     first_order = first_order ? 1 : 0;
-    if (g->alias_kind == first_order && (first_order || (g->alias_p == p && g->alias_q_param == q && g->alias_extend == extend)))
+    if (g->gd->alias_kind == first_order && (first_order || (g->gd->alias_p == p && g->gd->alias_q_param == q && g->gd->alias_extend == extend)))
         return PW_OK;
-    const uint32_t n = g->n_nodes;
+    const uint32_t n = g->gd->n_nodes;
     std::vector<uint32_t> indptr((size_t)n + 1);
-    HIP_TRY(hipMemcpy(indptr.data(), g->d_indptr, sizeof(uint32_t) * indptr.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(indptr.data(), g->gd->d_indptr, sizeof(uint32_t) * indptr.size(), hipMemcpyDeviceToHost));
     std::vector<uint64_t> aptr((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) {
         uint64_t d = indptr[i + 1] - indptr[i];
@@ -1294,39 +1298,39 @@ PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int 
     }
     const uint64_t n_alias = aptr[n];
     const size_t cap = n_alias ? n_alias : 1;
-    if (g->alias_indptr.ensure((size_t)n + 1) || g->alias_j.ensure(cap) || g->alias_q.ensure(cap) ||
-        g->alias_s.ensure(cap) || g->alias_l.ensure(cap) || g->edge_row.ensure(g->nnz ? g->nnz : 1))
+    if (g->gd->alias_indptr.ensure((size_t)n + 1) || g->gd->alias_j.ensure(cap) || g->gd->alias_q.ensure(cap) ||
+        g->gd->alias_s.ensure(cap) || g->gd->alias_l.ensure(cap) || g->gd->edge_row.ensure(g->gd->nnz ? g->gd->nnz : 1))
         return PW_ERR_NOMEM;
-    HIP_TRY(hipMemcpy(g->alias_indptr.p, aptr.data(), sizeof(uint64_t) * aptr.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->gd->alias_indptr.p, aptr.data(), sizeof(uint64_t) * aptr.size(), hipMemcpyHostToDevice));
     pw::CsrDev c = csr_dev(g);
-    if (n) hipLaunchKernelGGL(pw::edge_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, g->d_indptr, n, g->edge_row.p);
-    const uint64_t work = first_order ? (uint64_t)n : (uint64_t)g->nnz;
+    if (n) hipLaunchKernelGGL(pw::edge_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, g->gd->d_indptr, n, g->gd->edge_row.p);
+    const uint64_t work = first_order ? (uint64_t)n : (uint64_t)g->gd->nnz;
     if (work)
         hipLaunchKernelGGL(pw::alias_tables_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, g->stream, c, p, q,
-                           extend, first_order, g->edge_row.p, g->alias_indptr.p, g->alias_j.p, g->alias_q.p,
-                           g->alias_s.p, g->alias_l.p);
+                           extend, first_order, g->gd->edge_row.p, g->gd->alias_indptr.p, g->gd->alias_j.p, g->gd->alias_q.p,
+                           g->gd->alias_s.p, g->gd->alias_l.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g->stream));
-    g->alias_s.release();   // scratch of the build only (2 x sum(deg^2) words)
-    g->alias_l.release();
-    g->n_alias = n_alias;
-    g->alias_kind = first_order;
-    g->alias_p = p;
-    g->alias_q_param = q;
-    g->alias_extend = extend;
+    g->gd->alias_s.release();   // scratch of the build only (2 x sum(deg^2) words)
+    g->gd->alias_l.release();
+    g->gd->n_alias = n_alias;
+    g->gd->alias_kind = first_order;
+    g->gd->alias_p = p;
+    g->gd->alias_q_param = q;
+    g->gd->alias_extend = extend;
     return PW_OK;
 }
 
 PW_EXPORT int pw_precomp_export(pw_graph *g, uint64_t *alias_indptr, uint32_t *alias_j, float *alias_q,
                                 uint64_t *n_entries) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    if (g->alias_kind < 0) return fail(PW_ERR_INVALID, "no alias tables built");
+    if (g->gd->alias_kind < 0) return fail(PW_ERR_INVALID, "no alias tables built");
     if (set_device(g)) return PW_ERR_HIP;
-    if (n_entries) *n_entries = g->n_alias;
+    if (n_entries) *n_entries = g->gd->n_alias;
     if (alias_indptr)
-        HIP_TRY(hipMemcpy(alias_indptr, g->alias_indptr.p, sizeof(uint64_t) * ((size_t)g->n_nodes + 1), hipMemcpyDeviceToHost));
-    if (alias_j && g->n_alias) HIP_TRY(hipMemcpy(alias_j, g->alias_j.p, sizeof(uint32_t) * g->n_alias, hipMemcpyDeviceToHost));
-    if (alias_q && g->n_alias) HIP_TRY(hipMemcpy(alias_q, g->alias_q.p, sizeof(float) * g->n_alias, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(alias_indptr, g->gd->alias_indptr.p, sizeof(uint64_t) * ((size_t)g->gd->n_nodes + 1), hipMemcpyDeviceToHost));
+    if (alias_j && g->gd->n_alias) HIP_TRY(hipMemcpy(alias_j, g->gd->alias_j.p, sizeof(uint32_t) * g->gd->n_alias, hipMemcpyDeviceToHost));
+    if (alias_q && g->gd->n_alias) HIP_TRY(hipMemcpy(alias_q, g->gd->alias_q.p, sizeof(float) * g->gd->n_alias, hipMemcpyDeviceToHost));
     return PW_OK;
 }
 
@@ -1344,11 +1348,11 @@ static bool mode_sequential_stream(int mode) {
 static int simulate_sequential(pw_graph *g, int mode, double p, double q, int extend, const uint32_t *d_starts,
                                uint64_t n_jobs, uint32_t L, int has_seed, uint32_t seed, uint32_t *d_out,
                                pw_stats *st) {
-    if (g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "this mode needs a CSR graph handle");
+    if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "this mode needs a CSR graph handle");
     if (mode == PW_MODE_PRECOMP) { int rc = pw_precomp_build(g, p, q, extend, 0); if (rc) return rc; }
     if (mode == PW_MODE_PRECOMP_FIRST_ORDER) { int rc = pw_precomp_build(g, 1.0, 1.0, 0, 1); if (rc) return rc; }
     if (g->mt_state.ensure(pw::MT_N)) return PW_ERR_NOMEM;
-    if (g->probs_scratch.ensure((size_t)g->max_degree + 1)) return PW_ERR_NOMEM;
+    if (g->probs_scratch.ensure((size_t)g->gd->max_degree + 1)) return PW_ERR_NOMEM;
     uint32_t st0[pw::MT_N];
     pw::mt_seed_state(st0, seed);
     HIP_TRY(hipMemcpy(g->mt_state.p, st0, sizeof(st0), hipMemcpyHostToDevice));
@@ -1362,10 +1366,10 @@ static int simulate_sequential(pw_graph *g, int mode, double p, double q, int ex
     a.n_jobs = n_jobs;
     a.starts = d_starts;
     a.mt_seed_state = g->mt_state.p;
-    a.alias_indptr = g->alias_indptr.p;
-    a.alias_j = g->alias_j.p;
-    a.alias_q = g->alias_q.p;
-    a.n_alias = g->n_alias;
+    a.alias_indptr = g->gd->alias_indptr.p;
+    a.alias_j = g->gd->alias_j.p;
+    a.alias_q = g->gd->alias_q.p;
+    a.n_alias = g->gd->n_alias;
     a.probs_scratch = g->probs_scratch.p;
     a.out = d_out;
     a.stats = g->counters.p + 1;
@@ -1394,11 +1398,11 @@ static int simulate_sequential(pw_graph *g, int mode, double p, double q, int ex
 typedef void (*walk_kernel_fn)(pw::WalkArgs);
 
 static walk_kernel_fn pick_kernel(const pw_graph *g, bool extend) {
-    if (g->kind == 0) {
-        if (g->unit) return pw::walk_kernel<float, false, true, false>;
+    if (g->gd->kind == 0) {
+        if (g->gd->unit) return pw::walk_kernel<float, false, true, false>;
         return extend ? pw::walk_kernel<float, false, false, true> : pw::walk_kernel<float, false, false, false>;
     }
-    if (g->unit) return pw::walk_kernel<double, true, true, false>;
+    if (g->gd->unit) return pw::walk_kernel<double, true, true, false>;
     return extend ? pw::walk_kernel<double, true, false, true> : pw::walk_kernel<double, true, false, false>;
 }
 
@@ -1410,10 +1414,10 @@ static bool is_pow2_double(double x) {
 
 static int launch_dense_bits(pw_graph *g, const pw::WalkArgs &wa, uint64_t *redo_total) {
     pw::DenseArgs da;
-    da.adjbits = g->d_adjbits;
-    da.deg = g->d_deg;
-    da.n = g->n_nodes;
-    da.wpr = g->words_per_row;
+    da.adjbits = g->gd->d_adjbits;
+    da.deg = g->gd->d_deg;
+    da.n = g->gd->n_nodes;
+    da.wpr = g->gd->words_per_row;
     da.p = wa.p;
     da.q = wa.q;
     da.L = wa.L;
@@ -1492,28 +1496,28 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, bool extend) {
     wa.tot_e = nullptr;
     wa.tot_v = nullptr;
     wa.resume = 0;
-    if (g->kind != 0 || g->unit || !g->nnz || g->tot_failed || getenv("PECANPY_AMD_NO_TOT")) return 0;
-    const bool fresh = g->tot_extend == (extend ? 1 : 0) && g->tot_p == wa.p && g->tot_q == wa.q &&
-                       (!extend || g->tot_thr_version == g->thr_version);
+    if (g->gd->kind != 0 || g->gd->unit || !g->gd->nnz || g->gd->tot_failed || getenv("PECANPY_AMD_NO_TOT")) return 0;
+    const bool fresh = g->gd->tot_extend == (extend ? 1 : 0) && g->gd->tot_p == wa.p && g->gd->tot_q == wa.q &&
+                       (!extend || g->gd->tot_thr_version == g->gd->thr_version);
     // The table costs one row scan per CSR entry and saves one per sampled step: a call that samples fewer steps than
     // the graph has entries is faster through the two-pass step (an existing table is used whatever the call's size)
-    if (!fresh && wa.n_jobs * (uint64_t)wa.L < (uint64_t)g->nnz && !getenv("PECANPY_AMD_FORCE_TOT")) return 0;
+    if (!fresh && wa.n_jobs * (uint64_t)wa.L < (uint64_t)g->gd->nnz && !getenv("PECANPY_AMD_FORCE_TOT")) return 0;
     if (!fresh) {
-        if (!g->d_tot_e) {
-            hipError_t e = hipMalloc((void **)&g->d_tot_e, sizeof(float) * (size_t)g->nnz);
-            if (e == hipSuccess) e = hipMalloc((void **)&g->d_tot_v, sizeof(float) * (size_t)(g->n_nodes ? g->n_nodes : 1));
-            if (e != hipSuccess) { g->tot_failed = true; (void)hipGetLastError(); return 0; }
+        if (!g->gd->d_tot_e) {
+            hipError_t e = hipMalloc((void **)&g->gd->d_tot_e, sizeof(float) * (size_t)g->gd->nnz);
+            if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_tot_v, sizeof(float) * (size_t)(g->gd->n_nodes ? g->gd->n_nodes : 1));
+            if (e != hipSuccess) { g->gd->tot_failed = true; (void)hipGetLastError(); return 0; }
         }
         uint32_t *d_edge_row = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_edge_row, sizeof(uint32_t) * (size_t)g->nnz));
-        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->d_indptr, g->n_nodes, d_edge_row);
+        HIP_TRY(hipMalloc((void **)&d_edge_row, sizeof(uint32_t) * (size_t)g->gd->nnz));
+        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->n_nodes, d_edge_row);
         pw::WalkArgs ba = wa;
         hipError_t e = hipEventRecord(g->ev[4], g->stream);
         if (e == hipSuccess) {
-            const uint64_t items = (uint64_t)g->nnz + g->n_nodes;
+            const uint64_t items = (uint64_t)g->gd->nnz + g->gd->n_nodes;
             const unsigned grid = (unsigned)((items + pw::WAVES_PER_BLOCK - 1) / pw::WAVES_PER_BLOCK);
-            if (extend) hipLaunchKernelGGL(pw::tot_build_kernel<true>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row, g->d_tot_e, g->d_tot_v);
-            else hipLaunchKernelGGL(pw::tot_build_kernel<false>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row, g->d_tot_e, g->d_tot_v);
+            if (extend) hipLaunchKernelGGL(pw::tot_build_kernel<true>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row, g->gd->d_tot_e, g->gd->d_tot_v);
+            else hipLaunchKernelGGL(pw::tot_build_kernel<false>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row, g->gd->d_tot_e, g->gd->d_tot_v);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(g->ev[5], g->stream);
@@ -1522,15 +1526,15 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, bool extend) {
         if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("normaliser table: ") + hipGetErrorString(e));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
-        g->tot_build_ms = ms;
+        g->gd->tot_build_ms = ms;
         g->param_ms_call += ms;
-        g->tot_extend = extend ? 1 : 0;
-        g->tot_p = wa.p;
-        g->tot_q = wa.q;
-        g->tot_thr_version = g->thr_version;
+        g->gd->tot_extend = extend ? 1 : 0;
+        g->gd->tot_p = wa.p;
+        g->gd->tot_q = wa.q;
+        g->gd->tot_thr_version = g->gd->thr_version;
     }
-    wa.tot_e = g->d_tot_e;
-    wa.tot_v = g->d_tot_v;
+    wa.tot_e = g->gd->d_tot_e;
+    wa.tot_v = g->gd->d_tot_v;
     return 0;
 }
 
@@ -1540,29 +1544,29 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, bool extend) {
 // the form does not apply: the wave-per-walk kernel then serves the call.
 static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, bool extend, bool *ok) {
     *ok = false;
-    if (g->kind != 0 || g->unit || !g->nnz || !g->d_lines || g->lanes_off || !wa.tot_e || g->wl_failed) return 0;
+    if (g->gd->kind != 0 || g->gd->unit || !g->gd->nnz || !g->gd->d_lines || g->gd->lanes_off || !wa.tot_e || g->gd->wl_failed) return 0;
     if (getenv("PECANPY_AMD_NO_LANES") || getenv("PECANPY_AMD_NO_WLANES")) return 0;
-    if (extend && !g->d_thr) return 0;
+    if (extend && !g->gd->d_thr) return 0;
     // (the float64 evaluation of the prefix differences is part of the decision's error budget: moderate biases only)
     if (!(wa.p >= 1.0 / 1024 && wa.p <= 1024.0 && wa.q >= 1.0 / 1024 && wa.q <= 1024.0)) return 0;
-    const bool fresh = g->wl_extend == (extend ? 1 : 0) && g->wl_p == wa.p && g->wl_q == wa.q &&
-                       (!extend || g->wl_thr_version == g->thr_version);
+    const bool fresh = g->gd->wl_extend == (extend ? 1 : 0) && g->gd->wl_p == wa.p && g->gd->wl_q == wa.q &&
+                       (!extend || g->gd->wl_thr_version == g->gd->thr_version);
     if (fresh) { *ok = true; return 0; }
-    const uint32_t nnz = g->nnz;
-    auto give_up = [&]() { g->wl_failed = true; (void)hipGetLastError(); return 0; };
-    if (!g->d_wb) {
-        hipError_t e = hipMalloc((void **)&g->d_wb, sizeof(float) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->d_wpq, sizeof(pw::PrefixPair) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->d_wl_dprev, sizeof(double) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->d_wl_off, sizeof(unsigned long long) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->d_wck_off, sizeof(unsigned long long) * (size_t)nnz);
-        const bool have_rows = g->d_wedge_row != nullptr;   // (a handle with a PARTIAL index kept them from its creation: pw_csr_create)
-        if (e == hipSuccess && !have_rows) e = hipMalloc((void **)&g->d_wedge_row, sizeof(uint32_t) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->d_wp1, sizeof(pw::PrefixPair) * (size_t)nnz);
+    const uint32_t nnz = g->gd->nnz;
+    auto give_up = [&]() { g->gd->wl_failed = true; (void)hipGetLastError(); return 0; };
+    if (!g->gd->d_wb) {
+        hipError_t e = hipMalloc((void **)&g->gd->d_wb, sizeof(float) * (size_t)nnz);
+        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wpq, sizeof(pw::PrefixPair) * (size_t)nnz);
+        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wl_dprev, sizeof(double) * (size_t)nnz);
+        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wl_off, sizeof(unsigned long long) * (size_t)nnz);
+        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wck_off, sizeof(unsigned long long) * (size_t)nnz);
+        const bool have_rows = g->gd->d_wedge_row != nullptr;   // (a handle with a PARTIAL index kept them from its creation: pw_csr_create)
+        if (e == hipSuccess && !have_rows) e = hipMalloc((void **)&g->gd->d_wedge_row, sizeof(uint32_t) * (size_t)nnz);
+        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wp1, sizeof(pw::PrefixPair) * (size_t)nnz);
         if (e != hipSuccess) return give_up();
-        if (!have_rows) hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->d_indptr, g->n_nodes, g->d_wedge_row);
-        hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->d_indptr,
-                           (const float *)g->d_data, g->n_nodes, g->d_wp1);
+        if (!have_rows) hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->n_nodes, g->gd->d_wedge_row);
+        hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->gd->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_indptr,
+                           (const float *)g->gd->d_data, g->gd->n_nodes, g->gd->d_wp1);
     }
     uint64_t *d_tiles = nullptr;
     const uint64_t n_tiles = ((uint64_t)nnz + pw::CL_TILE - 1) / pw::CL_TILE;
@@ -1572,16 +1576,16 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, bool extend,
     HIP_TRY(hipEventRecord(g->ev[4], g->stream));
     // offsets of the per-entry delta lists (one float64 per list entry) and of the recorded chain values
     uint64_t entries = 0, records = 0;
-    hipLaunchKernelGGL(pw::entry_tile_sums_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, nnz, d_tiles);
+    hipLaunchKernelGGL(pw::entry_tile_sums_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles);
     hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-    hipLaunchKernelGGL(pw::entry_offsets_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, nnz, d_tiles, g->d_wl_off);
+    hipLaunchKernelGGL(pw::entry_offsets_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles, g->gd->d_wl_off);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&entries, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::entry_tile_sums_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, nnz, d_tiles);
+        hipLaunchKernelGGL(pw::entry_tile_sums_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles);
         hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-        hipLaunchKernelGGL(pw::entry_offsets_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->d_lines, nnz, d_tiles, g->d_wck_off);
+        hipLaunchKernelGGL(pw::entry_offsets_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles, g->gd->d_wck_off);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&records, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
@@ -1589,38 +1593,38 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, bool extend,
     if (e != hipSuccess) { cleanup(); return fail(PW_ERR_HIP, std::string("weighted lane tables (offsets): ") + hipGetErrorString(e)); }
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    if (entries + 1 > g->wdl_cap) {
-        if (g->d_wdl) (void)hipFree(g->d_wdl);
-        g->d_wdl = nullptr;
-        g->wdl_cap = 0;
-        if ((entries + 1) * sizeof(double) > free_b / 2 || hipMalloc((void **)&g->d_wdl, sizeof(double) * (size_t)(entries + 1)) != hipSuccess) {
+    if (entries + 1 > g->gd->wdl_cap) {
+        if (g->gd->d_wdl) (void)hipFree(g->gd->d_wdl);
+        g->gd->d_wdl = nullptr;
+        g->gd->wdl_cap = 0;
+        if ((entries + 1) * sizeof(double) > free_b / 2 || hipMalloc((void **)&g->gd->d_wdl, sizeof(double) * (size_t)(entries + 1)) != hipSuccess) {
             cleanup();
             return give_up();
         }
-        g->wdl_cap = entries + 1;
+        g->gd->wdl_cap = entries + 1;
     }
-    if (records + 1 > g->wck_cap) {
-        if (g->d_wck) (void)hipFree(g->d_wck);
-        g->d_wck = nullptr;
-        g->wck_cap = 0;
-        if ((records + 1) * sizeof(float) > free_b / 4 || hipMalloc((void **)&g->d_wck, sizeof(float) * (size_t)(records + 1)) != hipSuccess) {
+    if (records + 1 > g->gd->wck_cap) {
+        if (g->gd->d_wck) (void)hipFree(g->gd->d_wck);
+        g->gd->d_wck = nullptr;
+        g->gd->wck_cap = 0;
+        if ((records + 1) * sizeof(float) > free_b / 4 || hipMalloc((void **)&g->gd->d_wck, sizeof(float) * (size_t)(records + 1)) != hipSuccess) {
             cleanup();
             return give_up();
         }
-        g->wck_cap = records + 1;
+        g->gd->wck_cap = records + 1;
     }
     const unsigned egrid = (unsigned)(((uint64_t)nnz + 255) / 256);
     pw::CsrDev c = csr_dev(g);
-    if (extend) hipLaunchKernelGGL(pw::wbase_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->d_data, g->d_wedge_row, g->d_thr, wa.q, nnz, g->d_wb);
-    else hipLaunchKernelGGL(pw::wbase_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->d_data, g->d_wedge_row, (const float *)nullptr, wa.q, nnz, g->d_wb);
-    hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->d_indptr, g->d_wb,
-                       g->n_nodes, g->d_wpq);
-    if (extend) hipLaunchKernelGGL(pw::wlist_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, c, g->d_wedge_row, g->d_wb, wa.p, wa.q, g->d_wl_off, g->d_wdl, g->d_wl_dprev);
-    else hipLaunchKernelGGL(pw::wlist_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, c, g->d_wedge_row, g->d_wb, wa.p, wa.q, g->d_wl_off, g->d_wdl, g->d_wl_dprev);
+    if (extend) hipLaunchKernelGGL(pw::wbase_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->gd->d_data, g->gd->d_wedge_row, g->gd->d_thr, wa.q, nnz, g->gd->d_wb);
+    else hipLaunchKernelGGL(pw::wbase_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->gd->d_data, g->gd->d_wedge_row, (const float *)nullptr, wa.q, nnz, g->gd->d_wb);
+    hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->gd->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->d_wb,
+                       g->gd->n_nodes, g->gd->d_wpq);
+    if (extend) hipLaunchKernelGGL(pw::wlist_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, c, g->gd->d_wedge_row, g->gd->d_wb, wa.p, wa.q, g->gd->d_wl_off, g->gd->d_wdl, g->gd->d_wl_dprev);
+    else hipLaunchKernelGGL(pw::wlist_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, c, g->gd->d_wedge_row, g->gd->d_wb, wa.p, wa.q, g->gd->d_wl_off, g->gd->d_wdl, g->gd->d_wl_dprev);
     if (records) {   // the chain's value after every CHAIN_CKPT-th element of the rows longer than that, per arriving entry
         const unsigned cgrid = (unsigned)(((uint64_t)nnz + pw::WAVES_PER_BLOCK - 1) / pw::WAVES_PER_BLOCK);
-        if (extend) hipLaunchKernelGGL(pw::wckpt_kernel<true>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->d_wedge_row, g->d_wck_off, g->d_wck);
-        else hipLaunchKernelGGL(pw::wckpt_kernel<false>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->d_wedge_row, g->d_wck_off, g->d_wck);
+        if (extend) hipLaunchKernelGGL(pw::wckpt_kernel<true>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->gd->d_wedge_row, g->gd->d_wck_off, g->gd->d_wck);
+        else hipLaunchKernelGGL(pw::wckpt_kernel<false>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->gd->d_wedge_row, g->gd->d_wck_off, g->gd->d_wck);
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(g->ev[5], g->stream);
@@ -1630,10 +1634,10 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, bool extend,
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
     g->param_ms_call += ms;
-    g->wl_extend = extend ? 1 : 0;
-    g->wl_p = wa.p;
-    g->wl_q = wa.q;
-    g->wl_thr_version = g->thr_version;
+    g->gd->wl_extend = extend ? 1 : 0;
+    g->gd->wl_p = wa.p;
+    g->gd->wl_q = wa.q;
+    g->gd->wl_thr_version = g->gd->thr_version;
     *ok = true;
     return 0;
 }
@@ -1642,63 +1646,63 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, bool extend,
 // over (a partial sum inside the bound's interval: ~10^-11 of the steps) are walked again by the complete kernel
 // LDS of one wavefront: prev's packed row + its prefix popcounts + the block prefixes
 static bool dense_weighted_lds_ok(const pw_graph *g) {
-    const uint64_t lds = (uint64_t)g->words_per_row * 12u + ((uint64_t)g->max_degree / pw::DWBLK_MIN + 2u) * 8u;
+    const uint64_t lds = (uint64_t)g->gd->words_per_row * 12u + ((uint64_t)g->gd->max_degree / pw::DWBLK_MIN + 2u) * 8u;
     return lds <= 60u * 1024u;
 }
 
 static bool dense_weighted_eligible(const pw_graph *g, const pw::WalkArgs &wa, bool extend) {
-    if (g->kind != 1 || g->unit || g->bits_only || !g->dense_nonneg || !g->d_adjbits || !g->d_data) return false;
-    if (extend && !g->d_thr) return false;
+    if (g->gd->kind != 1 || g->gd->unit || g->gd->bits_only || !g->gd->dense_nonneg || !g->gd->d_adjbits || !g->gd->d_data) return false;
+    if (extend && !g->gd->d_thr) return false;
     if (wa.resume || getenv("PECANPY_AMD_DENSE_NO_WFAST")) return false;
     return dense_weighted_lds_ok(g);
 }
 
 // node2vec++ has no other kernel: what it cannot walk is refused before the call starts (simulate_device_impl, run_probe)
 static int n2vpp_check(const pw_graph *g) {
-    if (g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs a dense graph handle");
-    if (g->bits_only) return fail(PW_ERR_UNSUPPORTED, "node2vec++: a dense graph created from packed bits has no compressed rows");
-    if (!g->dense_nonneg) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights");
-    if (!g->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
-    if (!g->d_adjbits || (!g->unit && !g->d_data)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: the handle has no dense rows");
+    if (g->gd->kind != 1) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs a dense graph handle");
+    if (g->gd->bits_only) return fail(PW_ERR_UNSUPPORTED, "node2vec++: a dense graph created from packed bits has no compressed rows");
+    if (!g->gd->dense_nonneg) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights");
+    if (!g->gd->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
+    if (!g->gd->d_adjbits || (!g->gd->unit && !g->gd->d_data)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: the handle has no dense rows");
     if (!dense_weighted_lds_ok(g)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: prev's packed row does not fit one wavefront's LDS");
     return PW_OK;
 }
 
 // node2vec++ on CSR handles (walk_sparse_pp.hip.h): likewise no other kernel
 static int spp_check(pw_graph *g) {
-    if (g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++ needs a CSR graph handle");
-    if (!g->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
-    if (g->nnz && (!g->d_vrec || !g->d_kf || !g->d_fbits || !g->d_slots))
+    if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++ needs a CSR graph handle");
+    if (!g->gd->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
+    if (g->gd->nnz && (!g->gd->d_vrec || !g->gd->d_kf || !g->gd->d_fbits || !g->gd->d_slots))
         return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++: the handle has no membership index");
-    if (g->spp_zero < 0) {   // a stored 0.0f is a neighbour here but not in the dense reference (its b = 0 gives 0 / 0)
-        g->spp_zero = 0;
-        if (!g->unit && g->d_data && g->nnz) {
+    if (g->gd->spp_zero < 0) {   // a stored 0.0f is a neighbour here but not in the dense reference (its b = 0 gives 0 / 0)
+        g->gd->spp_zero = 0;
+        if (!g->gd->unit && g->gd->d_data && g->gd->nnz) {
             if (set_device(g)) return PW_ERR_HIP;
             if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
             unsigned long long flag = 0;
             HIP_TRY(hipMemsetAsync(g->counters.p, 0, sizeof(flag), g->stream));
-            hipLaunchKernelGGL(pw::csr_zero_weight_kernel, dim3((unsigned)(((uint64_t)g->nnz + 255) / 256)), dim3(256), 0, g->stream,
-                               (const float *)g->d_data, (uint64_t)g->nnz, g->counters.p);
+            hipLaunchKernelGGL(pw::csr_zero_weight_kernel, dim3((unsigned)(((uint64_t)g->gd->nnz + 255) / 256)), dim3(256), 0, g->stream,
+                               (const float *)g->gd->d_data, (uint64_t)g->gd->nnz, g->counters.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&flag, g->counters.p, sizeof(flag), hipMemcpyDeviceToHost, g->stream));
             HIP_TRY(hipStreamSynchronize(g->stream));
-            g->spp_zero = flag ? 1 : 0;
+            g->gd->spp_zero = flag ? 1 : 0;
         }
     }
-    if (g->spp_zero) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights (a stored weight is 0)");
+    if (g->gd->spp_zero) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights (a stored weight is 0)");
     return PW_OK;
 }
 
 static pw::SparsePPArgs spp_args(const pw_graph *g, double p, double q) {
     pw::SparsePPArgs sa;
     memset(&sa, 0, sizeof(sa));
-    sa.vrec = g->d_vrec;
-    sa.kf = g->d_kf;
-    sa.data = g->unit ? nullptr : (const float *)g->d_data;
-    sa.fbits = g->d_fbits;
-    sa.slots = g->d_slots;
-    sa.thr = g->d_thr;
-    sa.n = g->n_nodes;
+    sa.vrec = g->gd->d_vrec;
+    sa.kf = g->gd->d_kf;
+    sa.data = g->gd->unit ? nullptr : (const float *)g->gd->d_data;
+    sa.fbits = g->gd->d_fbits;
+    sa.slots = g->gd->d_slots;
+    sa.thr = g->gd->d_thr;
+    sa.n = g->gd->n_nodes;
     sa.p = p;
     sa.q = q;
     return sa;
@@ -1723,7 +1727,7 @@ static int launch_sparse_pp(pw_graph *g, const pw::WalkArgs &wa) {
     const char *xt = getenv("PECANPY_AMD_DENSE_EXACT_TEST");  // tests: steps with (job + step) % k == 0 are decided by the in-kernel chain
     sa.exact_every = xt ? (uint32_t)strtoul(xt, nullptr, 10) : 0u;
     typedef void (*spp_fn)(pw::SparsePPArgs);
-    spp_fn fn = g->unit ? pw::walk_sparse_pp_kernel<true> : pw::walk_sparse_pp_kernel<false>;
+    spp_fn fn = g->gd->unit ? pw::walk_sparse_pp_kernel<true> : pw::walk_sparse_pp_kernel<false>;
     int occ = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, pw::WAVE, 0));
     if (occ < 1) occ = 1;
@@ -1741,13 +1745,13 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, int bias, 
     uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
     if (!n_work) return 0;
     pw::DenseWArgs da;
-    da.indptr = g->d_indptr;
-    da.indices = g->d_indices;
-    da.data = (const double *)g->d_data;
-    da.adjbits = g->d_adjbits;
-    da.thr = g->d_thr;
-    da.n = g->n_nodes;
-    da.wpr = g->words_per_row;
+    da.indptr = g->gd->d_indptr;
+    da.indices = g->gd->d_indices;
+    da.data = (const double *)g->gd->d_data;
+    da.adjbits = g->gd->d_adjbits;
+    da.thr = g->gd->d_thr;
+    da.n = g->gd->n_nodes;
+    da.wpr = g->gd->words_per_row;
     da.p = wa.p;
     da.q = wa.q;
     da.L = wa.L;
@@ -1768,7 +1772,7 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, int bias, 
     da.redo_every = rt ? (uint32_t)strtoul(rt, nullptr, 10) : 0u;
     const char *xt = getenv("PECANPY_AMD_DENSE_EXACT_TEST");  // tests: steps with (job + step) % k == 0 are decided by the in-kernel chain
     da.exact_every = xt ? (uint32_t)strtoul(xt, nullptr, 10) : 0u;
-    da.lds_blocks = g->max_degree / pw::DWBLK_MIN + 2u;
+    da.lds_blocks = g->gd->max_degree / pw::DWBLK_MIN + 2u;
     const size_t lds = (size_t)da.wpr * 8u + (size_t)da.lds_blocks * 8u + (size_t)da.wpr * 4u;
     typedef void (*dw_fn)(pw::DenseWArgs);
     dw_fn fn = bias == pw::DW_N2VPLUS ? pw::walk_dense_weighted_kernel<pw::DW_N2VPLUS>
@@ -1812,9 +1816,9 @@ static int launch_wave_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_
     // unweighted dense graphs: the column-space kernels at every size (round 6: with prev's row in LDS and DPP sums the packed rows
     // beat the compressed ones from N = 1 000 on -- ER-1k 364 -> 682, ER-8k 207 -> 1 135, ER-12k 158 -> 1 145 M steps/s; rounds 2-5
     // sent matrices of up to 12 000 rows through their compressed rows; PECANPY_AMD_DENSE_SMALL_ROWS=1: that rule)
-    if (g->call_n2vpp) return launch_dense_weighted(g, wa, g->unit ? pw::DW_N2VPP_UNIT : pw::DW_N2VPP, redo_total);
+    if (g->call_n2vpp) return launch_dense_weighted(g, wa, g->gd->unit ? pw::DW_N2VPP_UNIT : pw::DW_N2VPP, redo_total);
     const bool small_rows = env_on("PECANPY_AMD_DENSE_SMALL_ROWS");
-    if (g->kind == 1 && g->unit && g->d_deg && (g->bits_only || g->n_nodes > 12000 || !small_rows)) return launch_dense_bits(g, wa, redo_total);
+    if (g->gd->kind == 1 && g->gd->unit && g->gd->d_deg && (g->gd->bits_only || g->gd->n_nodes > 12000 || !small_rows)) return launch_dense_bits(g, wa, redo_total);
     if (dense_weighted_eligible(g, wa, extend)) return launch_dense_weighted(g, wa, extend ? pw::DW_N2VPLUS : pw::DW_N2V, redo_total);
     int occ = 0;
     walk_kernel_fn fn = pick_kernel(g, extend);
@@ -1827,14 +1831,14 @@ static int launch_wave_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_
     if (grid < 1) grid = 1;
     HIP_TRY(hipMemsetAsync(g->counters.p, 0, sizeof(unsigned long long), g->stream));
     pw::WalkArgs wk = wa;
-    if (g->has_loop) wk.lazy_ok = 0;   // (self loops: the lazy step's key classification would meet prev among the common neighbours)
+    if (g->gd->has_loop) wk.lazy_ok = 0;   // (self loops: the lazy step's key classification would meet prev among the common neighbours)
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wk);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 static bool lanes_eligible(const pw_graph *g, const pw::WalkArgs &wa) {
-    return g->kind == 0 && g->unit && g->d_lines && !g->lanes_off && wa.lazy_ok && !getenv("PECANPY_AMD_NO_LANES");
+    return g->gd->kind == 0 && g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && wa.lazy_ok && !getenv("PECANPY_AMD_NO_LANES");
 }
 
 // One lane per walk (walk_lanes.hip.h); the jobs it hands back (overflow reads, rows outside the exact range) are
@@ -1843,11 +1847,11 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     const uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
     if (g->redo.ensure(n_work ? n_work : 1)) return PW_ERR_NOMEM;
     pw::LanesArgs la;
-    la.lines = g->d_lines;
-    la.clist = g->d_clist;
-    la.vlines = g->vlines ? 1u : 0u;
-    la.vrec = g->d_vrec;
-    la.nnz = g->nnz;
+    la.lines = g->gd->d_lines;
+    la.clist = g->gd->d_clist;
+    la.vlines = g->gd->vlines ? 1u : 0u;
+    la.vrec = g->gd->d_vrec;
+    la.nnz = g->gd->nnz;
     la.L = wa.L;
     la.n_jobs = wa.n_jobs;
     la.starts = wa.starts;
@@ -1863,12 +1867,12 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     la.redo_count = g->counters.p + 6;
     la.w_out = wa.w_out;
     la.w_prev = wa.w_prev;
-    la.wpq = g->d_wpq;
-    la.wdl = g->d_wdl;
-    la.wl_off = g->d_wl_off;
-    la.wl_dprev = g->d_wl_dprev;
+    la.wpq = g->gd->d_wpq;
+    la.wdl = g->gd->d_wdl;
+    la.wl_off = g->gd->d_wl_off;
+    la.wl_dprev = g->gd->d_wl_dprev;
     la.tot_e = wa.tot_e;
-    la.wp1 = g->d_wp1;
+    la.wp1 = g->gd->d_wp1;
     la.wl_pos = wa.q >= 1.0 ? 1u : 0u;
     la.tot_v = wa.tot_v;
     int occ = 0;
@@ -1905,7 +1909,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     //  18.4 with the queue, 22.1 in place.  On the RMAT-22 graph, 1.3 / 2.6 / 3.2 M jobs: 12.9 -> 10.3, 18.5 -> 17.5,
     //  19.1-20.5 -> 21.0: nine jobs per resident lane is the crossover.  PECANPY_AMD_CHAIN_TAIL set: the queue rule alone decides.)
     // (not with a partial index: without a queue the steps whose list was left out hand their walks to walk_kernel for good)
-    if (!weighted && !tail_env && g->list_max_len == 0xffffffffu && n_work <= 9 * lanes_resident) use_queue = false;
+    if (!weighted && !tail_env && g->gd->list_max_len == 0xffffffffu && n_work <= 9 * lanes_resident) use_queue = false;
     // CHAINS form (round 5): job arrays of a few walks per resident lane -- a shard of a multi-GPU run, RMAT-18..20 sized calls --
     // in ONE launch whose wavefronts run the float chains themselves (from the pool, PW_LANES_CHAIN_TH steps at a time) instead
     // of parking the walks for lanes_chain_kernel and a next round: every round of such a call lasts as long as its slowest
@@ -1921,7 +1925,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
     if (occ_c < 1) occ_c = 1;
     const uint64_t lanes_resident_c = (uint64_t)g->n_cu * (uint64_t)occ_c * pw::WAVES_PER_BLOCK * pw::WAVE;
     bool chains_form = !weighted && !getenv("PECANPY_AMD_VERIFY_TIGHT") && !tail_env && !getenv("PECANPY_AMD_NO_CHAIN_QUEUE") &&
-                       g->list_max_len == 0xffffffffu && n_work >= lanes_resident_c && n_work <= 16 * lanes_resident_c;
+                       g->gd->list_max_len == 0xffffffffu && n_work >= lanes_resident_c && n_work <= 16 * lanes_resident_c;
     if (const char *ce = getenv("PECANPY_AMD_LANE_CHAINS")) chains_form = atoi(ce) != 0 && !weighted && !getenv("PECANPY_AMD_VERIFY_TIGHT");
     if (chains_form) use_queue = true;      // (a step that finds the pool full is still parked: the round loop below takes care of it)
     // Queue capacities (round 6: from what CAN be parked, not from the job array -- device memory a fresh box has not handed out
@@ -1991,7 +1995,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
         // one round of 3.7 ms; the pass 103.4 -> 102.3 ms.  32 (the second round too: 5.2 M walks): 12.9 ms against 7.7 + 3.0 + 2.1;
         // 64 (every round behind the first): 44.6 against 36.1 (profiles/r06_late_chains.txt).
         const bool chains_late = late_chains > 0 && round >= 1 && !weighted && use_queue && !verify_full && !tail_env &&
-                                 g->list_max_len == 0xffffffffu && todo >= lanes_resident_c && todo <= late_chains * lanes_resident_c;
+                                 g->gd->list_max_len == 0xffffffffu && todo >= lanes_resident_c && todo <= late_chains * lanes_resident_c;
         const bool chains_now = (chains_form && round == 0) || chains_late;
         bool queue_out = chains_now || (use_queue && todo > tail && round < (weighted ? 512 : 64));
         if (queue_out && round >= 1 && g->susp[round & 1].ensure((size_t)todo + 2 * (size_t)lanes_resident)) {
@@ -2042,7 +2046,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
             if (n_chk) {
                 HIP_TRY(hipMemsetAsync(g->counters.p + 40, 0, 4 * sizeof(unsigned long long), g->stream));
                 hipLaunchKernelGGL(pw::lanes_verify_kernel, dim3((unsigned)((n_chk + 255) / 256)), dim3(256), 0, g->stream, g->ver.p,
-                                   (uint64_t)n_chk, g->d_lines, g->d_clist, wa.w_prev, g->counters.p + 40, g->ver_bad.p, 16u);
+                                   (uint64_t)n_chk, g->gd->d_lines, g->gd->d_clist, wa.w_prev, g->counters.p + 40, g->ver_bad.p, 16u);
                 HIP_TRY(hipGetLastError());
                 unsigned long long vc[4] = {0, 0, 0, 0};
                 HIP_TRY(hipMemcpyAsync(vc, g->counters.p + 40, sizeof(vc), hipMemcpyDeviceToHost, g->stream));
@@ -2068,22 +2072,22 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
             const int eager_wgs = g->twin_active ? 6 : 8;   // (workgroups per CU)
             const unsigned egrid_e = (unsigned)std::min<uint64_t>(want_e, (uint64_t)g->n_cu * (uint64_t)eager_wgs);
             if (extend) hipLaunchKernelGGL(pw::lanes_eager_weighted_kernel<true>, dim3(egrid_e), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa,
-                                           g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12, (const uint32_t *)g->d_wedge_row,
-                                           (const unsigned long long *)g->d_wck_off, (const float *)g->d_wck);
+                                           g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12, (const uint32_t *)g->gd->d_wedge_row,
+                                           (const unsigned long long *)g->gd->d_wck_off, (const float *)g->gd->d_wck);
             else hipLaunchKernelGGL(pw::lanes_eager_weighted_kernel<false>, dim3(egrid_e), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa,
-                                    g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12, (const uint32_t *)g->d_wedge_row,
-                                    (const unsigned long long *)g->d_wck_off, (const float *)g->d_wck);
+                                    g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12, (const uint32_t *)g->gd->d_wedge_row,
+                                    (const unsigned long long *)g->gd->d_wck_off, (const float *)g->gd->d_wck);
             HIP_TRY(hipGetLastError());
         } else if (parked) {   // settle the queue just filled
             hipLaunchKernelGGL(pw::lanes_chain_kernel, dim3((unsigned)((parked + 255) / 256)), dim3(256), 0, g->stream,
-                               g->susp[round & 1].p, (uint64_t)parked, g->d_lines, g->d_clist, wa.w_prev, g->counters.p + 1);
+                               g->susp[round & 1].p, (uint64_t)parked, g->gd->d_lines, g->gd->d_clist, wa.w_prev, g->counters.p + 1);
             HIP_TRY(hipGetLastError());
-            if (g->list_max_len != 0xffffffffu) {   // partial index: the steps whose entry's list was left out (one wavefront each)
+            if (g->gd->list_max_len != 0xffffffffu) {   // partial index: the steps whose entry's list was left out (one wavefront each)
                 HIP_TRY(hipMemsetAsync(g->counters.p + 13, 0, sizeof(unsigned long long), g->stream));
                 const uint64_t want_e = (parked + pw::WAVES_PER_BLOCK - 1) / pw::WAVES_PER_BLOCK;
                 hipLaunchKernelGGL(pw::lanes_eager_kernel, dim3((unsigned)std::min<uint64_t>(want_e, (uint64_t)g->n_cu * 8)),
                                    dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->susp[round & 1].p, (uint64_t)parked, g->counters.p + 12,
-                                   (const uint32_t *)g->d_wedge_row);
+                                   (const uint32_t *)g->gd->d_wedge_row);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -2115,7 +2119,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
         g->ver_dropped += n_rec_s - n_chk;
         HIP_TRY(hipEventRecord(g->ev[4], g->stream));
         hipLaunchKernelGGL(pw::lanes_verify_kernel, dim3((unsigned)((n_chk + 255) / 256)), dim3(256), 0, g->stream, g->ver.p,
-                           (uint64_t)n_chk, g->d_lines, g->d_clist, wa.w_prev, g->counters.p + 44, g->ver_bad.p, 16u, g->ver_jobs.p, VER_JOBS_CAP);
+                           (uint64_t)n_chk, g->gd->d_lines, g->gd->d_clist, wa.w_prev, g->counters.p + 44, g->ver_bad.p, 16u, g->ver_jobs.p, VER_JOBS_CAP);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(g->ev[5], g->stream));
         HIP_TRY(hipMemcpyAsync(vs, g->counters.p + 44, sizeof(vs), hipMemcpyDeviceToHost, g->stream));
@@ -2188,35 +2192,35 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_redo, bo
 // Unit-weight graphs whose 1/p or 1/q is not a power of two: the lane kernel in its FLOATS form -- every step is the
 // reference's two float32 chains, evaluated per lane (walk_lanes.hip.h); one launch, nothing is parked.
 static bool lanes_float_eligible(const pw_graph *g, const pw::WalkArgs &wa) {
-    return g->kind == 0 && g->unit && g->d_lines && !g->lanes_off && !wa.lazy_ok && !getenv("PECANPY_AMD_NO_LANES");
+    return g->gd->kind == 0 && g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && !wa.lazy_ok && !getenv("PECANPY_AMD_NO_LANES");
 }
 
 // FLOATS form: the row totals of all arriving lines, once per (1/q, 1/p) (walk_lanes.hip.h: unit_tot_kernel; cached in the
 // handle, reported as param_index_ms): the step then is ONE bounded decision instead of two float chains.  A call that
 // samples fewer steps than the graph has lines runs the two-chain step (an existing table is used whatever the call's size).
 static int ensure_unit_tot(pw_graph *g, const pw::WalkArgs &wa) {
-    if (g->utot_failed) return 0;
-    const uint64_t n_lines = (uint64_t)g->nnz + (g->vlines ? g->n_nodes : 0);
-    const bool fresh = g->d_utot && g->utot_wo == wa.w_out && g->utot_wp == wa.w_prev;
+    if (g->gd->utot_failed) return 0;
+    const uint64_t n_lines = (uint64_t)g->gd->nnz + (g->gd->vlines ? g->gd->n_nodes : 0);
+    const bool fresh = g->gd->d_utot && g->gd->utot_wo == wa.w_out && g->gd->utot_wp == wa.w_prev;
     if (fresh || !(wa.n_jobs * (uint64_t)wa.L >= n_lines || getenv("PECANPY_AMD_FORCE_TOT"))) return 0;
-    if (!g->d_utot && hipMalloc((void **)&g->d_utot, sizeof(float) * (size_t)(n_lines ? n_lines : 1)) != hipSuccess) {
+    if (!g->gd->d_utot && hipMalloc((void **)&g->gd->d_utot, sizeof(float) * (size_t)(n_lines ? n_lines : 1)) != hipSuccess) {
         (void)hipGetLastError();
-        g->d_utot = nullptr;
-        g->utot_failed = true;
+        g->gd->d_utot = nullptr;
+        g->gd->utot_failed = true;
         return 0;
     }
-    g->utot_wo = g->utot_wp = 0;
+    g->gd->utot_wo = g->gd->utot_wp = 0;
     HIP_TRY(hipEventRecord(g->ev[4], g->stream));
-    hipLaunchKernelGGL(pw::unit_tot_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, g->stream, g->d_lines, g->d_clist, n_lines,
-                       wa.w_out, wa.w_prev, g->d_utot);
+    hipLaunchKernelGGL(pw::unit_tot_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_lines, g->gd->d_clist, n_lines,
+                       wa.w_out, wa.w_prev, g->gd->d_utot);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(g->ev[5], g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     float tms = 0;
     HIP_TRY(hipEventElapsedTime(&tms, g->ev[4], g->ev[5]));
     g->param_ms_call += tms;
-    g->utot_wo = wa.w_out;
-    g->utot_wp = wa.w_prev;
+    g->gd->utot_wo = wa.w_out;
+    g->gd->utot_wp = wa.w_prev;
     return 0;
 }
 
@@ -2225,11 +2229,11 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_re
     if (g->redo.ensure(n_work ? n_work : 1)) return PW_ERR_NOMEM;
     pw::LanesArgs la;
     memset(&la, 0, sizeof(la));
-    la.lines = g->d_lines;
-    la.clist = g->d_clist;
-    la.vlines = g->vlines ? 1u : 0u;
-    la.vrec = g->d_vrec;
-    la.nnz = g->nnz;
+    la.lines = g->gd->d_lines;
+    la.clist = g->gd->d_clist;
+    la.vlines = g->gd->vlines ? 1u : 0u;
+    la.vrec = g->gd->d_vrec;
+    la.nnz = g->gd->nnz;
     la.L = wa.L;
     la.n_jobs = wa.n_jobs;
     la.starts = wa.starts;
@@ -2248,7 +2252,7 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_re
     la.susp_count = g->counters.p + 32;
     la.ver_count = g->counters.p + 40;
     la.susp_chunk = 1;
-    if (g->d_utot && g->utot_wo == wa.w_out && g->utot_wp == wa.w_prev) la.tot_e = g->d_utot;   // (ensure_unit_tot)
+    if (g->gd->d_utot && g->gd->utot_wo == wa.w_out && g->gd->utot_wp == wa.w_prev) la.tot_e = g->gd->d_utot;   // (ensure_unit_tot)
     // verification of the interval decision (round 6: lane_tight_values), as in launch_lane_walks: every settled step in test
     // mode (PECANPY_AMD_VERIFY_TIGHT=1), a sample of them in production (PECANPY_AMD_VERIFY_SAMPLE=N, default 1024, 0 = off)
     const char *ver_env = getenv("PECANPY_AMD_VERIFY_TIGHT");
@@ -2301,7 +2305,7 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, uint64_t *n_re
         const unsigned long long n_chk = n_rec < la.ver_cap ? n_rec : la.ver_cap;
         g->ver_dropped += n_rec - n_chk;
         hipLaunchKernelGGL(pw::lanes_verify_kernel, dim3((unsigned)((n_chk + 255) / 256)), dim3(256), 0, g->stream, g->ver.p, (uint64_t)n_chk,
-                           g->d_lines, g->d_clist, wa.w_prev, g->counters.p + 44, g->ver_bad.p, 16u, g->ver_jobs.p, VER_JOBS_CAP, 1u);
+                           g->gd->d_lines, g->gd->d_clist, wa.w_prev, g->counters.p + 44, g->ver_bad.p, 16u, g->ver_jobs.p, VER_JOBS_CAP, 1u);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(vs, g->counters.p + 44, sizeof(vs), hipMemcpyDeviceToHost, g->stream));
     }
@@ -2525,13 +2529,13 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
                                 pw_stats *stats) {
     if (!g || (n_jobs && (!d_starts || !d_out))) return fail(PW_ERR_INVALID, "null pointer");
     if (!mode_on_the_fly(mode) && !mode_sequential_stream(mode)) return fail(PW_ERR_INVALID, "unknown mode");
-    if (mode == PW_MODE_SPARSE_OTF && g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
-    if (mode == PW_MODE_DENSE_OTF && g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
+    if (mode == PW_MODE_SPARSE_OTF && g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
+    if (mode == PW_MODE_DENSE_OTF && g->gd->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
     const bool n2vpp = mode == PW_MODE_NODE2VEC_PLUSPLUS;
     if (n2vpp) { int rcn = n2vpp_check(g); if (rcn) return rcn; extend = 0; }   // (node2vec++ ignores extend)
     const bool spp = mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
     if (spp) { int rcn = spp_check(g); if (rcn) return rcn; extend = 0; }
-    if (extend && !g->unit && !g->d_thr)
+    if (extend && !g->gd->unit && !g->gd->d_thr)
         return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
     if (walk_length < 1) return fail(PW_ERR_INVALID, "walk_length must be >= 1");
@@ -2559,7 +2563,7 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
     if (rc) return rc;
 
     g->call_runnable = total / walk_length;
-    const bool lanes_pre = g->kind == 0 && g->unit && g->d_lines && !g->lanes_off && mode == PW_MODE_SPARSE_OTF;
+    const bool lanes_pre = g->gd->kind == 0 && g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF;
     // (zero-fill of the walk matrix for the lane kernel: on the side stream, overlapped with the stream expansion.  No
     //  return path may leave that write to the CALLER's buffer in flight: the guard waits for the side stream.)
     struct SideGuard {
@@ -2809,7 +2813,7 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
     st.verify_dropped = g->ver_dropped;
     st.verify_ties = g->ver_ties;
     st.eager_steps = h[12];
-    st.index_max_list = g->kind == 0 && g->d_lines ? g->list_max_len : 0u;
+    st.index_max_list = g->gd->kind == 0 && g->gd->d_lines ? g->gd->list_max_len : 0u;
     if (stats) *stats = st;
     return PW_OK;
 }
@@ -2817,32 +2821,15 @@ static int simulate_device_impl(pw_graph *g, int mode, double p, double q, int e
 // ---- TWIN contexts: the two halves of a weighted job array side by side on one GPU (round 6) --------------------------------
 // The weighted lane form alternates two kernels that leave most of the GPU idle in turn: a lane round (one lane per walk) and
 // the eager kernel that decides what the round parked (one wavefront per record, bound by the latency of its row scans) --
-// 51 % + 48 % of a C5 pass.  Walked as two independent halves on two call contexts (own streams, counters and queues; graph,
-// index and per-(p, q) tables shared), one half's eager kernel runs beside the other half's lane round: C5 417 -> ~330 ms per
-// pass with two plain replicas (tools/replica_bench.py), without a second copy of anything here.  The walks are those of one
-// call: the second half is addressed into the stream by the draws of the first (walked again if dead ends made them fewer).
+// 51 % + 48 % of a C5 pass.  Walked as two independent halves on two call contexts (own streams, counters and queues; one
+// GraphData: graph, index and per-(p, q) tables shared), one half's eager kernel runs beside the other half's lane round:
+// C5 417 -> ~330 ms per pass with two plain replicas (tools/replica_bench.py), without a second copy of anything here.  The
+// walks are those of one call: the second half is addressed into the stream by the draws of the first (walked again if dead
+// ends made them fewer).
 static pw_graph *make_twin(pw_graph *g) {
     pw_graph *t = new pw_graph();
-    if (graph_common_init(t, g->device)) { pw_graph_destroy(t); return nullptr; }
-    t->alias = true;
+    if (graph_common_init(t, g->device, g->gd)) { pw_graph_destroy(t); return nullptr; }
     return t;
-}
-// everything the twin reads of the graph: pointers and the keys that say which (p, q) the tables were built for
-static void twin_share(pw_graph *t, const pw_graph *g) {
-    t->kind = g->kind; t->n_nodes = g->n_nodes; t->nnz = g->nnz; t->unit = g->unit; t->max_degree = g->max_degree;
-    t->d_indptr = g->d_indptr; t->d_indices = g->d_indices; t->d_hasnbr = g->d_hasnbr; t->d_data = g->d_data; t->d_thr = g->d_thr;
-    t->d_adjbits = g->d_adjbits; t->d_deg = g->d_deg; t->bits_only = g->bits_only; t->d_foff = g->d_foff; t->d_fbits = g->d_fbits;
-    t->d_kf = g->d_kf; t->d_tab_off = g->d_tab_off; t->d_slots = g->d_slots; t->d_vrec = g->d_vrec; t->d_lines = g->d_lines;
-    t->d_clist = g->d_clist; t->clist_bytes = g->clist_bytes; t->line_bytes = g->line_bytes; t->vlines = g->vlines;
-    t->has_loop = g->has_loop; t->lanes_off = g->lanes_off; t->n_clist = g->n_clist; t->list_max_len = g->list_max_len;
-    t->words_per_row = g->words_per_row;
-    t->d_tot_e = g->d_tot_e; t->d_tot_v = g->d_tot_v; t->tot_p = g->tot_p; t->tot_q = g->tot_q; t->tot_extend = g->tot_extend;
-    t->tot_thr_version = g->tot_thr_version; t->thr_version = g->thr_version; t->tot_failed = g->tot_failed;
-    t->d_utot = g->d_utot; t->utot_wo = g->utot_wo; t->utot_wp = g->utot_wp; t->utot_failed = g->utot_failed;
-    t->d_wb = g->d_wb; t->d_wpq = g->d_wpq; t->d_wdl = g->d_wdl; t->d_wl_dprev = g->d_wl_dprev; t->d_wl_off = g->d_wl_off;
-    t->d_wedge_row = g->d_wedge_row; t->d_wp1 = g->d_wp1; t->d_wck_off = g->d_wck_off; t->d_wck = g->d_wck; t->wdl_cap = g->wdl_cap;
-    t->wck_cap = g->wck_cap; t->wl_p = g->wl_p; t->wl_q = g->wl_q; t->wl_extend = g->wl_extend; t->wl_thr_version = g->wl_thr_version;
-    t->wl_failed = g->wl_failed;
 }
 
 static void add_stats(pw_stats &total, const pw_stats &st, bool side_by_side) {
@@ -2881,7 +2868,7 @@ static int simulate_twin(pw_graph *g, int mode, double p, double q, int extend, 
     std::promise<bool> ready;
     std::future<bool> ready_f = ready.get_future();
     bool signalled = false;
-    g->on_tables_ready = [&]() { twin_share(t, g); signalled = true; ready.set_value(true); };
+    g->on_tables_ready = [&]() { signalled = true; ready.set_value(true); };
     int rc_b = 0;
     std::string err_b;
     std::thread tb;
@@ -2900,11 +2887,10 @@ static int simulate_twin(pw_graph *g, int mode, double p, double q, int extend, 
     g->on_tables_ready = nullptr;
     if (!signalled) ready.set_value(false);     // (the first half failed before its tables were in place: the second is not walked)
     if (threaded) tb.join();
-    else if (!rc) { twin_share(t, g); run_b(stream_skip + nominal_a); }   // (no thread to be had: one half after the other)
+    else if (!rc) run_b(stream_skip + nominal_a);   // (no thread to be had: one half after the other)
     if (rc) return rc;
     if (rc_b) return fail(rc_b, err_b);
     if (sa.total_steps != nominal_a && !sa.stream_addressing) {   // dead ends in the first half: the second starts earlier in the stream
-        twin_share(t, g);
         run_b(stream_skip + sa.total_steps);
         if (rc_b) return fail(rc_b, err_b);
     }
@@ -2917,8 +2903,8 @@ PW_EXPORT int pw_simulate_device(pw_graph *g, int mode, double p, double q, int 
                                  int has_seed, uint32_t seed, uint64_t stream_skip, uint32_t *d_out,
                                  pw_stats *stats) {
     // weighted CSR graphs on the lane index, whole job arrays of a million walks or more: two halves side by side (above)
-    if (g && !g->alias && g->kind == 0 && !g->unit && g->d_lines && !g->lanes_off && mode == PW_MODE_SPARSE_OTF && n_jobs >= (1ull << 20) &&
-        d_starts && d_out && walk_length >= 1 && p > 0 && q > 0 && (!extend || g->d_thr) && !getenv("PECANPY_AMD_NO_TWIN") &&
+    if (g && g->gd->kind == 0 && !g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF && n_jobs >= (1ull << 20) &&
+        d_starts && d_out && walk_length >= 1 && p > 0 && q > 0 && (!extend || g->gd->d_thr) && !getenv("PECANPY_AMD_NO_TWIN") &&
         !getenv("PECANPY_AMD_NO_LANES") && !getenv("PECANPY_AMD_NO_WLANES") && !getenv("PECANPY_AMD_NO_CHAIN_QUEUE")) {
         if (!has_seed) seed = os_seed();
         return simulate_twin(g, mode, p, q, extend, d_starts, n_jobs, walk_length, seed, stream_skip, d_out, stats);
@@ -3193,7 +3179,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
     for (int i = 0; i < n_handles; i++)
         if (!handles[i]) return fail(PW_ERR_INVALID, "null handle");
     for (int i = 1; i < n_handles; i++)
-        if (handles[i]->n_nodes != handles[0]->n_nodes || handles[i]->nnz != handles[0]->nnz || handles[i]->kind != handles[0]->kind)
+        if (handles[i]->gd->n_nodes != handles[0]->gd->n_nodes || handles[i]->gd->nnz != handles[0]->gd->nnz || handles[i]->gd->kind != handles[0]->gd->kind)
             return fail(PW_ERR_INVALID, "pw_simulate_multi: the handles are not replicas of one graph");
     if (!has_seed) { seed = os_seed(); has_seed = 1; }   // (every shard walks the same stream)
     const size_t W = (size_t)walk_length + 2;
@@ -3282,16 +3268,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
                 if (S.rc) { S.err = g_err; break; }
                 skip_c += st.total_steps;
                 if (c == 0) tot = st;
-                else {
-                    tot.total_steps += st.total_steps; tot.overflow_reads += st.overflow_reads; tot.clamped_reads += st.clamped_reads;
-                    tot.dead_end_walks += st.dead_end_walks; tot.repair_rounds += st.repair_rounds; tot.walk_kernel_ms += st.walk_kernel_ms;
-                    tot.rng_kernel_ms += st.rng_kernel_ms; tot.walk_kernel_launches += st.walk_kernel_launches;
-                    tot.stream_addressing |= st.stream_addressing; tot.lane_rounds += st.lane_rounds; tot.redo_walks += st.redo_walks;
-                    tot.list_entries_read += st.list_entries_read; tot.ambiguous_steps += st.ambiguous_steps; tot.lane_kernel_ms += st.lane_kernel_ms;
-                    tot.wave_chain_steps += st.wave_chain_steps; tot.param_index_ms += st.param_index_ms; tot.verify_checked += st.verify_checked;
-                    tot.verify_mismatch += st.verify_mismatch; tot.verify_dropped += st.verify_dropped; tot.verify_ties += st.verify_ties;
-                    tot.eager_steps += st.eager_steps;
-                }
+                else add_stats(tot, st, false);
                 if (!local) {   // (the walks of this chunk are complete: pw_simulate_device returns after its stream has drained)
                     e = hipMemcpyPeerAsync(out + (S.lo + a) * W, handles[0]->device, S.d_tmp + a * W, g->device, sizeof(uint32_t) * (b - a) * W, g->copy_stream);
                     if (e != hipSuccess) { S.rc = PW_ERR_HIP; S.err = std::string("pw_simulate_multi (peer copy): ") + hipGetErrorString(e); }
@@ -3334,20 +3311,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
     if (rc) return rc;
     if (stats) {
         pw_stats total = sh[0].st;
-        for (int i = 1; i < n_sh; i++) {
-            const pw_stats &st = sh[i].st;
-            total.total_steps += st.total_steps; total.overflow_reads += st.overflow_reads; total.clamped_reads += st.clamped_reads;
-            total.dead_end_walks += st.dead_end_walks; total.repair_rounds += st.repair_rounds;
-            total.walk_kernel_ms = std::max(total.walk_kernel_ms, st.walk_kernel_ms);     // (the shards run side by side)
-            total.rng_kernel_ms = std::max(total.rng_kernel_ms, st.rng_kernel_ms);
-            total.lane_kernel_ms = std::max(total.lane_kernel_ms, st.lane_kernel_ms);
-            total.walk_kernel_launches += st.walk_kernel_launches;
-            total.stream_addressing |= st.stream_addressing; total.lane_rounds = std::max(total.lane_rounds, st.lane_rounds);
-            total.redo_walks += st.redo_walks; total.list_entries_read += st.list_entries_read; total.ambiguous_steps += st.ambiguous_steps;
-            total.wave_chain_steps += st.wave_chain_steps; total.param_index_ms = std::max(total.param_index_ms, st.param_index_ms);
-            total.verify_checked += st.verify_checked; total.verify_mismatch += st.verify_mismatch; total.verify_dropped += st.verify_dropped;
-            total.verify_ties += st.verify_ties; total.eager_steps += st.eager_steps;
-        }
+        for (int i = 1; i < n_sh; i++) add_stats(total, sh[i].st, true);   // (the shards run side by side)
         *stats = total;
     }
     return PW_OK;
@@ -3376,25 +3340,25 @@ static int run_probe_n2vpp(pw_graph *g, double p, double q, uint32_t cur, int ha
     };
     hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
     if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
-    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->max_degree + 1));
+    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->gd->max_degree + 1));
     if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
     pw::ProbeArgs pa;
     pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
     pa.r = r; pa.probs = d_probs; pa.out = d_out;
     pw::DenseWArgs da;
     memset(&da, 0, sizeof(da));
-    da.indptr = g->d_indptr;
-    da.indices = g->d_indices;
-    da.data = (const double *)g->d_data;
-    da.adjbits = g->d_adjbits;
-    da.thr = g->d_thr;
-    da.n = g->n_nodes;
-    da.wpr = g->words_per_row;
+    da.indptr = g->gd->d_indptr;
+    da.indices = g->gd->d_indices;
+    da.data = (const double *)g->gd->d_data;
+    da.adjbits = g->gd->d_adjbits;
+    da.thr = g->gd->d_thr;
+    da.n = g->gd->n_nodes;
+    da.wpr = g->gd->words_per_row;
     da.p = p;
     da.q = q;
     const size_t lds = (size_t)da.wpr * 12u;
     typedef void (*dwp_fn)(pw::DenseWArgs, const pw::ProbeArgs *);
-    dwp_fn fn = g->unit ? pw::dense_w_probe_kernel<pw::DW_N2VPP_UNIT> : pw::dense_w_probe_kernel<pw::DW_N2VPP>;
+    dwp_fn fn = g->gd->unit ? pw::dense_w_probe_kernel<pw::DW_N2VPP_UNIT> : pw::dense_w_probe_kernel<pw::DW_N2VPP>;
     uint32_t zero[4] = {0, 0, 0, 0};
     e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
@@ -3426,14 +3390,14 @@ static int run_probe_spp(pw_graph *g, double p, double q, uint32_t cur, int has_
     };
     hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
     if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
-    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->max_degree + 1));
+    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->gd->max_degree + 1));
     if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
     pw::ProbeArgs pa;
     pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
     pa.r = r; pa.probs = d_probs; pa.out = d_out;
     const pw::SparsePPArgs sa = spp_args(g, p, q);
     typedef void (*spp_probe_fn)(pw::SparsePPArgs, const pw::ProbeArgs *);
-    spp_probe_fn fn = g->unit ? pw::sparse_pp_probe_kernel<true> : pw::sparse_pp_probe_kernel<false>;
+    spp_probe_fn fn = g->gd->unit ? pw::sparse_pp_probe_kernel<true> : pw::sparse_pp_probe_kernel<false>;
     uint32_t zero[4] = {0, 0, 0, 0};
     e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
@@ -3454,20 +3418,20 @@ static int run_probe_spp(pw_graph *g, double p, double q, uint32_t cur, int has_
 static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint32_t cur, int has_prev, uint32_t prev, double r,
                      void *probs_host, uint32_t *out_host) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    if (mode == PW_MODE_SPARSE_OTF && g->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
-    if (mode == PW_MODE_DENSE_OTF && g->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
+    if (mode == PW_MODE_SPARSE_OTF && g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
+    if (mode == PW_MODE_DENSE_OTF && g->gd->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
     if (!mode_on_the_fly(mode)) return fail(PW_ERR_UNSUPPORTED, "single steps are provided for the on-the-fly modes");
     if (mode == PW_MODE_NODE2VEC_PLUSPLUS) { int rcn = n2vpp_check(g); if (rcn) return rcn; }
     if (mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS) { int rcn = spp_check(g); if (rcn) return rcn; }
-    if (g->bits_only) return fail(PW_ERR_UNSUPPORTED, "dense graph created from packed bits has no compressed rows");
+    if (g->gd->bits_only) return fail(PW_ERR_UNSUPPORTED, "dense graph created from packed bits has no compressed rows");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
-    if (cur >= g->n_nodes || (has_prev && prev >= g->n_nodes)) return fail(PW_ERR_INVALID, "vertex out of range");
+    if (cur >= g->gd->n_nodes || (has_prev && prev >= g->gd->n_nodes)) return fail(PW_ERR_INVALID, "vertex out of range");
     if (mode == PW_MODE_NODE2VEC_PLUSPLUS) return run_probe_n2vpp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
     if (mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS) return run_probe_spp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
-    if (extend && !g->unit && !g->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
+    if (extend && !g->gd->unit && !g->gd->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (set_device(g)) return PW_ERR_HIP;
-    const bool ext = extend && !g->unit;
-    const size_t elem = g->kind == 0 ? sizeof(float) : sizeof(double);
+    const bool ext = extend && !g->gd->unit;
+    const size_t elem = g->gd->kind == 0 ? sizeof(float) : sizeof(double);
     pw::ProbeArgs *d_pa = nullptr;
     uint32_t *d_out = nullptr;
     void *d_probs = nullptr;
@@ -3478,7 +3442,7 @@ static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint
     };
     hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
     if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
-    if (e == hipSuccess && probs_host) e = hipMalloc(&d_probs, elem * ((size_t)g->max_degree + 1));
+    if (e == hipSuccess && probs_host) e = hipMalloc(&d_probs, elem * ((size_t)g->gd->max_degree + 1));
     if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
     pw::ProbeArgs pa;
     pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
@@ -3492,9 +3456,9 @@ static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint
     wa.w_out = (float)(1.0 / q);
     wa.w_prev = (float)(1.0 / p);
     probe_kernel_fn fn;
-    if (g->kind == 0) fn = g->unit ? pw::step_probe_kernel<float, false, true, false>
+    if (g->gd->kind == 0) fn = g->gd->unit ? pw::step_probe_kernel<float, false, true, false>
                                     : (ext ? pw::step_probe_kernel<float, false, false, true> : pw::step_probe_kernel<float, false, false, false>);
-    else fn = g->unit ? pw::step_probe_kernel<double, true, true, false>
+    else fn = g->gd->unit ? pw::step_probe_kernel<double, true, true, false>
                       : (ext ? pw::step_probe_kernel<double, true, false, true> : pw::step_probe_kernel<double, true, false, false>);
     uint32_t zero[4] = {0, 0, 0, 0};
     e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
