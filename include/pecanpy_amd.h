@@ -268,10 +268,31 @@ int pw_stream_release(pw_graph *g);
  * Not bit-comparable with gensim itself (its own random streams; not installed here).
  *   walks   host uint32[n_walks, walk_length + 2] as pw_simulate returns it (indices into 0..n_nodes-1; a node id
  *           >= n_nodes or a length cell > walk_length + 1 is rejected with PW_ERR_INVALID)
- *   vectors host float32[n_nodes, dim] (out), dim <= 512 */
+ *   vectors host float32[n_nodes, dim] (out), dim <= 512
+ * walk_length must be below 8192 (the thinned walk of a wavefront lives in LDS).  pw_sgns_train is upload ->
+ * pw_sgns_train_device -> download: one preparation path, one kernel. */
 int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
                   uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
                   float sample, uint32_t seed, uint32_t workers, float *vectors);
+
+/* What a training call did.  vocab_ms: counting pass, noise table, keep probabilities and their upload (host clock);
+ * init_ms: syn0 initialisation and upload (host clock); train_ms: the training kernels of all epochs (hipEvent). */
+typedef struct pw_sgns_stats {
+    double vocab_ms, init_ms, train_ms;
+    uint64_t kept_occurrences; /* occurrences that survived the subsampling, summed over the epochs */
+    uint64_t trained_pairs;    /* (centre, context) pairs, each updating negative + 1 target rows at most */
+    uint64_t wavefronts;       /* wavefronts of one training launch */
+} pw_sgns_stats;
+
+/* The same trainer on a walk matrix that is already in device memory, where pw_simulate_device leaves it: no copy of
+ * the matrix in either direction (the word counts come down and the tables go up: tens of MB).
+ *   d_walks   device uint32[n_walks, walk_length + 2] on `device` (same checks and error texts as pw_sgns_train)
+ *   d_vectors device float32[n_nodes, dim] on `device` (out; trained in place)
+ *   stats     may be NULL
+ * Work is queued on the device's default stream; the call returns after it has finished. */
+int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                         uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                         float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats);
 
 /* ---- random stream service (host side; usable without a GPU) ---------------------------- */
 /* doubles #offset.. of RandomState(seed).random_sample, produced with MT19937 jump-ahead. */

@@ -44,6 +44,21 @@ class PwStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwSgnsStats(C.Structure):
+    """``pw_sgns_stats`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("vocab_ms", C.c_double),
+        ("init_ms", C.c_double),
+        ("train_ms", C.c_double),
+        ("kept_occurrences", C.c_uint64),
+        ("trained_pairs", C.c_uint64),
+        ("wavefronts", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 MODE_IDS = {
     "SparseOTF": 0,
     "DenseOTF": 1,
@@ -93,6 +108,8 @@ SYMBOLS = {
     "pw_stream_release": (C.c_int, [C.c_void_p]),
     "pw_sgns_train": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                 C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "pw_sgns_train_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_stream_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_noise_thresholds_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),

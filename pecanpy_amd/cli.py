@@ -3,7 +3,8 @@
 Flag names, defaults, the mode sanity rules and the stage order follow the reference CLI
 (src/pecanpy/cli.py: flags :27-176, ``check_mode`` :179-254, ``read_graph`` :257-304, pipeline
 :307-351) so that existing invocations keep working.  Walks come from the GPU; the skip-gram stage
-uses gensim when it is importable and otherwise writes the walks (one per line) to ``--output``.
+uses gensim when it is importable; without it walks and skip-gram both run on the GPU (``Base.embed_array``: the
+walk matrix stays in device memory).  ``PECANPY_AMD_DUMP_WALKS=1`` writes the walks (one per line) to ``--output``.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
 """
@@ -164,14 +165,11 @@ def learn_embeddings(args, walks, g=None):
             warnings.warn(f"gensim is not installed and no graph was passed: {len(walks)} walks written to "
                           f"{args.output} instead of embeddings", stacklevel=2)
             return
-        from .embed import save_word2vec_format, train_sgns
+        from .embed import train_sgns
 
         vecs = train_sgns(_walk_matrix(g, walks), g.num_nodes, dim=args.dimensions, window=args.window_size,
                           epochs=args.epochs, seed=args.random_state)
-        if args.output.endswith(".npz"):
-            np.savez(args.output, IDs=g.nodes, data=vecs)
-        else:
-            save_word2vec_format(args.output, g.nodes, vecs)
+        _save_vectors(args, g, vecs)
         return
     w2v = Word2Vec(walks, vector_size=args.dimensions, window=args.window_size, min_count=0, sg=1,
                    workers=args.workers, epochs=args.epochs, seed=args.random_state)
@@ -182,13 +180,45 @@ def learn_embeddings(args, walks, g=None):
         vectors.save_word2vec_format(args.output)
 
 
+def _gpu_route():
+    """Graph -> vectors without ID lists: taken when gensim is absent and the walks are not asked for as text."""
+    if os.environ.get("PECANPY_AMD_DUMP_WALKS"):
+        return False
+    try:
+        import gensim  # noqa: F401
+    except ImportError:
+        return True
+    return False
+
+
+def _save_vectors(args, g, vecs):
+    if args.output.endswith(".npz"):
+        np.savez(args.output, IDs=g.nodes, data=vecs)
+    else:
+        from .embed import save_word2vec_format
+
+        save_word2vec_format(args.output, g.nodes, vecs)
+
+
+@Timer("generate walks + train embeddings")
+def embed_on_gpu(args, g):
+    """Walks and skip-gram in device memory (``Base.embed_array``), the vectors written as ``learn_embeddings`` writes
+    them; no ``List[List[str]]`` corpus and no index matrix on the host."""
+    vecs = g.embed_array(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
+                         window_size=args.window_size, epochs=args.epochs)
+    _save_vectors(args, g, vecs)
+
+
 def main(argv=None):
     """read graph -> preprocess -> walks (GPU) -> embeddings."""
     args = parse_args(argv)
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)
     preprocess(g)
-    learn_embeddings(args, simulate_walks(args, g), g)
+    if _gpu_route():
+        embed_on_gpu(args, g)
+    else:
+        learn_embeddings(args, simulate_walks(args, g), g)
 
 
 if __name__ == "__main__":

@@ -3500,32 +3500,45 @@ PW_EXPORT int pw_probs(pw_graph *g, int mode, double p, double q, int extend, ui
 }
 
 // ---- skip-gram with negative sampling over a walk matrix (sgns.hip.h) -------------------------
-PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
-                            uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
-                            float sample, uint32_t seed, uint32_t workers, float *vectors) {
-    if (!walks || !vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+template <int PER>
+static void sgns_launch(unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
+    hipLaunchKernelGGL(pw::sgns_walk_kernel<PER>, dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep);
+}
+
+PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                                   uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                                   float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats) {
+    if (!d_walks || !d_vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
     if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
     if (window == 0 || epochs == 0) return fail(PW_ERR_INVALID, "window and epochs must be positive");
+    const uint32_t L = walk_length;
+    // the survivors of a walk live in the wavefront's LDS: four wavefronts to a workgroup while that fits, else one
+    const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
+    if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
+    const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
     int ndev = pw_device_count();
     if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
-    const uint32_t L = walk_length;
-    const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)L + 2), vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    uint32_t *d_walks = nullptr, *d_table = nullptr;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    const size_t vbytes = sizeof(float) * (size_t)n_nodes * dim;
+    uint32_t *d_table = nullptr;
     unsigned long long *d_cnt = nullptr;
-    float *d_syn0 = nullptr, *d_syn1 = nullptr, *d_keep = nullptr;
+    float *d_syn1 = nullptr, *d_keep = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     auto cleanup = [&]() {
-        for (void *q : {(void *)d_walks, (void *)d_table, (void *)d_cnt, (void *)d_syn0, (void *)d_syn1, (void *)d_keep})
+        for (void *q : {(void *)d_table, (void *)d_cnt, (void *)d_syn1, (void *)d_keep})
             if (q) (void)hipFree(q);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
     };
     auto bail = [&](int code, const std::string &msg) { cleanup(); return fail(code, msg); };
-    hipError_t e = hipMalloc((void **)&d_walks, wbytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cnt, sizeof(unsigned long long) * ((size_t)n_nodes + 1));   // [n_nodes]: first bad walk
-    if (e == hipSuccess) e = hipMalloc((void **)&d_syn0, vbytes);
+    auto t_vocab = clk::now();
+    // d_cnt: [0, n_nodes) word counts, [n_nodes] first bad walk, [n_nodes + 1, n_nodes + 3) the training kernel's counters
+    hipError_t e = hipMalloc((void **)&d_cnt, sizeof(unsigned long long) * ((size_t)n_nodes + 3));
     if (e == hipSuccess) e = hipMalloc((void **)&d_syn1, vbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_walks, walks, wbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * (size_t)n_nodes);
+    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * ((size_t)n_nodes + 3));
     if (e == hipSuccess) e = hipMemset(d_cnt + n_nodes, 0xff, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(d_syn1, 0, vbytes);
     if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
@@ -3562,50 +3575,114 @@ PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks,
         for (uint32_t i = 0; i < n_nodes; i++)
             keep[i] = cnt[i] ? (float)std::min(1.0, (std::sqrt((double)cnt[i] / thr) + 1.0) * thr / (double)cnt[i]) : 1.0f;
     }
-    // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded
-    std::vector<float> init((size_t)n_nodes * dim);
+    e = hipMalloc((void **)&d_table, sizeof(uint32_t) * (size_t)table_size);
+    if (e == hipSuccess) e = hipMemcpy(d_table, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
+    if (e == hipSuccess && sample > 0) {
+        e = hipMalloc((void **)&d_keep, sizeof(float) * (size_t)n_nodes);
+        if (e == hipSuccess) e = hipMemcpy(d_keep, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    const double vocab_ms = ms_since(t_vocab);
+    // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded; trained in place in the caller's buffer
+    auto t_init = clk::now();
     {
+        std::vector<float> init((size_t)n_nodes * dim);
         uint64_t x = 0x9E3779B97F4A7C15ull ^ ((uint64_t)seed << 17);
         for (auto &f : init) {
             x = x * 6364136223846793005ull + 1442695040888963407ull;
             f = (((float)((x >> 40) & 0xffffff) / 16777216.0f) - 0.5f) / (float)dim;
         }
-    }
-    e = hipMalloc((void **)&d_table, sizeof(uint32_t) * (size_t)table_size);
-    if (e == hipSuccess) e = hipMemcpy(d_table, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_syn0, init.data(), vbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && sample > 0) {
-        e = hipMalloc((void **)&d_keep, sizeof(float) * (size_t)n_nodes);
-        if (e == hipSuccess) e = hipMemcpy(d_keep, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
+        e = hipMemcpy(d_vectors, init.data(), vbytes, hipMemcpyHostToDevice);
     }
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+    if (e == hipSuccess) e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
     if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    const double init_ms = ms_since(t_init);
     pw::SgnsArgs a;
     a.walks = d_walks; a.n_walks = n_walks; a.L = L; a.dim = dim; a.window = window; a.negative = negative;
-    a.syn0 = d_syn0; a.syn1 = d_syn1; a.table = d_table; a.table_size = table_size; a.keep = d_keep;
+    a.syn0 = d_vectors; a.syn1 = d_syn1; a.table = d_table; a.table_size = table_size; a.keep = d_keep;
     a.alpha = alpha; a.min_alpha = min_alpha; a.item_total = n_items * epochs; a.seed = seed;
-    // concurrency.  workers == 1: ONE wavefront walks the corpus in sentence order (deterministic: the run gensim's
-    // workers=1 corresponds to; compared with oracle/sgns_ref.c).  workers == 0: as many wavefronts as keep hogwild
-    // collisions rare -- far more wavefronts than vocabulary rows in flight would overwrite most updates of a small
-    // graph: at least ~256 items per wavefront.  workers > 1: that many wavefronts.
-    unsigned blocks, threads = 256;
+    a.counters = d_cnt + n_nodes + 1;
+    // concurrency.  workers == 1: ONE wavefront takes the walks in order (deterministic: the run gensim's workers=1
+    // corresponds to; compared with oracle/sgns_ref.c).  workers == 0: as many wavefronts as keep hogwild collisions
+    // rare -- far more wavefronts than vocabulary rows in flight would overwrite most updates of a small graph.  The rule
+    // "at least ~256 items per wavefront, at most 8 workgroups per CU" is now counted in walks: a wavefront owns at least
+    // ceil(256 / (L + 1)) walks (4 for the default 80-step walks), and the cap is 32 wavefronts per CU whatever the
+    // workgroup size.  workers > 1: that many wavefronts (rounded up to whole workgroups).
+    unsigned blocks, threads = 64 * waves_per_block;
     if (workers == 1) { blocks = 1; threads = 64; }
-    else if (workers > 1) blocks = (workers + 3) / 4;
+    else if (workers > 1) blocks = (workers + waves_per_block - 1) / waves_per_block;
     else {
-        const uint64_t want_blocks = (n_items + 1023) / 1024;
-        blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want_blocks, (uint64_t)prop.multiProcessorCount * 8));
+        const uint64_t walks_per_wave = (256 + (uint64_t)L) / ((uint64_t)L + 1);
+        const uint64_t want_waves = (n_walks + walks_per_wave - 1) / walks_per_wave;
+        const uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>(want_waves, (uint64_t)prop.multiProcessorCount * 32));
+        blocks = (unsigned)((waves + waves_per_block - 1) / waves_per_block);
     }
+    const size_t lds = lds_wave * (threads / 64);
+    a.n_waves = blocks * (threads / 64);
+    const int per = (int)((dim + 63) / 64);
+    (void)hipEventRecord(ev0, 0);
     for (uint32_t ep = 0; ep < epochs; ep++) {
         a.item_base = n_items * ep;
-        hipLaunchKernelGGL(pw::sgns_kernel, dim3(blocks), dim3(threads), 0, 0, a);
+        switch (per) {   // one instance per count of components per lane: only the last component needs a lane guard
+        case 1: sgns_launch<1>(blocks, threads, lds, a); break;
+        case 2: sgns_launch<2>(blocks, threads, lds, a); break;
+        case 3: sgns_launch<3>(blocks, threads, lds, a); break;
+        case 4: sgns_launch<4>(blocks, threads, lds, a); break;
+        case 5: sgns_launch<5>(blocks, threads, lds, a); break;
+        case 6: sgns_launch<6>(blocks, threads, lds, a); break;
+        case 7: sgns_launch<7>(blocks, threads, lds, a); break;
+        default: sgns_launch<8>(blocks, threads, lds, a); break;
+        }
     }
+    (void)hipEventRecord(ev1, 0);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(vectors, d_syn0, vbytes, hipMemcpyDeviceToHost);
+    float train_ms = 0;
+    unsigned long long counters[2] = {0, 0};
+    if (e == hipSuccess) e = hipEventElapsedTime(&train_ms, ev0, ev1);
+    if (e == hipSuccess) e = hipMemcpy(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost);
     cleanup();
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    if (stats) {
+        stats->vocab_ms = vocab_ms; stats->init_ms = init_ms; stats->train_ms = train_ms;
+        stats->kept_occurrences = counters[0]; stats->trained_pairs = counters[1];
+        stats->wavefronts = (uint64_t)blocks * (threads / 64);
+    }
     return PW_OK;
+}
+
+// host-matrix entry: upload, the device entry, download
+PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                            uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                            float sample, uint32_t seed, uint32_t workers, float *vectors) {
+    if (!walks || !vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+    if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
+    int ndev = pw_device_count();
+    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2), vbytes = sizeof(float) * (size_t)n_nodes * dim;
+    uint32_t *d_walks = nullptr;
+    float *d_vectors = nullptr;
+    auto cleanup = [&]() {
+        if (d_walks) (void)hipFree(d_walks);
+        if (d_vectors) (void)hipFree(d_vectors);
+    };
+    hipError_t e = hipMalloc((void **)&d_walks, wbytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_vectors, vbytes);
+    if (e == hipSuccess) e = hipMemcpy(d_walks, walks, wbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e)); }
+    int rc = pw_sgns_train_device(device, d_walks, n_walks, walk_length, n_nodes, dim, window, negative, epochs, alpha, min_alpha,
+                                  sample, seed, workers, d_vectors, nullptr);
+    if (rc == PW_OK) {
+        e = hipMemcpy(vectors, d_vectors, vbytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    }
+    cleanup();
+    return rc;
 }
 
 // ---- host self test of the exact-arithmetic decision ---------------------------------------------------

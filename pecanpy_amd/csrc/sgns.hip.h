@@ -7,12 +7,21 @@
 //   the centre (label 1) and `negative` words drawn from the unigram^0.75 table (label 0),
 //   g = (label - sigmoid(v.u)) * lr, u += g v, v += sum g u; learning rate decaying linearly over the run.
 // Every random choice is a hash of (seed, epoch, walk, position[, context, draw]) -- no generator state -- so the set
-// of updates is a function of the seed alone; what the hardware adds is their ORDER: one wavefront per (walk,
-// position), hogwild (unsynchronised) like gensim's worker threads.  With ONE wavefront (pw_sgns_train: workers = 1)
-// the updates run in sentence order and the result is compared with the sequential CPU restatement
-// (oracle/sgns_ref.c, tests/test_gpu_sgns.py) within float tolerance.
-// The `dim` components of a vector are spread over the 64 lanes, dot products are wave reductions.
+// of updates is a function of the seed alone; what the hardware adds is their ORDER.
+//
+// Walk-resident kernel: a wavefront owns a WALK and visits its positions in order (hogwild -- unsynchronised, like gensim's
+// worker threads -- is over walks).  Per (epoch, walk) the subsampling decision of every occurrence is taken once, 64
+// occurrences per ballot word, and the survivors are compacted into LDS as (position, node) pairs; the window of a centre
+// over the thinned walk is then index arithmetic on that list: no hash and no dependent keep[row[p]] load per neighbour.
+// Per (centre, context) pair the chain of target indices (it depends on no vector data) is evaluated first and the rows of
+// syn1 are requested together, SGNS_GROUP at a time, then consumed in order; a target that repeats inside a group is read
+// again after the row was written, so the sequential semantics hold.  The arithmetic order is the restatement's
+// (oracle/sgns_ref.c): component k on lane k % 64, per-lane partial sums in ascending k, xor butterfly 32 -> 1, neu1e
+// accumulated in draw order.  With ONE wavefront (pw_sgns_train*: workers = 1) the updates run in sentence order and the
+// result is compared with that restatement within float tolerance (tests/test_gpu_sgns.py, tests/test_gpu_embed_device.py).
+// The kernel writes global memory through vector stores only; the two counters are per-lane atomics of lane 0, once per walk.
 #pragma once
+#include <cstddef>
 #include "wave.h"
 
 namespace pw {
@@ -29,6 +38,8 @@ struct SgnsArgs {
     float alpha, min_alpha;
     uint64_t item_base, item_total;       // position of this launch in the whole run (learning-rate schedule)
     uint64_t seed;
+    uint32_t n_waves;                     // wavefronts of the launch (the stride of a wavefront over the walks)
+    unsigned long long *counters;         // [0] occurrences that survived the subsampling, [1] (centre, context) pairs trained
 };
 
 __device__ __forceinline__ uint64_t sgns_mix(uint64_t x) {
@@ -42,82 +53,150 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 constexpr int SGNS_MAX_PER_LANE = 8;   // dim <= 512
+constexpr int SGNS_GROUP = 6;          // target rows requested together (negative + 1 of the default model)
 
+// LDS of one wavefront: positions and nodes of the occurrences of its walk that survived the subsampling
+__host__ __device__ inline size_t sgns_lds_bytes_per_wave(uint32_t L) { return sizeof(uint32_t) * 2 * ((size_t)L + 1); }
+
+// PER: components per lane, 64 * (PER - 1) < dim <= 64 * PER: only the last component of a lane can lie beyond dim, so one
+// lane mask (`tail`) guards it and the others are read and written without a guard
+template <int PER>
 __global__ void __launch_bounds__(256)
-sgns_kernel(SgnsArgs a) {
+sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t *__restrict__ table, const float *__restrict__ keep) {
+    // (walks / table / keep once more as arguments of their own: __restrict__ on a kernel argument is what lets the compiler
+    // read them through the scalar cache although the loop stores to syn0 / syn1)
+    extern __shared__ uint32_t sgns_lds[];
     const int lane = lane_id();
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / WAVE;
-    const uint32_t W = a.L + 2, per = (a.dim + WAVE - 1) / WAVE;
-    const uint64_t n_items = a.n_walks * (uint64_t)(a.L + 1);
-    for (uint64_t item = wave; item < n_items; item += n_waves) {
-        const uint64_t wk = item / (a.L + 1);
-        const uint32_t pos = (uint32_t)(item - wk * (a.L + 1));
-        const uint32_t *row = a.walks + wk * W;
-        const uint32_t len = row[a.L + 1];
-        if (pos >= len) continue;
-        // occurrence (walk, p) of this epoch survives the subsampling?  (every wavefront that meets it agrees)
-        const uint64_t occ0 = a.item_base + wk * (uint64_t)(a.L + 1);
+    const uint32_t wib = readfirst_u32(threadIdx.x / WAVE), wpb = blockDim.x / WAVE;   // (uniform: walk state lives in SGPRs)
+    const uint32_t wave = blockIdx.x * wpb + wib;
+    const uint32_t L1 = a.L + 1;
+    const bool tail = (uint32_t)lane < a.dim - 64u * (PER - 1);
+    uint32_t *kpos = sgns_lds + (size_t)wib * 2 * L1, *knode = kpos + L1;
+    // arguments that are needed once per walk or once per centre are read again from the kernarg segment where they are
+    // used (wave.h: kernarg) instead of living in SGPRs across the pair loop, which needs every one of them
+#define SGNS_ARG(T, field) kernarg<T>(offsetof(SgnsArgs, field))
+    for (uint64_t wk = wave; wk < SGNS_ARG(uint64_t, n_walks); wk += SGNS_ARG(uint32_t, n_waves)) {
+        const uint32_t *row = walks + wk * (uint64_t)(a.L + 2);      // (L < 8192)
+        const uint32_t len = min(row[L1], L1);                        // (the count kernel rejected longer; bounds the LDS writes)
+        const uint64_t occ0 = SGNS_ARG(uint64_t, item_base) + wk * (uint64_t)L1;
 #define occ(p) sgns_mix(a.seed ^ (occ0 + (p)) * 0x9E3779B97F4A7C15ull)
-#define kept(p) (!a.keep || (float)(occ(p) >> 40) * (1.0f / 16777216.0f) < a.keep[row[p]])
-        if (!kept(pos)) continue;
-        const uint32_t centre = row[pos];
-        uint64_t rs = sgns_mix(occ(pos));
-        const uint32_t eff = a.window - (uint32_t)(rs % a.window);                              // shrunk window, 1 .. window
-        const float lr = fmaxf(a.min_alpha, a.alpha - (a.alpha - a.min_alpha) * (float)((double)(a.item_base + item) / (double)a.item_total));
-        // the window over the thinned walk: up to eff surviving positions on either side
-        uint32_t lo = pos, hi = pos, got = 0;
-        for (uint32_t c = pos; c-- > 0 && got < eff;) if (kept(c)) { lo = c; got++; }
-        got = 0;
-        for (uint32_t c = pos + 1; c < len && got < eff; c++) if (kept(c)) { hi = c; got++; }
-        for (uint32_t c = lo; c <= hi; c++) {
-            if (c == pos || !kept(c)) continue;
-            const uint32_t ctx = row[c];
-            rs = sgns_mix(rs + c);
-            float *v = a.syn0 + (uint64_t)ctx * a.dim;
-            float vin[SGNS_MAX_PER_LANE], acc[SGNS_MAX_PER_LANE];
-#pragma unroll
-            for (int t = 0; t < SGNS_MAX_PER_LANE; t++) {
-                const uint32_t k = (uint32_t)t * WAVE + lane;
-                vin[t] = (t < (int)per && k < a.dim) ? v[k] : 0.0f;
-                acc[t] = 0.0f;
+        // which occurrences of this epoch survive the subsampling: one ballot per 64, compacted in walk order
+        wave_lds_fence();                                             // (the previous walk's readers are done)
+        uint32_t nk = 0;
+        for (uint32_t base = 0; base < len; base += WAVE) {
+            const uint32_t p = base + lane;
+            bool k = p < len;
+            uint32_t node = 0;
+            if (k) {
+                node = row[p];
+                if (keep) k = (float)(occ(p) >> 40) * (1.0f / 16777216.0f) < keep[node];
             }
-            for (uint32_t ng = 0; ng <= a.negative; ng++) {
-                uint32_t target = centre;
-                if (ng) {
-                    rs = sgns_mix(rs + ng);
-                    target = a.table[(uint32_t)(rs >> 16) % a.table_size];
-                    if (target == centre) continue;
-                }
-                float *u = a.syn1 + (uint64_t)target * a.dim;
-                float uu[SGNS_MAX_PER_LANE], dot = 0.0f;
+            const uint64_t m = ballot(k);
+            if (k) {
+                const uint32_t j = nk + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                kpos[j] = p;
+                knode[j] = node;
+            }
+            nk += (uint32_t)__popcll(m);
+        }
+        wave_lds_fence();
+        uint32_t n_pairs = 0;
+        for (uint32_t j = 0; j < nk; j++) {
+            const uint32_t pos = readfirst_u32(kpos[j]), centre = readfirst_u32(knode[j]);
+            uint64_t rs = sgns_mix(occ(pos));
+            const uint32_t window = SGNS_ARG(uint32_t, window);
+            const uint32_t eff = window - (uint32_t)(rs % window);                              // shrunk window, 1 .. window
+            const float alpha = SGNS_ARG(float, alpha), min_alpha = SGNS_ARG(float, min_alpha);
+            const float lr = fmaxf(min_alpha, alpha - (alpha - min_alpha) * (float)((double)(occ0 + pos) / (double)SGNS_ARG(uint64_t, item_total)));
+            // the window over the thinned walk: up to eff survivors on either side
+            const uint32_t lo = j - min(eff, j), hi = j + min(eff, nk - 1 - j);
+            for (uint32_t i = lo; i <= hi; i++) {
+                if (i == j) continue;
+                const uint32_t c = readfirst_u32(kpos[i]), ctx = readfirst_u32(knode[i]);
+                rs = sgns_mix(rs + c);
+                float *v = a.syn0 + (uint64_t)ctx * a.dim;
+                float vin[PER], acc[PER];
 #pragma unroll
-                for (int t = 0; t < SGNS_MAX_PER_LANE; t++) {
-                    const uint32_t k = (uint32_t)t * WAVE + lane;
-                    uu[t] = (t < (int)per && k < a.dim) ? u[k] : 0.0f;
-                    dot += vin[t] * uu[t];
+                for (int s = 0; s < PER; s++) {
+                    const uint32_t k = (uint32_t)s * WAVE + lane;
+                    vin[s] = (s < PER - 1 || tail) ? v[k] : 0.0f;
+                    acc[s] = 0.0f;
                 }
-                dot = wave_sum(dot);
-                const float sig = dot > 6.0f ? 1.0f : (dot < -6.0f ? 0.0f : 1.0f / (1.0f + __expf(-dot)));
-                const float g = ((ng == 0 ? 1.0f : 0.0f) - sig) * lr;
+                for (uint32_t g0 = 0; g0 <= a.negative; g0 += SGNS_GROUP) {
+                    // the targets of this group: the chain of draws reads no vector
+                    uint32_t tgt[SGNS_GROUP];
+                    uint32_t act = 0;                                  // bit t: target t is trained
 #pragma unroll
-                for (int t = 0; t < SGNS_MAX_PER_LANE; t++) {
-                    const uint32_t k = (uint32_t)t * WAVE + lane;
-                    if (t < (int)per && k < a.dim) {
-                        acc[t] += g * uu[t];
-                        u[k] = uu[t] + g * vin[t];
+                    for (int t = 0; t < SGNS_GROUP; t++) {
+                        // (no branch: the table reads of a group are independent of each other and go out together)
+                        const uint32_t ng = g0 + (uint32_t)t;
+                        const bool draw = ng != 0 && ng <= a.negative;
+                        const uint64_t next = sgns_mix(rs + ng);
+                        rs = draw ? next : rs;
+                        const uint32_t drawn = table[(uint32_t)(rs >> 16) % a.table_size];
+                        tgt[t] = draw ? drawn : centre;
+                        act |= (uint32_t)(ng <= a.negative && !(draw && drawn == centre)) << t;
+                    }
+                    uint32_t again = 0;                                // bit t: an earlier target of the group writes row t first
+#pragma unroll
+                    for (int t = 1; t < SGNS_GROUP; t++)
+#pragma unroll
+                        for (int e = 0; e < t; e++) again |= (uint32_t)((act >> e & 1u) && tgt[e] == tgt[t]) << t;
+                    // their rows, requested together
+                    float uu[SGNS_GROUP][PER];
+#pragma unroll
+                    for (int t = 0; t < SGNS_GROUP; t++) {
+                        const float *u = a.syn1 + (uint64_t)tgt[t] * a.dim;
+#pragma unroll
+                        for (int s = 0; s < PER; s++) {
+                            const uint32_t k = (uint32_t)s * WAVE + lane;
+                            uu[t][s] = ((act >> t & 1u) && (s < PER - 1 || tail)) ? u[k] : 0.0f;
+                        }
+                    }
+                    // consumed in order
+#pragma unroll
+                    for (int t = 0; t < SGNS_GROUP; t++) {
+                        if (!(act >> t & 1u)) continue;
+                        float *u = a.syn1 + (uint64_t)tgt[t] * a.dim;
+                        if (again >> t & 1u) {                          // read the row again, after the store
+#pragma unroll
+                            for (int s = 0; s < PER; s++) {
+                                const uint32_t k = (uint32_t)s * WAVE + lane;
+                                uu[t][s] = (s < PER - 1 || tail) ? u[k] : 0.0f;
+                            }
+                        }
+                        float dot = 0.0f;
+#pragma unroll
+                        for (int s = 0; s < PER; s++) dot += vin[s] * uu[t][s];
+                        dot = wave_sum(dot);
+                        const float sig = dot > 6.0f ? 1.0f : (dot < -6.0f ? 0.0f : 1.0f / (1.0f + __expf(-dot)));
+                        const float g = ((g0 + (uint32_t)t == 0 ? 1.0f : 0.0f) - sig) * lr;
+#pragma unroll
+                        for (int s = 0; s < PER; s++) {
+                            const uint32_t k = (uint32_t)s * WAVE + lane;
+                            if (s < PER - 1 || tail) {
+                                acc[s] += g * uu[t][s];
+                                u[k] = uu[t][s] + g * vin[s];
+                            }
+                        }
                     }
                 }
-            }
 #pragma unroll
-            for (int t = 0; t < SGNS_MAX_PER_LANE; t++) {
-                const uint32_t k = (uint32_t)t * WAVE + lane;
-                if (t < (int)per && k < a.dim) v[k] = vin[t] + acc[t];
+                for (int s = 0; s < PER; s++) {
+                    const uint32_t k = (uint32_t)s * WAVE + lane;
+                    if (s < PER - 1 || tail) v[k] = vin[s] + acc[s];
+                }
+                n_pairs++;
             }
         }
 #undef occ
-#undef kept
+        unsigned long long *counters = SGNS_ARG(unsigned long long *, counters);
+        if (counters && lane == 0 && nk) {                            // (per walk: two atomics against thousands of row updates)
+            atomicAdd(&counters[0], (unsigned long long)nk);
+            atomicAdd(&counters[1], (unsigned long long)n_pairs);
+        }
     }
+#undef SGNS_ARG
 }
 
 // word counts of a walk matrix (vocabulary statistics for the sampling table and the subsampling probabilities);

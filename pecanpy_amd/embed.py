@@ -1,11 +1,13 @@
 """Skip-gram embeddings from a walk matrix on the GPU (reference: gensim ``Word2Vec(walks, sg=1, ...)`` in
 ``Base.embed`` / ``cli.learn_embeddings``, src/pecanpy/pecanpy.py:276-290, cli.py:307-325).
 
-``train_sgns`` runs word2vec's skip-gram-with-negative-sampling update as a HIP kernel (``pw_sgns_train``,
-csrc/sgns.hip.h) directly on the ``uint32[n_jobs, L+2]`` matrix the walk engine produces -- no ``List[List[str]]`` corpus
-in between.  Same model and defaults as gensim's (negative=5, ns_exponent=0.75, sample=1e-3, alpha 0.025 -> 1e-4,
-shrunk windows over the subsampled walk); not bit-comparable with gensim's own random streams -- the deterministic
-single-wavefront mode is checked against a sequential CPU restatement of the algorithm instead (tests/test_gpu_sgns.py).
+``train_sgns_device`` runs word2vec's skip-gram-with-negative-sampling update as a HIP kernel (``pw_sgns_train_device``,
+csrc/sgns.hip.h: a wavefront owns a walk) on the ``[n_jobs, L+2]`` matrix where ``WalkEngine.simulate_device`` leaves it, in
+device memory -- no host copy of the matrix and no ``List[List[str]]`` corpus in between; ``train_sgns`` is the same
+trainer for a matrix that lives on the host (upload, same kernel, download).  Same model and defaults as gensim's
+(negative=5, ns_exponent=0.75, sample=1e-3, alpha 0.025 -> 1e-4, shrunk windows over the subsampled walk); not
+bit-comparable with gensim's own random streams -- the deterministic single-wavefront mode is checked against a sequential
+CPU restatement of the algorithm instead (tests/test_gpu_sgns.py, tests/test_gpu_embed_device.py).
 """
 import ctypes as C
 
@@ -13,7 +15,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["train_sgns", "save_word2vec_format"]
+__all__ = ["train_sgns", "train_sgns_device", "save_word2vec_format"]
 
 
 def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
@@ -35,9 +37,59 @@ def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5,
     return out
 
 
+def train_sgns_device(d_walks, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
+                      sample=1e-3, seed=None, workers=0, out=None):
+    """``train_sgns`` on a walk matrix in device memory: ``d_walks`` is what ``WalkEngine.simulate_device`` returns, a
+    contiguous int32 CUDA tensor ``[n_walks, walk_length + 2]`` (uint32 storage).  Returns a ``float32[num_nodes, dim]``
+    tensor on the same device (``out`` when given: contiguous, that shape, dtype and device).  The matrix never visits the
+    host.  What the call did (``pw_sgns_stats``: ``vocab_ms``, ``init_ms``, ``train_ms``, ``kept_occurrences``,
+    ``trained_pairs``, ``wavefronts``) is left in ``train_sgns_device.last_stats``."""
+    import torch
+
+    if not isinstance(d_walks, torch.Tensor) or not d_walks.is_cuda or d_walks.dtype != torch.int32 or not d_walks.is_contiguous():
+        raise ValueError("d_walks must be a contiguous int32 CUDA tensor")
+    if d_walks.dim() != 2 or d_walks.shape[1] < 3:
+        raise ValueError("walk matrix must be int32[n_walks, walk_length + 2]")
+    shape = (int(num_nodes), int(dim))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=d_walks.device)
+    elif (not isinstance(out, torch.Tensor) or out.device != d_walks.device or out.dtype != torch.float32
+          or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32[num_nodes, dim] tensor on the device of d_walks")
+    lib = _lib.load()
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1)[0])
+    torch.cuda.current_stream(d_walks.device).synchronize()  # the matrix was produced on torch's stream
+    st = _lib.PwSgnsStats()
+    _lib.check(lib.pw_sgns_train_device(d_walks.device.index, C.c_void_p(d_walks.data_ptr()), d_walks.shape[0], d_walks.shape[1] - 2,
+                                        shape[0], shape[1], int(window), int(negative), int(epochs), float(alpha), float(min_alpha),
+                                        float(sample), int(seed) & 0xFFFFFFFF, int(workers), C.c_void_p(out.data_ptr()), C.byref(st)))
+    train_sgns_device.last_stats = st.as_dict()
+    return out
+
+
+train_sgns_device.last_stats = None
+
+
+_WRITE_ROWS = 1 << 14   # rows formatted per write
+
+
 def save_word2vec_format(path, node_ids, vectors):
-    """The text format gensim's ``KeyedVectors.save_word2vec_format`` writes (cli.py:323-325)."""
-    with open(path, "w", encoding="utf-8") as f:
-        f.write(f"{len(node_ids)} {vectors.shape[1]}\n")
-        for name, vec in zip(node_ids, vectors):
-            f.write(str(name) + " " + " ".join(f"{x:.6f}" for x in vec) + "\n")
+    """The text format gensim's ``KeyedVectors.save_word2vec_format`` writes (cli.py:323-325): a header line
+    ``count dim``, then per node its name and the components as ``%.6f``, separated by single spaces.  Rows are
+    formatted a block at a time (one ``%`` application and one write per block of rows, not one per component)."""
+    vectors = np.asarray(vectors)
+    dim = vectors.shape[1]
+    row_fmt = "%s" + " %.6f" * dim + "\n"
+    with open(path, "w", encoding="utf-8", newline="\n") as f:
+        f.write(f"{len(node_ids)} {dim}\n")
+        n = min(len(node_ids), vectors.shape[0])
+        for lo in range(0, n, _WRITE_ROWS):
+            hi = min(n, lo + _WRITE_ROWS)
+            block = vectors[lo:hi].astype(np.float64).tolist()   # Python floats: what the f-string of a float32 formats
+            fmt = row_fmt * (hi - lo)
+            flat = []
+            for name, row in zip(node_ids[lo:hi], block):
+                flat.append(str(name))
+                flat.extend(row)
+            f.write(fmt % tuple(flat))

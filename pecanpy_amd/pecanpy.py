@@ -78,6 +78,7 @@ class Base(BaseGraph):
         self._run_seed = None
         self.device = None  # GPU index; None -> LOCAL_RANK / 0
         self.last_stats = None
+        self.last_embed_stats = None
         # the library's one-time start-up (~140 ms for the first stream it creates) runs on a helper thread beside what comes
         # next in the reference's flow -- reading the graph (cli.py:328-337) -- instead of in front of the first walk
         import os
@@ -321,23 +322,75 @@ class Base(BaseGraph):
             self.preprocess_transition_probs()
             self._preprocessed = True
 
+    def _device_walks(self, num_walks, walk_length):
+        """The walk matrix of ``simulate_walks_array`` as a device tensor (``WalkEngine.simulate_device``), or ``None`` where
+        that call takes another route: under ``torch.distributed``, with the in-process multi-GPU engine, and for engines
+        without a device entry."""
+        self._preprocess_transition_probs()
+        self._run_seed = self._call_seed()
+        starts = self._start_array(num_walks, self._run_seed)
+        eng = self._get_engine()
+        if self._dist() is not None or self._multi_engine(starts.size, walk_length) is not None or not hasattr(eng, "simulate_device"):
+            return None
+        import torch
+
+        seed = self._run_seed if self.random_state is None else self.random_state
+        d_starts = torch.from_numpy(starts.view(np.int32)).to(torch.device("cuda", eng.device))
+        d_walks = eng.simulate_device(self._mode, self.p, self.q, self.extend, d_starts, walk_length, seed=seed)
+        self._note_stats(eng.last_stats)
+        return d_walks
+
+    def embed_array(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0):
+        """Walks and skip-gram on the GPU, the walk matrix staying in device memory: start array -> ``simulate_device`` ->
+        ``pecanpy_amd.embed.train_sgns_device`` -> ``float32[num_nodes, dim]`` in node order, copied to the host once.
+        ``workers`` is the trainer's (0: hogwild, 1: one wavefront, deterministic under ``random_state``).
+
+        ``self.last_embed_stats`` records the call: ``walk_matrix_host_bytes`` (0 on this route), ``walk_ms``, ``train_ms``
+        (the training kernels), ``vocab_ms``, ``init_ms``, ``sgns_call_ms``, ``download_ms``, ``trained_pairs``,
+        ``kept_occurrences``, ``wavefronts``.  Where the walks cannot stay on one device (see ``_device_walks``) the
+        host-matrix route of ``simulate_walks_array`` + ``train_sgns`` runs instead and ``walk_matrix_host_bytes`` holds
+        the bytes of the matrix that crossed to the host and back."""
+        import time
+
+        from .embed import train_sgns, train_sgns_device
+
+        t0 = time.perf_counter()
+        d_walks = self._device_walks(num_walks, walk_length)
+        if d_walks is None:
+            mat = self.simulate_walks_array(num_walks, walk_length)
+            t1 = time.perf_counter()
+            vec = train_sgns(mat, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
+                             device=self._device_index(), workers=workers)
+            t2 = time.perf_counter()
+            self.last_embed_stats = {"walk_matrix_host_bytes": 2 * int(mat.nbytes), "walk_ms": (t1 - t0) * 1e3,
+                                     "sgns_call_ms": (t2 - t1) * 1e3}
+            return vec
+        import torch
+
+        torch.cuda.synchronize(d_walks.device)
+        t1 = time.perf_counter()
+        d_vec = train_sgns_device(d_walks, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
+                                  workers=workers)
+        t2 = time.perf_counter()
+        vec = d_vec.cpu().numpy()
+        t3 = time.perf_counter()
+        self.last_embed_stats = {"walk_matrix_host_bytes": 0, "walk_ms": (t1 - t0) * 1e3, "sgns_call_ms": (t2 - t1) * 1e3,
+                                 "download_ms": (t3 - t2) * 1e3, **train_sgns_device.last_stats}
+        return vec
+
     def embed(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, verbose=False):
         """``simulate_walks`` + skip-gram (pecanpy.py:240-290): returns ``float32[num_nodes, dim]`` in node order.
 
         With gensim installed the reference's call is made (``Word2Vec(walks, sg=1, min_count=0, ...)``); without
-        it the GPU trainer of this package runs on the walk matrix directly (``pecanpy_amd.embed.train_sgns``: same
-        model and defaults, no string corpus)."""
+        it the GPU pipeline of this package runs (``embed_array``: same model and defaults, the walk matrix stays in
+        device memory, no string corpus)."""
         try:
             from gensim.models import Word2Vec
         except ImportError:
             Word2Vec = None
         if Word2Vec is None:
-            from .embed import train_sgns
-
-            mat = Timer("generate walks", verbose)(self.simulate_walks_array)(num_walks, walk_length)
-            return Timer("train embeddings", verbose)(train_sgns)(
-                mat, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
-                device=self._device_index())
+            return Timer("generate walks + train embeddings", verbose)(self.embed_array)(
+                dim=dim, num_walks=num_walks, walk_length=walk_length, window_size=window_size, epochs=epochs)
         walks = Timer("generate walks", verbose)(self.simulate_walks)(num_walks, walk_length)
         w2v = Timer("train embeddings", verbose)(Word2Vec)(
             walks, vector_size=dim, window=window_size, sg=1, min_count=0, workers=self.workers,
