@@ -507,10 +507,10 @@ walk_dense_bits_kernel(DenseArgs a) {
         for (uint32_t z = j + lane; z <= L; z += WAVE) row[z] = 0;
     }
     if (lane == 0) {
-        if (st_steps) atomicAdd(&a.stats[0], st_steps);
-        if (st_over) atomicAdd(&a.stats[1], st_over);
-        if (st_clamp) atomicAdd(&a.stats[2], st_clamp);
-        if (st_dead) atomicAdd(&a.stats[3], st_dead);
+        if (st_steps) atomicAdd(&a.stats[ST_STEPS], st_steps);
+        if (st_over) atomicAdd(&a.stats[ST_OVERFLOW], st_over);
+        if (st_clamp) atomicAdd(&a.stats[ST_CLAMPED], st_clamp);
+        if (st_dead) atomicAdd(&a.stats[ST_DEAD], st_dead);
     }
 }
 
@@ -758,8 +758,8 @@ walk_dense_fast_kernel(DenseArgs a, uint32_t *redo_list, unsigned long long *red
         for (uint32_t z = j + lane; z <= L; z += WAVE) row[z] = 0;
     }
     if (lane == 0) {
-        if (st_steps) atomicAdd(&a.stats[0], st_steps);
-        if (st_dead) atomicAdd(&a.stats[3], st_dead);
+        if (st_steps) atomicAdd(&a.stats[ST_STEPS], st_steps);
+        if (st_dead) atomicAdd(&a.stats[ST_DEAD], st_dead);
     }
 }
 

@@ -417,10 +417,10 @@ walk_dense_weighted_kernel(DenseWArgs a) {
         for (uint32_t z = j + lane; z <= L; z += WAVE) row[z] = 0;
     }
     if (lane == 0) {
-        if (st_steps) atomicAdd(&a.stats[0], st_steps);
-        if (st_dead) atomicAdd(&a.stats[3], st_dead);
-        if (st_exact) atomicAdd(&a.stats[7], st_exact);   // (pw_stats.ambiguous_steps: steps decided by the float64 chain itself)
-        if (st_clamp) { atomicAdd(&a.stats[1], st_clamp); atomicAdd(&a.stats[2], st_clamp); }   // (overflow + clamped reads)
+        if (st_steps) atomicAdd(&a.stats[ST_STEPS], st_steps);
+        if (st_dead) atomicAdd(&a.stats[ST_DEAD], st_dead);
+        if (st_exact) atomicAdd(&a.stats[ST_AMBIGUOUS], st_exact);   // (pw_stats.ambiguous_steps: steps decided by the float64 chain itself)
+        if (st_clamp) { atomicAdd(&a.stats[ST_OVERFLOW], st_clamp); atomicAdd(&a.stats[ST_CLAMPED], st_clamp); }   // (overflow + clamped reads)
     }
 }
 

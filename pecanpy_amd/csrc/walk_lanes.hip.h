@@ -95,9 +95,8 @@ struct LanesArgs {
     uint64_t rng_base;
     uint32_t *out;                            // [n_jobs, L + 2], zero-filled by the caller before the first launch
     unsigned long long *job_counter;
-    unsigned long long *stats;                // [0] steps [1] overflow reads [2] clamped reads [3] dead-end walks
-                                              // [6] list entries read [7] steps the a-priori bound left open
-                                              // [9] of those, steps that needed the float32 chain
+    unsigned long long *stats;                // counters + CTR_STATS (counters.h): ST_STEPS, ST_OVERFLOW, ST_DEAD, ST_LIST_READS,
+                                              // ST_AMBIGUOUS, ST_WAVE_CHAIN
     uint32_t *redo_list;                      // jobs handed to walk_kernel
     unsigned long long *redo_count;
     float w_out, w_prev;                      // fl32(1/q), fl32(1/p): powers of two (host checked)
@@ -242,7 +241,7 @@ __device__ unsigned long long g_lprof[16];
         } else {                                                                                \
             A.e = oe_ != NOT_FOUND ? oe_ : A.s0 + choice;                                       \
             if (oe_ != NOT_FOUND) {   /* (~1e-5 of the steps: counted where it happens; a sampled transition too) */ \
-                atomicAdd(LAP(unsigned long long *, stats) + 1, 1ull); atomicAdd(LAP(unsigned long long *, stats) + 0, 1ull);                     \
+                atomicAdd(LAP(unsigned long long *, stats) + ST_OVERFLOW, 1ull); atomicAdd(LAP(unsigned long long *, stats) + ST_STEPS, 1ull);                     \
             }                                                                                   \
             fetch_ = true;                                                                      \
         }                                                                                       \
@@ -1252,11 +1251,11 @@ walk_lanes_kernel(LanesArgs a) {
         probes_w += (unsigned long long)__shfl_down((long long)probes_w, (unsigned)off, WAVE);
     }
     if (lane == 0) {
-        if (n_steps) atomicAdd(LAP(unsigned long long *, stats) + 0, n_steps);
-        if (dead_w) atomicAdd(LAP(unsigned long long *, stats) + 3, dead_w);
-        if (probes_w) atomicAdd(LAP(unsigned long long *, stats) + 6, probes_w);
-        if (n_amb) atomicAdd(LAP(unsigned long long *, stats) + 7, n_amb);
-        if (n_wave) atomicAdd(LAP(unsigned long long *, stats) + 9, n_wave);
+        if (n_steps) atomicAdd(LAP(unsigned long long *, stats) + ST_STEPS, n_steps);
+        if (dead_w) atomicAdd(LAP(unsigned long long *, stats) + ST_DEAD, dead_w);
+        if (probes_w) atomicAdd(LAP(unsigned long long *, stats) + ST_LIST_READS, probes_w);
+        if (n_amb) atomicAdd(LAP(unsigned long long *, stats) + ST_AMBIGUOUS, n_amb);
+        if (n_wave) atomicAdd(LAP(unsigned long long *, stats) + ST_WAVE_CHAIN, n_wave);
     }
 }
 #undef LA64
@@ -1330,8 +1329,8 @@ lanes_chain_kernel(SuspRec *q, uint64_t n, const ELine *__restrict__ lines, cons
         done += (unsigned long long)__shfl_down((long long)done, (unsigned)off, WAVE);
     }
     if (lane_id() == 0 && done) {
-        atomicAdd(stats + 6, reads_l);
-        atomicAdd(stats + 9, done);
+        atomicAdd(stats + ST_LIST_READS, reads_l);
+        atomicAdd(stats + ST_WAVE_CHAIN, done);
     }
 }
 
@@ -1626,7 +1625,7 @@ lanes_verify_kernel(const VerRec *q, uint64_t n, const ELine *__restrict__ lines
         if (res == LANE_TIE) tie = 1;
         else if (res != q0.w) {
             mis = 1;
-            const unsigned long long slot = atomicAdd(counts + 3, 1ull);
+            const unsigned long long slot = atomicAdd(counts + VER_BAD, 1ull);
             if (bad_jobs && slot < bad_jobs_cap) bad_jobs[slot] = q[i].job;
             if (slot < bad_cap) { bad[slot] = q[i]; bad[slot].job = res; }
         }
@@ -1637,9 +1636,9 @@ lanes_verify_kernel(const VerRec *q, uint64_t n, const ELine *__restrict__ lines
         tie += (unsigned long long)__shfl_down((long long)tie, (unsigned)off, WAVE);
     }
     if (lane_id() == 0 && chk) {
-        atomicAdd(counts + 0, chk);
-        if (mis) atomicAdd(counts + 1, mis);
-        if (tie) atomicAdd(counts + 2, tie);
+        atomicAdd(counts + VER_CHECKED, chk);
+        if (mis) atomicAdd(counts + VER_MISMATCH, mis);
+        if (tie) atomicAdd(counts + VER_TIES, tie);
     }
 }
 

@@ -217,10 +217,10 @@ walk_seq_kernel(SeqArgs a) {
             steps++;
         }
     }
-    a.stats[0] = steps;
-    a.stats[1] = over;
-    a.stats[2] = clamp;
-    a.stats[3] = dead;
+    a.stats[ST_STEPS] = steps;
+    a.stats[ST_OVERFLOW] = over;
+    a.stats[ST_CLAMPED] = clamp;
+    a.stats[ST_DEAD] = dead;
 }
 
 // ---- unseeded runs of the alias / first-order modes: one lane per walk, counter-based draws -------------
@@ -301,8 +301,8 @@ walk_alias_parallel_kernel(SeqArgs a, uint64_t seed) {
         cur = nxt;
         steps++;
     }
-    if (steps) atomicAdd(&a.stats[0], steps);
-    if (dead) atomicAdd(&a.stats[3], dead);
+    if (steps) atomicAdd(&a.stats[ST_STEPS], steps);
+    if (dead) atomicAdd(&a.stats[ST_DEAD], dead);
 }
 
 }  // namespace pw

@@ -30,6 +30,7 @@
 // scalar loads and kernel arguments are re-read at the point of use (wave.h) because the 80 SGPRs
 // a wave gets at 8 waves/SIMD are the scarcest resource of this kernel.
 #pragma once
+#include "counters.h"
 #include "seqscan.h"
 #include "wave.h"
 
@@ -160,7 +161,7 @@ struct WalkArgs {
     uint64_t rng_base;
     uint32_t *out;                            // [n_jobs, L + 2]
     unsigned long long *job_counter;
-    unsigned long long *stats;  // [0] steps [1] overflow reads [2] clamped reads [3] dead-end walks
+    unsigned long long *stats;  // counters + CTR_STATS (counters.h): ST_STEPS, ST_OVERFLOW, ST_CLAMPED, ST_DEAD in that order
     float w_out, w_prev;        // fl32(1/q), fl32(1/p): the unit-weight biases (host computed)
     uint32_t lazy_ok;           // both are powers of two in a safe exponent range (lazy path precondition)
     // weighted CSR graphs: the normaliser of every transition, precomputed per (p, q, extend) by tot_build_kernel
@@ -1505,7 +1506,7 @@ walk_kernel(WalkArgs a) {
             const uint32_t s0 = vc.s0, d = vc.d, t0 = vp.s0, dp = vp.d;
             if (d == 0) {
                 len_out = j;
-                if (j > 1 && lane == 0) stat[3]++;
+                if (j > 1 && lane == 0) stat[ST_DEAD]++;
                 break;
             }
             const double r = as_scalar<double>(PW_KARG(uint64_t, rng))[soff + (j - 1)];
@@ -1541,13 +1542,13 @@ walk_kernel(WalkArgs a) {
             bool clamped = false;
             const bool real_edge = choice < d;
             if (!real_edge) {
-                if (lane == 0) stat[1]++;
+                if (lane == 0) stat[ST_OVERFLOW]++;
                 if (DENSE) { choice = d - 1; clamped = true; }  // reference reads past a temporary: clamp
             }
             uint64_t pos = (uint64_t)s0 + choice;
             const uint32_t nnz = PW_KARG(uint32_t, g.nnz);
             if (pos >= nnz) { pos = nnz - 1; clamped = true; }
-            if (clamped && lane == 0) stat[2]++;
+            if (clamped && lane == 0) stat[ST_CLAMPED]++;
             prev_edge = (real_edge && !clamped) ? (uint32_t)pos : NOT_FOUND;
             // The edge just taken: one 16-byte record names the next vertex, its degree, the number of
             // common neighbours and where cur sits in the next vertex's row.  When cur's row is the
@@ -1582,7 +1583,7 @@ walk_kernel(WalkArgs a) {
         if (lane == 0) {
             row[0] = start;
             row[L + 1] = len_out;
-            stat[0] += j - j_first;   // transitions sampled here
+            stat[ST_STEPS] += j - j_first;   // transitions sampled here
         }
         for (uint32_t z = j + lane; z <= L; z += WAVE) row[z] = 0;
     }
