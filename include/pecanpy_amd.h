@@ -142,6 +142,49 @@ int pw_warmup(int device, double *ms);
 int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, const float *data,
                   uint32_t n_nodes, uint32_t nnz, int device, pw_graph **out);
 
+/* ---- CSR built on the device from an edge list (COO) that is already in device memory ------------------------------------
+ * The sparse counterpart of pw_dense_create_bits(on_device = 1): a caller that holds a graph as edge arrays on the GPU (a
+ * PyTorch edge_index, a COO buffer) gets the reference's CSR without sorting, symmetrising and deduplicating on the host.
+ * Semantics = AdjlstGraph.add_edge / to_csr of the reference (graph.py:238-268, 323-341) with IMPLICIT INTEGER IDS: vertex i
+ * is id i -- no renumbering by first appearance, unlike pw_edgelist_read.
+ *   d_src, d_dst  int64[m] on `device` (two pointers: the rows of a [2, m] tensor work without a copy)
+ *   d_weight      float32[m] on `device`, or NULL: unweighted (the result then has no data array: the unit-weight case of
+ *                 pw_csr_create's data == NULL)
+ *   n_nodes       0: largest id listed + 1 (edges that are dropped count too)
+ *   - an edge with weight <= 0 is dropped and counted (the reference's "Non-positive edge ignored");
+ *   - kept edge i inserts (src, dst) and, when directed == 0, then (dst, src) with the same weight; insertion order is edge
+ *     order, forward before reverse; for every ordered pair the LAST insertion's weight wins;
+ *   - rows ascending and duplicate-free; vertices without a kept edge are empty rows;
+ *   - PW_ERR_INVALID, nothing kept allocated: a NaN or infinite weight (pw_csr_create's rule), a negative id, an id >= n_nodes,
+ *     n_nodes > 2^32 - 2, or 2^32 or more insertions; PW_ERR_NOMEM with the sizes in the message when the scratch (two
+ *     key arrays of 8 bytes and, with weights, two of 4 bytes per insertion, 1/8 of that again for histograms) does not fit.
+ * The result is a function of the input alone (a stable radix sort on (src, dst) keeps equal pairs in insertion order; no
+ * result depends on the order atomics arrive in).  Work runs on the device's default stream; the call returns when it is done.
+ *   pw_csr_dev_shape    n_nodes, nnz, insertions (the reference's num_edges counter: insertions, not distinct edges),
+ *                       dropped, build_ms (HIP-event time of the build's kernels: the allocations and the two small
+ *                       device-to-host reads between them are not in it); NULL = skip
+ *   pw_csr_dev_export   copies to host arrays of the caller: indptr uint32[n_nodes + 1], indices uint32[nnz], data
+ *                       float32[nnz] (all 1.0 when no weights were given); NULL = skip
+ *   pw_csr_create_device  a walk handle on the same device: the same validation, membership index and lane index, hence the
+ *                       same walks, as pw_csr_create on the exported arrays.  The host passes of the index build (work items,
+ *                       degrees) read host arrays: h_indptr / h_indices / h_data = what pw_csr_dev_export wrote (h_data is
+ *                       ignored when no weights were given), so a caller that exported anyway pays no second download; all
+ *                       three NULL = the CSR comes down once inside the call.  Arrays that differ from the device CSR give
+ *                       an inconsistent handle.  The handle's device copy is made device to device; the pw_csr_dev stays
+ *                       valid and owns its arrays until pw_csr_dev_destroy, so the device holds the CSR twice while the handle
+ *                       is built.  pw_csr_create builds the lane index only when it fits in half of the free device memory:
+ *                       within one CSR's size of that limit this handle can come without the lane index that pw_csr_create
+ *                       on the exported arrays, with the pw_csr_dev destroyed first, would build. */
+typedef struct pw_csr_dev pw_csr_dev;
+int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64_t *d_dst, const float *d_weight, uint64_t m,
+                         uint64_t n_nodes, int directed, pw_csr_dev **out);
+int pw_csr_dev_shape(const pw_csr_dev *c, uint64_t *n_nodes, uint64_t *nnz, uint64_t *insertions, uint64_t *dropped,
+                     double *build_ms);
+int pw_csr_dev_export(const pw_csr_dev *c, uint32_t *indptr, uint32_t *indices, float *data);
+void pw_csr_dev_destroy(pw_csr_dev *c);
+int pw_csr_create_device(const pw_csr_dev *c, const uint32_t *h_indptr, const uint32_t *h_indices, const float *h_data,
+                         pw_graph **out);
+
 /* Device time (ms) of the index kernels pw_csr_create ran, device bytes of the index, and the number of entries
  * of the lane kernel's common-neighbour lists (0: lane index not built).  Any pointer may be NULL. */
 int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t *index_bytes, uint64_t *lane_list_entries);

@@ -82,6 +82,12 @@ SYMBOLS = {
     "pw_warmup": (C.c_int, [C.c_int, _f64p]),
     "pw_csr_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int,
                                 C.POINTER(C.c_void_p)]),
+    "pw_coo_to_csr_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                       C.POINTER(C.c_void_p)]),
+    "pw_csr_dev_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(C.c_double)]),
+    "pw_csr_dev_export": (C.c_int, [C.c_void_p] * 4),
+    "pw_csr_dev_destroy": (None, [C.c_void_p]),
+    "pw_csr_create_device": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]),
     "pw_graph_index_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pw_lane_index_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pw_dense_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),

@@ -36,6 +36,7 @@
 #include "walk_sparse.hip.h"
 #include "walk_lanes.hip.h"
 #include "sgns.hip.h"
+#include "coo_csr.hip.h"
 
 #define PW_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -771,8 +772,11 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     return 0;
 }
 
-PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, const float *data,
-                            uint32_t n_nodes, uint32_t nnz, int device, pw_graph **out) {
+// pw_csr_create, and pw_csr_create_device through d_csr: the same arrays already in the memory of `device` (indptr, indices,
+// data or NULL), which the handle then copies device to device instead of uploading the host arrays a second time -- the host
+// arrays are still what the host passes below read.
+static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, const float *data, uint32_t n_nodes, uint32_t nnz,
+                           int device, pw_graph **out, const void *const *d_csr) {
     if (!indptr || !out || (nnz && !indices)) return fail(PW_ERR_INVALID, "null pointer");
     if (indptr[0] != 0) return fail(PW_ERR_INVALID, "indptr[0] != 0");
     if (indptr[n_nodes] != nnz) return fail(PW_ERR_INVALID, "indptr[n_nodes] != nnz");
@@ -819,16 +823,19 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
             if (!csr_taken) for (void *q : {indptr, indices, data}) if (q) (void)hipFree(q);
         }
     } pre;
-    auto up_work = [&pre, device, indptr, indices, data, n_nodes, nnz]() {
+    auto up_work = [&pre, device, indptr, indices, data, n_nodes, nnz, d_csr]() {
         if ((pre.err = hipSetDevice(device)) != hipSuccess) return;
-        auto up1 = [&](void **dst, const void *src, size_t bytes) {
+        auto up1 = [&](void **dst, const void *src, const void *d_src, size_t bytes) {
             if (pre.err != hipSuccess) return;
             pre.err = hipMalloc(dst, bytes ? bytes : 4);
-            if (pre.err == hipSuccess && bytes) pre.err = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+            if (pre.err == hipSuccess && bytes)
+                pre.err = d_src ? hipMemcpy(*dst, d_src, bytes, hipMemcpyDeviceToDevice) : hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
         };
-        up1(&pre.indptr, indptr, sizeof(uint32_t) * ((size_t)n_nodes + 1));
-        up1(&pre.indices, indices, sizeof(uint32_t) * (size_t)nnz);
-        if (data) up1(&pre.data, data, sizeof(float) * (size_t)nnz);
+        up1(&pre.indptr, indptr, d_csr ? d_csr[0] : nullptr, sizeof(uint32_t) * ((size_t)n_nodes + 1));
+        up1(&pre.indices, indices, d_csr ? d_csr[1] : nullptr, sizeof(uint32_t) * (size_t)nnz);
+        if (data) up1(&pre.data, data, d_csr ? d_csr[2] : nullptr, sizeof(float) * (size_t)nnz);
+        // (a device-to-device hipMemcpy may return before the copy has run; the handle's streams do not wait for the null stream)
+        if (d_csr && pre.err == hipSuccess) pre.err = hipStreamSynchronize(nullptr);
     };
     try { pre.t_up = std::thread(up_work); } catch (const std::system_error &) { up_work(); }   // (thread limit: on this thread)
     if (nnz && !getenv("PECANPY_AMD_NO_LAZY") && !getenv("PECANPY_AMD_NO_PREALLOC")) {
@@ -981,6 +988,254 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
     (void)hipFree(d_flags);
     *out = g;
     return PW_OK;
+}
+
+PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, const float *data,
+                            uint32_t n_nodes, uint32_t nnz, int device, pw_graph **out) {
+    return csr_create_impl(indptr, indices, data, n_nodes, nnz, device, out, nullptr);
+}
+
+// ---- CSR from an edge list in device memory (csrc/coo_csr.hip.h) -----------------------------------------------------------------
+struct pw_csr_dev {
+    int device = 0;
+    uint64_t n_nodes = 0, nnz = 0, insertions = 0, dropped = 0;
+    double build_ms = 0;
+    uint32_t *d_indptr = nullptr, *d_indices = nullptr;
+    float *d_data = nullptr;   // NULL: no weights were given (every weight 1.0)
+};
+
+PW_EXPORT void pw_csr_dev_destroy(pw_csr_dev *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    for (void *q : {(void *)c->d_indptr, (void *)c->d_indices, (void *)c->d_data})
+        if (q) (void)hipFree(q);
+    delete c;
+}
+
+namespace {
+
+uint64_t scan_tmp_elems(uint64_t n) {   // tile sums of every level of device_exclusive_scan
+    uint64_t total = 0;
+    while (n > (uint64_t)pw::USCAN_TILE) {
+        n = (n + pw::USCAN_TILE - 1) / pw::USCAN_TILE;
+        total += n;
+    }
+    return total;
+}
+
+// exclusive scan of d_x[0, n) in place on the null stream; d_tmp: scan_tmp_elems(n) words
+void device_exclusive_scan(uint32_t *d_x, uint64_t n, uint32_t *d_tmp) {
+    if (n == 0) return;
+    const uint64_t tiles = (n + pw::USCAN_TILE - 1) / pw::USCAN_TILE;
+    if (tiles == 1) {
+        hipLaunchKernelGGL(pw::scan_apply_kernel, dim3(1), dim3(256), 0, nullptr, d_x, n, (const uint32_t *)nullptr);
+        return;
+    }
+    hipLaunchKernelGGL(pw::scan_reduce_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, (const uint32_t *)d_x, n, d_tmp);
+    device_exclusive_scan(d_tmp, tiles, d_tmp + tiles);
+    hipLaunchKernelGGL(pw::scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, d_x, n, (const uint32_t *)d_tmp);
+}
+
+}  // namespace
+
+PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64_t *d_dst, const float *d_weight, uint64_t m,
+                                   uint64_t n_nodes, int directed, pw_csr_dev **out) {
+    if (!out || (m && (!d_src || !d_dst))) return fail(PW_ERR_INVALID, "null pointer");
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (n_nodes > 0xfffffffeull) return fail(PW_ERR_INVALID, "n_nodes beyond the 32-bit CSR limit (at most 2^32 - 2 vertices)");
+    const uint64_t mult = directed ? 1 : 2;
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    const unsigned stride_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)prop.multiProcessorCount * 16));
+
+    // everything the call allocates: scratch freed on every way out, the result's arrays only on failure
+    struct Mem {
+        std::vector<void *> scratch;
+        pw_csr_dev *res = nullptr;
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of the three kernel spans
+        ~Mem() {
+            for (void *q : scratch) if (q) (void)hipFree(q);
+            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+            if (res) pw_csr_dev_destroy(res);
+        }
+    } mem;
+    uint64_t scratch_bytes = 0;
+    auto alloc = [&](void **p, uint64_t bytes, const char *what) -> int {
+        *p = nullptr;
+        hipError_t e = hipMalloc(p, bytes ? bytes : 4);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            return fail(PW_ERR_NOMEM, std::string("pw_coo_to_csr_device: ") + what + " (" + std::to_string(bytes) + " bytes, " +
+                                          std::to_string(scratch_bytes) + " bytes of scratch before it) does not fit in device memory: " +
+                                          hipGetErrorString(e));
+        }
+        mem.scratch.push_back(*p);
+        scratch_bytes += bytes;
+        return 0;
+    };
+    // build_ms = the sum of three spans of kernels on the null stream; the allocations, the two small device-to-host reads and the
+    // host logic between the spans are outside it
+    for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
+
+    // 1. validation, kept edges, largest id
+    unsigned long long *d_flags = nullptr;
+    uint32_t *d_keep = nullptr;
+    int rc = alloc((void **)&d_flags, 4 * sizeof(unsigned long long), "flags");
+    if (!rc && d_weight) rc = alloc((void **)&d_keep, sizeof(uint32_t) * (m + 1), "kept-edge ranks");
+    if (rc) return rc;
+    unsigned long long h_flags[4] = {~0ull, ~0ull, 0ull, 0ull};
+    HIP_TRY(hipMemcpy(d_flags, h_flags, sizeof(h_flags), hipMemcpyHostToDevice));
+    HIP_TRY(hipEventRecord(mem.ev[0], nullptr));
+    if (m) {
+        hipLaunchKernelGGL(pw::coo_validate_kernel, dim3(stride_grid), dim3(256), 0, nullptr, d_src, d_dst, d_weight, m,
+                           n_nodes ? n_nodes : 0xfffffffeull, d_keep, d_flags);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(mem.ev[1], nullptr));
+    HIP_TRY(hipMemcpy(h_flags, d_flags, sizeof(h_flags), hipMemcpyDeviceToHost));
+    if (h_flags[0] != ~0ull)
+        return fail(PW_ERR_INVALID, "edge " + std::to_string(h_flags[0]) + ": vertex id negative or >= " +
+                                        (n_nodes ? "n_nodes (" + std::to_string(n_nodes) + ")" : std::string("2^32 - 2 (the 32-bit CSR limit)")));
+    if (h_flags[1] != ~0ull)
+        return fail(PW_ERR_INVALID, "edge " + std::to_string(h_flags[1]) + ": edge weights must be finite (NaN or infinite weight)");
+    const uint64_t n = n_nodes ? n_nodes : (uint64_t)h_flags[3];
+    const uint64_t dropped = h_flags[2], kept = m - dropped;
+    if (kept > 0xffffffffull / mult) return fail(PW_ERR_INVALID, "edge list makes 2^32 or more insertions (the 32-bit CSR limit)");
+    const uint64_t n_ins = kept * mult;
+    int bits = 1;
+    while (bits < 32 && (1ull << bits) < n) bits++;
+
+    // 2.-3. keys in insertion order
+    const uint64_t n_waves = (n_ins + pw::RADIX_SUB - 1) / pw::RADIX_SUB;
+    const uint64_t hist_elems = (uint64_t)pw::RADIX_BINS * n_waves;
+    const uint64_t scan_max = std::max(std::max(hist_elems, n_ins + 1), d_weight ? m + 1 : 0);
+    uint64_t *d_keys[2] = {nullptr, nullptr};
+    float *d_w[2] = {nullptr, nullptr};
+    uint32_t *d_hist = nullptr, *d_tmp = nullptr;
+    rc = alloc((void **)&d_keys[0], sizeof(uint64_t) * (n_ins + 1), "sort keys");
+    if (!rc) rc = alloc((void **)&d_keys[1], sizeof(uint64_t) * (n_ins + 1), "sort keys (second buffer)");
+    if (!rc && d_weight) rc = alloc((void **)&d_w[0], sizeof(float) * n_ins, "sort weights");
+    if (!rc && d_weight) rc = alloc((void **)&d_w[1], sizeof(float) * n_ins, "sort weights (second buffer)");
+    if (!rc) rc = alloc((void **)&d_hist, sizeof(uint32_t) * hist_elems, "radix histograms");
+    if (!rc) rc = alloc((void **)&d_tmp, sizeof(uint32_t) * scan_tmp_elems(scan_max), "scan tile sums");
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(mem.ev[2], nullptr));
+    if (d_weight && dropped) {
+        HIP_TRY(hipMemsetAsync(d_keep + m, 0, sizeof(uint32_t), nullptr));
+        device_exclusive_scan(d_keep, m + 1, d_tmp);
+    }
+    if (n_ins) {
+        hipLaunchKernelGGL(pw::coo_expand_kernel, dim3(stride_grid), dim3(256), 0, nullptr, d_src, d_dst, d_weight, m,
+                           (const uint32_t *)(d_weight && dropped ? d_keep : nullptr), directed ? 1 : 0, bits, n_ins, d_keys[0], d_w[0]);
+        // 4. stable LSD radix sort over the 2 * bits significant key bits
+        const unsigned wave_grid = (unsigned)((n_waves + 3) / 4);
+        for (int shift = 0; shift < 2 * bits; shift += pw::RADIX_BITS) {
+            hipLaunchKernelGGL(pw::radix_hist_kernel, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], n_ins, shift, d_hist, n_waves);
+            device_exclusive_scan(d_hist, hist_elems, d_tmp);
+            if (d_weight)
+                hipLaunchKernelGGL(pw::radix_scatter_kernel<true>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)d_w[0],
+                                   d_keys[1], d_w[1], n_ins, shift, (const uint32_t *)d_hist, n_waves);
+            else
+                hipLaunchKernelGGL(pw::radix_scatter_kernel<false>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)nullptr,
+                                   d_keys[1], (float *)nullptr, n_ins, shift, (const uint32_t *)d_hist, n_waves);
+            std::swap(d_keys[0], d_keys[1]);
+            std::swap(d_w[0], d_w[1]);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    // 5. keep-last flags and their scan: the buffer the sort left free holds pos[n_ins + 1], then the row of every kept entry
+    uint32_t *d_pos = (uint32_t *)d_keys[1], *d_rows = d_pos + (n_ins + 1);
+    uint32_t nnz32 = 0;
+    if (n_ins) {
+        hipLaunchKernelGGL(pw::coo_mark_kernel, dim3((unsigned)((n_ins + 256) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], n_ins, d_pos);
+        device_exclusive_scan(d_pos, n_ins + 1, d_tmp);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(mem.ev[3], nullptr));
+    if (n_ins) {
+        HIP_TRY(hipMemcpy(&nnz32, d_pos + n_ins, sizeof(nnz32), hipMemcpyDeviceToHost));
+    }
+    const uint64_t nnz = nnz32;
+    if (nnz > n_ins) return fail(PW_ERR_HIP, "pw_coo_to_csr_device: entry count beyond the insertions (internal error)");
+
+    mem.res = new pw_csr_dev();
+    pw_csr_dev *c = mem.res;
+    c->device = device;
+    c->n_nodes = n; c->nnz = nnz; c->insertions = n_ins; c->dropped = dropped;
+    auto alloc_out = [&](void **p, uint64_t bytes, const char *what) -> int {
+        hipError_t e = hipMalloc(p, bytes ? bytes : 4);
+        if (e == hipSuccess) return 0;
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail(PW_ERR_NOMEM, std::string("pw_coo_to_csr_device: ") + what + " (" + std::to_string(bytes) + " bytes beside " +
+                                      std::to_string(scratch_bytes) + " bytes of scratch) does not fit in device memory: " + hipGetErrorString(e));
+    };
+    rc = alloc_out((void **)&c->d_indptr, sizeof(uint32_t) * (n + 1), "indptr");
+    if (!rc) rc = alloc_out((void **)&c->d_indices, sizeof(uint32_t) * nnz, "indices");
+    if (!rc && d_weight) rc = alloc_out((void **)&c->d_data, sizeof(float) * nnz, "data");
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(mem.ev[4], nullptr));
+    if (n_ins)
+        hipLaunchKernelGGL(pw::coo_compact_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)d_w[0],
+                           n_ins, (const uint32_t *)d_pos, bits, nnz, c->d_indices, c->d_data, d_rows);
+    // 6. row offsets
+    hipLaunchKernelGGL(pw::coo_indptr_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, nullptr, (const uint32_t *)d_rows, nnz, n, c->d_indptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(mem.ev[5], nullptr));
+    HIP_TRY(hipEventSynchronize(mem.ev[5]));
+    for (int k = 0; k < 6; k += 2) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, mem.ev[k], mem.ev[k + 1]));
+        c->build_ms += ms;
+    }
+    mem.res = nullptr;
+    *out = c;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_csr_dev_shape(const pw_csr_dev *c, uint64_t *n_nodes, uint64_t *nnz, uint64_t *insertions, uint64_t *dropped, double *build_ms) {
+    if (!c) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_nodes) *n_nodes = c->n_nodes;
+    if (nnz) *nnz = c->nnz;
+    if (insertions) *insertions = c->insertions;
+    if (dropped) *dropped = c->dropped;
+    if (build_ms) *build_ms = c->build_ms;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_csr_dev_export(const pw_csr_dev *c, uint32_t *indptr, uint32_t *indices, float *data) {
+    if (!c) return fail(PW_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    if (indptr) HIP_TRY(hipMemcpy(indptr, c->d_indptr, sizeof(uint32_t) * (c->n_nodes + 1), hipMemcpyDeviceToHost));
+    if (indices && c->nnz) HIP_TRY(hipMemcpy(indices, c->d_indices, sizeof(uint32_t) * c->nnz, hipMemcpyDeviceToHost));
+    if (data && c->nnz) {
+        if (c->d_data) HIP_TRY(hipMemcpy(data, c->d_data, sizeof(float) * c->nnz, hipMemcpyDeviceToHost));
+        else std::fill(data, data + c->nnz, 1.0f);
+    }
+    return PW_OK;
+}
+
+PW_EXPORT int pw_csr_create_device(const pw_csr_dev *c, const uint32_t *h_indptr, const uint32_t *h_indices, const float *h_data,
+                                   pw_graph **out) {
+    if (!c || !out) return fail(PW_ERR_INVALID, "null pointer");
+    // the host passes of csr_create_impl (work items of the lane index, degrees, filter and table sizes) read host arrays: the
+    // caller's export, or the CSR comes down once here; the handle's own device copy is made device to device
+    const void *d_csr[3] = {c->d_indptr, c->d_indices, c->d_data};
+    if (h_indptr || h_indices || h_data) {
+        if (!h_indptr || (c->nnz && !h_indices) || (c->nnz && c->d_data && !h_data))
+            return fail(PW_ERR_INVALID, "pw_csr_create_device: host arrays must be given together (data only for a weighted CSR) or not at all");
+        return csr_create_impl(h_indptr, h_indices, c->d_data ? h_data : nullptr, (uint32_t)c->n_nodes, (uint32_t)c->nnz, c->device, out, d_csr);
+    }
+    std::unique_ptr<uint32_t[]> indptr(new (std::nothrow) uint32_t[c->n_nodes + 1]), indices(new (std::nothrow) uint32_t[c->nnz ? c->nnz : 1]);
+    std::unique_ptr<float[]> data(c->d_data ? new (std::nothrow) float[c->nnz ? c->nnz : 1] : nullptr);
+    if (!indptr || !indices || (c->d_data && !data)) return fail(PW_ERR_NOMEM, "pw_csr_create_device: host copy of the CSR");
+    int rc = pw_csr_dev_export(c, indptr.get(), indices.get(), data.get());
+    if (rc) return rc;
+    return csr_create_impl(indptr.get(), indices.get(), data.get(), (uint32_t)c->n_nodes, (uint32_t)c->nnz, c->device, out, d_csr);
 }
 
 PW_EXPORT int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t *index_bytes, uint64_t *lane_list_entries) {

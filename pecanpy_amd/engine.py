@@ -59,6 +59,45 @@ def tapered_bounds(n_jobs, n_chunks):
     return [(cuts[c], cuts[c + 1]) for c in range(n_chunks)]
 
 
+def check_edge_index(edge_index, edge_weight=None, num_nodes=None):
+    """Shape and dtype rules of ``from_edge_index``; returns ``m``.  Looks at metadata only (no library, no device): an
+    integer ``[2, m]`` torch tensor or NumPy array, a float ``[m]`` weight vector, a non-negative ``num_nodes``."""
+    def describe(x, what):
+        if isinstance(x, np.ndarray):
+            kind = "int" if x.dtype.kind in "iu" else "float" if x.dtype.kind == "f" else "other"
+            if x.dtype == np.uint64:
+                kind = "uint64"
+            return tuple(x.shape), kind
+        if type(x).__module__.split(".")[0] == "torch" and hasattr(x, "is_floating_point"):
+            import torch
+
+            kind = ("float" if x.is_floating_point() else
+                    "other" if x.is_complex() or x.dtype == torch.bool else
+                    "uint64" if x.dtype == getattr(torch, "uint64", None) else "int")
+            return tuple(x.shape), kind
+        raise ValueError(f"{what} must be a torch tensor or a NumPy array, got {type(x).__name__}")
+
+    shape, kind = describe(edge_index, "edge_index")
+    if len(shape) != 2 or shape[0] != 2:
+        raise ValueError(f"edge_index must have shape [2, m], got {list(shape)}")
+    if kind == "uint64":   # (ids of 2^63 or more would wrap negative on the way to int64)
+        raise ValueError("edge_index of dtype uint64 is not accepted: pass int64 (or a narrower integer type)")
+    if kind != "int":
+        raise ValueError("edge_index must hold integers (vertex i is id i)")
+    m = int(shape[1])
+    if edge_weight is not None:
+        wshape, wkind = describe(edge_weight, "edge_weight")
+        if wkind != "float":
+            raise ValueError("edge_weight must hold floats")
+        if len(wshape) != 1 or wshape[0] != m:
+            raise ValueError(f"edge_weight must have shape [{m}] (one weight per edge), got {list(wshape)}")
+    if num_nodes is not None and (int(num_nodes) != num_nodes or int(num_nodes) < 0):
+        raise ValueError("num_nodes must be a non-negative integer")
+    if num_nodes is not None and int(num_nodes) == 0 and m > 0:
+        raise ValueError("num_nodes = 0 with a non-empty edge list (omit num_nodes to have it inferred)")
+    return m
+
+
 class WalkEngine:
     def __init__(self, handle, lib, kind, n_nodes, device):
         self._h = handle
@@ -116,6 +155,79 @@ class WalkEngine:
             torch.cuda.current_stream(bits.device).synchronize()
             _lib.check(lib.pw_dense_create_bits(C.c_void_p(bits.data_ptr()), int(n_nodes), 1, int(device), C.byref(h)))
         return cls(h, lib, "dense", int(n_nodes), int(device))
+
+    @classmethod
+    def from_edge_index(cls, edge_index, edge_weight=None, num_nodes=None, directed=False, device=None):
+        """CSR handle from an edge list, built on the device (``pw_coo_to_csr_device`` + ``pw_csr_create_device``).
+
+        ``edge_index``: integer ``[2, m]`` torch tensor or NumPy array; ``edge_weight``: float ``[m]`` or ``None``.  A
+        CUDA tensor is used where it is (``device`` defaults to its device); host input is uploaded first and takes the
+        same path.  Vertex ``i`` is id ``i`` (no first-appearance renumbering, unlike the edge-list file reader); the
+        semantics are the reference's ``add_edge`` / ``to_csr``: non-positive weights dropped, the reverse edge inserted
+        unless ``directed``, the last insertion of a pair wins.
+
+        The engine carries the exported host arrays as ``eng.csr = (indptr, indices, data)`` (``data`` all ones when
+        unweighted) and ``eng.build_stats``: ``edge_list_host_bytes`` (bytes of the edge list that crossed the host:
+        0 for CUDA input), ``n_nodes``, ``nnz``, ``insertions``, ``dropped``, ``build_ms`` (device time of the CSR build)
+        and the wall clock of the stages (``coo_call_ms``, ``export_ms``, ``handle_ms``)."""
+        import time
+
+        m = check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
+        import torch
+
+        lib = _lib.load()
+        host_bytes = 0
+        if isinstance(edge_index, torch.Tensor) and edge_index.is_cuda:
+            dev = edge_index.device
+            if device is not None and int(device) != dev.index:
+                raise ValueError(f"edge_index lives on cuda:{dev.index}, the engine was asked for device {int(device)}")
+        else:
+            dev = torch.device("cuda", int(device or 0))
+            if int(lib.pw_device_count()) <= 0:
+                raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+
+        def to_dev(x, dtype):
+            nonlocal host_bytes
+            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+            if not t.is_cuda:
+                host_bytes += t.numel() * t.element_size()
+            return t.to(device=dev, dtype=dtype)
+
+        ei = to_dev(edge_index, torch.int64)
+        src, dst = ei[0].contiguous(), ei[1].contiguous()   # (rows of a contiguous [2, m] tensor: views, no copy)
+        w = to_dev(edge_weight, torch.float32).contiguous() if edge_weight is not None else None
+        if w is not None and w.device != dev:
+            raise ValueError("edge_index and edge_weight must be on the same device")
+        torch.cuda.current_stream(dev).synchronize()   # inputs were produced on torch's stream
+        t0 = time.perf_counter()
+        c = C.c_void_p()
+        _lib.check(lib.pw_coo_to_csr_device(dev.index, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                            C.c_void_p(w.data_ptr() if w is not None else 0), m,
+                                            int(num_nodes or 0), int(bool(directed)), C.byref(c)))
+        try:
+            t1 = time.perf_counter()
+            shape = [C.c_uint64(0) for _ in range(4)]
+            ms = C.c_double(0)
+            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
+            n, nnz, insertions, dropped = (int(s.value) for s in shape)
+            indptr = np.empty(n + 1, dtype=np.uint32)
+            indices = np.empty(nnz, dtype=np.uint32)
+            data = np.empty(nnz, dtype=np.float32)
+            _lib.check(lib.pw_csr_dev_export(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data)))
+            t2 = time.perf_counter()
+            h = C.c_void_p()
+            _lib.check(lib.pw_csr_create_device(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), C.byref(h)))   # (no second download)
+            t3 = time.perf_counter()
+        finally:
+            lib.pw_csr_dev_destroy(c)
+        eng = cls(h, lib, "csr", n, dev.index)
+        eng._max_degree = int(np.diff(indptr.astype(np.int64)).max()) if n else 0
+        eng._nnz = nnz
+        eng.csr = (indptr, indices, data)
+        eng.build_stats = {"edge_list_host_bytes": int(host_bytes), "n_nodes": n, "nnz": nnz, "insertions": insertions,
+                           "dropped": dropped, "build_ms": float(ms.value), "coo_call_ms": (t1 - t0) * 1e3,
+                           "export_ms": (t2 - t1) * 1e3, "handle_ms": (t3 - t2) * 1e3}
+        return eng
 
     def set_thresholds(self, thr):
         thr = np.ascontiguousarray(thr, dtype=np.float32)

@@ -79,6 +79,7 @@ class Base(BaseGraph):
         self.device = None  # GPU index; None -> LOCAL_RANK / 0
         self.last_stats = None
         self.last_embed_stats = None
+        self.last_build_stats = None   # from_edge_index: what the device build of the CSR did
         # the library's one-time start-up (~140 ms for the first stream it creates) runs on a helper thread beside what comes
         # next in the reference's flow -- reading the graph (cli.py:328-337) -- instead of in front of the first walk
         import os
@@ -412,6 +413,49 @@ class _SparseBase(Base, SparseGraph):
 
     def _make_engine(self, device):
         return WalkEngine.from_csr(self.indptr, self.indices, self.data, device=device)
+
+    @classmethod
+    def from_edge_index(cls, edge_index, edge_weight=None, num_nodes=None, directed=False, node_ids=None, **kwargs):
+        """Graph from an edge list held as arrays, the CSR built ON THE DEVICE (``pw_coo_to_csr_device``).
+
+        ``edge_index``: integer ``[2, m]`` torch tensor (a CUDA tensor is used where it is; a CPU tensor or a NumPy
+        array is uploaded first and takes the same path); ``edge_weight``: float ``[m]`` or ``None`` (unweighted);
+        ``num_nodes``: ``None`` = largest id listed + 1; ``node_ids``: as in ``from_csr``; ``kwargs``: the constructor's.
+
+        Vertex ``i`` IS id ``i``: there is no renumbering by first appearance, which is how ``read_edg`` numbers the
+        vertices of an edge-list file.  Otherwise the semantics are the reference's ``AdjlstGraph.add_edge`` /
+        ``to_csr`` (graph.py:238-268, 323-341): an edge with a non-positive weight is dropped (one ``RuntimeWarning``
+        with the count), every kept edge is inserted in both directions unless ``directed``, the last insertion of an
+        ordered pair wins, rows come out ascending.  NaN or infinite weights and ids outside ``[0, num_nodes)`` raise.
+
+        The object's host ``indptr`` / ``indices`` / ``data`` are filled from the device CSR (``data`` all ones when
+        unweighted, as ``from_csr`` does) and the walk handle created from it is installed as the object's engine: the
+        first ``simulate_walks`` / ``embed_array`` does not upload the graph again.  ``last_build_stats`` records the
+        call (``edge_list_host_bytes``: 0 for a CUDA ``edge_index``; sizes, ``dropped``, ``build_ms``, stage times)."""
+        from .engine import check_edge_index
+
+        check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
+        g = cls(**kwargs)
+        device = edge_index.device.index if getattr(edge_index, "is_cuda", False) else g._device_index()
+        eng = WalkEngine.from_edge_index(edge_index, edge_weight, num_nodes=num_nodes, directed=directed, device=device)
+        try:
+            if node_ids is not None and len(node_ids) != eng.n_nodes:
+                raise ValueError(f"node_ids has {len(node_ids)} entries, the graph has {eng.n_nodes} vertices")
+        except Exception:
+            eng.close()
+            raise
+        if device != g._device_index():
+            g.device = device   # (a CUDA edge_index decides where the graph lives)
+        g.indptr, g.indices, g.data = eng.csr
+        g.set_node_ids(node_ids, implicit_ids=node_ids is None, num_nodes=eng.n_nodes)
+        g._engine = eng
+        g._engine_key = (g._graph_key(), g._device_index())
+        g.last_build_stats = dict(eng.build_stats)
+        if eng.build_stats["dropped"]:
+            import warnings
+
+            warnings.warn(f"{eng.build_stats['dropped']} non-positive edge(s) ignored", RuntimeWarning, stacklevel=2)
+        return g
 
     def get_has_nbrs(self):
         """``has_nbrs(idx)`` callback (sparse_rw.py:12-20); host-side helper, not used by the GPU path."""
