@@ -206,6 +206,35 @@ int pw_dense_create(const double *data, uint32_t n_nodes, int device, pw_graph *
 int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, int on_device, int device,
                          pw_graph **out);
 
+/* ---- dense handles built on the device ------------------------------------------------------------------------------------
+ * pw_dense_create is one host thread over all n^2 values; these entries make the same handle from data that is already in
+ * device memory (csrc/dense_build.hip.h): two passes over the matrix, or one over a device CSR.
+ *   pw_dense_create_device    d_data: row-major [n_nodes, n_nodes] matrix on `device`, float64 (is_f32 = 0) or float32 (is_f32
+ *                             != 0: every value widened to float64, which is exact).  The handle equals pw_dense_create's on the
+ *                             same values: packed adjacency rows (tail bits zero), rows compressed in ascending column order,
+ *                             values dropped when they are all 1.0, degrees, the same 2^32 - 1 edge limit.  A NaN is a non-zero
+ *                             entry, -0.0 is none.  n_nodes == 0: PW_ERR_INVALID.  The matrix is only read, and not referenced
+ *                             after the call.  Work runs on the handle's stream; the call returns when it is done.
+ *   pw_dense_create_from_csr  the same handle from a pw_csr_dev (pw_coo_to_csr_device): the dense float64 form of that CSR --
+ *                             float32 weights widened, every weight 1.0 when the CSR has none.  The pw_csr_dev stays valid.
+ *   build_ms (optional)       HIP-event time of the build's kernels; allocations and the small device-to-host reads between
+ *                             them are outside it (as pw_csr_dev_shape's build_ms).
+ *   pw_dense_noise_thresholds the node2vec+ thresholds pw_noise_thresholds_dense computes from the matrix, computed on the device
+ *                             from the handle's compressed rows (all ones for a unit handle; NaN for an empty row), bit for bit;
+ *                             installed in the handle as pw_graph_set_thresholds installs them and copied to thr[n_nodes] when
+ *                             thr is not NULL.  PW_ERR_UNSUPPORTED for CSR handles and pw_dense_create_bits handles.
+ *   pw_dense_shape            n_nodes, nnz, words per adjacency row, maximum degree of a dense handle; NULL = skip
+ *   pw_dense_export           test hook and host read-back: copies to host arrays of the caller indptr uint32[n + 1], indices
+ *                             uint32[nnz], data float64[nnz] (all 1.0 for a unit handle), adjbits uint64[n * words_per_row], deg
+ *                             uint32[n]; *flags: bit 0 = unit, bit 1 = dense_nonneg; NULL = skip.  indices / data:
+ *                             PW_ERR_UNSUPPORTED for pw_dense_create_bits handles. */
+int pw_dense_create_device(int device, const void *d_data, int is_f32, uint32_t n_nodes, pw_graph **out, double *build_ms);
+int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, double *build_ms);
+int pw_dense_noise_thresholds(pw_graph *g, double gamma, float *thr);
+int pw_dense_shape(const pw_graph *g, uint32_t *n_nodes, uint32_t *nnz, uint32_t *words_per_row, uint32_t *max_degree);
+int pw_dense_export(pw_graph *g, uint32_t *indptr, uint32_t *indices, double *data, uint64_t *adjbits, uint32_t *deg,
+                    uint32_t *flags);
+
 /* node2vec+ noise thresholds, float32[n_nodes] (sparse_rw.py:22-35 / dense_rw.py:11-19);
  * required before a call with extend != 0. */
 int pw_graph_set_thresholds(pw_graph *g, const float *thr);
@@ -361,6 +390,9 @@ int pw_noise_thresholds_csr_f64(const uint32_t *indptr, const float *data, uint3
  * differ by an ulp when gamma * std is not exact in float32 (gamma = 0.1, ...); the Python layer picks the one that
  * matches the installed NumPy, i.e. what the reference's expression would give in the same environment. */
 int pw_noise_thresholds_csr_numpy1(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr);
+/* Test hook: the dense formula for ONE row of n values (a row's non-zeros in column order) as the device computes it in
+ * pw_dense_noise_thresholds -- the host build of the same routine (csrc/dense_build.hip.h: threshold_row). */
+int pw_selftest_thresholds_row(const double *row, uint64_t n, double gamma, float *thr);
 
 /* ---- edge-list ingestion (host side; usable without a GPU) -------------------------------- */
 /* Fast path of AdjlstGraph.read + to_csr (reference src/pecanpy/graph.py:270-341): parses a 2- or

@@ -92,6 +92,11 @@ SYMBOLS = {
     "pw_lane_index_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pw_dense_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "pw_dense_create_bits": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "pw_dense_create_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_double)]),
+    "pw_dense_create_from_csr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double)]),
+    "pw_dense_noise_thresholds": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "pw_dense_shape": (C.c_int, [C.c_void_p, _u32p, _u32p, _u32p, _u32p]),
+    "pw_dense_export": (C.c_int, [C.c_void_p] * 6 + [_u32p]),
     "pw_graph_set_thresholds": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pw_graph_destroy": (None, [C.c_void_p]),
     "pw_simulate": (C.c_int, _SIM_ARGS),
@@ -120,6 +125,7 @@ SYMBOLS = {
     "pw_stream_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_noise_thresholds_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_noise_thresholds_csr_numpy1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
+    "pw_selftest_thresholds_row": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p]),
     "pw_noise_thresholds_dense": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_noise_thresholds_csr_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_edgelist_read": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),

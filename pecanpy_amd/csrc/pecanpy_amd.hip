@@ -37,6 +37,7 @@
 #include "walk_lanes.hip.h"
 #include "sgns.hip.h"
 #include "coo_csr.hip.h"
+#include "dense_build.hip.h"
 
 #define PW_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -1381,6 +1382,199 @@ PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, in
     if (e == hipSuccess) e = hipMemcpy(g->gd->d_indptr, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice);
     if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
     *out = g;
+    return PW_OK;
+}
+
+// ---- dense handles built on the device (csrc/dense_build.hip.h) -------------------------------------------------------------
+namespace {
+
+// what the two device builders share once adjbits, deg and the flags are on the device: degrees down, indptr and max_degree
+// as pw_dense_create_bits computes them (same edge limit, same message), indptr up
+int dense_finish_degrees(pw_graph *g, uint32_t flags, std::vector<uint32_t> &indptr) {
+    GraphData &gd = *g->gd;
+    const uint64_t n = gd.n_nodes;
+    std::vector<uint32_t> deg(n);
+    HIP_TRY(hipMemcpy(deg.data(), gd.d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    indptr.assign(n + 1, 0);
+    uint64_t nnz = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        nnz += deg[i];
+        if (nnz >= 0xffffffffull) return fail(PW_ERR_INVALID, "dense graph has more than 2^32-1 edges");
+        indptr[i + 1] = (uint32_t)nnz;
+        if (deg[i] > gd.max_degree) gd.max_degree = deg[i];
+    }
+    gd.nnz = (uint32_t)nnz;
+    gd.unit = !(flags & pw::DENSE_FLAG_NOT_UNIT);
+    gd.dense_nonneg = !(flags & pw::DENSE_FLAG_NOT_NONNEG);
+    return 0;
+}
+
+unsigned dense_row_grid(uint64_t n) { return (unsigned)std::min<uint64_t>(n, 1u << 20); }   // one workgroup per row, rows strided beyond
+
+}  // namespace
+
+PW_EXPORT int pw_dense_create_device(int device, const void *d_data, int is_f32, uint32_t n_nodes, pw_graph **out, double *build_ms) {
+    if (!d_data || !out) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_nodes == 0) return fail(PW_ERR_INVALID, "pw_dense_create_device: empty graph");
+    pw_graph *g = new pw_graph();
+    int rc = graph_common_init(g, device);
+    if (rc) { pw_graph_destroy(g); return rc; }
+    GraphData &gd = *g->gd;
+    const uint64_t n = n_nodes;
+    const uint32_t wpr = (uint32_t)((n + 63) / 64);
+    gd.kind = 1;
+    gd.n_nodes = n_nodes;
+    gd.words_per_row = wpr;
+    uint32_t *d_flags = nullptr;
+    // the kernels run on the handle's stream between event pairs; allocations, the degree download and the indptr upload lie
+    // outside the pairs (build_ms as pw_csr_dev's is defined)
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&gd.d_adjbits, sizeof(uint64_t) * n * wpr));
+        HIP_TRY(hipMalloc((void **)&gd.d_deg, sizeof(uint32_t) * n));
+        HIP_TRY(hipMalloc((void **)&d_flags, sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), g->stream));
+        HIP_TRY(hipEventRecord(g->ev[0], g->stream));
+        if (is_f32)
+            hipLaunchKernelGGL(pw::dense_count_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
+                               gd.d_adjbits, gd.d_deg, d_flags);
+        else
+            hipLaunchKernelGGL(pw::dense_count_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
+                               gd.d_adjbits, gd.d_deg, d_flags);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(g->ev[1], g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        uint32_t flags = 0;
+        HIP_TRY(hipMemcpy(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> indptr;
+        int r = dense_finish_degrees(g, flags, indptr);
+        if (r) return r;
+        const uint64_t nnz = gd.nnz;
+        HIP_TRY(hipMalloc((void **)&gd.d_indptr, sizeof(uint32_t) * (n + 1)));
+        HIP_TRY(hipMemcpy(gd.d_indptr, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc((void **)&gd.d_indices, nnz ? sizeof(uint32_t) * nnz : 8));
+        if (!gd.unit) HIP_TRY(hipMalloc((void **)&gd.d_data, nnz ? sizeof(double) * nnz : 8));
+        HIP_TRY(hipEventRecord(g->ev[2], g->stream));
+        if (nnz) {
+            if (is_f32)
+                hipLaunchKernelGGL(pw::dense_fill_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
+                                   (const uint64_t *)gd.d_adjbits, (const uint32_t *)gd.d_indptr, gd.d_indices, (double *)gd.d_data);
+            else
+                hipLaunchKernelGGL(pw::dense_fill_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
+                                   (const uint64_t *)gd.d_adjbits, (const uint32_t *)gd.d_indptr, gd.d_indices, (double *)gd.d_data);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(g->ev[3], g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        float ms_count = 0, ms_fill = 0;
+        HIP_TRY(hipEventElapsedTime(&ms_count, g->ev[0], g->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms_fill, g->ev[2], g->ev[3]));
+        if (build_ms) *build_ms = (double)ms_count + (double)ms_fill;
+        return 0;
+    };
+    rc = body();
+    if (d_flags) (void)hipFree(d_flags);
+    if (rc) { pw_graph_destroy(g); return rc; }
+    *out = g;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, double *build_ms) {
+    if (!c || !out) return fail(PW_ERR_INVALID, "null pointer");
+    if (c->n_nodes == 0) return fail(PW_ERR_INVALID, "pw_dense_create_from_csr: empty graph");
+    pw_graph *g = new pw_graph();
+    int rc = graph_common_init(g, c->device);
+    if (rc) { pw_graph_destroy(g); return rc; }
+    GraphData &gd = *g->gd;
+    const uint64_t n = c->n_nodes, nnz = c->nnz;
+    const uint32_t wpr = (uint32_t)((n + 63) / 64);
+    gd.kind = 1;
+    gd.n_nodes = (uint32_t)n;
+    gd.words_per_row = wpr;
+    uint32_t *d_flags = nullptr;
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&gd.d_adjbits, sizeof(uint64_t) * n * wpr));
+        HIP_TRY(hipMalloc((void **)&gd.d_deg, sizeof(uint32_t) * n));
+        HIP_TRY(hipMalloc((void **)&gd.d_indptr, sizeof(uint32_t) * (n + 1)));
+        HIP_TRY(hipMalloc((void **)&gd.d_indices, nnz ? sizeof(uint32_t) * nnz : 8));
+        if (c->d_data) HIP_TRY(hipMalloc((void **)&gd.d_data, nnz ? sizeof(double) * nnz : 8));
+        HIP_TRY(hipMalloc((void **)&d_flags, sizeof(uint32_t)));
+        HIP_TRY(hipEventRecord(g->ev[0], g->stream));
+        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), g->stream));
+        HIP_TRY(hipMemsetAsync(gd.d_adjbits, 0, sizeof(uint64_t) * n * wpr, g->stream));
+        HIP_TRY(hipMemcpyAsync(gd.d_indptr, c->d_indptr, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToDevice, g->stream));
+        if (nnz) HIP_TRY(hipMemcpyAsync(gd.d_indices, c->d_indices, sizeof(uint32_t) * nnz, hipMemcpyDeviceToDevice, g->stream));
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, 1u << 20);
+        hipLaunchKernelGGL(pw::csr_to_dense_kernel, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr, (const uint32_t *)c->d_indices,
+                           (const float *)c->d_data, (uint32_t)n, wpr, gd.d_adjbits, (double *)gd.d_data, gd.d_deg, d_flags);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(g->ev[1], g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        uint32_t flags = 0;
+        HIP_TRY(hipMemcpy(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> indptr;
+        int r = dense_finish_degrees(g, flags, indptr);
+        if (r) return r;
+        if (gd.nnz != nnz) return fail(PW_ERR_HIP, "pw_dense_create_from_csr: degrees do not add up to the CSR's entries (internal error)");
+        if (gd.unit && gd.d_data) {   // every weight 1.0: the values are dropped, as pw_dense_create drops them
+            (void)hipFree(gd.d_data);
+            gd.d_data = nullptr;
+        }
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+        if (build_ms) *build_ms = ms;
+        return 0;
+    };
+    rc = body();
+    if (d_flags) (void)hipFree(d_flags);
+    if (rc) { pw_graph_destroy(g); return rc; }
+    *out = g;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_dense_noise_thresholds(pw_graph *g, double gamma, float *thr) {
+    if (!g) return fail(PW_ERR_INVALID, "null pointer");
+    GraphData &gd = *g->gd;
+    if (gd.kind != 1 || gd.bits_only) return fail(PW_ERR_UNSUPPORTED, "pw_dense_noise_thresholds: needs a dense handle with compressed rows");
+    if (set_device(g)) return PW_ERR_HIP;
+    const uint64_t n = gd.n_nodes;
+    if (n == 0) return PW_OK;
+    if (!gd.d_thr) HIP_TRY(hipMalloc((void **)&gd.d_thr, sizeof(float) * n));
+    hipLaunchKernelGGL(pw::dense_thresholds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, (const uint32_t *)gd.d_indptr,
+                       (const double *)gd.d_data, gd.n_nodes, gamma, gd.d_thr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    gd.thr_version++;
+    if (thr) HIP_TRY(hipMemcpy(thr, gd.d_thr, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return PW_OK;
+}
+
+PW_EXPORT int pw_dense_export(pw_graph *g, uint32_t *indptr, uint32_t *indices, double *data, uint64_t *adjbits, uint32_t *deg, uint32_t *flags) {
+    if (!g) return fail(PW_ERR_INVALID, "null pointer");
+    const GraphData &gd = *g->gd;
+    if (gd.kind != 1) return fail(PW_ERR_UNSUPPORTED, "pw_dense_export: not a dense handle");
+    if ((indices || data) && gd.bits_only) return fail(PW_ERR_UNSUPPORTED, "pw_dense_export: a handle created from packed bits has no compressed rows");
+    if (set_device(g)) return PW_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    const uint64_t n = gd.n_nodes, nnz = gd.nnz;
+    if (indptr) HIP_TRY(hipMemcpy(indptr, gd.d_indptr, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToHost));
+    if (indices && nnz) HIP_TRY(hipMemcpy(indices, gd.d_indices, sizeof(uint32_t) * nnz, hipMemcpyDeviceToHost));
+    if (data && nnz) {
+        if (gd.d_data) HIP_TRY(hipMemcpy(data, gd.d_data, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+        else std::fill(data, data + nnz, 1.0);
+    }
+    if (adjbits && n) HIP_TRY(hipMemcpy(adjbits, gd.d_adjbits, sizeof(uint64_t) * n * gd.words_per_row, hipMemcpyDeviceToHost));
+    if (deg && n) HIP_TRY(hipMemcpy(deg, gd.d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    if (flags) *flags = (gd.unit ? 1u : 0u) | (gd.dense_nonneg ? 2u : 0u);
+    return PW_OK;
+}
+
+PW_EXPORT int pw_dense_shape(const pw_graph *g, uint32_t *n_nodes, uint32_t *nnz, uint32_t *words_per_row, uint32_t *max_degree) {
+    if (!g) return fail(PW_ERR_INVALID, "null pointer");
+    if (g->gd->kind != 1) return fail(PW_ERR_UNSUPPORTED, "pw_dense_shape: not a dense handle");
+    if (n_nodes) *n_nodes = g->gd->n_nodes;
+    if (nnz) *nnz = g->gd->nnz;
+    if (words_per_row) *words_per_row = g->gd->words_per_row;
+    if (max_degree) *max_degree = g->gd->max_degree;
     return PW_OK;
 }
 
@@ -4443,6 +4637,12 @@ PW_EXPORT int pw_noise_thresholds_dense(const double *data, uint32_t n_nodes, do
 }
 
 // ---- edge-list ingestion (host only) ----------------------------------------------------------------
+PW_EXPORT int pw_selftest_thresholds_row(const double *row, uint64_t n, double gamma, float *thr) {
+    if ((n && !row) || !thr) return fail(PW_ERR_INVALID, "null pointer");
+    *thr = pw::threshold_row([row](uint64_t i) { return row[i]; }, n, gamma);
+    return PW_OK;
+}
+
 struct pw_edgelist {
     pw::EdgeList el;
 };

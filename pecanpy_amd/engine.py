@@ -98,6 +98,62 @@ def check_edge_index(edge_index, edge_weight=None, num_nodes=None):
     return m
 
 
+def check_dense_matrix(mat, device=None):
+    """Shape and dtype rules of ``from_dense_tensor``; returns ``n``.  Looks at metadata only (no library, no device): a
+    square, non-empty 2-d torch tensor or NumPy array of a real dtype (float or integer; not bool, not complex), and a
+    ``device`` that does not contradict the device of a CUDA tensor."""
+    if isinstance(mat, np.ndarray):
+        kind = {"f": "float", "i": "int", "u": "int", "b": "bool", "c": "complex"}.get(mat.dtype.kind, "other")
+    elif hasattr(mat, "is_floating_point") and hasattr(mat, "is_complex") and hasattr(mat, "shape"):   # a torch tensor
+        kind = ("complex" if mat.is_complex() else "float" if mat.is_floating_point() else
+                "bool" if str(mat.dtype).endswith("bool") else "int")
+    else:
+        raise ValueError(f"dense adjacency must be a torch tensor or a NumPy array, got {type(mat).__name__}")
+    shape = tuple(mat.shape)
+    if len(shape) != 2 or shape[0] != shape[1]:
+        raise ValueError(f"dense adjacency must be a square 2-d matrix, got shape {list(shape)}")
+    if shape[0] == 0:
+        raise ValueError("dense adjacency must have at least one vertex")
+    if shape[0] > 0xFFFFFFFF:
+        raise ValueError("dense adjacency has more than 2^32 - 1 vertices")
+    if kind not in ("float", "int"):
+        raise ValueError(f"dense adjacency must hold real numbers (float or integer), got {mat.dtype}")
+    if getattr(mat, "is_cuda", False) and device is not None and int(device) != mat.device.index:
+        raise ValueError(f"the matrix lives on cuda:{mat.device.index}, the engine was asked for device {int(device)}")
+    return int(shape[0])
+
+
+def _edge_list_to_device(lib, edge_index, edge_weight, device):
+    """The device tensors ``(src, dst, w, dev, host_bytes)`` of an edge list that passed ``check_edge_index``: a CUDA tensor is
+    used where it is, host input is uploaded; torch's stream is synchronised (the library works on its own streams)."""
+    import torch
+
+    host_bytes = 0
+    if isinstance(edge_index, torch.Tensor) and edge_index.is_cuda:
+        dev = edge_index.device
+        if device is not None and int(device) != dev.index:
+            raise ValueError(f"edge_index lives on cuda:{dev.index}, the engine was asked for device {int(device)}")
+    else:
+        dev = torch.device("cuda", int(device or 0))
+        if int(lib.pw_device_count()) <= 0:
+            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+
+    def to_dev(x, dtype):
+        nonlocal host_bytes
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        if not t.is_cuda:
+            host_bytes += t.numel() * t.element_size()
+        return t.to(device=dev, dtype=dtype)
+
+    ei = to_dev(edge_index, torch.int64)
+    src, dst = ei[0].contiguous(), ei[1].contiguous()   # (rows of a contiguous [2, m] tensor: views, no copy)
+    w = to_dev(edge_weight, torch.float32).contiguous() if edge_weight is not None else None
+    if w is not None and w.device != dev:
+        raise ValueError("edge_index and edge_weight must be on the same device")
+    torch.cuda.current_stream(dev).synchronize()   # inputs were produced on torch's stream
+    return src, dst, w, dev, host_bytes
+
+
 class WalkEngine:
     def __init__(self, handle, lib, kind, n_nodes, device):
         self._h = handle
@@ -173,32 +229,8 @@ class WalkEngine:
         import time
 
         m = check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
-        import torch
-
         lib = _lib.load()
-        host_bytes = 0
-        if isinstance(edge_index, torch.Tensor) and edge_index.is_cuda:
-            dev = edge_index.device
-            if device is not None and int(device) != dev.index:
-                raise ValueError(f"edge_index lives on cuda:{dev.index}, the engine was asked for device {int(device)}")
-        else:
-            dev = torch.device("cuda", int(device or 0))
-            if int(lib.pw_device_count()) <= 0:
-                raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
-
-        def to_dev(x, dtype):
-            nonlocal host_bytes
-            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-            if not t.is_cuda:
-                host_bytes += t.numel() * t.element_size()
-            return t.to(device=dev, dtype=dtype)
-
-        ei = to_dev(edge_index, torch.int64)
-        src, dst = ei[0].contiguous(), ei[1].contiguous()   # (rows of a contiguous [2, m] tensor: views, no copy)
-        w = to_dev(edge_weight, torch.float32).contiguous() if edge_weight is not None else None
-        if w is not None and w.device != dev:
-            raise ValueError("edge_index and edge_weight must be on the same device")
-        torch.cuda.current_stream(dev).synchronize()   # inputs were produced on torch's stream
+        src, dst, w, dev, host_bytes = _edge_list_to_device(lib, edge_index, edge_weight, device)
         t0 = time.perf_counter()
         c = C.c_void_p()
         _lib.check(lib.pw_coo_to_csr_device(dev.index, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
@@ -228,6 +260,131 @@ class WalkEngine:
                            "dropped": dropped, "build_ms": float(ms.value), "coo_call_ms": (t1 - t0) * 1e3,
                            "export_ms": (t2 - t1) * 1e3, "handle_ms": (t3 - t2) * 1e3}
         return eng
+
+    @classmethod
+    def from_dense_tensor(cls, mat, device=None):
+        """Dense handle from a matrix, built on the device (``pw_dense_create_device``): the same handle as ``from_dense`` on
+        the same values, without the host pass over the ``n * n`` entries.
+
+        ``mat``: square 2-d torch tensor or NumPy array.  float64 and float32 are used as they are (float32 is widened to
+        float64 inside the kernels, which is exact); other real dtypes are converted to float64.  A CUDA tensor is used
+        where it is (made contiguous if needed; ``device`` defaults to its device); host input is uploaded first and takes
+        the same path.  The matrix is not referenced after the call.
+
+        ``eng.build_stats``: ``matrix_host_bytes`` (bytes of the matrix that crossed from the host: 0 for CUDA input),
+        ``n_nodes``, ``nnz``, ``unit``, ``build_ms`` (device time of the build's kernels) and the wall clock of the stages
+        (``upload_ms``: conversion / upload / making contiguous; ``create_call_ms``: the library call)."""
+        import time
+
+        n = check_dense_matrix(mat, device)   # ValueError before the library or a device is touched
+        import torch
+
+        lib = _lib.load()
+        t0 = time.perf_counter()
+        host_bytes = 0
+        if isinstance(mat, torch.Tensor) and mat.is_cuda:
+            t = mat
+        else:
+            if int(lib.pw_device_count()) <= 0:
+                raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+            if isinstance(mat, np.ndarray):
+                if mat.dtype not in (np.float32, np.float64):
+                    mat = mat.astype(np.float64)
+                t = torch.from_numpy(np.ascontiguousarray(mat))
+            else:
+                t = mat if mat.dtype in (torch.float32, torch.float64) else mat.to(torch.float64)
+            host_bytes = t.numel() * t.element_size()
+            t = t.to(torch.device("cuda", int(device or 0)))
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        t = t.contiguous()
+        dev = t.device
+        torch.cuda.current_stream(dev).synchronize()   # the matrix was produced on torch's stream
+        t1 = time.perf_counter()
+        h, ms = C.c_void_p(), C.c_double(0)
+        _lib.check(lib.pw_dense_create_device(dev.index, C.c_void_p(t.data_ptr()), int(t.dtype == torch.float32), n,
+                                              C.byref(h), C.byref(ms)))
+        t2 = time.perf_counter()
+        del t
+        eng = cls(h, lib, "dense", n, dev.index)
+        shape = eng._dense_shape()
+        eng._max_degree, eng._nnz = shape["max_degree"], shape["nnz"]
+        eng.build_stats = {"matrix_host_bytes": int(host_bytes), "n_nodes": n, "nnz": shape["nnz"], "unit": eng._dense_flags()[0],
+                           "build_ms": float(ms.value), "upload_ms": (t1 - t0) * 1e3, "create_call_ms": (t2 - t1) * 1e3}
+        return eng
+
+    @classmethod
+    def dense_from_edge_index(cls, edge_index, edge_weight=None, num_nodes=None, directed=False, device=None):
+        """Dense handle from an edge list, built on the device: ``pw_coo_to_csr_device`` (the rules of ``from_edge_index``),
+        then ``pw_dense_create_from_csr``.  The matrix the handle stands for holds the float32 weights widened to float64
+        (1.0 everywhere when ``edge_weight`` is ``None``).  ``eng.build_stats`` has the keys of ``from_edge_index``
+        (``export_ms`` is 0: nothing is exported; ``handle_ms``: the dense handle) and ``dense_build_ms``, the device time
+        of the dense build's kernels."""
+        import time
+
+        m = check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
+        lib = _lib.load()
+        src, dst, w, dev, host_bytes = _edge_list_to_device(lib, edge_index, edge_weight, device)
+        t0 = time.perf_counter()
+        c = C.c_void_p()
+        _lib.check(lib.pw_coo_to_csr_device(dev.index, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                            C.c_void_p(w.data_ptr() if w is not None else 0), m,
+                                            int(num_nodes or 0), int(bool(directed)), C.byref(c)))
+        try:
+            t1 = time.perf_counter()
+            shape = [C.c_uint64(0) for _ in range(4)]
+            ms, dense_ms = C.c_double(0), C.c_double(0)
+            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
+            n, nnz, insertions, dropped = (int(s.value) for s in shape)
+            h = C.c_void_p()
+            _lib.check(lib.pw_dense_create_from_csr(c, C.byref(h), C.byref(dense_ms)))
+            t2 = time.perf_counter()
+        finally:
+            lib.pw_csr_dev_destroy(c)
+        eng = cls(h, lib, "dense", n, dev.index)
+        eng._max_degree, eng._nnz = eng._dense_shape()["max_degree"], nnz
+        eng.build_stats = {"edge_list_host_bytes": int(host_bytes), "n_nodes": n, "nnz": nnz, "insertions": insertions,
+                           "dropped": dropped, "build_ms": float(ms.value), "coo_call_ms": (t1 - t0) * 1e3, "export_ms": 0.0,
+                           "handle_ms": (t2 - t1) * 1e3, "dense_build_ms": float(dense_ms.value)}
+        return eng
+
+    def _dense_shape(self):
+        v = [C.c_uint32(0) for _ in range(4)]
+        _lib.check(self._lib.pw_dense_shape(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_nodes", "nnz", "words_per_row", "max_degree"), (int(x.value) for x in v)))
+
+    def _dense_flags(self):
+        f = C.c_uint32(0)
+        _lib.check(self._lib.pw_dense_export(self._h, None, None, None, None, None, C.byref(f)))
+        return bool(f.value & 1), bool(f.value & 2)
+
+    def dense_arrays(self, rows=True):
+        """Host copies of a dense handle's arrays (``pw_dense_export``) as a dict: ``indptr`` uint32[n + 1], ``indices``
+        uint32[nnz] and ``data`` float64[nnz] (the rows compressed in ascending column order; ``data`` all ones for a unit
+        handle), ``adjbits`` uint64[n, words_per_row], ``deg`` uint32[n], the flags ``unit`` and ``dense_nonneg``, and
+        ``nnz``, ``words_per_row``, ``max_degree``.  ``rows=False`` leaves ``indices`` / ``data`` out (handles made from
+        packed bits have none)."""
+        shape = self._dense_shape()
+        n, nnz, wpr = shape["n_nodes"], shape["nnz"], shape["words_per_row"]
+        out = {"indptr": np.zeros(n + 1, dtype=np.uint32), "adjbits": np.zeros((n, wpr), dtype=np.uint64),
+               "deg": np.zeros(n, dtype=np.uint32)}
+        if rows:
+            out["indices"] = np.zeros(nnz, dtype=np.uint32)
+            out["data"] = np.zeros(nnz, dtype=np.float64)
+        flags = C.c_uint32(0)
+        _lib.check(self._lib.pw_dense_export(self._h, _np_ptr(out["indptr"]), _np_ptr(out.get("indices")), _np_ptr(out.get("data")),
+                                             _np_ptr(out["adjbits"]), _np_ptr(out["deg"]), C.byref(flags)))
+        out.update(unit=bool(flags.value & 1), dense_nonneg=bool(flags.value & 2), nnz=nnz, words_per_row=wpr,
+                   max_degree=shape["max_degree"])
+        return out
+
+    def compute_thresholds(self, gamma):
+        """node2vec+ noise thresholds of a dense handle computed on the device from its compressed rows
+        (``pw_dense_noise_thresholds``: what ``pw_noise_thresholds_dense`` gives for the matrix, bit for bit) and installed
+        in the handle; returns them as float32[n_nodes]."""
+        thr = np.zeros(self.n_nodes, dtype=np.float32)
+        _lib.check(self._lib.pw_dense_noise_thresholds(self._h, float(gamma), _np_ptr(thr)))
+        return thr
 
     def set_thresholds(self, thr):
         thr = np.ascontiguousarray(thr, dtype=np.float32)

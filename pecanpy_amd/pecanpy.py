@@ -79,7 +79,7 @@ class Base(BaseGraph):
         self.device = None  # GPU index; None -> LOCAL_RANK / 0
         self.last_stats = None
         self.last_embed_stats = None
-        self.last_build_stats = None   # from_edge_index: what the device build of the CSR did
+        self.last_build_stats = None   # from_edge_index / from_tensor: what the device build of the graph did
         # the library's one-time start-up (~140 ms for the first stream it creates) runs on a helper thread beside what comes
         # next in the reference's flow -- reading the graph (cli.py:328-337) -- instead of in front of the first walk
         import os
@@ -545,12 +545,113 @@ class _DenseBase(Base, DenseGraph):
         Base.__init__(self, *args, **kwargs)
         self._data = None
         self._nonzero = None
+        self._device_built = None   # from_tensor / from_edge_index: token of the graph the installed engine was built from
 
     def _graph_key(self):
+        if self._device_built is not None:   # (survives the lazy fill of `data`: the engine keeps walking)
+            return ("device-built", id(self._device_built))
         return (id(self._data),)
 
     def _make_engine(self, device):
         return WalkEngine.from_dense(self.data, device=device)
+
+    def _get_engine(self):
+        if (self._device_built is not None and self._data is None and self._engine is not None
+                and self._engine_key != (self._graph_key(), self._device_index())):
+            self._materialize()   # the object moves to another device: the matrix comes down before its engine goes
+        return super()._get_engine()
+
+    # ---- graphs built on the device: the host matrix is filled on first read -------------------------------------------
+    def _materialize(self):
+        """``data`` / ``nonzero`` of an object made by ``from_tensor`` / ``from_edge_index``, rebuilt on the host from the
+        handle's compressed rows (``WalkEngine.dense_arrays``): the values the reference's attributes would hold."""
+        if self._data is not None or self._device_built is None or self._engine is None:
+            return
+        a = self._engine.dense_arrays()
+        n = self._engine.n_nodes
+        rows = np.repeat(np.arange(n), np.diff(a["indptr"].astype(np.int64)))
+        mat = np.zeros((n, n))
+        mat[rows, a["indices"]] = a["data"]
+        nonzero = np.zeros((n, n), dtype=bool)
+        nonzero[rows, a["indices"]] = True
+        self._data, self._nonzero = mat, nonzero
+
+    @property
+    def data(self):
+        self._materialize()
+        return self._data
+
+    @data.setter
+    def data(self, data):
+        self._device_built = None   # a matrix assigned by the caller replaces a graph built on the device
+        DenseGraph.data.fset(self, data)
+
+    @property
+    def nonzero(self):
+        self._materialize()
+        return self._nonzero
+
+    def _install_device_engine(self, eng, device, node_ids):
+        try:
+            if node_ids is not None and len(node_ids) != eng.n_nodes:
+                raise ValueError(f"node_ids has {len(node_ids)} entries, the graph has {eng.n_nodes} vertices")
+        except Exception:
+            eng.close()
+            raise
+        if device != self._device_index():
+            self.device = device   # (a CUDA input decides where the graph lives)
+        self.set_node_ids(node_ids, implicit_ids=node_ids is None, num_nodes=eng.n_nodes)
+        self._data = self._nonzero = None
+        self._device_built = object()
+        self._engine = eng
+        self._engine_key = (self._graph_key(), self._device_index())
+        self.last_build_stats = dict(eng.build_stats)
+
+    @classmethod
+    def from_tensor(cls, adj, node_ids=None, **kwargs):
+        """Graph from a dense adjacency matrix, the walk handle built ON THE DEVICE (``pw_dense_create_device``).
+
+        ``adj``: square 2-d torch tensor or NumPy array (float64 / float32 as they are, other real dtypes converted to
+        float64).  A CUDA tensor is used where it is and decides the device; a CPU tensor or a NumPy array is uploaded
+        first and takes the same path.  ``node_ids``: as in ``from_mat`` (``None``: ``"0" .. "N-1"``); ``kwargs``: the
+        constructor's.
+
+        The handle is installed as the object's engine and equals the one ``from_mat`` would create from the same values,
+        so the walks are the same.  The object keeps no reference to ``adj`` and does not download the matrix: ``data`` and
+        ``nonzero`` are rebuilt on the host from the handle's compressed rows when they are first read, and until then
+        ``get_noise_thresholds`` computes on the device (``pw_dense_noise_thresholds``).  ``last_build_stats`` records the
+        call (``matrix_host_bytes``: 0 for a CUDA tensor; ``n_nodes``, ``nnz``, ``unit``, ``build_ms``, stage times)."""
+        from .engine import check_dense_matrix
+
+        check_dense_matrix(adj)   # ValueError before the library or a device is touched
+        g = cls(**kwargs)
+        device = adj.device.index if getattr(adj, "is_cuda", False) else g._device_index()
+        g._install_device_engine(WalkEngine.from_dense_tensor(adj, device=device), device, node_ids)
+        return g
+
+    @classmethod
+    def from_edge_index(cls, edge_index, edge_weight=None, num_nodes=None, directed=False, node_ids=None, **kwargs):
+        """Dense graph from an edge list held as arrays, built ON THE DEVICE (``pw_coo_to_csr_device``, then
+        ``pw_dense_create_from_csr``).  Arguments, checks and the warning for dropped edges are those of the sparse classes'
+        ``from_edge_index``; ``last_build_stats`` has the same keys.
+
+        Semantics: the reference's ``AdjlstGraph.add_edge`` + ``to_dense()`` (graph.py:238-268, 343-362) with vertex ``i``
+        = id ``i``: non-positive weights dropped, the reverse edge inserted unless ``directed``, the last insertion of an
+        ordered pair wins.  Weights are taken as float32, as the sparse route takes them: the matrix this object stands for
+        holds those float32 values widened to float64 (an edge-list FILE read by ``read_edg`` keeps its float64 literals).
+        ``data`` / ``nonzero`` are filled on first read, as after ``from_tensor``."""
+        from .engine import check_edge_index
+
+        check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
+        g = cls(**kwargs)
+        device = edge_index.device.index if getattr(edge_index, "is_cuda", False) else g._device_index()
+        eng = WalkEngine.dense_from_edge_index(edge_index, edge_weight, num_nodes=num_nodes, directed=directed, device=device)
+        g._install_device_engine(eng, device, node_ids)
+        if eng.build_stats["dropped"]:
+            import warnings
+
+            warnings.warn(f"{eng.build_stats['dropped']} non-positive edge(s) ignored", RuntimeWarning, stacklevel=2)
+        return g
 
     def get_has_nbrs(self):
         nonzero = self.nonzero
@@ -558,7 +659,11 @@ class _DenseBase(Base, DenseGraph):
 
     def get_noise_thresholds(self):
         """Dense variant (rw/dense_rw.py:11-19): float64 rows, non-zero entries only; native restatement
-        of NumPy's reductions (``pw_noise_thresholds_dense``) with the NumPy loop as fallback."""
+        of NumPy's reductions (``pw_noise_thresholds_dense``) with the NumPy loop as fallback.  For a graph built on the
+        device whose host matrix has not been read yet the same values come from the handle's compressed rows
+        (``pw_dense_noise_thresholds``)."""
+        if self._device_built is not None and self._data is None and self._engine is not None:
+            return self._engine.compute_thresholds(self.gamma)
         n = self.num_nodes
         thr = np.zeros(n, dtype=np.float32)
         try:
