@@ -366,6 +366,42 @@ int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, 
                          uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
                          float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats);
 
+/* ---- the embedding file written from device memory (csrc/emb_text.hip.h) --------------------------------------------------
+ * The text format of gensim's KeyedVectors.save_word2vec_format, the output of `pecanpy --output G.emb` (cli.py:323-325), made
+ * on the device from the vectors where pw_sgns_train_device leaves them: only the text crosses to the host.
+ *   file       "<n_rows> <dim>\n", then per row its name, " " + the component for every component, "\n".  A component is
+ *              written as printf("%.6f", (double)x) writes it -- Python's "%.6f" % float(x) -- byte for byte: rounded to six
+ *              decimals exactly, ties to even on the binary value (integer arithmetic on mantissa and exponent); -0.0 and
+ *              negative values that round to zero give "-0.000000"; "nan" for a NaN of either sign; "inf" / "-inf"; at most
+ *              47 characters (-FLT_MAX).  The bytes are a function of the input alone.
+ *   d_vectors  device float32[n_rows, dim] on `device`, row-major and contiguous; only read.  Any n_rows >= 1, dim >= 1.
+ *   id_chars, id_offsets   host: the names as one byte blob (UTF-8 as given, not inspected) and uint64[n_rows + 1] offsets,
+ *              row i's name = id_chars[id_offsets[i] : id_offsets[i + 1]] (pw_edgelist_export's layout); uploaded by the call.
+ *   path       created or truncated; the library writes it itself (fwrite of whole chunks).
+ *   chunks     the rows are taken in consecutive blocks, each the longest run of rows whose text fits a byte budget: 32 MiB, or
+ *              PECANPY_AMD_EMB_CHUNK_BYTES; a budget below what one row can take (its name, dim times 48 bytes, the newline,
+ *              with the longest name) is raised to that.  One device buffer of the budget (of the whole text when that is
+ *              less) and two pinned host buffers: chunk k + 1 is formatted and copied while chunk k is written.
+ *   stats      optional.
+ * PW_ERR_INVALID: n_rows == 0, dim == 0, offsets that do not ascend, a path that cannot be opened or written (strerror in
+ * the message).  A failed call may leave a partial file.  Work runs on the device's default stream; the call returns when
+ * the file is closed.  pw_vectors_write_text is the same for a matrix in host memory: upload, then the same path. */
+typedef struct pw_emb_write_stats {
+    double format_ms;   /* HIP-event time of the kernels: count pass, scan, the fill pass of every chunk */
+    double copy_ms;     /* HIP-event time of the device-to-host copies of the chunks */
+    double write_ms;    /* host clock of the fwrite calls and the fclose */
+    uint64_t bytes;     /* size of the file */
+    uint64_t chunks;
+} pw_emb_write_stats;
+int pw_vectors_write_text_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
+                                 const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats);
+int pw_vectors_write_text(int device, const float *vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
+                          const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats);
+/* Test hook: x[i] as the writer formats it, at chars[48 i ..) (the rest of the slot zero), lens[i] = the number of characters
+ * (0xffffffff if the writer's count pass would disagree with its fill pass).  on_device = 0: the host build of the routine
+ * (csrc/emb_text.hip.h: format_f6), usable without a GPU; on_device != 0: one thread per value of a kernel on `device`. */
+int pw_selftest_format_f6(int on_device, int device, const float *x, uint64_t n, char *chars, uint32_t *lens);
+
 /* ---- random stream service (host side; usable without a GPU) ---------------------------- */
 /* doubles #offset.. of RandomState(seed).random_sample, produced with MT19937 jump-ahead. */
 int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, double *out);

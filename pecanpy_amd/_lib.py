@@ -59,6 +59,20 @@ class PwSgnsStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwEmbWriteStats(C.Structure):
+    """``pw_emb_write_stats`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("format_ms", C.c_double),
+        ("copy_ms", C.c_double),
+        ("write_ms", C.c_double),
+        ("bytes", C.c_uint64),
+        ("chunks", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 MODE_IDS = {
     "SparseOTF": 0,
     "DenseOTF": 1,
@@ -121,6 +135,11 @@ SYMBOLS = {
                                 C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
     "pw_sgns_train_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pw_vectors_write_text_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,
+                                               C.POINTER(PwEmbWriteStats)]),
+    "pw_vectors_write_text": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,
+                                        C.POINTER(PwEmbWriteStats)]),
+    "pw_selftest_format_f6": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_stream_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_noise_thresholds_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),

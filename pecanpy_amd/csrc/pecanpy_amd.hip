@@ -12,6 +12,7 @@
 #include <new>
 #include <random>
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <functional>
@@ -38,6 +39,7 @@
 #include "sgns.hip.h"
 #include "coo_csr.hip.h"
 #include "dense_build.hip.h"
+#include "emb_text.hip.h"
 
 #define PW_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -4131,6 +4133,262 @@ PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks,
     }
     cleanup();
     return rc;
+}
+
+// ---- the word2vec text file written from device memory (csrc/emb_text.hip.h) -------------------------------------------------
+namespace {
+
+constexpr uint64_t EMB_CHUNK_DEFAULT = 32ull << 20;   // bytes of text per chunk: PECANPY_AMD_EMB_CHUNK_BYTES overrides
+
+uint64_t emb_scan_tmp_elems(uint64_t n) {   // tile sums of every level of emb_exclusive_scan
+    uint64_t total = 0;
+    while (n > (uint64_t)pw::EMB_SCAN_TILE) {
+        n = (n + pw::EMB_SCAN_TILE - 1) / pw::EMB_SCAN_TILE;
+        total += n;
+    }
+    return total;
+}
+
+// exclusive scan of d_x[0, n) in place on the null stream; d_tmp: emb_scan_tmp_elems(n) words
+void emb_exclusive_scan(uint64_t *d_x, uint64_t n, uint64_t *d_tmp) {
+    const uint64_t tiles = (n + pw::EMB_SCAN_TILE - 1) / pw::EMB_SCAN_TILE;
+    if (tiles <= 1) {
+        hipLaunchKernelGGL(pw::emb_scan_apply_kernel, dim3(1), dim3(256), 0, nullptr, d_x, n, (const uint64_t *)nullptr);
+        return;
+    }
+    hipLaunchKernelGGL(pw::emb_scan_reduce_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, (const uint64_t *)d_x, n, d_tmp);
+    emb_exclusive_scan(d_tmp, tiles, d_tmp + tiles);
+    hipLaunchKernelGGL(pw::emb_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, d_x, n, (const uint64_t *)d_tmp);
+}
+
+}  // namespace
+
+PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
+                                           const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
+    if (!d_vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
+    uint64_t longest_name = 0;
+    for (uint64_t i = 0; i < n_rows; i++) {
+        if (id_offsets[i + 1] < id_offsets[i])
+            return fail(PW_ERR_INVALID, "pw_vectors_write_text: id_offsets do not ascend at row " + std::to_string(i));
+        longest_name = std::max(longest_name, id_offsets[i + 1] - id_offsets[i]);
+    }
+    const uint64_t id_bytes = id_offsets[n_rows];
+    if (id_bytes && !id_chars) return fail(PW_ERR_INVALID, "null pointer");
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    // the byte budget of a chunk: at least what one row can take (name, dim times " " + 47 characters, newline)
+    const uint64_t row_max = longest_name + (uint64_t)dim * pw::F6_SLOT + 1;
+    uint64_t budget = EMB_CHUNK_DEFAULT;
+    if (const char *v = getenv("PECANPY_AMD_EMB_CHUNK_BYTES"))
+        if (*v) budget = (uint64_t)strtoull(v, nullptr, 10);
+    budget = std::max(budget, row_max);
+
+    // everything the call owns: released on every way out
+    struct Mem {
+        FILE *file = nullptr;
+        std::vector<void *> dev;
+        void *pinned[2] = {nullptr, nullptr};
+        bool queued = false;   // work may be in flight on the default stream
+        hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Mem() {
+            if (queued) (void)hipStreamSynchronize(nullptr);
+            if (file) (void)fclose(file);
+            for (void *q : dev) if (q) (void)hipFree(q);
+            for (void *q : pinned) if (q) (void)hipHostFree(q);
+            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        }
+    } mem;
+    mem.file = fopen(path, "wb");
+    if (!mem.file) return fail(PW_ERR_INVALID, std::string("pw_vectors_write_text: cannot open ") + path + ": " + strerror(errno));
+    auto write_failed = [&]() {
+        return fail(PW_ERR_INVALID, std::string("pw_vectors_write_text: cannot write ") + path + ": " + strerror(errno));
+    };
+    if (fprintf(mem.file, "%llu %u\n", (unsigned long long)n_rows, dim) < 0) return write_failed();
+
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    mem.queued = true;
+    for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
+    auto alloc = [&](void **p, uint64_t bytes) -> int {
+        *p = nullptr;
+        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            return fail(PW_ERR_NOMEM, "pw_vectors_write_text: " + std::to_string(bytes) + " bytes do not fit in device memory: " + hipGetErrorString(e));
+        }
+        mem.dev.push_back(*p);
+        return 0;
+    };
+    char *d_ids = nullptr, *d_buf = nullptr;
+    uint64_t *d_id_off = nullptr, *d_row_off = nullptr, *d_tmp = nullptr;
+    uint32_t *d_flags = nullptr;
+    int rc;
+    if ((rc = alloc((void **)&d_ids, id_bytes)) || (rc = alloc((void **)&d_id_off, sizeof(uint64_t) * (n_rows + 1))) ||
+        (rc = alloc((void **)&d_row_off, sizeof(uint64_t) * (n_rows + 1))) ||
+        (rc = alloc((void **)&d_tmp, sizeof(uint64_t) * emb_scan_tmp_elems(n_rows + 1))) || (rc = alloc((void **)&d_flags, sizeof(uint32_t))))
+        return rc;
+    if (id_bytes) HIP_TRY(hipMemcpyAsync(d_ids, id_chars, id_bytes, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(d_id_off, id_offsets, sizeof(uint64_t) * (n_rows + 1), hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), nullptr));
+    HIP_TRY(hipMemsetAsync(d_row_off + n_rows, 0, sizeof(uint64_t), nullptr));   // (the scan's last input: its output is the total)
+
+    // count pass and scan: row_off[i] = byte offset of row i in the text behind the header, row_off[n_rows] = the total
+    const unsigned row_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rows + 3) / 4, (uint64_t)prop.multiProcessorCount * 16));
+    HIP_TRY(hipEventRecord(mem.ev[0], nullptr));
+    hipLaunchKernelGGL(pw::emb_count_kernel, dim3(row_grid), dim3(256), 0, nullptr, d_vectors, n_rows, dim, (const uint64_t *)d_id_off, d_row_off);
+    emb_exclusive_scan(d_row_off, n_rows + 1, d_tmp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(mem.ev[1], nullptr));
+    std::vector<uint64_t> row_off(n_rows + 1);
+    HIP_TRY(hipMemcpyAsync(row_off.data(), d_row_off, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, mem.ev[0], mem.ev[1]));
+    double format_ms = ms, copy_ms = 0, write_ms = 0;
+    const uint64_t total = row_off[n_rows];
+    for (uint64_t i = 0; i < n_rows; i++)   // (what the fill pass is bounded by: checked before anything is written through it)
+        if (row_off[i + 1] < row_off[i] || row_off[i + 1] - row_off[i] > row_max)
+            return fail(PW_ERR_HIP, "pw_vectors_write_text: row byte counts out of range (internal error)");
+
+    // chunks: consecutive rows while their text fits the budget (one row always does)
+    const uint64_t buf_bytes = std::min(budget, total);
+    if ((rc = alloc((void **)&d_buf, buf_bytes))) return rc;
+    for (auto &p : mem.pinned) {
+        hipError_t e = hipHostMalloc(&p, buf_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(PW_ERR_NOMEM, std::string("pw_vectors_write_text: pinned host buffer: ") + hipGetErrorString(e));
+        }
+    }
+    struct Chunk { uint64_t lo, hi; };
+    auto next_chunk = [&](uint64_t lo) {
+        // the last row whose end lies within the budget from row lo's start
+        const uint64_t limit = row_off[lo] + buf_bytes;
+        const uint64_t hi = (uint64_t)(std::upper_bound(row_off.begin() + lo + 1, row_off.end(), limit) - row_off.begin()) - 1;
+        return Chunk{lo, hi};
+    };
+    // slot s = chunk index & 1: events 2 + 3 s .. 4 + 3 s = fill begin, fill end, copy end
+    auto issue = [&](const Chunk &c, int s) -> int {
+        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((c.hi - c.lo + 3) / 4, (uint64_t)prop.multiProcessorCount * 16));
+        HIP_TRY(hipEventRecord(mem.ev[2 + 3 * s], nullptr));
+        hipLaunchKernelGGL(pw::emb_fill_kernel, dim3(grid), dim3(256), 0, nullptr, d_vectors, c.lo, c.hi, dim, (const char *)d_ids,
+                           (const uint64_t *)d_id_off, (const uint64_t *)d_row_off, d_buf, d_flags);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(mem.ev[3 + 3 * s], nullptr));
+        HIP_TRY(hipMemcpyAsync(mem.pinned[s], d_buf, row_off[c.hi] - row_off[c.lo], hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipEventRecord(mem.ev[4 + 3 * s], nullptr));
+        return 0;
+    };
+    using clk = std::chrono::steady_clock;
+    uint64_t n_chunks = 0;
+    Chunk cur = next_chunk(0);
+    if ((rc = issue(cur, 0))) return rc;
+    while (true) {
+        const int s = (int)(n_chunks & 1);
+        Chunk nxt{cur.hi, cur.hi};
+        if (cur.hi < n_rows) {   // the copy of the next chunk runs beside this chunk's fwrite
+            nxt = next_chunk(cur.hi);
+            if ((rc = issue(nxt, s ^ 1))) return rc;
+        }
+        HIP_TRY(hipEventSynchronize(mem.ev[4 + 3 * s]));
+        float ms_fill = 0, ms_copy = 0;
+        HIP_TRY(hipEventElapsedTime(&ms_fill, mem.ev[2 + 3 * s], mem.ev[3 + 3 * s]));
+        HIP_TRY(hipEventElapsedTime(&ms_copy, mem.ev[3 + 3 * s], mem.ev[4 + 3 * s]));
+        format_ms += ms_fill;
+        copy_ms += ms_copy;
+        const uint64_t bytes = row_off[cur.hi] - row_off[cur.lo];
+        const auto t0 = clk::now();
+        if (fwrite(mem.pinned[s], 1, bytes, mem.file) != bytes) return write_failed();
+        write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        n_chunks++;
+        if (cur.hi >= n_rows) break;
+        cur = nxt;
+    }
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpyAsync(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (flags) return fail(PW_ERR_HIP, "pw_vectors_write_text: the fill pass disagreed with the count pass (internal error)");
+    const auto t0 = clk::now();
+    FILE *f = mem.file;
+    mem.file = nullptr;
+    if (fclose(f) != 0) return write_failed();
+    write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    if (stats) {
+        stats->format_ms = format_ms; stats->copy_ms = copy_ms; stats->write_ms = write_ms;
+        stats->bytes = total + (uint64_t)snprintf(nullptr, 0, "%llu %u\n", (unsigned long long)n_rows, dim);
+        stats->chunks = n_chunks;
+    }
+    return PW_OK;
+}
+
+// host-matrix entry: upload, then the device entry
+PW_EXPORT int pw_vectors_write_text(int device, const float *vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
+                                    const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
+    if (!vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t vbytes = sizeof(float) * (size_t)n_rows * dim;
+    float *d_vectors = nullptr;
+    hipError_t e = hipMalloc((void **)&d_vectors, vbytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PW_ERR_NOMEM, std::string("pw_vectors_write_text: the matrix does not fit in device memory: ") + hipGetErrorString(e));
+    }
+    e = hipMemcpy(d_vectors, vectors, vbytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? pw_vectors_write_text_device(device, d_vectors, n_rows, dim, id_chars, id_offsets, path, stats)
+                             : fail(PW_ERR_HIP, std::string("pw_vectors_write_text: ") + hipGetErrorString(e));
+    (void)hipFree(d_vectors);
+    return rc;
+}
+
+// x[i] formatted into chars[48 i ..) (the rest of the slot zero), lens[i] = the count.  on_device = 0: the host build of
+// format_f6; on_device = 1: one GPU thread per value.
+PW_EXPORT int pw_selftest_format_f6(int on_device, int device, const float *x, uint64_t n, char *chars, uint32_t *lens) {
+    if (n && (!x || !chars || !lens)) return fail(PW_ERR_INVALID, "null pointer");
+    if (n == 0) return PW_OK;
+    if (!on_device) {
+        memset(chars, 0, (size_t)n * pw::F6_SLOT);
+        for (uint64_t i = 0; i < n; i++) {
+            const pw::F6 f = pw::f6_decompose(x[i]);
+            const uint32_t len = pw::f6_emit(f, chars + i * pw::F6_SLOT);
+            lens[i] = len == pw::f6_len(f) ? len : 0xffffffffu;
+        }
+        return PW_OK;
+    }
+    int ndev = pw_device_count();
+    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    float *d_x = nullptr;
+    char *d_chars = nullptr;
+    uint32_t *d_lens = nullptr;
+    auto cleanup = [&]() {
+        for (void *q : {(void *)d_x, (void *)d_chars, (void *)d_lens})
+            if (q) (void)hipFree(q);
+    };
+    const size_t cbytes = (size_t)n * pw::F6_SLOT;
+    hipError_t e = hipMalloc((void **)&d_x, sizeof(float) * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_chars, cbytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_lens, sizeof(uint32_t) * (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(d_x, x, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_chars, 0, cbytes);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pw::f6_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)d_x, n, d_chars, d_lens);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(chars, d_chars, cbytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(lens, d_lens, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_format_f6: ") + hipGetErrorString(e));
+    return PW_OK;
 }
 
 // ---- host self test of the exact-arithmetic decision ---------------------------------------------------

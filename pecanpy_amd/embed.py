@@ -1,6 +1,10 @@
 """Skip-gram embeddings from a walk matrix on the GPU (reference: gensim ``Word2Vec(walks, sg=1, ...)`` in
 ``Base.embed`` / ``cli.learn_embeddings``, src/pecanpy/pecanpy.py:276-290, cli.py:307-325).
 
+``save_word2vec_format_device`` writes the text file of the vectors from device memory (``pw_vectors_write_text_device``,
+csrc/emb_text.hip.h: exact ``%.6f`` on the GPU, only the text crosses to the host), byte for byte what
+``save_word2vec_format`` writes.
+
 ``train_sgns_device`` runs word2vec's skip-gram-with-negative-sampling update as a HIP kernel (``pw_sgns_train_device``,
 csrc/sgns.hip.h: a wavefront owns a walk) on the ``[n_jobs, L+2]`` matrix where ``WalkEngine.simulate_device`` leaves it, in
 device memory -- no host copy of the matrix and no ``List[List[str]]`` corpus in between; ``train_sgns`` is the same
@@ -15,7 +19,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["train_sgns", "train_sgns_device", "save_word2vec_format"]
+__all__ = ["train_sgns", "train_sgns_device", "save_word2vec_format", "save_word2vec_format_device"]
 
 
 def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
@@ -93,3 +97,40 @@ def save_word2vec_format(path, node_ids, vectors):
                 flat.append(str(name))
                 flat.extend(row)
             f.write(fmt % tuple(flat))
+
+
+def save_word2vec_format_device(path, node_ids, d_vectors):
+    """``save_word2vec_format`` for vectors in device memory: ``d_vectors`` is a contiguous float32 CUDA tensor ``[n, dim]``
+    (what ``train_sgns_device`` returns), ``node_ids`` its ``n`` names (``str(name)`` encoded as UTF-8).  The text is made on
+    the GPU (``pw_vectors_write_text_device``) and written by the library in chunks; the file equals
+    ``save_word2vec_format(path, node_ids, d_vectors.cpu().numpy())`` byte for byte.  What the call did
+    (``pw_emb_write_stats``: ``format_ms``, ``copy_ms``, ``write_ms``, ``bytes``, ``chunks``) is left in
+    ``save_word2vec_format_device.last_stats``."""
+    import os
+
+    import torch
+
+    if not isinstance(d_vectors, torch.Tensor) or not d_vectors.is_cuda:
+        raise ValueError("d_vectors must be a CUDA tensor (a contiguous float32[n, dim] in device memory)")
+    if d_vectors.dtype != torch.float32:
+        raise ValueError(f"d_vectors must be float32, not {d_vectors.dtype}")
+    if not d_vectors.is_contiguous():
+        raise ValueError("d_vectors must be contiguous (row-major, dense)")
+    if d_vectors.dim() != 2 or d_vectors.shape[0] < 1 or d_vectors.shape[1] < 1:
+        raise ValueError("d_vectors must be float32[n, dim] with n >= 1 and dim >= 1")
+    n, dim = int(d_vectors.shape[0]), int(d_vectors.shape[1])
+    if len(node_ids) != n:
+        raise ValueError(f"{len(node_ids)} node names for {n} rows")
+    names = [str(name).encode("utf-8") for name in node_ids]
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=n), out=offsets[1:])
+    blob = b"".join(names)
+    lib = _lib.load()
+    torch.cuda.current_stream(d_vectors.device).synchronize()  # the vectors were produced on torch's stream
+    st = _lib.PwEmbWriteStats()
+    _lib.check(lib.pw_vectors_write_text_device(d_vectors.device.index, C.c_void_p(d_vectors.data_ptr()), n, dim, blob,
+                                                C.c_void_p(offsets.ctypes.data), os.fsencode(path), C.byref(st)))
+    save_word2vec_format_device.last_stats = st.as_dict()
+
+
+save_word2vec_format_device.last_stats = None

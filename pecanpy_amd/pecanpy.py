@@ -341,6 +341,43 @@ class Base(BaseGraph):
         self._note_stats(eng.last_stats)
         return d_walks
 
+    def _train_on_device(self, dim, num_walks, walk_length, window_size, epochs, workers):
+        """Walks and trainer with the walk matrix in device memory: ``(d_vectors, walk_ms, sgns_call_ms)``, or ``None`` where
+        ``_device_walks`` returns ``None``."""
+        import time
+
+        from .embed import train_sgns_device
+
+        t0 = time.perf_counter()
+        d_walks = self._device_walks(num_walks, walk_length)
+        if d_walks is None:
+            return None
+        import torch
+
+        torch.cuda.synchronize(d_walks.device)
+        t1 = time.perf_counter()
+        d_vec = train_sgns_device(d_walks, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
+                                  workers=workers)
+        t2 = time.perf_counter()
+        return d_vec, (t1 - t0) * 1e3, (t2 - t1) * 1e3
+
+    def _embed_through_host(self, t0, dim, num_walks, walk_length, window_size, epochs, workers):
+        """The route of ``embed_array`` and ``embed_to_file`` once ``_train_on_device`` has returned ``None``:
+        ``simulate_walks_array`` + ``train_sgns``, the walk matrix crossing to the host and back.  ``t0`` is when the caller
+        began."""
+        import time
+
+        from .embed import train_sgns
+
+        mat = self.simulate_walks_array(num_walks, walk_length)
+        t1 = time.perf_counter()
+        vec = train_sgns(mat, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
+                         device=self._device_index(), workers=workers)
+        t2 = time.perf_counter()
+        self.last_embed_stats = {"walk_matrix_host_bytes": 2 * int(mat.nbytes), "walk_ms": (t1 - t0) * 1e3,
+                                 "sgns_call_ms": (t2 - t1) * 1e3}
+        return vec
+
     def embed_array(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0):
         """Walks and skip-gram on the GPU, the walk matrix staying in device memory: start array -> ``simulate_device`` ->
         ``pecanpy_amd.embed.train_sgns_device`` -> ``float32[num_nodes, dim]`` in node order, copied to the host once.
@@ -353,31 +390,49 @@ class Base(BaseGraph):
         the bytes of the matrix that crossed to the host and back."""
         import time
 
-        from .embed import train_sgns, train_sgns_device
+        from .embed import train_sgns_device
 
         t0 = time.perf_counter()
-        d_walks = self._device_walks(num_walks, walk_length)
-        if d_walks is None:
-            mat = self.simulate_walks_array(num_walks, walk_length)
-            t1 = time.perf_counter()
-            vec = train_sgns(mat, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
-                             device=self._device_index(), workers=workers)
-            t2 = time.perf_counter()
-            self.last_embed_stats = {"walk_matrix_host_bytes": 2 * int(mat.nbytes), "walk_ms": (t1 - t0) * 1e3,
-                                     "sgns_call_ms": (t2 - t1) * 1e3}
-            return vec
-        import torch
-
-        torch.cuda.synchronize(d_walks.device)
-        t1 = time.perf_counter()
-        d_vec = train_sgns_device(d_walks, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
-                                  workers=workers)
+        trained = self._train_on_device(dim, num_walks, walk_length, window_size, epochs, workers)
+        if trained is None:
+            return self._embed_through_host(t0, dim, num_walks, walk_length, window_size, epochs, workers)
+        d_vec, walk_ms, sgns_call_ms = trained
         t2 = time.perf_counter()
         vec = d_vec.cpu().numpy()
         t3 = time.perf_counter()
-        self.last_embed_stats = {"walk_matrix_host_bytes": 0, "walk_ms": (t1 - t0) * 1e3, "sgns_call_ms": (t2 - t1) * 1e3,
+        self.last_embed_stats = {"walk_matrix_host_bytes": 0, "walk_ms": walk_ms, "sgns_call_ms": sgns_call_ms,
                                  "download_ms": (t3 - t2) * 1e3, **train_sgns_device.last_stats}
         return vec
+
+    def embed_to_file(self, path, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0):
+        """``embed_array`` + ``save_word2vec_format`` without the vectors visiting the host: walks, trainer and the device
+        writer (``pecanpy_amd.embed.save_word2vec_format_device``); only the text of the file leaves the device.  The file
+        holds the bytes ``save_word2vec_format(path, self.nodes, self.embed_array(...))`` writes for the same vectors.
+
+        ``self.last_embed_stats``: ``embed_array``'s keys without ``download_ms``, plus ``vectors_host_bytes`` (0 on this
+        route), ``write_call_ms`` and the writer's ``format_ms``, ``copy_ms``, ``write_ms``, ``bytes``, ``chunks``.  Where
+        the walks cannot stay on one device (see ``_device_walks``) ``embed_array`` + ``save_word2vec_format`` run instead
+        and ``vectors_host_bytes`` holds the bytes of the matrix that came to the host."""
+        import time
+
+        from .embed import save_word2vec_format, save_word2vec_format_device, train_sgns_device
+
+        t0 = time.perf_counter()
+        trained = self._train_on_device(dim, num_walks, walk_length, window_size, epochs, workers)
+        if trained is None:       # the route is decided once: what embed_array does from here on, not embed_array again
+            vec = self._embed_through_host(t0, dim, num_walks, walk_length, window_size, epochs, workers)
+            t0 = time.perf_counter()
+            save_word2vec_format(path, self.nodes, vec)
+            self.last_embed_stats = {**self.last_embed_stats, "vectors_host_bytes": int(vec.nbytes),
+                                     "write_call_ms": (time.perf_counter() - t0) * 1e3}
+            return
+        d_vec, walk_ms, sgns_call_ms = trained
+        trainer = train_sgns_device.last_stats
+        t0 = time.perf_counter()
+        save_word2vec_format_device(path, self.nodes, d_vec)
+        self.last_embed_stats = {"walk_matrix_host_bytes": 0, "vectors_host_bytes": 0, "walk_ms": walk_ms,
+                                 "sgns_call_ms": sgns_call_ms, "write_call_ms": (time.perf_counter() - t0) * 1e3, **trainer,
+                                 **save_word2vec_format_device.last_stats}
 
     def embed(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, verbose=False):
         """``simulate_walks`` + skip-gram (pecanpy.py:240-290): returns ``float32[num_nodes, dim]`` in node order.
