@@ -402,6 +402,43 @@ int pw_vectors_write_text(int device, const float *vectors, uint64_t n_rows, uin
  * (csrc/emb_text.hip.h: format_f6), usable without a GPU; on_device != 0: one thread per value of a kernel on `device`. */
 int pw_selftest_format_f6(int on_device, int device, const float *x, uint64_t n, char *chars, uint32_t *lens);
 
+/* ---- the walk corpus file written from device memory (csrc/walk_text.hip.h) ------------------------------------------------
+ * One walk per line, the names of its nodes separated by single spaces: what gensim's LineSentence / Word2Vec(corpus_file=),
+ * fastText and word2vec.c read, and what `pecanpy --task walks` writes -- made on the device from the walk matrix where
+ * pw_simulate_device leaves it: only the text crosses to the host.
+ *   file       no header.  Row r with len = r[walk_length + 1] gives the names of r[0] .. r[len - 1] joined by " ", then "\n"
+ *              (len == 0: just "\n").  Cells at positions >= len are never read.  The bytes are a function of the input alone.
+ *   d_walks    device uint32[n_walks, walk_length + 2] on `device`, row-major and contiguous; only read.  walk_length < 2^31.
+ *   id_chars, id_offsets, n_names   host: the names as one byte blob (UTF-8 as given, not inspected) and uint64[n_names + 1]
+ *              offsets, node i's name = id_chars[id_offsets[i] : id_offsets[i + 1]] (at most 2^25 - 1 bytes, may be empty);
+ *              uploaded by the call.  The names are looked up by node index.
+ *   path       created or truncated; the library writes it itself (fwrite of whole chunks).
+ *   chunks     as pw_vectors_write_text_device: consecutive rows while their text fits a byte budget of 32 MiB, or
+ *              PECANPY_AMD_WALKS_CHUNK_BYTES; a budget below the longest possible row, (walk_length + 1) * (longest name + 1),
+ *              is raised to that.  One device buffer, two pinned host buffers.
+ *   stats      optional.
+ * n_walks == 0 writes an empty file; walk_length == 0 is a corpus of start nodes; n_names may exceed what a node index can
+ * address (the names beyond are never looked up).  PW_ERR_INVALID: offsets that do not ascend, a name that is too long, a path that
+ * cannot be opened or written (strerror in the message), and what the matrix itself holds: a row length above
+ * walk_length + 1 ("row length ...") or, among the first len cells of a row, a node index >= n_names ("node index ...
+ * outside the ... names").  The matrix is checked on the device before any text is made -- such a value is compared, never
+ * used as an index -- and the file is left empty.  Any other failed call may leave a partial file.  Work runs on the
+ * device's default stream; the call returns when the file is closed.  pw_walks_write_text is the same for a matrix in host
+ * memory: upload, then the same path. */
+typedef struct pw_walks_write_stats {
+    double format_ms;   /* HIP-event time of the kernels: count pass, scan, the fill pass of every chunk */
+    double copy_ms;     /* HIP-event time of the device-to-host copies of the chunks */
+    double write_ms;    /* host clock of the fwrite calls and the fclose */
+    uint64_t bytes;     /* size of the file */
+    uint64_t chunks;
+    uint64_t rows;      /* lines written = n_walks */
+    uint64_t tokens;    /* names written = the sum of the row lengths */
+} pw_walks_write_stats;
+int pw_walks_write_text_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, const char *id_chars,
+                               const uint64_t *id_offsets, uint64_t n_names, const char *path, pw_walks_write_stats *stats);
+int pw_walks_write_text(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, const char *id_chars,
+                        const uint64_t *id_offsets, uint64_t n_names, const char *path, pw_walks_write_stats *stats);
+
 /* ---- random stream service (host side; usable without a GPU) ---------------------------- */
 /* doubles #offset.. of RandomState(seed).random_sample, produced with MT19937 jump-ahead. */
 int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, double *out);

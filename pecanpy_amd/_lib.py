@@ -73,6 +73,22 @@ class PwEmbWriteStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwWalksWriteStats(C.Structure):
+    """``pw_walks_write_stats`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("format_ms", C.c_double),
+        ("copy_ms", C.c_double),
+        ("write_ms", C.c_double),
+        ("bytes", C.c_uint64),
+        ("chunks", C.c_uint64),
+        ("rows", C.c_uint64),
+        ("tokens", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 MODE_IDS = {
     "SparseOTF": 0,
     "DenseOTF": 1,
@@ -139,6 +155,10 @@ SYMBOLS = {
                                                C.POINTER(PwEmbWriteStats)]),
     "pw_vectors_write_text": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,
                                         C.POINTER(PwEmbWriteStats)]),
+    "pw_walks_write_text_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p,
+                                             C.POINTER(PwWalksWriteStats)]),
+    "pw_walks_write_text": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p,
+                                      C.POINTER(PwWalksWriteStats)]),
     "pw_selftest_format_f6": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_stream_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),

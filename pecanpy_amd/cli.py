@@ -4,7 +4,8 @@ Flag names, defaults, the mode sanity rules and the stage order follow the refer
 (src/pecanpy/cli.py: flags :27-176, ``check_mode`` :179-254, ``read_graph`` :257-304, pipeline
 :307-351) so that existing invocations keep working.  Walks come from the GPU; the skip-gram stage
 uses gensim when it is importable; without it walks and skip-gram both run on the GPU (``Base.embed_array``: the
-walk matrix stays in device memory).  ``PECANPY_AMD_DUMP_WALKS=1`` writes the walks (one per line) to ``--output``.
+walk matrix stays in device memory).  ``--task walks`` writes the walks (one per line) to ``--output`` instead of training,
+the text made in device memory; ``PECANPY_AMD_DUMP_WALKS=1`` does the same through the ID lists of ``simulate_walks``.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
 """
@@ -24,8 +25,9 @@ MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "Sp
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
     ("--output", dict(required=True, help="embedding file (.npz -> IDs/data arrays, else word2vec text)")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense"),
-                    help="run node2vec, or only convert the edge list to CSR / dense .npz")),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks"),
+                    help="run node2vec; only convert the edge list to CSR / dense .npz; or (walks) generate the walks and "
+                         "write them, one per line, to --output; no training")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
     ("--walk-length", dict(type=int, default=80, help="steps per walk")),
@@ -109,7 +111,7 @@ def read_graph(args):
         raise NotImplementedError("Node2vec+ not implemented for directed graph yet.")
     if args.extend and not args.weighted:
         print("NOTE: node2vec+ is equivalent to node2vec for unweighted graphs.")
-    if args.task != "pecanpy":
+    if args.task in ("tocsr", "todense"):
         _convert_only(args)
 
     engine_cls = getattr(pecanpy, args.mode)
@@ -200,6 +202,12 @@ def _save_vectors(args, g, vecs):
         save_word2vec_format(args.output, g.nodes, vecs)
 
 
+@Timer("generate walks + write them")
+def walks_to_file(args, g):
+    """``--task walks``: the walk corpus as text (``Base.walks_to_file``: formatted in device memory, no ID lists)."""
+    g.walks_to_file(args.output, args.num_walks, args.walk_length)
+
+
 @Timer("generate walks + train embeddings")
 def embed_on_gpu(args, g):
     """Walks and skip-gram in device memory (``Base.embed_array``), the vectors written as ``learn_embeddings`` writes
@@ -215,7 +223,9 @@ def main(argv=None):
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)
     preprocess(g)
-    if _gpu_route():
+    if args.task == "walks":
+        walks_to_file(args, g)
+    elif _gpu_route():
         embed_on_gpu(args, g)
     else:
         learn_embeddings(args, simulate_walks(args, g), g)

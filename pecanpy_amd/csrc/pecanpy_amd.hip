@@ -40,6 +40,7 @@
 #include "coo_csr.hip.h"
 #include "dense_build.hip.h"
 #include "emb_text.hip.h"
+#include "walk_text.hip.h"
 
 #define PW_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -4161,166 +4162,229 @@ void emb_exclusive_scan(uint64_t *d_x, uint64_t n, uint64_t *d_tmp) {
     hipLaunchKernelGGL(pw::emb_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, d_x, n, (const uint64_t *)d_tmp);
 }
 
-}  // namespace
+// What a call that writes a text file from device memory owns -- released on every way out -- and the part the embedding
+// writer and the walk writer share: the scan of the row byte counts, then consecutive rows in chunks that fit a byte budget,
+// through one device buffer and two pinned host buffers.  A writer opens the file (with its header line, if it has one),
+// allocates and uploads what its kernels read, launches its count kernel between count_begin and count_end, and hands
+// write_chunks a callable that launches its fill kernel for rows [lo, hi).
+struct TextFile {
+    const std::string who;   // the entry's name in the error texts
+    const std::string path;
+    FILE *file = nullptr;
+    std::vector<void *> dev;
+    void *pinned[2] = {nullptr, nullptr};
+    bool queued = false;   // work may be in flight on the default stream
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int n_cu = 1;
+    uint64_t *d_row_off = nullptr, *d_tmp = nullptr;   // uint64[n_rows + 1]: byte counts, then offsets; the scan's tile sums
+    uint32_t *d_flags = nullptr;                       // one word the fill kernel raises
+    std::vector<uint64_t> row_off;                     // host copy: row_off[i] = offset of row i behind the header, [n_rows] = total
+    double format_ms = 0, copy_ms = 0, write_ms = 0;
+    uint64_t header_bytes = 0, n_chunks = 0;
 
-PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
-                                           const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
-    if (!d_vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
-    if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
-    uint64_t longest_name = 0;
-    for (uint64_t i = 0; i < n_rows; i++) {
-        if (id_offsets[i + 1] < id_offsets[i])
-            return fail(PW_ERR_INVALID, "pw_vectors_write_text: id_offsets do not ascend at row " + std::to_string(i));
-        longest_name = std::max(longest_name, id_offsets[i + 1] - id_offsets[i]);
+    TextFile(const char *who_, const char *path_) : who(who_), path(path_) {}
+    TextFile(const TextFile &) = delete;
+    ~TextFile() {
+        if (queued) (void)hipStreamSynchronize(nullptr);
+        if (file) (void)fclose(file);
+        for (void *q : dev) if (q) (void)hipFree(q);
+        for (void *q : pinned) if (q) (void)hipHostFree(q);
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     }
-    const uint64_t id_bytes = id_offsets[n_rows];
-    if (id_bytes && !id_chars) return fail(PW_ERR_INVALID, "null pointer");
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
-    // the byte budget of a chunk: at least what one row can take (name, dim times " " + 47 characters, newline)
-    const uint64_t row_max = longest_name + (uint64_t)dim * pw::F6_SLOT + 1;
-    uint64_t budget = EMB_CHUNK_DEFAULT;
-    if (const char *v = getenv("PECANPY_AMD_EMB_CHUNK_BYTES"))
-        if (*v) budget = (uint64_t)strtoull(v, nullptr, 10);
-    budget = std::max(budget, row_max);
-
-    // everything the call owns: released on every way out
-    struct Mem {
-        FILE *file = nullptr;
-        std::vector<void *> dev;
-        void *pinned[2] = {nullptr, nullptr};
-        bool queued = false;   // work may be in flight on the default stream
-        hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Mem() {
-            if (queued) (void)hipStreamSynchronize(nullptr);
-            if (file) (void)fclose(file);
-            for (void *q : dev) if (q) (void)hipFree(q);
-            for (void *q : pinned) if (q) (void)hipHostFree(q);
-            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        }
-    } mem;
-    mem.file = fopen(path, "wb");
-    if (!mem.file) return fail(PW_ERR_INVALID, std::string("pw_vectors_write_text: cannot open ") + path + ": " + strerror(errno));
-    auto write_failed = [&]() {
-        return fail(PW_ERR_INVALID, std::string("pw_vectors_write_text: cannot write ") + path + ": " + strerror(errno));
-    };
-    if (fprintf(mem.file, "%llu %u\n", (unsigned long long)n_rows, dim) < 0) return write_failed();
-
-    HIP_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    mem.queued = true;
-    for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
-    auto alloc = [&](void **p, uint64_t bytes) -> int {
+    int write_failed() const { return fail(PW_ERR_INVALID, who + ": cannot write " + path + ": " + strerror(errno)); }
+    int open(const std::string &header) {
+        file = fopen(path.c_str(), "wb");
+        if (!file) return fail(PW_ERR_INVALID, who + ": cannot open " + path + ": " + strerror(errno));
+        if (fwrite(header.data(), 1, header.size(), file) != header.size()) return write_failed();
+        header_bytes = header.size();
+        return 0;
+    }
+    int begin(int device) {
+        HIP_TRY(hipSetDevice(device));
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        n_cu = prop.multiProcessorCount;
+        queued = true;
+        for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+        return 0;
+    }
+    int alloc(void **p, uint64_t bytes) {
         *p = nullptr;
         hipError_t e = hipMalloc(p, bytes ? bytes : 16);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             *p = nullptr;
-            return fail(PW_ERR_NOMEM, "pw_vectors_write_text: " + std::to_string(bytes) + " bytes do not fit in device memory: " + hipGetErrorString(e));
+            return fail(PW_ERR_NOMEM, who + ": " + std::to_string(bytes) + " bytes do not fit in device memory: " + hipGetErrorString(e));
         }
-        mem.dev.push_back(*p);
+        dev.push_back(*p);
         return 0;
-    };
-    char *d_ids = nullptr, *d_buf = nullptr;
-    uint64_t *d_id_off = nullptr, *d_row_off = nullptr, *d_tmp = nullptr;
-    uint32_t *d_flags = nullptr;
+    }
+    int alloc_rows(uint64_t n_rows) {
+        int rc;
+        if ((rc = alloc((void **)&d_row_off, sizeof(uint64_t) * (n_rows + 1))) ||
+            (rc = alloc((void **)&d_tmp, sizeof(uint64_t) * emb_scan_tmp_elems(n_rows + 1))) || (rc = alloc((void **)&d_flags, sizeof(uint32_t))))
+            return rc;
+        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), nullptr));
+        HIP_TRY(hipMemsetAsync(d_row_off + n_rows, 0, sizeof(uint64_t), nullptr));   // (the scan's last input: its output is the total)
+        return 0;
+    }
+    // blocks of four wavefronts for one wavefront per row, rows strided over the grid
+    unsigned grid(uint64_t rows) const { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((rows + 3) / 4, (uint64_t)n_cu * 16)); }
+
+    // count pass and scan: the writer's count kernel, launched between the two, leaves row i's byte count in d_row_off[i]
+    int count_begin() {
+        HIP_TRY(hipEventRecord(ev[0], nullptr));
+        return 0;
+    }
+    int count_end(uint64_t n_rows) {
+        emb_exclusive_scan(d_row_off, n_rows + 1, d_tmp);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1], nullptr));
+        row_off.resize(n_rows + 1);
+        HIP_TRY(hipMemcpyAsync(row_off.data(), d_row_off, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        format_ms = ms;
+        return 0;
+    }
+    uint64_t bytes() const { return header_bytes + row_off.back(); }
+
+    // fill(lo, hi, blocks, d_buf) launches the fill kernel for rows [lo, hi) on the default stream: their text at
+    // d_buf[row_off[row] - row_off[lo]].  budget >= row_max >= the bytes of any one row.  Closes the file.
+    template <typename Fill> int write_chunks(uint64_t budget, uint64_t row_max, Fill fill) {
+        const uint64_t n_rows = row_off.size() - 1, total = row_off[n_rows];
+        for (uint64_t i = 0; i < n_rows; i++)   // (what the fill pass is bounded by: checked before anything is written through it)
+            if (row_off[i + 1] < row_off[i] || row_off[i + 1] - row_off[i] > row_max)
+                return fail(PW_ERR_HIP, who + ": row byte counts out of range (internal error)");
+
+        // chunks: consecutive rows while their text fits the budget (one row always does)
+        const uint64_t buf_bytes = std::min(budget, total);
+        char *d_buf = nullptr;
+        int rc;
+        if ((rc = alloc((void **)&d_buf, buf_bytes))) return rc;
+        for (auto &p : pinned) {
+            hipError_t e = hipHostMalloc(&p, buf_bytes, hipHostMallocDefault);
+            if (e != hipSuccess) {
+                p = nullptr;
+                return fail(PW_ERR_NOMEM, who + ": pinned host buffer: " + hipGetErrorString(e));
+            }
+        }
+        struct Chunk { uint64_t lo, hi; };
+        auto next_chunk = [&](uint64_t lo) {
+            // the last row whose end lies within the budget from row lo's start
+            const uint64_t limit = row_off[lo] + buf_bytes;
+            const uint64_t hi = (uint64_t)(std::upper_bound(row_off.begin() + lo + 1, row_off.end(), limit) - row_off.begin()) - 1;
+            return Chunk{lo, hi};
+        };
+        // slot s = chunk index & 1: events 2 + 3 s .. 4 + 3 s = fill begin, fill end, copy end
+        auto issue = [&](const Chunk &c, int s) -> int {
+            HIP_TRY(hipEventRecord(ev[2 + 3 * s], nullptr));
+            fill(c.lo, c.hi, grid(c.hi - c.lo), d_buf);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[3 + 3 * s], nullptr));
+            HIP_TRY(hipMemcpyAsync(pinned[s], d_buf, row_off[c.hi] - row_off[c.lo], hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipEventRecord(ev[4 + 3 * s], nullptr));
+            return 0;
+        };
+        using clk = std::chrono::steady_clock;
+        Chunk cur = next_chunk(0);
+        if ((rc = issue(cur, 0))) return rc;
+        while (true) {
+            const int s = (int)(n_chunks & 1);
+            Chunk nxt{cur.hi, cur.hi};
+            if (cur.hi < n_rows) {   // the copy of the next chunk runs beside this chunk's fwrite
+                nxt = next_chunk(cur.hi);
+                if ((rc = issue(nxt, s ^ 1))) return rc;
+            }
+            HIP_TRY(hipEventSynchronize(ev[4 + 3 * s]));
+            float ms_fill = 0, ms_copy = 0;
+            HIP_TRY(hipEventElapsedTime(&ms_fill, ev[2 + 3 * s], ev[3 + 3 * s]));
+            HIP_TRY(hipEventElapsedTime(&ms_copy, ev[3 + 3 * s], ev[4 + 3 * s]));
+            format_ms += ms_fill;
+            copy_ms += ms_copy;
+            const uint64_t bytes = row_off[cur.hi] - row_off[cur.lo];
+            const auto t0 = clk::now();
+            if (fwrite(pinned[s], 1, bytes, file) != bytes) return write_failed();
+            write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+            n_chunks++;
+            if (cur.hi >= n_rows) break;
+            cur = nxt;
+        }
+        uint32_t flags = 0;
+        HIP_TRY(hipMemcpyAsync(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if (flags) return fail(PW_ERR_HIP, who + ": the fill pass disagreed with the count pass (internal error)");
+        const auto t0 = clk::now();
+        FILE *f = file;
+        file = nullptr;
+        if (fclose(f) != 0) return write_failed();
+        write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        return 0;
+    }
+};
+
+// the names of a writer call: offsets that ascend, the longest name; `what` is what one name belongs to in the error text
+int check_names(const char *who, const char *what, const char *id_chars, const uint64_t *id_offsets, uint64_t n_names,
+                uint64_t *longest_name) {
+    *longest_name = 0;
+    for (uint64_t i = 0; i < n_names; i++) {
+        if (id_offsets[i + 1] < id_offsets[i])
+            return fail(PW_ERR_INVALID, std::string(who) + ": id_offsets do not ascend at " + what + " " + std::to_string(i));
+        *longest_name = std::max(*longest_name, id_offsets[i + 1] - id_offsets[i]);
+    }
+    if (id_offsets[n_names] && !id_chars) return fail(PW_ERR_INVALID, "null pointer");
+    return 0;
+}
+
+uint64_t chunk_budget(const char *env_name, uint64_t row_max) {   // bytes of text per chunk: at least what one row can take
+    uint64_t budget = EMB_CHUNK_DEFAULT;
+    if (const char *v = getenv(env_name))
+        if (*v) budget = (uint64_t)strtoull(v, nullptr, 10);
+    return std::max(budget, row_max);
+}
+
+}  // namespace
+
+PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
+                                           const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
+    const char *who = "pw_vectors_write_text";
+    if (!d_vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
+    uint64_t longest_name = 0;
     int rc;
-    if ((rc = alloc((void **)&d_ids, id_bytes)) || (rc = alloc((void **)&d_id_off, sizeof(uint64_t) * (n_rows + 1))) ||
-        (rc = alloc((void **)&d_row_off, sizeof(uint64_t) * (n_rows + 1))) ||
-        (rc = alloc((void **)&d_tmp, sizeof(uint64_t) * emb_scan_tmp_elems(n_rows + 1))) || (rc = alloc((void **)&d_flags, sizeof(uint32_t))))
+    if ((rc = check_names(who, "row", id_chars, id_offsets, n_rows, &longest_name))) return rc;
+    const uint64_t id_bytes = id_offsets[n_rows];
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    // the byte budget of a chunk: at least what one row can take (name, dim times " " + 47 characters, newline)
+    const uint64_t row_max = longest_name + (uint64_t)dim * pw::F6_SLOT + 1;
+    const uint64_t budget = chunk_budget("PECANPY_AMD_EMB_CHUNK_BYTES", row_max);
+
+    TextFile out(who, path);
+    if ((rc = out.open(std::to_string(n_rows) + " " + std::to_string(dim) + "\n")) || (rc = out.begin(device))) return rc;
+    char *d_ids = nullptr;
+    uint64_t *d_id_off = nullptr;
+    if ((rc = out.alloc((void **)&d_ids, id_bytes)) || (rc = out.alloc((void **)&d_id_off, sizeof(uint64_t) * (n_rows + 1))) ||
+        (rc = out.alloc_rows(n_rows)))
         return rc;
     if (id_bytes) HIP_TRY(hipMemcpyAsync(d_ids, id_chars, id_bytes, hipMemcpyHostToDevice, nullptr));
     HIP_TRY(hipMemcpyAsync(d_id_off, id_offsets, sizeof(uint64_t) * (n_rows + 1), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), nullptr));
-    HIP_TRY(hipMemsetAsync(d_row_off + n_rows, 0, sizeof(uint64_t), nullptr));   // (the scan's last input: its output is the total)
 
-    // count pass and scan: row_off[i] = byte offset of row i in the text behind the header, row_off[n_rows] = the total
-    const unsigned row_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rows + 3) / 4, (uint64_t)prop.multiProcessorCount * 16));
-    HIP_TRY(hipEventRecord(mem.ev[0], nullptr));
-    hipLaunchKernelGGL(pw::emb_count_kernel, dim3(row_grid), dim3(256), 0, nullptr, d_vectors, n_rows, dim, (const uint64_t *)d_id_off, d_row_off);
-    emb_exclusive_scan(d_row_off, n_rows + 1, d_tmp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(mem.ev[1], nullptr));
-    std::vector<uint64_t> row_off(n_rows + 1);
-    HIP_TRY(hipMemcpyAsync(row_off.data(), d_row_off, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, mem.ev[0], mem.ev[1]));
-    double format_ms = ms, copy_ms = 0, write_ms = 0;
-    const uint64_t total = row_off[n_rows];
-    for (uint64_t i = 0; i < n_rows; i++)   // (what the fill pass is bounded by: checked before anything is written through it)
-        if (row_off[i + 1] < row_off[i] || row_off[i + 1] - row_off[i] > row_max)
-            return fail(PW_ERR_HIP, "pw_vectors_write_text: row byte counts out of range (internal error)");
-
-    // chunks: consecutive rows while their text fits the budget (one row always does)
-    const uint64_t buf_bytes = std::min(budget, total);
-    if ((rc = alloc((void **)&d_buf, buf_bytes))) return rc;
-    for (auto &p : mem.pinned) {
-        hipError_t e = hipHostMalloc(&p, buf_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(PW_ERR_NOMEM, std::string("pw_vectors_write_text: pinned host buffer: ") + hipGetErrorString(e));
-        }
-    }
-    struct Chunk { uint64_t lo, hi; };
-    auto next_chunk = [&](uint64_t lo) {
-        // the last row whose end lies within the budget from row lo's start
-        const uint64_t limit = row_off[lo] + buf_bytes;
-        const uint64_t hi = (uint64_t)(std::upper_bound(row_off.begin() + lo + 1, row_off.end(), limit) - row_off.begin()) - 1;
-        return Chunk{lo, hi};
-    };
-    // slot s = chunk index & 1: events 2 + 3 s .. 4 + 3 s = fill begin, fill end, copy end
-    auto issue = [&](const Chunk &c, int s) -> int {
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((c.hi - c.lo + 3) / 4, (uint64_t)prop.multiProcessorCount * 16));
-        HIP_TRY(hipEventRecord(mem.ev[2 + 3 * s], nullptr));
-        hipLaunchKernelGGL(pw::emb_fill_kernel, dim3(grid), dim3(256), 0, nullptr, d_vectors, c.lo, c.hi, dim, (const char *)d_ids,
-                           (const uint64_t *)d_id_off, (const uint64_t *)d_row_off, d_buf, d_flags);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(mem.ev[3 + 3 * s], nullptr));
-        HIP_TRY(hipMemcpyAsync(mem.pinned[s], d_buf, row_off[c.hi] - row_off[c.lo], hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipEventRecord(mem.ev[4 + 3 * s], nullptr));
-        return 0;
-    };
-    using clk = std::chrono::steady_clock;
-    uint64_t n_chunks = 0;
-    Chunk cur = next_chunk(0);
-    if ((rc = issue(cur, 0))) return rc;
-    while (true) {
-        const int s = (int)(n_chunks & 1);
-        Chunk nxt{cur.hi, cur.hi};
-        if (cur.hi < n_rows) {   // the copy of the next chunk runs beside this chunk's fwrite
-            nxt = next_chunk(cur.hi);
-            if ((rc = issue(nxt, s ^ 1))) return rc;
-        }
-        HIP_TRY(hipEventSynchronize(mem.ev[4 + 3 * s]));
-        float ms_fill = 0, ms_copy = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_fill, mem.ev[2 + 3 * s], mem.ev[3 + 3 * s]));
-        HIP_TRY(hipEventElapsedTime(&ms_copy, mem.ev[3 + 3 * s], mem.ev[4 + 3 * s]));
-        format_ms += ms_fill;
-        copy_ms += ms_copy;
-        const uint64_t bytes = row_off[cur.hi] - row_off[cur.lo];
-        const auto t0 = clk::now();
-        if (fwrite(mem.pinned[s], 1, bytes, mem.file) != bytes) return write_failed();
-        write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-        n_chunks++;
-        if (cur.hi >= n_rows) break;
-        cur = nxt;
-    }
-    uint32_t flags = 0;
-    HIP_TRY(hipMemcpyAsync(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if (flags) return fail(PW_ERR_HIP, "pw_vectors_write_text: the fill pass disagreed with the count pass (internal error)");
-    const auto t0 = clk::now();
-    FILE *f = mem.file;
-    mem.file = nullptr;
-    if (fclose(f) != 0) return write_failed();
-    write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    if ((rc = out.count_begin())) return rc;
+    hipLaunchKernelGGL(pw::emb_count_kernel, dim3(out.grid(n_rows)), dim3(256), 0, nullptr, d_vectors, n_rows, dim, (const uint64_t *)d_id_off,
+                       out.d_row_off);
+    if ((rc = out.count_end(n_rows))) return rc;
+    rc = out.write_chunks(budget, row_max, [&](uint64_t lo, uint64_t hi, unsigned blocks, char *d_buf) {
+        hipLaunchKernelGGL(pw::emb_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_vectors, lo, hi, dim, (const char *)d_ids,
+                           (const uint64_t *)d_id_off, (const uint64_t *)out.d_row_off, d_buf, out.d_flags);
+    });
+    if (rc) return rc;
     if (stats) {
-        stats->format_ms = format_ms; stats->copy_ms = copy_ms; stats->write_ms = write_ms;
-        stats->bytes = total + (uint64_t)snprintf(nullptr, 0, "%llu %u\n", (unsigned long long)n_rows, dim);
-        stats->chunks = n_chunks;
+        stats->format_ms = out.format_ms; stats->copy_ms = out.copy_ms; stats->write_ms = out.write_ms;
+        stats->bytes = out.bytes();
+        stats->chunks = out.n_chunks;
     }
     return PW_OK;
 }
@@ -4345,6 +4409,106 @@ PW_EXPORT int pw_vectors_write_text(int device, const float *vectors, uint64_t n
     int rc = e == hipSuccess ? pw_vectors_write_text_device(device, d_vectors, n_rows, dim, id_chars, id_offsets, path, stats)
                              : fail(PW_ERR_HIP, std::string("pw_vectors_write_text: ") + hipGetErrorString(e));
     (void)hipFree(d_vectors);
+    return rc;
+}
+
+// ---- the walk corpus file written from device memory (csrc/walk_text.hip.h) ---------------------------------------------------
+PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length,
+                                         const char *id_chars, const uint64_t *id_offsets, uint64_t n_names, const char *path,
+                                         pw_walks_write_stats *stats) {
+    const char *who = "pw_walks_write_text";
+    if ((n_walks && !d_walks) || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
+    if (walk_length >= (1u << 31)) return fail(PW_ERR_INVALID, "pw_walks_write_text: walk_length must be below 2^31");
+    uint64_t longest_name = 0;
+    int rc;
+    if ((rc = check_names(who, "name", id_chars, id_offsets, n_names, &longest_name))) return rc;
+    if (longest_name > pw::WALK_NAME_MAX)
+        return fail(PW_ERR_INVALID, "pw_walks_write_text: a name of " + std::to_string(longest_name) + " bytes (at most " +
+                                        std::to_string(pw::WALK_NAME_MAX) + ")");
+    const uint64_t id_bytes = id_offsets[n_names];
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    // the byte budget of a chunk: at least the longest possible row, walk_length + 1 times the longest name and its separator
+    const uint64_t row_max = ((uint64_t)walk_length + 1) * (longest_name + 1);
+    const uint64_t budget = chunk_budget("PECANPY_AMD_WALKS_CHUNK_BYTES", row_max);
+
+    TextFile out(who, path);
+    if ((rc = out.open(""))) return rc;
+    if (stats) *stats = pw_walks_write_stats{0, 0, 0, 0, 0, 0, 0};
+    if (n_walks == 0) {   // the empty file
+        FILE *f = out.file;
+        out.file = nullptr;
+        return fclose(f) == 0 ? PW_OK : out.write_failed();
+    }
+    if ((rc = out.begin(device))) return rc;
+    char *d_ids = nullptr;
+    uint64_t *d_id_off = nullptr;
+    unsigned long long *d_found = nullptr;   // the count kernel's findings: lowest row with a bad length, with a bad token; tokens
+    if ((rc = out.alloc((void **)&d_ids, id_bytes)) || (rc = out.alloc((void **)&d_id_off, sizeof(uint64_t) * (n_names + 1))) ||
+        (rc = out.alloc((void **)&d_found, sizeof(unsigned long long) * 3)) || (rc = out.alloc_rows(n_walks)))
+        return rc;
+    if (id_bytes) HIP_TRY(hipMemcpyAsync(d_ids, id_chars, id_bytes, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(d_id_off, id_offsets, sizeof(uint64_t) * (n_names + 1), hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemsetAsync(d_found, 0xff, sizeof(unsigned long long) * 2, nullptr));
+    HIP_TRY(hipMemsetAsync(d_found + 2, 0, sizeof(unsigned long long), nullptr));
+
+    if ((rc = out.count_begin())) return rc;
+    hipLaunchKernelGGL(pw::walk_text_count_kernel, dim3(out.grid(n_walks)), dim3(256), 0, nullptr, d_walks, n_walks, walk_length,
+                       (const uint64_t *)d_id_off, n_names, out.d_row_off, d_found);
+    if ((rc = out.count_end(n_walks))) return rc;
+    unsigned long long found[3];
+    HIP_TRY(hipMemcpy(found, d_found, sizeof(found), hipMemcpyDeviceToHost));
+    const uint64_t width = (uint64_t)walk_length + 2;
+    if (found[0] != ~0ull) {   // nothing of the matrix was looked up, and no fill pass runs: the file stays empty
+        uint32_t len = 0;
+        HIP_TRY(hipMemcpy(&len, d_walks + found[0] * width + walk_length + 1, sizeof(len), hipMemcpyDeviceToHost));
+        return fail(PW_ERR_INVALID, "pw_walks_write_text: row length " + std::to_string(len) + " in row " + std::to_string(found[0]) +
+                                        " exceeds walk_length + 1 = " + std::to_string((uint64_t)walk_length + 1));
+    }
+    if (found[1] != ~0ull) {
+        std::vector<uint32_t> row(width);
+        HIP_TRY(hipMemcpy(row.data(), d_walks + found[1] * width, sizeof(uint32_t) * width, hipMemcpyDeviceToHost));
+        uint64_t c = 0;
+        while (c < row[walk_length + 1] && row[c] < n_names) c++;
+        return fail(PW_ERR_INVALID, "pw_walks_write_text: node index " + std::to_string(row[c]) + " at position " + std::to_string(c) +
+                                        " of row " + std::to_string(found[1]) + " outside the " + std::to_string(n_names) + " names");
+    }
+    rc = out.write_chunks(budget, row_max, [&](uint64_t lo, uint64_t hi, unsigned blocks, char *d_buf) {
+        hipLaunchKernelGGL(pw::walk_text_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_walks, lo, hi, walk_length, (const char *)d_ids,
+                           (const uint64_t *)d_id_off, n_names, (const uint64_t *)out.d_row_off, d_buf, out.d_flags);
+    });
+    if (rc) return rc;
+    if (stats) {
+        stats->format_ms = out.format_ms; stats->copy_ms = out.copy_ms; stats->write_ms = out.write_ms;
+        stats->bytes = out.bytes();
+        stats->chunks = out.n_chunks;
+        stats->rows = n_walks;
+        stats->tokens = found[2];
+    }
+    return PW_OK;
+}
+
+// host-matrix entry: upload, then the device entry
+PW_EXPORT int pw_walks_write_text(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, const char *id_chars,
+                                  const uint64_t *id_offsets, uint64_t n_names, const char *path, pw_walks_write_stats *stats) {
+    if (n_walks == 0 || !walks || walk_length >= (1u << 31))   // (nothing to upload, or refused there)
+        return pw_walks_write_text_device(device, nullptr, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats);
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2);
+    uint32_t *d_walks = nullptr;
+    hipError_t e = hipMalloc((void **)&d_walks, wbytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PW_ERR_NOMEM, std::string("pw_walks_write_text: the matrix does not fit in device memory: ") + hipGetErrorString(e));
+    }
+    e = hipMemcpy(d_walks, walks, wbytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? pw_walks_write_text_device(device, d_walks, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats)
+                             : fail(PW_ERR_HIP, std::string("pw_walks_write_text: ") + hipGetErrorString(e));
+    (void)hipFree(d_walks);
     return rc;
 }
 

@@ -79,6 +79,7 @@ class Base(BaseGraph):
         self.device = None  # GPU index; None -> LOCAL_RANK / 0
         self.last_stats = None
         self.last_embed_stats = None
+        self.last_corpus_stats = None   # walks_to_file: what the call did
         self.last_build_stats = None   # from_edge_index / from_tensor: what the device build of the graph did
         # the library's one-time start-up (~140 ms for the first stream it creates) runs on a helper thread beside what comes
         # next in the reference's flow -- reading the graph (cli.py:328-337) -- instead of in front of the first walk
@@ -433,6 +434,37 @@ class Base(BaseGraph):
         self.last_embed_stats = {"walk_matrix_host_bytes": 0, "vectors_host_bytes": 0, "walk_ms": walk_ms,
                                  "sgns_call_ms": sgns_call_ms, "write_call_ms": (time.perf_counter() - t0) * 1e3, **trainer,
                                  **save_word2vec_format_device.last_stats}
+
+    def walks_to_file(self, path, num_walks=10, walk_length=80):
+        """The walks of ``simulate_walks(num_walks, walk_length)`` as a text file, one walk per line with the node IDs
+        separated by single spaces (``pecanpy_amd.corpus``), without ``List[List[str]]``: ``_device_walks`` ->
+        ``save_walks_device``; neither the walk matrix nor ID lists visit the host, only the text of the file leaves the
+        device.  For a seeded object the file holds the bytes ``cli._dump_walks(path, self.simulate_walks(...))`` writes.
+
+        ``self.last_corpus_stats``: ``walk_matrix_host_bytes`` (0 on this route), ``walk_ms``, ``write_call_ms`` and the
+        writer's ``format_ms``, ``copy_ms``, ``write_ms``, ``bytes``, ``chunks``, ``rows``, ``tokens``.  Where the walks
+        cannot stay on one device (see ``_device_walks``) ``simulate_walks_array`` + ``save_walks`` run instead and
+        ``walk_matrix_host_bytes`` holds the bytes of the matrix that came to the host."""
+        import time
+
+        from .corpus import save_walks, save_walks_device
+
+        t0 = time.perf_counter()
+        d_walks = self._device_walks(num_walks, walk_length)
+        if d_walks is None:
+            mat = self.simulate_walks_array(num_walks, walk_length)
+            t1 = time.perf_counter()
+            save_walks(path, self.nodes, mat)
+            self.last_corpus_stats = {"walk_matrix_host_bytes": int(mat.nbytes), "walk_ms": (t1 - t0) * 1e3,
+                                      "write_call_ms": (time.perf_counter() - t1) * 1e3}
+            return
+        import torch
+
+        torch.cuda.synchronize(d_walks.device)
+        t1 = time.perf_counter()
+        save_walks_device(path, self.nodes, d_walks)
+        self.last_corpus_stats = {"walk_matrix_host_bytes": 0, "walk_ms": (t1 - t0) * 1e3,
+                                  "write_call_ms": (time.perf_counter() - t1) * 1e3, **save_walks_device.last_stats}
 
     def embed(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, verbose=False):
         """``simulate_walks`` + skip-gram (pecanpy.py:240-290): returns ``float32[num_nodes, dim]`` in node order.
