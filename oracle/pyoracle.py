@@ -286,23 +286,40 @@ _SGNS = None
 
 
 def sgns_train(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
-               sample=1e-3, seed=0):
+               sample=1e-3, seed=0, order=None, return_counts=False):
     """Sequential skip-gram with negative sampling over a walk matrix (oracle/sgns_ref.c: word2vec.c / gensim sg=1,
     the model of Base.embed, src/pecanpy/pecanpy.py:276-290).  Returns ``(vectors float32[num_nodes, dim], mean loss of
-    the last epoch)``."""
+    the last epoch)``.
+
+    ``order``: a permutation of the walk indices, the visiting order inside every epoch (default: sentence order); the
+    hashes and the learning-rate schedule keep using each walk's own index.  ``return_counts=True`` appends
+    ``(kept_occurrences, trained_pairs)``, summed over the epochs, defined as the trainer's two counters."""
     global _SGNS
     if _SGNS is None:
         path = os.path.join(_HERE, "libsgns_ref.so")
         if not os.path.exists(path):
             build()
         _SGNS = C.CDLL(path)
+        if not hasattr(_SGNS, "sgns_ref_train_ex"):   # a library left from before the entry point existed: make renews it
+            build()
+            _SGNS = C.CDLL(path)
     mat = np.ascontiguousarray(walk_matrix, dtype=np.uint32)
+    if mat.ndim != 2 or mat.shape[1] < 3:
+        raise ValueError("walk matrix must be uint32[n_walks, walk_length + 2]")
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.uint64)
+        if order.shape != (mat.shape[0],):
+            raise ValueError("order must name every walk once")
     out = np.zeros((int(num_nodes), int(dim)), dtype=np.float32)
     loss = C.c_double(0)
-    rc = _SGNS.sgns_ref_train(mat.ctypes.data_as(C.c_void_p), C.c_uint64(mat.shape[0]), C.c_uint32(mat.shape[1] - 2),
-                              C.c_uint32(int(num_nodes)), C.c_uint32(int(dim)), C.c_uint32(int(window)), C.c_uint32(int(negative)),
-                              C.c_uint32(int(epochs)), C.c_float(alpha), C.c_float(min_alpha), C.c_float(sample),
-                              C.c_uint32(int(seed) & 0xFFFFFFFF), out.ctypes.data_as(C.c_void_p), C.byref(loss))
+    counts = (C.c_uint64 * 2)(0, 0)
+    rc = _SGNS.sgns_ref_train_ex(mat.ctypes.data_as(C.c_void_p), C.c_uint64(mat.shape[0]), C.c_uint32(mat.shape[1] - 2),
+                                 C.c_uint32(int(num_nodes)), C.c_uint32(int(dim)), C.c_uint32(int(window)), C.c_uint32(int(negative)),
+                                 C.c_uint32(int(epochs)), C.c_float(alpha), C.c_float(min_alpha), C.c_float(sample),
+                                 C.c_uint32(int(seed) & 0xFFFFFFFF), out.ctypes.data_as(C.c_void_p), C.byref(loss), counts,
+                                 order.ctypes.data_as(C.c_void_p) if order is not None else None)
     if rc != 0:
-        raise ValueError("sgns_ref_train: malformed walk matrix")
+        raise ValueError("sgns_ref_train: malformed walk matrix or order")
+    if return_counts:
+        return out, float(loss.value), (int(counts[0]), int(counts[1]))
     return out, float(loss.value)

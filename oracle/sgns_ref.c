@@ -36,10 +36,16 @@ static uint64_t mix64(uint64_t x) {
 static float u24(uint64_t x) { return (float)(x >> 40) * (1.0f / 16777216.0f); }
 
 /* vectors: float32[n_nodes * dim] (syn0 after training); loss (may be NULL): mean SGNS loss of the pairs trained in the
- * last epoch, evaluated before each update.  Returns 0, or -1 on a malformed walk matrix / allocation failure. */
-EXPORT int sgns_ref_train(const uint32_t *walks, uint64_t n_walks, uint32_t L, uint32_t n_nodes, uint32_t dim,
-                          uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha, float sample,
-                          uint32_t seed, float *vectors, double *loss) {
+ * last epoch, evaluated before each update.
+ * counts (may be NULL): [0] occurrences that survived the subsampling, [1] (centre, context) pairs trained, both summed over
+ * all epochs -- the trainer's two counters (a pair counts once, whatever its negatives).
+ * order (may be NULL = 0 .. n_walks - 1): a permutation of the walk indices, the order in which the walks are visited inside
+ * every epoch.  Every hash and the learning-rate schedule still use the walk's OWN index: only the order of the updates
+ * changes, which is all that a run of several wavefronts changes (wavefront w of n takes walks w, w + n, ...).
+ * Returns 0, or -1 on a malformed walk matrix / an order that is no permutation / allocation failure. */
+EXPORT int sgns_ref_train_ex(const uint32_t *walks, uint64_t n_walks, uint32_t L, uint32_t n_nodes, uint32_t dim,
+                             uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha, float sample,
+                             uint32_t seed, float *vectors, double *loss, uint64_t *counts, const uint64_t *order) {
     const uint32_t W = L + 2;
     const uint64_t n_items = n_walks * (uint64_t)(L + 1);
     uint64_t *cnt = calloc(n_nodes, sizeof(uint64_t));
@@ -47,6 +53,17 @@ EXPORT int sgns_ref_train(const uint32_t *walks, uint64_t n_walks, uint32_t L, u
     float *keep = sample > 0 ? malloc(sizeof(float) * n_nodes) : NULL;
     float *neu1e = malloc(sizeof(float) * dim);
     if (!cnt || !syn1 || !neu1e || (sample > 0 && !keep)) return -1;
+    if (order) {   /* every walk exactly once */
+        unsigned char *seen = calloc(n_walks ? n_walks : 1, 1);
+        if (!seen) return -1;
+        int ok = 1;
+        for (uint64_t i = 0; i < n_walks && ok; i++) {
+            if (order[i] >= n_walks || seen[order[i]]) ok = 0;
+            else seen[order[i]] = 1;
+        }
+        free(seen);
+        if (!ok) return -1;
+    }
     /* vocabulary statistics */
     for (uint64_t wk = 0; wk < n_walks; wk++) {
         const uint32_t *row = walks + wk * W;
@@ -94,17 +111,19 @@ EXPORT int sgns_ref_train(const uint32_t *walks, uint64_t n_walks, uint32_t L, u
     }
     const uint64_t item_total = n_items * epochs;
     double loss_sum = 0;
-    uint64_t loss_n = 0;
+    uint64_t loss_n = 0, n_kept = 0, n_pairs = 0;
     for (uint32_t ep = 0; ep < epochs; ep++) {
         const uint64_t item_base = n_items * ep;
         const int last_epoch = ep + 1 == epochs;
-        for (uint64_t wk = 0; wk < n_walks; wk++) {
+        for (uint64_t visit = 0; visit < n_walks; visit++) {
+            const uint64_t wk = order ? order[visit] : visit;
             const uint32_t *row = walks + wk * W;
             const uint32_t len = row[L + 1];
 #define OCC(p) mix64((uint64_t)seed ^ (item_base + wk * (uint64_t)(L + 1) + (p)) * 0x9E3779B97F4A7C15ull)
 #define KEPT(p) (!keep || u24(OCC(p)) < keep[row[p]])
             for (uint32_t pos = 0; pos < len; pos++) {
                 if (!KEPT(pos)) continue;
+                n_kept++;
                 const uint64_t item = wk * (uint64_t)(L + 1) + pos;
                 uint64_t rs = mix64(OCC(pos));
                 const uint32_t eff = window - (uint32_t)(rs % window);
@@ -155,6 +174,7 @@ EXPORT int sgns_ref_train(const uint32_t *walks, uint64_t n_walks, uint32_t L, u
                         }
                     }
                     for (uint32_t k = 0; k < dim; k++) v[k] += neu1e[k];
+                    n_pairs++;
                 }
             }
 #undef OCC
@@ -162,6 +182,14 @@ EXPORT int sgns_ref_train(const uint32_t *walks, uint64_t n_walks, uint32_t L, u
         }
     }
     if (loss) *loss = loss_n ? loss_sum / (double)loss_n : 0.0;
+    if (counts) { counts[0] = n_kept; counts[1] = n_pairs; }
     free(cnt); free(syn1); free(keep); free(neu1e); free(table);
     return 0;
+}
+
+EXPORT int sgns_ref_train(const uint32_t *walks, uint64_t n_walks, uint32_t L, uint32_t n_nodes, uint32_t dim,
+                          uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha, float sample,
+                          uint32_t seed, float *vectors, double *loss) {
+    return sgns_ref_train_ex(walks, n_walks, L, n_nodes, dim, window, negative, epochs, alpha, min_alpha, sample, seed, vectors,
+                             loss, NULL, NULL);
 }

@@ -19,6 +19,13 @@
 // (oracle/sgns_ref.c): component k on lane k % 64, per-lane partial sums in ascending k, xor butterfly 32 -> 1, neu1e
 // accumulated in draw order.  With ONE wavefront (pw_sgns_train*: workers = 1) the updates run in sentence order and the
 // result is compared with that restatement within float tolerance (tests/test_gpu_sgns.py, tests/test_gpu_embed_device.py).
+// The PARALLEL form (several wavefronts of a workgroup on their LDS slices, several workgroups, the stride over the walks,
+// the rounding of workers to whole workgroups, one wavefront per workgroup from L = 2048, exactly 64 KiB of LDS at L = 2047
+// and L = 8191) is held to two things that need no tolerance of their own (tests/test_gpu_sgns_waves.py): on a corpus whose
+// walk wk names only rows of component wk % n_waves, with negative = 0, no two wavefronts share a row and each takes its
+// walks in ascending order, so the vectors equal those of workers = 1 bit for bit; and the two counters, hashes of
+// (seed, epoch, walk, position), equal the restatement's counts in any run, a racing one with negatives included.  What
+// a racing run's vectors are compared by stays statistical (similarity structure, tests/test_gpu_sgns.py).
 // The kernel writes global memory through vector stores only; the two counters are per-lane atomics of lane 0, once per walk.
 #pragma once
 #include <cstddef>
