@@ -26,6 +26,7 @@
 
 #include "../../include/pecanpy_amd.h"
 #include "aux_kernels.hip.h"
+#include "devmem.hpp"
 #include "edgelist.hpp"
 #include "thresholds.hpp"
 #include "mtjump.hpp"
@@ -110,25 +111,14 @@ bool wlanes_worth(const LaneSwitches &sw, uint64_t n_jobs) {
             return fail(PW_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
     } while (0)
 
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-        if (e != hipSuccess) return fail(PW_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        cap = n;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+using pw::DevBuf;      // (devmem.hpp: every device allocation of this file lives in one, pinned host memory in a PinnedBuf)
+using pw::PinnedBuf;
+
+// scratch that is reused across calls: grown on demand, PW_ERR_NOMEM when the device has no room for it
+template <typename T> int grow(DevBuf<T> &b, size_t n) {
+    const hipError_t e = b.ensure(n);
+    return e == hipSuccess ? 0 : fail(PW_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
 
 }  // namespace
 
@@ -146,7 +136,6 @@ struct GraphDesc {
                                                         // built (the wave kernel's lazy step reads it) but the lane kernel is not used
     bool vlines = false;                                // lines[nnz + v]: the line of vertex v's mirrored overflow read
     uint64_t clist_bytes = 0, line_bytes = 0;
-    uint64_t fbits_words = 0, slot_words = 0;           // sizes of d_fbits / d_slots (pw_graph_replicate copies the buffers)
     uint64_t n_clist = 0;
     uint32_t list_max_len = 0xffffffffu;                // partial index: lists longer than this were left out (EL_NO_LIST)
     uint64_t index_bytes = 0;                           // device bytes of the membership / lane index
@@ -160,42 +149,41 @@ struct GraphDesc {
 // every table in place.
 struct GraphData : GraphDesc {
     int device = 0;
-    uint32_t *d_indptr = nullptr, *d_indices = nullptr;
-    uint32_t *d_hasnbr = nullptr;                       // bit v: vertex v has neighbours (stream offsets; built by the first call)
-    void *d_data = nullptr;          // float32 (CSR graphs) or float64 (dense graphs); null when unit
-    float *d_thr = nullptr;
-    uint64_t *d_adjbits = nullptr;   // dense graphs: bit-packed adjacency rows
-    uint32_t *d_deg = nullptr;       // dense graphs: row degrees
-    uint32_t *d_foff = nullptr;      // CSR graphs: per-row membership filters (offsets, bits)
-    uint64_t *d_fbits = nullptr;
-    uint2 *d_kf = nullptr;           // CSR graphs: (neighbour id, filter word) per CSR entry
-    uint64_t *d_tab_off = nullptr, *d_slots = nullptr;  // CSR graphs: adjacency index (exact lookups)
-    uint4 *d_vrec = nullptr;                            // CSR graphs: per-vertex record (row start, degree, filter, index)
-    pw::ELine *d_lines = nullptr;                       // lane index (walk_lanes.hip.h): 64-byte edge line per CSR entry; its first 16 bytes
+    DevBuf<uint32_t> d_indptr, d_indices;
+    DevBuf<uint32_t> d_hasnbr;                          // bit v: vertex v has neighbours (stream offsets; built by the first call)
+    DevBuf<void> d_data;             // float32 (CSR graphs) or float64 (dense graphs); null when unit
+    DevBuf<float> d_thr;
+    DevBuf<uint64_t> d_adjbits;      // dense graphs: bit-packed adjacency rows
+    DevBuf<uint32_t> d_deg;          // dense graphs: row degrees
+    DevBuf<uint32_t> d_foff;         // CSR graphs: per-row membership filters (offsets, bits)
+    DevBuf<uint64_t> d_fbits;
+    DevBuf<uint2> d_kf;              // CSR graphs: (neighbour id, filter word) per CSR entry
+    DevBuf<uint64_t> d_tab_off, d_slots;                // CSR graphs: adjacency index (exact lookups)
+    DevBuf<uint4> d_vrec;                               // CSR graphs: per-vertex record (row start, degree, filter, index)
+    DevBuf<pw::ELine> d_lines;                          // lane index (walk_lanes.hip.h): 64-byte edge line per CSR entry; its first 16 bytes
                                                         // {neighbour, common-neighbour count, reverse position, degree} also serve walk_kernel's lazy step
-    uint8_t *d_clist = nullptr;                         // lane index: the lists too long for their edge line
+    DevBuf<uint8_t> d_clist;                            // lane index: the lists too long for their edge line
     double index_build_ms = 0;                          // device time of all index KERNELS of pw_csr_create (event pairs around them)
     double create_wall_ms = 0;                          // wall clock of pw_csr_create: runtime start-up, host passes, H2D, allocations, kernels
     uint64_t thr_version = 0;                           // thresholds uploaded (pw_graph_set_thresholds calls)
-    float *d_tot_e = nullptr, *d_tot_v = nullptr;       // weighted CSR graphs: per-edge / per-vertex normalisers
+    DevBuf<float> d_tot_e, d_tot_v;                     // weighted CSR graphs: per-edge / per-vertex normalisers
     double tot_p = 0, tot_q = 0;                        // ... built for these parameters
     int tot_extend = -1;                                // -1: none yet
     uint64_t tot_thr_version = 0;                       // thresholds uploaded since the table was built?
     bool tot_failed = false;
     double tot_build_ms = 0;
-    float *d_utot = nullptr;                            // unit graphs, 1/p or 1/q not a power of two: row total per arriving line
+    DevBuf<float> d_utot;                               // unit graphs, 1/p or 1/q not a power of two: row total per arriving line
     float utot_wo = 0, utot_wp = 0;                     // ... built for these biases (0: none)
     bool utot_failed = false;
     // weighted lane form (walk_lanes.hip.h: WEIGHTED): base values, their per-row float64 prefix sums, per-entry delta prefix sums
-    float *d_wb = nullptr;
-    pw::PrefixPair *d_wpq = nullptr;
-    double *d_wdl = nullptr, *d_wl_dprev = nullptr;
-    unsigned long long *d_wl_off = nullptr;
-    uint32_t *d_wedge_row = nullptr;                    // ... source vertex of every CSR entry
-    pw::PrefixPair *d_wp1 = nullptr;                    // ... per-row prefix sums of the raw weights (first steps; graph-static)
-    unsigned long long *d_wck_off = nullptr;            // ... recorded chain values (wckpt_kernel): first record of entry e
-    float *d_wck = nullptr;
-    uint64_t wdl_cap = 0, wck_cap = 0;
+    DevBuf<float> d_wb;
+    DevBuf<pw::PrefixPair> d_wpq;
+    DevBuf<double> d_wdl, d_wl_dprev;
+    DevBuf<unsigned long long> d_wl_off;
+    DevBuf<uint32_t> d_wedge_row;                       // ... source vertex of every CSR entry
+    DevBuf<pw::PrefixPair> d_wp1;                       // ... per-row prefix sums of the raw weights (first steps; graph-static)
+    DevBuf<unsigned long long> d_wck_off;               // ... recorded chain values (wckpt_kernel): first record of entry e
+    DevBuf<float> d_wck;
     double wl_p = 0, wl_q = 0;
     int wl_extend = -1;
     uint64_t wl_thr_version = 0;
@@ -213,21 +201,7 @@ struct GraphData : GraphDesc {
     explicit GraphData(int dev) : device(dev) {}
     GraphData(const GraphData &) = delete;
     GraphData &operator=(const GraphData &) = delete;
-    ~GraphData() {
-        (void)hipSetDevice(device);
-        for (void *q : {(void *)d_indptr, (void *)d_indices, (void *)d_hasnbr, (void *)d_data, (void *)d_thr, (void *)d_adjbits,
-                        (void *)d_deg, (void *)d_foff, (void *)d_fbits, (void *)d_kf, (void *)d_tab_off, (void *)d_slots, (void *)d_vrec,
-                        (void *)d_lines, (void *)d_clist, (void *)d_tot_e, (void *)d_tot_v, (void *)d_utot, (void *)d_wb, (void *)d_wpq,
-                        (void *)d_wdl, (void *)d_wl_dprev, (void *)d_wl_off, (void *)d_wedge_row, (void *)d_wp1, (void *)d_wck_off,
-                        (void *)d_wck})
-            if (q) (void)hipFree(q);
-        alias_indptr.release();
-        alias_j.release();
-        alias_s.release();
-        alias_l.release();
-        edge_row.release();
-        alias_q.release();
-    }
+    ~GraphData() { (void)hipSetDevice(device); }   // (the members free themselves behind this body: on their own device)
 };
 
 // A call context over a graph: streams, events, counters, random stream and scratch buffers, and the flags of the
@@ -257,8 +231,8 @@ struct pw_graph {
     hipStream_t copy_stream = nullptr;     // pw_simulate: the D2H of one part of the walk matrix runs here, under the walks of the next
     static constexpr int N_STAGE = 12;
     hipEvent_t ev_copy[N_STAGE] = {};
-    void *stage[N_STAGE] = {};             // pinned staging buffers of pw_simulate's copy out
-    uint32_t *seed_state = nullptr;        // pinned: the seed's MT19937 state on its way to the device
+    PinnedBuf<void> stage[N_STAGE];        // pinned staging buffers of pw_simulate's copy out
+    PinnedBuf<uint32_t> seed_state;        // pinned: the seed's MT19937 state on its way to the device
     double lane_ms = 0;              // lane kernel time of the current call
     int n_cu = 0;
     // scratch reused across calls
@@ -365,25 +339,6 @@ PW_EXPORT void pw_graph_destroy(pw_graph *g) {
     if (!g) return;
     if (g->twin) { pw_graph_destroy(g->twin); g->twin = nullptr; }
     (void)hipSetDevice(g->device);
-    g->redo.release();
-    g->susp[0].release();
-    g->susp[1].release();
-    g->ver.release();
-    g->ver_bad.release();
-    g->ver_jobs.release();
-    g->stream_off.release();
-    g->tile_sums.release();
-    g->rng.release();
-    g->mt_state.release();
-    for (auto &c : g->mt_cache) c.states.release();
-    g->jump_table.release();
-    g->jump_tmp.release();
-    g->changed.release();
-    g->counters.release();
-    g->probs_scratch.release();
-    for (auto &b : g->stage)
-        if (b) (void)hipHostFree(b);
-    if (g->seed_state) (void)hipHostFree(g->seed_state);
     for (auto &e : g->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : g->round_ev)
@@ -394,8 +349,7 @@ PW_EXPORT void pw_graph_destroy(pw_graph *g) {
     if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
     if (g->stream2) (void)hipStreamDestroy(g->stream2);
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    g->gd.reset();   // (the graph goes with the last context that walks it)
-    delete g;
+    delete g;        // (its buffers with it, and the graph with the last context that walks it)
 }
 
 // a call context on `device` over `gd` (a twin's: the primary's graph) or over a new, empty graph
@@ -515,13 +469,18 @@ static void make_lane_work_items(const uint32_t *indptr, const uint32_t *indices
         }                                                                                                        \
     } while (0)
 
-static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d_edge_row, bool has_loop, void *pre_lines = nullptr,
-                            uint64_t pre_bytes = 0) {
-    // (pre_lines: the edge lines' memory, allocated by pw_csr_create's helper thread beside the host pass and the first kernels
-    //  -- device memory a fresh box hands out for the first time costs up to ~25 ms per GB of hipMalloc; owned by g from here on)
-    if (pre_lines) g->gd->d_lines = (pw::ELine *)pre_lines;
-    auto no_index = [&]() { if (g->gd->d_lines) { (void)hipFree(g->gd->d_lines); g->gd->d_lines = nullptr; } return 0; };
-    if (!g->gd->nnz) return no_index();
+static_assert(sizeof(pw::ELine) == 64, "the edge lines are sized in whole lines: one more than the graph has, 64 bytes of slack");
+
+static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d_edge_row, bool has_loop) {
+    // (g->gd->d_lines may hold the edge lines' memory already: pw_csr_create's helper thread allocates it beside the host pass and
+    //  the first kernels -- device memory a fresh box hands out for the first time costs up to ~25 ms per GB of hipMalloc)
+    auto drop = [&](int rc) {   // no lane index
+        g->gd->d_lines.release();
+        g->gd->d_clist.release();
+        (void)hipGetLastError();
+        return rc;
+    };
+    if (!g->gd->nnz) return drop(0);
     const uint32_t nnz = g->gd->nnz, n_nodes = g->gd->n_nodes;
     const bool dbg = getenv("PECANPY_AMD_CREATE_DEBUG") != nullptr;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -535,7 +494,7 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     };
     std::vector<pw::LaneBuildItem> &small = items.small, &large = items.large;
     const uint64_t segcnt_total = items.segcnt_total;
-    if (segcnt_total >= 0xffffffffull) return no_index();   // (rows this long and this many: no lane index)
+    if (segcnt_total >= 0xffffffffull) return drop(0);   // (rows this long and this many: no lane index)
     // + one OVERFLOW line per vertex (walk_lanes.hip.h: vline_init_kernel): the pair of its mirrored choice == degree read
     const bool vlines = (uint64_t)nnz + n_nodes < 0xffffffffull && !getenv("PECANPY_AMD_NO_VLINES");
     const uint32_t n_lines = vlines ? nnz + n_nodes : nnz;
@@ -543,55 +502,43 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     (void)hipMemGetInfo(&free_b, &total_b);
     stamp("hipMemGetInfo");
     const uint64_t line_bytes = (uint64_t)n_lines * sizeof(pw::ELine) + 64;
-    if (g->gd->d_lines && pre_bytes != line_bytes) no_index();   // (cannot happen: the same formula sized it)
-    if (!g->gd->d_lines && line_bytes > free_b / 2) return 0;
-    pw::LaneBuildItem *d_small = nullptr, *d_large = nullptr;
-    uint32_t *d_segcnt = nullptr;
-    uint64_t *d_tiles = nullptr, *d_etiles = nullptr;
-    uint32_t *d_log = nullptr, *d_seglo = nullptr, *d_vm0 = nullptr;    // LOGGED build (below)
-    unsigned long long *d_logoff = nullptr;
+    if (g->gd->d_lines.p && g->gd->d_lines.bytes() != line_bytes) g->gd->d_lines.release();   // (cannot happen: the same formula sized it)
+    if (!g->gd->d_lines.p && line_bytes > free_b / 2) return 0;
+    struct Scratch {   // of the build: released in one assignment, before the last stamp
+        DevBuf<pw::LaneBuildItem> d_small, d_large;
+        DevBuf<uint32_t> d_segcnt;
+        DevBuf<uint64_t> d_tiles, d_etiles;
+        DevBuf<uint32_t> d_log, d_seglo, d_vm0;    // LOGGED build (below)
+        DevBuf<unsigned long long> d_logoff;
+    } sc;
     const uint64_t n_tiles = ((uint64_t)n_lines + pw::CL_TILE - 1) / pw::CL_TILE;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_small, (void *)d_large, (void *)d_segcnt, (void *)d_tiles, (void *)d_etiles, (void *)d_log,
-                        (void *)d_seglo, (void *)d_vm0, (void *)d_logoff})
-            if (q) (void)hipFree(q);
-    };
-    auto drop = [&](int rc) {   // no lane index
-        cleanup();
-        if (g->gd->d_lines) (void)hipFree(g->gd->d_lines);
-        if (g->gd->d_clist) (void)hipFree(g->gd->d_clist);
-        g->gd->d_lines = nullptr;
-        g->gd->d_clist = nullptr;
-        (void)hipGetLastError();
-        return rc;
-    };
-    hipError_t e = g->gd->d_lines ? hipSuccess : hipMalloc((void **)&g->gd->d_lines, line_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_small, sizeof(pw::LaneBuildItem) * (small.size() + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_large, sizeof(pw::LaneBuildItem) * (large.size() + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_segcnt, sizeof(uint32_t) * (size_t)(segcnt_total + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, sizeof(uint64_t) * (n_tiles + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_etiles, sizeof(uint64_t) * (n_tiles + 1));
+    hipError_t e = g->gd->d_lines.p ? hipSuccess : g->gd->d_lines.alloc((size_t)n_lines + 1);
+    if (e == hipSuccess) e = sc.d_small.alloc(small.size() + 1);
+    if (e == hipSuccess) e = sc.d_large.alloc(large.size() + 1);
+    if (e == hipSuccess) e = sc.d_segcnt.alloc((size_t)(segcnt_total + 1));
+    if (e == hipSuccess) e = sc.d_tiles.alloc(n_tiles + 1);
+    if (e == hipSuccess) e = sc.d_etiles.alloc(n_tiles + 1);
     if (e == hipSuccess && !small.empty())
-        e = hipMemcpyAsync(d_small, small.data(), sizeof(pw::LaneBuildItem) * small.size(), hipMemcpyHostToDevice, g->stream);
+        e = hipMemcpyAsync(sc.d_small.p, small.data(), sizeof(pw::LaneBuildItem) * small.size(), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess && !large.empty())
-        e = hipMemcpyAsync(d_large, large.data(), sizeof(pw::LaneBuildItem) * large.size(), hipMemcpyHostToDevice, g->stream);
+        e = hipMemcpyAsync(sc.d_large.p, large.data(), sizeof(pw::LaneBuildItem) * large.size(), hipMemcpyHostToDevice, g->stream);
     if (e != hipSuccess) return drop(e == hipErrorOutOfMemory ? 0 : fail(PW_ERR_HIP, std::string("lane index: ") + hipGetErrorString(e)));
     stamp("hipMalloc + item upload");
     pw::CsrDev c = csr_dev(g);
     pw::LaneBuildArgs ba;
-    ba.indptr = g->gd->d_indptr;
-    ba.indices = g->gd->d_indices;
-    ba.lines = g->gd->d_lines;
+    ba.indptr = g->gd->d_indptr.p;
+    ba.indices = g->gd->d_indices.p;
+    ba.lines = g->gd->d_lines.p;
     ba.clist = nullptr;
-    ba.segcnt = d_segcnt;
+    ba.segcnt = sc.d_segcnt.p;
     ba.max_len = 0xffffffffu;
     ba.log = nullptr;
     ba.log_off = nullptr;
     ba.seglo = nullptr;
     ba.logged = 0;
     INDEX_KERNELS_BEGIN(g);
-    hipLaunchKernelGGL(pw::eline_init_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, c, d_edge_row, g->gd->d_lines);
-    if (vlines) hipLaunchKernelGGL(pw::vline_init_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, c, g->gd->d_lines);
+    hipLaunchKernelGGL(pw::eline_init_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, c, d_edge_row, g->gd->d_lines.p);
+    if (vlines) hipLaunchKernelGGL(pw::vline_init_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, c, g->gd->d_lines.p);
     const unsigned vgrid = (unsigned)(((uint64_t)n_nodes * pw::WAVE + 255) / 256);
     // LOGGED build (round 5; walk_lanes.hip.h: LaneBuildArgs): the COUNT pass keeps its matches in a log -- one block of d_k
     // four-byte slots per pair, the pair's upper bound: 50 GB of address space at RMAT-22 of which the matches touch 5 -- and
@@ -607,34 +554,34 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     bool logged = false;
     const uint64_t nnz_tiles = ((uint64_t)nnz + pw::CL_TILE - 1) / pw::CL_TILE;
     if (env_on("PECANPY_AMD_INDEX_LOGGED") && !has_loop) {   // (self loops: the two-pass build)
-        e = hipMalloc((void **)&d_logoff, sizeof(unsigned long long) * ((size_t)nnz + 1));
+        e = sc.d_logoff.alloc((size_t)nnz + 1);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pw::log_tile_sums_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, g->gd->d_indptr,
-                               d_edge_row, nnz, d_tiles);
-            hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, nnz_tiles);
-            hipLaunchKernelGGL(pw::log_offsets_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, g->gd->d_indptr,
-                               d_edge_row, nnz, d_tiles, d_logoff);
-            e = hipMemcpyAsync(&log_slots, d_tiles + nnz_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+            hipLaunchKernelGGL(pw::log_tile_sums_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, g->gd->d_indptr.p,
+                               d_edge_row, nnz, sc.d_tiles.p);
+            hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, sc.d_tiles.p, nnz_tiles);
+            hipLaunchKernelGGL(pw::log_offsets_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, g->gd->d_indptr.p,
+                               d_edge_row, nnz, sc.d_tiles.p, sc.d_logoff.p);
+            e = hipMemcpyAsync(&log_slots, sc.d_tiles.p + nnz_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
         }
         INDEX_KERNELS_END(g);                       // (the allocations below are host time, not index-kernel time)
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
         size_t free_now = 0, total_now = 0;
         (void)hipMemGetInfo(&free_now, &total_now);
         if (e == hipSuccess && log_slots && (log_slots + 64) * sizeof(uint32_t) <= free_now / 3) {
-            e = hipMalloc((void **)&d_log, (log_slots + 64) * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMalloc((void **)&d_seglo, sizeof(uint32_t) * (size_t)(segcnt_total + 1));
-            if (e == hipSuccess) e = hipMalloc((void **)&d_vm0, sizeof(uint32_t) * ((size_t)n_nodes + 1));
-            if (e == hipSuccess) e = hipMemcpyAsync(d_vm0, items.vm0.data(), sizeof(uint32_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, g->stream);
+            e = sc.d_log.alloc(log_slots + 64);
+            if (e == hipSuccess) e = sc.d_seglo.alloc((size_t)(segcnt_total + 1));
+            if (e == hipSuccess) e = sc.d_vm0.alloc((size_t)n_nodes + 1);
+            if (e == hipSuccess) e = hipMemcpyAsync(sc.d_vm0.p, items.vm0.data(), sizeof(uint32_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, g->stream);
             logged = e == hipSuccess;
         }
         if (!logged) {   // (no room: the two passes)
             (void)hipGetLastError();
-            for (void **q : {(void **)&d_log, (void **)&d_seglo, (void **)&d_vm0, (void **)&d_logoff})
-                if (*q) { (void)hipFree(*q); *q = nullptr; }
+            for (DevBuf<uint32_t> *q : {&sc.d_log, &sc.d_seglo, &sc.d_vm0}) q->release();
+            sc.d_logoff.release();
         } else {
-            ba.log = d_log;
-            ba.log_off = d_logoff;
-            ba.seglo = d_seglo;
+            ba.log = sc.d_log.p;
+            ba.log_off = sc.d_logoff.p;
+            ba.seglo = sc.d_seglo.p;
         }
         stamp("log offsets + allocation");
         INDEX_KERNELS_BEGIN(g);
@@ -647,30 +594,30 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
             // LDS serves EIGHT wavefronts per SIMD instead of four (26-32 VGPRs: the registers allow it).  RMAT-22, same box:
             // index kernels 170.6 -> 117.0 ms with 512 lanes, 122.7 with 1024; COUNT + FILL of the long rows 130 -> ~77 ms.
             const dim3 lg((unsigned)large.size());
-            if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, true>), lg, dim3(512), 0, g->stream, ba, d_large);
-            else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false, true>), lg, dim3(512), 0, g->stream, ba, d_large);
-            else hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false>), lg, dim3(512), 0, g->stream, ba, d_large);
+            if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, true>), lg, dim3(512), 0, g->stream, ba, sc.d_large.p);
+            else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false, true>), lg, dim3(512), 0, g->stream, ba, sc.d_large.p);
+            else hipLaunchKernelGGL((pw::lane_lists_kernel<512, pw::LB_SEG, false>), lg, dim3(512), 0, g->stream, ba, sc.d_large.p);
         }
         if (!small.empty()) {
-            if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, true>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, d_small);
-            else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, false, true>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, d_small);
-            else hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, false>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, d_small);
+            if (fill) hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, true>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, sc.d_small.p);
+            else if (logged) hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, false, true>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, sc.d_small.p);
+            else hipLaunchKernelGGL((pw::lane_lists_kernel<64, pw::LB_SMALL, false>), dim3((unsigned)small.size()), dim3(64), 0, g->stream, ba, sc.d_small.p);
         }
         if (vlines) {
-            if (fill) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines, g->gd->d_clist);
-            else hipLaunchKernelGGL(pw::vline_lists_kernel<false>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines, (uint8_t *)nullptr);
+            if (fill) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines.p, g->gd->d_clist.p);
+            else hipLaunchKernelGGL(pw::vline_lists_kernel<false>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines.p, (uint8_t *)nullptr);
         }
     };
     lists(false);
     uint64_t units = 0, entries = 0;
     auto offsets = [&](uint32_t max_len) -> hipError_t {   // list offsets (16-byte units) of the lists of at most max_len entries
-        hipLaunchKernelGGL(pw::clist_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, n_lines, nnz, d_tiles, d_etiles, max_len);
-        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_etiles, n_tiles);
-        hipLaunchKernelGGL(pw::clist_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, n_lines, d_tiles, max_len);
+        hipLaunchKernelGGL(pw::clist_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, n_lines, nnz, sc.d_tiles.p, sc.d_etiles.p, max_len);
+        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, sc.d_tiles.p, n_tiles);
+        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, sc.d_etiles.p, n_tiles);
+        hipLaunchKernelGGL(pw::clist_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, n_lines, sc.d_tiles.p, max_len);
         hipError_t e2 = hipGetLastError();
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&units, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&entries, d_etiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&units, sc.d_tiles.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&entries, sc.d_etiles.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
         return e2;
     };
     e = offsets(0xffffffffu);
@@ -689,19 +636,19 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     uint32_t max_len = 0xffffffffu;
     if (units * 16 + 64 > budget || units >= 0xffffffffull) {
         const uint32_t HL = 1u << 17;
-        unsigned long long *d_hist = nullptr;
+        DevBuf<unsigned long long> d_hist;
         std::vector<unsigned long long> hist(HL);
-        e = hipMalloc((void **)&d_hist, sizeof(unsigned long long) * HL);
-        if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, sizeof(unsigned long long) * HL, g->stream);
+        e = d_hist.alloc(HL);
+        if (e == hipSuccess) e = hipMemsetAsync(d_hist.p, 0, sizeof(unsigned long long) * HL, g->stream);
         if (e == hipSuccess) {
             INDEX_KERNELS_BEGIN(g);
             hipLaunchKernelGGL(pw::clist_length_hist_kernel, dim3((unsigned)(((uint64_t)n_lines + 255) / 256)), dim3(256), 0, g->stream,
-                               g->gd->d_lines, n_lines, d_hist, HL);
+                               g->gd->d_lines.p, n_lines, d_hist.p, HL);
             e = hipGetLastError();
             INDEX_KERNELS_END(g);
         }
-        if (e == hipSuccess) e = hipMemcpy(hist.data(), d_hist, sizeof(unsigned long long) * HL, hipMemcpyDeviceToHost);
-        if (d_hist) (void)hipFree(d_hist);
+        if (e == hipSuccess) e = hipMemcpy(hist.data(), d_hist.p, sizeof(unsigned long long) * HL, hipMemcpyDeviceToHost);
+        d_hist.release();
         if (e != hipSuccess) return drop(fail(PW_ERR_HIP, std::string("lane index (length histogram): ") + hipGetErrorString(e)));
         const uint64_t cap_units = std::min<uint64_t>(budget > 64 ? (budget - 64) / 16 : 0, 0xfffffffeull);
         uint64_t run = 0;
@@ -721,51 +668,51 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     const uint64_t list_bytes = units * 16 + 64;
     if (units >= 0xffffffffull || list_bytes > free_b - free_b / 8) return drop(0);
     if (has_loop && max_len != 0xffffffffu) return drop(0);   // (loop_fix_kernel edits stored lists: no partial index with self loops)
-    e = hipMalloc((void **)&g->gd->d_clist, list_bytes);
+    e = g->gd->d_clist.alloc(list_bytes);
     if (e != hipSuccess) return drop(e == hipErrorOutOfMemory ? 0 : fail(PW_ERR_HIP, std::string("lane index (lists): ") + hipGetErrorString(e)));
     stamp("hipMalloc of the lists");
-    ba.clist = g->gd->d_clist;
+    ba.clist = g->gd->d_clist.p;
     ba.max_len = max_len;
     INDEX_KERNELS_BEGIN(g);
     if (logged) {   // the logged matches to their places; the FILL pass is left with the pairs of rows beyond 65536 entries
-        hipLaunchKernelGGL(pw::lane_scatter_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, ba, d_edge_row, d_vm0, nnz);
+        hipLaunchKernelGGL(pw::lane_scatter_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, ba, d_edge_row, sc.d_vm0.p, nnz);
         ba.logged = 1u;
-        if (vlines) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines, g->gd->d_clist);
+        if (vlines) hipLaunchKernelGGL(pw::vline_lists_kernel<true>, dim3(vgrid), dim3(256), 0, g->stream, c, g->gd->d_lines.p, g->gd->d_clist.p);
     } else
     lists(true);
     unsigned long long loop_removed = 0;
     if (has_loop) {   // self loops: prev's own position leaves the lists of the entries whose source has one (walk_lanes.hip.h)
-        uint32_t *d_self = nullptr;
-        unsigned long long *d_removed = nullptr;
+        DevBuf<uint32_t> d_self;
+        DevBuf<unsigned long long> d_removed;
         const size_t words = ((size_t)n_nodes + 31) / 32 + 1;
-        e = hipMalloc((void **)&d_self, sizeof(uint32_t) * words);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_removed, sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemsetAsync(d_self, 0, sizeof(uint32_t) * words, g->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, sizeof(unsigned long long), g->stream);
+        e = d_self.alloc(words);
+        if (e == hipSuccess) e = d_removed.alloc(1);
+        if (e == hipSuccess) e = hipMemsetAsync(d_self.p, 0, sizeof(uint32_t) * words, g->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_removed.p, 0, sizeof(unsigned long long), g->stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pw::self_loop_bits_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->d_indices, n_nodes, d_self);
+            hipLaunchKernelGGL(pw::self_loop_bits_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->d_indices.p, n_nodes, d_self.p);
             hipLaunchKernelGGL(pw::loop_fix_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream, d_edge_row,
-                               (const uint32_t *)d_self, g->gd->d_lines, g->gd->d_clist, nnz, d_removed);
+                               (const uint32_t *)d_self.p, g->gd->d_lines.p, g->gd->d_clist.p, nnz, d_removed.p);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(&loop_removed, d_removed, sizeof(loop_removed), hipMemcpyDeviceToHost, g->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&loop_removed, d_removed.p, sizeof(loop_removed), hipMemcpyDeviceToHost, g->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-        if (d_self) (void)hipFree(d_self);
-        if (d_removed) (void)hipFree(d_removed);
+        d_self.release();
+        d_removed.release();
         if (e != hipSuccess) return drop(fail(PW_ERR_HIP, std::string("lane index (self loops): ") + hipGetErrorString(e)));
     }
     {   // (logged build: lane_scatter_kernel wrote the pivots of the CSR entries' lists with the lists; the overflow lines are left)
         const uint32_t first = logged ? nnz : 0u;
         if (n_lines > first)
             hipLaunchKernelGGL(pw::eline_pivots_kernel, dim3((unsigned)(((uint64_t)(n_lines - first) + 255) / 256)), dim3(256), 0, g->stream,
-                               g->gd->d_lines, g->gd->d_clist, n_lines, first);
+                               g->gd->d_lines.p, g->gd->d_clist.p, n_lines, first);
     }
     e = hipGetLastError();
     INDEX_KERNELS_END(g);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e != hipSuccess) return drop(fail(PW_ERR_HIP, std::string("lane index (fill pass): ") + hipGetErrorString(e)));
     stamp("fill pass + pivots");
-    cleanup();
+    sc = Scratch{};
     stamp("hipFree of the scratch");
     g->gd->n_clist = entries - loop_removed;
     g->gd->list_max_len = max_len;
@@ -817,40 +764,39 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     // costs ~120 ms (EXPERIMENTS.md, rounds 5-6); it runs beside the validation / membership kernels too.
     struct Pre {
         std::thread t_up, t_lines;
-        void *indptr = nullptr, *indices = nullptr, *data = nullptr;   // (1): handed to g once t_up is joined
+        DevBuf<uint32_t> indptr, indices;   // (1): moved into g once t_up is joined
+        DevBuf<void> data;
         hipError_t err = hipSuccess;
-        void *lines = nullptr; uint64_t line_bytes = 0; bool lines_taken = false, csr_taken = false;   // (2)
-        ~Pre() {
+        DevBuf<pw::ELine> lines; size_t n_lines = 0;   // (2): moved into g once t_lines is joined
+        ~Pre() {   // (the threads write the members: joined before those go)
             if (t_up.joinable()) t_up.join();
             if (t_lines.joinable()) t_lines.join();
-            if (lines && !lines_taken) (void)hipFree(lines);
-            if (!csr_taken) for (void *q : {indptr, indices, data}) if (q) (void)hipFree(q);
         }
     } pre;
     auto up_work = [&pre, device, indptr, indices, data, n_nodes, nnz, d_csr]() {
         if ((pre.err = hipSetDevice(device)) != hipSuccess) return;
-        auto up1 = [&](void **dst, const void *src, const void *d_src, size_t bytes) {
+        auto up1 = [&](auto &dst, const void *src, const void *d_src, size_t n) {
             if (pre.err != hipSuccess) return;
-            pre.err = hipMalloc(dst, bytes ? bytes : 4);
-            if (pre.err == hipSuccess && bytes)
-                pre.err = d_src ? hipMemcpy(*dst, d_src, bytes, hipMemcpyDeviceToDevice) : hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+            pre.err = dst.alloc(n);
+            if (pre.err == hipSuccess && n)
+                pre.err = d_src ? hipMemcpy(dst.p, d_src, dst.bytes(), hipMemcpyDeviceToDevice) : hipMemcpy(dst.p, src, dst.bytes(), hipMemcpyHostToDevice);
         };
-        up1(&pre.indptr, indptr, d_csr ? d_csr[0] : nullptr, sizeof(uint32_t) * ((size_t)n_nodes + 1));
-        up1(&pre.indices, indices, d_csr ? d_csr[1] : nullptr, sizeof(uint32_t) * (size_t)nnz);
-        if (data) up1(&pre.data, data, d_csr ? d_csr[2] : nullptr, sizeof(float) * (size_t)nnz);
+        up1(pre.indptr, indptr, d_csr ? d_csr[0] : nullptr, (size_t)n_nodes + 1);
+        up1(pre.indices, indices, d_csr ? d_csr[1] : nullptr, (size_t)nnz);
+        if (data) up1(pre.data, data, d_csr ? d_csr[2] : nullptr, sizeof(float) * (size_t)nnz);
         // (a device-to-device hipMemcpy may return before the copy has run; the handle's streams do not wait for the null stream)
         if (d_csr && pre.err == hipSuccess) pre.err = hipStreamSynchronize(nullptr);
     };
     try { pre.t_up = std::thread(up_work); } catch (const std::system_error &) { up_work(); }   // (thread limit: on this thread)
     if (nnz && !getenv("PECANPY_AMD_NO_LAZY") && !getenv("PECANPY_AMD_NO_PREALLOC")) {
         const bool vl = (uint64_t)nnz + n_nodes < 0xffffffffull && !getenv("PECANPY_AMD_NO_VLINES");
-        pre.line_bytes = (uint64_t)(vl ? nnz + n_nodes : nnz) * sizeof(pw::ELine) + 64;
+        pre.n_lines = (size_t)(vl ? nnz + n_nodes : nnz) + 1;   // (build_lane_index's size: one line of slack)
         try {
             pre.t_lines = std::thread([&pre, device]() {
                 size_t free_b = 0, total_b = 0;
                 if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;
-                if (pre.line_bytes > free_b / 2) return;               // (build_lane_index's rule: no lane index then)
-                if (hipMalloc(&pre.lines, pre.line_bytes) != hipSuccess) { pre.lines = nullptr; (void)hipGetLastError(); }
+                if (pre.n_lines * sizeof(pw::ELine) > free_b / 2) return;   // (build_lane_index's rule: no lane index then)
+                (void)pre.lines.alloc(pre.n_lines);
             });
         } catch (const std::system_error &) {}   // (thread limit: build_lane_index allocates)
     }
@@ -880,60 +826,57 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     foff[n_nodes] = (uint32_t)frun;
     off[n_nodes] = trun;
     g->gd->max_degree = md;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        HIP_TRY(hipMalloc(dst, bytes ? bytes : 4));
-        if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    auto up = [&](auto &dst, const void *src, size_t n) -> int {
+        HIP_TRY(dst.alloc(n));
+        if (n) HIP_TRY(hipMemcpy(dst.p, src, dst.bytes(), hipMemcpyHostToDevice));
         return 0;
     };
     // the CSR arrays, uploaded by the helper thread meanwhile (the lines' allocation may still be running: joined further down)
     if (pre.t_up.joinable()) pre.t_up.join();
     if (pre.err != hipSuccess) { pw_graph_destroy(g); return fail(pre.err == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("CSR upload: ") + hipGetErrorString(pre.err)); }
-    g->gd->d_indptr = (uint32_t *)pre.indptr; g->gd->d_indices = (uint32_t *)pre.indices; g->gd->d_data = pre.data;
-    pre.csr_taken = true;
+    g->gd->d_indptr = std::move(pre.indptr); g->gd->d_indices = std::move(pre.indices); g->gd->d_data = std::move(pre.data);
     stamp("host pass + H2D of the CSR");
 
     // ---- device side: validation, weight scan, membership index ------------------------------------------------
-    uint32_t *d_edge_row = nullptr;
-    unsigned long long *d_flags = nullptr;   // [0] first entry with index >= n_nodes  [1] first entry out of order
+    DevBuf<uint32_t> d_edge_row;
+    DevBuf<unsigned long long> d_flags;      // [0] first entry with index >= n_nodes  [1] first entry out of order
                                              // [2] some weight != 1.0f  [3] self loop present  [4] some weight negative / NaN / inf
     auto bail = [&](int code, const std::string &msg) {
-        if (d_edge_row) (void)hipFree(d_edge_row);
-        if (d_flags) (void)hipFree(d_flags);
         pw_graph_destroy(g);
         return fail(code, msg);
     };
-    hipError_t e = hipMalloc((void **)&d_edge_row, sizeof(uint32_t) * (size_t)(nnz ? nnz : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_flags, 5 * sizeof(unsigned long long));
+    hipError_t e = d_edge_row.alloc(nnz);
+    if (e == hipSuccess) e = d_flags.alloc(5);
     unsigned long long h_flags[5] = {~0ull, ~0ull, 0ull, 0ull, 0ull};
-    if (e == hipSuccess) e = hipMemcpyAsync(d_flags, h_flags, sizeof(h_flags), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_flags.p, h_flags, sizeof(h_flags), hipMemcpyHostToDevice, g->stream);
     g->gd->index_build_ms = 0;
     INDEX_KERNELS_BEGIN(g);
     if (e == hipSuccess && nnz) {
-        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr, n_nodes, d_edge_row);
+        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr.p, n_nodes, d_edge_row.p);
         hipLaunchKernelGGL(pw::csr_validate_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream,
-                           g->gd->d_indptr, g->gd->d_indices, (const float *)g->gd->d_data, d_edge_row, n_nodes, nnz, d_flags);
+                           g->gd->d_indptr.p, g->gd->d_indices.p, (const float *)g->gd->d_data.p, d_edge_row.p, n_nodes, nnz, d_flags.p);
         e = hipGetLastError();
     }
     INDEX_KERNELS_END(g);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, d_flags, sizeof(h_flags), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, d_flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("CSR validation: ") + hipGetErrorString(e));
     if (h_flags[0] != ~0ull) {
         uint32_t row = 0;
-        (void)hipMemcpy(&row, d_edge_row + h_flags[0], sizeof(row), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(&row, d_edge_row.p + h_flags[0], sizeof(row), hipMemcpyDeviceToHost);
         return bail(PW_ERR_INVALID, "CSR entry " + std::to_string(h_flags[0]) + " (row " + std::to_string(row) +
                                         "): column index >= n_nodes");
     }
     if (h_flags[1] != ~0ull) {
         uint32_t row = 0;
-        (void)hipMemcpy(&row, d_edge_row + h_flags[1], sizeof(row), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(&row, d_edge_row.p + h_flags[1], sizeof(row), hipMemcpyDeviceToHost);
         return bail(PW_ERR_INVALID, "row " + std::to_string(row) + " (CSR entry " + std::to_string(h_flags[1]) +
                                         "): column indices must be strictly ascending within a row (sorted, no duplicates), "
                                         "as the reference's to_csr produces them (graph.py:336)");
     }
     stamp("validation kernels");
     g->gd->unit = !(data && h_flags[2]);
-    if (g->gd->unit && g->gd->d_data) { (void)hipFree(g->gd->d_data); g->gd->d_data = nullptr; }   // unit weights are never read
+    if (g->gd->unit) g->gd->d_data.release();   // unit weights are never read
     const bool has_loop = h_flags[3] != 0;
     // A negative, NaN or infinite weight: the reference turns it into meaningless "probabilities" (w / w.sum(), cumsum, searchsorted:
     // pecanpy.py:556-557) without complaint; the exact scans here (wave kernel: monotone partial sums; weighted lane form: a float64
@@ -943,26 +886,24 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
         return bail(PW_ERR_INVALID, "edge weights must be finite and >= 0 (a negative, NaN or infinite weight makes the reference's "
                                     "transition probabilities w / w.sum() meaningless; this library does not reproduce them)");
 
-    rc = up((void **)&g->gd->d_foff, foff.data(), sizeof(uint32_t) * foff.size());
-    if (!rc) rc = up((void **)&g->gd->d_tab_off, off.data(), sizeof(uint64_t) * off.size());
-    if (rc) { if (d_edge_row) (void)hipFree(d_edge_row); (void)hipFree(d_flags); pw_graph_destroy(g); return rc; }
-    e = hipMalloc((void **)&g->gd->d_fbits, sizeof(uint64_t) * (frun ? frun : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_kf, sizeof(uint2) * (size_t)(nnz ? nnz : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_slots, sizeof(uint64_t) * (trun ? trun : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_vrec, sizeof(uint4) * ((size_t)n_nodes + 1));
-    if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_fbits, 0, sizeof(uint64_t) * (frun ? frun : 1), g->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_slots, 0xff, sizeof(uint64_t) * (trun ? trun : 1), g->stream);
+    rc = up(g->gd->d_foff, foff.data(), foff.size());
+    if (!rc) rc = up(g->gd->d_tab_off, off.data(), off.size());
+    if (rc) { pw_graph_destroy(g); return rc; }
+    e = g->gd->d_fbits.alloc(frun ? frun : 1);   // (at least one word each: the memsets below clear what was allocated)
+    if (e == hipSuccess) e = g->gd->d_kf.alloc(nnz);
+    if (e == hipSuccess) e = g->gd->d_slots.alloc(trun ? trun : 1);
+    if (e == hipSuccess) e = g->gd->d_vrec.alloc((size_t)n_nodes + 1);
+    if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_fbits.p, 0, g->gd->d_fbits.bytes(), g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_slots.p, 0xff, g->gd->d_slots.bytes(), g->stream);
     if (e != hipSuccess) return bail(PW_ERR_NOMEM, std::string("membership index: ") + hipGetErrorString(e));
     g->gd->index_bytes = sizeof(uint64_t) * (frun + trun) + sizeof(uint2) * (uint64_t)nnz + sizeof(uint4) * ((uint64_t)n_nodes + 1);
-    g->gd->fbits_words = frun;
-    g->gd->slot_words = trun;
     INDEX_KERNELS_BEGIN(g);
-    hipLaunchKernelGGL(pw::vrec_build_kernel, dim3((n_nodes + 256) / 256), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->d_foff,
-                       g->gd->d_tab_off, n_nodes, g->gd->d_vrec);
+    hipLaunchKernelGGL(pw::vrec_build_kernel, dim3((n_nodes + 256) / 256), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->d_foff.p,
+                       g->gd->d_tab_off.p, n_nodes, g->gd->d_vrec.p);
     if (n_nodes && nnz)
         hipLaunchKernelGGL(pw::membership_build_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream,
-                           g->gd->d_indptr, g->gd->d_indices, d_edge_row, g->gd->d_foff, g->gd->d_tab_off, (unsigned long long *)g->gd->d_fbits, g->gd->d_kf,
-                           (unsigned long long *)g->gd->d_slots, nnz, 4294967296.0 / (double)nnz);
+                           g->gd->d_indptr.p, g->gd->d_indices.p, d_edge_row.p, g->gd->d_foff.p, g->gd->d_tab_off.p, (unsigned long long *)g->gd->d_fbits.p, g->gd->d_kf.p,
+                           (unsigned long long *)g->gd->d_slots.p, nnz, 4294967296.0 / (double)nnz);
     e = hipGetLastError();
     INDEX_KERNELS_END(g);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
@@ -978,18 +919,16 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
         g->gd->lanes_off = read_lane_switches().no_lanes;
         item_thread.join();
         if (pre.t_lines.joinable()) pre.t_lines.join();
-        pre.lines_taken = pre.lines != nullptr;
-        rc = build_lane_index(g, items, d_edge_row, has_loop, pre.lines, pre.line_bytes);
-        if (rc) { (void)hipFree(d_edge_row); (void)hipFree(d_flags); pw_graph_destroy(g); return rc; }
+        g->gd->d_lines = std::move(pre.lines);
+        rc = build_lane_index(g, items, d_edge_row.p, has_loop);
+        if (rc) { pw_graph_destroy(g); return rc; }
     }
     (void)hipStreamSynchronize(g->stream);
     stamp("lane index");
     g->gd->create_wall_ms = (now() - t_begin) * 1e3;
     // a PARTIAL index keeps the source vertex of every CSR entry (4 bytes per entry): lanes_eager_kernel reads the vertex a
     // parked step came from there instead of bisecting indptr for it (22 dependent loads per step)
-    if (g->gd->d_lines && g->gd->list_max_len != 0xffffffffu && !g->gd->d_wedge_row) g->gd->d_wedge_row = d_edge_row;
-    else (void)hipFree(d_edge_row);
-    (void)hipFree(d_flags);
+    if (g->gd->d_lines.p && g->gd->list_max_len != 0xffffffffu) g->gd->d_wedge_row = std::move(d_edge_row);
     *out = g;
     return PW_OK;
 }
@@ -1004,15 +943,13 @@ struct pw_csr_dev {
     int device = 0;
     uint64_t n_nodes = 0, nnz = 0, insertions = 0, dropped = 0;
     double build_ms = 0;
-    uint32_t *d_indptr = nullptr, *d_indices = nullptr;
-    float *d_data = nullptr;   // NULL: no weights were given (every weight 1.0)
+    DevBuf<uint32_t> d_indptr, d_indices;
+    DevBuf<float> d_data;      // empty: no weights were given (every weight 1.0)
 };
 
 PW_EXPORT void pw_csr_dev_destroy(pw_csr_dev *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void *q : {(void *)c->d_indptr, (void *)c->d_indices, (void *)c->d_data})
-        if (q) (void)hipFree(q);
     delete c;
 }
 
@@ -1055,30 +992,23 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const unsigned stride_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)prop.multiProcessorCount * 16));
 
-    // everything the call allocates: scratch freed on every way out, the result's arrays only on failure
+    // what the call holds beside its scratch buffers: the events of the three kernel spans (begin / end), and the result until it is handed out
     struct Mem {
-        std::vector<void *> scratch;
         pw_csr_dev *res = nullptr;
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of the three kernel spans
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         ~Mem() {
-            for (void *q : scratch) if (q) (void)hipFree(q);
             for (auto &e : ev) if (e) (void)hipEventDestroy(e);
             if (res) pw_csr_dev_destroy(res);
         }
     } mem;
     uint64_t scratch_bytes = 0;
-    auto alloc = [&](void **p, uint64_t bytes, const char *what) -> int {
-        *p = nullptr;
-        hipError_t e = hipMalloc(p, bytes ? bytes : 4);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            return fail(PW_ERR_NOMEM, std::string("pw_coo_to_csr_device: ") + what + " (" + std::to_string(bytes) + " bytes, " +
+    auto alloc = [&](auto &buf, uint64_t n, const char *what) -> int {
+        const hipError_t e = buf.alloc(n);
+        if (e != hipSuccess)
+            return fail(PW_ERR_NOMEM, std::string("pw_coo_to_csr_device: ") + what + " (" + std::to_string(n * sizeof(*buf.p)) + " bytes, " +
                                           std::to_string(scratch_bytes) + " bytes of scratch before it) does not fit in device memory: " +
                                           hipGetErrorString(e));
-        }
-        mem.scratch.push_back(*p);
-        scratch_bytes += bytes;
+        scratch_bytes += buf.bytes();
         return 0;
     };
     // build_ms = the sum of three spans of kernels on the null stream; the allocations, the two small device-to-host reads and the
@@ -1086,10 +1016,12 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
 
     // 1. validation, kept edges, largest id
-    unsigned long long *d_flags = nullptr;
-    uint32_t *d_keep = nullptr;
-    int rc = alloc((void **)&d_flags, 4 * sizeof(unsigned long long), "flags");
-    if (!rc && d_weight) rc = alloc((void **)&d_keep, sizeof(uint32_t) * (m + 1), "kept-edge ranks");
+    DevBuf<unsigned long long> flags_buf;
+    DevBuf<uint32_t> keep_buf;
+    int rc = alloc(flags_buf, 4, "flags");
+    if (!rc && d_weight) rc = alloc(keep_buf, m + 1, "kept-edge ranks");
+    unsigned long long *const d_flags = flags_buf.p;
+    uint32_t *const d_keep = keep_buf.p;
     if (rc) return rc;
     unsigned long long h_flags[4] = {~0ull, ~0ull, 0ull, 0ull};
     HIP_TRY(hipMemcpy(d_flags, h_flags, sizeof(h_flags), hipMemcpyHostToDevice));
@@ -1117,16 +1049,19 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     const uint64_t n_waves = (n_ins + pw::RADIX_SUB - 1) / pw::RADIX_SUB;
     const uint64_t hist_elems = (uint64_t)pw::RADIX_BINS * n_waves;
     const uint64_t scan_max = std::max(std::max(hist_elems, n_ins + 1), d_weight ? m + 1 : 0);
-    uint64_t *d_keys[2] = {nullptr, nullptr};
-    float *d_w[2] = {nullptr, nullptr};
-    uint32_t *d_hist = nullptr, *d_tmp = nullptr;
-    rc = alloc((void **)&d_keys[0], sizeof(uint64_t) * (n_ins + 1), "sort keys");
-    if (!rc) rc = alloc((void **)&d_keys[1], sizeof(uint64_t) * (n_ins + 1), "sort keys (second buffer)");
-    if (!rc && d_weight) rc = alloc((void **)&d_w[0], sizeof(float) * n_ins, "sort weights");
-    if (!rc && d_weight) rc = alloc((void **)&d_w[1], sizeof(float) * n_ins, "sort weights (second buffer)");
-    if (!rc) rc = alloc((void **)&d_hist, sizeof(uint32_t) * hist_elems, "radix histograms");
-    if (!rc) rc = alloc((void **)&d_tmp, sizeof(uint32_t) * scan_tmp_elems(scan_max), "scan tile sums");
+    DevBuf<uint64_t> keys_buf[2];
+    DevBuf<float> w_buf[2];
+    DevBuf<uint32_t> hist_buf, tmp_buf;
+    rc = alloc(keys_buf[0], n_ins + 1, "sort keys");
+    if (!rc) rc = alloc(keys_buf[1], n_ins + 1, "sort keys (second buffer)");
+    if (!rc && d_weight) rc = alloc(w_buf[0], n_ins, "sort weights");
+    if (!rc && d_weight) rc = alloc(w_buf[1], n_ins, "sort weights (second buffer)");
+    if (!rc) rc = alloc(hist_buf, hist_elems, "radix histograms");
+    if (!rc) rc = alloc(tmp_buf, scan_tmp_elems(scan_max), "scan tile sums");
     if (rc) return rc;
+    uint64_t *d_keys[2] = {keys_buf[0].p, keys_buf[1].p};   // (the sort swaps the two views; the owners stay put)
+    float *d_w[2] = {w_buf[0].p, w_buf[1].p};
+    uint32_t *const d_hist = hist_buf.p, *const d_tmp = tmp_buf.p;
     HIP_TRY(hipEventRecord(mem.ev[2], nullptr));
     if (d_weight && dropped) {
         HIP_TRY(hipMemsetAsync(d_keep + m, 0, sizeof(uint32_t), nullptr));
@@ -1170,24 +1105,22 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     pw_csr_dev *c = mem.res;
     c->device = device;
     c->n_nodes = n; c->nnz = nnz; c->insertions = n_ins; c->dropped = dropped;
-    auto alloc_out = [&](void **p, uint64_t bytes, const char *what) -> int {
-        hipError_t e = hipMalloc(p, bytes ? bytes : 4);
+    auto alloc_out = [&](auto &buf, uint64_t n, const char *what) -> int {
+        const hipError_t e = buf.alloc(n);
         if (e == hipSuccess) return 0;
-        (void)hipGetLastError();
-        *p = nullptr;
-        return fail(PW_ERR_NOMEM, std::string("pw_coo_to_csr_device: ") + what + " (" + std::to_string(bytes) + " bytes beside " +
+        return fail(PW_ERR_NOMEM, std::string("pw_coo_to_csr_device: ") + what + " (" + std::to_string(n * sizeof(*buf.p)) + " bytes beside " +
                                       std::to_string(scratch_bytes) + " bytes of scratch) does not fit in device memory: " + hipGetErrorString(e));
     };
-    rc = alloc_out((void **)&c->d_indptr, sizeof(uint32_t) * (n + 1), "indptr");
-    if (!rc) rc = alloc_out((void **)&c->d_indices, sizeof(uint32_t) * nnz, "indices");
-    if (!rc && d_weight) rc = alloc_out((void **)&c->d_data, sizeof(float) * nnz, "data");
+    rc = alloc_out(c->d_indptr, n + 1, "indptr");
+    if (!rc) rc = alloc_out(c->d_indices, nnz, "indices");
+    if (!rc && d_weight) rc = alloc_out(c->d_data, nnz, "data");
     if (rc) return rc;
     HIP_TRY(hipEventRecord(mem.ev[4], nullptr));
     if (n_ins)
         hipLaunchKernelGGL(pw::coo_compact_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)d_w[0],
-                           n_ins, (const uint32_t *)d_pos, bits, nnz, c->d_indices, c->d_data, d_rows);
+                           n_ins, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p, d_rows);
     // 6. row offsets
-    hipLaunchKernelGGL(pw::coo_indptr_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, nullptr, (const uint32_t *)d_rows, nnz, n, c->d_indptr);
+    hipLaunchKernelGGL(pw::coo_indptr_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, nullptr, (const uint32_t *)d_rows, nnz, n, c->d_indptr.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(mem.ev[5], nullptr));
     HIP_TRY(hipEventSynchronize(mem.ev[5]));
@@ -1214,10 +1147,10 @@ PW_EXPORT int pw_csr_dev_shape(const pw_csr_dev *c, uint64_t *n_nodes, uint64_t 
 PW_EXPORT int pw_csr_dev_export(const pw_csr_dev *c, uint32_t *indptr, uint32_t *indices, float *data) {
     if (!c) return fail(PW_ERR_INVALID, "null pointer");
     HIP_TRY(hipSetDevice(c->device));
-    if (indptr) HIP_TRY(hipMemcpy(indptr, c->d_indptr, sizeof(uint32_t) * (c->n_nodes + 1), hipMemcpyDeviceToHost));
-    if (indices && c->nnz) HIP_TRY(hipMemcpy(indices, c->d_indices, sizeof(uint32_t) * c->nnz, hipMemcpyDeviceToHost));
+    if (indptr) HIP_TRY(hipMemcpy(indptr, c->d_indptr.p, sizeof(uint32_t) * (c->n_nodes + 1), hipMemcpyDeviceToHost));
+    if (indices && c->nnz) HIP_TRY(hipMemcpy(indices, c->d_indices.p, sizeof(uint32_t) * c->nnz, hipMemcpyDeviceToHost));
     if (data && c->nnz) {
-        if (c->d_data) HIP_TRY(hipMemcpy(data, c->d_data, sizeof(float) * c->nnz, hipMemcpyDeviceToHost));
+        if (c->d_data.p) HIP_TRY(hipMemcpy(data, c->d_data.p, sizeof(float) * c->nnz, hipMemcpyDeviceToHost));
         else std::fill(data, data + c->nnz, 1.0f);
     }
     return PW_OK;
@@ -1228,15 +1161,15 @@ PW_EXPORT int pw_csr_create_device(const pw_csr_dev *c, const uint32_t *h_indptr
     if (!c || !out) return fail(PW_ERR_INVALID, "null pointer");
     // the host passes of csr_create_impl (work items of the lane index, degrees, filter and table sizes) read host arrays: the
     // caller's export, or the CSR comes down once here; the handle's own device copy is made device to device
-    const void *d_csr[3] = {c->d_indptr, c->d_indices, c->d_data};
+    const void *d_csr[3] = {c->d_indptr.p, c->d_indices.p, c->d_data.p};
     if (h_indptr || h_indices || h_data) {
-        if (!h_indptr || (c->nnz && !h_indices) || (c->nnz && c->d_data && !h_data))
+        if (!h_indptr || (c->nnz && !h_indices) || (c->nnz && c->d_data.p && !h_data))
             return fail(PW_ERR_INVALID, "pw_csr_create_device: host arrays must be given together (data only for a weighted CSR) or not at all");
-        return csr_create_impl(h_indptr, h_indices, c->d_data ? h_data : nullptr, (uint32_t)c->n_nodes, (uint32_t)c->nnz, c->device, out, d_csr);
+        return csr_create_impl(h_indptr, h_indices, c->d_data.p ? h_data : nullptr, (uint32_t)c->n_nodes, (uint32_t)c->nnz, c->device, out, d_csr);
     }
     std::unique_ptr<uint32_t[]> indptr(new (std::nothrow) uint32_t[c->n_nodes + 1]), indices(new (std::nothrow) uint32_t[c->nnz ? c->nnz : 1]);
-    std::unique_ptr<float[]> data(c->d_data ? new (std::nothrow) float[c->nnz ? c->nnz : 1] : nullptr);
-    if (!indptr || !indices || (c->d_data && !data)) return fail(PW_ERR_NOMEM, "pw_csr_create_device: host copy of the CSR");
+    std::unique_ptr<float[]> data(c->d_data.p ? new (std::nothrow) float[c->nnz ? c->nnz : 1] : nullptr);
+    if (!indptr || !indices || (c->d_data.p && !data)) return fail(PW_ERR_NOMEM, "pw_csr_create_device: host copy of the CSR");
     int rc = pw_csr_dev_export(c, indptr.get(), indices.get(), data.get());
     if (rc) return rc;
     return csr_create_impl(indptr.get(), indices.get(), data.get(), (uint32_t)c->n_nodes, (uint32_t)c->nnz, c->device, out, d_csr);
@@ -1246,7 +1179,7 @@ PW_EXPORT int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t 
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
     if (build_ms) *build_ms = g->gd->index_build_ms;
     if (index_bytes) *index_bytes = g->gd->index_bytes;
-    if (lane_list_entries) *lane_list_entries = g->gd->d_lines ? g->gd->n_clist : 0;
+    if (lane_list_entries) *lane_list_entries = g->gd->d_lines.p ? g->gd->n_clist : 0;
     return PW_OK;
 }
 
@@ -1255,11 +1188,11 @@ PW_EXPORT int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t 
 // in row v of the common neighbours.
 PW_EXPORT int pw_lane_index_export(pw_graph *g, uint32_t *n_in, uint32_t *rev_pos, uint32_t *entries) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    if (!g->gd->d_lines) return fail(PW_ERR_UNSUPPORTED, "this graph has no lane index");
+    if (!g->gd->d_lines.p) return fail(PW_ERR_UNSUPPORTED, "this graph has no lane index");
     if (set_device(g)) return PW_ERR_HIP;
     const uint32_t nnz = g->gd->nnz;
     std::vector<pw::ELine> lines(nnz);
-    HIP_TRY(hipMemcpy(lines.data(), g->gd->d_lines, sizeof(pw::ELine) * (size_t)nnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lines.data(), g->gd->d_lines.p, sizeof(pw::ELine) * (size_t)nnz, hipMemcpyDeviceToHost));
     std::vector<uint64_t> off((size_t)nnz + 1, 0);
     for (uint32_t e = 0; e < nnz; e++) {
         if (n_in) n_in[e] = lines[e].n_in;
@@ -1268,20 +1201,18 @@ PW_EXPORT int pw_lane_index_export(pw_graph *g, uint32_t *n_in, uint32_t *rev_po
     }
     if (off[nnz] != g->gd->n_clist) return fail(PW_ERR_HIP, "lane index: entry count mismatch");
     if (!entries || !off[nnz]) return PW_OK;
-    uint64_t *d_off = nullptr;
-    uint32_t *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_off, sizeof(uint64_t) * off.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(uint32_t) * (size_t)off[nnz]);
-    if (e == hipSuccess) e = hipMemcpy(d_off, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice);
+    DevBuf<uint64_t> d_off;
+    DevBuf<uint32_t> d_out;
+    hipError_t e = d_off.alloc(off.size());
+    if (e == hipSuccess) e = d_out.alloc((size_t)off[nnz]);
+    if (e == hipSuccess) e = hipMemcpy(d_off.p, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pw::lane_index_export_kernel, dim3((unsigned)(((uint64_t)nnz + 255) / 256)), dim3(256), 0, g->stream,
-                           g->gd->d_lines, g->gd->d_clist, nnz, d_off, d_out);
+                           g->gd->d_lines.p, g->gd->d_clist.p, nnz, d_off.p, d_out.p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess) e = hipMemcpy(entries, d_out, sizeof(uint32_t) * (size_t)off[nnz], hipMemcpyDeviceToHost);
-    if (d_off) (void)hipFree(d_off);
-    if (d_out) (void)hipFree(d_out);
+    if (e == hipSuccess) e = hipMemcpy(entries, d_out.p, sizeof(uint32_t) * (size_t)off[nnz], hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_lane_index_export: ") + hipGetErrorString(e));
     return PW_OK;
 }
@@ -1324,22 +1255,22 @@ PW_EXPORT int pw_dense_create(const double *data, uint32_t n_nodes, int device, 
     g->gd->unit = unit;
     g->gd->dense_nonneg = nonneg;
     g->gd->words_per_row = wpr;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        HIP_TRY(hipMalloc(dst, bytes ? bytes : 8));
-        if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    auto up = [&](auto &dst, const void *src, size_t n) -> int {
+        HIP_TRY(dst.alloc(n));
+        if (n) HIP_TRY(hipMemcpy(dst.p, src, dst.bytes(), hipMemcpyHostToDevice));
         return 0;
     };
-    rc = up((void **)&g->gd->d_indptr, indptr.data(), sizeof(uint32_t) * indptr.size());
-    if (!rc) rc = up((void **)&g->gd->d_indices, cols.data(), sizeof(uint32_t) * cols.size());
-    if (!rc && !unit) rc = up((void **)&g->gd->d_data, vals.data(), sizeof(double) * vals.size());
-    if (!rc) rc = up((void **)&g->gd->d_adjbits, bits.data(), sizeof(uint64_t) * bits.size());
+    rc = up(g->gd->d_indptr, indptr.data(), indptr.size());
+    if (!rc) rc = up(g->gd->d_indices, cols.data(), cols.size());
+    if (!rc && !unit) rc = up(g->gd->d_data, vals.data(), sizeof(double) * vals.size());
+    if (!rc) rc = up(g->gd->d_adjbits, bits.data(), bits.size());
     if (!rc) {
         std::vector<uint32_t> deg(n);
         for (uint64_t i = 0; i < n; i++) {
             deg[i] = indptr[i + 1] - indptr[i];
             if (deg[i] > g->gd->max_degree) g->gd->max_degree = deg[i];
         }
-        rc = up((void **)&g->gd->d_deg, deg.data(), sizeof(uint32_t) * deg.size());
+        rc = up(g->gd->d_deg, deg.data(), deg.size());
     }
     if (rc) { pw_graph_destroy(g); return rc; }
     *out = g;
@@ -1360,18 +1291,18 @@ PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, in
     g->gd->bits_only = true;
     g->gd->words_per_row = wpr;
     const size_t bytes = sizeof(uint64_t) * (size_t)n * wpr;
-    hipError_t e = hipMalloc((void **)&g->gd->d_adjbits, bytes);
+    hipError_t e = g->gd->d_adjbits.alloc((size_t)n * wpr);
     // the copy must be ordered with the kernels of this handle's (non-blocking) stream
-    if (e == hipSuccess) e = hipMemcpyAsync(g->gd->d_adjbits, adjbits, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->gd->d_adjbits.p, adjbits, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_deg, sizeof(uint32_t) * n);
+    if (e == hipSuccess) e = g->gd->d_deg.alloc(n);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::dense_degree_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_adjbits, n_nodes, wpr, g->gd->d_deg);
+        hipLaunchKernelGGL(pw::dense_degree_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_adjbits.p, n_nodes, wpr, g->gd->d_deg.p);
         e = hipGetLastError();
     }
     std::vector<uint32_t> deg(n), indptr(n + 1, 0);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess) e = hipMemcpy(deg.data(), g->gd->d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(deg.data(), g->gd->d_deg.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
     uint64_t nnz = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -1381,8 +1312,8 @@ PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, in
         if (deg[i] > g->gd->max_degree) g->gd->max_degree = deg[i];
     }
     g->gd->nnz = (uint32_t)nnz;
-    e = hipMalloc((void **)&g->gd->d_indptr, sizeof(uint32_t) * (n + 1));   // only used for stream offsets
-    if (e == hipSuccess) e = hipMemcpy(g->gd->d_indptr, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice);
+    e = g->gd->d_indptr.alloc(n + 1);   // only used for stream offsets
+    if (e == hipSuccess) e = hipMemcpy(g->gd->d_indptr.p, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice);
     if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
     *out = g;
     return PW_OK;
@@ -1397,7 +1328,7 @@ int dense_finish_degrees(pw_graph *g, uint32_t flags, std::vector<uint32_t> &ind
     GraphData &gd = *g->gd;
     const uint64_t n = gd.n_nodes;
     std::vector<uint32_t> deg(n);
-    HIP_TRY(hipMemcpy(deg.data(), gd.d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(deg.data(), gd.d_deg.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     indptr.assign(n + 1, 0);
     uint64_t nnz = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -1428,42 +1359,42 @@ PW_EXPORT int pw_dense_create_device(int device, const void *d_data, int is_f32,
     gd.kind = 1;
     gd.n_nodes = n_nodes;
     gd.words_per_row = wpr;
-    uint32_t *d_flags = nullptr;
+    DevBuf<uint32_t> d_flags;
     // the kernels run on the handle's stream between event pairs; allocations, the degree download and the indptr upload lie
     // outside the pairs (build_ms as pw_csr_dev's is defined)
     auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&gd.d_adjbits, sizeof(uint64_t) * n * wpr));
-        HIP_TRY(hipMalloc((void **)&gd.d_deg, sizeof(uint32_t) * n));
-        HIP_TRY(hipMalloc((void **)&d_flags, sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), g->stream));
+        HIP_TRY(gd.d_adjbits.alloc(n * wpr));
+        HIP_TRY(gd.d_deg.alloc(n));
+        HIP_TRY(d_flags.alloc(1));
+        HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
         HIP_TRY(hipEventRecord(g->ev[0], g->stream));
         if (is_f32)
             hipLaunchKernelGGL(pw::dense_count_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
-                               gd.d_adjbits, gd.d_deg, d_flags);
+                               gd.d_adjbits.p, gd.d_deg.p, d_flags.p);
         else
             hipLaunchKernelGGL(pw::dense_count_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
-                               gd.d_adjbits, gd.d_deg, d_flags);
+                               gd.d_adjbits.p, gd.d_deg.p, d_flags.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(g->ev[1], g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         uint32_t flags = 0;
-        HIP_TRY(hipMemcpy(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost));
         std::vector<uint32_t> indptr;
         int r = dense_finish_degrees(g, flags, indptr);
         if (r) return r;
         const uint64_t nnz = gd.nnz;
-        HIP_TRY(hipMalloc((void **)&gd.d_indptr, sizeof(uint32_t) * (n + 1)));
-        HIP_TRY(hipMemcpy(gd.d_indptr, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&gd.d_indices, nnz ? sizeof(uint32_t) * nnz : 8));
-        if (!gd.unit) HIP_TRY(hipMalloc((void **)&gd.d_data, nnz ? sizeof(double) * nnz : 8));
+        HIP_TRY(gd.d_indptr.alloc(n + 1));
+        HIP_TRY(hipMemcpy(gd.d_indptr.p, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice));
+        HIP_TRY(gd.d_indices.alloc(nnz));
+        if (!gd.unit) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
         HIP_TRY(hipEventRecord(g->ev[2], g->stream));
         if (nnz) {
             if (is_f32)
                 hipLaunchKernelGGL(pw::dense_fill_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
-                                   (const uint64_t *)gd.d_adjbits, (const uint32_t *)gd.d_indptr, gd.d_indices, (double *)gd.d_data);
+                                   (const uint64_t *)gd.d_adjbits.p, (const uint32_t *)gd.d_indptr.p, gd.d_indices.p, (double *)gd.d_data.p);
             else
                 hipLaunchKernelGGL(pw::dense_fill_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
-                                   (const uint64_t *)gd.d_adjbits, (const uint32_t *)gd.d_indptr, gd.d_indices, (double *)gd.d_data);
+                                   (const uint64_t *)gd.d_adjbits.p, (const uint32_t *)gd.d_indptr.p, gd.d_indices.p, (double *)gd.d_data.p);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(g->ev[3], g->stream));
@@ -1475,7 +1406,6 @@ PW_EXPORT int pw_dense_create_device(int device, const void *d_data, int is_f32,
         return 0;
     };
     rc = body();
-    if (d_flags) (void)hipFree(d_flags);
     if (rc) { pw_graph_destroy(g); return rc; }
     *out = g;
     return PW_OK;
@@ -1493,42 +1423,38 @@ PW_EXPORT int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, doub
     gd.kind = 1;
     gd.n_nodes = (uint32_t)n;
     gd.words_per_row = wpr;
-    uint32_t *d_flags = nullptr;
+    DevBuf<uint32_t> d_flags;
     auto body = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&gd.d_adjbits, sizeof(uint64_t) * n * wpr));
-        HIP_TRY(hipMalloc((void **)&gd.d_deg, sizeof(uint32_t) * n));
-        HIP_TRY(hipMalloc((void **)&gd.d_indptr, sizeof(uint32_t) * (n + 1)));
-        HIP_TRY(hipMalloc((void **)&gd.d_indices, nnz ? sizeof(uint32_t) * nnz : 8));
-        if (c->d_data) HIP_TRY(hipMalloc((void **)&gd.d_data, nnz ? sizeof(double) * nnz : 8));
-        HIP_TRY(hipMalloc((void **)&d_flags, sizeof(uint32_t)));
+        HIP_TRY(gd.d_adjbits.alloc(n * wpr));
+        HIP_TRY(gd.d_deg.alloc(n));
+        HIP_TRY(gd.d_indptr.alloc(n + 1));
+        HIP_TRY(gd.d_indices.alloc(nnz));
+        if (c->d_data.p) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
+        HIP_TRY(d_flags.alloc(1));
         HIP_TRY(hipEventRecord(g->ev[0], g->stream));
-        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), g->stream));
-        HIP_TRY(hipMemsetAsync(gd.d_adjbits, 0, sizeof(uint64_t) * n * wpr, g->stream));
-        HIP_TRY(hipMemcpyAsync(gd.d_indptr, c->d_indptr, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToDevice, g->stream));
-        if (nnz) HIP_TRY(hipMemcpyAsync(gd.d_indices, c->d_indices, sizeof(uint32_t) * nnz, hipMemcpyDeviceToDevice, g->stream));
+        HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
+        HIP_TRY(hipMemsetAsync(gd.d_adjbits.p, 0, sizeof(uint64_t) * n * wpr, g->stream));
+        HIP_TRY(hipMemcpyAsync(gd.d_indptr.p, c->d_indptr.p, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToDevice, g->stream));
+        if (nnz) HIP_TRY(hipMemcpyAsync(gd.d_indices.p, c->d_indices.p, sizeof(uint32_t) * nnz, hipMemcpyDeviceToDevice, g->stream));
         const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, 1u << 20);
-        hipLaunchKernelGGL(pw::csr_to_dense_kernel, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr, (const uint32_t *)c->d_indices,
-                           (const float *)c->d_data, (uint32_t)n, wpr, gd.d_adjbits, (double *)gd.d_data, gd.d_deg, d_flags);
+        hipLaunchKernelGGL(pw::csr_to_dense_kernel, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p, (const uint32_t *)c->d_indices.p,
+                           (const float *)c->d_data.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p, gd.d_deg.p, d_flags.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(g->ev[1], g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         uint32_t flags = 0;
-        HIP_TRY(hipMemcpy(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost));
         std::vector<uint32_t> indptr;
         int r = dense_finish_degrees(g, flags, indptr);
         if (r) return r;
         if (gd.nnz != nnz) return fail(PW_ERR_HIP, "pw_dense_create_from_csr: degrees do not add up to the CSR's entries (internal error)");
-        if (gd.unit && gd.d_data) {   // every weight 1.0: the values are dropped, as pw_dense_create drops them
-            (void)hipFree(gd.d_data);
-            gd.d_data = nullptr;
-        }
+        if (gd.unit) gd.d_data.release();   // every weight 1.0: the values are dropped, as pw_dense_create drops them
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
         if (build_ms) *build_ms = ms;
         return 0;
     };
     rc = body();
-    if (d_flags) (void)hipFree(d_flags);
     if (rc) { pw_graph_destroy(g); return rc; }
     *out = g;
     return PW_OK;
@@ -1541,13 +1467,13 @@ PW_EXPORT int pw_dense_noise_thresholds(pw_graph *g, double gamma, float *thr) {
     if (set_device(g)) return PW_ERR_HIP;
     const uint64_t n = gd.n_nodes;
     if (n == 0) return PW_OK;
-    if (!gd.d_thr) HIP_TRY(hipMalloc((void **)&gd.d_thr, sizeof(float) * n));
-    hipLaunchKernelGGL(pw::dense_thresholds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, (const uint32_t *)gd.d_indptr,
-                       (const double *)gd.d_data, gd.n_nodes, gamma, gd.d_thr);
+    if (!gd.d_thr.p) HIP_TRY(gd.d_thr.alloc(n));
+    hipLaunchKernelGGL(pw::dense_thresholds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, (const uint32_t *)gd.d_indptr.p,
+                       (const double *)gd.d_data.p, gd.n_nodes, gamma, gd.d_thr.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g->stream));
     gd.thr_version++;
-    if (thr) HIP_TRY(hipMemcpy(thr, gd.d_thr, sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (thr) HIP_TRY(hipMemcpy(thr, gd.d_thr.p, sizeof(float) * n, hipMemcpyDeviceToHost));
     return PW_OK;
 }
 
@@ -1559,14 +1485,14 @@ PW_EXPORT int pw_dense_export(pw_graph *g, uint32_t *indptr, uint32_t *indices, 
     if (set_device(g)) return PW_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(g->stream));
     const uint64_t n = gd.n_nodes, nnz = gd.nnz;
-    if (indptr) HIP_TRY(hipMemcpy(indptr, gd.d_indptr, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToHost));
-    if (indices && nnz) HIP_TRY(hipMemcpy(indices, gd.d_indices, sizeof(uint32_t) * nnz, hipMemcpyDeviceToHost));
+    if (indptr) HIP_TRY(hipMemcpy(indptr, gd.d_indptr.p, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToHost));
+    if (indices && nnz) HIP_TRY(hipMemcpy(indices, gd.d_indices.p, sizeof(uint32_t) * nnz, hipMemcpyDeviceToHost));
     if (data && nnz) {
-        if (gd.d_data) HIP_TRY(hipMemcpy(data, gd.d_data, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+        if (gd.d_data.p) HIP_TRY(hipMemcpy(data, gd.d_data.p, sizeof(double) * nnz, hipMemcpyDeviceToHost));
         else std::fill(data, data + nnz, 1.0);
     }
-    if (adjbits && n) HIP_TRY(hipMemcpy(adjbits, gd.d_adjbits, sizeof(uint64_t) * n * gd.words_per_row, hipMemcpyDeviceToHost));
-    if (deg && n) HIP_TRY(hipMemcpy(deg, gd.d_deg, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    if (adjbits && n) HIP_TRY(hipMemcpy(adjbits, gd.d_adjbits.p, sizeof(uint64_t) * n * gd.words_per_row, hipMemcpyDeviceToHost));
+    if (deg && n) HIP_TRY(hipMemcpy(deg, gd.d_deg.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     if (flags) *flags = (gd.unit ? 1u : 0u) | (gd.dense_nonneg ? 2u : 0u);
     return PW_OK;
 }
@@ -1584,8 +1510,8 @@ PW_EXPORT int pw_dense_shape(const pw_graph *g, uint32_t *n_nodes, uint32_t *nnz
 PW_EXPORT int pw_graph_set_thresholds(pw_graph *g, const float *thr) {
     if (!g || !thr) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
-    if (!g->gd->d_thr) HIP_TRY(hipMalloc((void **)&g->gd->d_thr, sizeof(float) * (size_t)g->gd->n_nodes));
-    HIP_TRY(hipMemcpy(g->gd->d_thr, thr, sizeof(float) * (size_t)g->gd->n_nodes, hipMemcpyHostToDevice));
+    if (!g->gd->d_thr.p) HIP_TRY(g->gd->d_thr.alloc(g->gd->n_nodes));
+    HIP_TRY(hipMemcpy(g->gd->d_thr.p, thr, sizeof(float) * (size_t)g->gd->n_nodes, hipMemcpyHostToDevice));
     g->gd->thr_version++;
     return PW_OK;
 }
@@ -1600,34 +1526,21 @@ PW_EXPORT int pw_graph_replicate(const pw_graph *src, int device, pw_graph **out
     int rc = graph_common_init(g, device);
     if (rc) { pw_graph_destroy(g); return rc; }
     static_cast<GraphDesc &>(*g->gd) = *src->gd;
-    g->gd->thr_version = src->gd->d_thr ? 1 : 0;
-    const uint64_t n = src->gd->n_nodes, nnz = src->gd->nnz;
-    const bool rows = !src->gd->bits_only;   // (dense graphs created from packed bits have no compressed rows)
-    struct Buf { void **dst; const void *from; uint64_t bytes; };
-    const Buf bufs[] = {
-        {(void **)&g->gd->d_indptr, src->gd->d_indptr, sizeof(uint32_t) * (n + 1)},
-        {(void **)&g->gd->d_indices, src->gd->d_indices, rows ? sizeof(uint32_t) * nnz : 0},
-        {(void **)&g->gd->d_data, src->gd->d_data, (src->gd->kind == 0 ? sizeof(float) : sizeof(double)) * nnz},
-        {(void **)&g->gd->d_thr, src->gd->d_thr, sizeof(float) * n},
-        {(void **)&g->gd->d_adjbits, src->gd->d_adjbits, sizeof(uint64_t) * n * src->gd->words_per_row},
-        {(void **)&g->gd->d_deg, src->gd->d_deg, sizeof(uint32_t) * n},
-        {(void **)&g->gd->d_foff, src->gd->d_foff, sizeof(uint32_t) * (n + 1)},
-        {(void **)&g->gd->d_fbits, src->gd->d_fbits, sizeof(uint64_t) * src->gd->fbits_words},
-        {(void **)&g->gd->d_kf, src->gd->d_kf, sizeof(uint2) * nnz},
-        {(void **)&g->gd->d_tab_off, src->gd->d_tab_off, sizeof(uint64_t) * (n + 1)},
-        {(void **)&g->gd->d_slots, src->gd->d_slots, sizeof(uint64_t) * src->gd->slot_words},
-        {(void **)&g->gd->d_vrec, src->gd->d_vrec, sizeof(uint4) * (n + 1)},
-        {(void **)&g->gd->d_lines, src->gd->d_lines, src->gd->line_bytes},
-        {(void **)&g->gd->d_clist, src->gd->d_clist, src->gd->clist_bytes},
-    };
+    g->gd->thr_version = src->gd->d_thr.p ? 1 : 0;
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e = hipSuccess;
-    for (const Buf &b : bufs) {
-        if (!b.from) continue;
-        e = hipMalloc(b.dst, b.bytes ? b.bytes : 8);
-        if (e == hipSuccess && b.bytes) e = hipMemcpyPeerAsync(*b.dst, device, b.from, src->device, b.bytes, g->stream);
-        if (e != hipSuccess) break;
-    }
+    // the graph's arrays and its whole per-graph index, each as large as the source holds it
+    auto copy = [&](auto GraphData::*m) {
+        const auto &from = (*src->gd).*m;
+        auto &to = (*g->gd).*m;
+        if (!from.p || e != hipSuccess) return;
+        e = to.alloc(from.cap);
+        if (e == hipSuccess && from.bytes()) e = hipMemcpyPeerAsync(to.p, device, from.p, src->device, from.bytes(), g->stream);
+    };
+    copy(&GraphData::d_indptr);   copy(&GraphData::d_indices);   copy(&GraphData::d_data);      copy(&GraphData::d_thr);
+    copy(&GraphData::d_adjbits);  copy(&GraphData::d_deg);       copy(&GraphData::d_foff);      copy(&GraphData::d_fbits);
+    copy(&GraphData::d_kf);       copy(&GraphData::d_tab_off);   copy(&GraphData::d_slots);     copy(&GraphData::d_vrec);
+    copy(&GraphData::d_lines);    copy(&GraphData::d_clist);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e != hipSuccess) {
         pw_graph_destroy(g);
@@ -1683,13 +1596,13 @@ static int compute_offsets(pw_graph *g, const uint32_t *d_starts, const uint32_t
                            uint64_t *n_changed, uint64_t j0 = 0, uint64_t n_all = 0, uint64_t *first_mismatch = nullptr) {
     if (n_all < j0 + n_jobs) n_all = j0 + n_jobs;
     uint64_t n_tiles = (n_jobs + pw::SCAN_TILE - 1) / pw::SCAN_TILE;
-    if (g->stream_off.ensure(n_all + 1)) return PW_ERR_NOMEM;
-    if (g->tile_sums.ensure((n_all + pw::SCAN_TILE - 1) / pw::SCAN_TILE + 1)) return PW_ERR_NOMEM;
-    if (track_changes && g->changed.ensure(n_all)) return PW_ERR_NOMEM;
-    if (!g->gd->d_hasnbr) {
+    if (grow(g->stream_off, n_all + 1)) return PW_ERR_NOMEM;
+    if (grow(g->tile_sums, (n_all + pw::SCAN_TILE - 1) / pw::SCAN_TILE + 1)) return PW_ERR_NOMEM;
+    if (track_changes && grow(g->changed, n_all)) return PW_ERR_NOMEM;
+    if (!g->gd->d_hasnbr.p) {
         const uint32_t words = (g->gd->n_nodes + 31u) / 32u;
-        HIP_TRY(hipMalloc((void **)&g->gd->d_hasnbr, sizeof(uint32_t) * (size_t)(words ? words : 1)));
-        hipLaunchKernelGGL(pw::has_nbr_bits_kernel, dim3((words + 255) / 256 ? (words + 255) / 256 : 1), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->n_nodes, g->gd->d_hasnbr);
+        HIP_TRY(g->gd->d_hasnbr.alloc(words));
+        hipLaunchKernelGGL(pw::has_nbr_bits_kernel, dim3((words + 255) / 256 ? (words + 255) / 256 : 1), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->n_nodes, g->gd->d_hasnbr.p);
     }
     const uint32_t *w_starts = d_starts + j0;
     const uint32_t *w_walks = d_walks ? d_walks + j0 * ((uint64_t)L + 2) : nullptr;
@@ -1698,10 +1611,10 @@ static int compute_offsets(pw_graph *g, const uint32_t *d_starts, const uint32_t
     unsigned long long *fm = first_mismatch ? g->counters.p + pw::CTR_FIRST_CHANGED : nullptr;
     if (fm) HIP_TRY(hipMemsetAsync(fm, 0xff, sizeof(unsigned long long), g->stream));
     hipLaunchKernelGGL(pw::draws_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream,
-                       g->gd->d_hasnbr, w_starts, w_walks, L, n_jobs, g->tile_sums.p);
+                       g->gd->d_hasnbr.p, w_starts, w_walks, L, n_jobs, g->tile_sums.p);
     hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, g->tile_sums.p, n_tiles);
     hipLaunchKernelGGL(pw::draws_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream,
-                       g->gd->d_hasnbr, w_starts, w_walks, L, n_jobs, g->tile_sums.p, skip, g->stream_off.p + j0,
+                       g->gd->d_hasnbr.p, w_starts, w_walks, L, n_jobs, g->tile_sums.p, skip, g->stream_off.p + j0,
                        track_changes ? g->changed.p : nullptr, cc, j0, fm);
     HIP_TRY(hipGetLastError());
     uint64_t tot = 0;
@@ -1734,36 +1647,35 @@ PW_EXPORT int pw_count_stream_draws(pw_graph *g, const uint32_t *starts, uint64_
                                     uint32_t walk_length, uint64_t *out_draws) {
     if (!g || !starts || !out_draws) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
-    if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
-    uint32_t *d_starts = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_starts, sizeof(uint32_t) * (n_jobs ? n_jobs : 1)));
-    hipError_t e = hipMemcpy(d_starts, starts, sizeof(uint32_t) * n_jobs, hipMemcpyHostToDevice);
+    if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
+    DevBuf<uint32_t> d_starts;
+    HIP_TRY(d_starts.alloc(n_jobs));
+    hipError_t e = hipMemcpy(d_starts.p, starts, sizeof(uint32_t) * n_jobs, hipMemcpyHostToDevice);
     int rc = 0;
     uint64_t tot = 0;
     if (e != hipSuccess) rc = fail(PW_ERR_HIP, hipGetErrorString(e));
-    if (!rc) rc = check_starts(g, d_starts, n_jobs);
-    if (!rc && n_jobs) rc = compute_offsets(g, d_starts, nullptr, walk_length, n_jobs, 0, false, &tot, nullptr);
-    (void)hipFree(d_starts);
+    if (!rc) rc = check_starts(g, d_starts.p, n_jobs);
+    if (!rc && n_jobs) rc = compute_offsets(g, d_starts.p, nullptr, walk_length, n_jobs, 0, false, &tot, nullptr);
     *out_draws = tot;
     return rc;
 }
 
 static pw::CsrDev csr_dev(const pw_graph *g) {
     pw::CsrDev c;
-    c.indptr = g->gd->d_indptr;
-    c.indices = g->gd->d_indices;
-    c.data = g->gd->d_data;
-    c.thr = g->gd->d_thr;
-    c.adjbits = g->gd->d_adjbits;
-    c.foff = g->gd->d_foff;
-    c.fbits = g->gd->d_fbits;
-    c.kf = g->gd->d_kf;
-    c.tab_off = g->gd->d_tab_off;
-    c.slots = g->gd->d_slots;
-    c.tri = (const uint4 *)g->gd->d_lines;   // (stride: one 64-byte line per CSR entry)
-    c.clist = g->gd->d_clist;
+    c.indptr = g->gd->d_indptr.p;
+    c.indices = g->gd->d_indices.p;
+    c.data = g->gd->d_data.p;
+    c.thr = g->gd->d_thr.p;
+    c.adjbits = g->gd->d_adjbits.p;
+    c.foff = g->gd->d_foff.p;
+    c.fbits = g->gd->d_fbits.p;
+    c.kf = g->gd->d_kf.p;
+    c.tab_off = g->gd->d_tab_off.p;
+    c.slots = g->gd->d_slots.p;
+    c.tri = (const uint4 *)g->gd->d_lines.p;   // (stride: one 64-byte line per CSR entry)
+    c.clist = g->gd->d_clist.p;
     c.step_edge = 0xffffffffu;
-    c.vrec = g->gd->d_vrec;
+    c.vrec = g->gd->d_vrec.p;
     c.words_per_row = g->gd->words_per_row;
     c.n_nodes = g->gd->n_nodes;
     c.nnz = g->gd->nnz;
@@ -1774,14 +1686,14 @@ PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int 
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
     if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "alias tables need a CSR graph handle");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
-    if (extend && !g->gd->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
+    if (extend && !g->gd->d_thr.p) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (set_device(g)) return PW_ERR_HIP;
     first_order = first_order ? 1 : 0;
     if (g->gd->alias_kind == first_order && (first_order || (g->gd->alias_p == p && g->gd->alias_q_param == q && g->gd->alias_extend == extend)))
         return PW_OK;
     const uint32_t n = g->gd->n_nodes;
     std::vector<uint32_t> indptr((size_t)n + 1);
-    HIP_TRY(hipMemcpy(indptr.data(), g->gd->d_indptr, sizeof(uint32_t) * indptr.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(indptr.data(), g->gd->d_indptr.p, sizeof(uint32_t) * indptr.size(), hipMemcpyDeviceToHost));
     std::vector<uint64_t> aptr((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) {
         uint64_t d = indptr[i + 1] - indptr[i];
@@ -1789,12 +1701,12 @@ PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int 
     }
     const uint64_t n_alias = aptr[n];
     const size_t cap = n_alias ? n_alias : 1;
-    if (g->gd->alias_indptr.ensure((size_t)n + 1) || g->gd->alias_j.ensure(cap) || g->gd->alias_q.ensure(cap) ||
-        g->gd->alias_s.ensure(cap) || g->gd->alias_l.ensure(cap) || g->gd->edge_row.ensure(g->gd->nnz ? g->gd->nnz : 1))
+    if (grow(g->gd->alias_indptr, (size_t)n + 1) || grow(g->gd->alias_j, cap) || grow(g->gd->alias_q, cap) ||
+        grow(g->gd->alias_s, cap) || grow(g->gd->alias_l, cap) || grow(g->gd->edge_row, g->gd->nnz ? g->gd->nnz : 1))
         return PW_ERR_NOMEM;
     HIP_TRY(hipMemcpy(g->gd->alias_indptr.p, aptr.data(), sizeof(uint64_t) * aptr.size(), hipMemcpyHostToDevice));
     pw::CsrDev c = csr_dev(g);
-    if (n) hipLaunchKernelGGL(pw::edge_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, g->gd->d_indptr, n, g->gd->edge_row.p);
+    if (n) hipLaunchKernelGGL(pw::edge_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, g->gd->d_indptr.p, n, g->gd->edge_row.p);
     const uint64_t work = first_order ? (uint64_t)n : (uint64_t)g->gd->nnz;
     if (work)
         hipLaunchKernelGGL(pw::alias_tables_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, g->stream, c, p, q,
@@ -1842,8 +1754,8 @@ static int simulate_sequential(pw_graph *g, int mode, double p, double q, int ex
     if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "this mode needs a CSR graph handle");
     if (mode == PW_MODE_PRECOMP) { int rc = pw_precomp_build(g, p, q, extend, 0); if (rc) return rc; }
     if (mode == PW_MODE_PRECOMP_FIRST_ORDER) { int rc = pw_precomp_build(g, 1.0, 1.0, 0, 1); if (rc) return rc; }
-    if (g->mt_state.ensure(pw::MT_N)) return PW_ERR_NOMEM;
-    if (g->probs_scratch.ensure((size_t)g->gd->max_degree + 1)) return PW_ERR_NOMEM;
+    if (grow(g->mt_state, pw::MT_N)) return PW_ERR_NOMEM;
+    if (grow(g->probs_scratch, (size_t)g->gd->max_degree + 1)) return PW_ERR_NOMEM;
     uint32_t st0[pw::MT_N];
     pw::mt_seed_state(st0, seed);
     HIP_TRY(hipMemcpy(g->mt_state.p, st0, sizeof(st0), hipMemcpyHostToDevice));
@@ -1905,8 +1817,8 @@ static bool is_pow2_double(double x) {
 
 static int launch_dense_bits(pw_graph *g, const pw::WalkArgs &wa, uint64_t *redo_total) {
     pw::DenseArgs da;
-    da.adjbits = g->gd->d_adjbits;
-    da.deg = g->gd->d_deg;
+    da.adjbits = g->gd->d_adjbits.p;
+    da.deg = g->gd->d_deg.p;
     da.n = g->gd->n_nodes;
     da.wpr = g->gd->words_per_row;
     da.p = wa.p;
@@ -1957,7 +1869,7 @@ static int launch_dense_bits(pw_graph *g, const pw::WalkArgs &wa, uint64_t *redo
     };
     unsigned grid = 1;
     if (ff && n_work) {
-        if (g->redo.ensure(n_work)) return PW_ERR_NOMEM;
+        if (grow(g->redo, n_work)) return PW_ERR_NOMEM;
         if (grid_for((const void *)ff, n_work, &grid)) return PW_ERR_HIP;
         HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_JOB, 0, sizeof(unsigned long long), g->stream));
         HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_REDO, 0, sizeof(unsigned long long), g->stream));
@@ -1994,26 +1906,26 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &s
     // the graph has entries is faster through the two-pass step (an existing table is used whatever the call's size)
     if (!fresh && wa.n_jobs * (uint64_t)wa.L < (uint64_t)g->gd->nnz && !sw.force_tot) return 0;
     if (!fresh) {
-        if (!g->gd->d_tot_e) {
-            hipError_t e = hipMalloc((void **)&g->gd->d_tot_e, sizeof(float) * (size_t)g->gd->nnz);
-            if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_tot_v, sizeof(float) * (size_t)(g->gd->n_nodes ? g->gd->n_nodes : 1));
-            if (e != hipSuccess) { g->gd->tot_failed = true; (void)hipGetLastError(); return 0; }
+        if (!g->gd->d_tot_e.p) {
+            hipError_t e = g->gd->d_tot_e.alloc(g->gd->nnz);
+            if (e == hipSuccess) e = g->gd->d_tot_v.alloc(g->gd->n_nodes);
+            if (e != hipSuccess) { g->gd->tot_failed = true; return 0; }
         }
-        uint32_t *d_edge_row = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_edge_row, sizeof(uint32_t) * (size_t)g->gd->nnz));
-        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->n_nodes, d_edge_row);
+        DevBuf<uint32_t> d_edge_row;
+        HIP_TRY(d_edge_row.alloc(g->gd->nnz));
+        hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->n_nodes, d_edge_row.p);
         pw::WalkArgs ba = wa;
         hipError_t e = hipEventRecord(g->ev[4], g->stream);
         if (e == hipSuccess) {
             const uint64_t items = (uint64_t)g->gd->nnz + g->gd->n_nodes;
             const unsigned grid = (unsigned)((items + pw::WAVES_PER_BLOCK - 1) / pw::WAVES_PER_BLOCK);
-            if (extend) hipLaunchKernelGGL(pw::tot_build_kernel<true>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row, g->gd->d_tot_e, g->gd->d_tot_v);
-            else hipLaunchKernelGGL(pw::tot_build_kernel<false>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row, g->gd->d_tot_e, g->gd->d_tot_v);
+            if (extend) hipLaunchKernelGGL(pw::tot_build_kernel<true>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row.p, g->gd->d_tot_e.p, g->gd->d_tot_v.p);
+            else hipLaunchKernelGGL(pw::tot_build_kernel<false>, dim3(grid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, ba, d_edge_row.p, g->gd->d_tot_e.p, g->gd->d_tot_v.p);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(g->ev[5], g->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-        (void)hipFree(d_edge_row);
+        d_edge_row.release();
         if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("normaliser table: ") + hipGetErrorString(e));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
@@ -2024,8 +1936,8 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &s
         g->gd->tot_q = wa.q;
         g->gd->tot_thr_version = g->gd->thr_version;
     }
-    wa.tot_e = g->gd->d_tot_e;
-    wa.tot_v = g->gd->d_tot_v;
+    wa.tot_e = g->gd->d_tot_e.p;
+    wa.tot_v = g->gd->d_tot_v.p;
     return 0;
 }
 
@@ -2035,9 +1947,9 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &s
 // the form does not apply: the wave-per-walk kernel then serves the call.
 static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, const LaneSwitches &sw, bool extend, bool *ok) {
     *ok = false;
-    if (g->gd->kind != 0 || g->gd->unit || !g->gd->nnz || !g->gd->d_lines || g->gd->lanes_off || !wa.tot_e || g->gd->wl_failed) return 0;
+    if (g->gd->kind != 0 || g->gd->unit || !g->gd->nnz || !g->gd->d_lines.p || g->gd->lanes_off || !wa.tot_e || g->gd->wl_failed) return 0;
     if (sw.no_lanes || sw.no_wlanes) return 0;
-    if (extend && !g->gd->d_thr) return 0;
+    if (extend && !g->gd->d_thr.p) return 0;
     // (the float64 evaluation of the prefix differences is part of the decision's error budget: moderate biases only)
     if (!(wa.p >= 1.0 / 1024 && wa.p <= 1024.0 && wa.q >= 1.0 / 1024 && wa.q <= 1024.0)) return 0;
     const bool fresh = g->gd->wl_extend == (extend ? 1 : 0) && g->gd->wl_p == wa.p && g->gd->wl_q == wa.q &&
@@ -2045,82 +1957,70 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, const LaneSw
     if (fresh) { *ok = true; return 0; }
     const uint32_t nnz = g->gd->nnz;
     auto give_up = [&]() { g->gd->wl_failed = true; (void)hipGetLastError(); return 0; };
-    if (!g->gd->d_wb) {
-        hipError_t e = hipMalloc((void **)&g->gd->d_wb, sizeof(float) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wpq, sizeof(pw::PrefixPair) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wl_dprev, sizeof(double) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wl_off, sizeof(unsigned long long) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wck_off, sizeof(unsigned long long) * (size_t)nnz);
-        const bool have_rows = g->gd->d_wedge_row != nullptr;   // (a handle with a PARTIAL index kept them from its creation: pw_csr_create)
-        if (e == hipSuccess && !have_rows) e = hipMalloc((void **)&g->gd->d_wedge_row, sizeof(uint32_t) * (size_t)nnz);
-        if (e == hipSuccess) e = hipMalloc((void **)&g->gd->d_wp1, sizeof(pw::PrefixPair) * (size_t)nnz);
+    if (!g->gd->d_wb.p) {
+        hipError_t e = g->gd->d_wb.alloc(nnz);
+        if (e == hipSuccess) e = g->gd->d_wpq.alloc(nnz);
+        if (e == hipSuccess) e = g->gd->d_wl_dprev.alloc(nnz);
+        if (e == hipSuccess) e = g->gd->d_wl_off.alloc(nnz);
+        if (e == hipSuccess) e = g->gd->d_wck_off.alloc(nnz);
+        const bool have_rows = g->gd->d_wedge_row.p != nullptr;   // (a handle with a PARTIAL index kept them from its creation: pw_csr_create)
+        if (e == hipSuccess && !have_rows) e = g->gd->d_wedge_row.alloc(nnz);
+        if (e == hipSuccess) e = g->gd->d_wp1.alloc(nnz);
         if (e != hipSuccess) return give_up();
-        if (!have_rows) hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->n_nodes, g->gd->d_wedge_row);
-        hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->gd->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_indptr,
-                           (const float *)g->gd->d_data, g->gd->n_nodes, g->gd->d_wp1);
+        if (!have_rows) hipLaunchKernelGGL(pw::csr_edge_rows_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->n_nodes, g->gd->d_wedge_row.p);
+        hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->gd->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_indptr.p,
+                           (const float *)g->gd->d_data.p, g->gd->n_nodes, g->gd->d_wp1.p);
     }
-    uint64_t *d_tiles = nullptr;
+    DevBuf<uint64_t> tiles;
     const uint64_t n_tiles = ((uint64_t)nnz + pw::CL_TILE - 1) / pw::CL_TILE;
-    auto cleanup = [&]() { if (d_tiles) (void)hipFree(d_tiles); };
-    hipError_t e = hipMalloc((void **)&d_tiles, sizeof(uint64_t) * (n_tiles + 1));
-    if (e != hipSuccess) { cleanup(); return give_up(); }
+    hipError_t e = tiles.alloc(n_tiles + 1);
+    if (e != hipSuccess) return give_up();
+    uint64_t *const d_tiles = tiles.p;
     HIP_TRY(hipEventRecord(g->ev[4], g->stream));
     // offsets of the per-entry delta lists (one float64 per list entry) and of the recorded chain values
     uint64_t entries = 0, records = 0;
-    hipLaunchKernelGGL(pw::entry_tile_sums_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles);
+    hipLaunchKernelGGL(pw::entry_tile_sums_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles);
     hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-    hipLaunchKernelGGL(pw::entry_offsets_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles, g->gd->d_wl_off);
+    hipLaunchKernelGGL(pw::entry_offsets_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles, g->gd->d_wl_off.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&entries, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::entry_tile_sums_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles);
+        hipLaunchKernelGGL(pw::entry_tile_sums_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles);
         hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-        hipLaunchKernelGGL(pw::entry_offsets_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines, nnz, d_tiles, g->gd->d_wck_off);
+        hipLaunchKernelGGL(pw::entry_offsets_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles, g->gd->d_wck_off.p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&records, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_HIP, std::string("weighted lane tables (offsets): ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("weighted lane tables (offsets): ") + hipGetErrorString(e));
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    if (entries + 1 > g->gd->wdl_cap) {
-        if (g->gd->d_wdl) (void)hipFree(g->gd->d_wdl);
-        g->gd->d_wdl = nullptr;
-        g->gd->wdl_cap = 0;
-        if ((entries + 1) * sizeof(double) > free_b / 2 || hipMalloc((void **)&g->gd->d_wdl, sizeof(double) * (size_t)(entries + 1)) != hipSuccess) {
-            cleanup();
-            return give_up();
-        }
-        g->gd->wdl_cap = entries + 1;
+    if (entries + 1 > g->gd->d_wdl.cap) {
+        g->gd->d_wdl.release();
+        if ((entries + 1) * sizeof(double) > free_b / 2 || g->gd->d_wdl.alloc((size_t)(entries + 1)) != hipSuccess) return give_up();
     }
-    if (records + 1 > g->gd->wck_cap) {
-        if (g->gd->d_wck) (void)hipFree(g->gd->d_wck);
-        g->gd->d_wck = nullptr;
-        g->gd->wck_cap = 0;
-        if ((records + 1) * sizeof(float) > free_b / 4 || hipMalloc((void **)&g->gd->d_wck, sizeof(float) * (size_t)(records + 1)) != hipSuccess) {
-            cleanup();
-            return give_up();
-        }
-        g->gd->wck_cap = records + 1;
+    if (records + 1 > g->gd->d_wck.cap) {
+        g->gd->d_wck.release();
+        if ((records + 1) * sizeof(float) > free_b / 4 || g->gd->d_wck.alloc((size_t)(records + 1)) != hipSuccess) return give_up();
     }
     const unsigned egrid = (unsigned)(((uint64_t)nnz + 255) / 256);
     pw::CsrDev c = csr_dev(g);
-    if (extend) hipLaunchKernelGGL(pw::wbase_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->gd->d_data, g->gd->d_wedge_row, g->gd->d_thr, wa.q, nnz, g->gd->d_wb);
-    else hipLaunchKernelGGL(pw::wbase_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->gd->d_data, g->gd->d_wedge_row, (const float *)nullptr, wa.q, nnz, g->gd->d_wb);
-    hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->gd->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_indptr, g->gd->d_wb,
-                       g->gd->n_nodes, g->gd->d_wpq);
-    if (extend) hipLaunchKernelGGL(pw::wlist_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, c, g->gd->d_wedge_row, g->gd->d_wb, wa.p, wa.q, g->gd->d_wl_off, g->gd->d_wdl, g->gd->d_wl_dprev);
-    else hipLaunchKernelGGL(pw::wlist_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, c, g->gd->d_wedge_row, g->gd->d_wb, wa.p, wa.q, g->gd->d_wl_off, g->gd->d_wdl, g->gd->d_wl_dprev);
+    if (extend) hipLaunchKernelGGL(pw::wbase_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->gd->d_data.p, g->gd->d_wedge_row.p, g->gd->d_thr.p, wa.q, nnz, g->gd->d_wb.p);
+    else hipLaunchKernelGGL(pw::wbase_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, (const float *)g->gd->d_data.p, g->gd->d_wedge_row.p, (const float *)nullptr, wa.q, nnz, g->gd->d_wb.p);
+    hipLaunchKernelGGL(pw::wprefix_kernel, dim3((unsigned)(((uint64_t)g->gd->n_nodes * pw::WAVE + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->d_wb.p,
+                       g->gd->n_nodes, g->gd->d_wpq.p);
+    if (extend) hipLaunchKernelGGL(pw::wlist_kernel<true>, dim3(egrid), dim3(256), 0, g->stream, c, g->gd->d_wedge_row.p, g->gd->d_wb.p, wa.p, wa.q, g->gd->d_wl_off.p, g->gd->d_wdl.p, g->gd->d_wl_dprev.p);
+    else hipLaunchKernelGGL(pw::wlist_kernel<false>, dim3(egrid), dim3(256), 0, g->stream, c, g->gd->d_wedge_row.p, g->gd->d_wb.p, wa.p, wa.q, g->gd->d_wl_off.p, g->gd->d_wdl.p, g->gd->d_wl_dprev.p);
     if (records) {   // the chain's value after every CHAIN_CKPT-th element of the rows longer than that, per arriving entry
         const unsigned cgrid = (unsigned)(((uint64_t)nnz + pw::WAVES_PER_BLOCK - 1) / pw::WAVES_PER_BLOCK);
-        if (extend) hipLaunchKernelGGL(pw::wckpt_kernel<true>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->gd->d_wedge_row, g->gd->d_wck_off, g->gd->d_wck);
-        else hipLaunchKernelGGL(pw::wckpt_kernel<false>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->gd->d_wedge_row, g->gd->d_wck_off, g->gd->d_wck);
+        if (extend) hipLaunchKernelGGL(pw::wckpt_kernel<true>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->gd->d_wedge_row.p, g->gd->d_wck_off.p, g->gd->d_wck.p);
+        else hipLaunchKernelGGL(pw::wckpt_kernel<false>, dim3(cgrid), dim3(pw::WAVES_PER_BLOCK * pw::WAVE), 0, g->stream, wa, g->gd->d_wedge_row.p, g->gd->d_wck_off.p, g->gd->d_wck.p);
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(g->ev[5], g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    cleanup();
+    tiles.release();
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("weighted lane tables: ") + hipGetErrorString(e));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
@@ -2142,8 +2042,8 @@ static bool dense_weighted_lds_ok(const pw_graph *g) {
 }
 
 static bool dense_weighted_eligible(const pw_graph *g, const pw::WalkArgs &wa, bool extend) {
-    if (g->gd->kind != 1 || g->gd->unit || g->gd->bits_only || !g->gd->dense_nonneg || !g->gd->d_adjbits || !g->gd->d_data) return false;
-    if (extend && !g->gd->d_thr) return false;
+    if (g->gd->kind != 1 || g->gd->unit || g->gd->bits_only || !g->gd->dense_nonneg || !g->gd->d_adjbits.p || !g->gd->d_data.p) return false;
+    if (extend && !g->gd->d_thr.p) return false;
     if (wa.resume || getenv("PECANPY_AMD_DENSE_NO_WFAST")) return false;
     return dense_weighted_lds_ok(g);
 }
@@ -2153,8 +2053,8 @@ static int n2vpp_check(const pw_graph *g) {
     if (g->gd->kind != 1) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs a dense graph handle");
     if (g->gd->bits_only) return fail(PW_ERR_UNSUPPORTED, "node2vec++: a dense graph created from packed bits has no compressed rows");
     if (!g->gd->dense_nonneg) return fail(PW_ERR_UNSUPPORTED, "node2vec++ needs finite, positive edge weights");
-    if (!g->gd->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
-    if (!g->gd->d_adjbits || (!g->gd->unit && !g->gd->d_data)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: the handle has no dense rows");
+    if (!g->gd->d_thr.p) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
+    if (!g->gd->d_adjbits.p || (!g->gd->unit && !g->gd->d_data.p)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: the handle has no dense rows");
     if (!dense_weighted_lds_ok(g)) return fail(PW_ERR_UNSUPPORTED, "node2vec++: prev's packed row does not fit one wavefront's LDS");
     return PW_OK;
 }
@@ -2162,18 +2062,18 @@ static int n2vpp_check(const pw_graph *g) {
 // node2vec++ on CSR handles (walk_sparse_pp.hip.h): likewise no other kernel
 static int spp_check(pw_graph *g) {
     if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++ needs a CSR graph handle");
-    if (!g->gd->d_thr) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
-    if (g->gd->nnz && (!g->gd->d_vrec || !g->gd->d_kf || !g->gd->d_fbits || !g->gd->d_slots))
+    if (!g->gd->d_thr.p) return fail(PW_ERR_INVALID, "node2vec++ uses the noise thresholds: call pw_graph_set_thresholds() first");
+    if (g->gd->nnz && (!g->gd->d_vrec.p || !g->gd->d_kf.p || !g->gd->d_fbits.p || !g->gd->d_slots.p))
         return fail(PW_ERR_UNSUPPORTED, "sparse node2vec++: the handle has no membership index");
     if (g->gd->spp_zero < 0) {   // a stored 0.0f is a neighbour here but not in the dense reference (its b = 0 gives 0 / 0)
         g->gd->spp_zero = 0;
-        if (!g->gd->unit && g->gd->d_data && g->gd->nnz) {
+        if (!g->gd->unit && g->gd->d_data.p && g->gd->nnz) {
             if (set_device(g)) return PW_ERR_HIP;
-            if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
+            if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
             unsigned long long flag = 0;
             HIP_TRY(hipMemsetAsync(g->counters.p, 0, sizeof(flag), g->stream));
             hipLaunchKernelGGL(pw::csr_zero_weight_kernel, dim3((unsigned)(((uint64_t)g->gd->nnz + 255) / 256)), dim3(256), 0, g->stream,
-                               (const float *)g->gd->d_data, (uint64_t)g->gd->nnz, g->counters.p);
+                               (const float *)g->gd->d_data.p, (uint64_t)g->gd->nnz, g->counters.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&flag, g->counters.p, sizeof(flag), hipMemcpyDeviceToHost, g->stream));
             HIP_TRY(hipStreamSynchronize(g->stream));
@@ -2187,12 +2087,12 @@ static int spp_check(pw_graph *g) {
 static pw::SparsePPArgs spp_args(const pw_graph *g, double p, double q) {
     pw::SparsePPArgs sa;
     memset(&sa, 0, sizeof(sa));
-    sa.vrec = g->gd->d_vrec;
-    sa.kf = g->gd->d_kf;
-    sa.data = g->gd->unit ? nullptr : (const float *)g->gd->d_data;
-    sa.fbits = g->gd->d_fbits;
-    sa.slots = g->gd->d_slots;
-    sa.thr = g->gd->d_thr;
+    sa.vrec = g->gd->d_vrec.p;
+    sa.kf = g->gd->d_kf.p;
+    sa.data = g->gd->unit ? nullptr : (const float *)g->gd->d_data.p;
+    sa.fbits = g->gd->d_fbits.p;
+    sa.slots = g->gd->d_slots.p;
+    sa.thr = g->gd->d_thr.p;
     sa.n = g->gd->n_nodes;
     sa.p = p;
     sa.q = q;
@@ -2236,11 +2136,11 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, int bias, 
     uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
     if (!n_work) return 0;
     pw::DenseWArgs da;
-    da.indptr = g->gd->d_indptr;
-    da.indices = g->gd->d_indices;
-    da.data = (const double *)g->gd->d_data;
-    da.adjbits = g->gd->d_adjbits;
-    da.thr = g->gd->d_thr;
+    da.indptr = g->gd->d_indptr.p;
+    da.indices = g->gd->d_indices.p;
+    da.data = (const double *)g->gd->d_data.p;
+    da.adjbits = g->gd->d_adjbits.p;
+    da.thr = g->gd->d_thr.p;
     da.n = g->gd->n_nodes;
     da.wpr = g->gd->words_per_row;
     da.p = wa.p;
@@ -2256,7 +2156,7 @@ static int launch_dense_weighted(pw_graph *g, const pw::WalkArgs &wa, int bias, 
     da.out = wa.out;
     da.job_counter = wa.job_counter;
     da.stats = wa.stats;
-    if (g->redo.ensure(n_work)) return PW_ERR_NOMEM;
+    if (grow(g->redo, n_work)) return PW_ERR_NOMEM;
     da.redo_list = g->redo.p;
     da.redo_count = g->counters.p + pw::CTR_REDO;
     const char *rt = getenv("PECANPY_AMD_DENSE_REDO_TEST");   // tests: every k-th walk is handed over at its third step
@@ -2321,7 +2221,7 @@ static int launch_wave_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_
     // sent matrices of up to 12 000 rows through their compressed rows; PECANPY_AMD_DENSE_SMALL_ROWS=1: that rule)
     if (g->call_n2vpp) return launch_dense_weighted(g, wa, g->gd->unit ? pw::DW_N2VPP_UNIT : pw::DW_N2VPP, redo_total);
     const bool small_rows = env_on("PECANPY_AMD_DENSE_SMALL_ROWS");
-    if (g->gd->kind == 1 && g->gd->unit && g->gd->d_deg && (g->gd->bits_only || g->gd->n_nodes > 12000 || !small_rows)) return launch_dense_bits(g, wa, redo_total);
+    if (g->gd->kind == 1 && g->gd->unit && g->gd->d_deg.p && (g->gd->bits_only || g->gd->n_nodes > 12000 || !small_rows)) return launch_dense_bits(g, wa, redo_total);
     if (dense_weighted_eligible(g, wa, extend)) return launch_dense_weighted(g, wa, extend ? pw::DW_N2VPLUS : pw::DW_N2V, redo_total);
     int occ = 0;
     walk_kernel_fn fn = pick_kernel(g, extend);
@@ -2336,14 +2236,14 @@ static int launch_wave_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_
 }
 
 static bool lanes_eligible(const pw_graph *g, const pw::WalkArgs &wa, const LaneSwitches &sw) {
-    return g->gd->kind == 0 && g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && wa.lazy_ok && !sw.no_lanes;
+    return g->gd->kind == 0 && g->gd->unit && g->gd->d_lines.p && !g->gd->lanes_off && wa.lazy_ok && !sw.no_lanes;
 }
 
 // The LanesArgs fields that every lane launch takes from (g, wa); the rest is zero until the launcher sets what is
 // particular to its form.
 static pw::LanesArgs common_lanes_args(const pw_graph *g, const pw::WalkArgs &wa) {
     pw::LanesArgs la = {};
-    la.lines = g->gd->d_lines;   la.clist = g->gd->d_clist;   la.vlines = g->gd->vlines ? 1u : 0u;   la.vrec = g->gd->d_vrec;   la.nnz = g->gd->nnz;
+    la.lines = g->gd->d_lines.p;   la.clist = g->gd->d_clist.p;   la.vlines = g->gd->vlines ? 1u : 0u;   la.vrec = g->gd->d_vrec.p;   la.nnz = g->gd->nnz;
     la.L = wa.L;                 la.n_jobs = wa.n_jobs;       la.starts = wa.starts;   la.stream_off = wa.stream_off;
     la.job_list = wa.job_list;   la.n_list = wa.n_list;       la.redo_list = g->redo.p;
     la.rng = wa.rng;             la.rng_base = wa.rng_base;   la.out = wa.out;
@@ -2405,7 +2305,7 @@ static int plan_verification(pw_graph *g, const LaneSwitches &sw, bool applies, 
         }
         if (sw.has_verify_cap) cap = sw.verify_cap;
     }
-    if (g->ver.ensure(cap) || g->ver_bad.ensure(VER_BAD_CAP) || ((vp->sample || floats) && g->ver_jobs.ensure(VER_JOBS_CAP))) return PW_ERR_NOMEM;
+    if (grow(g->ver, cap) || grow(g->ver_bad, VER_BAD_CAP) || ((vp->sample || floats) && grow(g->ver_jobs, VER_JOBS_CAP))) return PW_ERR_NOMEM;
     vp->cap = cap;
     la.ver = g->ver.p;
     la.ver_cap = cap;
@@ -2427,7 +2327,7 @@ static int verify_records(pw_graph *g, const pw::WalkArgs &wa, uint64_t ver_cap,
         // (the lane kernel's record counter shares CTR_VER with the counts of the per-round check)
         if (slot == pw::CTR_VER) HIP_TRY(hipMemsetAsync(counts, 0, pw::N_VER_COUNTS * sizeof(unsigned long long), g->stream));
         hipLaunchKernelGGL(pw::lanes_verify_kernel, dim3((unsigned)((n_chk + 255) / 256)), dim3(256), 0, g->stream, g->ver.p, (uint64_t)n_chk,
-                           g->gd->d_lines, g->gd->d_clist, wa.w_prev, counts, g->ver_bad.p, VER_BAD_CAP, list_jobs ? g->ver_jobs.p : nullptr,
+                           g->gd->d_lines.p, g->gd->d_clist.p, wa.w_prev, counts, g->ver_bad.p, VER_BAD_CAP, list_jobs ? g->ver_jobs.p : nullptr,
                            list_jobs ? VER_JOBS_CAP : 0u, floats ? 1u : 0u);
         HIP_TRY(hipGetLastError());
         if (ev_launched) HIP_TRY(hipEventRecord(ev_launched, g->stream));
@@ -2560,8 +2460,7 @@ static int plan_lane_call(pw_graph *g, const pw::WalkArgs &wa, const LaneSwitche
     // + the void slots of every wavefront's LAST reservation (< 128 each; leftovers of earlier ones are used up)
     const uint64_t can_park = (!wa.job_list && g->call_runnable && g->call_runnable < n_work) ? g->call_runnable : n_work;
     const size_t q_cap = (size_t)can_park + 2 * (size_t)lanes_resident;
-    if (use_queue && g->susp[0].ensure(q_cap)) {
-        (void)hipGetLastError();
+    if (use_queue && g->susp[0].ensure(q_cap) != hipSuccess) {
         use_queue = false;              // no room for the queues: chains run in place
         chains_form = false;
     }
@@ -2578,18 +2477,18 @@ static int settle_lane_queue(pw_graph *g, const pw::WalkArgs &wa, bool weighted,
         HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_EAGER_NEXT, 0, sizeof(unsigned long long), g->stream));   // (record counter of the persistent grid)
         const dim3 egrid((unsigned)std::min<uint64_t>(want_e, (uint64_t)g->n_cu * (uint64_t)(g->twin_active ? EAGER_WGS_TWIN : EAGER_WGS)));
         auto fn = extend ? pw::lanes_eager_weighted_kernel<true> : pw::lanes_eager_weighted_kernel<false>;
-        hipLaunchKernelGGL(fn, egrid, eblock, 0, g->stream, wa, queue, (uint64_t)parked, eager_stats, (const uint32_t *)g->gd->d_wedge_row,
-                           (const unsigned long long *)g->gd->d_wck_off, (const float *)g->gd->d_wck);
+        hipLaunchKernelGGL(fn, egrid, eblock, 0, g->stream, wa, queue, (uint64_t)parked, eager_stats, (const uint32_t *)g->gd->d_wedge_row.p,
+                           (const unsigned long long *)g->gd->d_wck_off.p, (const float *)g->gd->d_wck.p);
         HIP_TRY(hipGetLastError());
         return 0;
     }
     hipLaunchKernelGGL(pw::lanes_chain_kernel, dim3((unsigned)((parked + 255) / 256)), dim3(256), 0, g->stream,
-                       queue, (uint64_t)parked, g->gd->d_lines, g->gd->d_clist, wa.w_prev, g->counters.p + pw::CTR_STATS);
+                       queue, (uint64_t)parked, g->gd->d_lines.p, g->gd->d_clist.p, wa.w_prev, g->counters.p + pw::CTR_STATS);
     HIP_TRY(hipGetLastError());
     if (g->gd->list_max_len != 0xffffffffu) {   // partial index: the steps whose entry's list was left out (one wavefront each)
         HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_EAGER_NEXT, 0, sizeof(unsigned long long), g->stream));
         hipLaunchKernelGGL(pw::lanes_eager_kernel, dim3((unsigned)std::min<uint64_t>(want_e, (uint64_t)g->n_cu * EAGER_WGS)), eblock, 0, g->stream,
-                           wa, queue, (uint64_t)parked, eager_stats, (const uint32_t *)g->gd->d_wedge_row);
+                           wa, queue, (uint64_t)parked, eager_stats, (const uint32_t *)g->gd->d_wedge_row.p);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -2661,10 +2560,10 @@ static int finish_lane_rounds(pw_graph *g, const pw::WalkArgs &wa, const LaneSwi
 // walked again by the wave-per-walk kernel.  *n_redo receives their number.
 static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &sw, uint64_t *n_redo, bool weighted = false, bool extend = false) {
     const uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
-    if (g->redo.ensure(n_work ? n_work : 1)) return PW_ERR_NOMEM;
+    if (grow(g->redo, n_work ? n_work : 1)) return PW_ERR_NOMEM;
     pw::LanesArgs la = common_lanes_args(g, wa);
-    la.wpq = g->gd->d_wpq;   la.wdl = g->gd->d_wdl;   la.wl_off = g->gd->d_wl_off;   la.wl_dprev = g->gd->d_wl_dprev;
-    la.wp1 = g->gd->d_wp1;   la.wl_pos = wa.q >= 1.0 ? 1u : 0u;
+    la.wpq = g->gd->d_wpq.p;   la.wdl = g->gd->d_wdl.p;   la.wl_off = g->gd->d_wl_off.p;   la.wl_dprev = g->gd->d_wl_dprev.p;
+    la.wp1 = g->gd->d_wp1.p;   la.wl_pos = wa.q >= 1.0 ? 1u : 0u;
     la.tot_e = wa.tot_e;     la.tot_v = wa.tot_v;
     LanePlan pl;
     int rc = plan_lane_call(g, wa, sw, weighted, n_work, &pl);
@@ -2689,8 +2588,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &
         const bool chains_now = (pl.chains_form && round == 0) || chains_late;
         constexpr int MAX_ROUNDS = 64, MAX_ROUNDS_WEIGHTED = 512;   // queueing rounds; the one behind them runs its chains in place
         bool queue_out = chains_now || (pl.use_queue && todo > pl.tail && round < (weighted ? MAX_ROUNDS_WEIGHTED : MAX_ROUNDS));
-        if (queue_out && round >= 1 && g->susp[round & 1].ensure((size_t)todo + 2 * (size_t)pl.lanes_resident)) {
-            (void)hipGetLastError();
+        if (queue_out && round >= 1 && g->susp[round & 1].ensure((size_t)todo + 2 * (size_t)pl.lanes_resident) != hipSuccess) {
             queue_out = false;          // (no room for the other queue: this round runs its chains in place and is the last)
         }
         la.susp = queue_out ? g->susp[round & 1].p : nullptr;
@@ -2736,7 +2634,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &
 // Unit-weight graphs whose 1/p or 1/q is not a power of two: the lane kernel in its FLOATS form -- every step is the
 // reference's two float32 chains, evaluated per lane (walk_lanes.hip.h); one launch, nothing is parked.
 static bool lanes_float_eligible(const pw_graph *g, const pw::WalkArgs &wa, const LaneSwitches &sw) {
-    return g->gd->kind == 0 && g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && !wa.lazy_ok && !sw.no_lanes;
+    return g->gd->kind == 0 && g->gd->unit && g->gd->d_lines.p && !g->gd->lanes_off && !wa.lazy_ok && !sw.no_lanes;
 }
 
 // FLOATS form: the row totals of all arriving lines, once per (1/q, 1/p) (walk_lanes.hip.h: unit_tot_kernel; cached in the
@@ -2745,18 +2643,16 @@ static bool lanes_float_eligible(const pw_graph *g, const pw::WalkArgs &wa, cons
 static int ensure_unit_tot(pw_graph *g, const pw::WalkArgs &wa, const LaneSwitches &sw) {
     if (g->gd->utot_failed) return 0;
     const uint64_t n_lines = (uint64_t)g->gd->nnz + (g->gd->vlines ? g->gd->n_nodes : 0);
-    const bool fresh = g->gd->d_utot && g->gd->utot_wo == wa.w_out && g->gd->utot_wp == wa.w_prev;
+    const bool fresh = g->gd->d_utot.p && g->gd->utot_wo == wa.w_out && g->gd->utot_wp == wa.w_prev;
     if (fresh || !(wa.n_jobs * (uint64_t)wa.L >= n_lines || sw.force_tot)) return 0;
-    if (!g->gd->d_utot && hipMalloc((void **)&g->gd->d_utot, sizeof(float) * (size_t)(n_lines ? n_lines : 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        g->gd->d_utot = nullptr;
+    if (!g->gd->d_utot.p && g->gd->d_utot.alloc(n_lines) != hipSuccess) {
         g->gd->utot_failed = true;
         return 0;
     }
     g->gd->utot_wo = g->gd->utot_wp = 0;
     HIP_TRY(hipEventRecord(g->ev[4], g->stream));
-    hipLaunchKernelGGL(pw::unit_tot_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_lines, g->gd->d_clist, n_lines,
-                       wa.w_out, wa.w_prev, g->gd->d_utot);
+    hipLaunchKernelGGL(pw::unit_tot_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, g->stream, g->gd->d_lines.p, g->gd->d_clist.p, n_lines,
+                       wa.w_out, wa.w_prev, g->gd->d_utot.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(g->ev[5], g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -2770,10 +2666,10 @@ static int ensure_unit_tot(pw_graph *g, const pw::WalkArgs &wa, const LaneSwitch
 
 static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &sw, uint64_t *n_redo) {
     const uint64_t n_work = wa.job_list ? wa.n_list : wa.n_jobs;
-    if (g->redo.ensure(n_work ? n_work : 1)) return PW_ERR_NOMEM;
+    if (grow(g->redo, n_work ? n_work : 1)) return PW_ERR_NOMEM;
     pw::LanesArgs la = common_lanes_args(g, wa);
     la.susp_chunk = 1;
-    if (g->gd->d_utot && g->gd->utot_wo == wa.w_out && g->gd->utot_wp == wa.w_prev) la.tot_e = g->gd->d_utot;   // (ensure_unit_tot)
+    if (g->gd->d_utot.p && g->gd->utot_wo == wa.w_out && g->gd->utot_wp == wa.w_prev) la.tot_e = g->gd->d_utot.p;   // (ensure_unit_tot)
     // verification of the interval decision (round 6: lane_tight_values), as in launch_lane_walks: every settled step in test
     // mode, a sample of them in production -- of the steps the row totals let the interval decide
     VerifyPlan vp;
@@ -2859,7 +2755,7 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
     }
     g->rng_hold.valid = false;      // (g->rng is about to be overwritten: whatever was held is gone)
     g->rng_hold.user = false;
-    if (g->rng.ensure(n_blocks * 312)) return PW_ERR_NOMEM;
+    if (grow(g->rng, n_blocks * 312)) return PW_ERR_NOMEM;
     uint64_t per_gen = 1;
     int per_gen_log = 0;
     // generators: each level of the jump tree is a launch or two, each generator expands its blocks one after the other --
@@ -2870,7 +2766,7 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
     const uint32_t n_gen = (uint32_t)((n_blocks + per_gen - 1) / per_gen);
     if (!g->jump_table_ready) {
         const size_t words = (size_t)(pw::MtJump::MAX_POW2 + 1) * pw::MT_PW;
-        if (g->jump_table.ensure(words)) return PW_ERR_NOMEM;
+        if (grow(g->jump_table, words)) return PW_ERR_NOMEM;
         HIP_TRY(hipMemcpy(g->jump_table.p, pw::MtJump::instance().pow2_table(), words * sizeof(uint64_t),
                           hipMemcpyHostToDevice));
         g->jump_table_ready = true;
@@ -2892,15 +2788,15 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
         for (auto &c : g->mt_cache)
             if (!c.valid) { mc = &c; break; } else if (c.stamp < mc->stamp) mc = &c;
         mc->valid = false;
-        if (mc->states.ensure((size_t)pw::MT_N * n_gen)) return PW_ERR_NOMEM;
+        if (grow(mc->states, (size_t)pw::MT_N * n_gen)) return PW_ERR_NOMEM;
         if (!g->jump_tmp.p) {   // (a jump's polynomial taps are split over several workgroups: partial results, kept zeroed)
-            if (g->jump_tmp.ensure((size_t)256 * pw::MT_N)) return PW_ERR_NOMEM;
+            if (grow(g->jump_tmp, (size_t)256 * pw::MT_N)) return PW_ERR_NOMEM;
             HIP_TRY(hipMemsetAsync(g->jump_tmp.p, 0, sizeof(uint32_t) * 256 * pw::MT_N, g->stream));
         }
-        if (!g->seed_state) HIP_TRY(hipHostMalloc((void **)&g->seed_state, sizeof(uint32_t) * pw::MT_N, hipHostMallocDefault));
+        if (!g->seed_state.p) HIP_TRY(g->seed_state.alloc(pw::MT_N));
         HIP_TRY(hipStreamSynchronize(g->stream));   // (the pinned seed state of an earlier call has been consumed)
-        pw::mt_seed_state(g->seed_state, seed);
-        HIP_TRY(hipMemcpyAsync(mc->states.p, g->seed_state, sizeof(uint32_t) * pw::MT_N, hipMemcpyHostToDevice, g->stream));
+        pw::mt_seed_state(g->seed_state.p, seed);
+        HIP_TRY(hipMemcpyAsync(mc->states.p, g->seed_state.p, sizeof(uint32_t) * pw::MT_N, hipMemcpyHostToDevice, g->stream));
     }
     mc->stamp = ++g->mt_stamp;
     uint32_t *const mt_states = mc->states.p;
@@ -2950,7 +2846,7 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
 PW_EXPORT int pw_stream_hold(pw_graph *g, uint32_t seed, uint64_t stream_skip, uint64_t n_draws) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
-    if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
+    if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
     g->rng_hold.valid = false;
     g->rng_hold.user = false;
     if (!n_draws) return PW_OK;
@@ -2998,7 +2894,7 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
     if (n2vpp) { int rcn = n2vpp_check(g); if (rcn) return rcn; extend = 0; }   // (node2vec++ ignores extend)
     const bool spp = mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
     if (spp) { int rcn = spp_check(g); if (rcn) return rcn; extend = 0; }
-    if (extend && !g->gd->unit && !g->gd->d_thr)
+    if (extend && !g->gd->unit && !g->gd->d_thr.p)
         return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
     if (walk_length < 1) return fail(PW_ERR_INVALID, "walk_length must be >= 1");
@@ -3008,7 +2904,7 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
     memset(&st, 0, sizeof(st));
     if (n_jobs == 0) { if (stats) *stats = st; return PW_OK; }
     if (!has_seed) seed = os_seed();
-    if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
+    if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
     { int rcs = check_starts(g, d_starts, n_jobs); if (rcs) return rcs; }
     g->call_n2vpp = n2vpp;
     g->call_spp = spp;
@@ -3026,7 +2922,7 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
     if (rc) return rc;
 
     g->call_runnable = total / walk_length;
-    const bool lanes_pre = g->gd->kind == 0 && g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF;
+    const bool lanes_pre = g->gd->kind == 0 && g->gd->unit && g->gd->d_lines.p && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF;
     // (zero-fill of the walk matrix for the lane kernel: on the side stream, overlapped with the stream expansion.  No
     //  return path may leave that write to the CALLER's buffer in flight: the guard waits for the side stream.)
     struct SideGuard {
@@ -3263,7 +3159,7 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
     st.verify_dropped = g->ver_dropped;
     st.verify_ties = g->ver_ties;
     st.eager_steps = h[pw::CTR_EAGER];
-    st.index_max_list = g->gd->kind == 0 && g->gd->d_lines ? g->gd->list_max_len : 0u;
+    st.index_max_list = g->gd->kind == 0 && g->gd->d_lines.p ? g->gd->list_max_len : 0u;
     if (stats) *stats = st;
     return PW_OK;
 }
@@ -3305,7 +3201,7 @@ static int simulate_twin(pw_graph *g, const LaneSwitches &sw, int mode, double p
     if (!g->twin) g->twin = make_twin(g);
     pw_graph *t = g->twin;
     if (!t) return simulate_device_impl(g, sw, mode, p, q, extend, d_starts, n_jobs, walk_length, 1, seed, stream_skip, d_out, stats);
-    if (g->counters.ensure(N_COUNTERS)) return PW_ERR_NOMEM;
+    if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
     { int rcs = check_starts(g, d_starts, n_jobs); if (rcs) return rcs; }
     const uint64_t half = n_jobs / 2;
     const size_t W = (size_t)walk_length + 2;
@@ -3354,8 +3250,8 @@ PW_EXPORT int pw_simulate_device(pw_graph *g, int mode, double p, double q, int 
                                  pw_stats *stats) {
     const LaneSwitches sw = read_lane_switches();   // (this call's: passed down, never kept)
     // weighted CSR graphs on the lane index, whole job arrays of a million walks or more: two halves side by side (above)
-    if (g && g->gd->kind == 0 && !g->gd->unit && g->gd->d_lines && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF && n_jobs >= (1ull << 20) &&
-        d_starts && d_out && walk_length >= 1 && p > 0 && q > 0 && (!extend || g->gd->d_thr) && !sw.no_twin &&
+    if (g && g->gd->kind == 0 && !g->gd->unit && g->gd->d_lines.p && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF && n_jobs >= (1ull << 20) &&
+        d_starts && d_out && walk_length >= 1 && p > 0 && q > 0 && (!extend || g->gd->d_thr.p) && !sw.no_twin &&
         !sw.no_lanes && !sw.no_wlanes && wlanes_worth(sw, n_jobs)) {
         if (!has_seed) seed = os_seed();
         return simulate_twin(g, sw, mode, p, q, extend, d_starts, n_jobs, walk_length, seed, stream_skip, d_out, stats);
@@ -3392,11 +3288,7 @@ static int copy_out_staged(pw_graph *g, void *dst, const void *d_src, size_t byt
     bool pinned = bytes >= 2 * CH;
     if (pinned)
         for (auto &b : g->stage)
-            if (!b && hipHostMalloc(&b, CH, hipHostMallocDefault) != hipSuccess) {
-                b = nullptr;
-                (void)hipGetLastError();
-                pinned = false;   // no pinned memory: plain copy
-            }
+            if (!b.p && b.alloc(CH) != hipSuccess) pinned = false;   // no pinned memory: plain copy
     if (!pinned) {
         if (feed && !feed->have(bytes, true)) return 0;   // (the producer failed: its error is the call's)
         HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, g->copy_stream));
@@ -3429,7 +3321,7 @@ static int copy_out_staged(pw_graph *g, void *dst, const void *d_src, size_t byt
                 if (ring.stop) return;
             }
             const hipError_t e = hipEventSynchronize(g->ev_copy[c % NBUF]);
-            if (e == hipSuccess) memcpy((char *)dst + c * CH, g->stage[c % NBUF], chunk_len(c));
+            if (e == hipSuccess) memcpy((char *)dst + c * CH, g->stage[c % NBUF].p, chunk_len(c));
             {
                 std::lock_guard<std::mutex> l(ring.m);
                 if (e != hipSuccess) { ring.err = e; ring.stop = true; }
@@ -3458,7 +3350,7 @@ static int copy_out_staged(pw_graph *g, void *dst, const void *d_src, size_t byt
         }
         t_feed += t1 - t0;
         t_ring += now() - t1;
-        issue_err = hipMemcpyAsync(g->stage[c % NBUF], (const char *)d_src + c * CH, chunk_len(c), hipMemcpyDeviceToHost, g->copy_stream);
+        issue_err = hipMemcpyAsync(g->stage[c % NBUF].p, (const char *)d_src + c * CH, chunk_len(c), hipMemcpyDeviceToHost, g->copy_stream);
         if (issue_err == hipSuccess) issue_err = hipEventRecord(g->ev_copy[c % NBUF], g->copy_stream);
         if (issue_err != hipSuccess) break;
         { std::lock_guard<std::mutex> l(ring.m); ring.issued = c + 1; }
@@ -3482,7 +3374,6 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
                           uint64_t stream_skip, uint32_t *out, pw_stats *stats) {
     if (!g || (n_jobs && (!starts || !out))) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
-    uint32_t *d_starts = nullptr, *d_out = nullptr;
     const bool dbg = getenv("PECANPY_AMD_COPY_DEBUG") != nullptr;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
@@ -3514,9 +3405,11 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
     constexpr int R = 3;
     const uint64_t part_rows = (n_jobs + (uint64_t)n_parts - 1) / (uint64_t)n_parts + 1;
     const size_t out_elems = ring ? (size_t)R * part_rows * W : (size_t)n_jobs * W;
-    HIP_TRY(hipMalloc((void **)&d_starts, sizeof(uint32_t) * (n_jobs ? n_jobs : 1)));
-    hipError_t e = hipMalloc((void **)&d_out, sizeof(uint32_t) * (out_elems ? out_elems : 1));
-    if (e != hipSuccess) { (void)hipFree(d_starts); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
+    DevBuf<uint32_t> starts_buf, out_buf;
+    HIP_TRY(starts_buf.alloc(n_jobs));
+    hipError_t e = out_buf.alloc(out_elems);
+    if (e != hipSuccess) return fail(PW_ERR_NOMEM, hipGetErrorString(e));
+    uint32_t *const d_starts = starts_buf.p, *const d_out = out_buf.p;
     int rc = 0;
     const double t1 = now();
     e = hipMemcpy(d_starts, starts, sizeof(uint32_t) * n_jobs, hipMemcpyHostToDevice);
@@ -3542,7 +3435,7 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
         g->rng_hold.valid = false;        // (a caller's pw_stream_hold ends here: this call expands the stream of its own array)
         g->rng_hold.user = false;
         hold_guard.mine = true;
-        if (g->counters.ensure(N_COUNTERS)) rc = PW_ERR_NOMEM;
+        if (grow(g->counters, N_COUNTERS)) rc = PW_ERR_NOMEM;
         if (!rc) rc = check_starts(g, d_starts, n_jobs);
         uint64_t nominal = 0, base = 0;
         if (!rc) rc = compute_offsets(g, d_starts, nullptr, walk_length, n_jobs, stream_skip, false, &nominal, nullptr);
@@ -3609,8 +3502,8 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
     }
     if (!rc && stats) *stats = total;
     const double t4 = now();
-    (void)hipFree(d_starts);
-    (void)hipFree(d_out);
+    starts_buf.release();
+    out_buf.release();
     if (dbg) fprintf(stderr, "[pw_simulate] alloc %.1f ms, starts in %.1f, walks %.1f, matrix out %.1f, free %.1f (%d parts%s)\n", (t1 - t0) * 1e3,
                      (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (now() - t4) * 1e3, n_parts, ring ? ", ring of 3 buffers" : "");
     return rc;
@@ -3639,7 +3532,7 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
     if (n_sh == 1 && !out_on_device) return pw_simulate(handles[0], mode, p, q, extend, starts, n_jobs, walk_length, has_seed, seed, stream_skip, out, stats);
     struct Shard {
         uint64_t lo = 0, hi = 0, skip = 0, nominal = 0;
-        uint32_t *d_starts = nullptr, *d_tmp = nullptr;
+        DevBuf<uint32_t> d_starts, d_tmp;   // (on the shard's device: freed below with that device current)
         pw_stats st;
         int rc = 0;
         std::string err;
@@ -3687,13 +3580,13 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
             hipError_t e = hipSetDevice(g->device);
             // (PECANPY_AMD_MULTI_FORCE_PEER=1, tests on a one-GPU box: replicas on the first device take the peer-copy path too)
             const bool local = g->device == handles[0]->device && !(i > 0 && env_on("PECANPY_AMD_MULTI_FORCE_PEER"));
-            if (e == hipSuccess && !S.d_starts) {
-                e = hipMalloc((void **)&S.d_starts, sizeof(uint32_t) * n);
-                if (e == hipSuccess) e = hipMemcpy(S.d_starts, starts + S.lo, sizeof(uint32_t) * n, hipMemcpyHostToDevice);
-                if (e == hipSuccess && !local) e = hipMalloc((void **)&S.d_tmp, sizeof(uint32_t) * n * W);
+            if (e == hipSuccess && !S.d_starts.p) {
+                e = S.d_starts.alloc(n);
+                if (e == hipSuccess) e = hipMemcpy(S.d_starts.p, starts + S.lo, sizeof(uint32_t) * n, hipMemcpyHostToDevice);
+                if (e == hipSuccess && !local) e = S.d_tmp.alloc(n * W);
             }
             if (e != hipSuccess) { S.rc = PW_ERR_HIP; S.err = std::string("pw_simulate_multi: ") + hipGetErrorString(e); return; }
-            uint32_t *dst = local ? out + S.lo * W : S.d_tmp;
+            uint32_t *dst = local ? out + S.lo * W : S.d_tmp.p;
             // A shard on another GPU is walked in three chunks of decreasing size (3 : 2 : 1) and chunk c travels -- peer copy on
             // the handle's copy stream, one xGMI link -- while chunk c + 1 is walked: what stays exposed at the end is the
             // smallest chunk's transfer (the tapered chunks of bench.py's RCCL gather).  Chunk c + 1 is
@@ -3715,13 +3608,13 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
                 if (b == a) continue;
                 pw_stats st;
                 memset(&st, 0, sizeof(st));
-                S.rc = pw_simulate_device(g, mode, p, q, extend, S.d_starts + a, b - a, walk_length, 1, seed, skip_c, dst + a * W, &st);
+                S.rc = pw_simulate_device(g, mode, p, q, extend, S.d_starts.p + a, b - a, walk_length, 1, seed, skip_c, dst + a * W, &st);
                 if (S.rc) { S.err = g_err; break; }
                 skip_c += st.total_steps;
                 if (c == 0) tot = st;
                 else add_stats(tot, st, false);
                 if (!local) {   // (the walks of this chunk are complete: pw_simulate_device returns after its stream has drained)
-                    e = hipMemcpyPeerAsync(out + (S.lo + a) * W, handles[0]->device, S.d_tmp + a * W, g->device, sizeof(uint32_t) * (b - a) * W, g->copy_stream);
+                    e = hipMemcpyPeerAsync(out + (S.lo + a) * W, handles[0]->device, S.d_tmp.p + a * W, g->device, sizeof(uint32_t) * (b - a) * W, g->copy_stream);
                     if (e != hipSuccess) { S.rc = PW_ERR_HIP; S.err = std::string("pw_simulate_multi (peer copy): ") + hipGetErrorString(e); }
                 }
                 a = b;
@@ -3752,10 +3645,10 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
         if (S.rc && !rc) rc = fail(S.rc, S.err);
     }
     for (int i = 0; i < n_sh; i++) {
-        if (sh[i].d_starts || sh[i].d_tmp) {
+        if (sh[i].d_starts.p || sh[i].d_tmp.p) {
             (void)hipSetDevice(handles[i]->device);
-            if (sh[i].d_starts) (void)hipFree(sh[i].d_starts);
-            if (sh[i].d_tmp) (void)hipFree(sh[i].d_tmp);
+            sh[i].d_starts.release();
+            sh[i].d_tmp.release();
         }
     }
     if (!rc && first_open < n_sh) rc = fail(PW_ERR_HIP, "pw_simulate_multi: shard addressing did not settle");
@@ -3777,32 +3670,48 @@ PW_EXPORT int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, do
 // ---- single-step probe (Base.get_move_forward of the drop-in API; probability vectors for the parity tests) --------
 typedef void (*probe_kernel_fn)(pw::WalkArgs, const pw::ProbeArgs *);
 
+// What every probe does around its kernel: ProbeArgs up, the four output words zeroed, `launch(d_pa)` on g->stream, the words
+// (and, for pw_probs, the probabilities: probs_elem bytes each) back.  `what` names the probe in the error text.
+template <typename Launch>
+static int probe_shell(pw_graph *g, uint32_t cur, int has_prev, uint32_t prev, double r, void *probs_host, size_t probs_elem, uint32_t *out_host,
+                       const char *what, Launch launch) {
+    if (set_device(g)) return PW_ERR_HIP;
+    DevBuf<pw::ProbeArgs> d_pa;
+    DevBuf<uint32_t> d_out;
+    DevBuf<void> d_probs;
+    hipError_t e = d_pa.alloc(1);
+    if (e == hipSuccess) e = d_out.alloc(4);
+    if (e == hipSuccess && probs_host) e = d_probs.alloc(probs_elem * ((size_t)g->gd->max_degree + 1));
+    if (e != hipSuccess) return fail(PW_ERR_NOMEM, hipGetErrorString(e));
+    pw::ProbeArgs pa;
+    pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
+    pa.r = r; pa.probs = d_probs.p; pa.out = d_out.p;
+    uint32_t zero[4] = {0, 0, 0, 0};
+    e = hipMemcpyAsync(d_pa.p, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out.p, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) {
+        launch((const pw::ProbeArgs *)d_pa.p);
+        e = hipGetLastError();
+    }
+    uint32_t out[4] = {0, 0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, sizeof(out), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    if (e == hipSuccess && probs_host && out[2]) e = hipMemcpy(probs_host, d_probs.p, probs_elem * out[2], hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    out_host[0] = out[0]; out_host[1] = out[1]; out_host[2] = out[2];
+    return PW_OK;
+}
+
 // node2vec++: the walk kernel's value() and two loops on one wavefront (walk_dense_w.hip.h, dense_w_probe_kernel)
 static int run_probe_n2vpp(pw_graph *g, double p, double q, uint32_t cur, int has_prev, uint32_t prev, double r,
                            void *probs_host, uint32_t *out_host) {
-    if (set_device(g)) return PW_ERR_HIP;
-    pw::ProbeArgs *d_pa = nullptr;
-    uint32_t *d_out = nullptr;
-    double *d_probs = nullptr;
-    auto cleanup = [&]() {
-        if (d_pa) (void)hipFree(d_pa);
-        if (d_out) (void)hipFree(d_out);
-        if (d_probs) (void)hipFree(d_probs);
-    };
-    hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
-    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->gd->max_degree + 1));
-    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
-    pw::ProbeArgs pa;
-    pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
-    pa.r = r; pa.probs = d_probs; pa.out = d_out;
     pw::DenseWArgs da;
     memset(&da, 0, sizeof(da));
-    da.indptr = g->gd->d_indptr;
-    da.indices = g->gd->d_indices;
-    da.data = (const double *)g->gd->d_data;
-    da.adjbits = g->gd->d_adjbits;
-    da.thr = g->gd->d_thr;
+    da.indptr = g->gd->d_indptr.p;
+    da.indices = g->gd->d_indices.p;
+    da.data = (const double *)g->gd->d_data.p;
+    da.adjbits = g->gd->d_adjbits.p;
+    da.thr = g->gd->d_thr.p;
     da.n = g->gd->n_nodes;
     da.wpr = g->gd->words_per_row;
     da.p = p;
@@ -3810,60 +3719,18 @@ static int run_probe_n2vpp(pw_graph *g, double p, double q, uint32_t cur, int ha
     const size_t lds = (size_t)da.wpr * 12u;
     typedef void (*dwp_fn)(pw::DenseWArgs, const pw::ProbeArgs *);
     dwp_fn fn = g->gd->unit ? pw::dense_w_probe_kernel<pw::DW_N2VPP_UNIT> : pw::dense_w_probe_kernel<pw::DW_N2VPP>;
-    uint32_t zero[4] = {0, 0, 0, 0};
-    e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), lds, g->stream, da, (const pw::ProbeArgs *)d_pa);
-        e = hipGetLastError();
-    }
-    uint32_t out[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess && probs_host && out[2]) e = hipMemcpy(probs_host, d_probs, sizeof(double) * out[2], hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("node2vec++ single-step probe: ") + hipGetErrorString(e));
-    out_host[0] = out[0]; out_host[1] = out[1]; out_host[2] = out[2];
-    return PW_OK;
+    return probe_shell(g, cur, has_prev, prev, r, probs_host, sizeof(double), out_host, "node2vec++ single-step probe",
+                       [&](const pw::ProbeArgs *d_pa) { hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), lds, g->stream, da, d_pa); });
 }
 
 // node2vec++ on CSR: the walk kernel's value() and two loops on one wavefront (walk_sparse_pp.hip.h, sparse_pp_probe_kernel)
 static int run_probe_spp(pw_graph *g, double p, double q, uint32_t cur, int has_prev, uint32_t prev, double r,
                          void *probs_host, uint32_t *out_host) {
-    if (set_device(g)) return PW_ERR_HIP;
-    pw::ProbeArgs *d_pa = nullptr;
-    uint32_t *d_out = nullptr;
-    double *d_probs = nullptr;
-    auto cleanup = [&]() {
-        if (d_pa) (void)hipFree(d_pa);
-        if (d_out) (void)hipFree(d_out);
-        if (d_probs) (void)hipFree(d_probs);
-    };
-    hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
-    if (e == hipSuccess && probs_host) e = hipMalloc((void **)&d_probs, sizeof(double) * ((size_t)g->gd->max_degree + 1));
-    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
-    pw::ProbeArgs pa;
-    pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
-    pa.r = r; pa.probs = d_probs; pa.out = d_out;
     const pw::SparsePPArgs sa = spp_args(g, p, q);
     typedef void (*spp_probe_fn)(pw::SparsePPArgs, const pw::ProbeArgs *);
     spp_probe_fn fn = g->gd->unit ? pw::sparse_pp_probe_kernel<true> : pw::sparse_pp_probe_kernel<false>;
-    uint32_t zero[4] = {0, 0, 0, 0};
-    e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), 0, g->stream, sa, (const pw::ProbeArgs *)d_pa);
-        e = hipGetLastError();
-    }
-    uint32_t out[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess && probs_host && out[2]) e = hipMemcpy(probs_host, d_probs, sizeof(double) * out[2], hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("node2vec++ single-step probe: ") + hipGetErrorString(e));
-    out_host[0] = out[0]; out_host[1] = out[1]; out_host[2] = out[2];
-    return PW_OK;
+    return probe_shell(g, cur, has_prev, prev, r, probs_host, sizeof(double), out_host, "node2vec++ single-step probe",
+                       [&](const pw::ProbeArgs *d_pa) { hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), 0, g->stream, sa, d_pa); });
 }
 
 static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint32_t cur, int has_prev, uint32_t prev, double r,
@@ -3879,25 +3746,8 @@ static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint
     if (cur >= g->gd->n_nodes || (has_prev && prev >= g->gd->n_nodes)) return fail(PW_ERR_INVALID, "vertex out of range");
     if (mode == PW_MODE_NODE2VEC_PLUSPLUS) return run_probe_n2vpp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
     if (mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS) return run_probe_spp(g, p, q, cur, has_prev, prev, r, probs_host, out_host);
-    if (extend && !g->gd->unit && !g->gd->d_thr) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
-    if (set_device(g)) return PW_ERR_HIP;
+    if (extend && !g->gd->unit && !g->gd->d_thr.p) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     const bool ext = extend && !g->gd->unit;
-    const size_t elem = g->gd->kind == 0 ? sizeof(float) : sizeof(double);
-    pw::ProbeArgs *d_pa = nullptr;
-    uint32_t *d_out = nullptr;
-    void *d_probs = nullptr;
-    auto cleanup = [&]() {
-        if (d_pa) (void)hipFree(d_pa);
-        if (d_out) (void)hipFree(d_out);
-        if (d_probs) (void)hipFree(d_probs);
-    };
-    hipError_t e = hipMalloc((void **)&d_pa, sizeof(pw::ProbeArgs));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * sizeof(uint32_t));
-    if (e == hipSuccess && probs_host) e = hipMalloc(&d_probs, elem * ((size_t)g->gd->max_degree + 1));
-    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_NOMEM, hipGetErrorString(e)); }
-    pw::ProbeArgs pa;
-    pa.cur = cur; pa.has_prev = has_prev ? 1u : 0u; pa.prev = has_prev ? prev : 0u; pa.want_probs = probs_host ? 1u : 0u;
-    pa.r = r; pa.probs = d_probs; pa.out = d_out;
     pw::WalkArgs wa;
     memset(&wa, 0, sizeof(wa));
     wa.g = csr_dev(g);
@@ -3911,21 +3761,8 @@ static int run_probe(pw_graph *g, int mode, double p, double q, int extend, uint
                                     : (ext ? pw::step_probe_kernel<float, false, false, true> : pw::step_probe_kernel<float, false, false, false>);
     else fn = g->gd->unit ? pw::step_probe_kernel<double, true, true, false>
                       : (ext ? pw::step_probe_kernel<double, true, false, true> : pw::step_probe_kernel<double, true, false, false>);
-    uint32_t zero[4] = {0, 0, 0, 0};
-    e = hipMemcpyAsync(d_pa, &pa, sizeof(pa), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, zero, sizeof(zero), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), 0, g->stream, wa, (const pw::ProbeArgs *)d_pa);
-        e = hipGetLastError();
-    }
-    uint32_t out[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e == hipSuccess && probs_host && out[2]) e = hipMemcpy(probs_host, d_probs, elem * out[2], hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("single-step probe: ") + hipGetErrorString(e));
-    out_host[0] = out[0]; out_host[1] = out[1]; out_host[2] = out[2];
-    return PW_OK;
+    return probe_shell(g, cur, has_prev, prev, r, probs_host, g->gd->kind == 0 ? sizeof(float) : sizeof(double), out_host, "single-step probe",
+                       [&](const pw::ProbeArgs *d_pa) { hipLaunchKernelGGL(fn, dim3(1), dim3(pw::WAVE), 0, g->stream, wa, d_pa); });
 }
 
 PW_EXPORT int pw_step(pw_graph *g, int mode, double p, double q, int extend, uint32_t cur, int has_prev, uint32_t prev, double r,
@@ -3974,37 +3811,36 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     const size_t vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    uint32_t *d_table = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    float *d_syn1 = nullptr, *d_keep = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_table, (void *)d_cnt, (void *)d_syn1, (void *)d_keep})
-            if (q) (void)hipFree(q);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    };
-    auto bail = [&](int code, const std::string &msg) { cleanup(); return fail(code, msg); };
+    DevBuf<uint32_t> table_buf;
+    DevBuf<unsigned long long> cnt_buf;
+    DevBuf<float> syn1_buf, keep_buf;
+    struct Events {   // the pair around the training launches
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    } evs;
+    hipEvent_t &ev0 = evs.ev0, &ev1 = evs.ev1;
     auto t_vocab = clk::now();
     // d_cnt: [0, n_nodes) word counts, [n_nodes] first bad walk, [n_nodes + 1, n_nodes + 3) the training kernel's counters
-    hipError_t e = hipMalloc((void **)&d_cnt, sizeof(unsigned long long) * ((size_t)n_nodes + 3));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_syn1, vbytes);
+    hipError_t e = cnt_buf.alloc((size_t)n_nodes + 3);
+    if (e == hipSuccess) e = syn1_buf.alloc((size_t)n_nodes * dim);
+    unsigned long long *const d_cnt = cnt_buf.p;
+    float *const d_syn1 = syn1_buf.p;
     if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * ((size_t)n_nodes + 3));
     if (e == hipSuccess) e = hipMemset(d_cnt + n_nodes, 0xff, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(d_syn1, 0, vbytes);
-    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     // vocabulary statistics (and the check that the matrix only names nodes of the vocabulary)
     const uint64_t n_items = n_walks * (uint64_t)(L + 1);
     hipLaunchKernelGGL(pw::sgns_count_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, 0, d_walks, n_walks, L, n_nodes, d_cnt,
                        d_cnt + n_nodes);
     std::vector<unsigned long long> cnt((size_t)n_nodes + 1);
     e = hipMemcpy(cnt.data(), d_cnt, sizeof(unsigned long long) * ((size_t)n_nodes + 1), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     if (cnt[n_nodes] != ~0ull)
-        return bail(PW_ERR_INVALID, "walk " + std::to_string(cnt[n_nodes]) + ": node id >= n_nodes or length cell > walk_length + 1");
+        return fail(PW_ERR_INVALID, "walk " + std::to_string(cnt[n_nodes]) + ": node id >= n_nodes or length cell > walk_length + 1");
     double total = 0, pow_total = 0;
     for (uint32_t i = 0; i < n_nodes; i++) { total += (double)cnt[i]; pow_total += std::pow((double)cnt[i], 0.75); }
-    if (!(total > 0)) return bail(PW_ERR_INVALID, "the walk matrix holds no nodes");
+    if (!(total > 0)) return fail(PW_ERR_INVALID, "the walk matrix holds no nodes");
     // word2vec's unigram^0.75 table (a word that never occurs owns no slot) and subsampling probabilities
     const uint32_t table_size = (uint32_t)std::min<uint64_t>(1ull << 26, std::max<uint64_t>(1ull << 16, 16ull * n_nodes));
     std::vector<uint32_t> table(table_size);
@@ -4026,13 +3862,14 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
         for (uint32_t i = 0; i < n_nodes; i++)
             keep[i] = cnt[i] ? (float)std::min(1.0, (std::sqrt((double)cnt[i] / thr) + 1.0) * thr / (double)cnt[i]) : 1.0f;
     }
-    e = hipMalloc((void **)&d_table, sizeof(uint32_t) * (size_t)table_size);
+    e = table_buf.alloc(table_size);
+    uint32_t *const d_table = table_buf.p;
     if (e == hipSuccess) e = hipMemcpy(d_table, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
     if (e == hipSuccess && sample > 0) {
-        e = hipMalloc((void **)&d_keep, sizeof(float) * (size_t)n_nodes);
-        if (e == hipSuccess) e = hipMemcpy(d_keep, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
+        e = keep_buf.alloc(n_nodes);
+        if (e == hipSuccess) e = hipMemcpy(keep_buf.p, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     const double vocab_ms = ms_since(t_vocab);
     // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded; trained in place in the caller's buffer
     auto t_init = clk::now();
@@ -4049,11 +3886,11 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
     if (e == hipSuccess) e = hipEventCreate(&ev0);
     if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     const double init_ms = ms_since(t_init);
     pw::SgnsArgs a;
     a.walks = d_walks; a.n_walks = n_walks; a.L = L; a.dim = dim; a.window = window; a.negative = negative;
-    a.syn0 = d_vectors; a.syn1 = d_syn1; a.table = d_table; a.table_size = table_size; a.keep = d_keep;
+    a.syn0 = d_vectors; a.syn1 = d_syn1; a.table = d_table; a.table_size = table_size; a.keep = keep_buf.p;
     a.alpha = alpha; a.min_alpha = min_alpha; a.item_total = n_items * epochs; a.seed = seed;
     a.counters = d_cnt + n_nodes + 1;
     // concurrency.  workers == 1: ONE wavefront takes the walks in order (deterministic: the run gensim's workers=1
@@ -4095,7 +3932,6 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
     unsigned long long counters[2] = {0, 0};
     if (e == hipSuccess) e = hipEventElapsedTime(&train_ms, ev0, ev1);
     if (e == hipSuccess) e = hipMemcpy(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost);
-    cleanup();
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     if (stats) {
         stats->vocab_ms = vocab_ms; stats->init_ms = init_ms; stats->train_ms = train_ms;
@@ -4116,23 +3952,18 @@ PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks,
     if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
     const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2), vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    uint32_t *d_walks = nullptr;
-    float *d_vectors = nullptr;
-    auto cleanup = [&]() {
-        if (d_walks) (void)hipFree(d_walks);
-        if (d_vectors) (void)hipFree(d_vectors);
-    };
-    hipError_t e = hipMalloc((void **)&d_walks, wbytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_vectors, vbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_walks, walks, wbytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cleanup(); return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e)); }
-    int rc = pw_sgns_train_device(device, d_walks, n_walks, walk_length, n_nodes, dim, window, negative, epochs, alpha, min_alpha,
-                                  sample, seed, workers, d_vectors, nullptr);
+    DevBuf<uint32_t> d_walks;
+    DevBuf<float> d_vectors;
+    hipError_t e = d_walks.alloc((size_t)n_walks * ((size_t)walk_length + 2));
+    if (e == hipSuccess) e = d_vectors.alloc((size_t)n_nodes * dim);
+    if (e == hipSuccess) e = hipMemcpy(d_walks.p, walks, wbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    int rc = pw_sgns_train_device(device, d_walks.p, n_walks, walk_length, n_nodes, dim, window, negative, epochs, alpha, min_alpha,
+                                  sample, seed, workers, d_vectors.p, nullptr);
     if (rc == PW_OK) {
-        e = hipMemcpy(vectors, d_vectors, vbytes, hipMemcpyDeviceToHost);
+        e = hipMemcpy(vectors, d_vectors.p, vbytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     }
-    cleanup();
     return rc;
 }
 
@@ -4171,24 +4002,23 @@ struct TextFile {
     const std::string who;   // the entry's name in the error texts
     const std::string path;
     FILE *file = nullptr;
-    std::vector<void *> dev;
-    void *pinned[2] = {nullptr, nullptr};
+    PinnedBuf<void> pinned[2];
     bool queued = false;   // work may be in flight on the default stream
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int n_cu = 1;
-    uint64_t *d_row_off = nullptr, *d_tmp = nullptr;   // uint64[n_rows + 1]: byte counts, then offsets; the scan's tile sums
-    uint32_t *d_flags = nullptr;                       // one word the fill kernel raises
+    DevBuf<uint64_t> d_row_off, d_tmp;       // uint64[n_rows + 1]: byte counts, then offsets; the scan's tile sums
+    DevBuf<uint32_t> d_flags;                // one word the fill kernel raises
+    DevBuf<char> d_ids, d_buf;               // the names' characters; the text of one chunk
+    DevBuf<uint64_t> d_id_off;               // the names' offsets
     std::vector<uint64_t> row_off;                     // host copy: row_off[i] = offset of row i behind the header, [n_rows] = total
     double format_ms = 0, copy_ms = 0, write_ms = 0;
     uint64_t header_bytes = 0, n_chunks = 0;
 
     TextFile(const char *who_, const char *path_) : who(who_), path(path_) {}
     TextFile(const TextFile &) = delete;
-    ~TextFile() {
+    ~TextFile() {   // (the buffers go behind this body: nothing of the call is in flight by then)
         if (queued) (void)hipStreamSynchronize(nullptr);
         if (file) (void)fclose(file);
-        for (void *q : dev) if (q) (void)hipFree(q);
-        for (void *q : pinned) if (q) (void)hipHostFree(q);
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     }
     int write_failed() const { return fail(PW_ERR_INVALID, who + ": cannot write " + path + ": " + strerror(errno)); }
@@ -4208,24 +4038,21 @@ struct TextFile {
         for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
         return 0;
     }
-    int alloc(void **p, uint64_t bytes) {
-        *p = nullptr;
-        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            return fail(PW_ERR_NOMEM, who + ": " + std::to_string(bytes) + " bytes do not fit in device memory: " + hipGetErrorString(e));
-        }
-        dev.push_back(*p);
-        return 0;
+    template <typename T> int alloc(DevBuf<T> &buf, uint64_t n) {
+        const hipError_t e = buf.alloc(n);
+        if (e == hipSuccess) return 0;
+        return fail(PW_ERR_NOMEM, who + ": " + std::to_string(n * sizeof(T)) + " bytes do not fit in device memory: " + hipGetErrorString(e));
     }
-    int alloc_rows(uint64_t n_rows) {
+    // the names of the call on the device, and the per-row buffers of the count pass
+    int alloc_rows(uint64_t n_rows, const char *id_chars, const uint64_t *id_offsets, uint64_t n_names) {
         int rc;
-        if ((rc = alloc((void **)&d_row_off, sizeof(uint64_t) * (n_rows + 1))) ||
-            (rc = alloc((void **)&d_tmp, sizeof(uint64_t) * emb_scan_tmp_elems(n_rows + 1))) || (rc = alloc((void **)&d_flags, sizeof(uint32_t))))
+        if ((rc = alloc(d_ids, id_offsets[n_names])) || (rc = alloc(d_id_off, n_names + 1)) || (rc = alloc(d_row_off, n_rows + 1)) ||
+            (rc = alloc(d_tmp, emb_scan_tmp_elems(n_rows + 1))) || (rc = alloc(d_flags, 1)))
             return rc;
-        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), nullptr));
-        HIP_TRY(hipMemsetAsync(d_row_off + n_rows, 0, sizeof(uint64_t), nullptr));   // (the scan's last input: its output is the total)
+        if (id_offsets[n_names]) HIP_TRY(hipMemcpyAsync(d_ids.p, id_chars, id_offsets[n_names], hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d_id_off.p, id_offsets, sizeof(uint64_t) * (n_names + 1), hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), nullptr));
+        HIP_TRY(hipMemsetAsync(d_row_off.p + n_rows, 0, sizeof(uint64_t), nullptr));   // (the scan's last input: its output is the total)
         return 0;
     }
     // blocks of four wavefronts for one wavefront per row, rows strided over the grid
@@ -4237,11 +4064,11 @@ struct TextFile {
         return 0;
     }
     int count_end(uint64_t n_rows) {
-        emb_exclusive_scan(d_row_off, n_rows + 1, d_tmp);
+        emb_exclusive_scan(d_row_off.p, n_rows + 1, d_tmp.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[1], nullptr));
         row_off.resize(n_rows + 1);
-        HIP_TRY(hipMemcpyAsync(row_off.data(), d_row_off, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipMemcpyAsync(row_off.data(), d_row_off.p, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost, nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -4260,15 +4087,11 @@ struct TextFile {
 
         // chunks: consecutive rows while their text fits the budget (one row always does)
         const uint64_t buf_bytes = std::min(budget, total);
-        char *d_buf = nullptr;
         int rc;
-        if ((rc = alloc((void **)&d_buf, buf_bytes))) return rc;
+        if ((rc = alloc(d_buf, buf_bytes))) return rc;
         for (auto &p : pinned) {
-            hipError_t e = hipHostMalloc(&p, buf_bytes, hipHostMallocDefault);
-            if (e != hipSuccess) {
-                p = nullptr;
-                return fail(PW_ERR_NOMEM, who + ": pinned host buffer: " + hipGetErrorString(e));
-            }
+            const hipError_t e = p.alloc(buf_bytes);
+            if (e != hipSuccess) return fail(PW_ERR_NOMEM, who + ": pinned host buffer: " + hipGetErrorString(e));
         }
         struct Chunk { uint64_t lo, hi; };
         auto next_chunk = [&](uint64_t lo) {
@@ -4280,10 +4103,10 @@ struct TextFile {
         // slot s = chunk index & 1: events 2 + 3 s .. 4 + 3 s = fill begin, fill end, copy end
         auto issue = [&](const Chunk &c, int s) -> int {
             HIP_TRY(hipEventRecord(ev[2 + 3 * s], nullptr));
-            fill(c.lo, c.hi, grid(c.hi - c.lo), d_buf);
+            fill(c.lo, c.hi, grid(c.hi - c.lo), d_buf.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ev[3 + 3 * s], nullptr));
-            HIP_TRY(hipMemcpyAsync(pinned[s], d_buf, row_off[c.hi] - row_off[c.lo], hipMemcpyDeviceToHost, nullptr));
+            HIP_TRY(hipMemcpyAsync(pinned[s].p, d_buf.p, row_off[c.hi] - row_off[c.lo], hipMemcpyDeviceToHost, nullptr));
             HIP_TRY(hipEventRecord(ev[4 + 3 * s], nullptr));
             return 0;
         };
@@ -4305,14 +4128,14 @@ struct TextFile {
             copy_ms += ms_copy;
             const uint64_t bytes = row_off[cur.hi] - row_off[cur.lo];
             const auto t0 = clk::now();
-            if (fwrite(pinned[s], 1, bytes, file) != bytes) return write_failed();
+            if (fwrite(pinned[s].p, 1, bytes, file) != bytes) return write_failed();
             write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
             n_chunks++;
             if (cur.hi >= n_rows) break;
             cur = nxt;
         }
         uint32_t flags = 0;
-        HIP_TRY(hipMemcpyAsync(&flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(hipMemcpyAsync(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost, nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
         if (flags) return fail(PW_ERR_HIP, who + ": the fill pass disagreed with the count pass (internal error)");
         const auto t0 = clk::now();
@@ -4354,7 +4177,6 @@ PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, u
     uint64_t longest_name = 0;
     int rc;
     if ((rc = check_names(who, "row", id_chars, id_offsets, n_rows, &longest_name))) return rc;
-    const uint64_t id_bytes = id_offsets[n_rows];
     const int n_dev = pw_device_count();
     if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
     if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
@@ -4364,21 +4186,15 @@ PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, u
 
     TextFile out(who, path);
     if ((rc = out.open(std::to_string(n_rows) + " " + std::to_string(dim) + "\n")) || (rc = out.begin(device))) return rc;
-    char *d_ids = nullptr;
-    uint64_t *d_id_off = nullptr;
-    if ((rc = out.alloc((void **)&d_ids, id_bytes)) || (rc = out.alloc((void **)&d_id_off, sizeof(uint64_t) * (n_rows + 1))) ||
-        (rc = out.alloc_rows(n_rows)))
-        return rc;
-    if (id_bytes) HIP_TRY(hipMemcpyAsync(d_ids, id_chars, id_bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d_id_off, id_offsets, sizeof(uint64_t) * (n_rows + 1), hipMemcpyHostToDevice, nullptr));
+    if ((rc = out.alloc_rows(n_rows, id_chars, id_offsets, n_rows))) return rc;
 
     if ((rc = out.count_begin())) return rc;
-    hipLaunchKernelGGL(pw::emb_count_kernel, dim3(out.grid(n_rows)), dim3(256), 0, nullptr, d_vectors, n_rows, dim, (const uint64_t *)d_id_off,
-                       out.d_row_off);
+    hipLaunchKernelGGL(pw::emb_count_kernel, dim3(out.grid(n_rows)), dim3(256), 0, nullptr, d_vectors, n_rows, dim, (const uint64_t *)out.d_id_off.p,
+                       out.d_row_off.p);
     if ((rc = out.count_end(n_rows))) return rc;
     rc = out.write_chunks(budget, row_max, [&](uint64_t lo, uint64_t hi, unsigned blocks, char *d_buf) {
-        hipLaunchKernelGGL(pw::emb_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_vectors, lo, hi, dim, (const char *)d_ids,
-                           (const uint64_t *)d_id_off, (const uint64_t *)out.d_row_off, d_buf, out.d_flags);
+        hipLaunchKernelGGL(pw::emb_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_vectors, lo, hi, dim, (const char *)out.d_ids.p,
+                           (const uint64_t *)out.d_id_off.p, (const uint64_t *)out.d_row_off.p, d_buf, out.d_flags.p);
     });
     if (rc) return rc;
     if (stats) {
@@ -4399,16 +4215,13 @@ PW_EXPORT int pw_vectors_write_text(int device, const float *vectors, uint64_t n
     if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
     const size_t vbytes = sizeof(float) * (size_t)n_rows * dim;
-    float *d_vectors = nullptr;
-    hipError_t e = hipMalloc((void **)&d_vectors, vbytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    DevBuf<float> d_vectors;
+    hipError_t e = d_vectors.alloc((size_t)n_rows * dim);
+    if (e != hipSuccess)
         return fail(PW_ERR_NOMEM, std::string("pw_vectors_write_text: the matrix does not fit in device memory: ") + hipGetErrorString(e));
-    }
-    e = hipMemcpy(d_vectors, vectors, vbytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? pw_vectors_write_text_device(device, d_vectors, n_rows, dim, id_chars, id_offsets, path, stats)
+    e = hipMemcpy(d_vectors.p, vectors, vbytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? pw_vectors_write_text_device(device, d_vectors.p, n_rows, dim, id_chars, id_offsets, path, stats)
                              : fail(PW_ERR_HIP, std::string("pw_vectors_write_text: ") + hipGetErrorString(e));
-    (void)hipFree(d_vectors);
     return rc;
 }
 
@@ -4425,7 +4238,6 @@ PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, ui
     if (longest_name > pw::WALK_NAME_MAX)
         return fail(PW_ERR_INVALID, "pw_walks_write_text: a name of " + std::to_string(longest_name) + " bytes (at most " +
                                         std::to_string(pw::WALK_NAME_MAX) + ")");
-    const uint64_t id_bytes = id_offsets[n_names];
     const int n_dev = pw_device_count();
     if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
     if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
@@ -4433,6 +4245,8 @@ PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, ui
     const uint64_t row_max = ((uint64_t)walk_length + 1) * (longest_name + 1);
     const uint64_t budget = chunk_budget("PECANPY_AMD_WALKS_CHUNK_BYTES", row_max);
 
+    DevBuf<unsigned long long> d_found;   // the count kernel's findings: lowest row with a bad length, with a bad token; tokens
+                                          // (declared before `out`: it goes after ~TextFile has waited for the stream)
     TextFile out(who, path);
     if ((rc = out.open(""))) return rc;
     if (stats) *stats = pw_walks_write_stats{0, 0, 0, 0, 0, 0, 0};
@@ -4442,23 +4256,16 @@ PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, ui
         return fclose(f) == 0 ? PW_OK : out.write_failed();
     }
     if ((rc = out.begin(device))) return rc;
-    char *d_ids = nullptr;
-    uint64_t *d_id_off = nullptr;
-    unsigned long long *d_found = nullptr;   // the count kernel's findings: lowest row with a bad length, with a bad token; tokens
-    if ((rc = out.alloc((void **)&d_ids, id_bytes)) || (rc = out.alloc((void **)&d_id_off, sizeof(uint64_t) * (n_names + 1))) ||
-        (rc = out.alloc((void **)&d_found, sizeof(unsigned long long) * 3)) || (rc = out.alloc_rows(n_walks)))
-        return rc;
-    if (id_bytes) HIP_TRY(hipMemcpyAsync(d_ids, id_chars, id_bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d_id_off, id_offsets, sizeof(uint64_t) * (n_names + 1), hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemsetAsync(d_found, 0xff, sizeof(unsigned long long) * 2, nullptr));
-    HIP_TRY(hipMemsetAsync(d_found + 2, 0, sizeof(unsigned long long), nullptr));
+    if ((rc = out.alloc_rows(n_walks, id_chars, id_offsets, n_names)) || (rc = out.alloc(d_found, 3))) return rc;
+    HIP_TRY(hipMemsetAsync(d_found.p, 0xff, sizeof(unsigned long long) * 2, nullptr));
+    HIP_TRY(hipMemsetAsync(d_found.p + 2, 0, sizeof(unsigned long long), nullptr));
 
     if ((rc = out.count_begin())) return rc;
     hipLaunchKernelGGL(pw::walk_text_count_kernel, dim3(out.grid(n_walks)), dim3(256), 0, nullptr, d_walks, n_walks, walk_length,
-                       (const uint64_t *)d_id_off, n_names, out.d_row_off, d_found);
+                       (const uint64_t *)out.d_id_off.p, n_names, out.d_row_off.p, d_found.p);
     if ((rc = out.count_end(n_walks))) return rc;
     unsigned long long found[3];
-    HIP_TRY(hipMemcpy(found, d_found, sizeof(found), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(found, d_found.p, sizeof(found), hipMemcpyDeviceToHost));
     const uint64_t width = (uint64_t)walk_length + 2;
     if (found[0] != ~0ull) {   // nothing of the matrix was looked up, and no fill pass runs: the file stays empty
         uint32_t len = 0;
@@ -4475,8 +4282,8 @@ PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, ui
                                         " of row " + std::to_string(found[1]) + " outside the " + std::to_string(n_names) + " names");
     }
     rc = out.write_chunks(budget, row_max, [&](uint64_t lo, uint64_t hi, unsigned blocks, char *d_buf) {
-        hipLaunchKernelGGL(pw::walk_text_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_walks, lo, hi, walk_length, (const char *)d_ids,
-                           (const uint64_t *)d_id_off, n_names, (const uint64_t *)out.d_row_off, d_buf, out.d_flags);
+        hipLaunchKernelGGL(pw::walk_text_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_walks, lo, hi, walk_length, (const char *)out.d_ids.p,
+                           (const uint64_t *)out.d_id_off.p, n_names, (const uint64_t *)out.d_row_off.p, d_buf, out.d_flags.p);
     });
     if (rc) return rc;
     if (stats) {
@@ -4499,16 +4306,13 @@ PW_EXPORT int pw_walks_write_text(int device, const uint32_t *walks, uint64_t n_
     if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
     const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2);
-    uint32_t *d_walks = nullptr;
-    hipError_t e = hipMalloc((void **)&d_walks, wbytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    DevBuf<uint32_t> d_walks;
+    hipError_t e = d_walks.alloc((size_t)n_walks * ((size_t)walk_length + 2));
+    if (e != hipSuccess)
         return fail(PW_ERR_NOMEM, std::string("pw_walks_write_text: the matrix does not fit in device memory: ") + hipGetErrorString(e));
-    }
-    e = hipMemcpy(d_walks, walks, wbytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? pw_walks_write_text_device(device, d_walks, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats)
+    e = hipMemcpy(d_walks.p, walks, wbytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? pw_walks_write_text_device(device, d_walks.p, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats)
                              : fail(PW_ERR_HIP, std::string("pw_walks_write_text: ") + hipGetErrorString(e));
-    (void)hipFree(d_walks);
     return rc;
 }
 
@@ -4530,27 +4334,22 @@ PW_EXPORT int pw_selftest_format_f6(int on_device, int device, const float *x, u
     if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
-    float *d_x = nullptr;
-    char *d_chars = nullptr;
-    uint32_t *d_lens = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_x, (void *)d_chars, (void *)d_lens})
-            if (q) (void)hipFree(q);
-    };
+    DevBuf<float> d_x;
+    DevBuf<char> d_chars;
+    DevBuf<uint32_t> d_lens;
     const size_t cbytes = (size_t)n * pw::F6_SLOT;
-    hipError_t e = hipMalloc((void **)&d_x, sizeof(float) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_chars, cbytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_lens, sizeof(uint32_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(d_x, x, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_chars, 0, cbytes);
+    hipError_t e = d_x.alloc(n);
+    if (e == hipSuccess) e = d_chars.alloc(cbytes);
+    if (e == hipSuccess) e = d_lens.alloc(n);
+    if (e == hipSuccess) e = hipMemcpy(d_x.p, x, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_chars.p, 0, cbytes);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::f6_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)d_x, n, d_chars, d_lens);
+        hipLaunchKernelGGL(pw::f6_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)d_x.p, n, d_chars.p, d_lens.p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(chars, d_chars, cbytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(lens, d_lens, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = hipMemcpy(chars, d_chars.p, cbytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(lens, d_lens.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_format_f6: ") + hipGetErrorString(e));
     return PW_OK;
 }
@@ -4802,37 +4601,32 @@ PW_EXPORT int pw_selftest_lane_floats(int on_device, int device, const uint8_t *
     if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
-    uint8_t *d_cls = nullptr;
-    void *d_cl = nullptr;
-    double *d_r = nullptr;
-    uint32_t *d_chain = nullptr, *d_lane = nullptr;
-    float *d_tots = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_cls, d_cl, (void *)d_r, (void *)d_chain, (void *)d_lane, (void *)d_tots})
-            if (q) (void)hipFree(q);
-    };
+    DevBuf<uint8_t> d_cls;
+    DevBuf<void> d_cl;
+    DevBuf<double> d_r;
+    DevBuf<uint32_t> d_chain, d_lane;
+    DevBuf<float> d_tots;
     const size_t cl_bytes = row.wide ? row.cl32.size() * sizeof(uint32_t) : row.cl16.size() * sizeof(uint16_t);
     const void *cl_host = row.wide ? (const void *)row.cl32.data() : (const void *)row.cl16.data();
     const size_t nr = n_r ? n_r : 1;
-    hipError_t e = hipMalloc((void **)&d_cls, n);
-    if (e == hipSuccess) e = hipMalloc(&d_cl, cl_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_r, sizeof(double) * nr);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_chain, sizeof(uint32_t) * nr);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_lane, sizeof(uint32_t) * nr);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tots, sizeof(float) * 2 * nr);
-    if (e == hipSuccess) e = hipMemcpy(d_cls, cls, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cl, cl_host, cl_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_r) e = hipMemcpy(d_r, r, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice);
+    hipError_t e = d_cls.alloc(n);
+    if (e == hipSuccess) e = d_cl.alloc(cl_bytes);
+    if (e == hipSuccess) e = d_r.alloc(nr);
+    if (e == hipSuccess) e = d_chain.alloc(nr);
+    if (e == hipSuccess) e = d_lane.alloc(nr);
+    if (e == hipSuccess) e = d_tots.alloc(2 * nr);
+    if (e == hipSuccess) e = hipMemcpy(d_cls.p, cls, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_cl.p, cl_host, cl_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_r) e = hipMemcpy(d_r.p, r, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice);
     if (e == hipSuccess && n_r) {
-        hipLaunchKernelGGL(pw::lane_floats_selftest_kernel, dim3((n_r + 255) / 256), dim3(256), 0, 0, d_cls, n, d_cl, row.wide, row.piv_off, row.n_cl,
-                           row.pp, w_out, w_prev, d_r, n_r, d_chain, d_lane, d_tots);
+        hipLaunchKernelGGL(pw::lane_floats_selftest_kernel, dim3((n_r + 255) / 256), dim3(256), 0, 0, d_cls.p, n, d_cl.p, row.wide, row.piv_off, row.n_cl,
+                           row.pp, w_out, w_prev, d_r.p, n_r, d_chain.p, d_lane.p, d_tots.p);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(chain, d_chain, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(lane, d_lane, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(tots, d_tots, sizeof(float) * 2 * (size_t)n_r, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(chain, d_chain.p, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(lane, d_lane.p, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(tots, d_tots.p, sizeof(float) * 2 * (size_t)n_r, hipMemcpyDeviceToHost);
     }
-    cleanup();
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_lane_floats: ") + hipGetErrorString(e));
     return PW_OK;
 }
@@ -4937,34 +4731,29 @@ PW_EXPORT int pw_selftest_lane(int on_device, int device, const uint8_t *cls, ui
     if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
     HIP_TRY(hipSetDevice(device));
-    uint8_t *d_cls = nullptr;
-    void *d_cl = nullptr;
-    double *d_r = nullptr;
-    uint32_t *d_chain = nullptr, *d_out = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_cls, d_cl, (void *)d_r, (void *)d_chain, (void *)d_out})
-            if (q) (void)hipFree(q);
-    };
+    DevBuf<uint8_t> d_cls;
+    DevBuf<void> d_cl;
+    DevBuf<double> d_r;
+    DevBuf<uint32_t> d_chain, d_out;
     const size_t cl_bytes = row.wide ? row.cl32.size() * sizeof(uint32_t) : row.cl16.size() * sizeof(uint16_t);
     const void *cl_host = row.wide ? (const void *)row.cl32.data() : (const void *)row.cl16.data();
-    hipError_t e = hipMalloc((void **)&d_cls, n);
-    if (e == hipSuccess) e = hipMalloc(&d_cl, cl_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_r, sizeof(double) * (size_t)(n_r ? n_r : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_chain, sizeof(uint32_t) * (size_t)(n_r ? n_r : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(uint32_t) * 4 * (size_t)(n_r ? n_r : 1));
-    if (e == hipSuccess) e = hipMemcpy(d_cls, cls, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cl, cl_host, cl_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_r) e = hipMemcpy(d_r, r, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice);
+    hipError_t e = d_cls.alloc(n);
+    if (e == hipSuccess) e = d_cl.alloc(cl_bytes);
+    if (e == hipSuccess) e = d_r.alloc(n_r);
+    if (e == hipSuccess) e = d_chain.alloc(n_r);
+    if (e == hipSuccess) e = d_out.alloc(4 * (size_t)n_r);
+    if (e == hipSuccess) e = hipMemcpy(d_cls.p, cls, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_cl.p, cl_host, cl_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_r) e = hipMemcpy(d_r.p, r, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice);
     std::vector<uint32_t> out4((size_t)4 * n_r);
     if (e == hipSuccess && n_r) {
-        hipLaunchKernelGGL(pw::lane_selftest_kernel, dim3((n_r + 255) / 256), dim3(256), 0, 0, d_cls, n, d_cl, row.wide, row.piv_off, row.n_cl, row.pp,
-                           w_out, w_prev, d_r, n_r, d_chain, d_out);
+        hipLaunchKernelGGL(pw::lane_selftest_kernel, dim3((n_r + 255) / 256), dim3(256), 0, 0, d_cls.p, n, d_cl.p, row.wide, row.piv_off, row.n_cl, row.pp,
+                           w_out, w_prev, d_r.p, n_r, d_chain.p, d_out.p);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(chain, d_chain, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out4.data(), d_out, sizeof(uint32_t) * 4 * (size_t)n_r, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(chain, d_chain.p, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out4.data(), d_out.p, sizeof(uint32_t) * 4 * (size_t)n_r, hipMemcpyDeviceToHost);
     }
-    cleanup();
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_lane: ") + hipGetErrorString(e));
     for (uint32_t i = 0; i < n_r; i++) {
         lane[i] = out4[4 * (size_t)i]; kmax[i] = out4[4 * (size_t)i + 1]; tight[i] = out4[4 * (size_t)i + 2];
