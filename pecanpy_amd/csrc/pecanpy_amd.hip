@@ -2952,6 +2952,10 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
     wa.stream_off = g->stream_off.p;
     wa.job_list = nullptr;
     wa.n_list = 0;
+    // (the lane kernel loads the draws as aligned 16-byte pairs: the block must start on such a boundary and hold an even number
+    //  of doubles -- whole blocks of 312 from an allocation's base do)
+    if (((uintptr_t)g->rng.p & 15u) != 0 || (g->rng.cap & 1u) != 0)
+        return fail(PW_ERR_INVALID, "stream buffer is not made of aligned pairs of draws");
     wa.rng = g->rng.p;
     wa.rng_base = rng_base;
     wa.out = d_out;

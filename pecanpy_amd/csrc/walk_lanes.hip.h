@@ -274,7 +274,7 @@ __device__ unsigned long long g_lprof[16];
                     for (uint32_t z_ = A.j; z_ <= L; z_++) row_[z_] = 0;                        \
                 }                                                                               \
                 A.flags = 0;                                                                    \
-            } else if (!(draw_prefetched_)) r = a.rng[A.soff + (A.j - 1)];   /* the next step's draw, asked for now */ \
+            } else if (!(draw_prefetched_)) next_draw(A.soff + (A.j - 1));   /* the next step's draw, asked for now (in pairs) */ \
     } while (0)
 
 // ---- a binade with a ROUNDING TIE, walked by the whole wavefront (round 6) ------------------------------------------------------
@@ -572,6 +572,29 @@ walk_lanes_kernel(LanesArgs a) {
     OutCells ob = {{0u, 0u, 0u, 0u}};   // staged output cells of the current walk
     float tot = 1.0f, wo = 1.0f;
     uint32_t kmax = 0;
+    // DRAW PAIRS: a walk's draws are consecutive doubles of the stream, and between two steps of a walk the sector that holds them
+    // has left the L2 -- every 8-byte draw load went out to the fabric as a request of its own, as dear as an edge line.  The draws
+    // are fetched as ALIGNED 16-byte PAIRS instead (aligned by byte address: a shard's stream_skip or a held stream cannot shift the
+    // parity; the host checks that the buffer starts on a 16-byte boundary and holds an even number of doubles, so a pair never
+    // leaves it): a load at an even draw keeps its neighbour in r_held for the walk's next step, which then issues no load -- one
+    // request per two steps.  The pair lands in (r, r_held) as it is; a load at an odd draw wanted the second double (take_hi), and
+    // the move is made where the next step begins, not behind the load: the load stays in flight beside the line fetch.
+    // The held draw belongs to the walk in this lane and is dropped wherever a lane takes a walk up (fresh job, settled pool slot,
+    // resumed queue record): pool slots, queue records and the job window do not carry it.
+    double r_held = 0.0;
+    bool held = false, take_hi = false;
+    // (not in the WEIGHTED queueing form: the two registers take it from six waves per SIMD to five)
+    constexpr bool PAIRS = !WEIGHTED || INPLACE;
+    auto next_draw = [&](uint64_t idx) {   // r <- draw #idx of this call's stream block, for the walk this lane holds
+        if (!PAIRS) { r = a.rng[idx]; return; }
+        if (held) { r = r_held; held = false; return; }
+        const double *pa = a.rng + idx;
+        const uint32_t off = (uint32_t)(uintptr_t)pa & 8u;   // (bit 3 of the byte address: the draw is the pair's second double)
+        const bool odd = off != 0u;
+        const double2 pr = *(const double2 *)((const char *)pa - off);
+        r = pr.x; r_held = pr.y;
+        take_hi = odd; held = !odd;
+    };
 
     typedef __attribute__((address_space(3))) void *lds_ptr_t;
     typedef const __attribute__((address_space(1))) void *glb_ptr_t;
@@ -735,6 +758,7 @@ walk_lanes_kernel(LanesArgs a) {
                     A.soff = ((uint64_t)p2.z << 32) | p2.y;
                     ob.v[0] = pool[3][sl].w; ob.v[1] = p4.z; ob.v[2] = p4.w;
                     A.flags = F_ACTIVE | F_PRE;
+                    held = false; take_hi = false;
                 }
                 m_set &= ~ballot(give);
                 wave_lds_fence();
@@ -816,6 +840,7 @@ walk_lanes_kernel(LanesArgs a) {
                     A.s0 = j0.z; A.d = j0.w; A.n_in = 0; A.pp = NOT_FOUND; A.e = WEIGHTED ? j0.y : 0u; A.coff = 0; A.j = 1;
                     r = __longlong_as_double((long long)(((unsigned long long)j1.w << 32) | j1.z));
                     A.flags = F_ACTIVE;
+                    held = false; take_hi = false;
                 }
                 win_pos += take_w;
                 continue;
@@ -839,6 +864,7 @@ walk_lanes_kernel(LanesArgs a) {
                     if (slot >= 2u) ob.v[1] = cell[1];
                     if (slot >= 3u) ob.v[2] = cell[2];
                     A.flags = F_ACTIVE | F_PRE;
+                    held = false; take_hi = false;
                 }
             }
         }
@@ -856,6 +882,7 @@ walk_lanes_kernel(LanesArgs a) {
         // their chains together once a few have gathered or nothing else can run.
         uint32_t choice = LANE_AMBIGUOUS;
         const bool runnable = A.flags == F_ACTIVE;
+        if (PAIRS && take_hi) { r = r_held; take_hi = false; }   // (the pair of an odd draw: its second double is the step's)
         if (FLOATS) {
             if (runnable && A.n_in != 0u && !edge_list_stored(A.d, A.n_in, A.coff)) choice = LANE_NEEDS_WAVE;   // (partial index)
             else if (runnable && a.tot_e) {
@@ -1208,7 +1235,7 @@ walk_lanes_kernel(LanesArgs a) {
             // the pass has just issued.)
             bool fetch = false;
             if (A.flags == F_ACTIVE && choice != LANE_AMBIGUOUS) PW_LANE_APPLY_HEAD(fetch);
-            if (fetch && A.j < L) r = a.rng[A.soff + A.j];   // (step A.j + 1 samples with double #(soff + A.j); unused if the walk ends)
+            if (fetch && A.j < L) next_draw(A.soff + A.j);   // (step A.j + 1 samples with double #(soff + A.j); unused if the walk ends)
             quad_issue(fetch, (const uint8_t *)a.lines, A.e);
             if (ballot(fetch)) {
                 quad_wait();
