@@ -487,6 +487,48 @@ int pw_edgelist_export(const pw_edgelist *e, uint32_t *indptr, uint32_t *indices
                        double *data64, uint64_t *id_offsets, char *id_chars);
 void pw_edgelist_destroy(pw_edgelist *e);
 
+/* ---- edge-list ingestion on the device (csrc/edgelist_dev.hip.h) ------------------------------------------------------------
+ * pw_edgelist_read's result -- the reference's CSR, vertices numbered by first appearance -- with the text of the file
+ * uploaded, tokenised and numbered in device memory and the CSR built there (pw_coo_to_csr_device's build; the float64 weights
+ * as parsed decide whether a repeated pair conflicts, the entries hold them rounded once to float32).  The reader accepts a
+ * SUBSET of what pw_edgelist_read accepts.  Return value:
+ *   PW_EDGELIST_OK                 *csr = the CSR (pw_csr_dev_shape / _export / _destroy, pw_csr_create_device), *ids = the names
+ *   PW_EDGELIST_NEEDS_HOST_READER  no error: the caller takes pw_edgelist_read's route.  Everything pw_edgelist_read declines
+ *                                  (see there), and: a weight literal outside  [+-]digits[.digits][e[+-]digits]  with at most 15
+ *                                  significand digits behind the leading zeros and a power of ten, fraction digits taken off,
+ *                                  within +-22 (the class one correctly rounded float64 operation evaluates); a delimiter of
+ *                                  more than 16 bytes; an empty file; a file of 4 GiB or more; 2^32 - 1 or more insertions;
+ *                                  scratch that does not fit in device (or host) memory
+ *   PW_EDGELIST_IO                 the file cannot be opened or read (the caller's own open then raises what Python raises)
+ *   < 0                            PW_ERR_*: no device, a HIP error
+ * Nothing stays allocated unless PW_EDGELIST_OK is returned.  stats (may be NULL; zeroed unless OK): wall clock of the stages,
+ * each ended by a wait for the device -- upload_ms (file -> pinned staging -> device text), scan_ms (byte classes, line
+ * starts, per-line records), ids_ms (id table, numbering, the names' spans), build_ms (the CSR build, allocations included;
+ * pw_csr_dev_shape has its kernels' time) -- and lines, n_nodes, file_bytes.
+ *   pw_edgelist_ids_shape   n_nodes, id_bytes (the names' characters in all)
+ *   pw_edgelist_ids_export  pw_edgelist_export's layout: id_offsets uint64[n_nodes + 1], id_chars char[id_bytes], vertex v's
+ *                           name = id_chars[id_offsets[v] : id_offsets[v + 1]], sliced from the bytes the call read */
+enum { PW_EDGELIST_OK = 0, PW_EDGELIST_NEEDS_HOST_READER = 1, PW_EDGELIST_IO = 2 };
+typedef struct pw_edgelist_dev_stats {
+    double upload_ms, scan_ms, ids_ms, build_ms;
+    uint64_t lines, n_nodes, file_bytes;
+} pw_edgelist_dev_stats;
+typedef struct pw_edgelist_ids pw_edgelist_ids;
+int pw_edgelist_read_device(const char *path, int weighted, int directed, const char *delimiter, int device, pw_csr_dev **csr,
+                            pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats);
+int pw_edgelist_ids_shape(const pw_edgelist_ids *ids, uint64_t *n_nodes, uint64_t *id_bytes);
+int pw_edgelist_ids_export(const pw_edgelist_ids *ids, uint64_t *id_offsets, char *id_chars);
+void pw_edgelist_ids_destroy(pw_edgelist_ids *ids);
+/* Host builds of the reader's text routines, no GPU needed.  Both return 1 (accepted), 0 (declined) or PW_ERR_INVALID.
+ *   pw_selftest_edgelist_weight  el_parse_weight on text[0, n): *value = the float64 (sign applied; the reader itself
+ *                                declines what is not > 0)
+ *   pw_selftest_edgelist_line    el_tokenize_line on the line text[lo, hi) (without its newline): *n_terms =
+ *                                len(line.strip().split(delimiter)); spans uint32[10] = (offset, length) of the first three
+ *                                terms, then of terms[0].strip() and terms[1].strip(); *weight (1.0 when unweighted) */
+int pw_selftest_edgelist_weight(const char *text, uint64_t n, double *value);
+int pw_selftest_edgelist_line(const char *text, uint64_t lo, uint64_t hi, const char *delimiter, int weighted, uint32_t *n_terms,
+                              uint32_t *spans, double *weight);
+
 /* ---- self test hooks (host only, no GPU needed -- except pw_selftest_lane with on_device) -- */
 /* Runs the binade-scan emulation of csrc/seqscan.h on a host array: returns through *index the
  * position np.searchsorted(np.cumsum(x), r) would return under sequential float32 semantics

@@ -89,6 +89,24 @@ class PwWalksWriteStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwEdgelistDevStats(C.Structure):
+    """``pw_edgelist_dev_stats`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("upload_ms", C.c_double),
+        ("scan_ms", C.c_double),
+        ("ids_ms", C.c_double),
+        ("build_ms", C.c_double),
+        ("lines", C.c_uint64),
+        ("n_nodes", C.c_uint64),
+        ("file_bytes", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+EDGELIST_OK, EDGELIST_NEEDS_HOST_READER, EDGELIST_IO = 0, 1, 2   # pw_edgelist_read_device's non-negative results
+
 MODE_IDS = {
     "SparseOTF": 0,
     "DenseOTF": 1,
@@ -171,6 +189,13 @@ SYMBOLS = {
     "pw_edgelist_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4),
     "pw_edgelist_export": (C.c_int, [C.c_void_p] * 7),
     "pw_edgelist_destroy": (None, [C.c_void_p]),
+    "pw_edgelist_read_device": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(PwEdgelistDevStats)]),
+    "pw_edgelist_ids_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pw_edgelist_ids_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pw_edgelist_ids_destroy": (None, [C.c_void_p]),
+    "pw_selftest_edgelist_weight": (C.c_int, [C.c_char_p, C.c_uint64, _f64p]),
+    "pw_selftest_edgelist_line": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int, _u32p, C.c_void_p, _f64p]),
     "pw_selftest_exact_decision": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_void_p]),
     "pw_selftest_lane": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_uint32,

@@ -6,6 +6,7 @@ Flag names, defaults, the mode sanity rules and the stage order follow the refer
 uses gensim when it is importable; without it walks and skip-gram both run on the GPU (``Base.embed_array``: the
 walk matrix stays in device memory).  ``--task walks`` writes the walks (one per line) to ``--output`` instead of training,
 the text made in device memory; ``PECANPY_AMD_DUMP_WALKS=1`` does the same through the ID lists of ``simulate_walks``.
+The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
 """
@@ -118,6 +119,12 @@ def read_graph(args):
     g = engine_cls(args.p, args.q, args.workers, args.verbose, args.extend, args.gamma, args.random_state)
     if args.input.endswith(".npz"):
         g.read_npz(args.input, args.weighted, implicit_ids=args.implicit_ids)
+    elif hasattr(g, "read_edg_device") and not os.environ.get("PECANPY_AMD_HOST_READER"):
+        # sparse modes: the edge list is parsed on the device (same arrays, warnings and exceptions: read_edg_device falls back
+        # to read_edg by itself); PECANPY_AMD_HOST_READER=1 keeps the host reader
+        g.read_edg_device(args.input, args.weighted, args.directed, args.delimiter)
+        if args.verbose:
+            print(f"edge list read by the {g.last_build_stats['reader']} reader")
     else:
         g.read_edg(args.input, args.weighted, args.directed, args.delimiter)
     check_mode(g, args)

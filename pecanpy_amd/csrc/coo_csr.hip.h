@@ -12,6 +12,8 @@
 //                            keys stay in insertion order, so the last of a run of equal keys is the last insertion
 //   5. coo_mark / scan / coo_compact   keep-last-of-run, output position, indices / data / row of every kept entry
 //   6. coo_indptr_kernel     indptr[r] = lower bound of r among the (ascending) rows
+// The edge-list reader (edgelist_dev.hip.h) takes the same path with float64 weights: coo_expand_lines_kernel, the sort carrying
+// the line index, coo_conflict_kernel (a pair inserted again with another float64 weight), coo_compact_lines_kernel.
 // Determinism: every output word is a function of the input alone.  Atomics are used for integer counts, a minimum and a
 // maximum only (order-independent results); the scatter ranks equal digits by lane order (ballots), never by arrival.
 //
@@ -125,6 +127,24 @@ coo_expand_kernel(const int64_t *__restrict__ src, const int64_t *__restrict__ d
     }
 }
 
+// The edge-list reader's form (edgelist_dev.hip.h): every edge kept, and what travels with insertion j is the index of its
+// LINE -- the float64 weights as parsed stay where they are, so that coo_conflict_kernel can compare them after the sort.
+__global__ void __launch_bounds__(256)
+coo_expand_lines_kernel(const int64_t *__restrict__ src, const int64_t *__restrict__ dst, uint64_t m, int directed, int bits, uint64_t n_ins,
+                        uint64_t *__restrict__ keys, uint32_t *__restrict__ line) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t s = (uint64_t)src[i], d = (uint64_t)dst[i];
+        const uint64_t j = directed ? i : 2 * i;
+        if (j + (directed ? 0 : 1) >= n_ins) continue;   // (cannot happen: n_ins = m or 2 m)
+        keys[j] = (s << bits) | d;
+        line[j] = (uint32_t)i;
+        if (!directed) {
+            keys[j + 1] = (d << bits) | s;
+            line[j + 1] = (uint32_t)i;
+        }
+    }
+}
+
 // ---- stable LSD radix pass ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 radix_hist_kernel(const uint64_t *__restrict__ keys, uint64_t n, int shift, uint32_t *__restrict__ hist, uint64_t n_waves) {
@@ -143,10 +163,11 @@ radix_hist_kernel(const uint64_t *__restrict__ keys, uint64_t n, int shift, uint
     for (int d = lane; d < RADIX_BINS; d += WAVE) hist[(uint64_t)d * n_waves + w] = cnt[wave][d];
 }
 
+// WEIGHTS: every key carries four bytes with it -- its float32 weight's bits, or (the edge-list reader) its line's index
 template <bool WEIGHTS>
 __global__ void __launch_bounds__(256)
-radix_scatter_kernel(const uint64_t *__restrict__ kin, const float *__restrict__ win, uint64_t *__restrict__ kout,
-                     float *__restrict__ wout, uint64_t n, int shift, const uint32_t *__restrict__ hist, uint64_t n_waves) {
+radix_scatter_kernel(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ win, uint64_t *__restrict__ kout,
+                     uint32_t *__restrict__ wout, uint64_t n, int shift, const uint32_t *__restrict__ hist, uint64_t n_waves) {
     __shared__ uint32_t base[4][RADIX_BINS];   // next output position of every digit of this wavefront's elements
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const uint64_t w = (uint64_t)blockIdx.x * 4 + wave;
@@ -201,6 +222,34 @@ coo_compact_kernel(const uint64_t *__restrict__ keys, const float *__restrict__ 
     indices[p] = (uint32_t)(key & ((1ull << bits) - 1));
     rows[p] = (uint32_t)(key >> bits);
     if (data) data[p] = w[j];
+}
+
+// ... the edge-list reader's forms.  An ordered pair inserted again with another float64 weight makes the reference warn: all
+// weights of a run of equal keys are equal exactly when every two neighbours in it are (the weights are > 0: no NaN).
+__global__ void __launch_bounds__(256)
+coo_conflict_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ line, const double *__restrict__ w64, uint64_t n, uint64_t m,
+                    uint32_t *__restrict__ conflict) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j + 1 >= n || keys[j] != keys[j + 1]) return;
+    const uint32_t a = line[j], b = line[j + 1];
+    if (a >= m || b >= m) return;   // (cannot happen: the payloads are line indices)
+    if (w64[a] != w64[b]) atomicOr(conflict, 1u);
+}
+
+__global__ void __launch_bounds__(256)
+coo_compact_lines_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ line, const double *__restrict__ w64, uint64_t n,
+                         uint64_t m, const uint32_t *__restrict__ pos, int bits, uint64_t nnz, uint32_t *__restrict__ indices,
+                         float *__restrict__ data, uint32_t *__restrict__ rows) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t key = keys[j];
+    if (j + 1 != n && key == keys[j + 1]) return;
+    const uint64_t p = pos[j];
+    if (p >= nnz) return;   // (cannot happen: nnz is the scan's total)
+    indices[p] = (uint32_t)(key & ((1ull << bits) - 1));
+    rows[p] = (uint32_t)(key >> bits);
+    const uint32_t l = line[j];
+    data[p] = l < m ? (float)w64[l] : 0.0f;   // the winner's weight as parsed, rounded once to float32 (to_csr)
 }
 
 __global__ void __launch_bounds__(256)

@@ -39,6 +39,7 @@
 #include "walk_lanes.hip.h"
 #include "sgns.hip.h"
 #include "coo_csr.hip.h"
+#include "edgelist_dev.hip.h"
 #include "dense_build.hip.h"
 #include "emb_text.hip.h"
 #include "walk_text.hip.h"
@@ -979,9 +980,14 @@ void device_exclusive_scan(uint32_t *d_x, uint64_t n, uint32_t *d_tmp) {
 
 }  // namespace
 
-PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64_t *d_dst, const float *d_weight, uint64_t m,
-                                   uint64_t n_nodes, int directed, pw_csr_dev **out) {
+// The build behind pw_coo_to_csr_device and pw_edgelist_read_device.  d_w64 (the edge-list reader; d_weight is NULL then):
+// the float64 weight of every edge as parsed, all > 0.  The sort then carries the edge's index instead of a weight; a pair
+// inserted again with another float64 weight sets *conflict and ends the call without a result (PW_OK, *out NULL: the
+// reference warns there), and the entries get the winner's weight rounded to float32.
+static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_dst, const float *d_weight, const double *d_w64, uint64_t m,
+                            uint64_t n_nodes, int directed, pw_csr_dev **out, int *conflict) {
     if (!out || (m && (!d_src || !d_dst))) return fail(PW_ERR_INVALID, "null pointer");
+    const bool payload = d_weight || d_w64;   // four bytes travel with every key
     const int n_dev = pw_device_count();
     if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
     if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
@@ -1050,17 +1056,19 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     const uint64_t hist_elems = (uint64_t)pw::RADIX_BINS * n_waves;
     const uint64_t scan_max = std::max(std::max(hist_elems, n_ins + 1), d_weight ? m + 1 : 0);
     DevBuf<uint64_t> keys_buf[2];
-    DevBuf<float> w_buf[2];
-    DevBuf<uint32_t> hist_buf, tmp_buf;
+    DevBuf<uint32_t> w_buf[2];   // the keys' payload: float32 bits, or edge indices (d_w64)
+    DevBuf<uint32_t> hist_buf, tmp_buf, conflict_buf;
     rc = alloc(keys_buf[0], n_ins + 1, "sort keys");
     if (!rc) rc = alloc(keys_buf[1], n_ins + 1, "sort keys (second buffer)");
-    if (!rc && d_weight) rc = alloc(w_buf[0], n_ins, "sort weights");
-    if (!rc && d_weight) rc = alloc(w_buf[1], n_ins, "sort weights (second buffer)");
+    if (!rc && payload) rc = alloc(w_buf[0], n_ins, "sort weights");
+    if (!rc && payload) rc = alloc(w_buf[1], n_ins, "sort weights (second buffer)");
+    if (!rc && d_w64) rc = alloc(conflict_buf, 1, "conflict flag");
     if (!rc) rc = alloc(hist_buf, hist_elems, "radix histograms");
     if (!rc) rc = alloc(tmp_buf, scan_tmp_elems(scan_max), "scan tile sums");
     if (rc) return rc;
     uint64_t *d_keys[2] = {keys_buf[0].p, keys_buf[1].p};   // (the sort swaps the two views; the owners stay put)
-    float *d_w[2] = {w_buf[0].p, w_buf[1].p};
+    uint32_t *d_w[2] = {w_buf[0].p, w_buf[1].p};
+    if (d_w64) HIP_TRY(hipMemset(conflict_buf.p, 0, sizeof(uint32_t)));
     uint32_t *const d_hist = hist_buf.p, *const d_tmp = tmp_buf.p;
     HIP_TRY(hipEventRecord(mem.ev[2], nullptr));
     if (d_weight && dropped) {
@@ -1068,19 +1076,23 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
         device_exclusive_scan(d_keep, m + 1, d_tmp);
     }
     if (n_ins) {
-        hipLaunchKernelGGL(pw::coo_expand_kernel, dim3(stride_grid), dim3(256), 0, nullptr, d_src, d_dst, d_weight, m,
-                           (const uint32_t *)(d_weight && dropped ? d_keep : nullptr), directed ? 1 : 0, bits, n_ins, d_keys[0], d_w[0]);
+        if (d_w64)
+            hipLaunchKernelGGL(pw::coo_expand_lines_kernel, dim3(stride_grid), dim3(256), 0, nullptr, d_src, d_dst, m, directed ? 1 : 0, bits, n_ins,
+                               d_keys[0], d_w[0]);
+        else
+            hipLaunchKernelGGL(pw::coo_expand_kernel, dim3(stride_grid), dim3(256), 0, nullptr, d_src, d_dst, d_weight, m,
+                               (const uint32_t *)(d_weight && dropped ? d_keep : nullptr), directed ? 1 : 0, bits, n_ins, d_keys[0], (float *)d_w[0]);
         // 4. stable LSD radix sort over the 2 * bits significant key bits
         const unsigned wave_grid = (unsigned)((n_waves + 3) / 4);
         for (int shift = 0; shift < 2 * bits; shift += pw::RADIX_BITS) {
             hipLaunchKernelGGL(pw::radix_hist_kernel, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], n_ins, shift, d_hist, n_waves);
             device_exclusive_scan(d_hist, hist_elems, d_tmp);
-            if (d_weight)
-                hipLaunchKernelGGL(pw::radix_scatter_kernel<true>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)d_w[0],
+            if (payload)
+                hipLaunchKernelGGL(pw::radix_scatter_kernel<true>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const uint32_t *)d_w[0],
                                    d_keys[1], d_w[1], n_ins, shift, (const uint32_t *)d_hist, n_waves);
             else
-                hipLaunchKernelGGL(pw::radix_scatter_kernel<false>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)nullptr,
-                                   d_keys[1], (float *)nullptr, n_ins, shift, (const uint32_t *)d_hist, n_waves);
+                hipLaunchKernelGGL(pw::radix_scatter_kernel<false>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const uint32_t *)nullptr,
+                                   d_keys[1], (uint32_t *)nullptr, n_ins, shift, (const uint32_t *)d_hist, n_waves);
             std::swap(d_keys[0], d_keys[1]);
             std::swap(d_w[0], d_w[1]);
         }
@@ -1092,11 +1104,23 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     if (n_ins) {
         hipLaunchKernelGGL(pw::coo_mark_kernel, dim3((unsigned)((n_ins + 256) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], n_ins, d_pos);
         device_exclusive_scan(d_pos, n_ins + 1, d_tmp);
+        if (d_w64)
+            hipLaunchKernelGGL(pw::coo_conflict_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0],
+                               (const uint32_t *)d_w[0], d_w64, n_ins, m, conflict_buf.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(mem.ev[3], nullptr));
     if (n_ins) {
         HIP_TRY(hipMemcpy(&nnz32, d_pos + n_ins, sizeof(nnz32), hipMemcpyDeviceToHost));
+    }
+    if (d_w64) {
+        uint32_t h_conflict = 0;
+        HIP_TRY(hipMemcpy(&h_conflict, conflict_buf.p, sizeof(h_conflict), hipMemcpyDeviceToHost));
+        if (h_conflict) {
+            if (conflict) *conflict = 1;
+            *out = nullptr;
+            return PW_OK;
+        }
     }
     const uint64_t nnz = nnz32;
     if (nnz > n_ins) return fail(PW_ERR_HIP, "pw_coo_to_csr_device: entry count beyond the insertions (internal error)");
@@ -1113,10 +1137,13 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     };
     rc = alloc_out(c->d_indptr, n + 1, "indptr");
     if (!rc) rc = alloc_out(c->d_indices, nnz, "indices");
-    if (!rc && d_weight) rc = alloc_out(c->d_data, nnz, "data");
+    if (!rc && payload) rc = alloc_out(c->d_data, nnz, "data");
     if (rc) return rc;
     HIP_TRY(hipEventRecord(mem.ev[4], nullptr));
-    if (n_ins)
+    if (n_ins && d_w64)
+        hipLaunchKernelGGL(pw::coo_compact_lines_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0],
+                           (const uint32_t *)d_w[0], d_w64, n_ins, m, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p, d_rows);
+    else if (n_ins)
         hipLaunchKernelGGL(pw::coo_compact_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)d_w[0],
                            n_ins, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p, d_rows);
     // 6. row offsets
@@ -1132,6 +1159,11 @@ PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64
     mem.res = nullptr;
     *out = c;
     return PW_OK;
+}
+
+PW_EXPORT int pw_coo_to_csr_device(int device, const int64_t *d_src, const int64_t *d_dst, const float *d_weight, uint64_t m,
+                                   uint64_t n_nodes, int directed, pw_csr_dev **out) {
+    return coo_to_csr_build(device, d_src, d_dst, d_weight, nullptr, m, n_nodes, directed, out, nullptr);
 }
 
 PW_EXPORT int pw_csr_dev_shape(const pw_csr_dev *c, uint64_t *n_nodes, uint64_t *nnz, uint64_t *insertions, uint64_t *dropped, double *build_ms) {
@@ -1173,6 +1205,245 @@ PW_EXPORT int pw_csr_create_device(const pw_csr_dev *c, const uint32_t *h_indptr
     int rc = pw_csr_dev_export(c, indptr.get(), indices.get(), data.get());
     if (rc) return rc;
     return csr_create_impl(indptr.get(), indices.get(), data.get(), (uint32_t)c->n_nodes, (uint32_t)c->nnz, c->device, out, d_csr);
+}
+
+
+// ---- an edge-list file parsed in device memory (csrc/edgelist_dev.hip.h) ---------------------------------------------------------
+struct pw_edgelist_ids {
+    std::unique_ptr<char[]> text;          // the bytes of the file as read
+    std::vector<uint32_t> off, len;        // vertex v's name = text[off[v], off[v] + len[v])
+    uint64_t id_bytes = 0;
+};
+
+PW_EXPORT void pw_edgelist_ids_destroy(pw_edgelist_ids *ids) { delete ids; }
+
+PW_EXPORT int pw_edgelist_ids_shape(const pw_edgelist_ids *ids, uint64_t *n_nodes, uint64_t *id_bytes) {
+    if (!ids) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_nodes) *n_nodes = ids->off.size();
+    if (id_bytes) *id_bytes = ids->id_bytes;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_edgelist_ids_export(const pw_edgelist_ids *ids, uint64_t *id_offsets, char *id_chars) {
+    if (!ids || !id_offsets || (ids->id_bytes && !id_chars)) return fail(PW_ERR_INVALID, "null pointer");
+    uint64_t at = 0;
+    for (size_t v = 0; v < ids->off.size(); v++) {
+        id_offsets[v] = at;
+        memcpy(id_chars + at, ids->text.get() + ids->off[v], ids->len[v]);
+        at += ids->len[v];
+    }
+    id_offsets[ids->off.size()] = at;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int directed, const char *delimiter, int device, pw_csr_dev **csr,
+                                      pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    if (!path || !csr || !ids) return fail(PW_ERR_INVALID, "null pointer");
+    *csr = nullptr;
+    *ids = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const size_t dl = delimiter ? strlen(delimiter) : 0;
+    if (dl == 0 || dl > pw::EL_MAX_DELIM) return PW_EDGELIST_NEEDS_HOST_READER;   // (str.split("") raises in Python)
+    for (size_t i = 0; i < dl; i++)
+        if ((unsigned char)delimiter[i] >= 0x80 || delimiter[i] == '\n' || delimiter[i] == '\r') return PW_EDGELIST_NEEDS_HOST_READER;
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+
+    // every buffer of the call, in front of `mem`: they go after its destructor has waited for the stream
+    DevBuf<char> d_text, d_delim;
+    PinnedBuf<char> pinned[2];
+    DevBuf<uint32_t> d_flags, d_segcnt, d_tmp, d_starts, d_table, d_slot, d_first, d_idoff, d_idlen;
+    DevBuf<pw::ElToken> d_tok;
+    DevBuf<double> d_w64;
+    DevBuf<int64_t> d_src, d_dst;
+    // ... and beside them: the file, the two copy events, the id handle until it is handed out
+    struct Mem {
+        FILE *file = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        pw_edgelist_ids *res = nullptr;
+        bool queued = false;
+        ~Mem() {
+            if (queued) (void)hipStreamSynchronize(nullptr);
+            if (file) (void)fclose(file);
+            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+            delete res;
+        }
+    } mem;
+    // scratch that does not fit is no error: the host reader still works
+    bool no_room = false;
+    auto alloc = [&](auto &buf, uint64_t n) { if (!no_room && buf.alloc(n) != hipSuccess) no_room = true; };
+
+    // ---- upload: the file in chunks through two pinned buffers into one device buffer; the host keeps the bytes for the names
+    auto t0 = clk::now();
+    mem.file = fopen(path, "rb");
+    if (!mem.file) return PW_EDGELIST_IO;
+    uint64_t n = 0;
+    if (fseek(mem.file, 0, SEEK_END) != 0) return PW_EDGELIST_IO;
+    {
+        const long sz = ftell(mem.file);
+        if (sz < 0) return PW_EDGELIST_IO;
+        n = (uint64_t)sz;
+        rewind(mem.file);
+    }
+    if (n == 0 || n >= (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;   // (an empty file has no graph to put on the device)
+    HIP_TRY(hipSetDevice(device));
+    mem.res = new (std::nothrow) pw_edgelist_ids();
+    if (mem.res) mem.res->text.reset(new (std::nothrow) char[n]);
+    if (!mem.res || !mem.res->text) return PW_EDGELIST_NEEDS_HOST_READER;
+    char *const h_text = mem.res->text.get();
+    constexpr uint64_t CHUNK = 16ull << 20;
+    alloc(d_text, n + 1);
+    for (auto &pb : pinned) if (!no_room && pb.alloc(std::min(CHUNK, n)) != hipSuccess) no_room = true;
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
+    mem.queued = true;
+    {
+        uint64_t at = 0;
+        for (int s = 0; at < n; s ^= 1) {
+            const uint64_t want = std::min(CHUNK, n - at);
+            if (at >= 2 * CHUNK) HIP_TRY(hipEventSynchronize(mem.ev[s]));   // this buffer's last copy has left it
+            if (fread(pinned[s].p, 1, want, mem.file) != want) return PW_EDGELIST_IO;   // (short: an error, or the file changed)
+            HIP_TRY(hipMemcpyAsync(d_text.p + at, pinned[s].p, want, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipEventRecord(mem.ev[s], nullptr));
+            memcpy(h_text + at, pinned[s].p, want);
+            at += want;
+        }
+        (void)fclose(mem.file);
+        mem.file = nullptr;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    const double upload_ms = ms_since(t0);
+
+    // ---- 1. byte classes and line starts
+    t0 = clk::now();
+    const uint64_t n_seg = (n + pw::EL_SEG - 1) / pw::EL_SEG;
+    const unsigned seg_grid = (unsigned)((n_seg + 3) / 4);
+    alloc(d_flags, 1);
+    alloc(d_segcnt, n_seg + 1);
+    alloc(d_tmp, scan_tmp_elems(n_seg + 1));
+    alloc(d_delim, pw::EL_MAX_DELIM);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), nullptr));
+    HIP_TRY(hipMemsetAsync(d_segcnt.p + n_seg, 0, sizeof(uint32_t), nullptr));   // (the scan's last input: its output is the total)
+    HIP_TRY(hipMemcpyAsync(d_delim.p, delimiter, dl, hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(pw::el_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, d_segcnt.p, d_flags.p);
+    device_exclusive_scan(d_segcnt.p, n_seg + 1, d_tmp.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t h_flags = 0, n_newlines = 0;
+    HIP_TRY(hipMemcpy(&n_newlines, d_segcnt.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_flags) return PW_EDGELIST_NEEDS_HOST_READER;
+    const uint64_t n_starts = (uint64_t)n_newlines + 1;
+    const uint64_t n_lines = (uint64_t)n_newlines + (h_text[n - 1] != '\n' ? 1 : 0);   // a last line without a newline counts
+    const uint64_t n_tok = 2 * n_lines;
+    if (n_tok >= 0xffffffffull || n_lines * (directed ? 1u : 2u) >= 0xffffffffull) return PW_EDGELIST_NEEDS_HOST_READER;
+    alloc(d_starts, n_starts);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    HIP_TRY(hipMemsetAsync(d_starts.p, 0, sizeof(uint32_t), nullptr));
+    hipLaunchKernelGGL(pw::el_starts_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, (const uint32_t *)d_segcnt.p,
+                       n_starts, d_starts.p);
+
+    // ---- 2. per-line records
+    alloc(d_tok, n_tok);
+    if (weighted) alloc(d_w64, n_lines);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    const unsigned line_grid = (unsigned)((n_lines + 255) / 256), tok_grid = (unsigned)((n_tok + 256) / 256);
+    hipLaunchKernelGGL(pw::el_lines_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, (const uint32_t *)d_starts.p, n_starts,
+                       n_lines, (const char *)d_delim.p, (uint32_t)dl, weighted ? 1 : 0, d_tok.p, d_w64.p, d_flags.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_flags) return PW_EDGELIST_NEEDS_HOST_READER;
+    d_starts.release();
+    d_segcnt.release();
+    const double scan_ms = ms_since(t0);
+
+    // ---- 3. first-appearance numbering
+    t0 = clk::now();
+    uint64_t table_size = 1024;
+    while (table_size < 2 * n_tok) table_size <<= 1;   // (n_tok < 2^32 - 1: at most 2^33 slots of which half stay free)
+    if (table_size > (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;
+    alloc(d_table, table_size);
+    alloc(d_slot, n_tok);
+    alloc(d_first, n_tok + 1);
+    alloc(d_tmp, scan_tmp_elems(n_tok + 1));
+    alloc(d_src, n_lines);
+    alloc(d_dst, n_lines);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(uint32_t) * table_size, nullptr));
+    hipLaunchKernelGGL(pw::el_insert_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, (const pw::ElToken *)d_tok.p, n_tok, d_table.p,
+                       (uint32_t)(table_size - 1), d_slot.p);
+    hipLaunchKernelGGL(pw::el_first_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const uint32_t *)d_table.p, (const uint32_t *)d_slot.p, n_tok, d_first.p);
+    device_exclusive_scan(d_first.p, n_tok + 1, d_tmp.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t n_nodes = 0;
+    HIP_TRY(hipMemcpy(&n_nodes, d_first.p + n_tok, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_nodes == 0 || n_nodes > n_tok) return fail(PW_ERR_HIP, "pw_edgelist_read_device: vertex count out of range (internal error)");
+    alloc(d_idoff, n_nodes);
+    alloc(d_idlen, n_nodes);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    hipLaunchKernelGGL(pw::el_number_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const pw::ElToken *)d_tok.p, (const uint32_t *)d_table.p,
+                       (const uint32_t *)d_slot.p, (const uint32_t *)d_first.p, n_tok, (uint64_t)n_nodes, d_src.p, d_dst.p, d_idoff.p, d_idlen.p, d_flags.p);
+    HIP_TRY(hipGetLastError());
+    try {
+        mem.res->off.resize(n_nodes);
+        mem.res->len.resize(n_nodes);
+    } catch (const std::bad_alloc &) {
+        return PW_EDGELIST_NEEDS_HOST_READER;
+    }
+    HIP_TRY(hipMemcpy(mem.res->off.data(), d_idoff.p, sizeof(uint32_t) * n_nodes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mem.res->len.data(), d_idlen.p, sizeof(uint32_t) * n_nodes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_flags) return fail(PW_ERR_HIP, "pw_edgelist_read_device: the id table is inconsistent (internal error)");
+    for (uint32_t v = 0; v < n_nodes; v++) {
+        if ((uint64_t)mem.res->off[v] + mem.res->len[v] > n) return fail(PW_ERR_HIP, "pw_edgelist_read_device: a name outside the text (internal error)");
+        mem.res->id_bytes += mem.res->len[v];
+    }
+    for (DevBuf<uint32_t> *b : {&d_table, &d_slot, &d_first, &d_idoff, &d_idlen, &d_tmp}) b->release();
+    d_tok.release();
+    d_text.release();
+    const double ids_ms = ms_since(t0);
+
+    // ---- 4. the CSR (coo_csr.hip.h), the sort carrying the line index so that the float64 weights can be compared
+    t0 = clk::now();
+    pw_csr_dev *c = nullptr;
+    int conflict = 0;
+    const int rc = coo_to_csr_build(device, d_src.p, d_dst.p, nullptr, weighted ? d_w64.p : nullptr, n_lines, n_nodes, directed, &c, &conflict);
+    if (rc == PW_ERR_NOMEM) return PW_EDGELIST_NEEDS_HOST_READER;
+    if (rc) return rc;
+    if (conflict || !c) return PW_EDGELIST_NEEDS_HOST_READER;   // the reference warns about the overwritten weight
+    if (stats) {
+        stats->upload_ms = upload_ms; stats->scan_ms = scan_ms; stats->ids_ms = ids_ms; stats->build_ms = ms_since(t0);
+        stats->lines = n_lines; stats->n_nodes = n_nodes; stats->file_bytes = n;
+    }
+    *csr = c;
+    *ids = mem.res;
+    mem.res = nullptr;
+    return PW_EDGELIST_OK;
+}
+
+// Host builds of the reader's two text routines (csrc/edgelist_dev.hip.h), for tests without a GPU.
+PW_EXPORT int pw_selftest_edgelist_weight(const char *text, uint64_t n, double *value) {
+    if ((n && !text) || !value || n > 0xffffffffull) return fail(PW_ERR_INVALID, "bad argument");
+    *value = 0.0;
+    return pw::el_parse_weight(text, (uint32_t)n, value) ? 1 : 0;
+}
+
+PW_EXPORT int pw_selftest_edgelist_line(const char *text, uint64_t lo, uint64_t hi, const char *delimiter, int weighted, uint32_t *n_terms,
+                                        uint32_t *spans, double *weight) {
+    if (!text || !delimiter || !n_terms || !spans || !weight || lo > hi || hi > 0xffffffffull) return fail(PW_ERR_INVALID, "bad argument");
+    const size_t dl = strlen(delimiter);
+    if (dl == 0) return fail(PW_ERR_INVALID, "empty delimiter");
+    pw::ElLine ln;
+    memset(&ln, 0, sizeof(ln));
+    const bool ok = pw::el_tokenize_line(text, lo, hi, delimiter, (uint32_t)dl, weighted != 0, &ln);
+    *n_terms = ln.n_terms;
+    for (int k = 0; k < 3; k++) { spans[2 * k] = ln.off[k]; spans[2 * k + 1] = ln.len[k]; }
+    for (int k = 0; k < 2; k++) { spans[6 + 2 * k] = ln.id_off[k]; spans[7 + 2 * k] = ln.id_len[k]; }
+    *weight = ln.weight;
+    return ok ? 1 : 0;
 }
 
 PW_EXPORT int pw_graph_index_info(const pw_graph *g, double *build_ms, uint64_t *index_bytes, uint64_t *lane_list_entries) {

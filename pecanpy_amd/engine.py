@@ -262,6 +262,73 @@ class WalkEngine:
         return eng
 
     @classmethod
+    def from_edgelist_file(cls, path, weighted, directed, delimiter="\t", device=None):
+        """CSR handle from an edge-list FILE, parsed and built on the device (``pw_edgelist_read_device`` +
+        ``pw_csr_create_device``): the text is uploaded, tokenised and numbered by first appearance in device memory and
+        handed to the build of ``from_edge_index``.  The result is what ``SparseGraph.read_edg`` gives, array for array.
+
+        Returns the engine, or ``None`` when the file needs the host reader (everything on which the reference warns or
+        raises, weight literals outside the class the device parses exactly, a file that cannot be opened, ...: see
+        include/pecanpy_amd.h) -- no error; the caller takes ``read_edg``.  The engine carries ``eng.csr = (indptr,
+        indices, data)`` (``data`` all ones when unweighted), ``eng.ids`` (the vertex names, first-appearance order) and
+        ``eng.build_stats``: the library's ``upload_ms``, ``scan_ms``, ``ids_ms``, ``build_ms`` (wall clock of the
+        stages), ``lines``, ``n_nodes``, ``file_bytes``, and ``nnz``, ``insertions``, ``csr_kernels_ms`` (device time of
+        the CSR build's kernels), ``read_call_ms``, ``export_ms``, ``handle_ms``."""
+        import os
+        import time
+
+        lib = _lib.load()
+        if int(lib.pw_device_count()) <= 0:
+            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+        try:
+            raw_delim = delimiter.encode("utf-8", "surrogateescape")
+        except (AttributeError, UnicodeError):
+            return None
+        if b"\0" in raw_delim:
+            return None
+        t0 = time.perf_counter()
+        c, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwEdgelistDevStats()
+        rc = lib.pw_edgelist_read_device(os.fsencode(path), int(bool(weighted)), int(bool(directed)), raw_delim, int(device or 0),
+                                         C.byref(c), C.byref(ids), C.byref(st))
+        if rc in (_lib.EDGELIST_NEEDS_HOST_READER, _lib.EDGELIST_IO):
+            return None
+        _lib.check(rc)
+        try:
+            t1 = time.perf_counter()
+            shape = [C.c_uint64(0) for _ in range(4)]
+            ms = C.c_double(0)
+            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
+            n, nnz, insertions, _ = (int(s.value) for s in shape)
+            indptr = np.empty(n + 1, dtype=np.uint32)
+            indices = np.empty(nnz, dtype=np.uint32)
+            data = np.empty(nnz, dtype=np.float32)
+            _lib.check(lib.pw_csr_dev_export(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data)))
+            dims = [C.c_uint64(0), C.c_uint64(0)]
+            _lib.check(lib.pw_edgelist_ids_shape(ids, C.byref(dims[0]), C.byref(dims[1])))
+            id_bytes = int(dims[1].value)
+            offs = np.empty(n + 1, dtype=np.uint64)
+            chars = np.empty(max(id_bytes, 1), dtype=np.uint8)
+            _lib.check(lib.pw_edgelist_ids_export(ids, _np_ptr(offs), _np_ptr(chars)))
+            blob = chars[:id_bytes].tobytes().decode("ascii")
+            cuts = offs.tolist()
+            names = [blob[a:b] for a, b in zip(cuts, cuts[1:])]
+            t2 = time.perf_counter()
+            h = C.c_void_p()
+            _lib.check(lib.pw_csr_create_device(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), C.byref(h)))   # (no second download)
+            t3 = time.perf_counter()
+        finally:
+            lib.pw_csr_dev_destroy(c)
+            lib.pw_edgelist_ids_destroy(ids)
+        eng = cls(h, lib, "csr", n, int(device or 0))
+        eng._max_degree = int(np.diff(indptr.astype(np.int64)).max()) if n else 0
+        eng._nnz = nnz
+        eng.csr = (indptr, indices, data)
+        eng.ids = names
+        eng.build_stats = {**st.as_dict(), "nnz": nnz, "insertions": insertions, "csr_kernels_ms": float(ms.value),
+                           "read_call_ms": (t1 - t0) * 1e3, "export_ms": (t2 - t1) * 1e3, "handle_ms": (t3 - t2) * 1e3}
+        return eng
+
+    @classmethod
     def from_dense_tensor(cls, mat, device=None):
         """Dense handle from a matrix, built on the device (``pw_dense_create_device``): the same handle as ``from_dense`` on
         the same values, without the host pass over the ``n * n`` entries.

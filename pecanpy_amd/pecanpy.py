@@ -544,6 +544,44 @@ class _SparseBase(Base, SparseGraph):
             warnings.warn(f"{eng.build_stats['dropped']} non-positive edge(s) ignored", RuntimeWarning, stacklevel=2)
         return g
 
+    def read_edg_device(self, path, weighted, directed, delimiter="\t"):
+        """``read_edg`` with the file parsed ON THE DEVICE (``WalkEngine.from_edgelist_file``): the text is uploaded,
+        tokenised, numbered by first appearance and turned into the CSR in device memory.  ``nodes``, ``indptr``,
+        ``indices`` and ``data`` (all ones when unweighted) come out as ``read_edg`` fills them, bit for bit, and the walk
+        handle created from the device CSR is installed as the object's engine: the first ``simulate_walks`` /
+        ``embed_array`` uploads nothing.
+
+        The device reader takes a subset of the files the native host reader takes; for everything else -- whatever makes
+        the reference warn or raise, weight literals it does not parse exactly, a file that cannot be opened, no GPU or no
+        library -- this method calls ``read_edg``, so warnings and exceptions are the reference's in every case.
+        ``last_build_stats["reader"]`` says which ran: ``"device"`` (with the stage times and sizes of
+        ``from_edgelist_file``) or ``"host"``."""
+        from . import _lib
+
+        try:   # without the library or a GPU there is nothing to read on: the host reader needs neither (the walks will say so)
+            have_device = int(_lib.load().pw_device_count()) > 0
+        except (_lib.PwError, OSError, AttributeError):
+            have_device = False
+        eng = None
+        if have_device:   # (a device error in the reader itself is raised, not papered over)
+            eng = WalkEngine.from_edgelist_file(path, weighted, directed, delimiter, device=self._device_index())
+        if eng is None:
+            self.read_edg(path, weighted, directed, delimiter)
+            self.last_build_stats = {"reader": "host"}
+            return
+        if self._multi is not None:
+            for rep in self._multi.engines[1:]:
+                rep.close()
+            self._multi = None
+        if self._engine is not None:
+            self._engine.close()
+        self.set_node_ids(eng.ids)
+        self.indptr, self.indices, self.data = eng.csr
+        self._engine = eng
+        self._engine_key = (self._graph_key(), self._device_index())
+        self._thr_key = None
+        self.last_build_stats = {"reader": "device", **eng.build_stats}
+
     def get_has_nbrs(self):
         """``has_nbrs(idx)`` callback (sparse_rw.py:12-20); host-side helper, not used by the GPU path."""
         indptr = self.indptr
