@@ -401,6 +401,10 @@ int pw_vectors_write_text(int device, const float *vectors, uint64_t n_rows, uin
  * (0xffffffff if the writer's count pass would disagree with its fill pass).  on_device = 0: the host build of the routine
  * (csrc/emb_text.hip.h: format_f6), usable without a GPU; on_device != 0: one thread per value of a kernel on `device`. */
 int pw_selftest_format_f6(int on_device, int device, const float *x, uint64_t n, char *chars, uint32_t *lens);
+/* Test hook: the device's exclusive prefix sum (csrc/scan.hip.h), the one behind every offset table of the library.  x = n
+ * values of uint32 (width 32) or uint64 (width 64) in host memory, replaced by x'[i] = x[0] + ... + x[i - 1] in that width;
+ * *total = their sum.  n == 0 launches nothing and gives 0. */
+int pw_selftest_exclusive_scan(int device, int width, void *x, uint64_t n, uint64_t *total);
 
 /* ---- the walk corpus file written from device memory (csrc/walk_text.hip.h) ------------------------------------------------
  * One walk per line, the names of its nodes separated by single spaces: what gensim's LineSentence / Word2Vec(corpus_file=),

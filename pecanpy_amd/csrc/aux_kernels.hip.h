@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan.hip.h"
 #include "walk_sparse.hip.h"
 
 namespace pw {
@@ -257,19 +258,19 @@ __global__ void csr_edge_rows_kernel(const uint32_t *__restrict__ indptr, uint32
 // Stream offsets.  draws[i] = number of doubles job i consumes.  First pass assumes every walk
 // from a start with neighbours runs its full length (always true on undirected graphs); repair
 // passes use the lengths the walk kernel actually produced (out[i][L+1] - 1).
-// Three small kernels = exclusive prefix sum over n_jobs 64-bit counts.
+// The exclusive prefix sum over n_jobs 64-bit counts is scan.hip.h's: its tile sums with JobDraws,
+// its scan of the tile sums, and draws_offsets_kernel in the place of its offsets kernel.
 // ---------------------------------------------------------------------------------------------
-constexpr int SCAN_BLOCK = 256;
-constexpr int SCAN_ITEMS = 16;
-constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;
-
-// (indptr: the has-neighbours BITMAP of the graph, has_nbr_bits_kernel below)
-__device__ __forceinline__ uint64_t job_draws(const uint32_t *indptr, const uint32_t *starts,
-                                              const uint32_t *walks, uint32_t L, uint64_t i) {
-    if (walks) return (uint64_t)walks[i * ((uint64_t)L + 2) + L + 1] - 1;
-    uint32_t v = starts[i];
-    return (indptr[v >> 5] >> (v & 31u)) & 1u ? (uint64_t)L : 0ull;
-}
+struct JobDraws {
+    const uint32_t *has;   // the has-neighbours BITMAP of the graph, has_nbr_bits_kernel below
+    const uint32_t *starts, *walks;
+    uint32_t L;
+    __device__ uint64_t operator()(uint64_t i) const {
+        if (walks) return (uint64_t)walks[i * ((uint64_t)L + 2) + L + 1] - 1;
+        const uint32_t v = starts[i];
+        return (has[v >> 5] >> (v & 31u)) & 1u ? (uint64_t)L : 0ull;
+    }
+};
 
 // bit v of has[] = vertex v has neighbours (512 KB at RMAT-22: cache resident, where the two scattered indptr reads per job of
 // rounds 1-4 were not -- the offsets scan of a 41.9 M-job array 1.9 -> 0.5 ms)
@@ -285,87 +286,20 @@ has_nbr_bits_kernel(const uint32_t *__restrict__ indptr, uint32_t n_nodes, uint3
     has[w] = bits;
 }
 
-__device__ __forceinline__ uint64_t block_reduce_u64(uint64_t v, uint64_t *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = SCAN_BLOCK / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] += sh[t + s];
-        __syncthreads();
-    }
-    uint64_t r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK)
-draws_tile_sums_kernel(const uint32_t *indptr, const uint32_t *starts, const uint32_t *walks,
-                       uint32_t L, uint64_t n_jobs, uint64_t *tile_sums) {
-    __shared__ uint64_t sh[SCAN_BLOCK];
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t s = 0;
-    for (int k = 0; k < SCAN_ITEMS; k++)
-        if (base + k < n_jobs) s += job_draws(indptr, starts, walks, L, base + k);
-    s = block_reduce_u64(s, sh);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = s;
-}
-
-// single block: exclusive scan of tile sums in place; total goes to tile_sums[n_tiles]
-__global__ void __launch_bounds__(SCAN_BLOCK)
-scan_tile_sums_kernel(uint64_t *tile_sums, uint64_t n_tiles) {
-    __shared__ uint64_t sh[SCAN_BLOCK];
-    __shared__ uint64_t carry;
-    const int t = threadIdx.x;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (uint64_t base = 0; base < n_tiles; base += SCAN_BLOCK) {
-        uint64_t v = base + t < n_tiles ? tile_sums[base + t] : 0;
-        sh[t] = v;
-        __syncthreads();
-        for (int off = 1; off < SCAN_BLOCK; off <<= 1) {
-            uint64_t add = t >= off ? sh[t - off] : 0;
-            __syncthreads();
-            sh[t] += add;
-            __syncthreads();
-        }
-        uint64_t incl = sh[t];
-        uint64_t c = carry;
-        if (base + t < n_tiles) tile_sums[base + t] = c + incl - v;
-        __syncthreads();
-        if (t == SCAN_BLOCK - 1) carry = c + incl;
-        __syncthreads();
-    }
-    if (t == 0) tile_sums[n_tiles] = carry;
-}
-
-// stream_off[i] = skip + exclusive prefix of draws.  If changed_list != nullptr, jobs whose offset
+// stream_off[i] = skip + exclusive prefix of draws (tile_sums: scanned).  If changed_list != nullptr, jobs whose offset
 // changed are appended to it (repair passes re-run exactly those) and *first_mismatch (optional) receives the smallest such
 // job index.  Block-wise repair (pw_simulate_device, sink-heavy directed graphs): the arrays are those of a WINDOW of the
 // job array (starts / walks / stream_off advanced to its first job, n_jobs = its length, skip = the stream offset of its
 // first job); `job_base` = index of that first job, added to what is reported.
 __global__ void __launch_bounds__(SCAN_BLOCK)
-draws_offsets_kernel(const uint32_t *indptr, const uint32_t *starts, const uint32_t *walks,
-                     uint32_t L, uint64_t n_jobs, const uint64_t *tile_sums, uint64_t skip,
+draws_offsets_kernel(JobDraws draws, uint64_t n_jobs, const uint64_t *tile_sums, uint64_t skip,
                      uint64_t *stream_off, uint32_t *changed_list,
                      unsigned long long *changed_count, uint64_t job_base, unsigned long long *first_mismatch) {
-    __shared__ uint64_t sh[SCAN_BLOCK];
-    const int t = threadIdx.x;
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)t * SCAN_ITEMS;
-    uint64_t loc[SCAN_ITEMS];
-    uint64_t s = 0;
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        loc[k] = base + k < n_jobs ? job_draws(indptr, starts, walks, L, base + k) : 0;
-        s += loc[k];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int off = 1; off < SCAN_BLOCK; off <<= 1) {
-        uint64_t add = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    uint64_t run = skip + tile_sums[blockIdx.x] + sh[t] - s;
+    __shared__ uint64_t wave_tot[4], wave_min[4];
+    uint64_t loc[SCAN_ITEMS], total;
+    const uint64_t s = tile_load<uint64_t>(draws, n_jobs, loc);
+    uint64_t run = skip + tile_sums[blockIdx.x] + block_excl_scan(s, wave_tot, &total);
+    const uint64_t base = tile_first();
     uint64_t first = ~0ull;
     for (int k = 0; k < SCAN_ITEMS; k++) {
         uint64_t i = base + k;
@@ -382,14 +316,8 @@ draws_offsets_kernel(const uint32_t *indptr, const uint32_t *starts, const uint3
         run += loc[k];
     }
     if (first_mismatch) {   // (one atomic per tile at most)
-        __syncthreads();
-        sh[t] = first;
-        __syncthreads();
-        for (int s2 = SCAN_BLOCK / 2; s2 > 0; s2 >>= 1) {
-            if (t < s2 && sh[t + s2] < sh[t]) sh[t] = sh[t + s2];
-            __syncthreads();
-        }
-        if (t == 0 && sh[0] != ~0ull) atomicMin(first_mismatch, (unsigned long long)sh[0]);
+        first = block_min(first, wave_min);
+        if (threadIdx.x == 0 && first != ~0ull) atomicMin(first_mismatch, (unsigned long long)first);
     }
 }
 

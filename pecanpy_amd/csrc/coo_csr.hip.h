@@ -6,7 +6,7 @@
 //
 // One code path for any m and any row length:
 //   1. coo_validate_kernel   ids in range, weights finite, keep[i] = weight > 0, dropped count, largest id
-//   2. scan of keep[]        rank of every kept edge = its place in insertion order
+//   2. scan of keep[]        rank of every kept edge = its place in insertion order (this scan and those below: scan.hip.h)
 //   3. coo_expand_kernel     insertion j -> key (src << bits | dst), bits = ceil(log2 n_nodes), in insertion order
 //   4. LSD radix sort        ceil(2 bits / 8) passes of 8 bits: per-wavefront histogram, scan, STABLE scatter -- equal
 //                            keys stay in insertion order, so the last of a run of equal keys is the last insertion
@@ -28,55 +28,9 @@
 
 namespace pw {
 
-constexpr int USCAN_ITEMS = 16;                    // consecutive elements per thread
-constexpr int USCAN_TILE = 256 * USCAN_ITEMS;       // elements per workgroup
 constexpr int RADIX_BITS = 8;
 constexpr int RADIX_BINS = 1 << RADIX_BITS;
 constexpr int RADIX_SUB = 2048;                   // elements per wavefront (32 rounds of 64)
-
-// ---- exclusive scan of uint32[n] in place: tile sums, (recursive) scan of the sums, tile scan with its offset ------------
-__device__ __forceinline__ uint32_t scan_block_exclusive(uint32_t v, uint32_t *total) {   // over the 256 threads of a workgroup
-    __shared__ uint32_t wave_tot[4];
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan_u32(v);
-    if (lane == WAVE - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < 4; w++) {
-        const uint32_t t = wave_tot[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
-__global__ void __launch_bounds__(256)
-scan_reduce_kernel(const uint32_t *__restrict__ x, uint64_t n, uint32_t *__restrict__ sums) {
-    const uint64_t first = (uint64_t)blockIdx.x * USCAN_TILE + (uint64_t)threadIdx.x * USCAN_ITEMS;
-    uint32_t s = 0;
-    for (int k = 0; k < USCAN_ITEMS; k++)
-        if (first + k < n) s += x[first + k];
-    uint32_t total;
-    (void)scan_block_exclusive(s, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(256)
-scan_apply_kernel(uint32_t *__restrict__ x, uint64_t n, const uint32_t *__restrict__ sums) {   // sums: scanned; NULL = one tile
-    const uint64_t first = (uint64_t)blockIdx.x * USCAN_TILE + (uint64_t)threadIdx.x * USCAN_ITEMS;
-    uint32_t v[USCAN_ITEMS], s = 0;
-    for (int k = 0; k < USCAN_ITEMS; k++) {
-        v[k] = first + k < n ? x[first + k] : 0u;
-        s += v[k];
-    }
-    uint32_t total;
-    uint32_t run = scan_block_exclusive(s, &total) + (sums ? sums[blockIdx.x] : 0u);
-    for (int k = 0; k < USCAN_ITEMS; k++) {
-        if (first + k < n) x[first + k] = run;
-        run += v[k];
-    }
-}
 
 // ---- edge list -> keys --------------------------------------------------------------------------------------------------
 // flags: [0] first edge with an id outside [0, limit)   [1] first edge with a NaN / infinite weight

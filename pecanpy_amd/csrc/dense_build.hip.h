@@ -24,7 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "wave.h"
+#include "scan.hip.h"
 
 namespace pw {
 
@@ -80,24 +80,6 @@ dense_count_kernel(const T *__restrict__ mat, uint32_t n, uint32_t wpr, uint64_t
         atomicOr(flags, (any_unit ? DENSE_FLAG_NOT_UNIT : 0u) | (any_neg ? DENSE_FLAG_NOT_NONNEG : 0u));
 }
 
-// exclusive scan of one value per thread over the 256 threads of the workgroup; `tot` = 4 words of LDS that the caller does
-// not touch between two calls without a barrier of its own
-__device__ __forceinline__ uint32_t dense_block_scan(uint32_t v, uint32_t *tot, uint32_t *total) {
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan_u32(v);
-    if (lane == WAVE - 1) tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const uint32_t t = tot[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 // ---- adjbits + matrix -> indices, data --------------------------------------------------------------------------------------
 // The row's words go through LDS 256 at a time: thread t reads word c + t and the workgroup scans the 256 population counts
 // (plus the count of the chunks before), then wave w takes words w, w + 4, ... of the chunk: lane l of a set bit writes column
@@ -120,7 +102,7 @@ dense_fill_kernel(const T *__restrict__ mat, uint32_t n, uint32_t wpr, const uin
             const uint32_t k = c + threadIdx.x;
             const uint64_t word = k < wpr ? bits[k] : 0ull;
             uint32_t total;
-            const uint32_t before = dense_block_scan((uint32_t)__popcll(word), s_tot, &total);
+            const uint32_t before = block_excl_scan((uint32_t)__popcll(word), s_tot, &total);
             s_word[threadIdx.x] = word;
             s_base[threadIdx.x] = run + before;
             __syncthreads();

@@ -7,7 +7,7 @@
 //
 //   1. el_count_kernel      one wavefront per 1024-byte segment, 16 bytes per lane: rejects the bytes read_edgelist rejects
 //                           (>= 0x80, control bytes but \t \r \n, a \r without \n behind it) and counts the segment's newlines
-//      scan of the counts   (coo_csr.hip.h's scan)
+//      scan of the counts   (scan.hip.h)
 //      el_starts_kernel     the same segments again: line k + 1 starts behind newline k
 //   2. el_lines_kernel      one thread per line: el_tokenize_line (strip, split(delimiter), the term-count rules, the stripped
 //                           spans of id1 / id2, el_parse_weight) -> token records (offset, length, FNV-1a hash), float64 weight

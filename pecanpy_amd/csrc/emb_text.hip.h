@@ -5,8 +5,7 @@
 // printf("%.6f", (double)x) = Python's "%.6f" % float(x).  Three steps, the shape of dense_build.hip.h:
 //   emb_count_kernel   one wavefront per row: every component's length, summed over the row's lanes, plus the name, the
 //                      separators and the newline -> the row's byte count (uint64)
-//   emb_scan_*         exclusive scan of the row counts in 64 bits (the file passes 4 GB at RMAT-22): tile sums,
-//                      (recursive) scan of the sums, tile scan with its offset
+//   exclusive scan     of the row counts in place, in 64 bits (the file passes 4 GB at RMAT-22): scan.hip.h
 //   emb_fill_kernel    one wavefront per row, 64 components per trip: a lane decomposes its value once (F6), the scan of
 //                      the lengths over the lanes gives its position in the trip's text, the lanes write their characters to
 //                      the wavefront's LDS stage, and the stage leaves as 16-byte vector stores at the text's final offset
@@ -155,7 +154,7 @@ PW_F6_HD uint32_t format_f6(float x, char *out) { return f6_emit(f6_decompose(x)
 }  // namespace pw
 
 #if defined(__HIPCC__)
-#include "wave.h"
+#include "scan.hip.h"
 
 namespace pw {
 
@@ -167,16 +166,6 @@ f6_selftest_kernel(const float *__restrict__ x, uint64_t n, char *__restrict__ c
     const F6 f = f6_decompose(x[i]);
     const uint32_t len = f6_emit(f, chars + i * F6_SLOT);
     lens[i] = len == f6_len(f) ? len : 0xffffffffu;   // (the count pass and the fill pass must agree)
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v) {
-    const int lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint64_t t = shfl_up_uint<uint64_t>(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
 }
 
 // ---- row byte counts ---------------------------------------------------------------------------------------------------------
@@ -192,57 +181,6 @@ emb_count_kernel(const float *__restrict__ vec, uint64_t n_rows, uint32_t dim, c
         for (uint64_t c = (uint64_t)lane; c < dim; c += WAVE) mine += 1u + f6_len(f6_decompose(src[c]));   // " " + value
         const uint64_t incl = wave_incl_scan_u64(mine);
         if (lane == WAVE - 1) row_bytes[row] = (id_off[row + 1] - id_off[row]) + incl + 1u;   // + "\n"
-    }
-}
-
-// ---- exclusive scan of uint64[n] in place --------------------------------------------------------------------------------------
-constexpr int EMB_SCAN_ITEMS = 8;
-constexpr int EMB_SCAN_TILE = 256 * EMB_SCAN_ITEMS;
-
-__device__ __forceinline__ uint64_t emb_block_scan(uint64_t v, uint64_t *wave_tot, uint64_t *total) {   // wave_tot: 4 words of LDS
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const uint64_t incl = wave_incl_scan_u64(v);
-    if (lane == WAVE - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const uint64_t t = wave_tot[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
-__global__ void __launch_bounds__(256)
-emb_scan_reduce_kernel(const uint64_t *__restrict__ x, uint64_t n, uint64_t *__restrict__ sums) {
-    __shared__ uint64_t wave_tot[4];
-    const uint64_t first = (uint64_t)blockIdx.x * EMB_SCAN_TILE + (uint64_t)threadIdx.x * EMB_SCAN_ITEMS;
-    uint64_t s = 0;
-    for (int k = 0; k < EMB_SCAN_ITEMS; k++)
-        if (first + k < n) s += x[first + k];
-    uint64_t total;
-    (void)emb_block_scan(s, wave_tot, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(256)
-emb_scan_apply_kernel(uint64_t *__restrict__ x, uint64_t n, const uint64_t *__restrict__ sums) {   // sums: scanned; NULL = one tile
-    __shared__ uint64_t wave_tot[4];
-    const uint64_t first = (uint64_t)blockIdx.x * EMB_SCAN_TILE + (uint64_t)threadIdx.x * EMB_SCAN_ITEMS;
-    uint64_t v[EMB_SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < EMB_SCAN_ITEMS; k++) {
-        v[k] = first + k < n ? x[first + k] : 0ull;
-        s += v[k];
-    }
-    uint64_t total;
-    uint64_t run = emb_block_scan(s, wave_tot, &total) + (sums ? sums[blockIdx.x] : 0ull);
-#pragma unroll
-    for (int k = 0; k < EMB_SCAN_ITEMS; k++) {
-        if (first + k < n) x[first + k] = run;
-        run += v[k];
     }
 }
 

@@ -512,13 +512,12 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
         DevBuf<uint32_t> d_log, d_seglo, d_vm0;    // LOGGED build (below)
         DevBuf<unsigned long long> d_logoff;
     } sc;
-    const uint64_t n_tiles = ((uint64_t)n_lines + pw::CL_TILE - 1) / pw::CL_TILE;
     hipError_t e = g->gd->d_lines.p ? hipSuccess : g->gd->d_lines.alloc((size_t)n_lines + 1);
     if (e == hipSuccess) e = sc.d_small.alloc(small.size() + 1);
     if (e == hipSuccess) e = sc.d_large.alloc(large.size() + 1);
     if (e == hipSuccess) e = sc.d_segcnt.alloc((size_t)(segcnt_total + 1));
-    if (e == hipSuccess) e = sc.d_tiles.alloc(n_tiles + 1);
-    if (e == hipSuccess) e = sc.d_etiles.alloc(n_tiles + 1);
+    if (e == hipSuccess) e = sc.d_tiles.alloc(pw::scan_scratch_elems(n_lines));    // (scan.hip.h: [0] = the total)
+    if (e == hipSuccess) e = sc.d_etiles.alloc(pw::scan_scratch_elems(n_lines));
     if (e == hipSuccess && !small.empty())
         e = hipMemcpyAsync(sc.d_small.p, small.data(), sizeof(pw::LaneBuildItem) * small.size(), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess && !large.empty())
@@ -553,16 +552,12 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     // 45 ms per graph.  The default is the two-pass build.
     uint64_t log_slots = 0;
     bool logged = false;
-    const uint64_t nnz_tiles = ((uint64_t)nnz + pw::CL_TILE - 1) / pw::CL_TILE;
     if (env_on("PECANPY_AMD_INDEX_LOGGED") && !has_loop) {   // (self loops: the two-pass build)
         e = sc.d_logoff.alloc((size_t)nnz + 1);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(pw::log_tile_sums_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, g->gd->d_indptr.p,
-                               d_edge_row, nnz, sc.d_tiles.p);
-            hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, sc.d_tiles.p, nnz_tiles);
-            hipLaunchKernelGGL(pw::log_offsets_kernel, dim3((unsigned)nnz_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, g->gd->d_indptr.p,
-                               d_edge_row, nnz, sc.d_tiles.p, sc.d_logoff.p);
-            e = hipMemcpyAsync(&log_slots, sc.d_tiles.p + nnz_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+            pw::exclusive_scan(g->stream, nnz, pw::LogSlots{g->gd->d_lines.p, g->gd->d_indptr.p, d_edge_row},
+                               pw::ScanStore<unsigned long long>{sc.d_logoff.p}, sc.d_tiles.p);
+            e = hipMemcpyAsync(&log_slots, sc.d_tiles.p, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
         }
         INDEX_KERNELS_END(g);                       // (the allocations below are host time, not index-kernel time)
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
@@ -612,13 +607,16 @@ static int build_lane_index(pw_graph *g, LaneWorkItems &items, const uint32_t *d
     lists(false);
     uint64_t units = 0, entries = 0;
     auto offsets = [&](uint32_t max_len) -> hipError_t {   // list offsets (16-byte units) of the lists of at most max_len entries
-        hipLaunchKernelGGL(pw::clist_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, n_lines, nnz, sc.d_tiles.p, sc.d_etiles.p, max_len);
-        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, sc.d_tiles.p, n_tiles);
-        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, sc.d_etiles.p, n_tiles);
-        hipLaunchKernelGGL(pw::clist_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, n_lines, sc.d_tiles.p, max_len);
+        const uint64_t n_tiles = pw::scan_tiles(n_lines);
+        const pw::ListUnits list_units{g->gd->d_lines.p, max_len};
+        hipLaunchKernelGGL(pw::clist_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream, list_units, n_lines, nnz, sc.d_tiles.p + 1,
+                           sc.d_etiles.p + 1);
+        pw::scan_sums(g->stream, n_tiles, sc.d_tiles.p);
+        pw::scan_sums(g->stream, n_tiles, sc.d_etiles.p);
+        pw::scan_tile_offsets(g->stream, n_lines, list_units, pw::ListOffset{g->gd->d_lines.p, max_len}, sc.d_tiles.p);
         hipError_t e2 = hipGetLastError();
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&units, sc.d_tiles.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&entries, sc.d_etiles.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&units, sc.d_tiles.p, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(&entries, sc.d_etiles.p, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
         return e2;
     };
     e = offsets(0xffffffffu);
@@ -954,32 +952,6 @@ PW_EXPORT void pw_csr_dev_destroy(pw_csr_dev *c) {
     delete c;
 }
 
-namespace {
-
-uint64_t scan_tmp_elems(uint64_t n) {   // tile sums of every level of device_exclusive_scan
-    uint64_t total = 0;
-    while (n > (uint64_t)pw::USCAN_TILE) {
-        n = (n + pw::USCAN_TILE - 1) / pw::USCAN_TILE;
-        total += n;
-    }
-    return total;
-}
-
-// exclusive scan of d_x[0, n) in place on the null stream; d_tmp: scan_tmp_elems(n) words
-void device_exclusive_scan(uint32_t *d_x, uint64_t n, uint32_t *d_tmp) {
-    if (n == 0) return;
-    const uint64_t tiles = (n + pw::USCAN_TILE - 1) / pw::USCAN_TILE;
-    if (tiles == 1) {
-        hipLaunchKernelGGL(pw::scan_apply_kernel, dim3(1), dim3(256), 0, nullptr, d_x, n, (const uint32_t *)nullptr);
-        return;
-    }
-    hipLaunchKernelGGL(pw::scan_reduce_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, (const uint32_t *)d_x, n, d_tmp);
-    device_exclusive_scan(d_tmp, tiles, d_tmp + tiles);
-    hipLaunchKernelGGL(pw::scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, d_x, n, (const uint32_t *)d_tmp);
-}
-
-}  // namespace
-
 // The build behind pw_coo_to_csr_device and pw_edgelist_read_device.  d_w64 (the edge-list reader; d_weight is NULL then):
 // the float64 weight of every edge as parsed, all > 0.  The sort then carries the edge's index instead of a weight; a pair
 // inserted again with another float64 weight sets *conflict and ends the call without a result (PW_OK, *out NULL: the
@@ -1064,7 +1036,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     if (!rc && payload) rc = alloc(w_buf[1], n_ins, "sort weights (second buffer)");
     if (!rc && d_w64) rc = alloc(conflict_buf, 1, "conflict flag");
     if (!rc) rc = alloc(hist_buf, hist_elems, "radix histograms");
-    if (!rc) rc = alloc(tmp_buf, scan_tmp_elems(scan_max), "scan tile sums");
+    if (!rc) rc = alloc(tmp_buf, pw::scan_scratch_elems(scan_max), "scan tile sums");
     if (rc) return rc;
     uint64_t *d_keys[2] = {keys_buf[0].p, keys_buf[1].p};   // (the sort swaps the two views; the owners stay put)
     uint32_t *d_w[2] = {w_buf[0].p, w_buf[1].p};
@@ -1073,7 +1045,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     HIP_TRY(hipEventRecord(mem.ev[2], nullptr));
     if (d_weight && dropped) {
         HIP_TRY(hipMemsetAsync(d_keep + m, 0, sizeof(uint32_t), nullptr));
-        device_exclusive_scan(d_keep, m + 1, d_tmp);
+        pw::exclusive_scan_inplace(nullptr, d_keep, m + 1, d_tmp);
     }
     if (n_ins) {
         if (d_w64)
@@ -1086,7 +1058,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
         const unsigned wave_grid = (unsigned)((n_waves + 3) / 4);
         for (int shift = 0; shift < 2 * bits; shift += pw::RADIX_BITS) {
             hipLaunchKernelGGL(pw::radix_hist_kernel, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], n_ins, shift, d_hist, n_waves);
-            device_exclusive_scan(d_hist, hist_elems, d_tmp);
+            pw::exclusive_scan_inplace(nullptr, d_hist, hist_elems, d_tmp);
             if (payload)
                 hipLaunchKernelGGL(pw::radix_scatter_kernel<true>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const uint32_t *)d_w[0],
                                    d_keys[1], d_w[1], n_ins, shift, (const uint32_t *)d_hist, n_waves);
@@ -1103,7 +1075,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     uint32_t nnz32 = 0;
     if (n_ins) {
         hipLaunchKernelGGL(pw::coo_mark_kernel, dim3((unsigned)((n_ins + 256) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], n_ins, d_pos);
-        device_exclusive_scan(d_pos, n_ins + 1, d_tmp);
+        pw::exclusive_scan_inplace(nullptr, d_pos, n_ins + 1, d_tmp);
         if (d_w64)
             hipLaunchKernelGGL(pw::coo_conflict_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0],
                                (const uint32_t *)d_w[0], d_w64, n_ins, m, conflict_buf.p);
@@ -1323,14 +1295,14 @@ PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int direct
     const unsigned seg_grid = (unsigned)((n_seg + 3) / 4);
     alloc(d_flags, 1);
     alloc(d_segcnt, n_seg + 1);
-    alloc(d_tmp, scan_tmp_elems(n_seg + 1));
+    alloc(d_tmp, pw::scan_scratch_elems(n_seg + 1));
     alloc(d_delim, pw::EL_MAX_DELIM);
     if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
     HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), nullptr));
     HIP_TRY(hipMemsetAsync(d_segcnt.p + n_seg, 0, sizeof(uint32_t), nullptr));   // (the scan's last input: its output is the total)
     HIP_TRY(hipMemcpyAsync(d_delim.p, delimiter, dl, hipMemcpyHostToDevice, nullptr));
     hipLaunchKernelGGL(pw::el_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, d_segcnt.p, d_flags.p);
-    device_exclusive_scan(d_segcnt.p, n_seg + 1, d_tmp.p);
+    pw::exclusive_scan_inplace(nullptr, d_segcnt.p, n_seg + 1, d_tmp.p);
     HIP_TRY(hipGetLastError());
     uint32_t h_flags = 0, n_newlines = 0;
     HIP_TRY(hipMemcpy(&n_newlines, d_segcnt.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1368,7 +1340,7 @@ PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int direct
     alloc(d_table, table_size);
     alloc(d_slot, n_tok);
     alloc(d_first, n_tok + 1);
-    alloc(d_tmp, scan_tmp_elems(n_tok + 1));
+    alloc(d_tmp, pw::scan_scratch_elems(n_tok + 1));
     alloc(d_src, n_lines);
     alloc(d_dst, n_lines);
     if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
@@ -1376,7 +1348,7 @@ PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int direct
     hipLaunchKernelGGL(pw::el_insert_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, (const pw::ElToken *)d_tok.p, n_tok, d_table.p,
                        (uint32_t)(table_size - 1), d_slot.p);
     hipLaunchKernelGGL(pw::el_first_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const uint32_t *)d_table.p, (const uint32_t *)d_slot.p, n_tok, d_first.p);
-    device_exclusive_scan(d_first.p, n_tok + 1, d_tmp.p);
+    pw::exclusive_scan_inplace(nullptr, d_first.p, n_tok + 1, d_tmp.p);
     HIP_TRY(hipGetLastError());
     uint32_t n_nodes = 0;
     HIP_TRY(hipMemcpy(&n_nodes, d_first.p + n_tok, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1866,9 +1838,8 @@ static int compute_offsets(pw_graph *g, const uint32_t *d_starts, const uint32_t
                            uint64_t n_jobs, uint64_t skip, bool track_changes, uint64_t *total,
                            uint64_t *n_changed, uint64_t j0 = 0, uint64_t n_all = 0, uint64_t *first_mismatch = nullptr) {
     if (n_all < j0 + n_jobs) n_all = j0 + n_jobs;
-    uint64_t n_tiles = (n_jobs + pw::SCAN_TILE - 1) / pw::SCAN_TILE;
     if (grow(g->stream_off, n_all + 1)) return PW_ERR_NOMEM;
-    if (grow(g->tile_sums, (n_all + pw::SCAN_TILE - 1) / pw::SCAN_TILE + 1)) return PW_ERR_NOMEM;
+    if (grow(g->tile_sums, pw::scan_scratch_elems(n_all))) return PW_ERR_NOMEM;   // (scan.hip.h: [0] = the total)
     if (track_changes && grow(g->changed, n_all)) return PW_ERR_NOMEM;
     if (!g->gd->d_hasnbr.p) {
         const uint32_t words = (g->gd->n_nodes + 31u) / 32u;
@@ -1881,15 +1852,15 @@ static int compute_offsets(pw_graph *g, const uint32_t *d_starts, const uint32_t
     if (track_changes) HIP_TRY(hipMemsetAsync(cc, 0, sizeof(unsigned long long), g->stream));
     unsigned long long *fm = first_mismatch ? g->counters.p + pw::CTR_FIRST_CHANGED : nullptr;
     if (fm) HIP_TRY(hipMemsetAsync(fm, 0xff, sizeof(unsigned long long), g->stream));
-    hipLaunchKernelGGL(pw::draws_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream,
-                       g->gd->d_hasnbr.p, w_starts, w_walks, L, n_jobs, g->tile_sums.p);
-    hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, g->tile_sums.p, n_tiles);
-    hipLaunchKernelGGL(pw::draws_offsets_kernel, dim3((unsigned)n_tiles), dim3(pw::SCAN_BLOCK), 0, g->stream,
-                       g->gd->d_hasnbr.p, w_starts, w_walks, L, n_jobs, g->tile_sums.p, skip, g->stream_off.p + j0,
+    const pw::JobDraws draws{g->gd->d_hasnbr.p, w_starts, w_walks, L};
+    pw::scan_tile_sums(g->stream, n_jobs, draws, g->tile_sums.p);
+    pw::scan_sums(g->stream, pw::scan_tiles(n_jobs), g->tile_sums.p);
+    hipLaunchKernelGGL(pw::draws_offsets_kernel, dim3((unsigned)pw::scan_tiles(n_jobs)), dim3(pw::SCAN_BLOCK), 0, g->stream,
+                       draws, n_jobs, (const uint64_t *)(g->tile_sums.p + 1), skip, g->stream_off.p + j0,
                        track_changes ? g->changed.p : nullptr, cc, j0, fm);
     HIP_TRY(hipGetLastError());
     uint64_t tot = 0;
-    HIP_TRY(hipMemcpyAsync(&tot, g->tile_sums.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&tot, g->tile_sums.p, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
     unsigned long long nc = 0, fmv = ~0ull;
     if (track_changes) HIP_TRY(hipMemcpyAsync(&nc, cc, sizeof(nc), hipMemcpyDeviceToHost, g->stream));
     if (fm) HIP_TRY(hipMemcpyAsync(&fmv, fm, sizeof(fmv), hipMemcpyDeviceToHost, g->stream));
@@ -2243,26 +2214,20 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, const LaneSw
                            (const float *)g->gd->d_data.p, g->gd->n_nodes, g->gd->d_wp1.p);
     }
     DevBuf<uint64_t> tiles;
-    const uint64_t n_tiles = ((uint64_t)nnz + pw::CL_TILE - 1) / pw::CL_TILE;
-    hipError_t e = tiles.alloc(n_tiles + 1);
+    hipError_t e = tiles.alloc(pw::scan_scratch_elems(nnz));   // (scan.hip.h: [0] = the total)
     if (e != hipSuccess) return give_up();
-    uint64_t *const d_tiles = tiles.p;
     HIP_TRY(hipEventRecord(g->ev[4], g->stream));
     // offsets of the per-entry delta lists (one float64 per list entry) and of the recorded chain values
     uint64_t entries = 0, records = 0;
-    hipLaunchKernelGGL(pw::entry_tile_sums_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles);
-    hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-    hipLaunchKernelGGL(pw::entry_offsets_kernel<0>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles, g->gd->d_wl_off.p);
+    pw::exclusive_scan(g->stream, nnz, pw::EntryCount<0>{g->gd->d_lines.p}, pw::ScanStore<unsigned long long>{g->gd->d_wl_off.p}, tiles.p);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&entries, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&entries, tiles.p, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::entry_tile_sums_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles);
-        hipLaunchKernelGGL(pw::scan_tile_sums_kernel, dim3(1), dim3(pw::SCAN_BLOCK), 0, g->stream, d_tiles, n_tiles);
-        hipLaunchKernelGGL(pw::entry_offsets_kernel<1>, dim3((unsigned)n_tiles), dim3(pw::CL_BLOCK), 0, g->stream, g->gd->d_lines.p, nnz, d_tiles, g->gd->d_wck_off.p);
+        pw::exclusive_scan(g->stream, nnz, pw::EntryCount<1>{g->gd->d_lines.p}, pw::ScanStore<unsigned long long>{g->gd->d_wck_off.p}, tiles.p);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&records, d_tiles + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&records, tiles.p, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("weighted lane tables (offsets): ") + hipGetErrorString(e));
     size_t free_b = 0, total_b = 0;
@@ -4247,27 +4212,6 @@ namespace {
 
 constexpr uint64_t EMB_CHUNK_DEFAULT = 32ull << 20;   // bytes of text per chunk: PECANPY_AMD_EMB_CHUNK_BYTES overrides
 
-uint64_t emb_scan_tmp_elems(uint64_t n) {   // tile sums of every level of emb_exclusive_scan
-    uint64_t total = 0;
-    while (n > (uint64_t)pw::EMB_SCAN_TILE) {
-        n = (n + pw::EMB_SCAN_TILE - 1) / pw::EMB_SCAN_TILE;
-        total += n;
-    }
-    return total;
-}
-
-// exclusive scan of d_x[0, n) in place on the null stream; d_tmp: emb_scan_tmp_elems(n) words
-void emb_exclusive_scan(uint64_t *d_x, uint64_t n, uint64_t *d_tmp) {
-    const uint64_t tiles = (n + pw::EMB_SCAN_TILE - 1) / pw::EMB_SCAN_TILE;
-    if (tiles <= 1) {
-        hipLaunchKernelGGL(pw::emb_scan_apply_kernel, dim3(1), dim3(256), 0, nullptr, d_x, n, (const uint64_t *)nullptr);
-        return;
-    }
-    hipLaunchKernelGGL(pw::emb_scan_reduce_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, (const uint64_t *)d_x, n, d_tmp);
-    emb_exclusive_scan(d_tmp, tiles, d_tmp + tiles);
-    hipLaunchKernelGGL(pw::emb_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, nullptr, d_x, n, (const uint64_t *)d_tmp);
-}
-
 // What a call that writes a text file from device memory owns -- released on every way out -- and the part the embedding
 // writer and the walk writer share: the scan of the row byte counts, then consecutive rows in chunks that fit a byte budget,
 // through one device buffer and two pinned host buffers.  A writer opens the file (with its header line, if it has one),
@@ -4322,7 +4266,7 @@ struct TextFile {
     int alloc_rows(uint64_t n_rows, const char *id_chars, const uint64_t *id_offsets, uint64_t n_names) {
         int rc;
         if ((rc = alloc(d_ids, id_offsets[n_names])) || (rc = alloc(d_id_off, n_names + 1)) || (rc = alloc(d_row_off, n_rows + 1)) ||
-            (rc = alloc(d_tmp, emb_scan_tmp_elems(n_rows + 1))) || (rc = alloc(d_flags, 1)))
+            (rc = alloc(d_tmp, pw::scan_scratch_elems(n_rows + 1))) || (rc = alloc(d_flags, 1)))
             return rc;
         if (id_offsets[n_names]) HIP_TRY(hipMemcpyAsync(d_ids.p, id_chars, id_offsets[n_names], hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(d_id_off.p, id_offsets, sizeof(uint64_t) * (n_names + 1), hipMemcpyHostToDevice, nullptr));
@@ -4339,7 +4283,7 @@ struct TextFile {
         return 0;
     }
     int count_end(uint64_t n_rows) {
-        emb_exclusive_scan(d_row_off.p, n_rows + 1, d_tmp.p);
+        pw::exclusive_scan_inplace(nullptr, d_row_off.p, n_rows + 1, d_tmp.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[1], nullptr));
         row_off.resize(n_rows + 1);
@@ -4627,6 +4571,34 @@ PW_EXPORT int pw_selftest_format_f6(int on_device, int device, const float *x, u
     if (e == hipSuccess) e = hipMemcpy(lens, d_lens.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_format_f6: ") + hipGetErrorString(e));
     return PW_OK;
+}
+
+// x[0, n) of uint32 (width 32) or uint64 (width 64) in host memory -> its exclusive scan in place, *total = the sum, through
+// scan.hip.h's entry on the null stream
+template <typename T> static int selftest_exclusive_scan(T *x, uint64_t n, uint64_t *total) {
+    DevBuf<T> d_x, d_scratch;
+    T sum = 0;
+    hipError_t e = d_x.alloc(n + 1);
+    if (e == hipSuccess) e = d_scratch.alloc(pw::scan_scratch_elems(n));
+    if (e == hipSuccess && n) e = hipMemcpy(d_x.p, x, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        pw::exclusive_scan_inplace(nullptr, d_x.p, n, d_scratch.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && n) e = hipMemcpy(x, d_x.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&sum, d_scratch.p, sizeof(T), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_exclusive_scan: ") + hipGetErrorString(e));
+    *total = sum;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_selftest_exclusive_scan(int device, int width, void *x, uint64_t n, uint64_t *total) {
+    if ((n && !x) || !total || (width != 32 && width != 64)) return fail(PW_ERR_INVALID, "bad argument");
+    int ndev = pw_device_count();
+    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    return width == 32 ? selftest_exclusive_scan((uint32_t *)x, n, total) : selftest_exclusive_scan((uint64_t *)x, n, total);
 }
 
 // ---- host self test of the exact-arithmetic decision ---------------------------------------------------

@@ -50,6 +50,7 @@
 // Registers decide everything here: any spill in the step loop costs more than a wave brings (queueing form: 106 VGPRs,
 // 4 workgroups per CU with its 36 KB of LDS; in place: 128; CHAINS: 142, 3 per CU).
 #pragma once
+#include "scan.hip.h"
 #include "walk_sparse.hip.h"
 
 namespace pw {
@@ -2005,10 +2006,6 @@ lane_lists_kernel(LaneBuildArgs a, const LaneBuildItem *__restrict__ items) {
     }
 }
 
-constexpr int CL_BLOCK = 256;
-constexpr int CL_ITEMS = 16;
-constexpr int CL_TILE = CL_BLOCK * CL_ITEMS;
-
 // ---- LOGGED build: slots of the log per entry, and the copy of the logged matches to their places ---------------------
 // slots of entry e2 = (h -> k): d_k when h takes the pair (the longer row; ties: the larger id; entries without a reverse
 // edge: their source) and both positions fit 16 bits, else 0
@@ -2019,48 +2016,11 @@ __device__ __forceinline__ uint32_t log_slots(const ELine *lines, const uint32_t
     const bool mine = rev == NOT_FOUND || d_h > d_k || (d_h == d_k && h > k);
     return (mine && d_h >= 2u && d_k) ? log_pair_slots(d_h, d_k) : 0u;
 }
-__global__ void __launch_bounds__(CL_BLOCK)
-log_tile_sums_kernel(const ELine *__restrict__ lines, const uint32_t *__restrict__ indptr, const uint32_t *__restrict__ edge_row, uint32_t nnz,
-                     uint64_t *tile_sums) {
-    __shared__ uint64_t sh[CL_BLOCK];
-    const uint64_t base = (uint64_t)blockIdx.x * CL_TILE + (uint64_t)threadIdx.x * CL_ITEMS;
-    uint64_t s = 0;
-    for (int k = 0; k < CL_ITEMS; k++)
-        if (base + k < nnz) s += log_slots(lines, indptr, edge_row, base + k);
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = CL_BLOCK / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = sh[0];
-}
-__global__ void __launch_bounds__(CL_BLOCK)
-log_offsets_kernel(const ELine *__restrict__ lines, const uint32_t *__restrict__ indptr, const uint32_t *__restrict__ edge_row, uint32_t nnz,
-                   const uint64_t *__restrict__ tile_sums, unsigned long long *off_out) {
-    __shared__ uint64_t sh[CL_BLOCK];
-    const int t = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * CL_TILE + (uint64_t)t * CL_ITEMS;
-    uint32_t loc[CL_ITEMS];
-    uint64_t s = 0;
-    for (int k = 0; k < CL_ITEMS; k++) {
-        loc[k] = base + k < nnz ? log_slots(lines, indptr, edge_row, base + k) : 0u;
-        s += loc[k];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int off = 1; off < CL_BLOCK; off <<= 1) {
-        const uint64_t add = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    uint64_t run = tile_sums[blockIdx.x] + sh[t] - s;
-    for (int k = 0; k < CL_ITEMS; k++) {
-        if (base + k < nnz) off_out[base + k] = run;
-        run += loc[k];
-    }
-}
+struct LogSlots {   // log_off = their exclusive scan (scan.hip.h)
+    const ELine *lines;
+    const uint32_t *indptr, *edge_row;
+    __device__ uint32_t operator()(uint64_t e2) const { return log_slots(lines, indptr, edge_row, e2); }
+};
 
 // The logged matches of every pair to their places: list (h -> k) = the low halves (positions in row k), list (k -> h) = the
 // high halves (positions in row h), both uint16.  One wavefront per 64 consecutive entries: lists of up to 32 matches are
@@ -2268,105 +2228,43 @@ eline_pivots_kernel(ELine *lines, const uint8_t *__restrict__ clist, uint32_t n_
     }
 }
 
-
-// tile_sums[b] = 16-byte units of tile b; entry_sums[b] = list entries of tile b
-__global__ void __launch_bounds__(CL_BLOCK)
-clist_tile_sums_kernel(const ELine *__restrict__ lines, uint32_t nnz, uint32_t nnz_real, uint64_t *tile_sums, uint64_t *entry_sums,
-                       uint32_t max_len) {
-    __shared__ uint64_t sh[CL_BLOCK], sh2[CL_BLOCK];
-    const uint64_t base = (uint64_t)blockIdx.x * CL_TILE + (uint64_t)threadIdx.x * CL_ITEMS;
-    uint64_t s = 0, s2 = 0;
-    for (int k = 0; k < CL_ITEMS; k++)
-        if (base + k < nnz) { s += list_units(lines, base + k, max_len); if (base + k < nnz_real) s2 += lines[base + k].n_in; }
-    sh[threadIdx.x] = s;
-    sh2[threadIdx.x] = s2;
-    __syncthreads();
-    for (int st = CL_BLOCK / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) { sh[threadIdx.x] += sh[threadIdx.x + st]; sh2[threadIdx.x] += sh2[threadIdx.x + st]; }
-        __syncthreads();
+// lines[e].coff = exclusive scan of the units (scan.hip.h) with ListUnits and ListOffset; the first level is a kernel of its
+// own because it sums a second quantity in the same pass over the lines: entry_sums[b] = list entries of tile b
+struct ListUnits {
+    const ELine *lines;
+    uint32_t max_len;
+    __device__ uint32_t operator()(uint64_t e) const { return list_units(lines, e, max_len); }
+};
+struct ListOffset {
+    ELine *lines;
+    uint32_t max_len;
+    __device__ void operator()(uint64_t e, uint64_t units_before) const {
+        const uint4 r0 = *(const uint4 *)(lines + e);
+        lines[e].coff = (!list_is_inline(r0.w, r0.y) && r0.y > max_len) ? EL_NO_LIST : (uint32_t)units_before;
     }
-    if (threadIdx.x == 0) { tile_sums[blockIdx.x] = sh[0]; entry_sums[blockIdx.x] = sh2[0]; }
-}
-
-// lines[e].coff = exclusive prefix sum of the units (tile_sums already scanned: scan_tile_sums_kernel)
-__global__ void __launch_bounds__(CL_BLOCK)
-clist_offsets_kernel(ELine *lines, uint32_t nnz, const uint64_t *__restrict__ tile_sums, uint32_t max_len) {
-    __shared__ uint64_t sh[CL_BLOCK];
-    const int t = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * CL_TILE + (uint64_t)t * CL_ITEMS;
-    uint32_t loc[CL_ITEMS];
-    uint64_t s = 0;
-    for (int k = 0; k < CL_ITEMS; k++) {
-        loc[k] = base + k < nnz ? list_units(lines, base + k, max_len) : 0u;
-        s += loc[k];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int off = 1; off < CL_BLOCK; off <<= 1) {
-        const uint64_t add = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    uint64_t run = tile_sums[blockIdx.x] + sh[t] - s;
-    for (int k = 0; k < CL_ITEMS; k++) {
-        if (base + k < nnz) {
-            const uint4 r0_ = *(const uint4 *)(lines + base + k);
-            lines[base + k].coff = (!list_is_inline(r0_.w, r0_.y) && r0_.y > max_len) ? EL_NO_LIST : (uint32_t)run;
-        }
-        run += loc[k];
-    }
+};
+__global__ void __launch_bounds__(SCAN_BLOCK)
+clist_tile_sums_kernel(ListUnits units, uint32_t nnz, uint32_t nnz_real, uint64_t *tile_sums, uint64_t *entry_sums) {
+    __shared__ uint64_t wave_tot[2][4];
+    const uint64_t base = tile_first();
+    uint64_t s = 0, s2 = 0, total, total2;
+    for (int k = 0; k < SCAN_ITEMS; k++)
+        if (base + k < nnz) { s += units(base + k); if (base + k < nnz_real) s2 += units.lines[base + k].n_in; }
+    (void)block_excl_scan(s, wave_tot[0], &total);
+    (void)block_excl_scan(s2, wave_tot[1], &total2);
+    if (threadIdx.x == 0) { tile_sums[blockIdx.x] = total; entry_sums[blockIdx.x] = total2; }
 }
 
 // Exclusive prefix sums over the CSR entries of a per-entry count (the weighted lane form's tables): MODE 0 = the list length
 // n_in (one float64 per list entry: wlist_kernel), MODE 1 = the recorded chain values of the entry's target row,
-// (degree - 1) / CHAIN_CKPT (wckpt_kernel).  Tile sums -> scan_tile_sums_kernel -> offsets.
-template <int MODE> __device__ __forceinline__ uint32_t entry_count(const ELine *lines, uint64_t e) {
-    const uint4 r0 = *(const uint4 *)(lines + e);
-    return MODE == 0 ? r0.y : (r0.w ? (r0.w - 1u) / CHAIN_CKPT : 0u);
-}
-template <int MODE>
-__global__ void __launch_bounds__(CL_BLOCK)
-entry_tile_sums_kernel(const ELine *__restrict__ lines, uint32_t nnz, uint64_t *tile_sums) {
-    __shared__ uint64_t sh[CL_BLOCK];
-    const uint64_t base = (uint64_t)blockIdx.x * CL_TILE + (uint64_t)threadIdx.x * CL_ITEMS;
-    uint64_t s = 0;
-    for (int k = 0; k < CL_ITEMS; k++)
-        if (base + k < nnz) s += entry_count<MODE>(lines, base + k);
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = CL_BLOCK / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
+// (degree - 1) / CHAIN_CKPT (wckpt_kernel).  The count functor of scan.hip.h's exclusive_scan.
+template <int MODE> struct EntryCount {
+    const ELine *lines;
+    __device__ uint32_t operator()(uint64_t e) const {
+        const uint4 r0 = *(const uint4 *)(lines + e);
+        return MODE == 0 ? r0.y : (r0.w ? (r0.w - 1u) / CHAIN_CKPT : 0u);
     }
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = sh[0];
-}
-template <int MODE>
-__global__ void __launch_bounds__(CL_BLOCK)
-entry_offsets_kernel(const ELine *__restrict__ lines, uint32_t nnz, const uint64_t *__restrict__ tile_sums, unsigned long long *off_out) {
-    __shared__ uint64_t sh[CL_BLOCK];
-    const int t = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * CL_TILE + (uint64_t)t * CL_ITEMS;
-    uint32_t loc[CL_ITEMS];
-    uint64_t s = 0;
-    for (int k = 0; k < CL_ITEMS; k++) {
-        loc[k] = base + k < nnz ? entry_count<MODE>(lines, base + k) : 0u;
-        s += loc[k];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int off = 1; off < CL_BLOCK; off <<= 1) {
-        const uint64_t add = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    uint64_t run = tile_sums[blockIdx.x] + sh[t] - s;
-    for (int k = 0; k < CL_ITEMS; k++) {
-        if (base + k < nnz) off_out[base + k] = run;
-        run += loc[k];
-    }
-}
+};
 
 // Recorded chain values: for every CSR entry e = (u -> v) whose target row has more than CHAIN_CKPT entries, the exact
 // float32 value of the reference's cumsum(w / tot) for a walker that arrived by e (prev = u, cur = v), after every

@@ -3,13 +3,13 @@
 // A row r of the walk matrix uint32[n_walks, walk_length + 2] with len = r[walk_length + 1] gives one line: the names of
 // r[0] .. r[len - 1] joined by single spaces, then "\n" (len == 0: just "\n").  Cells at positions >= len are never read.
 // The names are gathered by node index from the blob and offsets of pw_vectors_write_text_device.  The shape of
-// emb_text.hip.h, whose scan, stage store and piece size are used as they are:
+// emb_text.hip.h, whose stage store and piece size are used as they are:
 //   walk_text_count_kernel   one wavefront per row, lane l takes tokens l, l + 64, ...: the sum of name length + 1 in 64 bits.
 //                            Also the validation pass: a length above walk_length + 1, or a token >= n_names among the first
 //                            len cells, is compared -- never used as an index --, the row counts as 0 bytes and its number goes
 //                            to found[0] (length) or found[1] (token) with an atomic minimum, so the host names the first such row
 //                            whatever the order the wavefronts ran in; it launches no fill pass then.
-//   emb_scan_*               exclusive scan of the row counts in 64 bits
+//   exclusive scan           of the row counts in place, in 64 bits (scan.hip.h)
 //   walk_text_fill_kernel    one wavefront per row, 64 tokens per trip: a lane holds its token's name offset and length, the
 //                            scan of length + 1 over the lanes gives its position in the trip's text.  A trip whose text fits
 //                            the stage (EMB_PIECE bytes: every trip of names up to 47 bytes) is assembled there -- a lane copies

@@ -70,6 +70,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     v = dpp_add_u32<0x143, 0xC>(v);
     return v;
 }
+__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v) {   // 64-bit values: by shuffles
+    const int lane = lane_id();
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint64_t t = shfl_up_uint<uint64_t>(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
 // the same scan over float64 values (two DPP moves + one add per level; lanes without a source add +0.0: exact)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_add_f64(double v) {

@@ -119,7 +119,9 @@ def test_writer_kernels_compile_for_gfx950_without_scratch_or_spills(tmp_path):
     """``hipcc --offload-arch=gfx950`` on csrc/emb_text.hip.h with the library's flags: the compiler's resource remarks must
     show no scratch and no spills (the decomposition's five limbs stay in registers: every index into them is static).
 
-    Figures of this tree: VGPRs 46 (f6_selftest_kernel) / 58 (emb_count_kernel) / 10 and 30 (the scan) / 74
+    The scan of the row counts is csrc/scan.hip.h's kernel pair in the 64-bit in-place instantiation the writers launch.
+
+    Figures of this tree: VGPRs 46 (f6_selftest_kernel) / 58 (emb_count_kernel) / 38 and 48 (the scan) / 74
     (emb_fill_kernel, 12 416 bytes of LDS), scratch 0 bytes per lane and no spills in all five."""
     import os
     import re
@@ -129,13 +131,14 @@ def test_writer_kernels_compile_for_gfx950_without_scratch_or_spills(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     csrc = os.path.join(os.path.dirname(os.path.abspath(embed.__file__)), "csrc")
     src = tmp_path / "emb_only.hip"
-    src.write_text('#include "emb_text.hip.h"\n')
+    src.write_text('#include "emb_text.hip.h"\n'
+                   'template void pw::exclusive_scan_inplace<uint64_t>(hipStream_t, uint64_t *, uint64_t, uint64_t *);\n')
     res = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", f"-I{csrc}",
                           "-c", str(src), "-o", str(tmp_path / "emb_only.o"), "-Rpass-analysis=kernel-resource-usage"],
                          capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
     blocks = re.split(r"remark: [^\n]*Function Name: ", res.stderr)[1:]
-    kernels = ("f6_selftest_kernel", "emb_count_kernel", "emb_scan_reduce_kernel", "emb_scan_apply_kernel", "emb_fill_kernel")
+    kernels = ("f6_selftest_kernel", "emb_count_kernel", "tile_sums_kernel", "tile_offsets_kernel", "emb_fill_kernel")
     figures = {}
     for b in blocks:
         name = next((k for k in kernels if k in b.split("\n")[0]), None)
