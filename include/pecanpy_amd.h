@@ -216,7 +216,10 @@ int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, int on_devic
  *                             entry, -0.0 is none.  n_nodes == 0: PW_ERR_INVALID.  The matrix is only read, and not referenced
  *                             after the call.  Work runs on the handle's stream; the call returns when it is done.
  *   pw_dense_create_from_csr  the same handle from a pw_csr_dev (pw_coo_to_csr_device): the dense float64 form of that CSR --
- *                             float32 weights widened, every weight 1.0 when the CSR has none.  The pw_csr_dev stays valid.
+ *                             float32 weights widened, every weight 1.0 when the CSR has none.  A pw_csr_dev that carries float64
+ *                             weights (pw_edgelist_read_device_ex, PW_EDGELIST_KEEP_F64) gives them as they are, and unit /
+ *                             dense_nonneg are judged on them: weights that are all 1.00000001 are 1.0 in float32 and still make
+ *                             no unit handle; weights that are all exactly 1.0 do, values dropped.  The pw_csr_dev stays valid.
  *   build_ms (optional)       HIP-event time of the build's kernels; allocations and the small device-to-host reads between
  *                             them are outside it (as pw_csr_dev_shape's build_ms).
  *   pw_dense_noise_thresholds the node2vec+ thresholds pw_noise_thresholds_dense computes from the matrix, computed on the device
@@ -511,8 +514,18 @@ void pw_edgelist_destroy(pw_edgelist *e);
  * pw_csr_dev_shape has its kernels' time) -- and lines, n_nodes, file_bytes.
  *   pw_edgelist_ids_shape   n_nodes, id_bytes (the names' characters in all)
  *   pw_edgelist_ids_export  pw_edgelist_export's layout: id_offsets uint64[n_nodes + 1], id_chars char[id_bytes], vertex v's
- *                           name = id_chars[id_offsets[v] : id_offsets[v + 1]], sliced from the bytes the call read */
+ *                           name = id_chars[id_offsets[v] : id_offsets[v + 1]], sliced from the bytes the call read
+ * pw_edgelist_read_device_ex is the same call with a flags word (unknown bits: PW_ERR_INVALID); pw_edgelist_read_device is
+ * flags = 0.
+ *   PW_EDGELIST_KEEP_F64    a weighted file's CSR also keeps, per entry, the winning line's float64 weight exactly as parsed (8
+ *                           more bytes per entry, written by the launch that writes the float32 data, which stays bit for bit).
+ *                           pw_dense_create_from_csr then stores those values instead of the widened float32 ones: the handle of
+ *                           the reference's to_dense(), which keeps the Python float.  Without the bit, and for an unweighted
+ *                           file, nothing more is allocated.
+ *   pw_csr_dev_export_f64   test hook: data64 float64[nnz] = those weights; PW_ERR_UNSUPPORTED when the CSR holds none (built by
+ *                           pw_coo_to_csr_device, read without the bit, or from an unweighted file) */
 enum { PW_EDGELIST_OK = 0, PW_EDGELIST_NEEDS_HOST_READER = 1, PW_EDGELIST_IO = 2 };
+enum { PW_EDGELIST_KEEP_F64 = 1 };
 typedef struct pw_edgelist_dev_stats {
     double upload_ms, scan_ms, ids_ms, build_ms;
     uint64_t lines, n_nodes, file_bytes;
@@ -520,6 +533,9 @@ typedef struct pw_edgelist_dev_stats {
 typedef struct pw_edgelist_ids pw_edgelist_ids;
 int pw_edgelist_read_device(const char *path, int weighted, int directed, const char *delimiter, int device, pw_csr_dev **csr,
                             pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats);
+int pw_edgelist_read_device_ex(const char *path, int weighted, int directed, const char *delimiter, int device, uint32_t flags,
+                               pw_csr_dev **csr, pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats);
+int pw_csr_dev_export_f64(const pw_csr_dev *c, double *data64);
 int pw_edgelist_ids_shape(const pw_edgelist_ids *ids, uint64_t *n_nodes, uint64_t *id_bytes);
 int pw_edgelist_ids_export(const pw_edgelist_ids *ids, uint64_t *id_offsets, char *id_chars);
 void pw_edgelist_ids_destroy(pw_edgelist_ids *ids);

@@ -106,6 +106,8 @@ class PwEdgelistDevStats(C.Structure):
 
 
 EDGELIST_OK, EDGELIST_NEEDS_HOST_READER, EDGELIST_IO = 0, 1, 2   # pw_edgelist_read_device's non-negative results
+EDGELIST_KEEP_F64 = 1   # pw_edgelist_read_device_ex's flag bit: the CSR keeps the float64 weights for the dense build
+ERR_UNSUPPORTED = -4    # PW_ERR_UNSUPPORTED
 
 MODE_IDS = {
     "SparseOTF": 0,
@@ -192,6 +194,9 @@ SYMBOLS = {
     "pw_edgelist_destroy": (None, [C.c_void_p]),
     "pw_edgelist_read_device": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                           C.POINTER(PwEdgelistDevStats)]),
+    "pw_edgelist_read_device_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(PwEdgelistDevStats)]),
+    "pw_csr_dev_export_f64": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pw_edgelist_ids_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pw_edgelist_ids_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pw_edgelist_ids_destroy": (None, [C.c_void_p]),

@@ -120,8 +120,9 @@ def read_graph(args):
     if args.input.endswith(".npz"):
         g.read_npz(args.input, args.weighted, implicit_ids=args.implicit_ids)
     elif hasattr(g, "read_edg_device") and not os.environ.get("PECANPY_AMD_HOST_READER"):
-        # sparse modes: the edge list is parsed on the device (same arrays, warnings and exceptions: read_edg_device falls back
-        # to read_edg by itself); PECANPY_AMD_HOST_READER=1 keeps the host reader
+        # the edge list is parsed on the device, for the dense modes into the dense handle without an N x N host matrix (same
+        # arrays, warnings and exceptions: read_edg_device falls back to read_edg by itself); PECANPY_AMD_HOST_READER=1 keeps
+        # the host reader
         g.read_edg_device(args.input, args.weighted, args.directed, args.delimiter)
         if args.verbose:
             print(f"edge list read by the {g.last_build_stats['reader']} reader")

@@ -13,7 +13,8 @@
 //   5. coo_mark / scan / coo_compact   keep-last-of-run, output position, indices / data / row of every kept entry
 //   6. coo_indptr_kernel     indptr[r] = lower bound of r among the (ascending) rows
 // The edge-list reader (edgelist_dev.hip.h) takes the same path with float64 weights: coo_expand_lines_kernel, the sort carrying
-// the line index, coo_conflict_kernel (a pair inserted again with another float64 weight), coo_compact_lines_kernel.
+// the line index, coo_conflict_kernel (a pair inserted again with another float64 weight), coo_compact_lines_kernel (which
+// also leaves the winner's float64 weight beside its float32 rounding when the caller keeps them for the dense build).
 // Determinism: every output word is a function of the input alone.  Atomics are used for integer counts, a minimum and a
 // maximum only (order-independent results); the scatter ranks equal digits by lane order (ballots), never by arrival.
 //
@@ -193,7 +194,7 @@ coo_conflict_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restric
 __global__ void __launch_bounds__(256)
 coo_compact_lines_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ line, const double *__restrict__ w64, uint64_t n,
                          uint64_t m, const uint32_t *__restrict__ pos, int bits, uint64_t nnz, uint32_t *__restrict__ indices,
-                         float *__restrict__ data, uint32_t *__restrict__ rows) {
+                         float *__restrict__ data, double *__restrict__ data64, uint32_t *__restrict__ rows) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const uint64_t key = keys[j];
@@ -203,7 +204,9 @@ coo_compact_lines_kernel(const uint64_t *__restrict__ keys, const uint32_t *__re
     indices[p] = (uint32_t)(key & ((1ull << bits) - 1));
     rows[p] = (uint32_t)(key >> bits);
     const uint32_t l = line[j];
-    data[p] = l < m ? (float)w64[l] : 0.0f;   // the winner's weight as parsed, rounded once to float32 (to_csr)
+    const double w = l < m ? w64[l] : 0.0;
+    data[p] = (float)w;            // the winner's weight as parsed, rounded once to float32 (to_csr)
+    if (data64) data64[p] = w;     // ... and as parsed (to_dense keeps the Python float): the dense build's values
 }
 
 __global__ void __launch_bounds__(256)

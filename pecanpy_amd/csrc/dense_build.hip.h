@@ -11,7 +11,8 @@
 //   (host)               indptr = prefix sum of the degrees, the 2^32 - 1 edge limit, max_degree
 //   dense_fill_kernel    entry (i, x) goes to indptr[i] + population of the row's earlier words + population of its own word
 //                        below its bit: ascending columns, a function of the input alone
-// and a CSR in device memory (pw_csr_dev) by csr_to_dense_kernel: bits set from the CSR rows, values widened to float64.
+// and a CSR in device memory (pw_csr_dev) by csr_to_dense_kernel: bits set from the CSR rows, values widened to float64 -- or,
+// for the CSR of an edge-list file read with its float64 weights kept, those weights as parsed.
 // Atomics produce flags (atomicOr of constant bits) and the bits of a SET (csr_to_dense_kernel) only: no position and no
 // value depends on the order they arrive in.  One workgroup of 256 threads per row, rows strided over the grid; one code
 // path for every n >= 1 and every row population from 0 to n.
@@ -125,9 +126,13 @@ dense_fill_kernel(const T *__restrict__ mat, uint32_t n, uint32_t wpr, const uin
 
 // ---- device CSR -> adjbits (zeroed by the caller), data64, deg, flags ----------------------------------------------------------
 // One wavefront per row, rows strided over the waves of the grid.  The bits are a set: atomicOr of single bits, the result
-// does not depend on arrival order.  data32 == NULL: every weight is 1.0 (nothing widened, no flag raised).
+// does not depend on arrival order.  W = float: the CSR's float32 weights, widened (exact); W = double: the float64 weights an
+// edge-list file's CSR carries beside them (coo_compact_lines_kernel), stored as they are -- the flags are reduced from the
+// float64 values either way, so 1.00000001 (1.0 in float32) is not unit.  src == NULL: every weight is 1.0 (nothing stored,
+// no flag raised).
+template <typename W>
 __global__ void __launch_bounds__(256)
-csr_to_dense_kernel(const uint32_t *__restrict__ indptr, const uint32_t *__restrict__ indices, const float *__restrict__ data32,
+csr_to_dense_kernel(const uint32_t *__restrict__ indptr, const uint32_t *__restrict__ indices, const W *__restrict__ src,
                     uint32_t n, uint32_t wpr, uint64_t *__restrict__ adjbits, double *__restrict__ data64, uint32_t *__restrict__ deg,
                     uint32_t *__restrict__ flags) {
     const int lane = lane_id();
@@ -140,8 +145,8 @@ csr_to_dense_kernel(const uint32_t *__restrict__ indptr, const uint32_t *__restr
         for (uint32_t e = lo + (uint32_t)lane; e < hi; e += WAVE) {
             const uint32_t col = indices[e];
             if (col < n) atomicOr(&bits[col >> 6], 1ull << (col & 63u));   // (a CSR of pw_coo_to_csr_device has no column >= n)
-            if (data32) {
-                const double v = (double)data32[e];
+            if (src) {
+                const double v = (double)src[e];
                 data64[e] = v;
                 bad |= dense_entry_flags(v);
             }

@@ -944,6 +944,7 @@ struct pw_csr_dev {
     double build_ms = 0;
     DevBuf<uint32_t> d_indptr, d_indices;
     DevBuf<float> d_data;      // empty: no weights were given (every weight 1.0)
+    DevBuf<double> d_data64;   // the edge-list reader with PW_EDGELIST_KEEP_F64: every entry's weight as parsed; empty otherwise
 };
 
 PW_EXPORT void pw_csr_dev_destroy(pw_csr_dev *c) {
@@ -955,9 +956,9 @@ PW_EXPORT void pw_csr_dev_destroy(pw_csr_dev *c) {
 // The build behind pw_coo_to_csr_device and pw_edgelist_read_device.  d_w64 (the edge-list reader; d_weight is NULL then):
 // the float64 weight of every edge as parsed, all > 0.  The sort then carries the edge's index instead of a weight; a pair
 // inserted again with another float64 weight sets *conflict and ends the call without a result (PW_OK, *out NULL: the
-// reference warns there), and the entries get the winner's weight rounded to float32.
+// reference warns there), and the entries get the winner's weight rounded to float32 -- and, with keep_f64, as parsed beside it.
 static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_dst, const float *d_weight, const double *d_w64, uint64_t m,
-                            uint64_t n_nodes, int directed, pw_csr_dev **out, int *conflict) {
+                            uint64_t n_nodes, int directed, pw_csr_dev **out, int *conflict, bool keep_f64 = false) {
     if (!out || (m && (!d_src || !d_dst))) return fail(PW_ERR_INVALID, "null pointer");
     const bool payload = d_weight || d_w64;   // four bytes travel with every key
     const int n_dev = pw_device_count();
@@ -1110,11 +1111,13 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     rc = alloc_out(c->d_indptr, n + 1, "indptr");
     if (!rc) rc = alloc_out(c->d_indices, nnz, "indices");
     if (!rc && payload) rc = alloc_out(c->d_data, nnz, "data");
+    if (!rc && d_w64 && keep_f64) rc = alloc_out(c->d_data64, nnz, "float64 data");
     if (rc) return rc;
     HIP_TRY(hipEventRecord(mem.ev[4], nullptr));
     if (n_ins && d_w64)
         hipLaunchKernelGGL(pw::coo_compact_lines_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0],
-                           (const uint32_t *)d_w[0], d_w64, n_ins, m, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p, d_rows);
+                           (const uint32_t *)d_w[0], d_w64, n_ins, m, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p,
+                           c->d_data64.p, d_rows);
     else if (n_ins)
         hipLaunchKernelGGL(pw::coo_compact_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0], (const float *)d_w[0],
                            n_ins, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p, d_rows);
@@ -1157,6 +1160,15 @@ PW_EXPORT int pw_csr_dev_export(const pw_csr_dev *c, uint32_t *indptr, uint32_t 
         if (c->d_data.p) HIP_TRY(hipMemcpy(data, c->d_data.p, sizeof(float) * c->nnz, hipMemcpyDeviceToHost));
         else std::fill(data, data + c->nnz, 1.0f);
     }
+    return PW_OK;
+}
+
+PW_EXPORT int pw_csr_dev_export_f64(const pw_csr_dev *c, double *data64) {
+    if (!c || !data64) return fail(PW_ERR_INVALID, "null pointer");
+    if (!c->d_data64.p)
+        return fail(PW_ERR_UNSUPPORTED, "pw_csr_dev_export_f64: the CSR holds no float64 weights (pw_edgelist_read_device_ex with PW_EDGELIST_KEEP_F64 keeps them)");
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->nnz) HIP_TRY(hipMemcpy(data64, c->d_data64.p, sizeof(double) * c->nnz, hipMemcpyDeviceToHost));
     return PW_OK;
 }
 
@@ -1208,14 +1220,15 @@ PW_EXPORT int pw_edgelist_ids_export(const pw_edgelist_ids *ids, uint64_t *id_of
     return PW_OK;
 }
 
-PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int directed, const char *delimiter, int device, pw_csr_dev **csr,
-                                      pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
+PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int directed, const char *delimiter, int device, uint32_t flags,
+                                         pw_csr_dev **csr, pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     if (!path || !csr || !ids) return fail(PW_ERR_INVALID, "null pointer");
     *csr = nullptr;
     *ids = nullptr;
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (flags & ~(uint32_t)PW_EDGELIST_KEEP_F64) return fail(PW_ERR_INVALID, "pw_edgelist_read_device_ex: unknown flag bits");
     const size_t dl = delimiter ? strlen(delimiter) : 0;
     if (dl == 0 || dl > pw::EL_MAX_DELIM) return PW_EDGELIST_NEEDS_HOST_READER;   // (str.split("") raises in Python)
     for (size_t i = 0; i < dl; i++)
@@ -1382,7 +1395,8 @@ PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int direct
     t0 = clk::now();
     pw_csr_dev *c = nullptr;
     int conflict = 0;
-    const int rc = coo_to_csr_build(device, d_src.p, d_dst.p, nullptr, weighted ? d_w64.p : nullptr, n_lines, n_nodes, directed, &c, &conflict);
+    const int rc = coo_to_csr_build(device, d_src.p, d_dst.p, nullptr, weighted ? d_w64.p : nullptr, n_lines, n_nodes, directed, &c, &conflict,
+                                    (flags & PW_EDGELIST_KEEP_F64) != 0);
     if (rc == PW_ERR_NOMEM) return PW_EDGELIST_NEEDS_HOST_READER;
     if (rc) return rc;
     if (conflict || !c) return PW_EDGELIST_NEEDS_HOST_READER;   // the reference warns about the overwritten weight
@@ -1394,6 +1408,11 @@ PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int direct
     *ids = mem.res;
     mem.res = nullptr;
     return PW_EDGELIST_OK;
+}
+
+PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int directed, const char *delimiter, int device, pw_csr_dev **csr,
+                                      pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
+    return pw_edgelist_read_device_ex(path, weighted, directed, delimiter, device, 0u, csr, ids, stats);
 }
 
 // Host builds of the reader's two text routines (csrc/edgelist_dev.hip.h), for tests without a GPU.
@@ -1672,7 +1691,8 @@ PW_EXPORT int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, doub
         HIP_TRY(gd.d_deg.alloc(n));
         HIP_TRY(gd.d_indptr.alloc(n + 1));
         HIP_TRY(gd.d_indices.alloc(nnz));
-        if (c->d_data.p) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
+        const bool weights = c->d_data64.p || c->d_data.p;
+        if (weights) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
         HIP_TRY(d_flags.alloc(1));
         HIP_TRY(hipEventRecord(g->ev[0], g->stream));
         HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
@@ -1680,8 +1700,14 @@ PW_EXPORT int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, doub
         HIP_TRY(hipMemcpyAsync(gd.d_indptr.p, c->d_indptr.p, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToDevice, g->stream));
         if (nnz) HIP_TRY(hipMemcpyAsync(gd.d_indices.p, c->d_indices.p, sizeof(uint32_t) * nnz, hipMemcpyDeviceToDevice, g->stream));
         const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, 1u << 20);
-        hipLaunchKernelGGL(pw::csr_to_dense_kernel, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p, (const uint32_t *)c->d_indices.p,
-                           (const float *)c->d_data.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p, gd.d_deg.p, d_flags.p);
+        if (c->d_data64.p)   // an edge-list file's float64 weights as parsed: stored as they are, the flags reduced from them
+            hipLaunchKernelGGL(pw::csr_to_dense_kernel<double>, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p,
+                               (const uint32_t *)c->d_indices.p, (const double *)c->d_data64.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p,
+                               gd.d_deg.p, d_flags.p);
+        else
+            hipLaunchKernelGGL(pw::csr_to_dense_kernel<float>, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p,
+                               (const uint32_t *)c->d_indices.p, (const float *)c->d_data.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p,
+                               gd.d_deg.p, d_flags.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(g->ev[1], g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));

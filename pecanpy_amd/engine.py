@@ -154,6 +154,19 @@ def _edge_list_to_device(lib, edge_index, edge_weight, device):
     return src, dst, w, dev, host_bytes
 
 
+def _edgelist_names(lib, ids, n):
+    """The vertex names of a ``pw_edgelist_ids`` in first-appearance order."""
+    dims = [C.c_uint64(0), C.c_uint64(0)]
+    _lib.check(lib.pw_edgelist_ids_shape(ids, C.byref(dims[0]), C.byref(dims[1])))
+    id_bytes = int(dims[1].value)
+    offs = np.empty(n + 1, dtype=np.uint64)
+    chars = np.empty(max(id_bytes, 1), dtype=np.uint8)
+    _lib.check(lib.pw_edgelist_ids_export(ids, _np_ptr(offs), _np_ptr(chars)))
+    blob = chars[:id_bytes].tobytes().decode("ascii")
+    cuts = offs.tolist()
+    return [blob[a:b] for a, b in zip(cuts, cuts[1:])]
+
+
 class WalkEngine:
     def __init__(self, handle, lib, kind, n_nodes, device):
         self._h = handle
@@ -303,15 +316,7 @@ class WalkEngine:
             indices = np.empty(nnz, dtype=np.uint32)
             data = np.empty(nnz, dtype=np.float32)
             _lib.check(lib.pw_csr_dev_export(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data)))
-            dims = [C.c_uint64(0), C.c_uint64(0)]
-            _lib.check(lib.pw_edgelist_ids_shape(ids, C.byref(dims[0]), C.byref(dims[1])))
-            id_bytes = int(dims[1].value)
-            offs = np.empty(n + 1, dtype=np.uint64)
-            chars = np.empty(max(id_bytes, 1), dtype=np.uint8)
-            _lib.check(lib.pw_edgelist_ids_export(ids, _np_ptr(offs), _np_ptr(chars)))
-            blob = chars[:id_bytes].tobytes().decode("ascii")
-            cuts = offs.tolist()
-            names = [blob[a:b] for a, b in zip(cuts, cuts[1:])]
+            names = _edgelist_names(lib, ids, n)
             t2 = time.perf_counter()
             h = C.c_void_p()
             _lib.check(lib.pw_csr_create_device(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), C.byref(h)))   # (no second download)
@@ -413,6 +418,58 @@ class WalkEngine:
         eng.build_stats = {"edge_list_host_bytes": int(host_bytes), "n_nodes": n, "nnz": nnz, "insertions": insertions,
                            "dropped": dropped, "build_ms": float(ms.value), "coo_call_ms": (t1 - t0) * 1e3, "export_ms": 0.0,
                            "handle_ms": (t2 - t1) * 1e3, "dense_build_ms": float(dense_ms.value)}
+        return eng
+
+    @classmethod
+    def dense_from_edgelist_file(cls, path, weighted, directed, delimiter="\t", device=None):
+        """Dense handle from an edge-list FILE, parsed and built on the device: ``pw_edgelist_read_device_ex`` with the
+        float64 weights kept (``PW_EDGELIST_KEEP_F64``), then ``pw_dense_create_from_csr``.  The handle is the one
+        ``from_dense`` makes of ``DenseGraph.read_edg``'s matrix: the weights are the float64 literals of the file, not their
+        float32 roundings.  The CSR is neither exported nor turned into a CSR handle, and no ``n * n`` host array exists.
+
+        Returns the engine, or ``None`` when the file needs the host reader, under the rules of ``from_edgelist_file``.
+        The engine carries ``eng.ids`` and ``eng.build_stats``: the reader's ``upload_ms``, ``scan_ms``, ``ids_ms``,
+        ``build_ms``, ``lines``, ``n_nodes``, ``file_bytes``, and ``nnz``, ``insertions``, ``csr_kernels_ms``,
+        ``dense_build_ms`` (device time of the dense build's kernels), ``read_call_ms``, ``handle_ms`` (names and the dense
+        handle), ``unit`` and ``matrix_host_bytes`` (0)."""
+        import os
+        import time
+
+        lib = _lib.load()
+        if int(lib.pw_device_count()) <= 0:
+            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+        try:
+            raw_delim = delimiter.encode("utf-8", "surrogateescape")
+        except (AttributeError, UnicodeError):
+            return None
+        if b"\0" in raw_delim:
+            return None
+        t0 = time.perf_counter()
+        c, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwEdgelistDevStats()
+        rc = lib.pw_edgelist_read_device_ex(os.fsencode(path), int(bool(weighted)), int(bool(directed)), raw_delim, int(device or 0),
+                                            _lib.EDGELIST_KEEP_F64, C.byref(c), C.byref(ids), C.byref(st))
+        if rc in (_lib.EDGELIST_NEEDS_HOST_READER, _lib.EDGELIST_IO):
+            return None
+        _lib.check(rc)
+        try:
+            t1 = time.perf_counter()
+            shape = [C.c_uint64(0) for _ in range(4)]
+            ms, dense_ms = C.c_double(0), C.c_double(0)
+            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
+            n, nnz, insertions, _ = (int(s.value) for s in shape)
+            names = _edgelist_names(lib, ids, n)
+            h = C.c_void_p()
+            _lib.check(lib.pw_dense_create_from_csr(c, C.byref(h), C.byref(dense_ms)))
+            t2 = time.perf_counter()
+        finally:
+            lib.pw_csr_dev_destroy(c)
+            lib.pw_edgelist_ids_destroy(ids)
+        eng = cls(h, lib, "dense", n, int(device or 0))
+        eng._max_degree, eng._nnz = eng._dense_shape()["max_degree"], nnz
+        eng.ids = names
+        eng.build_stats = {**st.as_dict(), "nnz": nnz, "insertions": insertions, "csr_kernels_ms": float(ms.value),
+                           "dense_build_ms": float(dense_ms.value), "read_call_ms": (t1 - t0) * 1e3, "handle_ms": (t2 - t1) * 1e3,
+                           "unit": eng._dense_flags()[0], "matrix_host_bytes": 0}
         return eng
 
     def _dense_shape(self):

@@ -716,6 +716,15 @@ class _DenseBase(Base, DenseGraph):
         self._materialize()
         return self._nonzero
 
+    @property
+    def num_edges(self):
+        """``nonzero.sum()`` (graph.py:524-528).  While the graph is built on the device and its host matrix has not been
+        read, the same count comes from the handle (``pw_dense_shape``) and no ``N * N`` array is made for it -- ``density``,
+        and thereby ``check_mode``, goes through here."""
+        if self._device_built is not None and self._data is None and self._engine is not None:
+            return np.int64(self._engine._dense_shape()["nnz"])
+        return DenseGraph.num_edges.fget(self)
+
     def _install_device_engine(self, eng, device, node_ids):
         try:
             if node_ids is not None and len(node_ids) != eng.n_nodes:
@@ -777,6 +786,42 @@ class _DenseBase(Base, DenseGraph):
 
             warnings.warn(f"{eng.build_stats['dropped']} non-positive edge(s) ignored", RuntimeWarning, stacklevel=2)
         return g
+
+    def read_edg_device(self, path, weighted, directed, delimiter="\t"):
+        """``read_edg`` with the file parsed and the dense handle built ON THE DEVICE
+        (``WalkEngine.dense_from_edgelist_file``): the text is uploaded, tokenised, numbered by first appearance and sorted
+        in device memory as for the sparse classes, the CSR keeps the float64 weights as parsed, and
+        ``pw_dense_create_from_csr`` makes the handle of the matrix ``read_edg`` would assign to ``data`` -- float64
+        literals, not their float32 roundings.  No ``N * N`` host array is made: ``nodes`` are set from the reader's names,
+        the handle is installed as the object's engine, ``data`` / ``nonzero`` are filled on first read as after
+        ``from_tensor``, ``num_edges`` / ``density`` come from the handle and ``get_noise_thresholds`` computes on the device.
+
+        The contract is the sparse method's: for every file the device reader declines, without a GPU and without the
+        library this method calls ``read_edg``, so warnings and exceptions are the reference's in every case.
+        ``last_build_stats["reader"]`` says which ran: ``"device"`` (with the keys of ``dense_from_edgelist_file``) or
+        ``"host"``."""
+        from . import _lib
+
+        try:   # without the library or a GPU there is nothing to read on: the host reader needs neither (the walks will say so)
+            have_device = int(_lib.load().pw_device_count()) > 0
+        except (_lib.PwError, OSError, AttributeError):
+            have_device = False
+        eng = None
+        if have_device:   # (a device error in the reader itself is raised, not papered over)
+            eng = WalkEngine.dense_from_edgelist_file(path, weighted, directed, delimiter, device=self._device_index())
+        if eng is None:
+            self.read_edg(path, weighted, directed, delimiter)
+            self.last_build_stats = {"reader": "host"}
+            return
+        if self._multi is not None:
+            for rep in self._multi.engines[1:]:
+                rep.close()
+            self._multi = None
+        if self._engine is not None:
+            self._engine.close()
+        self._install_device_engine(eng, self._device_index(), eng.ids)
+        self._thr_key = None
+        self.last_build_stats = {"reader": "device", **eng.build_stats}
 
     def get_has_nbrs(self):
         nonzero = self.nonzero
