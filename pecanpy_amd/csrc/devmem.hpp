@@ -1,4 +1,4 @@
-// devmem.hpp -- the one owner of a device (or pinned host) allocation.  Host code only.
+// devmem.hpp -- the one owner of a device (or pinned host) allocation, of a stream, of an event.  Host code only.
 //
 // A Buf frees what it holds when it goes out of scope, moves but never copies, and hands kernels and argument structs the
 // plain pointer `.p`.  Allocation reports the runtime's hipError_t and leaves no sticky error behind: the caller decides
@@ -62,5 +62,45 @@ template <typename T> using PinnedBuf = Buf<T, PinnedMem>;
 static_assert(!std::is_copy_constructible<DevBuf<float>>::value && !std::is_copy_assignable<DevBuf<float>>::value, "a Buf has one owner");
 static_assert(std::is_nothrow_move_constructible<DevBuf<float>>::value && std::is_nothrow_move_assignable<DevBuf<float>>::value, "a Buf moves");
 static_assert(!std::is_copy_constructible<PinnedBuf<void>>::value && std::is_nothrow_move_constructible<PinnedBuf<void>>::value, "pinned too");
+
+// The one owner of a stream or an event: destroyed with it, moves but never copies, and converts to the plain handle wherever
+// the runtime or a launch takes one.  create() reports the runtime's hipError_t like Buf::alloc.
+struct StreamHandle {
+    typedef hipStream_t type;
+    static hipError_t make(type *h, unsigned flags) { return hipStreamCreateWithFlags(h, flags); }
+    static void destroy(type h) { (void)hipStreamDestroy(h); }
+};
+struct EventHandle {
+    typedef hipEvent_t type;
+    static hipError_t make(type *h, unsigned flags) { return hipEventCreateWithFlags(h, flags); }
+    static void destroy(type h) { (void)hipEventDestroy(h); }
+};
+
+template <typename H> struct Owned {
+    typename H::type h = nullptr;
+
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) { release(); h = o.h; o.h = nullptr; }
+        return *this;
+    }
+    ~Owned() { release(); }
+
+    operator typename H::type() const { return h; }
+    hipError_t create(unsigned flags) { release(); return H::make(&h, flags); }
+    void release() {
+        if (h) H::destroy(h);
+        h = nullptr;
+    }
+};
+
+using Stream = Owned<StreamHandle>;   // (the handles of this library: hipStreamNonBlocking)
+using Event = Owned<EventHandle>;     // (hipEventDefault: timed; hipEventDisableTiming: ordering only)
+
+static_assert(!std::is_copy_constructible<Stream>::value && std::is_nothrow_move_constructible<Stream>::value, "a stream has one owner");
+static_assert(!std::is_copy_constructible<Event>::value && std::is_nothrow_move_constructible<Event>::value, "an event has one owner");
 
 }  // namespace pw

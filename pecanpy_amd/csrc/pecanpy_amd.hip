@@ -205,7 +205,14 @@ struct GraphData : GraphDesc {
     ~GraphData() { (void)hipSetDevice(device); }   // (the members free themselves behind this body: on their own device)
 };
 
-// A call context over a graph: streams, events, counters, random stream and scratch buffers, and the flags of the
+// blocks of 312 draws from `first_block` on that cover the draws up to stream_skip + total (at least one): the one rounding
+// of expand_stream's range and of the range a hold keeps
+static uint64_t stream_blocks_from(uint64_t first_block, uint64_t stream_skip, uint64_t total) {
+    const uint64_t end_block = (stream_skip + total + 311) / 312;
+    return end_block > first_block ? end_block - first_block : 1;
+}
+
+// A call context over a graph: streams, events, counters, random stream and scratch buffers, and the state of the
 // current call.  The graph itself (gd) may be shared with a twin context.
 struct pw_graph {
     int device = 0;
@@ -214,35 +221,43 @@ struct pw_graph {
     // buffers): the weighted lane form walks the two halves of a job array on the two contexts side by side, so that one half's
     // eager kernel runs beside the other half's lane round (simulate_twin)
     pw_graph *twin = nullptr;
+    // INPUTS of a call, set around it by simulate_twin: not part of `call`, the driver's reset leaves them alone
     bool twin_active = false;                           // the current call runs on both contexts: each takes a share of the GPU
     std::function<void()> on_tables_ready;              // simulate_twin: called once the call's per-(p, q) tables are in place
-    bool wl_active = false;                             // the current call may run the weighted lane form (tables are there)
-    bool call_n2vpp = false;                            // the current call walks node2vec++ (walk_dense_w.hip.h)
-    bool call_spp = false;                              // ... node2vec++ on this CSR handle (walk_sparse_pp.hip.h)
-    bool wl_used = false;                               // ... and did
-    double param_ms_call = 0;                           // (p, q)-dependent index time of the current call
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // side stream: the zero-fill of the walk matrix runs under the stream expansion
-    hipEvent_t ev_side = nullptr;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> round_ev;          // lane rounds: a pair of events per round, read once behind the last round (no sync per round)
+    // What one call of the driver (simulate_device_impl) keeps for its launchers and its statistics: reset by ONE assignment
+    // there, behind the validation, and read and written through this name only.
+    struct Call {
+        bool n2vpp = false;                             // the current call walks node2vec++ (walk_dense_w.hip.h)
+        bool spp = false;                               // ... node2vec++ on this CSR handle (walk_sparse_pp.hip.h)
+        bool wl_active = false;                         // the current call may run the weighted lane form (tables are there)
+        bool wl_used = false;                           // ... and did
+        double param_ms = 0;                            // (p, q)-dependent index time of the current call
+        double lane_ms = 0;                             // lane kernel time of the current call
+        uint32_t lane_rounds = 0;                       // lane kernel launches of the current call
+        uint64_t runnable = 0;                          // whole-array call: jobs whose start has neighbours (the stream's nominal draws / walk_length)
+        uint64_t ver_checked = 0, ver_mismatch = 0, ver_dropped = 0, ver_ties = 0;   // verification counts of the current call
+    } call;
     // pw_simulate() walks a large job array in parts: the stream of the WHOLE array is expanded once, and while this is
     // set expand_stream() serves the parts' sub-ranges from g->rng as it stands (never kept across API calls)
     struct { bool valid = false, user = false; uint32_t seed = 0; uint64_t first_block = 0, n_blocks = 0; } rng_hold;   // (user: pw_stream_hold)
-    hipStream_t copy_stream = nullptr;     // pw_simulate: the D2H of one part of the walk matrix runs here, under the walks of the next
+    void drop_hold() { rng_hold.valid = false; rng_hold.user = false; }
+    // g->rng holds the draws [stream_skip, stream_skip + n_draws) of `seed`, expanded from draw `base` (expand_stream's *rng_base) on
+    void set_hold(uint32_t seed, uint64_t base, uint64_t stream_skip, uint64_t n_draws, bool user) {
+        rng_hold.valid = true;
+        rng_hold.user = user;
+        rng_hold.seed = seed;
+        rng_hold.first_block = base / 312;
+        rng_hold.n_blocks = stream_blocks_from(base / 312, stream_skip, n_draws);
+    }
     static constexpr int N_STAGE = 12;
-    hipEvent_t ev_copy[N_STAGE] = {};
     PinnedBuf<void> stage[N_STAGE];        // pinned staging buffers of pw_simulate's copy out
     PinnedBuf<uint32_t> seed_state;        // pinned: the seed's MT19937 state on its way to the device
-    double lane_ms = 0;              // lane kernel time of the current call
     int n_cu = 0;
     // scratch reused across calls
     DevBuf<uint64_t> stream_off, tile_sums;
     DevBuf<double> rng;
     DevBuf<uint32_t> mt_state, changed, redo;
     DevBuf<pw::SuspRec> susp[2];      // lane kernel: walks parked for the float chain (two queues, swapped per round)
-    uint32_t lane_rounds = 0;         // lane kernel launches of the last call
-    uint64_t call_runnable = 0;       // whole-array call: jobs whose start has neighbours (the stream's nominal draws / walk_length)
     // generator states of recent calls, keyed by (seed, first block, blocks per generator, generators): a repeated
     // call (every pass of a benchmark, every chunk of a sharded run) skips the ~20 sequential jump-ahead launches
     struct MtCache { bool valid = false; uint32_t seed = 0, n_gen = 0; uint64_t first_block = 0; int per_gen_log = 0; uint64_t stamp = 0;
@@ -251,12 +266,23 @@ struct pw_graph {
     // verification mode of the lane kernel (PECANPY_AMD_VERIFY_TIGHT=1): steps the interval decision settled
     DevBuf<pw::VerRec> ver, ver_bad;
     DevBuf<uint32_t> ver_jobs;        // sampled verification (production): walks of mismatching records, redone by walk_kernel
-    uint64_t ver_checked = 0, ver_mismatch = 0, ver_dropped = 0, ver_ties = 0;   // ... of the current call
     DevBuf<uint64_t> jump_table;  // MtJump::pow2_table() on the device
     DevBuf<uint32_t> jump_tmp;    // partial results of jumps whose taps are split over several workgroups (kept zeroed)
     bool jump_table_ready = false;
     DevBuf<unsigned long long> counters;  // N_COUNTERS device counters: counters.h names the slots
     DevBuf<float> probs_scratch;
+    // Streams and events LAST: members go in reverse order behind the destructor's body, so the events are destroyed first, then
+    // the streams, then the buffers above -- on this context's device (graph_common_init creates them; one that fails half way
+    // leaves what it made to this destructor)
+    pw::Stream stream;
+    pw::Stream stream2;              // side stream: the zero-fill of the walk matrix runs under the stream expansion
+    pw::Stream copy_stream;          // pw_simulate: the D2H of one part of the walk matrix runs here, under the walks of the next
+    pw::Event ev_copy[N_STAGE];
+    pw::Event ev_side;
+    std::vector<pw::Event> round_ev;       // lane rounds: a pair of events per round, read once behind the last round (no sync per round)
+    pw::Event ev[8];
+
+    ~pw_graph() { (void)hipSetDevice(device); }   // (the members release themselves behind this body: on their own device)
 };
 
 namespace {
@@ -339,18 +365,7 @@ PW_EXPORT int pw_warmup(int device, double *ms) {
 PW_EXPORT void pw_graph_destroy(pw_graph *g) {
     if (!g) return;
     if (g->twin) { pw_graph_destroy(g->twin); g->twin = nullptr; }
-    (void)hipSetDevice(g->device);
-    for (auto &e : g->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : g->round_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (g->ev_side) (void)hipEventDestroy(g->ev_side);
-    for (auto &e : g->ev_copy)
-        if (e) (void)hipEventDestroy(e);
-    if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
-    if (g->stream2) (void)hipStreamDestroy(g->stream2);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;        // (its buffers with it, and the graph with the last context that walks it)
+    delete g;        // (its events, streams and buffers with it, and the graph with the last context that walks it)
 }
 
 // a call context on `device` over `gd` (a twin's: the primary's graph) or over a new, empty graph
@@ -369,15 +384,15 @@ static int graph_common_init(pw_graph *g, int device, std::shared_ptr<GraphData>
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     g->n_cu = prop.multiProcessorCount;
     lap("device count / properties");
-    HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    HIP_TRY(g->stream.create(hipStreamNonBlocking));
     lap("stream");
-    HIP_TRY(hipStreamCreateWithFlags(&g->stream2, hipStreamNonBlocking));
+    HIP_TRY(g->stream2.create(hipStreamNonBlocking));
     lap("stream2");
-    HIP_TRY(hipEventCreateWithFlags(&g->ev_side, hipEventDisableTiming));
-    for (auto &e : g->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(g->ev_side.create(hipEventDisableTiming));
+    for (auto &e : g->ev) HIP_TRY(e.create(hipEventDefault));
     lap("events");
-    HIP_TRY(hipStreamCreateWithFlags(&g->copy_stream, hipStreamNonBlocking));
-    for (auto &e : g->ev_copy) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(g->copy_stream.create(hipStreamNonBlocking));
+    for (auto &e : g->ev_copy) HIP_TRY(e.create(hipEventDisableTiming));
     lap("copy stream + events");
     return 0;
 }
@@ -2198,7 +2213,7 @@ static int ensure_tot_table(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &s
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
         g->gd->tot_build_ms = ms;
-        g->param_ms_call += ms;
+        g->call.param_ms += ms;
         g->gd->tot_extend = extend ? 1 : 0;
         g->gd->tot_p = wa.p;
         g->gd->tot_q = wa.q;
@@ -2286,7 +2301,7 @@ static int ensure_wlane_tables(pw_graph *g, const pw::WalkArgs &wa, const LaneSw
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("weighted lane tables: ") + hipGetErrorString(e));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
-    g->param_ms_call += ms;
+    g->call.param_ms += ms;
     g->gd->wl_extend = extend ? 1 : 0;
     g->gd->wl_p = wa.p;
     g->gd->wl_q = wa.q;
@@ -2481,7 +2496,7 @@ static int launch_wave_walks(pw_graph *g, pw::WalkArgs &wa, bool extend, uint64_
     // unweighted dense graphs: the column-space kernels at every size (round 6: with prev's row in LDS and DPP sums the packed rows
     // beat the compressed ones from N = 1 000 on -- ER-1k 364 -> 682, ER-8k 207 -> 1 135, ER-12k 158 -> 1 145 M steps/s; rounds 2-5
     // sent matrices of up to 12 000 rows through their compressed rows; PECANPY_AMD_DENSE_SMALL_ROWS=1: that rule)
-    if (g->call_n2vpp) return launch_dense_weighted(g, wa, g->gd->unit ? pw::DW_N2VPP_UNIT : pw::DW_N2VPP, redo_total);
+    if (g->call.n2vpp) return launch_dense_weighted(g, wa, g->gd->unit ? pw::DW_N2VPP_UNIT : pw::DW_N2VPP, redo_total);
     const bool small_rows = env_on("PECANPY_AMD_DENSE_SMALL_ROWS");
     if (g->gd->kind == 1 && g->gd->unit && g->gd->d_deg.p && (g->gd->bits_only || g->gd->n_nodes > 12000 || !small_rows)) return launch_dense_bits(g, wa, redo_total);
     if (dense_weighted_eligible(g, wa, extend)) return launch_dense_weighted(g, wa, extend ? pw::DW_N2VPLUS : pw::DW_N2V, redo_total);
@@ -2583,7 +2598,7 @@ static int plan_verification(pw_graph *g, const LaneSwitches &sw, bool applies, 
 static int verify_records(pw_graph *g, const pw::WalkArgs &wa, uint64_t ver_cap, unsigned long long n_rec, int slot, bool list_jobs, bool floats,
                           hipEvent_t ev_launched, hipEvent_t ev_closing, unsigned long long vc[pw::N_VER_COUNTS]) {
     const unsigned long long n_chk = n_rec < ver_cap ? n_rec : ver_cap;
-    g->ver_dropped += n_rec - n_chk;
+    g->call.ver_dropped += n_rec - n_chk;
     unsigned long long *counts = g->counters.p + slot;
     if (n_chk) {
         // (the lane kernel's record counter shares CTR_VER with the counts of the per-round check)
@@ -2599,9 +2614,9 @@ static int verify_records(pw_graph *g, const pw::WalkArgs &wa, uint64_t ver_cap,
     }
     if (ev_closing) HIP_TRY(hipEventRecord(ev_closing, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    g->ver_checked += vc[pw::VER_CHECKED];
-    g->ver_mismatch += vc[pw::VER_MISMATCH];
-    g->ver_ties += vc[pw::VER_TIES];
+    g->call.ver_checked += vc[pw::VER_CHECKED];
+    g->call.ver_mismatch += vc[pw::VER_MISMATCH];
+    g->call.ver_ties += vc[pw::VER_TIES];
     return 0;
 }
 
@@ -2717,10 +2732,10 @@ static int plan_lane_call(pw_graph *g, const pw::WalkArgs &wa, const LaneSwitche
     if (chains_form) use_queue = true;      // (a step that finds the pool full is still parked: the round loop takes care of it)
     // Queue capacities (round 6: from what CAN be parked, not from the job array -- device memory a fresh box has not handed out
     // before costs ~23 ms per GB, and two queues of n_jobs records were 5.4 GB at RMAT-22): only walks whose start has neighbours
-    // are ever parked (g->call_runnable of them in a whole-array call: the stream's draws / walk_length), and the second queue
+    // are ever parked (g->call.runnable of them in a whole-array call: the stream's draws / walk_length), and the second queue
     // only ever holds walks that were in the first -- it is allocated after round 0, for the walks that round parked.
     // + the void slots of every wavefront's LAST reservation (< 128 each; leftovers of earlier ones are used up)
-    const uint64_t can_park = (!wa.job_list && g->call_runnable && g->call_runnable < n_work) ? g->call_runnable : n_work;
+    const uint64_t can_park = (!wa.job_list && g->call.runnable && g->call.runnable < n_work) ? g->call.runnable : n_work;
     const size_t q_cap = (size_t)can_park + 2 * (size_t)lanes_resident;
     if (use_queue && g->susp[0].ensure(q_cap) != hipSuccess) {
         use_queue = false;              // no room for the queues: chains run in place
@@ -2766,7 +2781,7 @@ static int finish_lane_rounds(pw_graph *g, const pw::WalkArgs &wa, const LaneSwi
     for (int r = 0; r < n_rounds; r++) {
         float rms = 0;
         HIP_TRY(hipEventElapsedTime(&rms, g->round_ev[2 * (size_t)r], g->round_ev[2 * (size_t)r + 1]));
-        g->lane_ms += rms;
+        g->call.lane_ms += rms;
     }
     if (vp.sample && n_rec_s) {   // the sample of ALL rounds (the records accumulate across them): re-decided by the chain, one launch
         HIP_TRY(hipEventRecord(g->ev[4], g->stream));
@@ -2774,7 +2789,7 @@ static int finish_lane_rounds(pw_graph *g, const pw::WalkArgs &wa, const LaneSwi
         if (rc) return rc;
         float vms = 0;
         HIP_TRY(hipEventElapsedTime(&vms, g->ev[4], g->ev[5]));
-        g->lane_ms += vms;              // (part of the lane path's time: the roofline's kernel time includes it)
+        g->call.lane_ms += vms;              // (part of the lane path's time: the roofline's kernel time includes it)
     }
     if (vp.full) g->ver.release();   // (test mode: up to half of the free memory -- not kept in the handle)
     if (vs[pw::VER_MISMATCH]) {
@@ -2864,9 +2879,9 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &
         HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_JOB, 0, sizeof(unsigned long long), g->stream));
         HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_PARKED, 0, sizeof(unsigned long long), g->stream));
         while (g->round_ev.size() < 2 * (size_t)round + 2) {   // (this round's pair: read behind the last round)
-            hipEvent_t ne = nullptr;
-            HIP_TRY(hipEventCreate(&ne));
-            g->round_ev.push_back(ne);
+            pw::Event ne;
+            HIP_TRY(ne.create(hipEventDefault));
+            g->round_ev.push_back(std::move(ne));
         }
         HIP_TRY(hipEventRecord(g->round_ev[2 * (size_t)round], g->stream));
         if (vp.full || (vp.sample && round == 0)) HIP_TRY(hipMemsetAsync(g->counters.p + pw::CTR_VER, 0, pw::N_VER_COUNTS * sizeof(unsigned long long), g->stream));
@@ -2877,7 +2892,7 @@ static int launch_lane_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &
         HIP_TRY(hipStreamSynchronize(g->stream));
         if (parked) { rc = settle_lane_queue(g, wa, weighted, extend, g->susp[round & 1].p, parked); if (rc) return rc; }
         HIP_TRY(hipEventRecord(g->round_ev[2 * (size_t)round + 1], g->stream));
-        g->lane_rounds++;
+        g->call.lane_rounds++;
         n_rounds = round + 1;
         if (sw.debug_rounds) {
             HIP_TRY(hipStreamSynchronize(g->stream));
@@ -2920,7 +2935,7 @@ static int ensure_unit_tot(pw_graph *g, const pw::WalkArgs &wa, const LaneSwitch
     HIP_TRY(hipStreamSynchronize(g->stream));
     float tms = 0;
     HIP_TRY(hipEventElapsedTime(&tms, g->ev[4], g->ev[5]));
-    g->param_ms_call += tms;
+    g->call.param_ms += tms;
     g->gd->utot_wo = wa.w_out;
     g->gd->utot_wp = wa.w_prev;
     return 0;
@@ -2959,8 +2974,8 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwit
     if (rc) return rc;
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, g->ev[4], g->ev[5]));
-    g->lane_ms += ms;
-    g->lane_rounds++;
+    g->call.lane_ms += ms;
+    g->call.lane_rounds++;
     if (vp.full) g->ver.release();
     if (vs[pw::VER_MISMATCH]) {
         rc = report_verify_mismatches(g, vs[pw::VER_BAD], true, vp.full || sw.debug_rounds);
@@ -2972,11 +2987,11 @@ static int launch_lane_float_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwit
 }
 
 static int launch_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &sw, bool extend, uint64_t *redo_total) {
-    if (g->call_spp) return launch_sparse_pp(g, wa);   // (node2vec++ on CSR: never the lane kernels)
+    if (g->call.spp) return launch_sparse_pp(g, wa);   // (node2vec++ on CSR: never the lane kernels)
     const bool floats = lanes_float_eligible(g, wa, sw);
     // weighted lane form: whole job arrays only (repair passes of a directed graph run on job lists: the wave kernel)
-    const bool wlanes = g->wl_active && !wa.job_list && wlanes_worth(sw, wa.n_jobs);
-    if (wlanes) g->wl_used = true;
+    const bool wlanes = g->call.wl_active && !wa.job_list && wlanes_worth(sw, wa.n_jobs);
+    if (wlanes) g->call.wl_used = true;
     if (!floats && !wlanes && !lanes_eligible(g, wa, sw)) return launch_wave_walks(g, wa, extend, redo_total);
     uint64_t n_redo = 0;
     int rc = wlanes ? launch_lane_walks(g, wa, sw, &n_redo, true, extend)
@@ -3006,8 +3021,7 @@ static int launch_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &sw, b
 // kernels on g->stream.
 static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t stream_skip, uint64_t total, uint64_t *rng_base) {
     const uint64_t first_block = stream_skip / 312;
-    const uint64_t end_block = (stream_skip + total + 311) / 312;
-    const uint64_t n_blocks = end_block > first_block ? end_block - first_block : 1;
+    const uint64_t n_blocks = stream_blocks_from(first_block, stream_skip, total);   // (pw_graph::set_hold: the same rounding)
     if (g->rng_hold.valid && g->rng_hold.seed == seed && first_block >= g->rng_hold.first_block &&
         first_block + n_blocks <= g->rng_hold.first_block + g->rng_hold.n_blocks) {
         HIP_TRY(hipEventRecord(g->ev[0], g->stream));   // (nothing to do: the callers still read the pair of events)
@@ -3015,8 +3029,7 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
         *rng_base = g->rng_hold.first_block * 312;
         return 0;
     }
-    g->rng_hold.valid = false;      // (g->rng is about to be overwritten: whatever was held is gone)
-    g->rng_hold.user = false;
+    g->drop_hold();                 // (g->rng is about to be overwritten: whatever was held is gone)
     if (grow(g->rng, n_blocks * 312)) return PW_ERR_NOMEM;
     uint64_t per_gen = 1;
     int per_gen_log = 0;
@@ -3109,24 +3122,18 @@ PW_EXPORT int pw_stream_hold(pw_graph *g, uint32_t seed, uint64_t stream_skip, u
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
     if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
-    g->rng_hold.valid = false;
-    g->rng_hold.user = false;
+    g->drop_hold();
     if (!n_draws) return PW_OK;
     uint64_t base = 0;
     int rc = expand_stream(g, seed, true, stream_skip, n_draws, &base);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(g->stream));
-    g->rng_hold.valid = true;
-    g->rng_hold.user = true;
-    g->rng_hold.seed = seed;
-    g->rng_hold.first_block = base / 312;
-    g->rng_hold.n_blocks = (stream_skip + n_draws + 311) / 312 > base / 312 ? (stream_skip + n_draws + 311) / 312 - base / 312 : 1;
+    g->set_hold(seed, base, stream_skip, n_draws, true);
     return PW_OK;
 }
 PW_EXPORT int pw_stream_release(pw_graph *g) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
-    g->rng_hold.valid = false;
-    g->rng_hold.user = false;
+    g->drop_hold();
     return PW_OK;
 }
 
@@ -3144,32 +3151,286 @@ PW_EXPORT int pw_stream_sample_device(pw_graph *g, uint32_t seed, uint64_t offse
     return PW_OK;
 }
 
-static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, double p, double q, int extend,
-                                const uint32_t *d_starts, uint64_t n_jobs, uint32_t walk_length,
-                                int has_seed, uint32_t seed, uint64_t stream_skip, uint32_t *d_out,
-                                pw_stats *stats) {
+// One call of the driver as its phases pass it on: the arguments as validated, the kernel arguments of its passes and what
+// the passes add up.
+struct WalkCall {
+    const LaneSwitches &sw;
+    const int mode;
+    const bool extend;
+    const uint32_t *const d_starts;
+    const uint64_t n_jobs;
+    const uint32_t walk_length;
+    const uint64_t stream_skip;
+    uint32_t *const d_out;
+    pw::WalkArgs wa;
+    pw_stats st;
+    uint64_t redo_total;
+    bool lanes;                       // a lane form serves the call: settled before the first pass, reported by fill_stats
+};
+
+// the arguments of a call against the handle; *extend: cleared for the modes that ignore it
+static int validate_call(pw_graph *g, int mode, double p, double q, int *extend, const uint32_t *d_starts, uint64_t n_jobs, uint32_t walk_length,
+                         const uint32_t *d_out) {
     if (!g || (n_jobs && (!d_starts || !d_out))) return fail(PW_ERR_INVALID, "null pointer");
     if (!mode_on_the_fly(mode) && !mode_sequential_stream(mode)) return fail(PW_ERR_INVALID, "unknown mode");
     if (mode == PW_MODE_SPARSE_OTF && g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "SparseOTF needs a CSR graph handle");
     if (mode == PW_MODE_DENSE_OTF && g->gd->kind != 1) return fail(PW_ERR_UNSUPPORTED, "DenseOTF needs a dense graph handle");
-    const bool n2vpp = mode == PW_MODE_NODE2VEC_PLUSPLUS;
-    if (n2vpp) { int rcn = n2vpp_check(g); if (rcn) return rcn; extend = 0; }   // (node2vec++ ignores extend)
-    const bool spp = mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
-    if (spp) { int rcn = spp_check(g); if (rcn) return rcn; extend = 0; }
-    if (extend && !g->gd->unit && !g->gd->d_thr.p)
+    if (mode == PW_MODE_NODE2VEC_PLUSPLUS) { int rcn = n2vpp_check(g); if (rcn) return rcn; *extend = 0; }   // (node2vec++ ignores extend)
+    if (mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS) { int rcn = spp_check(g); if (rcn) return rcn; *extend = 0; }
+    if (*extend && !g->gd->unit && !g->gd->d_thr.p)
         return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (!(p > 0) || !(q > 0)) return fail(PW_ERR_INVALID, "p and q must be positive");
     if (walk_length < 1) return fail(PW_ERR_INVALID, "walk_length must be >= 1");
     if (n_jobs >= 0xffffffffull) return fail(PW_ERR_INVALID, "n_jobs must fit uint32");
-    if (set_device(g)) return PW_ERR_HIP;
-    pw_stats st;
+    return set_device(g);
+}
+
+// the kernel arguments of the call's passes: the whole job array, its draws at g->rng from rng_base on
+static int make_walk_args(pw_graph *g, WalkCall &c, double p, double q, uint64_t rng_base) {
+    pw::WalkArgs &wa = c.wa;
+    wa.g = csr_dev(g);
+    wa.p = p;
+    wa.q = q;
+    wa.L = c.walk_length;
+    wa.n_jobs = c.n_jobs;
+    wa.starts = c.d_starts;
+    wa.stream_off = g->stream_off.p;
+    wa.job_list = nullptr;
+    wa.n_list = 0;
+    // (the lane kernel loads the draws as aligned 16-byte pairs: the block must start on such a boundary and hold an even number
+    //  of doubles -- whole blocks of 312 from an allocation's base do)
+    if (((uintptr_t)g->rng.p & 15u) != 0 || (g->rng.cap & 1u) != 0)
+        return fail(PW_ERR_INVALID, "stream buffer is not made of aligned pairs of draws");
+    wa.rng = g->rng.p;
+    wa.rng_base = rng_base;
+    wa.out = c.d_out;
+    wa.job_counter = g->counters.p + pw::CTR_JOB;
+    wa.stats = g->counters.p + pw::CTR_STATS;
+    wa.tot_e = nullptr;
+    wa.tot_v = nullptr;
+    wa.resume = 0;
+    {
+        // unit-weight biases exactly as the kernels form them: fl32(f64(1.0f) / q) (sparse_rw.py:59-62)
+        wa.w_out = (float)(1.0 / q);
+        wa.w_prev = (float)(1.0 / p);
+        auto pow2_ok = [](float w) {
+            int e = 0;
+            return std::frexp(w, &e) == 0.5f && e > -60 && e < 60;
+        };
+        wa.lazy_ok = (pow2_ok(wa.w_out) && pow2_ok(wa.w_prev)) ? 1u : 0u;
+    }
+    return 0;
+}
+
+// the per-(p, q) tables of the call, built (and their time added to g->call.param_ms) where they are not in place yet
+static int prepare_tables(pw_graph *g, WalkCall &c) {
+    const bool spp = c.mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
+    int rc = 0;
+    if (!spp) rc = ensure_tot_table(g, c.wa, c.sw, c.extend);   // (before the timed walk region: a per-(p, q) index, reported apart)
+    if (rc) return rc;
+    if (c.mode == PW_MODE_SPARSE_OTF && lanes_float_eligible(g, c.wa, c.sw)) { rc = ensure_unit_tot(g, c.wa, c.sw); if (rc) return rc; }
+    if (c.mode == PW_MODE_SPARSE_OTF && wlanes_worth(c.sw, c.n_jobs)) {
+        rc = ensure_wlane_tables(g, c.wa, c.sw, c.extend, &g->call.wl_active);   // (likewise; the weighted lane form needs both)
+        if (rc) return rc;
+        if (g->call.wl_active) {   // the lane kernel only writes the cells a walk fills (unit graphs: zero-filled on the side stream above)
+            HIP_TRY(hipMemsetAsync(c.d_out, 0, sizeof(uint32_t) * (size_t)c.n_jobs * ((size_t)c.walk_length + 2), g->stream));
+        }
+    }
+    if (g->on_tables_ready) { auto cb = g->on_tables_ready; g->on_tables_ready = nullptr; cb(); }
+    return 0;
+}
+
+// the first pass over the whole job array between ev[2] and ev[3]; h: the device counters behind it
+static int first_pass(pw_graph *g, WalkCall &c, bool lanes_pre, unsigned long long h[N_COUNTERS]) {
+    c.lanes = c.mode != PW_MODE_SPARSE_NODE2VEC_PLUSPLUS && (lanes_eligible(g, c.wa, c.sw) || lanes_float_eligible(g, c.wa, c.sw));
+    HIP_TRY(hipEventRecord(g->ev[2], g->stream));
+    // the lane kernel only writes the cells a walk fills: the matrix starts zeroed (pecanpy.py:182-187) -- by the side
+    // stream, under the stream expansion above
+    if (lanes_pre) HIP_TRY(hipStreamWaitEvent(g->stream, g->ev_side, 0));
+    int rc = launch_walks(g, c.wa, c.sw, c.extend, &c.redo_total);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(g->ev[3], g->stream));
+    HIP_TRY(hipMemcpyAsync(h, g->counters.p, N_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return 0;
+}
+
+#ifdef PW_PROF
+// instrumented build: where the wave-per-walk kernel's cycles went, per step of the first pass
+static int dump_walk_prof(const unsigned long long h[N_COUNTERS]) {
+    {
+        unsigned long long hp[16], zero[16] = {0};
+        HIP_TRY(hipMemcpyFromSymbol(hp, HIP_SYMBOL(pw::g_prof), sizeof(hp)));
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(pw::g_prof), zero, sizeof(zero)));
+        static const char *names[16] = {"step pro/epilogue", "lazy setup", "membership chunks", "build_rank", "seq_head",
+                                        "unit_chain", "eager fallback", "exact search", "#chunks", "#searches", "#eager steps",
+                                        "#ambiguous", "#chain tie fallbacks", "#search rounds", "-", "-"};
+        double tot = 0;
+        for (int i = 0; i < 8; i++) tot += (double)hp[i];
+        fprintf(stderr, "[pw_prof] steps=%llu\n", h[pw::CTR_STEPS]);
+        for (int i = 0; i < 8; i++)
+            fprintf(stderr, "[pw_prof] %-20s %6.2f%%  %.1f cycles/step\n", names[i], 100.0 * hp[i] / tot, (double)hp[i] / (double)h[pw::CTR_STEPS]);
+        for (int i = 8; i < 16; i++) fprintf(stderr, "[pw_prof] %-20s %.3f /step\n", names[i], (double)hp[i] / (double)h[pw::CTR_STEPS]);
+    }
+    return 0;
+}
+#endif
+
+// the jobs compute_offsets re-addressed (g->changed), walked again and their kernel time accounted; `off_first` (block-wise
+// repair): the offset of job `fm` is read back behind the walks, before the wait
+static int rewalk_changed(pw_graph *g, WalkCall &c, uint64_t n_changed, uint64_t *off_first = nullptr, uint64_t fm = 0) {
+    c.st.repair_rounds++;
+    c.wa.job_list = g->changed.p;
+    c.wa.n_list = n_changed;
+    HIP_TRY(hipEventRecord(g->ev[2], g->stream));
+    int rcw = launch_walks(g, c.wa, c.sw, c.extend, &c.redo_total);
+    if (rcw) return rcw;
+    HIP_TRY(hipEventRecord(g->ev[3], g->stream));
+    if (off_first) HIP_TRY(hipMemcpyAsync(off_first, g->stream_off.p + fm, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, g->ev[2], g->ev[3]));
+    c.st.walk_kernel_ms += ms;
+    c.st.walk_kernel_launches++;
+    return 0;
+}
+
+// (a) whole-array rounds, at most max_rounds of them.  *first: smallest job whose offset changed in the last round
+// (re-walked since: final); *consistent: a round re-addressed nothing.
+static int repair_whole_array(pw_graph *g, WalkCall &c, uint64_t max_rounds, uint64_t *first, bool *consistent) {
+    while (!*consistent && c.st.repair_rounds < max_rounds) {
+        uint64_t tot2 = 0, n_changed = 0;
+        int rc = compute_offsets(g, c.d_starts, c.d_out, c.walk_length, c.n_jobs, c.stream_skip, true, &tot2, &n_changed, 0, c.n_jobs, first);
+        if (rc) return rc;
+        if (c.sw.debug_rounds) fprintf(stderr, "[repair] round %llu: %llu jobs re-addressed\n", (unsigned long long)c.st.repair_rounds, (unsigned long long)n_changed);
+        if (n_changed == 0) { *consistent = true; break; }
+        rc = rewalk_changed(g, c, n_changed);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// (b) opt-in: every walk owns a fixed slot of walk_length draws
+static int repair_nominal(pw_graph *g, WalkCall &c) {
+    uint64_t tot2 = 0, n_changed = 0;
+    int rc = compute_offsets(g, c.d_starts, nullptr, c.walk_length, c.n_jobs, c.stream_skip, true, &tot2, &n_changed);
+    if (rc) return rc;
+    c.st.stream_addressing = 1;
+    if (c.sw.debug_rounds) fprintf(stderr, "[repair] %llu jobs re-addressed (nominal slots)\n", (unsigned long long)n_changed);
+    if (n_changed) {
+        rc = rewalk_changed(g, c, n_changed);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// (c) BLOCK-WISE, exact.  Invariant: every job below `first` is final and off_first is the stream offset of job `first`.
+// A round addresses the WINDOW [first, first + blk) from off_first (three small launches over the window, not the
+// array), re-walks the jobs of the window whose offset differs from the one they were last walked with, and moves
+// `first` to the first of them -- that job has now been walked with its final offset, everything before it was
+// consistent -- or to the end of a window in which nothing differed.  At least one job per round, O(window) work per
+// round; the window grows while rounds clear most of it and shrinks while they do not.  A time budget bounds the
+// whole (PECANPY_AMD_REPAIR_SECONDS, default 600; 0: none): the error names the alternatives.
+static int repair_blockwise(pw_graph *g, WalkCall &c, uint64_t first) {
+    const uint64_t n_jobs = c.n_jobs;
+    uint64_t blk = 4096;
+    const char *blk_env = getenv("PECANPY_AMD_REPAIR_BLOCK");
+    if (blk_env) blk = (uint64_t)strtoull(blk_env, nullptr, 10);
+    if (blk < 1) blk = 1;
+    const double budget_s = getenv("PECANPY_AMD_REPAIR_SECONDS") ? atof(getenv("PECANPY_AMD_REPAIR_SECONDS")) : 600.0;
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = now();
+    if (first == ~0ull || first >= n_jobs) first = 0;
+    uint64_t off_first = c.stream_skip;
+    if (first) HIP_TRY(hipMemcpy(&off_first, g->stream_off.p + first, sizeof(uint64_t), hipMemcpyDeviceToHost));   // (last whole-array scan)
+    while (first < n_jobs) {
+        const uint64_t n_win = first + blk < n_jobs ? blk : n_jobs - first;
+        uint64_t tot2 = 0, n_changed = 0, fm = ~0ull;
+        int rc = compute_offsets(g, c.d_starts, c.d_out, c.walk_length, n_win, off_first, true, &tot2, &n_changed, first, n_jobs, &fm);
+        if (rc) return rc;
+        if (c.sw.debug_rounds) fprintf(stderr, "[repair] round %llu (block-wise): window [%llu, +%llu): %llu jobs re-addressed\n",
+                                               (unsigned long long)c.st.repair_rounds, (unsigned long long)first, (unsigned long long)n_win, (unsigned long long)n_changed);
+        if (n_changed == 0) {           // the whole window is consistent: final
+            first += n_win;
+            off_first += tot2;
+            if (!blk_env && blk < (1ull << 20)) blk *= 2;
+            continue;
+        }
+        rc = rewalk_changed(g, c, n_changed, &off_first, fm);
+        if (rc) return rc;
+        if (!blk_env) {
+            const uint64_t adv = fm - first;
+            if (adv >= n_win / 2 && blk < (1ull << 20)) blk *= 2;
+            else if (adv < n_win / 16 && blk > 256) blk /= 2;
+        }
+        first = fm;                     // (walked with its final offset just now; the next window starts on it)
+        if (budget_s > 0 && now() - t_begin > budget_s)
+            return fail(PW_ERR_UNSUPPORTED, "dead-end repair: " + std::to_string(first) + " of " + std::to_string(n_jobs) + " walks final after " +
+                                            std::to_string((long long)budget_s) + " s of block-wise re-addressing (a directed graph full of sinks makes the "
+                                            "reference's single random stream sequential, pecanpy.py:198-206).  PECANPY_AMD_REPAIR_SECONDS=0 lifts the "
+                                            "limit; PECANPY_AMD_NOMINAL_STREAM=1 gives every walk a fixed slot of the stream instead (seeded, not the "
+                                            "reference's assignment)");
+    }
+    return 0;
+}
+
+// pw_stats of the call: the counters of the first pass (h), or -- after a repair -- of the final, self-consistent matrix
+static int fill_stats(pw_graph *g, WalkCall &c, unsigned long long h[N_COUNTERS], uint64_t dead) {
+    pw_stats &st = c.st;
+    if (st.repair_rounds) {
+        // statistics of the final, self-consistent matrix
+        HIP_TRY(hipMemcpy(h, g->counters.p, N_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        uint64_t tot2 = 0;
+        if (!st.stream_addressing) {
+            int rc = compute_offsets(g, c.d_starts, c.d_out, c.walk_length, c.n_jobs, c.stream_skip, false, &tot2, nullptr);
+            if (rc) return rc;
+        } else {  // offsets stay nominal; count the steps from the lengths without touching them
+            std::vector<uint32_t> lens(c.n_jobs);
+            HIP_TRY(hipMemcpy2D(lens.data(), sizeof(uint32_t), c.d_out + c.walk_length + 1,
+                                sizeof(uint32_t) * ((size_t)c.walk_length + 2), sizeof(uint32_t), c.n_jobs,
+                                hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < c.n_jobs; i++) tot2 += lens[i] - 1;
+        }
+        st.total_steps = tot2;
+    } else {
+        st.total_steps = h[pw::CTR_STEPS];
+    }
+    st.overflow_reads = h[pw::CTR_OVERFLOW];
+    st.clamped_reads = h[pw::CTR_CLAMPED];
+    st.dead_end_walks = dead;
+    st.lane_kernel = g->call.wl_used ? 3u : (c.lanes ? (lanes_float_eligible(g, c.wa, c.sw) ? 2u : 1u) : 0u);
+    st.redo_walks = c.redo_total;
+    st.list_entries_read = h[pw::CTR_LIST_READS];
+    st.ambiguous_steps = h[pw::CTR_AMBIGUOUS];
+    st.wave_chain_steps = h[pw::CTR_WAVE_CHAIN];
+    st.param_index_ms = g->call.param_ms;
+    st.lane_kernel_ms = g->call.lane_ms;
+    st.lane_rounds = g->call.lane_rounds;
+    st.verify_checked = g->call.ver_checked;
+    st.verify_mismatch = g->call.ver_mismatch;
+    st.verify_dropped = g->call.ver_dropped;
+    st.verify_ties = g->call.ver_ties;
+    st.eager_steps = h[pw::CTR_EAGER];
+    st.index_max_list = g->gd->kind == 0 && g->gd->d_lines.p ? g->gd->list_max_len : 0u;
+    return 0;
+}
+
+static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, double p, double q, int extend,
+                                const uint32_t *d_starts, uint64_t n_jobs, uint32_t walk_length,
+                                int has_seed, uint32_t seed, uint64_t stream_skip, uint32_t *d_out,
+                                pw_stats *stats) {
+    int rc = validate_call(g, mode, p, q, &extend, d_starts, n_jobs, walk_length, d_out);
+    if (rc) return rc;
+    WalkCall c{sw, mode, extend != 0, d_starts, n_jobs, walk_length, stream_skip, d_out, {}, {}, 0, false};
+    pw_stats &st = c.st;
     memset(&st, 0, sizeof(st));
     if (n_jobs == 0) { if (stats) *stats = st; return PW_OK; }
     if (!has_seed) seed = os_seed();
     if (grow(g->counters, N_COUNTERS)) return PW_ERR_NOMEM;
     { int rcs = check_starts(g, d_starts, n_jobs); if (rcs) return rcs; }
-    g->call_n2vpp = n2vpp;
-    g->call_spp = spp;
+    g->call = pw_graph::Call{};   // THE reset of the call's state: the phases and the launchers below only add to it
+    g->call.n2vpp = mode == PW_MODE_NODE2VEC_PLUSPLUS;
+    g->call.spp = mode == PW_MODE_SPARSE_NODE2VEC_PLUSPLUS;
     if (mode_sequential_stream(mode)) {
         if (stream_skip) return fail(PW_ERR_UNSUPPORTED, "alias / first-order modes consume a variable number of "
                                                          "words per step: the stream cannot be sharded");
@@ -3180,10 +3441,10 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
 
     // 1. stream offsets (nominal: every walk from a start with neighbours runs L steps)
     uint64_t total = 0;
-    int rc = compute_offsets(g, d_starts, nullptr, walk_length, n_jobs, stream_skip, false, &total, nullptr);
+    rc = compute_offsets(g, d_starts, nullptr, walk_length, n_jobs, stream_skip, false, &total, nullptr);
     if (rc) return rc;
 
-    g->call_runnable = total / walk_length;
+    g->call.runnable = total / walk_length;
     const bool lanes_pre = g->gd->kind == 0 && g->gd->unit && g->gd->d_lines.p && !g->gd->lanes_off && mode == PW_MODE_SPARSE_OTF;
     // (zero-fill of the walk matrix for the lane kernel: on the side stream, overlapped with the stream expansion.  No
     //  return path may leave that write to the CALLER's buffer in flight: the guard waits for the side stream.)
@@ -3204,82 +3465,14 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
 
     // 3. walks
     HIP_TRY(hipMemsetAsync(g->counters.p, 0, N_COUNTERS * sizeof(unsigned long long), g->stream));
-    pw::WalkArgs wa;
-    wa.g = csr_dev(g);
-    wa.p = p;
-    wa.q = q;
-    wa.L = walk_length;
-    wa.n_jobs = n_jobs;
-    wa.starts = d_starts;
-    wa.stream_off = g->stream_off.p;
-    wa.job_list = nullptr;
-    wa.n_list = 0;
-    // (the lane kernel loads the draws as aligned 16-byte pairs: the block must start on such a boundary and hold an even number
-    //  of doubles -- whole blocks of 312 from an allocation's base do)
-    if (((uintptr_t)g->rng.p & 15u) != 0 || (g->rng.cap & 1u) != 0)
-        return fail(PW_ERR_INVALID, "stream buffer is not made of aligned pairs of draws");
-    wa.rng = g->rng.p;
-    wa.rng_base = rng_base;
-    wa.out = d_out;
-    wa.job_counter = g->counters.p + pw::CTR_JOB;
-    wa.stats = g->counters.p + pw::CTR_STATS;
-    wa.tot_e = nullptr;
-    wa.tot_v = nullptr;
-    wa.resume = 0;
-    {
-        // unit-weight biases exactly as the kernels form them: fl32(f64(1.0f) / q) (sparse_rw.py:59-62)
-        wa.w_out = (float)(1.0 / q);
-        wa.w_prev = (float)(1.0 / p);
-        auto pow2_ok = [](float w) {
-            int e = 0;
-            return std::frexp(w, &e) == 0.5f && e > -60 && e < 60;
-        };
-        wa.lazy_ok = (pow2_ok(wa.w_out) && pow2_ok(wa.w_prev)) ? 1u : 0u;
-    }
-    g->param_ms_call = 0;
-    if (!spp) rc = ensure_tot_table(g, wa, sw, extend != 0);   // (before the timed walk region: a per-(p, q) index, reported apart)
-    if (rc) return rc;
-    if (mode == PW_MODE_SPARSE_OTF && lanes_float_eligible(g, wa, sw)) { rc = ensure_unit_tot(g, wa, sw); if (rc) return rc; }
-    g->wl_active = false;
-    g->wl_used = false;
-    if (mode == PW_MODE_SPARSE_OTF && wlanes_worth(sw, n_jobs)) {
-        rc = ensure_wlane_tables(g, wa, sw, extend != 0, &g->wl_active);   // (likewise; the weighted lane form needs both)
-        if (rc) return rc;
-        if (g->wl_active) {   // the lane kernel only writes the cells a walk fills (unit graphs: zero-filled on the side stream above)
-            HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(uint32_t) * (size_t)n_jobs * ((size_t)walk_length + 2), g->stream));
-        }
-    }
-    if (g->on_tables_ready) { auto cb = g->on_tables_ready; g->on_tables_ready = nullptr; cb(); }
-    uint64_t redo_total = 0;
-    const bool lanes = !spp && (lanes_eligible(g, wa, sw) || lanes_float_eligible(g, wa, sw));
-    g->lane_ms = 0;
-    g->lane_rounds = 0;
-    g->ver_checked = g->ver_mismatch = g->ver_dropped = g->ver_ties = 0;
-    HIP_TRY(hipEventRecord(g->ev[2], g->stream));
-    // the lane kernel only writes the cells a walk fills: the matrix starts zeroed (pecanpy.py:182-187) -- by the side
-    // stream, under the stream expansion above
-    if (lanes_pre) HIP_TRY(hipStreamWaitEvent(g->stream, g->ev_side, 0));
-    rc = launch_walks(g, wa, sw, extend != 0, &redo_total);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(g->ev[3], g->stream));
+    rc = make_walk_args(g, c, p, q, rng_base);
+    if (!rc) rc = prepare_tables(g, c);
     unsigned long long h[N_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(h, g->counters.p, sizeof(h), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (!rc) rc = first_pass(g, c, lanes_pre, h);
+    if (rc) return rc;
 #ifdef PW_PROF
-    {
-        unsigned long long hp[16], zero[16] = {0};
-        HIP_TRY(hipMemcpyFromSymbol(hp, HIP_SYMBOL(pw::g_prof), sizeof(hp)));
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(pw::g_prof), zero, sizeof(zero)));
-        static const char *names[16] = {"step pro/epilogue", "lazy setup", "membership chunks", "build_rank", "seq_head",
-                                        "unit_chain", "eager fallback", "exact search", "#chunks", "#searches", "#eager steps",
-                                        "#ambiguous", "#chain tie fallbacks", "#search rounds", "-", "-"};
-        double tot = 0;
-        for (int i = 0; i < 8; i++) tot += (double)hp[i];
-        fprintf(stderr, "[pw_prof] steps=%llu\n", h[pw::CTR_STEPS]);
-        for (int i = 0; i < 8; i++)
-            fprintf(stderr, "[pw_prof] %-20s %6.2f%%  %.1f cycles/step\n", names[i], 100.0 * hp[i] / tot, (double)hp[i] / (double)h[pw::CTR_STEPS]);
-        for (int i = 8; i < 16; i++) fprintf(stderr, "[pw_prof] %-20s %.3f /step\n", names[i], (double)hp[i] / (double)h[pw::CTR_STEPS]);
-    }
+    rc = dump_walk_prof(h);
+    if (rc) return rc;
 #endif
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
@@ -3301,131 +3494,15 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
     //    walk_length draws: reproducible under the seed and statistically equivalent, but not the reference's
     //    draw-for-draw assignment -- is an explicit opt-in (PECANPY_AMD_NOMINAL_STREAM=1), reported through
     //    pw_stats.stream_addressing = 1.
-    uint64_t dead = h[pw::CTR_DEAD];
+    const uint64_t dead = h[pw::CTR_DEAD];
     const uint64_t max_rounds = 32;
     const bool nominal_ok = env_on("PECANPY_AMD_NOMINAL_STREAM");
-    // (a) whole-array rounds
-    // the jobs compute_offsets re-addressed (g->changed), walked again and their kernel time accounted; `off_first` (block-wise
-    // repair): the offset of job `fm` is read back behind the walks, before the wait
-    auto rewalk_changed = [&](uint64_t n_changed, uint64_t *off_first = nullptr, uint64_t fm = 0) -> int {
-        st.repair_rounds++;
-        wa.job_list = g->changed.p;
-        wa.n_list = n_changed;
-        HIP_TRY(hipEventRecord(g->ev[2], g->stream));
-        int rcw = launch_walks(g, wa, sw, extend != 0, &redo_total);
-        if (rcw) return rcw;
-        HIP_TRY(hipEventRecord(g->ev[3], g->stream));
-        if (off_first) HIP_TRY(hipMemcpyAsync(off_first, g->stream_off.p + fm, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        HIP_TRY(hipEventElapsedTime(&ms, g->ev[2], g->ev[3]));
-        st.walk_kernel_ms += ms;
-        st.walk_kernel_launches++;
-        return 0;
-    };
     uint64_t first = ~0ull;          // smallest job whose offset changed in the last whole-array round (re-walked since: final)
     bool consistent = dead == 0;
-    while (!consistent && st.repair_rounds < max_rounds) {
-        uint64_t tot2 = 0, n_changed = 0;
-        rc = compute_offsets(g, d_starts, d_out, walk_length, n_jobs, stream_skip, true, &tot2, &n_changed, 0, n_jobs, &first);
-        if (rc) return rc;
-        if (sw.debug_rounds) fprintf(stderr, "[repair] round %llu: %llu jobs re-addressed\n", (unsigned long long)st.repair_rounds, (unsigned long long)n_changed);
-        if (n_changed == 0) { consistent = true; break; }
-        rc = rewalk_changed(n_changed);
-        if (rc) return rc;
-    }
-    if (!consistent && nominal_ok) {
-        // (b) opt-in: every walk owns a fixed slot of walk_length draws
-        uint64_t tot2 = 0, n_changed = 0;
-        rc = compute_offsets(g, d_starts, nullptr, walk_length, n_jobs, stream_skip, true, &tot2, &n_changed);
-        if (rc) return rc;
-        st.stream_addressing = 1;
-        if (sw.debug_rounds) fprintf(stderr, "[repair] %llu jobs re-addressed (nominal slots)\n", (unsigned long long)n_changed);
-        if (n_changed) {
-            rc = rewalk_changed(n_changed);
-            if (rc) return rc;
-        }
-    } else if (!consistent) {
-        // (c) BLOCK-WISE, exact.  Invariant: every job below `first` is final and off_first is the stream offset of job `first`.
-        // A round addresses the WINDOW [first, first + blk) from off_first (three small launches over the window, not the
-        // array), re-walks the jobs of the window whose offset differs from the one they were last walked with, and moves
-        // `first` to the first of them -- that job has now been walked with its final offset, everything before it was
-        // consistent -- or to the end of a window in which nothing differed.  At least one job per round, O(window) work per
-        // round; the window grows while rounds clear most of it and shrinks while they do not.  A time budget bounds the
-        // whole (PECANPY_AMD_REPAIR_SECONDS, default 600; 0: none): the error names the alternatives.
-        uint64_t blk = 4096;
-        const char *blk_env = getenv("PECANPY_AMD_REPAIR_BLOCK");
-        if (blk_env) blk = (uint64_t)strtoull(blk_env, nullptr, 10);
-        if (blk < 1) blk = 1;
-        const double budget_s = getenv("PECANPY_AMD_REPAIR_SECONDS") ? atof(getenv("PECANPY_AMD_REPAIR_SECONDS")) : 600.0;
-        auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double t_begin = now();
-        if (first == ~0ull || first >= n_jobs) first = 0;
-        uint64_t off_first = stream_skip;
-        if (first) HIP_TRY(hipMemcpy(&off_first, g->stream_off.p + first, sizeof(uint64_t), hipMemcpyDeviceToHost));   // (last whole-array scan)
-        while (first < n_jobs) {
-            const uint64_t n_win = first + blk < n_jobs ? blk : n_jobs - first;
-            uint64_t tot2 = 0, n_changed = 0, fm = ~0ull;
-            rc = compute_offsets(g, d_starts, d_out, walk_length, n_win, off_first, true, &tot2, &n_changed, first, n_jobs, &fm);
-            if (rc) return rc;
-            if (sw.debug_rounds) fprintf(stderr, "[repair] round %llu (block-wise): window [%llu, +%llu): %llu jobs re-addressed\n",
-                                                   (unsigned long long)st.repair_rounds, (unsigned long long)first, (unsigned long long)n_win, (unsigned long long)n_changed);
-            if (n_changed == 0) {           // the whole window is consistent: final
-                first += n_win;
-                off_first += tot2;
-                if (!blk_env && blk < (1ull << 20)) blk *= 2;
-                continue;
-            }
-            rc = rewalk_changed(n_changed, &off_first, fm);
-            if (rc) return rc;
-            if (!blk_env) {
-                const uint64_t adv = fm - first;
-                if (adv >= n_win / 2 && blk < (1ull << 20)) blk *= 2;
-                else if (adv < n_win / 16 && blk > 256) blk /= 2;
-            }
-            first = fm;                     // (walked with its final offset just now; the next window starts on it)
-            if (budget_s > 0 && now() - t_begin > budget_s)
-                return fail(PW_ERR_UNSUPPORTED, "dead-end repair: " + std::to_string(first) + " of " + std::to_string(n_jobs) + " walks final after " +
-                                                std::to_string((long long)budget_s) + " s of block-wise re-addressing (a directed graph full of sinks makes the "
-                                                "reference's single random stream sequential, pecanpy.py:198-206).  PECANPY_AMD_REPAIR_SECONDS=0 lifts the "
-                                                "limit; PECANPY_AMD_NOMINAL_STREAM=1 gives every walk a fixed slot of the stream instead (seeded, not the "
-                                                "reference's assignment)");
-        }
-    }
-    if (st.repair_rounds) {
-        // statistics of the final, self-consistent matrix
-        HIP_TRY(hipMemcpy(h, g->counters.p, sizeof(h), hipMemcpyDeviceToHost));
-        uint64_t tot2 = 0;
-        if (!st.stream_addressing) {
-            rc = compute_offsets(g, d_starts, d_out, walk_length, n_jobs, stream_skip, false, &tot2, nullptr);
-            if (rc) return rc;
-        } else {  // offsets stay nominal; count the steps from the lengths without touching them
-            std::vector<uint32_t> lens(n_jobs);
-            HIP_TRY(hipMemcpy2D(lens.data(), sizeof(uint32_t), d_out + walk_length + 1,
-                                sizeof(uint32_t) * ((size_t)walk_length + 2), sizeof(uint32_t), n_jobs,
-                                hipMemcpyDeviceToHost));
-            for (uint64_t i = 0; i < n_jobs; i++) tot2 += lens[i] - 1;
-        }
-        st.total_steps = tot2;
-    } else {
-        st.total_steps = h[pw::CTR_STEPS];
-    }
-    st.overflow_reads = h[pw::CTR_OVERFLOW];
-    st.clamped_reads = h[pw::CTR_CLAMPED];
-    st.dead_end_walks = dead;
-    st.lane_kernel = g->wl_used ? 3u : (lanes ? (lanes_float_eligible(g, wa, sw) ? 2u : 1u) : 0u);
-    st.redo_walks = redo_total;
-    st.list_entries_read = h[pw::CTR_LIST_READS];
-    st.ambiguous_steps = h[pw::CTR_AMBIGUOUS];
-    st.wave_chain_steps = h[pw::CTR_WAVE_CHAIN];
-    st.param_index_ms = g->param_ms_call;
-    st.lane_kernel_ms = g->lane_ms;
-    st.lane_rounds = g->lane_rounds;
-    st.verify_checked = g->ver_checked;
-    st.verify_mismatch = g->ver_mismatch;
-    st.verify_dropped = g->ver_dropped;
-    st.verify_ties = g->ver_ties;
-    st.eager_steps = h[pw::CTR_EAGER];
-    st.index_max_list = g->gd->kind == 0 && g->gd->d_lines.p ? g->gd->list_max_len : 0u;
+    rc = repair_whole_array(g, c, max_rounds, &first, &consistent);
+    if (!rc && !consistent) rc = nominal_ok ? repair_nominal(g, c) : repair_blockwise(g, c, first);
+    if (!rc) rc = fill_stats(g, c, h, dead);
+    if (rc) return rc;
     if (stats) *stats = st;
     return PW_OK;
 }
@@ -3503,6 +3580,8 @@ static int simulate_twin(pw_graph *g, const LaneSwitches &sw, int mode, double p
     if (rc) return rc;
     if (rc_b) return fail(rc_b, err_b);
     if (sa.total_steps != nominal_a && !sa.stream_addressing) {   // dead ends in the first half: the second starts earlier in the stream
+        // (twin_active is still set on both contexts -- active_guard -- although this rerun walks alone: its lane and eager grids
+        //  keep the twin's smaller share of the GPU.  That costs speed only, never a walk: ADVICE.md, second item; left as it is)
         run_b(stream_skip + sa.total_steps);
         if (rc_b) return fail(rc_b, err_b);
     }
@@ -3695,11 +3774,10 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
     struct HoldGuard {
         pw_graph *g;
         bool mine;
-        ~HoldGuard() { if (mine) g->rng_hold.valid = false; }
+        ~HoldGuard() { if (mine) g->drop_hold(); }
     } hold_guard{g, false};
     if (!rc && n_parts > 1 && !ring) {
-        g->rng_hold.valid = false;        // (a caller's pw_stream_hold ends here: this call expands the stream of its own array)
-        g->rng_hold.user = false;
+        g->drop_hold();                   // (a caller's pw_stream_hold ends here: this call expands the stream of its own array)
         hold_guard.mine = true;
         if (grow(g->counters, N_COUNTERS)) rc = PW_ERR_NOMEM;
         if (!rc) rc = check_starts(g, d_starts, n_jobs);
@@ -3709,10 +3787,7 @@ PW_EXPORT int pw_simulate(pw_graph *g, int mode, double p, double q, int extend,
         if (!rc) rc = expand_stream(g, seed, true, stream_skip, nominal, &base);
         if (!rc) {
             (void)hipEventRecord(g->ev[6], g->stream);   // (ev[0] / ev[1] are recorded again by every part)
-            g->rng_hold.valid = true;
-            g->rng_hold.seed = seed;
-            g->rng_hold.first_block = base / 312;
-            g->rng_hold.n_blocks = (stream_skip + nominal + 311) / 312 > base / 312 ? (stream_skip + nominal + 311) / 312 - base / 312 : 1;
+            g->set_hold(seed, base, stream_skip, nominal, false);
         }
     }
     const bool held = g->rng_hold.valid && hold_guard.mine;
