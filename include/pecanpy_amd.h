@@ -549,6 +549,39 @@ int pw_selftest_edgelist_weight(const char *text, uint64_t n, double *value);
 int pw_selftest_edgelist_line(const char *text, uint64_t lo, uint64_t hi, const char *delimiter, int weighted, uint32_t *n_terms,
                               uint32_t *spans, double *weight);
 
+/* ---- a walk corpus file read on the device (csrc/corpus_dev.hip.h) -----------------------------------------------------------
+ * The inverse of pw_walks_write_text_device: the text of a corpus file (one walk per line, names separated by white space) is
+ * uploaded and tokenised in device memory, the names are numbered by first appearance with the edge-list reader's id table,
+ * and the walk matrix uint32[n_rows, width] is laid out as pw_sgns_train_device and pw_walks_write_text_device take it: row r =
+ * the numbers of line r's tokens, zeros, and in the last cell the token count; width = the most tokens in a line (at least 1)
+ * + 1, i.e. walk_length = width - 2.  The byte definition is pecanpy_amd.corpus.read_walks.  Return value:
+ *   PW_EDGELIST_OK                 *out = the matrix (pw_corpus_dev_shape / _fill / _export / _destroy), *ids = the names in
+ *                                  first-appearance order (pw_edgelist_ids_shape / _export / _destroy)
+ *   PW_EDGELIST_NEEDS_HOST_READER  no error: the caller reads the file on the host.  A byte outside {\t, \n, \r, 0x20 .. 0x7E}
+ *                                  (\v, \f, 0x1C .. 0x1F, NUL, 0x7F, everything from 0x80 up); an empty file; a file of 4 GiB or
+ *                                  more; scratch or a matrix that does not fit in device (or host) memory
+ *   PW_EDGELIST_IO                 the file cannot be opened or read
+ *   < 0                            PW_ERR_*: no device, a HIP error
+ * Space, \t and \r separate tokens, \n ends a line; a last line without a newline counts, an empty line is a row of count 0.
+ * Nothing stays allocated unless PW_EDGELIST_OK is returned.  stats (may be NULL; zeroed unless OK): wall clock of the stages,
+ * each ended by a wait for the device -- upload_ms (file -> pinned staging -> device text), scan_ms (byte classes, newline and
+ * token-start counts, their scans, token offsets / lines, the width), tokens_ms (token records, id table, numbering), fill_ms
+ * (the matrix, the names' spans) -- and file_bytes, lines, tokens, names.
+ *   pw_corpus_dev_shape    n_rows, width, n_tokens (any may be NULL)
+ *   pw_corpus_dev_fill     the matrix into d_out, a device buffer of the handle's device with room for n_rows * width words
+ *                          (a torch tensor's storage); complete when the call returns
+ *   pw_corpus_dev_export   the same words to host memory */
+typedef struct pw_corpus_dev_stats {
+    double upload_ms, scan_ms, tokens_ms, fill_ms;
+    uint64_t file_bytes, lines, tokens, names;
+} pw_corpus_dev_stats;
+typedef struct pw_corpus_dev pw_corpus_dev;
+int pw_corpus_read_device(const char *path, int device, pw_corpus_dev **out, pw_edgelist_ids **ids, pw_corpus_dev_stats *stats);
+int pw_corpus_dev_shape(const pw_corpus_dev *c, uint64_t *n_rows, uint64_t *width, uint64_t *n_tokens);
+int pw_corpus_dev_fill(const pw_corpus_dev *c, uint32_t *d_out);
+int pw_corpus_dev_export(const pw_corpus_dev *c, uint32_t *h_out);
+void pw_corpus_dev_destroy(pw_corpus_dev *c);
+
 /* ---- self test hooks (host only, no GPU needed -- except pw_selftest_lane with on_device) -- */
 /* Runs the binade-scan emulation of csrc/seqscan.h on a host array: returns through *index the
  * position np.searchsorted(np.cumsum(x), r) would return under sequential float32 semantics

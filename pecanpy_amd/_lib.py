@@ -105,7 +105,24 @@ class PwEdgelistDevStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
-EDGELIST_OK, EDGELIST_NEEDS_HOST_READER, EDGELIST_IO = 0, 1, 2   # pw_edgelist_read_device's non-negative results
+class PwCorpusDevStats(C.Structure):
+    """``pw_corpus_dev_stats`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("upload_ms", C.c_double),
+        ("scan_ms", C.c_double),
+        ("tokens_ms", C.c_double),
+        ("fill_ms", C.c_double),
+        ("file_bytes", C.c_uint64),
+        ("lines", C.c_uint64),
+        ("tokens", C.c_uint64),
+        ("names", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+EDGELIST_OK, EDGELIST_NEEDS_HOST_READER, EDGELIST_IO = 0, 1, 2   # pw_edgelist_read_device's non-negative results (pw_corpus_read_device's too)
 EDGELIST_KEEP_F64 = 1   # pw_edgelist_read_device_ex's flag bit: the CSR keeps the float64 weights for the dense build
 ERR_UNSUPPORTED = -4    # PW_ERR_UNSUPPORTED
 
@@ -200,6 +217,11 @@ SYMBOLS = {
     "pw_edgelist_ids_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pw_edgelist_ids_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pw_edgelist_ids_destroy": (None, [C.c_void_p]),
+    "pw_corpus_read_device": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(PwCorpusDevStats)]),
+    "pw_corpus_dev_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3),
+    "pw_corpus_dev_fill": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pw_corpus_dev_export": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pw_corpus_dev_destroy": (None, [C.c_void_p]),
     "pw_selftest_edgelist_weight": (C.c_int, [C.c_char_p, C.c_uint64, _f64p]),
     "pw_selftest_edgelist_line": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int, _u32p, C.c_void_p, _f64p]),
     "pw_selftest_exact_decision": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_uint32,

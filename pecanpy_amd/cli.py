@@ -6,6 +6,7 @@ Flag names, defaults, the mode sanity rules and the stage order follow the refer
 uses gensim when it is importable; without it walks and skip-gram both run on the GPU (``Base.embed_array``: the
 walk matrix stays in device memory).  ``--task walks`` writes the walks (one per line) to ``--output`` instead of training,
 the text made in device memory; ``PECANPY_AMD_DUMP_WALKS=1`` does the same through the ID lists of ``simulate_walks``.
+``--task train`` takes such a file as ``--input`` and trains from it on the GPU, without a graph.
 The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
@@ -26,9 +27,10 @@ MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "Sp
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
     ("--output", dict(required=True, help="embedding file (.npz -> IDs/data arrays, else word2vec text)")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks"),
-                    help="run node2vec; only convert the edge list to CSR / dense .npz; or (walks) generate the walks and "
-                         "write them, one per line, to --output; no training")),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train"),
+                    help="run node2vec; only convert the edge list to CSR / dense .npz; (walks) generate the walks and "
+                         "write them, one per line, to --output, no training; or (train) train embeddings from a walk "
+                         "corpus file given as --input, no graph")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
     ("--walk-length", dict(type=int, default=80, help="steps per walk")),
@@ -225,9 +227,28 @@ def embed_on_gpu(args, g):
     _save_vectors(args, g, vecs)
 
 
+@Timer("read corpus + train embeddings")
+def train_from_corpus(args):
+    """``--task train``: ``--input`` is a walk corpus file (what ``--task walks`` writes); it is read and numbered in device
+    memory and trained there (``embed.train_sgns_file``); the vectors are written in order of first appearance."""
+    from .embed import save_word2vec_format_device, train_sgns_file
+
+    names, d_vectors = train_sgns_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
+                                       seed=args.random_state)
+    if args.verbose:
+        print(f"corpus read by the {train_sgns_file.last_stats['read']['reader']} reader")
+    if args.output.endswith(".npz"):
+        np.savez(args.output, IDs=names, data=d_vectors.cpu().numpy())
+    else:
+        save_word2vec_format_device(args.output, names, d_vectors)
+
+
 def main(argv=None):
-    """read graph -> preprocess -> walks (GPU) -> embeddings."""
+    """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings."""
     args = parse_args(argv)
+    if args.task == "train":   # no graph: the graph flags are ignored
+        train_from_corpus(args)
+        return
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)
     preprocess(g)

@@ -6,6 +6,10 @@
 ``cli._dump_walks`` writes for the ID lists of the same rows (``Base._map_walk``).  ``save_walks_device`` makes the same bytes on
 the GPU from the matrix where ``WalkEngine.simulate_device`` leaves it (``pw_walks_write_text_device``, csrc/walk_text.hip.h):
 neither the matrix nor ID lists visit the host, only the text does.
+
+``read_walks`` is the host reader and the byte definition of the way back: a corpus file -> the walk matrix and the names.
+``read_walks_device`` makes the same matrix on the GPU from the text (``pw_corpus_read_device``, csrc/corpus_dev.hip.h), where
+``embed.train_sgns_device`` takes it: only the file's bytes go up and only the names come down.
 """
 import ctypes as C
 import os
@@ -14,7 +18,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["save_walks", "save_walks_device"]
+__all__ = ["save_walks", "save_walks_device", "read_walks", "read_walks_device"]
 
 _WRITE_ROWS = 1 << 14   # rows formatted per write
 
@@ -79,3 +83,134 @@ def save_walks_device(path, node_ids, d_walks):
 
 
 save_walks_device.last_stats = None
+
+
+def _unknown_token(token, line, n_names):
+    return ValueError(f"token {token!r} in line {line} of the corpus is not among the {n_names} node ids")
+
+
+def read_walks(path, node_ids=None):
+    """The inverse of ``save_walks`` and the byte definition of what ``read_walks_device`` returns: ``(walk_matrix, names)``.
+
+    The file's bytes are split on ``b"\\n"``; an empty last piece is dropped (a file that ends in a newline; the empty file).
+    Every other piece is a line, an empty one included, and ``line.decode("utf-8").split()`` gives its tokens -- a ``\\r`` is
+    white space wherever it stands, as it is for gensim's ``LineSentence``.  ``names`` holds the distinct tokens in order of
+    first appearance and a token's index is its position there; with ``node_ids`` given the indices address ``node_ids``
+    (``str(name)``) instead, ``names`` is ``[str(x) for x in node_ids]`` and a token that is not among them is a
+    ``ValueError`` that names the token and its line (counted from 1).  ``walk_matrix`` is ``uint32[n_lines, W]`` with
+    ``W = max(most tokens in any line, 1) + 1``: a row with ``n`` tokens holds their indices in cells ``[0, n)``, 0 in cells
+    ``[n, W - 1)`` and ``n`` in cell ``W - 1`` -- the engine's row form with ``walk_length = W - 2``.  A file without lines
+    gives ``uint32[0, 2]`` and ``[]``."""
+    from array import array
+
+    with open(path, "rb") as f:
+        pieces = f.read().split(b"\n")
+    if pieces[-1] == b"":
+        pieces.pop()
+    if node_ids is None:
+        names, index = [], {}
+    else:
+        names, index = [str(x) for x in node_ids], {}
+        for i, name in enumerate(names):
+            index.setdefault(name, i)
+    flat = array("I")   # the indices of all tokens in file order: four bytes a token, not a Python object
+    lens = np.zeros(len(pieces), dtype=np.int64)
+    for r, piece in enumerate(pieces):
+        tokens = piece.decode("utf-8").split()
+        lens[r] = len(tokens)
+        if node_ids is None:
+            flat.extend([index.setdefault(t, len(index)) for t in tokens])
+        else:
+            try:
+                flat.extend([index[t] for t in tokens])
+            except KeyError as e:
+                raise _unknown_token(e.args[0], r + 1, len(names)) from None
+    if node_ids is None:
+        names = list(index)   # (a dict keeps insertion order: first appearance)
+    last = max(int(lens.max(initial=0)), 1)
+    mat = np.zeros((len(pieces), last + 1), dtype=np.uint32)
+    mat[:, :last][np.arange(last) < lens[:, None]] = np.frombuffer(flat, dtype=np.uint32)   # row by row, in front of each length
+    mat[:, last] = lens
+    return mat, names
+
+
+def read_walks_device(path, node_ids=None, device=0):
+    """``read_walks`` with the file read in device memory (``pw_corpus_read_device``, csrc/corpus_dev.hip.h): the text is
+    uploaded, tokenised and numbered by first appearance on the GPU and the matrix is laid out there.  Returns
+    ``(d_walks, names)``: ``d_walks`` a contiguous int32 CUDA tensor ``[n_lines, W]`` (uint32 storage), what
+    ``train_sgns_device`` and ``save_walks_device`` take, equal to ``read_walks(path, node_ids)[0]`` cell for cell; ``names``
+    the same list.  Only the file's bytes go up and only the names come down.
+
+    The device reader takes files whose bytes are all in ``{\\t, \\n, \\r, 0x20 .. 0x7E}``; any other file (a UTF-8 name,
+    ``\\x0b``, NUL, ..., the empty file, 4 GiB or more) is read by ``read_walks`` and uploaded -- no error.  With ``node_ids``
+    the remap from first-appearance numbers to positions in ``node_ids`` is built on the host over the names (not the tokens)
+    and applied on the device; an unknown token raises ``read_walks``' ``ValueError``.  ``read_walks_device.last_stats``:
+    ``"reader"`` (``"device"`` or ``"host"``), ``call_ms``, and for the device reader ``pw_corpus_dev_stats`` (``upload_ms``,
+    ``scan_ms``, ``tokens_ms``, ``fill_ms``, ``file_bytes``, ``lines``, ``tokens``, ``names``), ``names_ms`` (the names'
+    download and decoding) and ``remap_ms``."""
+    import time
+
+    import torch
+
+    from .engine import _edgelist_names
+
+    lib = _lib.load()
+    if int(lib.pw_device_count()) <= 0:
+        raise _lib.PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+    dev = torch.device("cuda", int(device or 0))
+    t0 = time.perf_counter()
+    h, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwCorpusDevStats()
+    rc = lib.pw_corpus_read_device(os.fsencode(path), dev.index, C.byref(h), C.byref(ids), C.byref(st))
+    if rc in (_lib.EDGELIST_NEEDS_HOST_READER, _lib.EDGELIST_IO):
+        mat, names = read_walks(path, node_ids)   # (a file that cannot be opened raises here what open() raises)
+        d_walks = torch.from_numpy(mat.view(np.int32)).to(dev)
+        read_walks_device.last_stats = {"reader": "host", "call_ms": (time.perf_counter() - t0) * 1e3, "lines": mat.shape[0],
+                                        "tokens": int(mat[:, -1].sum()), "names": len(names)}
+        return d_walks, names
+    _lib.check(rc)
+    try:
+        stats = st.as_dict()
+        shape = [C.c_uint64(0) for _ in range(3)]
+        _lib.check(lib.pw_corpus_dev_shape(h, *[C.byref(s) for s in shape]))
+        n_rows, width, _ = (int(s.value) for s in shape)
+        d_walks = torch.empty((n_rows, width), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(lib.pw_corpus_dev_fill(h, C.c_void_p(d_walks.data_ptr())))
+        t1 = time.perf_counter()
+        names = _edgelist_names(lib, ids, stats["names"])
+        stats["names_ms"] = (time.perf_counter() - t1) * 1e3
+    finally:
+        lib.pw_corpus_dev_destroy(h)
+        lib.pw_edgelist_ids_destroy(ids)
+    t1 = time.perf_counter()
+    if node_ids is not None:
+        d_walks, names = _remap_device(d_walks, names, node_ids)
+    stats["remap_ms"] = (time.perf_counter() - t1) * 1e3
+    stats["reader"] = "device"
+    stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+    read_walks_device.last_stats = stats
+    return d_walks, names
+
+
+def _remap_device(d_walks, names, node_ids):
+    """First-appearance numbers -> positions in ``node_ids``: a table over the names, gathered on the device."""
+    import torch
+
+    wanted = [str(x) for x in node_ids]
+    index = {}
+    for i, name in enumerate(wanted):
+        index.setdefault(name, i)
+    cells = d_walks[:, :-1]
+    in_row = torch.arange(cells.shape[1], device=d_walks.device) < d_walks[:, -1:]   # the cells in front of each row's length
+    unknown = next((k for k, name in enumerate(names) if name not in index), None)   # the first in the file: names are in that order
+    if unknown is not None:
+        line = int(((cells == unknown) & in_row).any(dim=1).nonzero()[0]) + 1
+        raise _unknown_token(names[unknown], line, len(wanted))
+    if names:
+        table = torch.tensor([index[name] for name in names], dtype=torch.int32, device=d_walks.device)
+        mapped = torch.where(in_row, table[cells.long()], torch.zeros((), dtype=torch.int32, device=d_walks.device))
+        d_walks = torch.cat([mapped, d_walks[:, -1:]], dim=1).contiguous()
+    return d_walks, wanted
+
+
+read_walks_device.last_stats = None

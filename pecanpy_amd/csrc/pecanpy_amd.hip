@@ -40,6 +40,7 @@
 #include "sgns.hip.h"
 #include "coo_csr.hip.h"
 #include "edgelist_dev.hip.h"
+#include "corpus_dev.hip.h"
 #include "dense_build.hip.h"
 #include "emb_text.hip.h"
 #include "walk_text.hip.h"
@@ -1235,6 +1236,57 @@ PW_EXPORT int pw_edgelist_ids_export(const pw_edgelist_ids *ids, uint64_t *id_of
     return PW_OK;
 }
 
+// The file at `path` -> d_text (n + 1 bytes of device memory, the last one unused) and res->text (the host's copy: the names are
+// sliced from it), in chunks through two pinned buffers.  PW_EDGELIST_OK; PW_EDGELIST_NEEDS_HOST_READER (an empty file, one of
+// 4 GiB or more, memory that does not fit); PW_EDGELIST_IO; PW_ERR_HIP.  Nothing is in flight when it returns.
+static int upload_text_file(const char *path, int device, DevBuf<char> &d_text, pw_edgelist_ids *res, uint64_t *n_out) {
+    // the pinned buffers in front of `io`: they go after its destructor has waited for the stream
+    PinnedBuf<char> pinned[2];
+    struct Io {
+        FILE *file = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        bool queued = false;
+        ~Io() {
+            if (queued) (void)hipStreamSynchronize(nullptr);
+            if (file) (void)fclose(file);
+            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        }
+    } io;
+    io.file = fopen(path, "rb");
+    if (!io.file) return PW_EDGELIST_IO;
+    uint64_t n = 0;
+    if (fseek(io.file, 0, SEEK_END) != 0) return PW_EDGELIST_IO;
+    {
+        const long sz = ftell(io.file);
+        if (sz < 0) return PW_EDGELIST_IO;
+        n = (uint64_t)sz;
+        rewind(io.file);
+    }
+    if (n == 0 || n >= (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;   // (an empty file has nothing to put on the device)
+    HIP_TRY(hipSetDevice(device));
+    res->text.reset(new (std::nothrow) char[n]);
+    if (!res->text) return PW_EDGELIST_NEEDS_HOST_READER;
+    char *const h_text = res->text.get();
+    constexpr uint64_t CHUNK = 16ull << 20;
+    if (d_text.alloc(n + 1) != hipSuccess) return PW_EDGELIST_NEEDS_HOST_READER;
+    for (auto &pb : pinned) if (pb.alloc(std::min(CHUNK, n)) != hipSuccess) return PW_EDGELIST_NEEDS_HOST_READER;
+    for (auto &e : io.ev) HIP_TRY(hipEventCreate(&e));
+    io.queued = true;
+    uint64_t at = 0;
+    for (int s = 0; at < n; s ^= 1) {
+        const uint64_t want = std::min(CHUNK, n - at);
+        if (at >= 2 * CHUNK) HIP_TRY(hipEventSynchronize(io.ev[s]));   // this buffer's last copy has left it
+        if (fread(pinned[s].p, 1, want, io.file) != want) return PW_EDGELIST_IO;   // (short: an error, or the file changed)
+        HIP_TRY(hipMemcpyAsync(d_text.p + at, pinned[s].p, want, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipEventRecord(io.ev[s], nullptr));
+        memcpy(h_text + at, pinned[s].p, want);
+        at += want;
+    }
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    *n_out = n;
+    return PW_EDGELIST_OK;
+}
+
 PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int directed, const char *delimiter, int device, uint32_t flags,
                                          pw_csr_dev **csr, pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
     using clk = std::chrono::steady_clock;
@@ -1254,21 +1306,16 @@ PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int dir
 
     // every buffer of the call, in front of `mem`: they go after its destructor has waited for the stream
     DevBuf<char> d_text, d_delim;
-    PinnedBuf<char> pinned[2];
     DevBuf<uint32_t> d_flags, d_segcnt, d_tmp, d_starts, d_table, d_slot, d_first, d_idoff, d_idlen;
     DevBuf<pw::ElToken> d_tok;
     DevBuf<double> d_w64;
     DevBuf<int64_t> d_src, d_dst;
-    // ... and beside them: the file, the two copy events, the id handle until it is handed out
+    // ... and beside them the id handle until it is handed out
     struct Mem {
-        FILE *file = nullptr;
-        hipEvent_t ev[2] = {nullptr, nullptr};
         pw_edgelist_ids *res = nullptr;
         bool queued = false;
         ~Mem() {
             if (queued) (void)hipStreamSynchronize(nullptr);
-            if (file) (void)fclose(file);
-            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
             delete res;
         }
     } mem;
@@ -1276,45 +1323,17 @@ PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int dir
     bool no_room = false;
     auto alloc = [&](auto &buf, uint64_t n) { if (!no_room && buf.alloc(n) != hipSuccess) no_room = true; };
 
-    // ---- upload: the file in chunks through two pinned buffers into one device buffer; the host keeps the bytes for the names
+    // ---- upload (upload_text_file); the host keeps the bytes for the names
     auto t0 = clk::now();
-    mem.file = fopen(path, "rb");
-    if (!mem.file) return PW_EDGELIST_IO;
-    uint64_t n = 0;
-    if (fseek(mem.file, 0, SEEK_END) != 0) return PW_EDGELIST_IO;
-    {
-        const long sz = ftell(mem.file);
-        if (sz < 0) return PW_EDGELIST_IO;
-        n = (uint64_t)sz;
-        rewind(mem.file);
-    }
-    if (n == 0 || n >= (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;   // (an empty file has no graph to put on the device)
-    HIP_TRY(hipSetDevice(device));
     mem.res = new (std::nothrow) pw_edgelist_ids();
-    if (mem.res) mem.res->text.reset(new (std::nothrow) char[n]);
-    if (!mem.res || !mem.res->text) return PW_EDGELIST_NEEDS_HOST_READER;
-    char *const h_text = mem.res->text.get();
-    constexpr uint64_t CHUNK = 16ull << 20;
-    alloc(d_text, n + 1);
-    for (auto &pb : pinned) if (!no_room && pb.alloc(std::min(CHUNK, n)) != hipSuccess) no_room = true;
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
-    mem.queued = true;
+    if (!mem.res) return PW_EDGELIST_NEEDS_HOST_READER;
+    uint64_t n = 0;
     {
-        uint64_t at = 0;
-        for (int s = 0; at < n; s ^= 1) {
-            const uint64_t want = std::min(CHUNK, n - at);
-            if (at >= 2 * CHUNK) HIP_TRY(hipEventSynchronize(mem.ev[s]));   // this buffer's last copy has left it
-            if (fread(pinned[s].p, 1, want, mem.file) != want) return PW_EDGELIST_IO;   // (short: an error, or the file changed)
-            HIP_TRY(hipMemcpyAsync(d_text.p + at, pinned[s].p, want, hipMemcpyHostToDevice, nullptr));
-            HIP_TRY(hipEventRecord(mem.ev[s], nullptr));
-            memcpy(h_text + at, pinned[s].p, want);
-            at += want;
-        }
-        (void)fclose(mem.file);
-        mem.file = nullptr;
-        HIP_TRY(hipStreamSynchronize(nullptr));
+        const int rc = upload_text_file(path, device, d_text, mem.res, &n);
+        if (rc != PW_EDGELIST_OK) return rc;
     }
+    mem.queued = true;
+    char *const h_text = mem.res->text.get();
     const double upload_ms = ms_since(t0);
 
     // ---- 1. byte classes and line starts
@@ -1428,6 +1447,197 @@ PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int dir
 PW_EXPORT int pw_edgelist_read_device(const char *path, int weighted, int directed, const char *delimiter, int device, pw_csr_dev **csr,
                                       pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
     return pw_edgelist_read_device_ex(path, weighted, directed, delimiter, device, 0u, csr, ids, stats);
+}
+
+// ---- a walk corpus file read in device memory (csrc/corpus_dev.hip.h) ------------------------------------------------------------
+struct pw_corpus_dev {
+    int device = 0;
+    uint64_t n_rows = 0, width = 0, n_tokens = 0;
+    DevBuf<uint32_t> d_mat;   // uint32[n_rows, width]
+};
+
+PW_EXPORT void pw_corpus_dev_destroy(pw_corpus_dev *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    delete c;
+}
+
+PW_EXPORT int pw_corpus_dev_shape(const pw_corpus_dev *c, uint64_t *n_rows, uint64_t *width, uint64_t *n_tokens) {
+    if (!c) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_rows) *n_rows = c->n_rows;
+    if (width) *width = c->width;
+    if (n_tokens) *n_tokens = c->n_tokens;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_corpus_dev_fill(const pw_corpus_dev *c, uint32_t *d_out) {
+    if (!c || !d_out) return fail(PW_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(d_out, c->d_mat.p, sizeof(uint32_t) * c->n_rows * c->width, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return PW_OK;
+}
+
+PW_EXPORT int pw_corpus_dev_export(const pw_corpus_dev *c, uint32_t *h_out) {
+    if (!c || !h_out) return fail(PW_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(h_out, c->d_mat.p, sizeof(uint32_t) * c->n_rows * c->width, hipMemcpyDeviceToHost));
+    return PW_OK;
+}
+
+PW_EXPORT int pw_corpus_read_device(const char *path, int device, pw_corpus_dev **out, pw_edgelist_ids **ids, pw_corpus_dev_stats *stats) {
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    if (!path || !out || !ids) return fail(PW_ERR_INVALID, "null pointer");
+    *out = nullptr;
+    *ids = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int n_dev = pw_device_count();
+    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+
+    // every buffer of the call, in front of `mem`: they go after its destructor has waited for the stream
+    DevBuf<char> d_text;
+    DevBuf<uint32_t> d_flags, d_segnl, d_segts, d_tmp, d_tokoff, d_tokline, d_linefirst, d_table, d_slot, d_first, d_nameoff, d_namelen;
+    DevBuf<pw::ElToken> d_tok;
+    // ... and beside them the two handles until they are handed out
+    struct Mem {
+        pw_edgelist_ids *res = nullptr;
+        pw_corpus_dev *mat = nullptr;
+        bool queued = false;
+        ~Mem() {
+            if (queued) (void)hipStreamSynchronize(nullptr);
+            delete res;
+            delete mat;
+        }
+    } mem;
+    // scratch that does not fit is no error: the host reader still works
+    bool no_room = false;
+    auto alloc = [&](auto &buf, uint64_t n) { if (!no_room && buf.alloc(n) != hipSuccess) no_room = true; };
+
+    // ---- upload (upload_text_file); the host keeps the bytes for the names
+    auto t0 = clk::now();
+    mem.res = new (std::nothrow) pw_edgelist_ids();
+    mem.mat = new (std::nothrow) pw_corpus_dev();
+    if (!mem.res || !mem.mat) return PW_EDGELIST_NEEDS_HOST_READER;
+    uint64_t n = 0;
+    {
+        const int rc = upload_text_file(path, device, d_text, mem.res, &n);
+        if (rc != PW_EDGELIST_OK) return rc;
+    }
+    mem.queued = true;
+    mem.mat->device = device;
+    const double upload_ms = ms_since(t0);
+
+    // ---- 1. + 2. byte classes; newlines and token starts counted, scanned and placed; the width
+    t0 = clk::now();
+    const uint64_t n_seg = (n + pw::CP_SEG - 1) / pw::CP_SEG;
+    const unsigned seg_grid = (unsigned)((n_seg + 3) / 4);
+    alloc(d_flags, 2);   // [0] the flags, [1] the most tokens in a line
+    alloc(d_segnl, n_seg + 1);
+    alloc(d_segts, n_seg + 1);
+    alloc(d_tmp, pw::scan_scratch_elems(n_seg + 1));
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    HIP_TRY(hipMemsetAsync(d_flags.p, 0, 2 * sizeof(uint32_t), nullptr));
+    HIP_TRY(hipMemsetAsync(d_segnl.p + n_seg, 0, sizeof(uint32_t), nullptr));   // (the scans' last inputs: their outputs are the totals)
+    HIP_TRY(hipMemsetAsync(d_segts.p + n_seg, 0, sizeof(uint32_t), nullptr));
+    hipLaunchKernelGGL(pw::cp_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, d_segnl.p, d_segts.p, d_flags.p);
+    pw::exclusive_scan_inplace(nullptr, d_segnl.p, n_seg + 1, d_tmp.p);
+    pw::exclusive_scan_inplace(nullptr, d_segts.p, n_seg + 1, d_tmp.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t h_flags = 0, n_newlines = 0, n_tok32 = 0;
+    HIP_TRY(hipMemcpy(&n_newlines, d_segnl.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n_tok32, d_segts.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_flags) return PW_EDGELIST_NEEDS_HOST_READER;
+    const uint64_t n_tok = n_tok32;   // (at most half the bytes and one: below 2^31 + 1)
+    const uint64_t n_lines = (uint64_t)n_newlines + (mem.res->text[n - 1] != '\n' ? 1 : 0);   // a last line without a newline counts
+    alloc(d_tokoff, n_tok);
+    alloc(d_tokline, n_tok);
+    alloc(d_linefirst, (uint64_t)n_newlines + 2);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    hipLaunchKernelGGL(pw::cp_place_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, (const uint32_t *)d_segnl.p,
+                       (const uint32_t *)d_segts.p, (uint64_t)n_newlines, n_tok, d_tokoff.p, d_tokline.p, d_linefirst.p);
+    const unsigned line_grid = (unsigned)((n_lines + 255) / 256), tok_grid = (unsigned)((n_tok + 256) / 256);
+    hipLaunchKernelGGL(pw::cp_width_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const uint32_t *)d_linefirst.p, n_lines, d_flags.p + 1);
+    HIP_TRY(hipGetLastError());
+    uint32_t max_len = 0;
+    HIP_TRY(hipMemcpy(&max_len, d_flags.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (max_len > n_tok) return fail(PW_ERR_HIP, "pw_corpus_read_device: line length out of range (internal error)");
+    const uint64_t width = (uint64_t)(max_len ? max_len : 1u) + 1;
+    d_segnl.release();
+    d_segts.release();
+    const double scan_ms = ms_since(t0);
+
+    // ---- 3. token records, first-appearance numbering (the edge-list reader's id table)
+    t0 = clk::now();
+    uint32_t n_names = 0;
+    if (n_tok) {
+        uint64_t table_size = 1024;
+        while (table_size < 2 * n_tok) table_size <<= 1;
+        alloc(d_tok, n_tok);
+        alloc(d_table, table_size);
+        alloc(d_slot, n_tok);
+        alloc(d_first, n_tok + 1);
+        alloc(d_tmp, pw::scan_scratch_elems(n_tok + 1));
+        if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+        HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(uint32_t) * table_size, nullptr));
+        hipLaunchKernelGGL(pw::cp_tokens_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, (const uint32_t *)d_tokoff.p, n_tok,
+                           d_tok.p);
+        hipLaunchKernelGGL(pw::el_insert_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, (const pw::ElToken *)d_tok.p, n_tok,
+                           d_table.p, (uint32_t)(table_size - 1), d_slot.p);
+        hipLaunchKernelGGL(pw::el_first_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const uint32_t *)d_table.p, (const uint32_t *)d_slot.p, n_tok,
+                           d_first.p);
+        pw::exclusive_scan_inplace(nullptr, d_first.p, n_tok + 1, d_tmp.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&n_names, d_first.p + n_tok, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (n_names == 0 || n_names > n_tok) return fail(PW_ERR_HIP, "pw_corpus_read_device: name count out of range (internal error)");
+    }
+    const double tokens_ms = ms_since(t0);
+
+    // ---- 4. the matrix and the names' spans
+    t0 = clk::now();
+    if (n_lines * width > (1ull << 40)) return PW_EDGELIST_NEEDS_HOST_READER;   // (4 TiB of cells: no device holds them)
+    alloc(mem.mat->d_mat, n_lines * width);
+    alloc(d_nameoff, n_names);
+    alloc(d_namelen, n_names);
+    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    HIP_TRY(hipMemsetAsync(mem.mat->d_mat.p, 0, sizeof(uint32_t) * n_lines * width, nullptr));
+    if (n_tok)
+        hipLaunchKernelGGL(pw::cp_fill_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const pw::ElToken *)d_tok.p, (const uint32_t *)d_table.p,
+                           (const uint32_t *)d_slot.p, (const uint32_t *)d_first.p, (const uint32_t *)d_tokline.p, (const uint32_t *)d_linefirst.p, n_tok,
+                           (uint64_t)n_names, n_lines, (uint32_t)width, mem.mat->d_mat.p, d_nameoff.p, d_namelen.p, d_flags.p);
+    hipLaunchKernelGGL(pw::cp_lengths_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const uint32_t *)d_linefirst.p, n_lines, (uint32_t)width,
+                       mem.mat->d_mat.p);
+    HIP_TRY(hipGetLastError());
+    try {
+        mem.res->off.resize(n_names);
+        mem.res->len.resize(n_names);
+    } catch (const std::bad_alloc &) {
+        return PW_EDGELIST_NEEDS_HOST_READER;
+    }
+    if (n_names) {
+        HIP_TRY(hipMemcpy(mem.res->off.data(), d_nameoff.p, sizeof(uint32_t) * n_names, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(mem.res->len.data(), d_namelen.p, sizeof(uint32_t) * n_names, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_flags) return fail(PW_ERR_HIP, "pw_corpus_read_device: the id table is inconsistent (internal error)");
+    for (uint32_t v = 0; v < n_names; v++) {
+        if ((uint64_t)mem.res->off[v] + mem.res->len[v] > n) return fail(PW_ERR_HIP, "pw_corpus_read_device: a name outside the text (internal error)");
+        mem.res->id_bytes += mem.res->len[v];
+    }
+    mem.mat->n_rows = n_lines;
+    mem.mat->width = width;
+    mem.mat->n_tokens = n_tok;
+    if (stats) {
+        stats->upload_ms = upload_ms; stats->scan_ms = scan_ms; stats->tokens_ms = tokens_ms; stats->fill_ms = ms_since(t0);
+        stats->file_bytes = n; stats->lines = n_lines; stats->tokens = n_tok; stats->names = n_names;
+    }
+    *out = mem.mat;
+    *ids = mem.res;
+    mem.mat = nullptr;
+    mem.res = nullptr;
+    return PW_EDGELIST_OK;
 }
 
 // Host builds of the reader's two text routines (csrc/edgelist_dev.hip.h), for tests without a GPU.

@@ -8,7 +8,8 @@ csrc/emb_text.hip.h: exact ``%.6f`` on the GPU, only the text crosses to the hos
 ``train_sgns_device`` runs word2vec's skip-gram-with-negative-sampling update as a HIP kernel (``pw_sgns_train_device``,
 csrc/sgns.hip.h: a wavefront owns a walk) on the ``[n_jobs, L+2]`` matrix where ``WalkEngine.simulate_device`` leaves it, in
 device memory -- no host copy of the matrix and no ``List[List[str]]`` corpus in between; ``train_sgns`` is the same
-trainer for a matrix that lives on the host (upload, same kernel, download).  Same model and defaults as gensim's
+trainer for a matrix that lives on the host (upload, same kernel, download), ``train_sgns_file`` for a walk corpus file
+(``corpus.read_walks_device``: read and numbered in device memory).  Same model and defaults as gensim's
 (negative=5, ns_exponent=0.75, sample=1e-3, alpha 0.025 -> 1e-4, shrunk windows over the subsampled walk); not
 bit-comparable with gensim's own random streams -- the deterministic single-wavefront mode is checked against a sequential
 CPU restatement of the algorithm instead (tests/test_gpu_sgns.py, tests/test_gpu_embed_device.py).
@@ -19,7 +20,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["train_sgns", "train_sgns_device", "save_word2vec_format", "save_word2vec_format_device"]
+__all__ = ["train_sgns", "train_sgns_device", "train_sgns_file", "save_word2vec_format", "save_word2vec_format_device"]
 
 
 def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
@@ -73,6 +74,43 @@ def train_sgns_device(d_walks, num_nodes, dim=128, window=10, epochs=1, negative
 
 
 train_sgns_device.last_stats = None
+
+MAX_WALK_LENGTH = 8191   # pw_sgns_train_device: a wavefront holds its walk in LDS (walk_length < 8192)
+
+
+def train_sgns_file(path, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3, seed=None,
+                    workers=0, device=0):
+    """``train_sgns_device`` on a walk corpus FILE (what ``pecanpy --task walks`` / ``Base.walks_to_file`` write, or any
+    trainer's ``LineSentence`` input): ``corpus.read_walks_device`` reads it into device memory, the names numbered by first
+    appearance, and the trainer runs on that matrix with ``num_nodes = len(names)``.  Returns ``(names, d_vectors)``:
+    ``d_vectors[i]`` is the vector of ``names[i]``, a ``float32[len(names), dim]`` tensor on ``device``.  A corpus without
+    lines is a ``ValueError`` before any device work; so is a line of more than ``MAX_WALK_LENGTH + 1`` tokens, before the
+    trainer starts.  ``train_sgns_file.last_stats``: ``"read"`` (``read_walks_device.last_stats``) and ``"train"``
+    (``train_sgns_device.last_stats``)."""
+    import os
+
+    from .corpus import read_walks_device
+
+    if os.path.getsize(path) == 0:
+        raise ValueError(f"{path}: a corpus without lines has nothing to train on")
+    d_walks, names = read_walks_device(path, device=device)
+    walk_length = d_walks.shape[1] - 2
+    if walk_length > MAX_WALK_LENGTH:
+        raise ValueError(f"{path}: a line of {walk_length + 1} tokens exceeds the trainer's walk length limit "
+                         f"(at most {MAX_WALK_LENGTH + 1} tokens per line)")
+    if not names:
+        raise ValueError(f"{path}: a corpus without tokens has nothing to train on")
+    if walk_length < 1:   # (lines of one token: no pairs; the trainer's matrix form needs walk_length >= 1)
+        import torch
+
+        d_walks = torch.cat([d_walks[:, :1], torch.zeros_like(d_walks[:, :1]), d_walks[:, 1:]], dim=1).contiguous()
+    d_vectors = train_sgns_device(d_walks, len(names), dim=dim, window=window, epochs=epochs, negative=negative, alpha=alpha,
+                                  min_alpha=min_alpha, sample=sample, seed=seed, workers=workers)
+    train_sgns_file.last_stats = {"read": read_walks_device.last_stats, "train": train_sgns_device.last_stats}
+    return names, d_vectors
+
+
+train_sgns_file.last_stats = None
 
 
 _WRITE_ROWS = 1 << 14   # rows formatted per write
