@@ -293,14 +293,15 @@ def sgns_train(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5,
 
     ``order``: a permutation of the walk indices, the visiting order inside every epoch (default: sentence order); the
     hashes and the learning-rate schedule keep using each walk's own index.  ``return_counts=True`` appends
-    ``(kept_occurrences, trained_pairs)``, summed over the epochs, defined as the trainer's two counters."""
+    ``(kept_occurrences, trained_pairs)``, summed over the epochs, defined as the trainer's two counters.
+    ``sgns_train.last_saturated``: how often this call took the sigmoid's saturated branches, ``(dot > 6, dot < -6)``."""
     global _SGNS
     if _SGNS is None:
         path = os.path.join(_HERE, "libsgns_ref.so")
         if not os.path.exists(path):
             build()
         _SGNS = C.CDLL(path)
-        if not hasattr(_SGNS, "sgns_ref_train_ex"):   # a library left from before the entry point existed: make renews it
+        if not hasattr(_SGNS, "sgns_ref_train_ex") or not hasattr(_SGNS, "sgns_ref_saturated"):   # a library left from before the entry point existed: make renews it
             build()
             _SGNS = C.CDLL(path)
     mat = np.ascontiguousarray(walk_matrix, dtype=np.uint32)
@@ -320,6 +321,12 @@ def sgns_train(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5,
                                  order.ctypes.data_as(C.c_void_p) if order is not None else None)
     if rc != 0:
         raise ValueError("sgns_ref_train: malformed walk matrix or order")
+    sat = (C.c_uint64 * 2)(0, 0)
+    _SGNS.sgns_ref_saturated(sat)
+    sgns_train.last_saturated = (int(sat[0]), int(sat[1]))
     if return_counts:
         return out, float(loss.value), (int(counts[0]), int(counts[1]))
     return out, float(loss.value)
+
+
+sgns_train.last_saturated = None

@@ -35,6 +35,11 @@ static uint64_t mix64(uint64_t x) {
 }
 static float u24(uint64_t x) { return (float)(x >> 40) * (1.0f / 16777216.0f); }
 
+/* how often the last call of sgns_ref_train_ex took a saturated branch of the sigmoid: [0] dot > 6, [1] dot < -6 (what a
+ * test needs in order to know that its case reaches those branches, and that another reference takes them as often) */
+static uint64_t saturated[2];
+EXPORT void sgns_ref_saturated(uint64_t out[2]) { out[0] = saturated[0]; out[1] = saturated[1]; }
+
 /* vectors: float32[n_nodes * dim] (syn0 after training); loss (may be NULL): mean SGNS loss of the pairs trained in the
  * last epoch, evaluated before each update.
  * counts (may be NULL): [0] occurrences that survived the subsampling, [1] (centre, context) pairs trained, both summed over
@@ -47,6 +52,7 @@ EXPORT int sgns_ref_train_ex(const uint32_t *walks, uint64_t n_walks, uint32_t L
                              uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha, float sample,
                              uint32_t seed, float *vectors, double *loss, uint64_t *counts, const uint64_t *order) {
     const uint32_t W = L + 2;
+    saturated[0] = saturated[1] = 0;
     const uint64_t n_items = n_walks * (uint64_t)(L + 1);
     uint64_t *cnt = calloc(n_nodes, sizeof(uint64_t));
     float *syn1 = calloc((size_t)n_nodes * dim, sizeof(float));
@@ -161,6 +167,8 @@ EXPORT int sgns_ref_train_ex(const uint32_t *walks, uint64_t n_walks, uint32_t L
                             memcpy(part, tmp, sizeof(part));
                         }
                         const float dot = part[0];
+                        saturated[0] += dot > 6.0f;
+                        saturated[1] += dot < -6.0f;
                         const float sig = dot > 6.0f ? 1.0f : (dot < -6.0f ? 0.0f : 1.0f / (1.0f + expf(-dot)));
                         if (last_epoch && loss) {
                             const double s = 1.0 / (1.0 + exp(-(double)dot));

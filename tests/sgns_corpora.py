@@ -116,6 +116,43 @@ def close_to_oracle(got, want):
     assert err <= bound, (err, bound)
 
 
+def run(d_walks, n, **kw):
+    """``train_sgns_device`` as ``(vectors on the host, what the call did)``."""
+    from pecanpy_amd.embed import train_sgns_device
+
+    got = train_sgns_device(d_walks, n, **kw).cpu().numpy()
+    return got, dict(train_sgns_device.last_stats)
+
+
+def held_to_one_wavefront_and_the_restatement(mat, n, kw, workers, wavefronts=None):
+    """What a run of several wavefronts on a component corpus with ``negative=0`` is held to (tests/test_gpu_sgns_waves.py;
+    tests/test_gpu_sgns_shapes.py at a wide instance): (a) the wavefront count, (b) bit-equal to ``workers=1``, (c) the
+    restatement within the one-wavefront bound, (d) its counters, (e) a second call bit-equal.  ``wavefronts=None``: any count
+    above one."""
+    from oracle import pyoracle as orc
+
+    d_walks = on_device(mat)
+    want, _, counts = orc.sgns_train(mat, n, return_counts=True, **kw)
+    got, st = run(d_walks, n, workers=workers, **kw)
+    print(f"wavefronts {st['wavefronts']}, kept {st['kept_occurrences']}, pairs {st['trained_pairs']} (restatement {counts})")
+    if wavefronts is None:
+        assert st["wavefronts"] > 1
+    else:
+        assert st["wavefronts"] == wavefronts                                                     # (a)
+    one, st1 = run(d_walks, n, workers=1, **kw)
+    assert st1["wavefronts"] == 1
+    differing = np.flatnonzero((got != one).any(axis=1))
+    assert np.array_equal(got, one), f"rows {differing[:8]} of {differing.size} differ from workers=1"   # (b)
+    close_to_oracle(got, want)                                                                    # (c)
+    assert (st["kept_occurrences"], st["trained_pairs"]) == counts                                # (d)
+    assert (st1["kept_occurrences"], st1["trained_pairs"]) == counts
+    again, st2 = run(d_walks, n, workers=workers, **kw)
+    assert np.array_equal(again, got)                                                             # (e)
+    assert (st2["kept_occurrences"], st2["trained_pairs"], st2["wavefronts"]) == counts + (st["wavefronts"],)
+    assert np.array_equal(d_walks.cpu().numpy().view(np.uint32), mat)                             # read, never written
+    return got
+
+
 # ---- the two counters, evaluated independently of oracle/sgns_ref.c ---------------------------------------------------------
 _M1, _M2, _GOLD = np.uint64(0xff51afd7ed558ccd), np.uint64(0xc4ceb9fe1a85ec53), np.uint64(0x9E3779B97F4A7C15)
 

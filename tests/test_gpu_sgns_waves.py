@@ -17,38 +17,10 @@ import pytest
 from oracle import pyoracle as orc
 from pecanpy_amd.embed import train_sgns, train_sgns_device
 from pecanpy_amd.engine import PwError
-from sgns_corpora import SEED, WAVE_CASES, case_corpus, case_kw, close_to_oracle, component_corpus, karate_walks, on_device
+from sgns_corpora import (SEED, WAVE_CASES, case_corpus, case_kw, close_to_oracle, component_corpus,
+                          held_to_one_wavefront_and_the_restatement, karate_walks, on_device, run)
 
 pytestmark = pytest.mark.gpu
-
-
-def run(d_walks, n, **kw):
-    got = train_sgns_device(d_walks, n, **kw).cpu().numpy()
-    return got, dict(train_sgns_device.last_stats)
-
-
-def held_to_one_wavefront_and_the_restatement(mat, n, kw, workers, wavefronts=None):
-    """(a) .. (e) of the module's contract; ``wavefronts=None``: any count above one."""
-    d_walks = on_device(mat)
-    want, _, counts = orc.sgns_train(mat, n, return_counts=True, **kw)
-    got, st = run(d_walks, n, workers=workers, **kw)
-    print(f"wavefronts {st['wavefronts']}, kept {st['kept_occurrences']}, pairs {st['trained_pairs']} (restatement {counts})")
-    if wavefronts is None:
-        assert st["wavefronts"] > 1
-    else:
-        assert st["wavefronts"] == wavefronts                                                     # (a)
-    one, st1 = run(d_walks, n, workers=1, **kw)
-    assert st1["wavefronts"] == 1
-    differing = np.flatnonzero((got != one).any(axis=1))
-    assert np.array_equal(got, one), f"rows {differing[:8]} of {differing.size} differ from workers=1"   # (b)
-    close_to_oracle(got, want)                                                                    # (c)
-    assert (st["kept_occurrences"], st["trained_pairs"]) == counts                                # (d)
-    assert (st1["kept_occurrences"], st1["trained_pairs"]) == counts
-    again, st2 = run(d_walks, n, workers=workers, **kw)
-    assert np.array_equal(again, got)                                                             # (e)
-    assert (st2["kept_occurrences"], st2["trained_pairs"], st2["wavefronts"]) == counts + (st["wavefronts"],)
-    assert np.array_equal(d_walks.cpu().numpy().view(np.uint32), mat)                             # read, never written
-    return got
 
 
 @pytest.mark.parametrize("case", WAVE_CASES, ids=[c["id"] for c in WAVE_CASES])
