@@ -369,6 +369,55 @@ int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, 
                          uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
                          float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats);
 
+/* ---- the trainer as a session: epochs in slices, a loss, both matrices (csrc/sgns.hip.h) ------------------------------------
+ * pw_sgns_train_device is create -> run(epochs) -> vectors_get(0) -> destroy on this handle: one preparation path.
+ *   pw_sgns_create_device  the preparation of pw_sgns_train_device -- the same checks and error texts, the word counts, the
+ *                          noise table, the keep probabilities, the seeded syn0, a zeroed syn1, the wavefront count from
+ *                          `workers` -- and no training.  The handle owns syn0, syn1 and the tables.  d_walks is BORROWED, not
+ *                          copied: the matrix must stay allocated and unchanged until pw_sgns_destroy.  `epochs` is the length of
+ *                          the learning-rate schedule.  flags: PW_SGNS_LOSS = every launch also computes the epoch's loss.
+ *   pw_sgns_run            the next n_epochs epochs of the schedule, one launch each; returns when they are done.  per_epoch
+ *                          (n_epochs cells, may be NULL): kept_occurrences and trained_pairs of that epoch; with PW_SGNS_LOSS
+ *                          loss = the sum over its trained evaluations of softplus(-dot) for the centre and softplus(dot) for a
+ *                          negative (gensim's skip-gram / negative-sampling loss), in float64 from the float32 dot product the
+ *                          update used, taken before the update; evaluations = their number.  Both 0 without the flag.  The sum
+ *                          is made without floating-point atomics, in an order fixed by the number of walks: per-walk sums in
+ *                          evaluation order, then blocks of 4096 walks, then the block sums.  With workers = 1 it is a function
+ *                          of the seed.  stats (may be NULL): vocab_ms / init_ms of the create call, train_ms and the counters of
+ *                          this run.  More epochs than the schedule has left: PW_ERR_INVALID before any launch.
+ *   pw_sgns_get_state / pw_sgns_set_state
+ *                          epoch: the global epoch index, which every hash of (seed, epoch, walk, position) uses; pw_sgns_run
+ *                          only ever grows it.  sched_pos / sched_total: epochs of the schedule done / in all; the learning rate
+ *                          of an item is alpha - (alpha - min_alpha) * (items before it in the schedule / items of the schedule),
+ *                          at least min_alpha.  set_state restores a checkpoint (with pw_sgns_vectors_set for both matrices)
+ *                          and starts a new schedule on the trained vectors (sched_pos = 0, another sched_total / alpha /
+ *                          min_alpha; epoch left as it is).  sched_total = 0 or sched_pos > sched_total: PW_ERR_INVALID.
+ *   pw_sgns_vectors_get / pw_sgns_vectors_set
+ *                          a device-to-device copy of syn0 (which = 0: the input vectors, the embedding) or syn1 (which = 1: the
+ *                          context vectors, gensim's syn1neg) out of / into the handle; d_ptr = float32[n_nodes, dim],
+ *                          contiguous, on the handle's device.
+ *   pw_sgns_destroy        frees what the handle owns; NULL is allowed. */
+enum { PW_SGNS_LOSS = 1 };
+typedef struct pw_sgns pw_sgns;
+typedef struct pw_sgns_epoch {
+    double loss;
+    uint64_t kept_occurrences, trained_pairs, evaluations;
+} pw_sgns_epoch;
+typedef struct pw_sgns_state {
+    uint64_t epoch;
+    uint64_t sched_pos, sched_total;
+    float alpha, min_alpha;
+} pw_sgns_state;
+int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                          uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                          float sample, uint32_t seed, uint32_t workers, uint32_t flags, pw_sgns **out);
+int pw_sgns_run(pw_sgns *s, uint32_t n_epochs, pw_sgns_epoch *per_epoch, pw_sgns_stats *stats);
+int pw_sgns_get_state(const pw_sgns *s, pw_sgns_state *st);
+int pw_sgns_set_state(pw_sgns *s, const pw_sgns_state *st);
+int pw_sgns_vectors_get(pw_sgns *s, int which, float *d_ptr);
+int pw_sgns_vectors_set(pw_sgns *s, int which, const float *d_ptr);
+void pw_sgns_destroy(pw_sgns *s);
+
 /* ---- the embedding file written from device memory (csrc/emb_text.hip.h) --------------------------------------------------
  * The text format of gensim's KeyedVectors.save_word2vec_format, the output of `pecanpy --output G.emb` (cli.py:323-325), made
  * on the device from the vectors where pw_sgns_train_device leaves them: only the text crosses to the host.

@@ -59,6 +59,36 @@ class PwSgnsStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwSgnsEpoch(C.Structure):
+    """``pw_sgns_epoch`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("loss", C.c_double),
+        ("kept_occurrences", C.c_uint64),
+        ("trained_pairs", C.c_uint64),
+        ("evaluations", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PwSgnsState(C.Structure):
+    """``pw_sgns_state`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("epoch", C.c_uint64),
+        ("sched_pos", C.c_uint64),
+        ("sched_total", C.c_uint64),
+        ("alpha", C.c_float),
+        ("min_alpha", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+PW_SGNS_LOSS = 1
+
+
 class PwEmbWriteStats(C.Structure):
     """``pw_emb_write_stats`` of include/pecanpy_amd.h."""
     _fields_ = [
@@ -188,6 +218,15 @@ SYMBOLS = {
                                 C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
     "pw_sgns_train_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pw_sgns_create_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.c_void_p)]),
+    "pw_sgns_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pw_sgns_get_state": (C.c_int, [C.c_void_p, C.POINTER(PwSgnsState)]),
+    "pw_sgns_set_state": (C.c_int, [C.c_void_p, C.POINTER(PwSgnsState)]),
+    "pw_sgns_vectors_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pw_sgns_vectors_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pw_sgns_destroy": (None, [C.c_void_p]),
     "pw_vectors_write_text_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,
                                                C.POINTER(PwEmbWriteStats)]),
     "pw_vectors_write_text": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,

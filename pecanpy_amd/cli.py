@@ -46,6 +46,8 @@ _OPTIONS = (
     ("--extend", dict(action="store_true", help="node2vec+ (weighted graphs)")),
     ("--gamma", dict(type=float, default=0, help="node2vec+ noisy-edge threshold = mean + gamma * std")),
     ("--random_state", dict(type=int, default=None, help="seed of the walk stream")),
+    ("--epoch_loss", dict(action="store_true", help="GPU trainer only: print the skip-gram loss of every epoch (sum and mean "
+                                                    "per evaluation); --workers 1 then also makes the trainer deterministic")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
     ("--implicit_ids", dict(action="store_true", help=".npz without IDs: use 0..N-1")),
 )
@@ -222,21 +224,47 @@ def walks_to_file(args, g):
 def embed_on_gpu(args, g):
     """Walks and skip-gram in device memory (``Base.embed_array``), the vectors written as ``learn_embeddings`` writes
     them; no ``List[List[str]]`` corpus and no index matrix on the host."""
-    vecs = g.embed_array(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
-                         window_size=args.window_size, epochs=args.epochs)
+    if args.epoch_loss:
+        with g.embed_session(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
+                             window_size=args.window_size, epochs=args.epochs, workers=_session_workers(args),
+                             compute_loss=True) as session:
+            _print_epoch_loss(session.run(args.epochs))
+            vecs = session.vectors().cpu().numpy()
+    else:
+        vecs = g.embed_array(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
+                             window_size=args.window_size, epochs=args.epochs)
     _save_vectors(args, g, vecs)
+
+
+def _session_workers(args):
+    """``--epoch_loss`` forwards ``--workers 1`` to the GPU trainer (one wavefront, deterministic); any other value keeps the
+    trainer's default."""
+    return 1 if args.cli_workers == 1 else 0
+
+
+def _print_epoch_loss(records):
+    for i, r in enumerate(records, 1):
+        mean = r["loss"] / r["evaluations"] if r["evaluations"] else 0.0
+        print(f"epoch {i}: loss {r['loss']:.6f}, mean {mean:.6f} over {r['evaluations']} evaluations")
 
 
 @Timer("read corpus + train embeddings")
 def train_from_corpus(args):
     """``--task train``: ``--input`` is a walk corpus file (what ``--task walks`` writes); it is read and numbered in device
     memory and trained there (``embed.train_sgns_file``); the vectors are written in order of first appearance."""
-    from .embed import save_word2vec_format_device, train_sgns_file
+    from .embed import save_word2vec_format_device, sgns_session_file, train_sgns_file
 
-    names, d_vectors = train_sgns_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
-                                       seed=args.random_state)
-    if args.verbose:
-        print(f"corpus read by the {train_sgns_file.last_stats['read']['reader']} reader")
+    if args.epoch_loss:
+        names, session = sgns_session_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
+                                           seed=args.random_state, workers=_session_workers(args), compute_loss=True)
+        with session:
+            _print_epoch_loss(session.run(args.epochs))
+            d_vectors = session.vectors()
+    else:
+        names, d_vectors = train_sgns_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
+                                           seed=args.random_state)
+        if args.verbose:
+            print(f"corpus read by the {train_sgns_file.last_stats['read']['reader']} reader")
     if args.output.endswith(".npz"):
         np.savez(args.output, IDs=names, data=d_vectors.cpu().numpy())
     else:
@@ -246,6 +274,7 @@ def train_from_corpus(args):
 def main(argv=None):
     """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings."""
     args = parse_args(argv)
+    args.cli_workers = args.workers   # (as given: below, 0 becomes the host's thread count for gensim)
     if args.task == "train":   # no graph: the graph flags are ignored
         train_from_corpus(args)
         return
@@ -257,6 +286,9 @@ def main(argv=None):
     elif _gpu_route():
         embed_on_gpu(args, g)
     else:
+        if args.epoch_loss:
+            warnings.warn("--epoch_loss reports the loss of the GPU trainer; gensim is importable (or the walks are dumped), "
+                          "so that route runs as without the flag and no loss is printed", stacklevel=2)
         learn_embeddings(args, simulate_walks(args, g), g)
 
 

@@ -4339,17 +4339,55 @@ PW_EXPORT int pw_probs(pw_graph *g, int mode, double p, double q, int extend, ui
 }
 
 // ---- skip-gram with negative sampling over a walk matrix (sgns.hip.h) -------------------------
-template <int PER>
+template <int PER, bool LOSS>
 static void sgns_launch(unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
-    hipLaunchKernelGGL(pw::sgns_walk_kernel<PER>, dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep);
+    hipLaunchKernelGGL((pw::sgns_walk_kernel<PER, LOSS>), dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep);
+}
+template <bool LOSS>
+static void sgns_launch_per(int per, unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
+    switch (per) {   // one instance per count of components per lane: only the last component needs a lane guard
+    case 1: sgns_launch<1, LOSS>(blocks, threads, lds, a); break;
+    case 2: sgns_launch<2, LOSS>(blocks, threads, lds, a); break;
+    case 3: sgns_launch<3, LOSS>(blocks, threads, lds, a); break;
+    case 4: sgns_launch<4, LOSS>(blocks, threads, lds, a); break;
+    case 5: sgns_launch<5, LOSS>(blocks, threads, lds, a); break;
+    case 6: sgns_launch<6, LOSS>(blocks, threads, lds, a); break;
+    case 7: sgns_launch<7, LOSS>(blocks, threads, lds, a); break;
+    default: sgns_launch<8, LOSS>(blocks, threads, lds, a); break;
+    }
 }
 
-PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
-                                   uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
-                                   float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats) {
-    if (!d_walks || !d_vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+// A trainer between launches: the two matrices, the tables of the vocabulary stage, the launch geometry, and where the run
+// stands (pw_sgns_state).  The walk matrix is the caller's.
+struct pw_sgns {
+    int device = 0;
+    pw::SgnsArgs a;                          // everything of a launch but item_base / lr_base / lr_total / alpha / min_alpha / counters
+    uint64_t n_items = 0;                    // n_walks * (walk_length + 1): the items of one epoch
+    uint32_t n_nodes = 0;
+    bool loss = false;
+    unsigned blocks = 1, threads = 64;
+    size_t lds = 0;
+    pw_sgns_state st;
+    double vocab_ms = 0, init_ms = 0;
+    DevBuf<float> syn0, syn1, keep;
+    DevBuf<uint32_t> table;
+    DevBuf<pw_sgns_epoch> epoch_out;         // what the launches of one pw_sgns_run leave, one cell per epoch
+    DevBuf<double> walk_loss, block_loss;    // PW_SGNS_LOSS: per walk, per SGNS_LOSS_CHUNK walks
+    DevBuf<unsigned long long> walk_evals, block_evals;
+    pw::Event ev0, ev1;                      // the pair around the training launches of a run
+};
+static_assert(offsetof(pw_sgns_epoch, kept_occurrences) + sizeof(uint64_t) == offsetof(pw_sgns_epoch, trained_pairs),
+              "the kernel's two counters are consecutive cells of an epoch's record");
+
+PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                                    uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                                    float sample, uint32_t seed, uint32_t workers, uint32_t flags, pw_sgns **out) {
+    if (!out) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+    *out = nullptr;
+    if (!d_walks || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
     if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
     if (window == 0 || epochs == 0) return fail(PW_ERR_INVALID, "window and epochs must be positive");
+    if (flags & ~(uint32_t)PW_SGNS_LOSS) return fail(PW_ERR_INVALID, "unknown flag");
     const uint32_t L = walk_length;
     // the survivors of a walk live in the wavefront's LDS: four wavefronts to a workgroup while that fits, else one
     const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
@@ -4362,23 +4400,18 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     const size_t vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    DevBuf<uint32_t> table_buf;
+    std::unique_ptr<pw_sgns> s(new pw_sgns);
+    s->device = device; s->n_nodes = n_nodes; s->loss = (flags & PW_SGNS_LOSS) != 0;
     DevBuf<unsigned long long> cnt_buf;
-    DevBuf<float> syn1_buf, keep_buf;
-    struct Events {   // the pair around the training launches
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
-    } evs;
-    hipEvent_t &ev0 = evs.ev0, &ev1 = evs.ev1;
     auto t_vocab = clk::now();
-    // d_cnt: [0, n_nodes) word counts, [n_nodes] first bad walk, [n_nodes + 1, n_nodes + 3) the training kernel's counters
-    hipError_t e = cnt_buf.alloc((size_t)n_nodes + 3);
-    if (e == hipSuccess) e = syn1_buf.alloc((size_t)n_nodes * dim);
+    // d_cnt: [0, n_nodes) word counts, [n_nodes] first bad walk
+    hipError_t e = cnt_buf.alloc((size_t)n_nodes + 1);
+    if (e == hipSuccess) e = s->syn0.alloc((size_t)n_nodes * dim);
+    if (e == hipSuccess) e = s->syn1.alloc((size_t)n_nodes * dim);
     unsigned long long *const d_cnt = cnt_buf.p;
-    float *const d_syn1 = syn1_buf.p;
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * ((size_t)n_nodes + 3));
+    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * (size_t)n_nodes);
     if (e == hipSuccess) e = hipMemset(d_cnt + n_nodes, 0xff, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_syn1, 0, vbytes);
+    if (e == hipSuccess) e = hipMemset(s->syn1.p, 0, vbytes);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     // vocabulary statistics (and the check that the matrix only names nodes of the vocabulary)
     const uint64_t n_items = n_walks * (uint64_t)(L + 1);
@@ -4413,16 +4446,15 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
         for (uint32_t i = 0; i < n_nodes; i++)
             keep[i] = cnt[i] ? (float)std::min(1.0, (std::sqrt((double)cnt[i] / thr) + 1.0) * thr / (double)cnt[i]) : 1.0f;
     }
-    e = table_buf.alloc(table_size);
-    uint32_t *const d_table = table_buf.p;
-    if (e == hipSuccess) e = hipMemcpy(d_table, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
+    e = s->table.alloc(table_size);
+    if (e == hipSuccess) e = hipMemcpy(s->table.p, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
     if (e == hipSuccess && sample > 0) {
-        e = keep_buf.alloc(n_nodes);
-        if (e == hipSuccess) e = hipMemcpy(keep_buf.p, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
+        e = s->keep.alloc(n_nodes);
+        if (e == hipSuccess) e = hipMemcpy(s->keep.p, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    const double vocab_ms = ms_since(t_vocab);
-    // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded; trained in place in the caller's buffer
+    s->vocab_ms = ms_since(t_vocab);
+    // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded
     auto t_init = clk::now();
     {
         std::vector<float> init((size_t)n_nodes * dim);
@@ -4431,19 +4463,28 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
             x = x * 6364136223846793005ull + 1442695040888963407ull;
             f = (((float)((x >> 40) & 0xffffff) / 16777216.0f) - 0.5f) / (float)dim;
         }
-        e = hipMemcpy(d_vectors, init.data(), vbytes, hipMemcpyHostToDevice);
+        e = hipMemcpy(s->syn0.p, init.data(), vbytes, hipMemcpyHostToDevice);
     }
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = s->ev0.create(hipEventDefault);
+    if (e == hipSuccess) e = s->ev1.create(hipEventDefault);
+    if (e == hipSuccess && s->loss) {
+        const size_t n_blocks = (size_t)((n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
+        e = s->walk_loss.alloc(n_walks);
+        if (e == hipSuccess) e = s->walk_evals.alloc(n_walks);
+        if (e == hipSuccess) e = s->block_loss.alloc(n_blocks);
+        if (e == hipSuccess) e = s->block_evals.alloc(n_blocks);
+    }
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    const double init_ms = ms_since(t_init);
-    pw::SgnsArgs a;
+    s->init_ms = ms_since(t_init);
+    pw::SgnsArgs &a = s->a;
     a.walks = d_walks; a.n_walks = n_walks; a.L = L; a.dim = dim; a.window = window; a.negative = negative;
-    a.syn0 = d_vectors; a.syn1 = d_syn1; a.table = d_table; a.table_size = table_size; a.keep = keep_buf.p;
-    a.alpha = alpha; a.min_alpha = min_alpha; a.item_total = n_items * epochs; a.seed = seed;
-    a.counters = d_cnt + n_nodes + 1;
+    a.syn0 = s->syn0.p; a.syn1 = s->syn1.p; a.table = s->table.p; a.table_size = table_size; a.keep = s->keep.p;
+    a.alpha = alpha; a.min_alpha = min_alpha; a.item_base = 0; a.lr_base = 0; a.lr_total = n_items * epochs; a.seed = seed;
+    a.counters = nullptr; a.walk_loss = s->walk_loss.p; a.walk_evals = s->walk_evals.p;
+    s->n_items = n_items;
+    s->st.epoch = 0; s->st.sched_pos = 0; s->st.sched_total = epochs; s->st.alpha = alpha; s->st.min_alpha = min_alpha;
     // concurrency.  workers == 1: ONE wavefront takes the walks in order (deterministic: the run gensim's workers=1
     // corresponds to; compared with oracle/sgns_ref.c).  workers == 0: as many wavefronts as keep hogwild collisions
     // rare -- far more wavefronts than vocabulary rows in flight would overwrite most updates of a small graph.  The rule
@@ -4459,37 +4500,110 @@ PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t
         const uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>(want_waves, (uint64_t)prop.multiProcessorCount * 32));
         blocks = (unsigned)((waves + waves_per_block - 1) / waves_per_block);
     }
-    const size_t lds = lds_wave * (threads / 64);
+    s->blocks = blocks; s->threads = threads;
+    s->lds = lds_wave * (threads / 64);
     a.n_waves = blocks * (threads / 64);
-    const int per = (int)((dim + 63) / 64);
-    (void)hipEventRecord(ev0, 0);
-    for (uint32_t ep = 0; ep < epochs; ep++) {
-        a.item_base = n_items * ep;
-        switch (per) {   // one instance per count of components per lane: only the last component needs a lane guard
-        case 1: sgns_launch<1>(blocks, threads, lds, a); break;
-        case 2: sgns_launch<2>(blocks, threads, lds, a); break;
-        case 3: sgns_launch<3>(blocks, threads, lds, a); break;
-        case 4: sgns_launch<4>(blocks, threads, lds, a); break;
-        case 5: sgns_launch<5>(blocks, threads, lds, a); break;
-        case 6: sgns_launch<6>(blocks, threads, lds, a); break;
-        case 7: sgns_launch<7>(blocks, threads, lds, a); break;
-        default: sgns_launch<8>(blocks, threads, lds, a); break;
+    *out = s.release();
+    return PW_OK;
+}
+
+PW_EXPORT int pw_sgns_run(pw_sgns *s, uint32_t n_epochs, pw_sgns_epoch *per_epoch, pw_sgns_stats *stats) {
+    if (!s) return fail(PW_ERR_INVALID, "null pointer");
+    if (n_epochs == 0) return fail(PW_ERR_INVALID, "n_epochs must be positive");
+    if (s->st.sched_pos + n_epochs > s->st.sched_total)   // (before any launch)
+        return fail(PW_ERR_INVALID, "the schedule has " + std::to_string(s->st.sched_total - s->st.sched_pos) + " of " +
+                                        std::to_string(s->st.sched_total) + " epochs left, " + std::to_string(n_epochs) + " asked for");
+    HIP_TRY(hipSetDevice(s->device));
+    hipError_t e = s->epoch_out.ensure(n_epochs);
+    if (e == hipSuccess) e = hipMemset(s->epoch_out.p, 0, sizeof(pw_sgns_epoch) * (size_t)n_epochs);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    pw::SgnsArgs a = s->a;
+    a.alpha = s->st.alpha; a.min_alpha = s->st.min_alpha; a.lr_total = s->n_items * s->st.sched_total;
+    const int per = (int)((a.dim + 63) / 64);
+    const unsigned n_blocks = (unsigned)((a.n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
+    (void)hipEventRecord(s->ev0, 0);
+    for (uint32_t i = 0; i < n_epochs; i++) {
+        a.item_base = s->n_items * (s->st.epoch + i);
+        a.lr_base = s->n_items * (s->st.sched_pos + i);
+        pw_sgns_epoch *cell = s->epoch_out.p + i;
+        a.counters = (unsigned long long *)&cell->kept_occurrences;
+        if (!s->loss) sgns_launch_per<false>(per, s->blocks, s->threads, s->lds, a);
+        else {
+            sgns_launch_per<true>(per, s->blocks, s->threads, s->lds, a);
+            hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(n_blocks), dim3(256), 0, 0, s->walk_loss.p, s->walk_evals.p, a.n_walks,
+                               (uint64_t)pw::SGNS_LOSS_CHUNK, s->block_loss.p, s->block_evals.p);
+            hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(1), dim3(256), 0, 0, s->block_loss.p, s->block_evals.p, (uint64_t)n_blocks,
+                               (uint64_t)n_blocks, &cell->loss, (unsigned long long *)&cell->evaluations);
         }
     }
-    (void)hipEventRecord(ev1, 0);
+    (void)hipEventRecord(s->ev1, 0);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
+    // (the launches were queued: whatever the outcome, the vectors have moved on by what ran)
+    s->st.epoch += n_epochs; s->st.sched_pos += n_epochs;
     float train_ms = 0;
-    unsigned long long counters[2] = {0, 0};
-    if (e == hipSuccess) e = hipEventElapsedTime(&train_ms, ev0, ev1);
-    if (e == hipSuccess) e = hipMemcpy(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost);
+    std::vector<pw_sgns_epoch> got(n_epochs);
+    if (e == hipSuccess) e = hipEventElapsedTime(&train_ms, s->ev0, s->ev1);
+    if (e == hipSuccess) e = hipMemcpy(got.data(), s->epoch_out.p, sizeof(pw_sgns_epoch) * (size_t)n_epochs, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    if (per_epoch) std::copy(got.begin(), got.end(), per_epoch);
     if (stats) {
-        stats->vocab_ms = vocab_ms; stats->init_ms = init_ms; stats->train_ms = train_ms;
-        stats->kept_occurrences = counters[0]; stats->trained_pairs = counters[1];
-        stats->wavefronts = (uint64_t)blocks * (threads / 64);
+        stats->vocab_ms = s->vocab_ms; stats->init_ms = s->init_ms; stats->train_ms = train_ms;
+        stats->kept_occurrences = stats->trained_pairs = 0;
+        for (const pw_sgns_epoch &g : got) { stats->kept_occurrences += g.kept_occurrences; stats->trained_pairs += g.trained_pairs; }
+        stats->wavefronts = (uint64_t)s->blocks * (s->threads / 64);
     }
     return PW_OK;
+}
+
+PW_EXPORT int pw_sgns_get_state(const pw_sgns *s, pw_sgns_state *st) {
+    if (!s || !st) return fail(PW_ERR_INVALID, "null pointer");
+    *st = s->st;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_sgns_set_state(pw_sgns *s, const pw_sgns_state *st) {
+    if (!s || !st) return fail(PW_ERR_INVALID, "null pointer");
+    if (st->sched_total == 0 || st->sched_pos > st->sched_total) return fail(PW_ERR_INVALID, "schedule position beyond its length");
+    // (the kernel counts items in 64 bits: n_items * epoch must fit)
+    const uint64_t most = ~0ull / s->n_items;
+    if (st->epoch >= most || st->sched_total >= most) return fail(PW_ERR_INVALID, "epoch index out of range");
+    if (!std::isfinite(st->alpha) || !std::isfinite(st->min_alpha)) return fail(PW_ERR_INVALID, "alpha and min_alpha must be finite");
+    s->st = *st;
+    return PW_OK;
+}
+
+static int sgns_vectors_copy(pw_sgns *s, int which, float *d_ptr, bool out) {
+    if (!s || !d_ptr) return fail(PW_ERR_INVALID, "null pointer");
+    if (which != 0 && which != 1) return fail(PW_ERR_INVALID, "which must be 0 (syn0) or 1 (syn1)");
+    HIP_TRY(hipSetDevice(s->device));
+    float *mine = which ? s->syn1.p : s->syn0.p;
+    const hipError_t e = hipMemcpy(out ? d_ptr : mine, out ? mine : d_ptr, sizeof(float) * (size_t)s->n_nodes * s->a.dim, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_vectors: ") + hipGetErrorString(e));
+    return PW_OK;
+}
+PW_EXPORT int pw_sgns_vectors_get(pw_sgns *s, int which, float *d_ptr) { return sgns_vectors_copy(s, which, d_ptr, true); }
+PW_EXPORT int pw_sgns_vectors_set(pw_sgns *s, int which, const float *d_ptr) { return sgns_vectors_copy(s, which, (float *)d_ptr, false); }
+
+PW_EXPORT void pw_sgns_destroy(pw_sgns *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    delete s;
+}
+
+// the one-shot entry: a session that runs its whole schedule and leaves syn0 in the caller's buffer
+PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                                   uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                                   float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats) {
+    if (!d_walks || !d_vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+    pw_sgns *raw = nullptr;
+    int rc = pw_sgns_create_device(device, d_walks, n_walks, walk_length, n_nodes, dim, window, negative, epochs, alpha, min_alpha, sample,
+                                   seed, workers, 0, &raw);
+    if (rc != PW_OK) return rc;
+    std::unique_ptr<pw_sgns, void (*)(pw_sgns *)> s(raw, pw_sgns_destroy);
+    rc = pw_sgns_run(s.get(), epochs, nullptr, stats);
+    if (rc != PW_OK) return rc;
+    return pw_sgns_vectors_get(s.get(), 0, d_vectors);
 }
 
 // host-matrix entry: upload, the device entry, download

@@ -43,10 +43,13 @@ struct SgnsArgs {
     uint32_t table_size;
     const float *__restrict__ keep;       // per word: probability of keeping an occurrence (subsampling), or nullptr
     float alpha, min_alpha;
-    uint64_t item_base, item_total;       // position of this launch in the whole run (learning-rate schedule)
+    uint64_t item_base;                   // n_items * (global epoch index): what the hashes of this launch start from
+    uint64_t lr_base, lr_total;           // n_items * (epochs of the schedule done / in all): where the learning rate stands
     uint64_t seed;
     uint32_t n_waves;                     // wavefronts of the launch (the stride of a wavefront over the walks)
     unsigned long long *counters;         // [0] occurrences that survived the subsampling, [1] (centre, context) pairs trained
+    double *walk_loss;                    // LOSS instances: [n_walks] sum of the loss terms of a walk's evaluations, one writer each
+    unsigned long long *walk_evals;       // LOSS instances: [n_walks] number of those evaluations
 };
 
 __device__ __forceinline__ uint64_t sgns_mix(uint64_t x) {
@@ -67,7 +70,13 @@ __host__ __device__ inline size_t sgns_lds_bytes_per_wave(uint32_t L) { return s
 
 // PER: components per lane, 64 * (PER - 1) < dim <= 64 * PER: only the last component of a lane can lie beyond dim, so one
 // lane mask (`tail`) guards it and the others are read and written without a guard
-template <int PER>
+// LOSS: every trained evaluation also adds its term of the skip-gram / negative-sampling loss (gensim's definition:
+// softplus(-dot) for the centre, softplus(dot) for a negative) to a per-walk sum, taken in float64 from the exact `dot` the
+// update uses -- before the row is written, not from the clipped sigmoid, so a saturated evaluation contributes its finite
+// term.  `dot` is wave-uniform after wave_sum: every lane carries the same sum and lane 0 stores it, once per walk, with
+// plain vector stores.  The update arithmetic is the same instructions on the same values; the LOSS = false instances are
+// the kernel without any of this.
+template <int PER, bool LOSS = false>
 __global__ void __launch_bounds__(256)
 sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t *__restrict__ table, const float *__restrict__ keep) {
     // (walks / table / keep once more as arguments of their own: __restrict__ on a kernel argument is what lets the compiler
@@ -108,13 +117,18 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
         }
         wave_lds_fence();
         uint32_t n_pairs = 0;
+        double loss = 0.0;
+        unsigned long long n_evals = 0;
         for (uint32_t j = 0; j < nk; j++) {
             const uint32_t pos = readfirst_u32(kpos[j]), centre = readfirst_u32(knode[j]);
             uint64_t rs = sgns_mix(occ(pos));
             const uint32_t window = SGNS_ARG(uint32_t, window);
             const uint32_t eff = window - (uint32_t)(rs % window);                              // shrunk window, 1 .. window
             const float alpha = SGNS_ARG(float, alpha), min_alpha = SGNS_ARG(float, min_alpha);
-            const float lr = fmaxf(min_alpha, alpha - (alpha - min_alpha) * (float)((double)(occ0 + pos) / (double)SGNS_ARG(uint64_t, item_total)));
+            // the item's place in the schedule: its place in the hash sequence moved from item_base to lr_base (mod 2^64; the
+            // two coincide in a one-shot run)
+            const uint64_t lr_shift = SGNS_ARG(uint64_t, lr_base) - SGNS_ARG(uint64_t, item_base);
+            const float lr = fmaxf(min_alpha, alpha - (alpha - min_alpha) * (float)((double)(occ0 + pos + lr_shift) / (double)SGNS_ARG(uint64_t, lr_total)));
             // the window over the thinned walk: up to eff survivors on either side
             const uint32_t lo = j - min(eff, j), hi = j + min(eff, nk - 1 - j);
             for (uint32_t i = lo; i <= hi; i++) {
@@ -176,6 +190,11 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
 #pragma unroll
                         for (int s = 0; s < PER; s++) dot += vin[s] * uu[t][s];
                         dot = wave_sum(dot);
+                        if (LOSS) {                                     // softplus(x) = max(x, 0) + log1p(exp(-|x|)), x = -dot for label 1
+                            const double x = g0 + (uint32_t)t == 0 ? -(double)dot : (double)dot;
+                            loss += fmax(x, 0.0) + log1p(exp(-fabs(x)));
+                            n_evals++;
+                        }
                         const float sig = dot > 6.0f ? 1.0f : (dot < -6.0f ? 0.0f : 1.0f / (1.0f + __expf(-dot)));
                         const float g = ((g0 + (uint32_t)t == 0 ? 1.0f : 0.0f) - sig) * lr;
 #pragma unroll
@@ -202,8 +221,41 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
             atomicAdd(&counters[0], (unsigned long long)nk);
             atomicAdd(&counters[1], (unsigned long long)n_pairs);
         }
+        if (LOSS && lane == 0) {                                       // (every walk of a launch is visited once: one writer per cell;
+            SGNS_ARG(double *, walk_loss)[wk] = loss;                  //  a walk without survivors writes zeros)
+            SGNS_ARG(unsigned long long *, walk_evals)[wk] = n_evals;
+        }
     }
 #undef SGNS_ARG
+}
+
+// The epoch's loss from the per-walk values, in an order that depends on nothing but their count: block b owns the indices
+// [b * chunk, (b + 1) * chunk), thread t of its 256 adds its indices t, t + 256, ... in ascending order, the 64 partial sums
+// of a wavefront meet in the xor butterfly 32 -> 1 and the four wavefront sums are added in wavefront order.  The host calls
+// it twice: chunk = SGNS_LOSS_CHUNK over the walks (a constant: the block ranges do not follow the device or the trainer's
+// launch), then one block with chunk = the number of block sums.  No floating-point atomic takes part; the evaluation counts
+// ride along (integers: any order gives the same sum).
+constexpr uint32_t SGNS_LOSS_CHUNK = 4096;
+__global__ void __launch_bounds__(256)
+sgns_loss_reduce_kernel(const double *__restrict__ in_loss, const unsigned long long *__restrict__ in_evals, uint64_t n, uint64_t chunk,
+                        double *__restrict__ out_loss, unsigned long long *__restrict__ out_evals) {
+    __shared__ double s_loss[4];
+    __shared__ unsigned long long s_evals[4];
+    const uint64_t lo = (uint64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    double loss = 0.0;
+    unsigned long long evals = 0;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) { loss += in_loss[i]; evals += in_evals[i]; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        loss += __shfl_xor(loss, off, WAVE);
+        evals += __shfl_xor(evals, off, WAVE);
+    }
+    if (threadIdx.x % WAVE == 0) { s_loss[threadIdx.x / WAVE] = loss; s_evals[threadIdx.x / WAVE] = evals; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out_loss[blockIdx.x] = ((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3];
+        out_evals[blockIdx.x] = s_evals[0] + s_evals[1] + s_evals[2] + s_evals[3];
+    }
 }
 
 // word counts of a walk matrix (vocabulary statistics for the sampling table and the subsampling probabilities);

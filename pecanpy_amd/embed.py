@@ -13,6 +13,10 @@ trainer for a matrix that lives on the host (upload, same kernel, download), ``t
 (negative=5, ns_exponent=0.75, sample=1e-3, alpha 0.025 -> 1e-4, shrunk windows over the subsampled walk); not
 bit-comparable with gensim's own random streams -- the deterministic single-wavefront mode is checked against a sequential
 CPU restatement of the algorithm instead (tests/test_gpu_sgns.py, tests/test_gpu_embed_device.py).
+
+``SgnsSession`` is the same trainer kept between launches (``pw_sgns``): epochs in slices, the loss of every epoch, both
+matrices, a checkpoint file, a new schedule on trained vectors (tests/test_gpu_sgns_session.py); ``sgns_session_file`` opens
+one on a corpus file.
 """
 import ctypes as C
 
@@ -20,7 +24,8 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["train_sgns", "train_sgns_device", "train_sgns_file", "save_word2vec_format", "save_word2vec_format_device"]
+__all__ = ["train_sgns", "train_sgns_device", "train_sgns_file", "save_word2vec_format", "save_word2vec_format_device",
+           "SgnsSession", "sgns_session_file"]
 
 
 def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
@@ -87,6 +92,18 @@ def train_sgns_file(path, dim=128, window=10, epochs=1, negative=5, alpha=0.025,
     lines is a ``ValueError`` before any device work; so is a line of more than ``MAX_WALK_LENGTH + 1`` tokens, before the
     trainer starts.  ``train_sgns_file.last_stats``: ``"read"`` (``read_walks_device.last_stats``) and ``"train"``
     (``train_sgns_device.last_stats``)."""
+    d_walks, names = _corpus_matrix(path, device)
+    d_vectors = train_sgns_device(d_walks, len(names), dim=dim, window=window, epochs=epochs, negative=negative, alpha=alpha,
+                                  min_alpha=min_alpha, sample=sample, seed=seed, workers=workers)
+    train_sgns_file.last_stats = {"read": _corpus_matrix.last_stats, "train": train_sgns_device.last_stats}
+    return names, d_vectors
+
+
+train_sgns_file.last_stats = None
+
+
+def _corpus_matrix(path, device):
+    """``(d_walks, names)`` of a walk corpus file as the trainer takes them, with ``train_sgns_file``'s errors."""
     import os
 
     from .corpus import read_walks_device
@@ -104,13 +121,228 @@ def train_sgns_file(path, dim=128, window=10, epochs=1, negative=5, alpha=0.025,
         import torch
 
         d_walks = torch.cat([d_walks[:, :1], torch.zeros_like(d_walks[:, :1]), d_walks[:, 1:]], dim=1).contiguous()
-    d_vectors = train_sgns_device(d_walks, len(names), dim=dim, window=window, epochs=epochs, negative=negative, alpha=alpha,
-                                  min_alpha=min_alpha, sample=sample, seed=seed, workers=workers)
-    train_sgns_file.last_stats = {"read": read_walks_device.last_stats, "train": train_sgns_device.last_stats}
-    return names, d_vectors
+    _corpus_matrix.last_stats = read_walks_device.last_stats
+    return d_walks, names
 
 
-train_sgns_file.last_stats = None
+_corpus_matrix.last_stats = None
+
+
+def sgns_session_file(path, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3, seed=None,
+                      workers=0, device=0, compute_loss=False):
+    """``train_sgns_file``'s twin: ``(names, session)``, an ``SgnsSession`` on the matrix read from the corpus file (same
+    reader, same errors), nothing trained yet.  ``session.vectors()[i]`` is the vector of ``names[i]``."""
+    d_walks, names = _corpus_matrix(path, device)
+    return names, SgnsSession(d_walks, len(names), dim=dim, window=window, epochs=epochs, negative=negative, alpha=alpha,
+                              min_alpha=min_alpha, sample=sample, seed=seed, workers=workers, compute_loss=compute_loss)
+
+
+class SgnsSession:
+    """The trainer of ``train_sgns_device`` kept between launches (``pw_sgns``, include/pecanpy_amd.h): the vocabulary stage
+    and the initialisation run once, in the constructor; ``run`` trains the next epochs of the learning-rate schedule, one
+    launch each, and reports every epoch; both matrices can be read and replaced; ``save`` / ``restore`` checkpoint a run;
+    ``reschedule`` starts a new schedule on the trained vectors.  ``epochs`` is the LENGTH of the schedule: ``run(1)``
+    ``epochs`` times, ``run(epochs)`` once and ``train_sgns_device(epochs=epochs)`` train the same vectors -- at ``workers=1``
+    bit for bit, since every random choice is a hash of (seed, epoch, walk, position) and the learning rate a function of the
+    position in the schedule.
+
+    ``compute_loss``: every epoch also reports gensim's skip-gram / negative-sampling loss, the sum over the trained
+    evaluations of ``softplus(-dot)`` (centre) or ``softplus(dot)`` (negative), from the dot product the update used, before
+    the update.  The vectors do not depend on the flag.
+
+    The session holds a reference to ``d_walks`` (the library borrows the matrix) and is a context manager; after ``close``
+    every use is a ``ValueError``."""
+
+    def __init__(self, d_walks, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
+                 sample=1e-3, seed=None, workers=0, compute_loss=False):
+        import torch
+
+        self._handle = None
+        num_nodes, dim, window, epochs, negative, workers = (int(x) for x in (num_nodes, dim, window, epochs, negative, workers))
+        if num_nodes < 1:
+            raise ValueError("num_nodes must be positive")
+        if not 1 <= dim <= 512:
+            raise ValueError("dim must be in 1..512")
+        if window < 1 or epochs < 1:
+            raise ValueError("window and epochs must be positive")
+        if negative < 0 or workers < 0:
+            raise ValueError("negative and workers must not be negative")
+        if not (np.isfinite(alpha) and np.isfinite(min_alpha) and np.isfinite(sample)) or sample < 0:
+            raise ValueError("alpha, min_alpha and sample must be finite, sample not negative")
+        if not isinstance(d_walks, torch.Tensor) or not d_walks.is_cuda or d_walks.dtype != torch.int32 or not d_walks.is_contiguous():
+            raise ValueError("d_walks must be a contiguous int32 CUDA tensor")
+        if d_walks.dim() != 2 or d_walks.shape[1] < 3:
+            raise ValueError("walk matrix must be int32[n_walks, walk_length + 2]")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1)[0])
+        self.params = dict(dim=dim, window=window, epochs=epochs, negative=negative, alpha=float(alpha), min_alpha=float(min_alpha),
+                           sample=float(sample), seed=int(seed) & 0xFFFFFFFF, workers=workers, compute_loss=bool(compute_loss))
+        self.num_nodes = num_nodes
+        self.d_walks = d_walks
+        self.last_stats = None
+        lib = _lib.load()
+        torch.cuda.current_stream(d_walks.device).synchronize()  # the matrix was produced on torch's stream
+        handle = C.c_void_p()
+        _lib.check(lib.pw_sgns_create_device(d_walks.device.index, C.c_void_p(d_walks.data_ptr()), d_walks.shape[0], d_walks.shape[1] - 2,
+                                             num_nodes, dim, window, negative, epochs, float(alpha), float(min_alpha), float(sample),
+                                             self.params["seed"], workers, _lib.PW_SGNS_LOSS if compute_loss else 0, C.byref(handle)))
+        self._handle = handle
+
+    # ---- life time
+    def close(self):
+        """Free the handle (both matrices, the tables).  Closing twice is harmless."""
+        if self._handle is not None:
+            _lib.load().pw_sgns_destroy(self._handle)
+            self._handle = None
+            self.d_walks = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown)
+            pass
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the session is closed")
+        return self._handle
+
+    @property
+    def corpus_shape(self):
+        """``(n_walks, walk_length, num_nodes)``"""
+        self._open()
+        return int(self.d_walks.shape[0]), int(self.d_walks.shape[1]) - 2, self.num_nodes
+
+    # ---- training
+    def run(self, epochs=1):
+        """Train the next ``epochs`` epochs of the schedule; one dict per epoch: ``loss`` (a float, 0.0 without
+        ``compute_loss``), ``evaluations``, ``kept_occurrences``, ``trained_pairs``.  More epochs than the schedule has left
+        is a ``ValueError`` and trains nothing (``reschedule`` starts a new schedule).  ``self.last_stats``: the run's
+        ``pw_sgns_stats``."""
+        handle = self._open()
+        epochs = int(epochs)
+        st = self.state
+        if epochs < 1:
+            raise ValueError("epochs must be positive")
+        if st["sched_pos"] + epochs > st["sched_total"]:
+            raise ValueError(f"the schedule has {st['sched_total'] - st['sched_pos']} of {st['sched_total']} epochs left, "
+                             f"{epochs} asked for: reschedule() starts a new one")
+        cells = (_lib.PwSgnsEpoch * epochs)()
+        stats = _lib.PwSgnsStats()
+        _lib.check(_lib.load().pw_sgns_run(handle, epochs, C.cast(cells, C.c_void_p), C.cast(C.pointer(stats), C.c_void_p)))
+        self.last_stats = stats.as_dict()
+        return [c.as_dict() for c in cells]
+
+    @property
+    def state(self):
+        """``epoch`` (the global epoch index the hashes use; it only grows), ``sched_pos`` / ``sched_total`` (epochs of the
+        schedule done / in all), ``alpha``, ``min_alpha``."""
+        st = _lib.PwSgnsState()
+        _lib.check(_lib.load().pw_sgns_get_state(self._open(), C.byref(st)))
+        return st.as_dict()
+
+    def _set_state(self, **fields):
+        st = _lib.PwSgnsState(**fields)
+        _lib.check(_lib.load().pw_sgns_set_state(self._open(), C.byref(st)))
+
+    def reschedule(self, epochs, alpha=None, min_alpha=None):
+        """A new learning-rate schedule of ``epochs`` epochs on the vectors as they are (gensim's ``train()`` on a trained
+        model): ``alpha`` / ``min_alpha`` default to the current ones.  The epoch index of the hashes goes on counting."""
+        st = self.state
+        epochs = int(epochs)
+        if epochs < 1:
+            raise ValueError("epochs must be positive")
+        alpha = st["alpha"] if alpha is None else float(alpha)
+        min_alpha = st["min_alpha"] if min_alpha is None else float(min_alpha)
+        if not (np.isfinite(alpha) and np.isfinite(min_alpha)):
+            raise ValueError("alpha and min_alpha must be finite")
+        self._set_state(epoch=st["epoch"], sched_pos=0, sched_total=epochs, alpha=alpha, min_alpha=min_alpha)
+
+    # ---- the matrices
+    def _matrix(self, which):
+        import torch
+
+        handle = self._open()
+        out = torch.empty((self.num_nodes, self.params["dim"]), dtype=torch.float32, device=self.d_walks.device)
+        _lib.check(_lib.load().pw_sgns_vectors_get(handle, which, C.c_void_p(out.data_ptr())))
+        return out
+
+    def vectors(self):
+        """A new ``float32[num_nodes, dim]`` CUDA tensor: the input vectors (``syn0``, gensim's ``wv``)."""
+        return self._matrix(0)
+
+    def context_vectors(self):
+        """A new ``float32[num_nodes, dim]`` CUDA tensor: the context vectors (``syn1``, gensim's ``syn1neg``)."""
+        return self._matrix(1)
+
+    def load(self, vectors=None, context_vectors=None):
+        """Replace ``syn0`` and / or ``syn1``: a CUDA tensor on the session's device, a CPU tensor or a NumPy array, each
+        ``float32[num_nodes, dim]`` -- another shape, dtype or device is a ``ValueError`` and changes nothing."""
+        import torch
+
+        handle = self._open()
+        shape = (self.num_nodes, self.params["dim"])
+        staged = []
+        for which, name, m in ((0, "vectors", vectors), (1, "context_vectors", context_vectors)):
+            if m is None:
+                continue
+            if isinstance(m, torch.Tensor):
+                if m.device.type not in ("cpu", "cuda") or (m.is_cuda and m.device != self.d_walks.device):
+                    raise ValueError(f"{name} must be on the host or on {self.d_walks.device}, not on {m.device}")
+                if m.dtype != torch.float32:
+                    raise ValueError(f"{name} must be float32, not {m.dtype}")
+            else:
+                m = np.asarray(m)
+                if m.dtype != np.float32:
+                    raise ValueError(f"{name} must be float32, not {m.dtype}")
+                m = torch.from_numpy(np.ascontiguousarray(m))
+            if tuple(m.shape) != shape:
+                raise ValueError(f"{name} must be float32{list(shape)}, not {list(m.shape)}")
+            staged.append((which, m.to(self.d_walks.device).contiguous()))
+        torch.cuda.current_stream(self.d_walks.device).synchronize()
+        for which, m in staged:
+            _lib.check(_lib.load().pw_sgns_vectors_set(handle, which, C.c_void_p(m.data_ptr())))
+
+    # ---- checkpoints
+    def save(self, path):
+        """An ``.npz`` with both matrices, the state, the constructor's parameters and ``(n_walks, walk_length,
+        num_nodes)``: what ``restore`` needs besides the walk matrix."""
+        st = self.state
+        arrays = dict(vectors=self.vectors().cpu().numpy(), context_vectors=self.context_vectors().cpu().numpy(),
+                      corpus_shape=np.array(self.corpus_shape, dtype=np.int64))
+        arrays.update({"state_" + k: np.array(v) for k, v in st.items()})
+        arrays.update({"param_" + k: np.array(v) for k, v in self.params.items()})
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def restore(cls, path, d_walks):
+        """The session ``save`` wrote, on the same corpus: ``d_walks`` must have the saved ``(n_walks, walk_length)`` --
+        another shape is a ``ValueError`` before any device work.  (The matrix itself is not in the file.)"""
+        with np.load(path) as z:
+            saved = {k: z[k] for k in z.files}
+        n_walks, walk_length, num_nodes = (int(x) for x in saved["corpus_shape"])
+        shape = tuple(getattr(d_walks, "shape", ()))
+        if len(shape) != 2 or (int(shape[0]), int(shape[1]) - 2) != (n_walks, walk_length):
+            raise ValueError(f"{path} was saved on a corpus of {n_walks} walks of length {walk_length}; "
+                             f"d_walks has the shape {list(shape)}")
+        params = {k[len("param_"):]: v.item() for k, v in saved.items() if k.startswith("param_")}
+        s = cls(d_walks, num_nodes, **params)
+        try:
+            s.load(vectors=saved["vectors"], context_vectors=saved["context_vectors"])
+            s._set_state(epoch=int(saved["state_epoch"]), sched_pos=int(saved["state_sched_pos"]),
+                         sched_total=int(saved["state_sched_total"]), alpha=float(saved["state_alpha"]),
+                         min_alpha=float(saved["state_min_alpha"]))
+        except Exception:
+            s.close()
+            raise
+        return s
 
 
 _WRITE_ROWS = 1 << 14   # rows formatted per write

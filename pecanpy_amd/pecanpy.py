@@ -405,6 +405,21 @@ class Base(BaseGraph):
                                  "download_ms": (t3 - t2) * 1e3, **train_sgns_device.last_stats}
         return vec
 
+    def embed_session(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0, compute_loss=False):
+        """The walks of ``embed_array`` generated in device memory and a ``pecanpy_amd.embed.SgnsSession`` on them, nothing
+        trained yet: ``session.run()`` trains the schedule of ``epochs`` epochs in slices and reports every epoch (with
+        ``compute_loss`` its loss), ``session.vectors()`` is ``float32[num_nodes, dim]`` in node order on the device.
+        ``session.run(epochs)`` trains what ``embed_array`` trains.  Under ``torch.distributed`` and with the in-process
+        multi-GPU engine there is no device matrix to hold a session on: ``NotImplementedError``."""
+        from .embed import SgnsSession
+
+        d_walks = self._device_walks(num_walks, walk_length)
+        if d_walks is None:
+            raise NotImplementedError("embed_session needs the walk matrix on one device: not under torch.distributed or "
+                                      "with the in-process multi-GPU engine")
+        return SgnsSession(d_walks, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
+                           workers=workers, compute_loss=compute_loss)
+
     def embed_to_file(self, path, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0):
         """``embed_array`` + ``save_word2vec_format`` without the vectors visiting the host: walks, trainer and the device
         writer (``pecanpy_amd.embed.save_word2vec_format_device``); only the text of the file leaves the device.  The file
