@@ -312,7 +312,9 @@ int pw_probs(pw_graph *g, int mode, double p, double q, int extend, uint32_t cur
  *   first_order = 1: PreCompFirstOrder.preprocess_transition_probs (pecanpy.py:336-361): nnz entries
  * pw_simulate* with PW_MODE_PRECOMP / PW_MODE_PRECOMP_FIRST_ORDER builds them on demand.
  * pw_precomp_export copies them to host arrays (alias_indptr uint64[n_nodes+1] may be NULL for
- * first_order); *n_entries receives the table length (call with NULL arrays to query it). */
+ * first_order); *n_entries receives the table length (call with NULL arrays to query it).
+ * Tables built with extend name the threshold upload they were built from: after pw_graph_set_thresholds the
+ * next build (or PreComp call) builds them again, and pw_precomp_export returns PW_ERR_INVALID until it has. */
 int pw_precomp_build(pw_graph *g, double p, double q, int extend, int first_order);
 int pw_precomp_export(pw_graph *g, uint64_t *alias_indptr, uint32_t *alias_j, float *alias_q,
                       uint64_t *n_entries);

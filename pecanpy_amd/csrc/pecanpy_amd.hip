@@ -148,7 +148,8 @@ struct GraphDesc {
 // pw_precomp_build and the lazy builders -- d_hasnbr in compute_offsets, ensure_tot_table, ensure_unit_tot,
 // ensure_wlane_tables, spp_check -- each of which writes nothing when its keys already match.  A twin context reads it
 // from another thread while the primary walks: its calls use the primary's (p, q, extend) and thresholds, so they find
-// every table in place.
+// every table in place -- or build, under those keys, one that the primary's smaller half declined and does not read.
+// Every table that reads the thresholds records the upload it was built from (*_thr_version against thr_version).
 struct GraphData : GraphDesc {
     int device = 0;
     DevBuf<uint32_t> d_indptr, d_indices;
@@ -199,6 +200,7 @@ struct GraphData : GraphDesc {
     int alias_kind = -1;  // -1 none, 0 second order, 1 first order
     double alias_p = 0, alias_q_param = 0;
     int alias_extend = 0;
+    uint64_t alias_thr_version = 0;                     // ... from this threshold upload (read by the extend tables only)
 
     explicit GraphData(int dev) : device(dev) {}
     GraphData(const GraphData &) = delete;
@@ -2182,7 +2184,10 @@ PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int 
     if (extend && !g->gd->d_thr.p) return fail(PW_ERR_INVALID, "extend: call pw_graph_set_thresholds() first");
     if (set_device(g)) return PW_ERR_HIP;
     first_order = first_order ? 1 : 0;
-    if (g->gd->alias_kind == first_order && (first_order || (g->gd->alias_p == p && g->gd->alias_q_param == q && g->gd->alias_extend == extend)))
+    extend = extend ? 1 : 0;
+    // (first-order tables never read the thresholds; second-order ones only with extend)
+    if (g->gd->alias_kind == first_order && (first_order || (g->gd->alias_p == p && g->gd->alias_q_param == q && g->gd->alias_extend == extend &&
+                                                             (!extend || g->gd->alias_thr_version == g->gd->thr_version))))
         return PW_OK;
     const uint32_t n = g->gd->n_nodes;
     std::vector<uint32_t> indptr((size_t)n + 1);
@@ -2214,6 +2219,7 @@ PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int 
     g->gd->alias_p = p;
     g->gd->alias_q_param = q;
     g->gd->alias_extend = extend;
+    g->gd->alias_thr_version = g->gd->thr_version;
     return PW_OK;
 }
 
@@ -2221,6 +2227,9 @@ PW_EXPORT int pw_precomp_export(pw_graph *g, uint64_t *alias_indptr, uint32_t *a
                                 uint64_t *n_entries) {
     if (!g) return fail(PW_ERR_INVALID, "null pointer");
     if (g->gd->alias_kind < 0) return fail(PW_ERR_INVALID, "no alias tables built");
+    // tables that the next PreComp call would build again are not handed out
+    if (g->gd->alias_kind == 0 && g->gd->alias_extend && g->gd->alias_thr_version != g->gd->thr_version)
+        return fail(PW_ERR_INVALID, "the alias tables were built from thresholds that have been replaced since: call pw_precomp_build() again");
     if (set_device(g)) return PW_ERR_HIP;
     if (n_entries) *n_entries = g->gd->n_alias;
     if (alias_indptr)
