@@ -398,8 +398,26 @@ int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, 
  *                          a device-to-device copy of syn0 (which = 0: the input vectors, the embedding) or syn1 (which = 1: the
  *                          context vectors, gensim's syn1neg) out of / into the handle; d_ptr = float32[n_nodes, dim],
  *                          contiguous, on the handle's device.
+ *   pw_sgns_evaluate       scores, trains nothing: the evaluations a PW_SGNS_LOSS launch of global epoch index `epoch` performs on
+ *                          the matrix -- the same subsampling, windows and negatives, hashes of (seed, epoch, walk, position)
+ *                          with item base n_walks * (walk_length + 1) * epoch of THAT matrix -- against syn0 / syn1 as they are,
+ *                          by a kernel of its own that writes no vector (sgns_eval_kernel).  d_walks = NULL: the session's own
+ *                          matrix (n_walks / walk_length ignored); any other device matrix may have its own shape and gets the
+ *                          checks and error texts of the create call (a node id >= n_nodes, a length cell > walk_length + 1,
+ *                          walk_length >= 8192).  out: loss, evaluations, kept_occurrences, trained_pairs (the pairs scored);
+ *                          PW_SGNS_LOSS is not needed on the handle.  The sum is made as pw_sgns_run makes it; nothing is
+ *                          written, so nothing races: the launch takes as many wavefronts as the matrix feeds whatever
+ *                          `workers` is, and the record is a function of (seed, epoch, matrix, vectors), bit for bit.  syn0,
+ *                          syn1, the tables and the state are unchanged.
+ *   pw_sgns_set_walks      another matrix under the session, BORROWED like the first (the old one is no longer used).  It must
+ *                          have the session's (n_walks, walk_length) -- the schedule arithmetic stays; another shape is
+ *                          PW_ERR_INVALID -- and gets the content checks of the create call.  flags = 0: the noise table and
+ *                          the keep probabilities stay those of the create call; PW_SGNS_RECOUNT: they are rebuilt from the new
+ *                          matrix by the create call's own path.  The state and both matrices are not touched.  On any error
+ *                          the session keeps the old matrix and all its tables.
  *   pw_sgns_destroy        frees what the handle owns; NULL is allowed. */
 enum { PW_SGNS_LOSS = 1 };
+enum { PW_SGNS_RECOUNT = 1 };
 typedef struct pw_sgns pw_sgns;
 typedef struct pw_sgns_epoch {
     double loss;
@@ -418,6 +436,8 @@ int pw_sgns_get_state(const pw_sgns *s, pw_sgns_state *st);
 int pw_sgns_set_state(pw_sgns *s, const pw_sgns_state *st);
 int pw_sgns_vectors_get(pw_sgns *s, int which, float *d_ptr);
 int pw_sgns_vectors_set(pw_sgns *s, int which, const float *d_ptr);
+int pw_sgns_evaluate(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint64_t epoch, pw_sgns_epoch *out);
+int pw_sgns_set_walks(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t flags);
 void pw_sgns_destroy(pw_sgns *s);
 
 /* ---- the embedding file written from device memory (csrc/emb_text.hip.h) --------------------------------------------------

@@ -87,6 +87,7 @@ class PwSgnsState(C.Structure):
 
 
 PW_SGNS_LOSS = 1
+PW_SGNS_RECOUNT = 1   # pw_sgns_set_walks
 
 
 class PwEmbWriteStats(C.Structure):
@@ -226,6 +227,8 @@ SYMBOLS = {
     "pw_sgns_set_state": (C.c_int, [C.c_void_p, C.POINTER(PwSgnsState)]),
     "pw_sgns_vectors_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pw_sgns_vectors_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pw_sgns_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(PwSgnsEpoch)]),
+    "pw_sgns_set_walks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     "pw_sgns_destroy": (None, [C.c_void_p]),
     "pw_vectors_write_text_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,
                                                C.POINTER(PwEmbWriteStats)]),

@@ -48,6 +48,10 @@ _OPTIONS = (
     ("--random_state", dict(type=int, default=None, help="seed of the walk stream")),
     ("--epoch_loss", dict(action="store_true", help="GPU trainer only: print the skip-gram loss of every epoch (sum and mean "
                                                     "per evaluation); --workers 1 then also makes the trainer deterministic")),
+    ("--fresh_walks", dict(action="store_true", help="GPU trainer only: every epoch after the first trains on newly drawn walks "
+                                                     "(call seed random_state + epoch); implies the route of --epoch_loss")),
+    ("--holdout_walks", dict(type=int, default=0, help="GPU trainer only: draw this many held-out walks per node once and print "
+                                                       "their mean loss after every epoch; implies the route of --epoch_loss")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
     ("--implicit_ids", dict(action="store_true", help=".npz without IDs: use 0..N-1")),
 )
@@ -224,10 +228,10 @@ def walks_to_file(args, g):
 def embed_on_gpu(args, g):
     """Walks and skip-gram in device memory (``Base.embed_array``), the vectors written as ``learn_embeddings`` writes
     them; no ``List[List[str]]`` corpus and no index matrix on the host."""
-    if args.epoch_loss:
+    if args.epoch_loss or args.fresh_walks or args.holdout_walks:
         with g.embed_session(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
                              window_size=args.window_size, epochs=args.epochs, workers=_session_workers(args),
-                             compute_loss=True) as session:
+                             compute_loss=True, fresh_walks=args.fresh_walks, holdout_walks=args.holdout_walks) as session:
             _print_epoch_loss(session.run(args.epochs))
             vecs = session.vectors().cpu().numpy()
     else:
@@ -245,7 +249,11 @@ def _session_workers(args):
 def _print_epoch_loss(records):
     for i, r in enumerate(records, 1):
         mean = r["loss"] / r["evaluations"] if r["evaluations"] else 0.0
-        print(f"epoch {i}: loss {r['loss']:.6f}, mean {mean:.6f} over {r['evaluations']} evaluations")
+        held = ""
+        if "holdout_loss" in r:
+            n = r["holdout_evaluations"]
+            held = f", held-out mean {r['holdout_loss'] / n if n else 0.0:.6f} over {n} evaluations"
+        print(f"epoch {i}: loss {r['loss']:.6f}, mean {mean:.6f} over {r['evaluations']} evaluations{held}")
 
 
 @Timer("read corpus + train embeddings")
@@ -253,6 +261,10 @@ def train_from_corpus(args):
     """``--task train``: ``--input`` is a walk corpus file (what ``--task walks`` writes); it is read and numbered in device
     memory and trained there (``embed.train_sgns_file``); the vectors are written in order of first appearance."""
     from .embed import save_word2vec_format_device, sgns_session_file, train_sgns_file
+
+    if args.fresh_walks or args.holdout_walks:
+        warnings.warn("--fresh_walks and --holdout_walks draw walks from a graph; --task train has none, so they are ignored",
+                      stacklevel=2)
 
     if args.epoch_loss:
         names, session = sgns_session_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
@@ -289,6 +301,9 @@ def main(argv=None):
         if args.epoch_loss:
             warnings.warn("--epoch_loss reports the loss of the GPU trainer; gensim is importable (or the walks are dumped), "
                           "so that route runs as without the flag and no loss is printed", stacklevel=2)
+        if args.fresh_walks or args.holdout_walks:
+            warnings.warn("--fresh_walks and --holdout_walks belong to the GPU trainer; gensim is importable (or the walks are "
+                          "dumped), so that route runs as without the flags", stacklevel=2)
         learn_embeddings(args, simulate_walks(args, g), g)
 
 

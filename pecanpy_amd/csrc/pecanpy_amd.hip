@@ -4384,53 +4384,43 @@ struct pw_sgns {
     DevBuf<double> walk_loss, block_loss;    // PW_SGNS_LOSS: per walk, per SGNS_LOSS_CHUNK walks
     DevBuf<unsigned long long> walk_evals, block_evals;
     pw::Event ev0, ev1;                      // the pair around the training launches of a run
+    float sample = 0;                        // of the create call: what PW_SGNS_RECOUNT rebuilds the keep probabilities with
+    unsigned n_cus = 1;
+    // pw_sgns_evaluate: its own per-walk and per-block cells (sized by the matrix it scores) and its record
+    DevBuf<double> eval_walk_loss, eval_block_loss;
+    DevBuf<unsigned long long> eval_walk_evals, eval_block_evals;
+    DevBuf<pw_sgns_epoch> eval_out;
 };
 static_assert(offsetof(pw_sgns_epoch, kept_occurrences) + sizeof(uint64_t) == offsetof(pw_sgns_epoch, trained_pairs),
               "the kernel's two counters are consecutive cells of an epoch's record");
 
-PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
-                                    uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
-                                    float sample, uint32_t seed, uint32_t workers, uint32_t flags, pw_sgns **out) {
-    if (!out) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    *out = nullptr;
-    if (!d_walks || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
-    if (window == 0 || epochs == 0) return fail(PW_ERR_INVALID, "window and epochs must be positive");
-    if (flags & ~(uint32_t)PW_SGNS_LOSS) return fail(PW_ERR_INVALID, "unknown flag");
-    const uint32_t L = walk_length;
-    // the survivors of a walk live in the wavefront's LDS: four wavefronts to a workgroup while that fits, else one
-    const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
-    if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
-    const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-    const size_t vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    std::unique_ptr<pw_sgns> s(new pw_sgns);
-    s->device = device; s->n_nodes = n_nodes; s->loss = (flags & PW_SGNS_LOSS) != 0;
+// The vocabulary stage of a walk matrix.  The device check first: a node id >= n_nodes or a length cell > walk_length + 1 is
+// PW_ERR_INVALID with the text every entry that takes a matrix shares.  With `out`, word2vec's unigram^0.75 table and the
+// subsampling probabilities from the word counts of that pass, uploaded; without it the check alone.
+struct SgnsVocab {
+    DevBuf<uint32_t> table;
+    DevBuf<float> keep;                      // (not allocated with sample = 0)
+    uint32_t table_size = 0;
+};
+static int sgns_vocabulary(const uint32_t *d_walks, uint64_t n_walks, uint32_t L, uint32_t n_nodes, float sample, SgnsVocab *out) {
     DevBuf<unsigned long long> cnt_buf;
-    auto t_vocab = clk::now();
     // d_cnt: [0, n_nodes) word counts, [n_nodes] first bad walk
     hipError_t e = cnt_buf.alloc((size_t)n_nodes + 1);
-    if (e == hipSuccess) e = s->syn0.alloc((size_t)n_nodes * dim);
-    if (e == hipSuccess) e = s->syn1.alloc((size_t)n_nodes * dim);
     unsigned long long *const d_cnt = cnt_buf.p;
     if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * (size_t)n_nodes);
     if (e == hipSuccess) e = hipMemset(d_cnt + n_nodes, 0xff, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(s->syn1.p, 0, vbytes);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     // vocabulary statistics (and the check that the matrix only names nodes of the vocabulary)
     const uint64_t n_items = n_walks * (uint64_t)(L + 1);
     hipLaunchKernelGGL(pw::sgns_count_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, 0, d_walks, n_walks, L, n_nodes, d_cnt,
                        d_cnt + n_nodes);
     std::vector<unsigned long long> cnt((size_t)n_nodes + 1);
-    e = hipMemcpy(cnt.data(), d_cnt, sizeof(unsigned long long) * ((size_t)n_nodes + 1), hipMemcpyDeviceToHost);
+    const size_t first = out ? 0 : n_nodes;   // (the check alone: only its cell comes down)
+    e = hipMemcpy(cnt.data() + first, d_cnt + first, sizeof(unsigned long long) * ((size_t)n_nodes + 1 - first), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
     if (cnt[n_nodes] != ~0ull)
         return fail(PW_ERR_INVALID, "walk " + std::to_string(cnt[n_nodes]) + ": node id >= n_nodes or length cell > walk_length + 1");
+    if (!out) return PW_OK;
     double total = 0, pow_total = 0;
     for (uint32_t i = 0; i < n_nodes; i++) { total += (double)cnt[i]; pow_total += std::pow((double)cnt[i], 0.75); }
     if (!(total > 0)) return fail(PW_ERR_INVALID, "the walk matrix holds no nodes");
@@ -4455,13 +4445,51 @@ PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_
         for (uint32_t i = 0; i < n_nodes; i++)
             keep[i] = cnt[i] ? (float)std::min(1.0, (std::sqrt((double)cnt[i] / thr) + 1.0) * thr / (double)cnt[i]) : 1.0f;
     }
-    e = s->table.alloc(table_size);
-    if (e == hipSuccess) e = hipMemcpy(s->table.p, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
+    e = out->table.alloc(table_size);
+    if (e == hipSuccess) e = hipMemcpy(out->table.p, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
     if (e == hipSuccess && sample > 0) {
-        e = s->keep.alloc(n_nodes);
-        if (e == hipSuccess) e = hipMemcpy(s->keep.p, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
+        e = out->keep.alloc(n_nodes);
+        if (e == hipSuccess) e = hipMemcpy(out->keep.p, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    out->table_size = table_size;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
+                                    uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
+                                    float sample, uint32_t seed, uint32_t workers, uint32_t flags, pw_sgns **out) {
+    if (!out) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+    *out = nullptr;
+    if (!d_walks || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+    if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
+    if (window == 0 || epochs == 0) return fail(PW_ERR_INVALID, "window and epochs must be positive");
+    if (flags & ~(uint32_t)PW_SGNS_LOSS) return fail(PW_ERR_INVALID, "unknown flag");
+    const uint32_t L = walk_length;
+    // the survivors of a walk live in the wavefront's LDS: four wavefronts to a workgroup while that fits, else one
+    const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
+    if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
+    const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
+    int ndev = pw_device_count();
+    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    const size_t vbytes = sizeof(float) * (size_t)n_nodes * dim;
+    std::unique_ptr<pw_sgns> s(new pw_sgns);
+    s->device = device; s->n_nodes = n_nodes; s->loss = (flags & PW_SGNS_LOSS) != 0; s->sample = sample;
+    auto t_vocab = clk::now();
+    hipError_t e = s->syn0.alloc((size_t)n_nodes * dim);
+    if (e == hipSuccess) e = s->syn1.alloc((size_t)n_nodes * dim);
+    if (e == hipSuccess) e = hipMemset(s->syn1.p, 0, vbytes);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
+    const uint64_t n_items = n_walks * (uint64_t)(L + 1);
+    SgnsVocab vocab;
+    if (int rc = sgns_vocabulary(d_walks, n_walks, L, n_nodes, sample, &vocab)) return rc;
+    const uint32_t table_size = vocab.table_size;
+    s->table = std::move(vocab.table);
+    s->keep = std::move(vocab.keep);
     s->vocab_ms = ms_since(t_vocab);
     // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded
     auto t_init = clk::now();
@@ -4509,7 +4537,7 @@ PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_
         const uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>(want_waves, (uint64_t)prop.multiProcessorCount * 32));
         blocks = (unsigned)((waves + waves_per_block - 1) / waves_per_block);
     }
-    s->blocks = blocks; s->threads = threads;
+    s->blocks = blocks; s->threads = threads; s->n_cus = (unsigned)std::max(1, prop.multiProcessorCount);
     s->lds = lds_wave * (threads / 64);
     a.n_waves = blocks * (threads / 64);
     *out = s.release();
@@ -4561,6 +4589,89 @@ PW_EXPORT int pw_sgns_run(pw_sgns *s, uint32_t n_epochs, pw_sgns_epoch *per_epoc
         stats->kept_occurrences = stats->trained_pairs = 0;
         for (const pw_sgns_epoch &g : got) { stats->kept_occurrences += g.kept_occurrences; stats->trained_pairs += g.trained_pairs; }
         stats->wavefronts = (uint64_t)s->blocks * (s->threads / 64);
+    }
+    return PW_OK;
+}
+
+template <int PER>
+static void sgns_eval_launch(unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
+    hipLaunchKernelGGL((pw::sgns_eval_kernel<PER>), dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep, a.syn0, a.syn1);
+}
+
+// Scores a walk matrix with the vectors as they are (sgns.hip.h: sgns_eval_kernel); nothing of the session changes.
+PW_EXPORT int pw_sgns_evaluate(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint64_t epoch,
+                               pw_sgns_epoch *out) {
+    if (!s || !out) return fail(PW_ERR_INVALID, "null pointer");
+    const bool own = d_walks == nullptr;
+    if (own) { d_walks = s->a.walks; n_walks = s->a.n_walks; walk_length = s->a.L; }
+    if (!n_walks) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
+    const uint32_t L = walk_length;
+    const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
+    if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
+    const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
+    // (the kernel counts items in 64 bits: n_items * epoch must fit)
+    const uint64_t n_items = n_walks * (uint64_t)(L + 1);
+    if (epoch >= ~0ull / n_items) return fail(PW_ERR_INVALID, "epoch index out of range");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!own)   // (the session's own matrix passed these checks when it was taken)
+        if (int rc = sgns_vocabulary(d_walks, n_walks, L, s->n_nodes, s->sample, nullptr)) return rc;
+    const unsigned n_blocks = (unsigned)((n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
+    hipError_t e = s->eval_walk_loss.ensure(n_walks);
+    if (e == hipSuccess) e = s->eval_walk_evals.ensure(n_walks);
+    if (e == hipSuccess) e = s->eval_block_loss.ensure(n_blocks);
+    if (e == hipSuccess) e = s->eval_block_evals.ensure(n_blocks);
+    if (e == hipSuccess) e = s->eval_out.ensure(1);
+    if (e == hipSuccess) e = hipMemset(s->eval_out.p, 0, sizeof(pw_sgns_epoch));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_evaluate: ") + hipGetErrorString(e));
+    pw::SgnsArgs a = s->a;
+    a.walks = d_walks; a.n_walks = n_walks; a.L = L;
+    a.item_base = n_items * epoch;
+    a.counters = (unsigned long long *)&s->eval_out.p->kept_occurrences;
+    a.walk_loss = s->eval_walk_loss.p; a.walk_evals = s->eval_walk_evals.p;
+    // nothing is written, so nothing races: a wavefront per walk up to what the device holds at once, whatever `workers` is
+    const uint64_t waves = std::min<uint64_t>(n_walks, (uint64_t)s->n_cus * 32);
+    const unsigned blocks = (unsigned)((waves + waves_per_block - 1) / waves_per_block), threads = 64 * waves_per_block;
+    a.n_waves = blocks * waves_per_block;
+    const size_t lds = lds_wave * waves_per_block;
+    switch ((a.dim + 63) / 64) {   // (as sgns_launch_per)
+    case 1: sgns_eval_launch<1>(blocks, threads, lds, a); break;
+    case 2: sgns_eval_launch<2>(blocks, threads, lds, a); break;
+    case 3: sgns_eval_launch<3>(blocks, threads, lds, a); break;
+    case 4: sgns_eval_launch<4>(blocks, threads, lds, a); break;
+    case 5: sgns_eval_launch<5>(blocks, threads, lds, a); break;
+    case 6: sgns_eval_launch<6>(blocks, threads, lds, a); break;
+    case 7: sgns_eval_launch<7>(blocks, threads, lds, a); break;
+    default: sgns_eval_launch<8>(blocks, threads, lds, a); break;
+    }
+    hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(n_blocks), dim3(256), 0, 0, a.walk_loss, a.walk_evals, n_walks,
+                       (uint64_t)pw::SGNS_LOSS_CHUNK, s->eval_block_loss.p, s->eval_block_evals.p);
+    hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(1), dim3(256), 0, 0, s->eval_block_loss.p, s->eval_block_evals.p, (uint64_t)n_blocks,
+                       (uint64_t)n_blocks, &s->eval_out.p->loss, (unsigned long long *)&s->eval_out.p->evaluations);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, s->eval_out.p, sizeof(pw_sgns_epoch), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_evaluate: ") + hipGetErrorString(e));
+    return PW_OK;
+}
+
+// Another matrix of the same shape under the session: the schedule arithmetic (n_items) stays, the state and both matrices
+// are not touched.  Everything that can fail comes before the first assignment.
+PW_EXPORT int pw_sgns_set_walks(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t flags) {
+    if (!s || !d_walks) return fail(PW_ERR_INVALID, "null pointer");
+    if (flags & ~(uint32_t)PW_SGNS_RECOUNT) return fail(PW_ERR_INVALID, "unknown flag");
+    if (n_walks != s->a.n_walks || walk_length != s->a.L)
+        return fail(PW_ERR_INVALID, "the session was created on " + std::to_string(s->a.n_walks) + " walks of length " + std::to_string(s->a.L) +
+                                        ": a matrix of " + std::to_string(n_walks) + " walks of length " + std::to_string(walk_length) +
+                                        " needs a session of its own");
+    HIP_TRY(hipSetDevice(s->device));
+    SgnsVocab vocab;
+    const bool recount = (flags & PW_SGNS_RECOUNT) != 0;
+    if (int rc = sgns_vocabulary(d_walks, n_walks, walk_length, s->n_nodes, s->sample, recount ? &vocab : nullptr)) return rc;
+    s->a.walks = d_walks;
+    if (recount) {
+        s->table = std::move(vocab.table);
+        s->keep = std::move(vocab.keep);
+        s->a.table = s->table.p; s->a.table_size = vocab.table_size; s->a.keep = s->keep.p;
     }
     return PW_OK;
 }

@@ -229,6 +229,142 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
 #undef SGNS_ARG
 }
 
+// The read-only form: the evaluations sgns_walk_kernel<PER, true> performs for the epoch of a.item_base on the matrix
+// `walks` -- the same ballot and compaction, the same shrunk window, the same chain `rs`, a negative that equals the centre
+// skipped -- scored against syn0 / syn1 as they are, and no update: no learning rate is read and no vector written.  `dot` is
+// the training kernel's (component k on lane k % 64, per-lane partial sums in ascending k, xor butterfly 32 -> 1), the term
+// the LOSS instances' float64 expression, the per-walk sum is taken in evaluation order with one writer per walk, and
+// sgns_loss_reduce_kernel follows: the result is a function of (seed, epoch, matrix, vectors) and bit-identical at any number
+// of wavefronts -- a.n_waves is the stride over the walks and nothing else.  What the missing stores buy:
+//   * syn0 / syn1 are const __restrict__, no row is read again after a write, and all SGNS_GROUP target rows of a group are
+//     requested without a guard on `act` together with the context row (a skipped target names the centre's row: a valid
+//     address whose dot is dropped), so a pair's loads go out in one batch with no branch between them;
+//   * `dot` is wave-uniform, so the float64 softplus need not run once per evaluation on 64 identical lanes: evaluation e of
+//     a batch parks x = -+dot in lane e, and when 64 are parked (or the walk ends) every lane takes the term of its own x at
+//     once; the terms are then added to the walk's sum one lane after the other -- the sequential order of the training
+//     kernel, so the sum has its bits;
+//   * nothing races, so the launch takes as many wavefronts as the corpus feeds whatever the session's `workers` is.
+// LDS per wavefront and the workgroup shapes are the training kernel's (sgns_lds_bytes_per_wave; one wavefront per workgroup
+// from L = 2048).  Global memory is written through vector stores only: the two per-walk cells by lane 0, the two counters
+// by lane 0's atomics, once per walk.
+template <int PER>
+__global__ void __launch_bounds__(256)
+sgns_eval_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t *__restrict__ table, const float *__restrict__ keep,
+                 const float *__restrict__ syn0, const float *__restrict__ syn1) {
+    extern __shared__ uint32_t sgns_lds[];
+    const int lane = lane_id();
+    const uint32_t wib = readfirst_u32(threadIdx.x / WAVE), wpb = blockDim.x / WAVE;
+    const uint32_t wave = blockIdx.x * wpb + wib;
+    const uint32_t L1 = a.L + 1;
+    const bool tail = (uint32_t)lane < a.dim - 64u * (PER - 1);
+    uint32_t *kpos = sgns_lds + (size_t)wib * 2 * L1, *knode = kpos + L1;
+    for (uint64_t wk = wave; wk < a.n_walks; wk += a.n_waves) {
+        const uint32_t *row = walks + wk * (uint64_t)(a.L + 2);      // (L < 8192)
+        const uint32_t len = min(row[L1], L1);                        // (the count kernel rejected longer; bounds the LDS writes)
+        const uint64_t occ0 = a.item_base + wk * (uint64_t)L1;
+#define occ(p) sgns_mix(a.seed ^ (occ0 + (p)) * 0x9E3779B97F4A7C15ull)
+        wave_lds_fence();                                             // (the previous walk's readers are done)
+        uint32_t nk = 0;
+        for (uint32_t base = 0; base < len; base += WAVE) {
+            const uint32_t p = base + lane;
+            bool k = p < len;
+            uint32_t node = 0;
+            if (k) {
+                node = row[p];
+                if (keep) k = (float)(occ(p) >> 40) * (1.0f / 16777216.0f) < keep[node];
+            }
+            const uint64_t m = ballot(k);
+            if (k) {
+                const uint32_t j = nk + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                kpos[j] = p;
+                knode[j] = node;
+            }
+            nk += (uint32_t)__popcll(m);
+        }
+        wave_lds_fence();
+        uint32_t n_pairs = 0;
+        double loss = 0.0;
+        unsigned long long n_evals = 0;
+        float parked = 0.0f;                                           // lane e: x of the batch's evaluation e
+        uint32_t n_parked = 0;                                         // (uniform) evaluations parked, < 64 between groups
+        // the terms of the parked evaluations, added in evaluation order; softplus(x) = max(x, 0) + log1p(exp(-|x|))
+#define SGNS_EVAL_FLUSH()                                                                              \
+        do {                                                                                           \
+            const double x = (double)parked;                                                           \
+            const double term = fmax(x, 0.0) + log1p(exp(-fabs(x)));                                   \
+            for (uint32_t e = 0; e < n_parked; e++) loss += readlane_f64(term, (int)e);                \
+            n_evals += n_parked;                                                                       \
+            n_parked = 0;                                                                              \
+        } while (0)
+        for (uint32_t j = 0; j < nk; j++) {
+            const uint32_t pos = readfirst_u32(kpos[j]), centre = readfirst_u32(knode[j]);
+            uint64_t rs = sgns_mix(occ(pos));
+            const uint32_t eff = a.window - (uint32_t)(rs % a.window);                          // shrunk window, 1 .. window
+            const uint32_t lo = j - min(eff, j), hi = j + min(eff, nk - 1 - j);
+            for (uint32_t i = lo; i <= hi; i++) {
+                if (i == j) continue;
+                const uint32_t c = readfirst_u32(kpos[i]), ctx = readfirst_u32(knode[i]);
+                rs = sgns_mix(rs + c);
+                const float *v = syn0 + (uint64_t)ctx * a.dim;
+                float vin[PER];
+#pragma unroll
+                for (int s = 0; s < PER; s++) {
+                    const uint32_t k = (uint32_t)s * WAVE + lane;
+                    vin[s] = (s < PER - 1 || tail) ? v[k] : 0.0f;
+                }
+                for (uint32_t g0 = 0; g0 <= a.negative; g0 += SGNS_GROUP) {
+                    if (n_parked + SGNS_GROUP > WAVE) SGNS_EVAL_FLUSH();
+                    uint32_t tgt[SGNS_GROUP];
+                    uint32_t act = 0;                                  // bit t: target t is scored
+#pragma unroll
+                    for (int t = 0; t < SGNS_GROUP; t++) {
+                        const uint32_t ng = g0 + (uint32_t)t;
+                        const bool draw = ng != 0 && ng <= a.negative;
+                        const uint64_t next = sgns_mix(rs + ng);
+                        rs = draw ? next : rs;
+                        const uint32_t drawn = table[(uint32_t)(rs >> 16) % a.table_size];
+                        tgt[t] = draw ? drawn : centre;
+                        act |= (uint32_t)(ng <= a.negative && !(draw && drawn == centre)) << t;
+                    }
+                    float uu[SGNS_GROUP][PER];
+#pragma unroll
+                    for (int t = 0; t < SGNS_GROUP; t++) {
+                        const float *u = syn1 + (uint64_t)tgt[t] * a.dim;
+#pragma unroll
+                        for (int s = 0; s < PER; s++) {
+                            const uint32_t k = (uint32_t)s * WAVE + lane;
+                            uu[t][s] = (s < PER - 1 || tail) ? u[k] : 0.0f;
+                        }
+                    }
+#pragma unroll
+                    for (int t = 0; t < SGNS_GROUP; t++) {
+                        float dot = 0.0f;
+#pragma unroll
+                        for (int s = 0; s < PER; s++) dot += vin[s] * uu[t][s];
+                        dot = wave_sum(dot);
+                        const bool on = act >> t & 1u;
+                        const float x = g0 + (uint32_t)t == 0 ? -dot : dot;   // (the float64 of -dot is minus the float64 of dot)
+                        parked = (on && (uint32_t)lane == n_parked) ? x : parked;
+                        n_parked += on;
+                    }
+                }
+                n_pairs++;
+            }
+        }
+        SGNS_EVAL_FLUSH();
+#undef SGNS_EVAL_FLUSH
+#undef occ
+        if (a.counters && lane == 0 && nk) {
+            atomicAdd(&a.counters[0], (unsigned long long)nk);
+            atomicAdd(&a.counters[1], (unsigned long long)n_pairs);
+        }
+        if (lane == 0) {                                               // (one writer per cell; a walk without survivors writes zeros)
+            a.walk_loss[wk] = loss;
+            a.walk_evals[wk] = n_evals;
+        }
+    }
+}
+
 // The epoch's loss from the per-walk values, in an order that depends on nothing but their count: block b owns the indices
 // [b * chunk, (b + 1) * chunk), thread t of its 256 adds its indices t, t + 256, ... in ascending order, the 64 partial sums
 // of a wavefront meet in the xor butterfly 32 -> 1 and the four wavefront sums are added in wavefront order.  The host calls

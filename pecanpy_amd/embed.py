@@ -16,7 +16,8 @@ CPU restatement of the algorithm instead (tests/test_gpu_sgns.py, tests/test_gpu
 
 ``SgnsSession`` is the same trainer kept between launches (``pw_sgns``): epochs in slices, the loss of every epoch, both
 matrices, a checkpoint file, a new schedule on trained vectors (tests/test_gpu_sgns_session.py); ``sgns_session_file`` opens
-one on a corpus file.
+one on a corpus file.  ``SgnsSession.evaluate`` scores any walk matrix with the vectors as they are, by a read-only kernel, and
+``SgnsSession.set_walks`` puts another corpus of the same shape under the session (tests/test_gpu_sgns_eval.py).
 """
 import ctypes as C
 
@@ -141,7 +142,8 @@ class SgnsSession:
     """The trainer of ``train_sgns_device`` kept between launches (``pw_sgns``, include/pecanpy_amd.h): the vocabulary stage
     and the initialisation run once, in the constructor; ``run`` trains the next epochs of the learning-rate schedule, one
     launch each, and reports every epoch; both matrices can be read and replaced; ``save`` / ``restore`` checkpoint a run;
-    ``reschedule`` starts a new schedule on the trained vectors.  ``epochs`` is the LENGTH of the schedule: ``run(1)``
+    ``reschedule`` starts a new schedule on the trained vectors; ``evaluate`` scores walks without training and ``set_walks``
+    changes the corpus.  ``epochs`` is the LENGTH of the schedule: ``run(1)``
     ``epochs`` times, ``run(epochs)`` once and ``train_sgns_device(epochs=epochs)`` train the same vectors -- at ``workers=1``
     bit for bit, since every random choice is a hash of (seed, epoch, walk, position) and the learning rate a function of the
     position in the schedule.
@@ -238,6 +240,65 @@ class SgnsSession:
         _lib.check(_lib.load().pw_sgns_run(handle, epochs, C.cast(cells, C.c_void_p), C.cast(C.pointer(stats), C.c_void_p)))
         self.last_stats = stats.as_dict()
         return [c.as_dict() for c in cells]
+
+    # ---- scoring without training, another corpus
+    @staticmethod
+    def _walks_checked(d_walks):
+        """The constructor's tensor checks."""
+        import torch
+
+        if not isinstance(d_walks, torch.Tensor) or not d_walks.is_cuda or d_walks.dtype != torch.int32 or not d_walks.is_contiguous():
+            raise ValueError("d_walks must be a contiguous int32 CUDA tensor")
+        if d_walks.dim() != 2 or d_walks.shape[1] < 3:
+            raise ValueError("walk matrix must be int32[n_walks, walk_length + 2]")
+        return d_walks
+
+    def _walks_on_my_device(self, d_walks):
+        import torch
+
+        self._walks_checked(d_walks)
+        if d_walks.device != self.d_walks.device:
+            raise ValueError(f"d_walks must be on {self.d_walks.device}, not on {d_walks.device}")
+        torch.cuda.current_stream(d_walks.device).synchronize()  # the matrix was produced on torch's stream
+        return d_walks
+
+    def evaluate(self, d_walks=None, epoch=None):
+        """The loss of the vectors as they are on a walk matrix, nothing trained (``pw_sgns_evaluate``: a read-only kernel of
+        its own): the record ``run`` reports for an epoch -- ``loss``, ``evaluations``, ``kept_occurrences``,
+        ``trained_pairs`` (the pairs scored) -- of the evaluations that epoch ``epoch`` of a training run on that matrix
+        performs, against ``syn0`` / ``syn1`` unchanged.  ``d_walks=None``: the session's own matrix; any other matrix (the
+        constructor's tensor checks, the session's device) may have its own shape -- held-out walks.  ``epoch=None``:
+        ``state["epoch"]``, the epoch ``run`` would train next.  Works without ``compute_loss``.  Vectors, tables and state
+        are untouched, and the record is a function of (seed, epoch, matrix, vectors) bit for bit, whatever ``workers`` is."""
+        handle = self._open()
+        if d_walks is not None:
+            self._walks_on_my_device(d_walks)
+        if epoch is not None and int(epoch) < 0:
+            raise ValueError("epoch must not be negative")
+        epoch = self.state["epoch"] if epoch is None else int(epoch)
+        cell = _lib.PwSgnsEpoch()
+        if d_walks is None:
+            rc = _lib.load().pw_sgns_evaluate(handle, None, 0, 0, epoch, C.byref(cell))
+        else:
+            rc = _lib.load().pw_sgns_evaluate(handle, C.c_void_p(d_walks.data_ptr()), d_walks.shape[0], d_walks.shape[1] - 2, epoch,
+                                              C.byref(cell))
+        _lib.check(rc)
+        return cell.as_dict()
+
+    def set_walks(self, d_walks, recount=False):
+        """Train on another matrix from here on (``pw_sgns_set_walks``): ``d_walks`` passes the constructor's tensor checks,
+        is on the session's device and has the session's shape -- the schedule arithmetic stays; another shape is a
+        ``ValueError``.  ``recount=False``: the noise table and the keep probabilities stay those of the constructor's
+        matrix; ``recount=True``: they are rebuilt from the new one.  Vectors and state are untouched.  The session holds
+        a reference to the new matrix once the library has accepted it; on any error it keeps the old one."""
+        handle = self._open()
+        self._walks_on_my_device(d_walks)
+        if tuple(d_walks.shape) != tuple(self.d_walks.shape):
+            raise ValueError(f"the session was created on a matrix of shape {list(self.d_walks.shape)}, d_walks has the shape "
+                             f"{list(d_walks.shape)}: another shape needs a session of its own")
+        _lib.check(_lib.load().pw_sgns_set_walks(handle, C.c_void_p(d_walks.data_ptr()), d_walks.shape[0], d_walks.shape[1] - 2,
+                                                 _lib.PW_SGNS_RECOUNT if recount else 0))
+        self.d_walks = d_walks
 
     @property
     def state(self):

@@ -10,12 +10,59 @@ kernel, :164-210) and the per-mode ``move_forward`` closures are replaced by one
 """
 import numpy as np
 
+from .embed import SgnsSession
 from .engine import WalkEngine
 from .graph import BaseGraph, DenseGraph, SparseGraph
 from .wrappers import Timer
 
 __all__ = ["Base", "FirstOrderUnweighted", "PreCompFirstOrder", "PreComp", "SparseOTF", "DenseOTF",
-           "WalkCorpus"]
+           "WalkCorpus", "GraphSgnsSession"]
+
+
+class GraphSgnsSession(SgnsSession):
+    """What ``Base.embed_session(fresh_walks=..., holdout_walks=...)`` returns: an ``SgnsSession`` that knows its graph and
+    draws walks from it between epochs (see there for the seeds).  ``run(n)`` trains one epoch at a time; ``last_stats`` is
+    the last epoch's."""
+
+    def __init__(self, graph, num_walks, walk_length, fresh_walks, holdout_walks, **params):
+        self._graph, self._num_walks, self._walk_length, self._fresh = graph, num_walks, walk_length, fresh_walks
+        self.d_holdout = None
+        super().__init__(graph._session_walks(num_walks, walk_length, self._seed_of(0)), graph.num_nodes, **params)
+        self._corpus_epoch = 0          # the epoch whose corpus the session holds
+        try:
+            if holdout_walks:
+                r = graph.random_state
+                seed = None if r is None else (int(r) - 1) & 0xFFFFFFFF   # (r = 0: 2^32 - 1)
+                self.d_holdout = graph._session_walks(holdout_walks, walk_length, seed)
+        except Exception:
+            self.close()
+            raise
+
+    def _seed_of(self, epoch):
+        r = self._graph.random_state
+        return None if r is None else (int(r) + epoch) & 0xFFFFFFFF
+
+    def run(self, epochs=1):
+        st = self.state
+        epochs = int(epochs)
+        if epochs < 1 or st["sched_pos"] + epochs > st["sched_total"]:
+            return super().run(epochs)   # (the parent's error: nothing is drawn and nothing trained)
+        records = []
+        for _ in range(epochs):
+            epoch = self.state["epoch"]
+            if self._fresh and epoch != self._corpus_epoch:
+                self.set_walks(self._graph._session_walks(self._num_walks, self._walk_length, self._seed_of(epoch)))
+                self._corpus_epoch = epoch
+            record = super().run(1)[0]
+            if self.d_holdout is not None:
+                held = self.evaluate(self.d_holdout, epoch=0)
+                record["holdout_loss"], record["holdout_evaluations"] = held["loss"], held["evaluations"]
+            records.append(record)
+        return records
+
+    def close(self):
+        super().close()
+        self.d_holdout = None
 
 
 class WalkCorpus:
@@ -405,20 +452,44 @@ class Base(BaseGraph):
                                  "download_ms": (t3 - t2) * 1e3, **train_sgns_device.last_stats}
         return vec
 
-    def embed_session(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0, compute_loss=False):
+    def _session_walks(self, num_walks, walk_length, call_seed="own"):
+        """``_device_walks`` for a session, drawn with the call seed ``call_seed`` in place of ``random_state`` when one is
+        given (``None``: a new OS seed); ``NotImplementedError`` where there is no device matrix."""
+        saved = self.random_state
+        if call_seed != "own":
+            self.random_state = call_seed
+        try:
+            d_walks = self._device_walks(num_walks, walk_length)
+        finally:
+            self.random_state = saved
+        if d_walks is None:
+            raise NotImplementedError("embed_session needs the walk matrix on one device: not under torch.distributed or "
+                                      "with the in-process multi-GPU engine")
+        return d_walks
+
+    def embed_session(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0, compute_loss=False,
+                      fresh_walks=False, holdout_walks=0):
         """The walks of ``embed_array`` generated in device memory and a ``pecanpy_amd.embed.SgnsSession`` on them, nothing
         trained yet: ``session.run()`` trains the schedule of ``epochs`` epochs in slices and reports every epoch (with
         ``compute_loss`` its loss), ``session.vectors()`` is ``float32[num_nodes, dim]`` in node order on the device.
         ``session.run(epochs)`` trains what ``embed_array`` trains.  Under ``torch.distributed`` and with the in-process
-        multi-GPU engine there is no device matrix to hold a session on: ``NotImplementedError``."""
+        multi-GPU engine there is no device matrix to hold a session on: ``NotImplementedError``.
+
+        ``fresh_walks`` / ``holdout_walks``: the session is a ``GraphSgnsSession``, which knows this graph.  The corpus of
+        epoch ``e`` is the walk matrix of this graph with call seed ``random_state + e`` (mod 2^32; ``random_state=None``: a
+        new OS seed per epoch).  With ``fresh_walks`` every epoch after the first trains on its own corpus, drawn in device
+        memory just before it (``set_walks``, the tables of the first corpus kept).  With ``holdout_walks = h > 0`` a
+        matrix of ``h`` walks per node is drawn once, with call seed ``random_state - 1`` (2^32 - 1 for ``random_state=0``),
+        and every epoch's record gains ``holdout_loss`` and ``holdout_evaluations``: ``evaluate`` on that matrix after the
+        epoch, always with ``epoch=0`` -- the same evaluations every time, so the figures compare across epochs."""
         from .embed import SgnsSession
 
-        d_walks = self._device_walks(num_walks, walk_length)
-        if d_walks is None:
-            raise NotImplementedError("embed_session needs the walk matrix on one device: not under torch.distributed or "
-                                      "with the in-process multi-GPU engine")
-        return SgnsSession(d_walks, self.num_nodes, dim=dim, window=window_size, epochs=epochs, seed=self.random_state,
-                           workers=workers, compute_loss=compute_loss)
+        params = dict(dim=dim, window=window_size, epochs=epochs, seed=self.random_state, workers=workers, compute_loss=compute_loss)
+        if not fresh_walks and not holdout_walks:
+            return SgnsSession(self._session_walks(num_walks, walk_length), self.num_nodes, **params)
+        if int(holdout_walks) < 0:
+            raise ValueError("holdout_walks must not be negative")
+        return GraphSgnsSession(self, num_walks, walk_length, bool(fresh_walks), int(holdout_walks), **params)
 
     def embed_to_file(self, path, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0):
         """``embed_array`` + ``save_word2vec_format`` without the vectors visiting the host: walks, trainer and the device
