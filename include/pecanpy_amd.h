@@ -415,6 +415,23 @@ int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, 
  *                          the keep probabilities stay those of the create call; PW_SGNS_RECOUNT: they are rebuilt from the new
  *                          matrix by the create call's own path.  The state and both matrices are not touched.  On any error
  *                          the session keeps the old matrix and all its tables.
+ *   pw_sgns_set_locks / pw_sgns_get_locks
+ *                          frozen rows.  d_lock0 / d_lock1: device uint8[n_nodes] on the handle's device, non-zero = the row of
+ *                          syn0 / syn1 is frozen; NULL = no row of that matrix.  The masks are COPIED (packed to bits by a small
+ *                          kernel, one ballot per 64 rows: bit r % 32 of word r / 32 covers row r, the bits at and beyond n_nodes
+ *                          in the last word are zero), not borrowed, and the handle owns the bit arrays.  A call replaces the
+ *                          locks of BOTH matrices; a mask without a non-zero byte counts as NULL.  A frozen row is read by every
+ *                          pair that names it and never written: pw_sgns_run then launches the LOCK instances of the kernel, which
+ *                          evaluate exactly what the others evaluate -- the same pairs, draws, dot products, loss terms, counters
+ *                          -- skip the store of a frozen row, and still let a free context row learn from a frozen target.  With no
+ *                          row frozen in either matrix pw_sgns_run launches the kernel without locks, bit for bit what a handle
+ *                          that never had locks runs.  Locks survive pw_sgns_run, pw_sgns_set_state, pw_sgns_vectors_set,
+ *                          pw_sgns_set_walks (with and without PW_SGNS_RECOUNT) and pw_sgns_evaluate; they do NOT protect against
+ *                          pw_sgns_vectors_set, which replaces a matrix wholesale as before.  On any error the handle keeps the
+ *                          locks it had.  get_locks writes them back as uint8[n_nodes] 0 / 1, zeros where none; either pointer
+ *                          may be NULL.
+ *   pw_sgns_lock_info      out[0] / out[1]: frozen rows of syn0 / syn1; out[2]: 1 when the last pw_sgns_run launched the LOCK
+ *                          instances, 0 when it launched the kernel without locks (or nothing ran yet).
  *   pw_sgns_destroy        frees what the handle owns; NULL is allowed. */
 enum { PW_SGNS_LOSS = 1 };
 enum { PW_SGNS_RECOUNT = 1 };
@@ -438,6 +455,9 @@ int pw_sgns_vectors_get(pw_sgns *s, int which, float *d_ptr);
 int pw_sgns_vectors_set(pw_sgns *s, int which, const float *d_ptr);
 int pw_sgns_evaluate(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint64_t epoch, pw_sgns_epoch *out);
 int pw_sgns_set_walks(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t flags);
+int pw_sgns_set_locks(pw_sgns *s, const uint8_t *d_lock0, const uint8_t *d_lock1);
+int pw_sgns_get_locks(const pw_sgns *s, uint8_t *d_lock0, uint8_t *d_lock1);
+int pw_sgns_lock_info(const pw_sgns *s, uint64_t out[3]);
 void pw_sgns_destroy(pw_sgns *s);
 
 /* ---- the embedding file written from device memory (csrc/emb_text.hip.h) --------------------------------------------------

@@ -229,6 +229,9 @@ SYMBOLS = {
     "pw_sgns_vectors_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pw_sgns_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(PwSgnsEpoch)]),
     "pw_sgns_set_walks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "pw_sgns_set_locks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pw_sgns_get_locks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pw_sgns_lock_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pw_sgns_destroy": (None, [C.c_void_p]),
     "pw_vectors_write_text_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p,
                                                C.POINTER(PwEmbWriteStats)]),

@@ -52,6 +52,14 @@ _OPTIONS = (
                                                      "(call seed random_state + epoch); implies the route of --epoch_loss")),
     ("--holdout_walks", dict(type=int, default=0, help="GPU trainer only: draw this many held-out walks per node once and print "
                                                        "their mean loss after every epoch; implies the route of --epoch_loss")),
+    ("--init_emb", dict(default=None, metavar="FILE",
+                        help="GPU trainer only: embed new nodes into old vectors -- an .npz with IDs / data as this program writes "
+                             "it, or a word2vec text file; its nodes start from these vectors, the others from the seeded "
+                             "initialisation; implies the route of --epoch_loss")),
+    ("--freeze_init", dict(action="store_true", help="with --init_emb: the given vectors stay exactly as they are, only the other "
+                                                     "nodes are trained")),
+    ("--walks_from", dict(default="new", choices=("new", "all"),
+                          help="with --init_emb: walks start from the nodes the file does not have (new) or from every node (all)")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
     ("--implicit_ids", dict(action="store_true", help=".npz without IDs: use 0..N-1")),
 )
@@ -228,7 +236,15 @@ def walks_to_file(args, g):
 def embed_on_gpu(args, g):
     """Walks and skip-gram in device memory (``Base.embed_array``), the vectors written as ``learn_embeddings`` writes
     them; no ``List[List[str]]`` corpus and no index matrix on the host."""
-    if args.epoch_loss or args.fresh_walks or args.holdout_walks:
+    if args.init_emb:
+        known_ids, vectors = _known_vectors(g, *read_init_emb(args.init_emb))
+        with g.extend_session(known_ids, vectors, starts=args.walks_from, freeze=args.freeze_init, num_walks=args.num_walks,
+                              walk_length=args.walk_length, window_size=args.window_size, epochs=args.epochs,
+                              workers=_session_workers(args), compute_loss=True, fresh_walks=args.fresh_walks,
+                              holdout_walks=args.holdout_walks) as session:
+            _print_epoch_loss(session.run(args.epochs))
+            vecs = session.vectors().cpu().numpy()
+    elif args.epoch_loss or args.fresh_walks or args.holdout_walks:
         with g.embed_session(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
                              window_size=args.window_size, epochs=args.epochs, workers=_session_workers(args),
                              compute_loss=True, fresh_walks=args.fresh_walks, holdout_walks=args.holdout_walks) as session:
@@ -238,6 +254,39 @@ def embed_on_gpu(args, g):
         vecs = g.embed_array(dim=args.dimensions, num_walks=args.num_walks, walk_length=args.walk_length,
                              window_size=args.window_size, epochs=args.epochs)
     _save_vectors(args, g, vecs)
+
+
+def read_init_emb(path):
+    """``(ids, float32[n, dim])`` of an embedding file: an ``.npz`` with ``IDs`` / ``data`` as this program writes it, or a
+    word2vec text file (a header line ``count dim``, then a name and ``dim`` numbers per line).  Read on the host."""
+    if path.endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            ids, data = [str(i) for i in z["IDs"].tolist()], np.ascontiguousarray(z["data"], dtype=np.float32)
+    else:
+        with open(path, encoding="utf-8") as f:
+            count, dim = (int(x) for x in f.readline().split())
+            rows = [line.rstrip("\n").split(" ") for line in f if line.strip()]
+        if len(rows) != count or any(len(r) != dim + 1 for r in rows):
+            raise ValueError(f"{path}: the header announces {count} rows of {dim} numbers, the file holds something else")
+        ids = [r[0] for r in rows]
+        data = np.array([r[1:] for r in rows], dtype=np.float32).reshape(count, dim)
+    if data.ndim != 2 or data.shape[0] != len(ids):
+        raise ValueError(f"{path}: {len(ids)} IDs for a data array of shape {list(data.shape)}")
+    return ids, data
+
+
+def _known_vectors(g, ids, data):
+    """The rows of an ``--init_emb`` file that name a node of the graph; the others are dropped with one warning."""
+    have = set(g.nodes)
+    keep = [i for i, name in enumerate(ids) if name in have]
+    if len(keep) != len(ids):
+        warnings.warn(f"--init_emb: {len(ids) - len(keep)} of {len(ids)} IDs are not in the graph and are dropped", stacklevel=3)
+    return [ids[i] for i in keep], np.ascontiguousarray(data[keep])
+
+
+def _warn_init_flags_ignored(args, why):
+    if args.init_emb or args.freeze_init:
+        warnings.warn(f"--init_emb, --freeze_init and --walks_from belong to the GPU trainer on a graph; {why}", stacklevel=3)
 
 
 def _session_workers(args):
@@ -265,6 +314,7 @@ def train_from_corpus(args):
     if args.fresh_walks or args.holdout_walks:
         warnings.warn("--fresh_walks and --holdout_walks draw walks from a graph; --task train has none, so they are ignored",
                       stacklevel=2)
+    _warn_init_flags_ignored(args, "--task train has no graph, so they are ignored")
 
     if args.epoch_loss:
         names, session = sgns_session_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
@@ -304,6 +354,7 @@ def main(argv=None):
         if args.fresh_walks or args.holdout_walks:
             warnings.warn("--fresh_walks and --holdout_walks belong to the GPU trainer; gensim is importable (or the walks are "
                           "dumped), so that route runs as without the flags", stacklevel=2)
+        _warn_init_flags_ignored(args, "gensim is importable (or the walks are dumped), so that route runs as without the flags")
         learn_embeddings(args, simulate_walks(args, g), g)
 
 

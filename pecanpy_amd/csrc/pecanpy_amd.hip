@@ -38,6 +38,7 @@
 #include "walk_sparse.hip.h"
 #include "walk_lanes.hip.h"
 #include "sgns.hip.h"
+#include "sgns_locks.hpp"
 #include "coo_csr.hip.h"
 #include "edgelist_dev.hip.h"
 #include "corpus_dev.hip.h"
@@ -4348,22 +4349,32 @@ PW_EXPORT int pw_probs(pw_graph *g, int mode, double p, double q, int extend, ui
 }
 
 // ---- skip-gram with negative sampling over a walk matrix (sgns.hip.h) -------------------------
-template <int PER, bool LOSS>
+template <int PER, bool LOSS, bool LOCK>
 static void sgns_launch(unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
-    hipLaunchKernelGGL((pw::sgns_walk_kernel<PER, LOSS>), dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep);
+    if constexpr (LOCK)
+        hipLaunchKernelGGL((pw::sgns_walk_kernel<PER, LOSS, true, uint32_t, uint32_t>), dim3(blocks), dim3(threads), lds, 0, a, a.walks,
+                           a.table, a.keep, a.lock0, a.lock1);
+    else
+        hipLaunchKernelGGL((pw::sgns_walk_kernel<PER, LOSS>), dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep);
 }
-template <bool LOSS>
+template <bool LOSS, bool LOCK>
 static void sgns_launch_per(int per, unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
     switch (per) {   // one instance per count of components per lane: only the last component needs a lane guard
-    case 1: sgns_launch<1, LOSS>(blocks, threads, lds, a); break;
-    case 2: sgns_launch<2, LOSS>(blocks, threads, lds, a); break;
-    case 3: sgns_launch<3, LOSS>(blocks, threads, lds, a); break;
-    case 4: sgns_launch<4, LOSS>(blocks, threads, lds, a); break;
-    case 5: sgns_launch<5, LOSS>(blocks, threads, lds, a); break;
-    case 6: sgns_launch<6, LOSS>(blocks, threads, lds, a); break;
-    case 7: sgns_launch<7, LOSS>(blocks, threads, lds, a); break;
-    default: sgns_launch<8, LOSS>(blocks, threads, lds, a); break;
+    case 1: sgns_launch<1, LOSS, LOCK>(blocks, threads, lds, a); break;
+    case 2: sgns_launch<2, LOSS, LOCK>(blocks, threads, lds, a); break;
+    case 3: sgns_launch<3, LOSS, LOCK>(blocks, threads, lds, a); break;
+    case 4: sgns_launch<4, LOSS, LOCK>(blocks, threads, lds, a); break;
+    case 5: sgns_launch<5, LOSS, LOCK>(blocks, threads, lds, a); break;
+    case 6: sgns_launch<6, LOSS, LOCK>(blocks, threads, lds, a); break;
+    case 7: sgns_launch<7, LOSS, LOCK>(blocks, threads, lds, a); break;
+    default: sgns_launch<8, LOSS, LOCK>(blocks, threads, lds, a); break;
     }
+}
+// (the LOCK instances only when a row of either matrix is frozen: without locks a run is the LOCK = false kernel)
+template <bool LOSS>
+static void sgns_launch_lock(bool lock, int per, unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
+    if (lock) sgns_launch_per<LOSS, true>(per, blocks, threads, lds, a);
+    else sgns_launch_per<LOSS, false>(per, blocks, threads, lds, a);
 }
 
 // A trainer between launches: the two matrices, the tables of the vocabulary stage, the launch geometry, and where the run
@@ -4390,6 +4401,10 @@ struct pw_sgns {
     DevBuf<double> eval_walk_loss, eval_block_loss;
     DevBuf<unsigned long long> eval_walk_evals, eval_block_evals;
     DevBuf<pw_sgns_epoch> eval_out;
+    // pw_sgns_set_locks: the frozen rows of syn0 / syn1 as bits (a.lock0 / a.lock1 point here); not allocated = no row frozen
+    DevBuf<uint32_t> lock0, lock1;
+    uint64_t n_locked[2] = {0, 0};
+    bool ran_locked = false;                 // the last pw_sgns_run launched the LOCK instances
 };
 static_assert(offsetof(pw_sgns_epoch, kept_occurrences) + sizeof(uint64_t) == offsetof(pw_sgns_epoch, trained_pairs),
               "the kernel's two counters are consecutive cells of an epoch's record");
@@ -4520,6 +4535,7 @@ PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_
     a.syn0 = s->syn0.p; a.syn1 = s->syn1.p; a.table = s->table.p; a.table_size = table_size; a.keep = s->keep.p;
     a.alpha = alpha; a.min_alpha = min_alpha; a.item_base = 0; a.lr_base = 0; a.lr_total = n_items * epochs; a.seed = seed;
     a.counters = nullptr; a.walk_loss = s->walk_loss.p; a.walk_evals = s->walk_evals.p;
+    a.lock0 = a.lock1 = nullptr;
     s->n_items = n_items;
     s->st.epoch = 0; s->st.sched_pos = 0; s->st.sched_total = epochs; s->st.alpha = alpha; s->st.min_alpha = min_alpha;
     // concurrency.  workers == 1: ONE wavefront takes the walks in order (deterministic: the run gensim's workers=1
@@ -4558,15 +4574,17 @@ PW_EXPORT int pw_sgns_run(pw_sgns *s, uint32_t n_epochs, pw_sgns_epoch *per_epoc
     a.alpha = s->st.alpha; a.min_alpha = s->st.min_alpha; a.lr_total = s->n_items * s->st.sched_total;
     const int per = (int)((a.dim + 63) / 64);
     const unsigned n_blocks = (unsigned)((a.n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
+    const bool lock = a.lock0 || a.lock1;
+    s->ran_locked = lock;
     (void)hipEventRecord(s->ev0, 0);
     for (uint32_t i = 0; i < n_epochs; i++) {
         a.item_base = s->n_items * (s->st.epoch + i);
         a.lr_base = s->n_items * (s->st.sched_pos + i);
         pw_sgns_epoch *cell = s->epoch_out.p + i;
         a.counters = (unsigned long long *)&cell->kept_occurrences;
-        if (!s->loss) sgns_launch_per<false>(per, s->blocks, s->threads, s->lds, a);
+        if (!s->loss) sgns_launch_lock<false>(lock, per, s->blocks, s->threads, s->lds, a);
         else {
-            sgns_launch_per<true>(per, s->blocks, s->threads, s->lds, a);
+            sgns_launch_lock<true>(lock, per, s->blocks, s->threads, s->lds, a);
             hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(n_blocks), dim3(256), 0, 0, s->walk_loss.p, s->walk_evals.p, a.n_walks,
                                (uint64_t)pw::SGNS_LOSS_CHUNK, s->block_loss.p, s->block_evals.p);
             hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(1), dim3(256), 0, 0, s->block_loss.p, s->block_evals.p, (uint64_t)n_blocks,
@@ -4704,6 +4722,66 @@ static int sgns_vectors_copy(pw_sgns *s, int which, float *d_ptr, bool out) {
 }
 PW_EXPORT int pw_sgns_vectors_get(pw_sgns *s, int which, float *d_ptr) { return sgns_vectors_copy(s, which, d_ptr, true); }
 PW_EXPORT int pw_sgns_vectors_set(pw_sgns *s, int which, const float *d_ptr) { return sgns_vectors_copy(s, which, (float *)d_ptr, false); }
+
+// The byte mask of one matrix packed into bits; `words` is left unallocated when no byte is set.
+static int sgns_pack_locks(uint32_t n_nodes, const uint8_t *d_mask, DevBuf<unsigned long long> &n_set, DevBuf<uint32_t> *words,
+                           uint64_t *count) {
+    *count = 0;
+    if (!d_mask) return PW_OK;
+    hipError_t e = words->alloc(pw::sgns_lock_words(n_nodes));
+    if (e == hipSuccess) e = hipMemset(n_set.p, 0, sizeof(unsigned long long));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_set_locks: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(pw::sgns_lock_pack_kernel, dim3(pw::sgns_lock_blocks(n_nodes)), dim3(pw::SGNS_LOCK_THREADS), 0, 0, d_mask, n_nodes,
+                       words->p, n_set.p);
+    unsigned long long n = 0;
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(&n, n_set.p, sizeof(n), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_set_locks: ") + hipGetErrorString(e));
+    if (!n) words->release();   // (a mask without a non-zero byte is "none")
+    *count = n;
+    return PW_OK;
+}
+
+// Everything that can fail comes before the first assignment: on an error the session keeps the locks it had.
+PW_EXPORT int pw_sgns_set_locks(pw_sgns *s, const uint8_t *d_lock0, const uint8_t *d_lock1) {
+    if (!s) return fail(PW_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf<unsigned long long> n_set;
+    if (hipError_t e = n_set.alloc(1)) return fail(PW_ERR_HIP, std::string("pw_sgns_set_locks: ") + hipGetErrorString(e));
+    DevBuf<uint32_t> w0, w1;
+    uint64_t n0 = 0, n1 = 0;
+    if (int rc = sgns_pack_locks(s->n_nodes, d_lock0, n_set, &w0, &n0)) return rc;
+    if (int rc = sgns_pack_locks(s->n_nodes, d_lock1, n_set, &w1, &n1)) return rc;
+    s->lock0 = std::move(w0); s->lock1 = std::move(w1);
+    s->a.lock0 = s->lock0.p; s->a.lock1 = s->lock1.p;
+    s->n_locked[0] = n0; s->n_locked[1] = n1;
+    return PW_OK;
+}
+
+PW_EXPORT int pw_sgns_get_locks(const pw_sgns *s, uint8_t *d_lock0, uint8_t *d_lock1) {
+    if (!s) return fail(PW_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t *words[2] = {s->lock0.p, s->lock1.p};
+    uint8_t *outs[2] = {d_lock0, d_lock1};
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < 2 && e == hipSuccess; m++) {
+        if (!outs[m]) continue;
+        if (!words[m]) e = hipMemset(outs[m], 0, s->n_nodes);
+        else
+            hipLaunchKernelGGL(pw::sgns_lock_unpack_kernel, dim3(pw::sgns_lock_blocks(s->n_nodes)), dim3(pw::SGNS_LOCK_THREADS), 0, 0, words[m],
+                               s->n_nodes, outs[m]);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_get_locks: ") + hipGetErrorString(e));
+    return PW_OK;
+}
+
+PW_EXPORT int pw_sgns_lock_info(const pw_sgns *s, uint64_t out[3]) {
+    if (!s || !out) return fail(PW_ERR_INVALID, "null pointer");
+    out[0] = s->n_locked[0]; out[1] = s->n_locked[1]; out[2] = s->ran_locked ? 1 : 0;
+    return PW_OK;
+}
 
 PW_EXPORT void pw_sgns_destroy(pw_sgns *s) {
     if (!s) return;

@@ -27,6 +27,8 @@
 // (seed, epoch, walk, position), equal the restatement's counts in any run, a racing one with negatives included.  What
 // a racing run's vectors are compared by stays statistical (similarity structure, tests/test_gpu_sgns.py).
 // The kernel writes global memory through vector stores only; the two counters are per-lane atomics of lane 0, once per walk.
+// Frozen rows (the LOCK instances): a row whose bit is set in lock0 / lock1 is read like any other and never stored; what is
+// evaluated -- pairs, draws, dot, loss, g, counters -- is what the LOCK = false instance evaluates on the same values.
 #pragma once
 #include <cstddef>
 #include "wave.h"
@@ -50,6 +52,8 @@ struct SgnsArgs {
     unsigned long long *counters;         // [0] occurrences that survived the subsampling, [1] (centre, context) pairs trained
     double *walk_loss;                    // LOSS instances: [n_walks] sum of the loss terms of a walk's evaluations, one writer each
     unsigned long long *walk_evals;       // LOSS instances: [n_walks] number of those evaluations
+    // LOCK instances: frozen rows of syn0 / syn1, bit r % 32 of word r / 32 covers row r; nullptr = no row of that matrix
+    const uint32_t *__restrict__ lock0, *__restrict__ lock1;
 };
 
 __device__ __forceinline__ uint64_t sgns_mix(uint64_t x) {
@@ -76,11 +80,25 @@ __host__ __device__ inline size_t sgns_lds_bytes_per_wave(uint32_t L) { return s
 // term.  `dot` is wave-uniform after wave_sum: every lane carries the same sum and lane 0 stores it, once per walk, with
 // plain vector stores.  The update arithmetic is the same instructions on the same values; the LOSS = false instances are
 // the kernel without any of this.
-template <int PER, bool LOSS = false>
+// LOCK: rows can be frozen.  The row index of a pair's context (`ctx`) and of every target (`tgt[t]`) is wave-uniform, so its
+// lock bit is one scalar-cache read: the context's with the pair, those of a group's SGNS_GROUP targets together, right after
+// the table reads that name them.  A frozen syn0 row skips the store of `v` at the end of the pair; a frozen syn1 row skips
+// the store of `u` and still adds g * u to `acc`, so a free context row learns from a frozen target.  A frozen target that
+// repeats inside a group is read again like a free one: nothing wrote it, the values are the same.  Everything else --
+// ballot, window, the chain `rs`, `dot`, the loss term, `sig`, `g`, `lr`, the counters -- is the same code: a lock changes what
+// is written, not what is evaluated.  The LOCK = false instances never look at lock0 / lock1 and are the kernel without any of
+// this; the driver launches them whenever no row of either matrix is frozen.  They keep the kernel's four arguments: the two
+// lock arguments are a pack (LK = uint32_t, uint32_t) that only the LOCK instances have.
+__device__ __forceinline__ const uint32_t *sgns_lock_arg(int) { return nullptr; }
+__device__ __forceinline__ const uint32_t *sgns_lock_arg(int which, const uint32_t *lock0, const uint32_t *lock1) { return which ? lock1 : lock0; }
+template <int PER, bool LOSS = false, bool LOCK = false, typename... LK>
 __global__ void __launch_bounds__(256)
-sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t *__restrict__ table, const float *__restrict__ keep) {
-    // (walks / table / keep once more as arguments of their own: __restrict__ on a kernel argument is what lets the compiler
-    // read them through the scalar cache although the loop stores to syn0 / syn1)
+sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t *__restrict__ table, const float *__restrict__ keep,
+                 const LK *__restrict__... lk) {
+    // (walks / table / keep / the lock words once more as arguments of their own: __restrict__ on a kernel argument is what
+    // lets the compiler read them through the scalar cache although the loop stores to syn0 / syn1)
+    static_assert(sizeof...(LK) == (LOCK ? 2 : 0), "lock0 and lock1 are arguments of the LOCK instances and of no other");
+    const uint32_t *const lock0 = sgns_lock_arg(0, lk...), *const lock1 = sgns_lock_arg(1, lk...);
     extern __shared__ uint32_t sgns_lds[];
     const int lane = lane_id();
     const uint32_t wib = readfirst_u32(threadIdx.x / WAVE), wpb = blockDim.x / WAVE;   // (uniform: walk state lives in SGPRs)
@@ -136,6 +154,8 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
                 const uint32_t c = readfirst_u32(kpos[i]), ctx = readfirst_u32(knode[i]);
                 rs = sgns_mix(rs + c);
                 float *v = a.syn0 + (uint64_t)ctx * a.dim;
+                bool vlock = false;                                    // (uniform) the context's row of syn0 is frozen
+                if (LOCK && lock0) vlock = lock0[ctx >> 5] >> (ctx & 31u) & 1u;
                 float vin[PER], acc[PER];
 #pragma unroll
                 for (int s = 0; s < PER; s++) {
@@ -157,6 +177,11 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
                         const uint32_t drawn = table[(uint32_t)(rs >> 16) % a.table_size];
                         tgt[t] = draw ? drawn : centre;
                         act |= (uint32_t)(ng <= a.negative && !(draw && drawn == centre)) << t;
+                    }
+                    uint32_t ulock = 0;                                // bit t: target t's row of syn1 is frozen
+                    if (LOCK && lock1) {
+#pragma unroll
+                        for (int t = 0; t < SGNS_GROUP; t++) ulock |= (lock1[tgt[t] >> 5] >> (tgt[t] & 31u) & 1u) << t;
                     }
                     uint32_t again = 0;                                // bit t: an earlier target of the group writes row t first
 #pragma unroll
@@ -202,7 +227,7 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
                             const uint32_t k = (uint32_t)s * WAVE + lane;
                             if (s < PER - 1 || tail) {
                                 acc[s] += g * uu[t][s];
-                                u[k] = uu[t][s] + g * vin[s];
+                                if (!(LOCK && (ulock >> t & 1u))) u[k] = uu[t][s] + g * vin[s];
                             }
                         }
                     }
@@ -210,7 +235,7 @@ sgns_walk_kernel(SgnsArgs a, const uint32_t *__restrict__ walks, const uint32_t 
 #pragma unroll
                 for (int s = 0; s < PER; s++) {
                     const uint32_t k = (uint32_t)s * WAVE + lane;
-                    if (s < PER - 1 || tail) v[k] = vin[s] + acc[s];
+                    if ((s < PER - 1 || tail) && !(LOCK && vlock)) v[k] = vin[s] + acc[s];
                 }
                 n_pairs++;
             }
@@ -392,6 +417,26 @@ sgns_loss_reduce_kernel(const double *__restrict__ in_loss, const unsigned long 
         out_loss[blockIdx.x] = ((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3];
         out_evals[blockIdx.x] = s_evals[0] + s_evals[1] + s_evals[2] + s_evals[3];
     }
+}
+
+// The lock bits of one matrix from a byte mask (non-zero = frozen): a wavefront takes 64 rows, one ballot, and its lane 0
+// stores the two words; rows at and beyond n_rows vote 0, so the bits past the end of the last word are zero.  `words` holds
+// 2 * ceil(n_rows / 64) cells.  n_set[0] += the rows frozen (one atomic per wavefront that has any).
+__global__ void __launch_bounds__(256)
+sgns_lock_pack_kernel(const uint8_t *__restrict__ mask, uint32_t n_rows, uint32_t *__restrict__ words, unsigned long long *n_set) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t m = ballot(r < n_rows && mask[r < n_rows ? r : 0] != 0);
+    if (lane_id() == 0 && (r & ~63ull) < n_rows) {
+        words[r >> 5] = (uint32_t)m;
+        words[(r >> 5) + 1] = (uint32_t)(m >> 32);
+        if (m) atomicAdd(n_set, (unsigned long long)__popcll(m));
+    }
+}
+// ... and back: mask[r] = bit r, as 0 / 1
+__global__ void __launch_bounds__(256)
+sgns_lock_unpack_kernel(const uint32_t *__restrict__ words, uint32_t n_rows, uint8_t *__restrict__ mask) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_rows) mask[r] = (uint8_t)(words[r >> 5] >> (r & 31u) & 1u);
 }
 
 // word counts of a walk matrix (vocabulary statistics for the sampling table and the subsampling probabilities);

@@ -143,7 +143,8 @@ class SgnsSession:
     and the initialisation run once, in the constructor; ``run`` trains the next epochs of the learning-rate schedule, one
     launch each, and reports every epoch; both matrices can be read and replaced; ``save`` / ``restore`` checkpoint a run;
     ``reschedule`` starts a new schedule on the trained vectors; ``evaluate`` scores walks without training and ``set_walks``
-    changes the corpus.  ``epochs`` is the LENGTH of the schedule: ``run(1)``
+    changes the corpus; ``freeze`` keeps chosen rows of either matrix exactly as they are while the others train.
+    ``epochs`` is the LENGTH of the schedule: ``run(1)``
     ``epochs`` times, ``run(epochs)`` once and ``train_sgns_device(epochs=epochs)`` train the same vectors -- at ``workers=1``
     bit for bit, since every random choice is a hash of (seed, epoch, walk, position) and the learning rate a function of the
     position in the schedule.
@@ -239,7 +240,88 @@ class SgnsSession:
         stats = _lib.PwSgnsStats()
         _lib.check(_lib.load().pw_sgns_run(handle, epochs, C.cast(cells, C.c_void_p), C.cast(C.pointer(stats), C.c_void_p)))
         self.last_stats = stats.as_dict()
+        self.last_stats["lock_instances"] = bool(self._lock_info()[2])
         return [c.as_dict() for c in cells]
+
+    # ---- frozen rows
+    def _lock_info(self):
+        """``pw_sgns_lock_info``: frozen rows of ``syn0``, of ``syn1``, and whether the last run launched the kernel's lock
+        instances."""
+        out = (C.c_uint64 * 3)()
+        _lib.check(_lib.load().pw_sgns_lock_info(self._open(), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def _row_mask(self, rows, name):
+        """``rows`` -- a bool mask of length ``num_nodes`` or an integer index array or tensor, on the host or on the
+        session's device -- as a uint8 CUDA tensor ``[num_nodes]``; every complaint is a ``ValueError``."""
+        import torch
+
+        dev = self.d_walks.device
+        if isinstance(rows, torch.Tensor):
+            if rows.device.type not in ("cpu", "cuda") or (rows.is_cuda and rows.device != dev):
+                raise ValueError(f"{name} must be on the host or on {dev}, not on {rows.device}")
+        else:
+            rows = np.asarray(rows)
+            if rows.dtype == object or rows.dtype.kind not in "biu":
+                raise ValueError(f"{name} must be a bool mask or integer indices, not {rows.dtype}")
+            if rows.dtype.kind == "u":   # (torch has no wide unsigned integers)
+                if rows.size and int(rows.max()) >= self.num_nodes:
+                    raise ValueError(f"{name} holds an index outside 0..{self.num_nodes - 1}")
+                rows = rows.astype(np.int64)
+            rows = torch.from_numpy(np.ascontiguousarray(rows))
+        if rows.dtype.is_floating_point or rows.dtype.is_complex:
+            raise ValueError(f"{name} must be a bool mask or integer indices, not {rows.dtype}")
+        if rows.dim() != 1:
+            raise ValueError(f"{name} must have one dimension, not {rows.dim()}")
+        if rows.dtype == torch.bool:
+            if rows.numel() != self.num_nodes:
+                raise ValueError(f"a mask must have num_nodes = {self.num_nodes} entries, {name} has {rows.numel()}")
+            return rows.to(dev).to(torch.uint8).contiguous()
+        rows = rows.to(dev).to(torch.int64)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self.num_nodes):
+            raise ValueError(f"{name} holds an index outside 0..{self.num_nodes - 1}")
+        mask = torch.zeros(self.num_nodes, dtype=torch.uint8, device=dev)
+        mask[rows] = 1
+        return mask
+
+    def freeze(self, rows, context=True):
+        """Freeze rows (``pw_sgns_set_locks``): a frozen row is read by every pair that names it and never written, so it
+        keeps its bits however long the session trains, while the other rows train on exactly the evaluations an unfrozen
+        session performs -- pairs, negatives, loss and counters are unchanged, and a free context row still learns from a
+        frozen target.  ``rows``: a bool mask of length ``num_nodes`` or an integer index array or tensor, on the host or on
+        the session's device: the rows of ``syn0`` (``vectors()``).  ``context=True`` freezes the same rows of ``syn1``
+        (``context_vectors()``), ``context=False`` leaves ``syn1`` free, a mask or index array freezes those rows of ``syn1``
+        instead.  Replaces what was frozen before.  Locks survive ``run``, ``reschedule``, ``set_walks``, ``evaluate`` and
+        ``load``; ``load`` still replaces a matrix wholesale, frozen rows included.  A mask of the wrong length, an index
+        outside ``0..num_nodes-1``, a tensor on another GPU, a floating-point dtype and a closed session are ``ValueError``s
+        that change nothing."""
+        import torch
+
+        handle = self._open()
+        m0 = self._row_mask(rows, "rows")
+        if context is True:
+            m1 = m0
+        elif context is False or context is None:
+            m1 = None
+        else:
+            m1 = self._row_mask(context, "context")
+        torch.cuda.current_stream(self.d_walks.device).synchronize()
+        _lib.check(_lib.load().pw_sgns_set_locks(handle, C.c_void_p(m0.data_ptr()), C.c_void_p(m1.data_ptr()) if m1 is not None else None))
+
+    def unfreeze(self):
+        """No row of either matrix is frozen from here on: ``run`` launches the kernel without locks again."""
+        _lib.check(_lib.load().pw_sgns_set_locks(self._open(), None, None))
+
+    @property
+    def frozen(self):
+        """``(mask0, mask1)``: bool CUDA tensors ``[num_nodes]``, the frozen rows of ``syn0`` and of ``syn1``."""
+        import torch
+
+        handle = self._open()
+        out = torch.empty((2, self.num_nodes), dtype=torch.uint8, device=self.d_walks.device)
+        torch.cuda.current_stream(self.d_walks.device).synchronize()
+        _lib.check(_lib.load().pw_sgns_get_locks(handle, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr())))
+        return out[0].to(torch.bool), out[1].to(torch.bool)
 
     # ---- scoring without training, another corpus
     @staticmethod
@@ -373,12 +455,17 @@ class SgnsSession:
     # ---- checkpoints
     def save(self, path):
         """An ``.npz`` with both matrices, the state, the constructor's parameters and ``(n_walks, walk_length,
-        num_nodes)``: what ``restore`` needs besides the walk matrix."""
+        num_nodes)``: what ``restore`` needs besides the walk matrix.  With frozen rows also ``frozen_vectors`` and
+        ``frozen_context`` (bool arrays), which ``restore`` applies; without, the file has no such keys."""
         st = self.state
         arrays = dict(vectors=self.vectors().cpu().numpy(), context_vectors=self.context_vectors().cpu().numpy(),
                       corpus_shape=np.array(self.corpus_shape, dtype=np.int64))
         arrays.update({"state_" + k: np.array(v) for k, v in st.items()})
         arrays.update({"param_" + k: np.array(v) for k, v in self.params.items()})
+        n0, n1, _ = self._lock_info()
+        if n0 or n1:   # (a session without frozen rows writes the file it always wrote)
+            m0, m1 = self.frozen
+            arrays.update(frozen_vectors=m0.cpu().numpy(), frozen_context=m1.cpu().numpy())
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
@@ -400,6 +487,8 @@ class SgnsSession:
             s._set_state(epoch=int(saved["state_epoch"]), sched_pos=int(saved["state_sched_pos"]),
                          sched_total=int(saved["state_sched_total"]), alpha=float(saved["state_alpha"]),
                          min_alpha=float(saved["state_min_alpha"]))
+            if "frozen_vectors" in saved:
+                s.freeze(saved["frozen_vectors"].astype(bool), context=saved["frozen_context"].astype(bool))
         except Exception:
             s.close()
             raise

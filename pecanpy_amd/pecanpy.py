@@ -24,16 +24,17 @@ class GraphSgnsSession(SgnsSession):
     draws walks from it between epochs (see there for the seeds).  ``run(n)`` trains one epoch at a time; ``last_stats`` is
     the last epoch's."""
 
-    def __init__(self, graph, num_walks, walk_length, fresh_walks, holdout_walks, **params):
+    def __init__(self, graph, num_walks, walk_length, fresh_walks, holdout_walks, start_nodes=None, **params):
         self._graph, self._num_walks, self._walk_length, self._fresh = graph, num_walks, walk_length, fresh_walks
+        self._start_nodes = start_nodes   # (None: every vertex) where every corpus of this session starts
         self.d_holdout = None
-        super().__init__(graph._session_walks(num_walks, walk_length, self._seed_of(0)), graph.num_nodes, **params)
+        super().__init__(graph._session_walks(num_walks, walk_length, self._seed_of(0), start_nodes), graph.num_nodes, **params)
         self._corpus_epoch = 0          # the epoch whose corpus the session holds
         try:
             if holdout_walks:
                 r = graph.random_state
                 seed = None if r is None else (int(r) - 1) & 0xFFFFFFFF   # (r = 0: 2^32 - 1)
-                self.d_holdout = graph._session_walks(holdout_walks, walk_length, seed)
+                self.d_holdout = graph._session_walks(holdout_walks, walk_length, seed, start_nodes)
         except Exception:
             self.close()
             raise
@@ -51,7 +52,7 @@ class GraphSgnsSession(SgnsSession):
         for _ in range(epochs):
             epoch = self.state["epoch"]
             if self._fresh and epoch != self._corpus_epoch:
-                self.set_walks(self._graph._session_walks(self._num_walks, self._walk_length, self._seed_of(epoch)))
+                self.set_walks(self._graph._session_walks(self._num_walks, self._walk_length, self._seed_of(epoch), self._start_nodes))
                 self._corpus_epoch = epoch
             record = super().run(1)[0]
             if self.d_holdout is not None:
@@ -238,31 +239,60 @@ class Base(BaseGraph):
         dist.broadcast_object_list(box, src=0)
         return box[0]
 
-    def _start_array(self, num_walks, seed=None):
-        """Each node ``num_walks`` times, then NumPy's legacy seeded shuffle (pecanpy.py:135-141)."""
-        nodes = np.arange(self.num_nodes, dtype=np.uint32)
+    def _indices_of(self, ids, what):
+        """``uint32`` vertex indices of a sequence of node IDs (as in ``self.nodes``), in the order given; an empty
+        sequence, an ID the graph does not have and a repeated ID are ``ValueError``s."""
+        ids = list(ids)
+        if not ids:
+            raise ValueError(f"{what} is empty")
+        idmap = self._node_idmap
+        if len(idmap) != self.num_nodes:    # (ID lists installed without set_node_ids)
+            idmap = dict(zip(self.nodes, range(self.num_nodes)))
+        unknown = [i for i in ids if i not in idmap]
+        if unknown:
+            raise ValueError(f"{what}: {len(unknown)} IDs are not in the graph (first: {unknown[0]!r})")
+        idx = np.fromiter((idmap[i] for i in ids), dtype=np.uint32, count=len(ids))
+        if np.unique(idx).size != idx.size:
+            raise ValueError(f"{what} names a vertex more than once")
+        return idx
+
+    def _start_array(self, num_walks, seed=None, start_idx=None):
+        """Each node ``num_walks`` times, then NumPy's legacy seeded shuffle (pecanpy.py:135-141).  ``start_idx``: the
+        same construction on a subset of the vertices -- its indices in the order given in place of ``0 .. N-1``."""
+        nodes = np.arange(self.num_nodes, dtype=np.uint32) if start_idx is None else np.asarray(start_idx, dtype=np.uint32)
         starts = np.concatenate([nodes] * num_walks)
         np.random.seed(self.random_state if seed is None else seed)
         np.random.shuffle(starts)
         return starts
 
-    def simulate_walks_array(self, num_walks, walk_length, gather=True):
+    def _starts_for(self, num_walks, start_nodes):
+        """The job array of a call: every check of ``start_nodes`` comes before the seed is drawn or the device touched."""
+        start_idx = None if start_nodes is None else self._indices_of(start_nodes, "start_nodes")
+        self._preprocess_transition_probs()
+        self._run_seed = self._call_seed()
+        return self._start_array(num_walks, self._run_seed, start_idx)
+
+    def simulate_walks_array(self, num_walks, walk_length, gather=True, start_nodes=None):
         """The walk index matrix ``uint32[n_jobs, walk_length + 2]`` (what ``_random_walks``
         returns in the reference); ``simulate_walks`` maps it to ID lists.  Under
         ``torch.distributed`` with ``gather=False`` every rank gets ``(rows, (lo, hi))``: its own
-        slice [lo, hi) of that matrix, without the final collective."""
-        self._preprocess_transition_probs()
-        self._run_seed = self._call_seed()
-        starts = self._start_array(num_walks, self._run_seed)
+        slice [lo, hi) of that matrix, without the final collective.
+
+        ``start_nodes``: a sequence of node IDs (as in ``self.nodes``) to walk from instead of every vertex.  The job array
+        is the reference's construction on that subset -- its indices in the order given, ``num_walks`` times, the same
+        seeded shuffle -- and the walks are what the engine draws for that array and seed (the reference's
+        ``_random_walks`` takes any start array too).  An unknown, repeated or missing ID is a ``ValueError``."""
+        starts = self._starts_for(num_walks, start_nodes)
         return self._random_walks(starts, walk_length, gather=gather)
 
-    def simulate_walks_corpus(self, num_walks, walk_length):
+    def simulate_walks_corpus(self, num_walks, walk_length, start_nodes=None):
         """Like ``simulate_walks`` but returns a lazy, re-iterable :class:`WalkCorpus`."""
-        return WalkCorpus(self.simulate_walks_array(num_walks, walk_length), self.nodes)
+        return WalkCorpus(self.simulate_walks_array(num_walks, walk_length, start_nodes=start_nodes), self.nodes)
 
-    def simulate_walks(self, num_walks, walk_length):
-        """Generate ``num_walks`` walks from every node; returns ``List[List[str]]``."""
-        mat = self.simulate_walks_array(num_walks, walk_length)
+    def simulate_walks(self, num_walks, walk_length, start_nodes=None):
+        """Generate ``num_walks`` walks from every node (from every node of ``start_nodes`` when given, see
+        ``simulate_walks_array``); returns ``List[List[str]]``."""
+        mat = self.simulate_walks_array(num_walks, walk_length, start_nodes=start_nodes)
         return [self._map_walk(row) for row in mat]
 
     def _note_stats(self, stats):
@@ -371,13 +401,11 @@ class Base(BaseGraph):
             self.preprocess_transition_probs()
             self._preprocessed = True
 
-    def _device_walks(self, num_walks, walk_length):
+    def _device_walks(self, num_walks, walk_length, start_nodes=None):
         """The walk matrix of ``simulate_walks_array`` as a device tensor (``WalkEngine.simulate_device``), or ``None`` where
         that call takes another route: under ``torch.distributed``, with the in-process multi-GPU engine, and for engines
         without a device entry."""
-        self._preprocess_transition_probs()
-        self._run_seed = self._call_seed()
-        starts = self._start_array(num_walks, self._run_seed)
+        starts = self._starts_for(num_walks, start_nodes)
         eng = self._get_engine()
         if self._dist() is not None or self._multi_engine(starts.size, walk_length) is not None or not hasattr(eng, "simulate_device"):
             return None
@@ -452,14 +480,15 @@ class Base(BaseGraph):
                                  "download_ms": (t3 - t2) * 1e3, **train_sgns_device.last_stats}
         return vec
 
-    def _session_walks(self, num_walks, walk_length, call_seed="own"):
+    def _session_walks(self, num_walks, walk_length, call_seed="own", start_nodes=None):
         """``_device_walks`` for a session, drawn with the call seed ``call_seed`` in place of ``random_state`` when one is
         given (``None``: a new OS seed); ``NotImplementedError`` where there is no device matrix."""
         saved = self.random_state
         if call_seed != "own":
             self.random_state = call_seed
         try:
-            d_walks = self._device_walks(num_walks, walk_length)
+            kw = {} if start_nodes is None else {"start_nodes": start_nodes}
+            d_walks = self._device_walks(num_walks, walk_length, **kw)
         finally:
             self.random_state = saved
         if d_walks is None:
@@ -491,6 +520,82 @@ class Base(BaseGraph):
             raise ValueError("holdout_walks must not be negative")
         return GraphSgnsSession(self, num_walks, walk_length, bool(fresh_walks), int(holdout_walks), **params)
 
+    def extend_session(self, known_ids, vectors, context_vectors=None, starts="new", freeze=True, num_walks=10, walk_length=80,
+                       window_size=10, epochs=1, workers=0, compute_loss=False, fresh_walks=False, holdout_walks=0):
+        """Embed new vertices into old vectors: a ``GraphSgnsSession`` on this graph in which every vertex of ``known_ids``
+        has its row of ``vectors`` (and, with ``context_vectors``, its row of ``syn1``) -- matched by ID; NumPy, a CPU tensor
+        or a CUDA tensor, ``float32[len(known_ids), dim]``, ``dim`` taken from ``vectors`` -- and the other vertices the
+        session's seeded initial ``syn0`` and a zero ``syn1``.  Nothing is trained yet; the other keywords are
+        ``embed_session``'s.
+
+        ``starts="new"``: the walks -- fresh and held-out ones too -- start from the vertices that are not in ``known_ids``,
+        ``num_walks`` each; ``"all"``: from every vertex.  ``freeze=True``: the known rows of ``syn0`` are frozen
+        (``SgnsSession.freeze``) and keep their bits however long the session trains; the known rows of ``syn1`` are frozen
+        only when ``context_vectors`` was given -- without old context vectors there is nothing to preserve, and a zero row
+        that cannot learn would teach the new vertices nothing.  The placement is a scatter on the device.
+
+        The vocabulary tables -- word counts, the noise table negatives are drawn from, the keep probabilities of the
+        subsampling -- come from the corpus the session is created on.  With ``starts="new"`` that is the neighbourhood of
+        the new vertices, not the whole graph, deliberately: negatives are drawn from where the new vertices live.
+
+        ``ValueError``: a known ID that is not in the graph, a repeated one, no new vertex with ``starts="new"``, a matrix
+        of another shape or dtype.  ``NotImplementedError`` where ``embed_session`` raises one."""
+        import torch
+
+        if starts not in ("new", "all"):
+            raise ValueError("starts must be 'new' or 'all'")
+        if int(holdout_walks) < 0:
+            raise ValueError("holdout_walks must not be negative")
+        known = self._indices_of(known_ids, "known_ids")
+        placed = []
+        for name, m in (("vectors", vectors), ("context_vectors", context_vectors)):
+            if m is None:
+                placed.append(None)
+                continue
+            if not isinstance(m, torch.Tensor):
+                m = torch.from_numpy(np.ascontiguousarray(m))
+            if m.dtype != torch.float32 or m.dim() != 2 or m.shape[0] != known.size or m.shape[1] < 1:
+                raise ValueError(f"{name} must be float32[{known.size}, dim], not {m.dtype}{list(m.shape)}")
+            if placed and placed[0] is not None and m.shape[1] != placed[0].shape[1]:
+                raise ValueError(f"context_vectors must have the dim of vectors ({placed[0].shape[1]}), not {m.shape[1]}")
+            placed.append(m)
+        if placed[0] is None:
+            raise ValueError("vectors must be float32[len(known_ids), dim]")
+        start_nodes = None
+        if starts == "new":
+            is_known = np.zeros(self.num_nodes, dtype=bool)
+            is_known[known] = True
+            ids = self.nodes
+            start_nodes = [ids[i] for i in np.flatnonzero(~is_known).tolist()]
+            if not start_nodes:
+                raise ValueError("every vertex of the graph is in known_ids: there is no new vertex to walk from (starts='all'?)")
+        s = GraphSgnsSession(self, num_walks, walk_length, bool(fresh_walks), int(holdout_walks), start_nodes=start_nodes,
+                             dim=int(placed[0].shape[1]), window=window_size, epochs=epochs, seed=self.random_state, workers=workers,
+                             compute_loss=compute_loss)
+        try:
+            dev = s.d_walks.device
+            rows = torch.from_numpy(known.astype(np.int64)).to(dev)
+            syn0 = s.vectors()
+            syn0[rows] = placed[0].to(dev)
+            syn1 = None
+            if placed[1] is not None:
+                syn1 = s.context_vectors()
+                syn1[rows] = placed[1].to(dev)
+            s.load(vectors=syn0, context_vectors=syn1)
+            if freeze:
+                s.freeze(rows, context=placed[1] is not None)
+        except Exception:
+            s.close()
+            raise
+        return s
+
+    def extend_embedding(self, known_ids, vectors, context_vectors=None, starts="new", freeze=True, **kw):
+        """``extend_session`` run through its whole schedule: ``float32[num_nodes, dim]`` in node order on the host, as
+        ``embed_array`` returns it -- the rows of ``known_ids`` bitwise those of ``vectors`` when ``freeze`` is set."""
+        with self.extend_session(known_ids, vectors, context_vectors=context_vectors, starts=starts, freeze=freeze, **kw) as s:
+            s.run(s.state["sched_total"])
+            return s.vectors().cpu().numpy()
+
     def embed_to_file(self, path, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, workers=0):
         """``embed_array`` + ``save_word2vec_format`` without the vectors visiting the host: walks, trainer and the device
         writer (``pecanpy_amd.embed.save_word2vec_format_device``); only the text of the file leaves the device.  The file
@@ -521,8 +626,8 @@ class Base(BaseGraph):
                                  "sgns_call_ms": sgns_call_ms, "write_call_ms": (time.perf_counter() - t0) * 1e3, **trainer,
                                  **save_word2vec_format_device.last_stats}
 
-    def walks_to_file(self, path, num_walks=10, walk_length=80):
-        """The walks of ``simulate_walks(num_walks, walk_length)`` as a text file, one walk per line with the node IDs
+    def walks_to_file(self, path, num_walks=10, walk_length=80, start_nodes=None):
+        """The walks of ``simulate_walks(num_walks, walk_length, start_nodes)`` as a text file, one walk per line with the node IDs
         separated by single spaces (``pecanpy_amd.corpus``), without ``List[List[str]]``: ``_device_walks`` ->
         ``save_walks_device``; neither the walk matrix nor ID lists visit the host, only the text of the file leaves the
         device.  For a seeded object the file holds the bytes ``cli._dump_walks(path, self.simulate_walks(...))`` writes.
@@ -536,9 +641,9 @@ class Base(BaseGraph):
         from .corpus import save_walks, save_walks_device
 
         t0 = time.perf_counter()
-        d_walks = self._device_walks(num_walks, walk_length)
+        d_walks = self._device_walks(num_walks, walk_length, start_nodes)
         if d_walks is None:
-            mat = self.simulate_walks_array(num_walks, walk_length)
+            mat = self.simulate_walks_array(num_walks, walk_length, start_nodes=start_nodes)
             t1 = time.perf_counter()
             save_walks(path, self.nodes, mat)
             self.last_corpus_stats = {"walk_matrix_host_bytes": int(mat.nbytes), "walk_ms": (t1 - t0) * 1e3,

@@ -7,7 +7,15 @@ alternating.  One JSON line: total and per-stage ms of every call, trained pairs
 (negative + 1) * 2 * 4 * dim + 2 * 4 * dim bytes (every target row read and written, the context row read and written), over
 the 8 TB/s HBM peak.  On a tree without embed_array only route (b) runs (that is how the figure of the item-per-wavefront
 kernel in MEASUREMENTS.md was taken).  The wall clock stops after the result is on the host (both routes end in a blocking copy).
-usage: python tools/embed_bench.py [scale=18] [calls=3]"""
+usage: python tools/embed_bench.py [scale=18] [calls=3]
+
+--freeze-fraction F [F ...]: instead of the two routes, one skip-gram session per F on the same walks (Base.embed_session, racing
+trainer): after the session is created a seeded random fraction F of the rows is frozen in BOTH matrices (SgnsSession.freeze), then
+the schedule runs; `train_ms` (the training kernels, hipEvent) of `calls` sessions per F after one warm-up session, the values of F
+taken in turn.  F = 0 freezes nothing and runs the kernel without locks.
+--extend-fraction P: the use case -- a seeded random fraction P of the vertices is "new", the others keep the vectors of a full
+embed_array; Base.extend_embedding(starts="new") end to end (walks from the new vertices, session, placement, training, vectors to
+the host) beside a full embed_array, `calls` of each, alternating."""
 import json
 import os
 import sys
@@ -19,18 +27,87 @@ DIM, WINDOW, NEGATIVE, EPOCHS, NUM_WALKS, WALK_LENGTH, SEED = 128, 10, 5, 1, 10,
 HBM_PEAK = 8e12
 
 
+def _flag(argv, name):
+    """The values after `name` up to the next flag (removed from argv), or None."""
+    if name not in argv:
+        return None
+    i = argv.index(name)
+    j = i + 1
+    while j < len(argv) and not argv[j].startswith("--"):
+        j += 1
+    values = [float(x) for x in argv[i + 1:j]]
+    del argv[i:j]
+    return values
+
+
+def freeze_table(g, fractions, calls, torch):
+    import numpy as np
+
+    def one(frac):
+        with g.embed_session(DIM, NUM_WALKS, WALK_LENGTH, WINDOW, EPOCHS) as s:
+            if frac > 0:
+                rows = np.random.default_rng(SEED).permutation(g.num_nodes)[:int(round(frac * g.num_nodes))]
+                s.freeze(torch.from_numpy(rows))
+            s.run(EPOCHS)
+            n0, n1, locked = s._lock_info()
+            return {"train_ms": round(s.last_stats["train_ms"], 2), "frozen_rows": [n0, n1], "lock_instances": bool(locked),
+                    "trained_pairs": s.last_stats["trained_pairs"]}
+
+    one(fractions[0])
+    rows = {f: [] for f in fractions}
+    for _ in range(calls):
+        for f in fractions:
+            torch.cuda.synchronize()
+            rows[f].append(one(f))
+    return {str(f): {"train_ms": [r["train_ms"] for r in rows[f]], "frozen_rows": rows[f][0]["frozen_rows"],
+                     "lock_instances": rows[f][0]["lock_instances"], "trained_pairs": rows[f][0]["trained_pairs"]} for f in fractions}
+
+
+def extend_table(g, frac, calls, torch):
+    import numpy as np
+
+    full = g.embed_array(DIM, NUM_WALKS, WALK_LENGTH, WINDOW, EPOCHS)          # (warm-up, and the old vectors)
+    new = np.zeros(g.num_nodes, dtype=bool)
+    new[np.random.default_rng(SEED).permutation(g.num_nodes)[:max(1, int(round(frac * g.num_nodes)))]] = True
+    known_ids = [g.nodes[i] for i in np.flatnonzero(~new).tolist()]
+    known_vec = np.ascontiguousarray(full[~new])
+    kw = dict(num_walks=NUM_WALKS, walk_length=WALK_LENGTH, window_size=WINDOW, epochs=EPOCHS)
+    got = g.extend_embedding(known_ids, known_vec, **kw)                        # (warm-up)
+    assert np.array_equal(got[~new].view(np.int32), known_vec.view(np.int32))
+    out = {"new_vertices": int(new.sum()), "extend_total_ms": [], "embed_array_total_ms": []}
+    for _ in range(calls):
+        for key, fn in (("extend_total_ms", lambda: g.extend_embedding(known_ids, known_vec, **kw)),
+                        ("embed_array_total_ms", lambda: g.embed_array(DIM, NUM_WALKS, WALK_LENGTH, WINDOW, EPOCHS))):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            out[key].append(round((time.perf_counter() - t) * 1e3, 2))
+    return out
+
+
 def main():
     import torch
 
     from pecanpy_amd import embed, pecanpy
     from pecanpy_amd.synth import rmat_csr
 
-    scale = int(sys.argv[1]) if len(sys.argv) > 1 else 18
-    calls = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    argv = sys.argv[1:]
+    fractions, extend = _flag(argv, "--freeze-fraction"), _flag(argv, "--extend-fraction")
+    scale = int(argv[0]) if len(argv) > 0 else 18
+    calls = int(argv[1]) if len(argv) > 1 else 3
     indptr, indices, data = rmat_csr(scale, seed=1)
     g = pecanpy.SparseOTF.from_csr(indptr, indices, data, p=0.5, q=2, random_state=SEED)
     g.device = 0
     have_a = hasattr(g, "embed_array")
+    if fractions or extend:
+        out = {"workload": f"RMAT-{scale} SparseOTF p=0.5 q=2, {NUM_WALKS} x {WALK_LENGTH}, SGNS dim {DIM} window {WINDOW} negative {NEGATIVE} "
+                           f"epochs {EPOCHS} seed {SEED}", "device": torch.cuda.get_device_name(0), "calls": calls}
+        if fractions:
+            out["freeze_fraction"] = freeze_table(g, fractions, calls, torch)
+        if extend:
+            out["extend"] = extend_table(g, extend[0], calls, torch)
+        print(json.dumps(out), flush=True)
+        return
 
     def route_a():
         t = time.perf_counter()
