@@ -3601,17 +3601,21 @@ static int fill_stats(pw_graph *g, WalkCall &c, unsigned long long h[N_COUNTERS]
         // statistics of the final, self-consistent matrix
         HIP_TRY(hipMemcpy(h, g->counters.p, N_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         uint64_t tot2 = 0;
+        std::vector<uint32_t> lens(c.n_jobs);
+        HIP_TRY(hipMemcpy2D(lens.data(), sizeof(uint32_t), c.d_out + c.walk_length + 1,
+                            sizeof(uint32_t) * ((size_t)c.walk_length + 2), sizeof(uint32_t), c.n_jobs,
+                            hipMemcpyDeviceToHost));
         if (!st.stream_addressing) {
             int rc = compute_offsets(g, c.d_starts, c.d_out, c.walk_length, c.n_jobs, c.stream_skip, false, &tot2, nullptr);
             if (rc) return rc;
         } else {  // offsets stay nominal; count the steps from the lengths without touching them
-            std::vector<uint32_t> lens(c.n_jobs);
-            HIP_TRY(hipMemcpy2D(lens.data(), sizeof(uint32_t), c.d_out + c.walk_length + 1,
-                                sizeof(uint32_t) * ((size_t)c.walk_length + 2), sizeof(uint32_t), c.n_jobs,
-                                hipMemcpyDeviceToHost));
             for (uint64_t i = 0; i < c.n_jobs; i++) tot2 += lens[i] - 1;
         }
         st.total_steps = tot2;
+        // the first pass counted the dead ends of walks that were walked again since: count those of the final matrix (a walk
+        // that moved and stopped before walk_length steps; a start without out-edges never moves and is not one)
+        dead = 0;
+        for (uint64_t i = 0; i < c.n_jobs; i++) dead += (lens[i] > 1u && lens[i] < c.walk_length + 1u) ? 1u : 0u;
     } else {
         st.total_steps = h[pw::CTR_STEPS];
     }

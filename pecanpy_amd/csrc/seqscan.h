@@ -110,7 +110,9 @@ template <typename T> struct Binade {
         Inc<T> r;
         if (M == 0) { r.a0 = r.a1 = 0; return r; }
         if (s <= 0) { r.a0 = r.a1 = SAT; return r; }        // x >= 2^e: the sum certainly leaves the binade
-        if (s > MANT + 2) { r.a0 = r.a1 = 0; return r; }    // x < ulp/4: absorbed
+        // x < ulp/4: absorbed.  An accumulator that has overflowed (eb == EXP_MASK: +inf) absorbs every finite x -- its
+        // "significand" must stay 2^MANT, or make() would hand back a NaN where the sequential sum is +inf
+        if (s > MANT + 2 || eb == FloatTraits<T>::EXP_MASK) { r.a0 = r.a1 = 0; return r; }
         UInt fl = M >> s;
         UInt rem = M & ((ONE << s) - 1);
         UInt half = ONE << (s - 1);

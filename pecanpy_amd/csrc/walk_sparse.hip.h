@@ -461,10 +461,12 @@ __device__ __forceinline__ uint32_t build_mask_bits(const CsrDev &g, uint32_t *m
         if (lane == 32) mask[(kb >> 5) + 1] = (uint32_t)(fb >> 32);
         if (in_mask) {
             // w(prev, x): position of x in prev's row by search (only for common neighbours)
-            bool is_in = false;
+            // (a non-neighbour of prev has data[prev, x] == 0: an out edge only where 0 < thr[x], dense_rw.py:95 -- under a
+            //  threshold of zero, or a NaN, it keeps its weight like an in-edge)
+            bool is_in = valid && !found && Arith<T>::in_edge((T)0, g.thr[x]);
             if (fb) {
                 const uint32_t jpos = lower_bound_u32(g.indices + t0, dp, x);
-                is_in = found && Arith<T>::in_edge(data[t0 + jpos], g.thr[x]);
+                if (found) is_in = Arith<T>::in_edge(data[t0 + jpos], g.thr[x]);
             }
             const uint64_t ib = ballot(is_in);
             if (lane == 0) in_mask[kb >> 5] = (uint32_t)ib;
@@ -552,7 +554,7 @@ template <typename T, bool UNIT> struct RowVals {
         }
         if (valid) {
             if (k == prev_pos) w = div_p(w);
-            else if (!(common && is_in)) {
+            else if (!is_in) {      // (an in-edge is a common neighbour, or on the dense path a non-neighbour of prev under thr[x] <= 0)
                 const double inv_q = 1.0 / q;
                 double alpha = inv_q + (1.0 - inv_q) * t;
                 if (Arith<T>::noisy(w, thr_cur)) alpha = inv_q < 1.0 ? inv_q : 1.0;
