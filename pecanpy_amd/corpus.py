@@ -152,11 +152,11 @@ def read_walks_device(path, node_ids=None, device=0):
 
     import torch
 
-    from .engine import _edgelist_names
+    from .engine import _edgelist_names, _no_device
 
     lib = _lib.load()
     if int(lib.pw_device_count()) <= 0:
-        raise _lib.PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+        _no_device()
     dev = torch.device("cuda", int(device or 0))
     t0 = time.perf_counter()
     h, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwCorpusDevStats()

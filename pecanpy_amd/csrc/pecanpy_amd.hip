@@ -123,6 +123,14 @@ template <typename T> int grow(DevBuf<T> &b, size_t n) {
     return e == hipSuccess ? 0 : fail(PW_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
 
+// the one device check of every entry that takes a device index
+int check_device(int device) {
+    const int n = pw_device_count();
+    if (n <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
+    if (device < 0 || device >= n) return fail(PW_ERR_INVALID, "device index out of range");
+    return 0;
+}
+
 }  // namespace
 
 // The scalar description of a graph: pw_graph_replicate copies it in one assignment.
@@ -291,6 +299,12 @@ struct pw_graph {
 
 namespace {
 
+// The owner of a call context under construction: every way out of a creator but the release() into *out destroys it (a twin
+// with it).  A creator's locals go in reverse order of declaration, so where the owner stands among them decides what the
+// handle outlives: each creator says so where it declares it.
+struct GraphDeleter { void operator()(pw_graph *g) const { pw_graph_destroy(g); } };
+using GraphOwner = std::unique_ptr<pw_graph, GraphDeleter>;
+
 int set_device(const pw_graph *g) {
     HIP_TRY(hipSetDevice(g->device));
     return 0;
@@ -355,9 +369,7 @@ PW_EXPORT int pw_device_count(void) {
 
 PW_EXPORT int pw_warmup(int device, double *ms) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int n = pw_device_count();
-    if (n <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= n) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -378,9 +390,7 @@ static int graph_common_init(pw_graph *g, int device, std::shared_ptr<GraphData>
     auto nowms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = nowms();
     auto lap = [&](const char *what) { if (dbg) { const double t = nowms(); fprintf(stderr, "[create]   init: %-28s %8.2f ms\n", what, t - t0); t0 = t; } };
-    int n = pw_device_count();
-    if (n <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     g->device = device;
     g->gd = gd ? std::move(gd) : std::make_shared<GraphData>(device);
     HIP_TRY(hipSetDevice(device));
@@ -772,9 +782,12 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
         if (nnz && !getenv("PECANPY_AMD_NO_LAZY")) make_lane_work_items(indptr, indices, n_nodes, items);
     }
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{item_thread};
-    pw_graph *g = new pw_graph();
+    // The handle's owner, in front of `pre`: it goes behind ~Pre, which joins the helper threads, and behind the scratch buffers
+    // further down (d_edge_row, d_flags), whose hipFree waits for the kernels that read them on the handle's stream.
+    GraphOwner owner(new pw_graph());
+    pw_graph *const g = owner.get();
     int rc = graph_common_init(g, device);
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     stamp("runtime / streams / events");
     // Two helper threads, from here on beside the host pass below: (1) the CSR arrays go to the device (261 MB of column indices
     // at RMAT-22 from pageable memory: ~25 ms); (2) the edge lines of the lane index (64 bytes per CSR entry + one per vertex:
@@ -827,7 +840,7 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     uint32_t md = 0;
     uint64_t frun = 0, trun = 0;
     for (uint32_t i = 0; i < n_nodes; i++) {
-        if (indptr[i + 1] < indptr[i]) { pw_graph_destroy(g); return fail(PW_ERR_INVALID, "indptr not monotone"); }
+        if (indptr[i + 1] < indptr[i]) return fail(PW_ERR_INVALID, "indptr not monotone");
         const uint32_t d = indptr[i + 1] - indptr[i];
         if (d > md) md = d;
         foff[i] = (uint32_t)frun;
@@ -839,8 +852,8 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
             trun += sz;
         }
     }
-    if (frun >= 0xffffffffull) { pw_graph_destroy(g); return fail(PW_ERR_INVALID, "graph too large for 32-bit filter offsets"); }
-    if ((trun >> 1) > 0xffffffffull) { pw_graph_destroy(g); return fail(PW_ERR_INVALID, "graph too large for 32-bit index offsets"); }
+    if (frun >= 0xffffffffull) return fail(PW_ERR_INVALID, "graph too large for 32-bit filter offsets");
+    if ((trun >> 1) > 0xffffffffull) return fail(PW_ERR_INVALID, "graph too large for 32-bit index offsets");
     foff[n_nodes] = (uint32_t)frun;
     off[n_nodes] = trun;
     g->gd->max_degree = md;
@@ -851,18 +864,15 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     };
     // the CSR arrays, uploaded by the helper thread meanwhile (the lines' allocation may still be running: joined further down)
     if (pre.t_up.joinable()) pre.t_up.join();
-    if (pre.err != hipSuccess) { pw_graph_destroy(g); return fail(pre.err == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("CSR upload: ") + hipGetErrorString(pre.err)); }
+    if (pre.err != hipSuccess) return fail(pre.err == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("CSR upload: ") + hipGetErrorString(pre.err));
     g->gd->d_indptr = std::move(pre.indptr); g->gd->d_indices = std::move(pre.indices); g->gd->d_data = std::move(pre.data);
     stamp("host pass + H2D of the CSR");
 
     // ---- device side: validation, weight scan, membership index ------------------------------------------------
+    // (scratch that kernels on g->stream read, declared behind the owner: freed first, and hipFree waits for the device)
     DevBuf<uint32_t> d_edge_row;
     DevBuf<unsigned long long> d_flags;      // [0] first entry with index >= n_nodes  [1] first entry out of order
                                              // [2] some weight != 1.0f  [3] self loop present  [4] some weight negative / NaN / inf
-    auto bail = [&](int code, const std::string &msg) {
-        pw_graph_destroy(g);
-        return fail(code, msg);
-    };
     hipError_t e = d_edge_row.alloc(nnz);
     if (e == hipSuccess) e = d_flags.alloc(5);
     unsigned long long h_flags[5] = {~0ull, ~0ull, 0ull, 0ull, 0ull};
@@ -878,17 +888,17 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     INDEX_KERNELS_END(g);
     if (e == hipSuccess) e = hipMemcpyAsync(h_flags, d_flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("CSR validation: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("CSR validation: ") + hipGetErrorString(e));
     if (h_flags[0] != ~0ull) {
         uint32_t row = 0;
         (void)hipMemcpy(&row, d_edge_row.p + h_flags[0], sizeof(row), hipMemcpyDeviceToHost);
-        return bail(PW_ERR_INVALID, "CSR entry " + std::to_string(h_flags[0]) + " (row " + std::to_string(row) +
+        return fail(PW_ERR_INVALID, "CSR entry " + std::to_string(h_flags[0]) + " (row " + std::to_string(row) +
                                         "): column index >= n_nodes");
     }
     if (h_flags[1] != ~0ull) {
         uint32_t row = 0;
         (void)hipMemcpy(&row, d_edge_row.p + h_flags[1], sizeof(row), hipMemcpyDeviceToHost);
-        return bail(PW_ERR_INVALID, "row " + std::to_string(row) + " (CSR entry " + std::to_string(h_flags[1]) +
+        return fail(PW_ERR_INVALID, "row " + std::to_string(row) + " (CSR entry " + std::to_string(h_flags[1]) +
                                         "): column indices must be strictly ascending within a row (sorted, no duplicates), "
                                         "as the reference's to_csr produces them (graph.py:336)");
     }
@@ -901,19 +911,19 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     // bound that takes the sign of a common neighbour's delta from q alone, seqscan.h: WeightedRow::margin) would NOT reproduce that
     // garbage bit for bit, so such a graph is refused instead of walked differently (error behaviour)
     if (data && h_flags[4] != 0)
-        return bail(PW_ERR_INVALID, "edge weights must be finite and >= 0 (a negative, NaN or infinite weight makes the reference's "
+        return fail(PW_ERR_INVALID, "edge weights must be finite and >= 0 (a negative, NaN or infinite weight makes the reference's "
                                     "transition probabilities w / w.sum() meaningless; this library does not reproduce them)");
 
     rc = up(g->gd->d_foff, foff.data(), foff.size());
     if (!rc) rc = up(g->gd->d_tab_off, off.data(), off.size());
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     e = g->gd->d_fbits.alloc(frun ? frun : 1);   // (at least one word each: the memsets below clear what was allocated)
     if (e == hipSuccess) e = g->gd->d_kf.alloc(nnz);
     if (e == hipSuccess) e = g->gd->d_slots.alloc(trun ? trun : 1);
     if (e == hipSuccess) e = g->gd->d_vrec.alloc((size_t)n_nodes + 1);
     if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_fbits.p, 0, g->gd->d_fbits.bytes(), g->stream);
     if (e == hipSuccess) e = hipMemsetAsync(g->gd->d_slots.p, 0xff, g->gd->d_slots.bytes(), g->stream);
-    if (e != hipSuccess) return bail(PW_ERR_NOMEM, std::string("membership index: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_NOMEM, std::string("membership index: ") + hipGetErrorString(e));
     g->gd->index_bytes = sizeof(uint64_t) * (frun + trun) + sizeof(uint2) * (uint64_t)nnz + sizeof(uint4) * ((uint64_t)n_nodes + 1);
     INDEX_KERNELS_BEGIN(g);
     hipLaunchKernelGGL(pw::vrec_build_kernel, dim3((n_nodes + 256) / 256), dim3(256), 0, g->stream, g->gd->d_indptr.p, g->gd->d_foff.p,
@@ -925,7 +935,7 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     e = hipGetLastError();
     INDEX_KERNELS_END(g);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e != hipSuccess) return bail(PW_ERR_HIP, std::string("membership index build: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("membership index build: ") + hipGetErrorString(e));
     stamp("membership index");
     g->gd->has_loop = has_loop;
     if (nnz && (!has_loop || g->gd->unit) && !getenv("PECANPY_AMD_NO_LAZY")) {   // (weighted graphs too: membership does not depend on the weights)
@@ -939,7 +949,7 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
         if (pre.t_lines.joinable()) pre.t_lines.join();
         g->gd->d_lines = std::move(pre.lines);
         rc = build_lane_index(g, items, d_edge_row.p, has_loop);
-        if (rc) { pw_graph_destroy(g); return rc; }
+        if (rc) return rc;
     }
     (void)hipStreamSynchronize(g->stream);
     stamp("lane index");
@@ -947,7 +957,7 @@ static int csr_create_impl(const uint32_t *indptr, const uint32_t *indices, cons
     // a PARTIAL index keeps the source vertex of every CSR entry (4 bytes per entry): lanes_eager_kernel reads the vertex a
     // parked step came from there instead of bisecting indptr for it (22 dependent loads per step)
     if (g->gd->d_lines.p && g->gd->list_max_len != 0xffffffffu) g->gd->d_wedge_row = std::move(d_edge_row);
-    *out = g;
+    *out = owner.release();
     return PW_OK;
 }
 
@@ -980,9 +990,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
                             uint64_t n_nodes, int directed, pw_csr_dev **out, int *conflict, bool keep_f64 = false) {
     if (!out || (m && (!d_src || !d_dst))) return fail(PW_ERR_INVALID, "null pointer");
     const bool payload = d_weight || d_w64;   // four bytes travel with every key
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     if (n_nodes > 0xfffffffeull) return fail(PW_ERR_INVALID, "n_nodes beyond the 32-bit CSR limit (at most 2^32 - 2 vertices)");
     const uint64_t mult = directed ? 1 : 2;
     HIP_TRY(hipSetDevice(device));
@@ -990,15 +998,13 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const unsigned stride_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)prop.multiProcessorCount * 16));
 
-    // what the call holds beside its scratch buffers: the events of the three kernel spans (begin / end), and the result until it is handed out
+    // what the call holds beside its scratch buffers: the result until it is handed out, and the events of the three kernel
+    // spans (begin / end)
     struct Mem {
         pw_csr_dev *res = nullptr;
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Mem() {
-            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-            if (res) pw_csr_dev_destroy(res);
-        }
+        ~Mem() { if (res) pw_csr_dev_destroy(res); }
     } mem;
+    pw::Event ev[6];
     uint64_t scratch_bytes = 0;
     auto alloc = [&](auto &buf, uint64_t n, const char *what) -> int {
         const hipError_t e = buf.alloc(n);
@@ -1011,7 +1017,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     };
     // build_ms = the sum of three spans of kernels on the null stream; the allocations, the two small device-to-host reads and the
     // host logic between the spans are outside it
-    for (auto &e : mem.ev) HIP_TRY(hipEventCreate(&e));
+    for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
 
     // 1. validation, kept edges, largest id
     DevBuf<unsigned long long> flags_buf;
@@ -1023,13 +1029,13 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     if (rc) return rc;
     unsigned long long h_flags[4] = {~0ull, ~0ull, 0ull, 0ull};
     HIP_TRY(hipMemcpy(d_flags, h_flags, sizeof(h_flags), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(mem.ev[0], nullptr));
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
     if (m) {
         hipLaunchKernelGGL(pw::coo_validate_kernel, dim3(stride_grid), dim3(256), 0, nullptr, d_src, d_dst, d_weight, m,
                            n_nodes ? n_nodes : 0xfffffffeull, d_keep, d_flags);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(mem.ev[1], nullptr));
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
     HIP_TRY(hipMemcpy(h_flags, d_flags, sizeof(h_flags), hipMemcpyDeviceToHost));
     if (h_flags[0] != ~0ull)
         return fail(PW_ERR_INVALID, "edge " + std::to_string(h_flags[0]) + ": vertex id negative or >= " +
@@ -1062,7 +1068,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     uint32_t *d_w[2] = {w_buf[0].p, w_buf[1].p};
     if (d_w64) HIP_TRY(hipMemset(conflict_buf.p, 0, sizeof(uint32_t)));
     uint32_t *const d_hist = hist_buf.p, *const d_tmp = tmp_buf.p;
-    HIP_TRY(hipEventRecord(mem.ev[2], nullptr));
+    HIP_TRY(hipEventRecord(ev[2], nullptr));
     if (d_weight && dropped) {
         HIP_TRY(hipMemsetAsync(d_keep + m, 0, sizeof(uint32_t), nullptr));
         pw::exclusive_scan_inplace(nullptr, d_keep, m + 1, d_tmp);
@@ -1101,7 +1107,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
                                (const uint32_t *)d_w[0], d_w64, n_ins, m, conflict_buf.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(mem.ev[3], nullptr));
+    HIP_TRY(hipEventRecord(ev[3], nullptr));
     if (n_ins) {
         HIP_TRY(hipMemcpy(&nnz32, d_pos + n_ins, sizeof(nnz32), hipMemcpyDeviceToHost));
     }
@@ -1132,7 +1138,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     if (!rc && payload) rc = alloc_out(c->d_data, nnz, "data");
     if (!rc && d_w64 && keep_f64) rc = alloc_out(c->d_data64, nnz, "float64 data");
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(mem.ev[4], nullptr));
+    HIP_TRY(hipEventRecord(ev[4], nullptr));
     if (n_ins && d_w64)
         hipLaunchKernelGGL(pw::coo_compact_lines_kernel, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, nullptr, (const uint64_t *)d_keys[0],
                            (const uint32_t *)d_w[0], d_w64, n_ins, m, (const uint32_t *)d_pos, bits, nnz, c->d_indices.p, c->d_data.p,
@@ -1143,11 +1149,11 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     // 6. row offsets
     hipLaunchKernelGGL(pw::coo_indptr_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, nullptr, (const uint32_t *)d_rows, nnz, n, c->d_indptr.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(mem.ev[5], nullptr));
-    HIP_TRY(hipEventSynchronize(mem.ev[5]));
+    HIP_TRY(hipEventRecord(ev[5], nullptr));
+    HIP_TRY(hipEventSynchronize(ev[5]));
     for (int k = 0; k < 6; k += 2) {
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, mem.ev[k], mem.ev[k + 1]));
+        HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
         c->build_ms += ms;
     }
     mem.res = nullptr;
@@ -1239,61 +1245,148 @@ PW_EXPORT int pw_edgelist_ids_export(const pw_edgelist_ids *ids, uint64_t *id_of
     return PW_OK;
 }
 
-// The file at `path` -> d_text (n + 1 bytes of device memory, the last one unused) and res->text (the host's copy: the names are
-// sliced from it), in chunks through two pinned buffers.  PW_EDGELIST_OK; PW_EDGELIST_NEEDS_HOST_READER (an empty file, one of
-// 4 GiB or more, memory that does not fit); PW_EDGELIST_IO; PW_ERR_HIP.  Nothing is in flight when it returns.
-static int upload_text_file(const char *path, int device, DevBuf<char> &d_text, pw_edgelist_ids *res, uint64_t *n_out) {
-    // the pinned buffers in front of `io`: they go after its destructor has waited for the stream
-    PinnedBuf<char> pinned[2];
-    struct Io {
-        FILE *file = nullptr;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        bool queued = false;
-        ~Io() {
-            if (queued) (void)hipStreamSynchronize(nullptr);
-            if (file) (void)fclose(file);
-            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+// What a call that reads a text file into device memory owns -- released on every way out -- and the part the edge-list reader
+// and the corpus reader share (TextFile's counterpart): the upload, the "no room is no error" allocator, the stage clock, and
+// the first-appearance id table with the download of the names' spans.  A buffer that only one reader uses stays a local of
+// that entry, declared in front of its TextRead: it then goes after the destructor below has waited for the stream.
+namespace {
+
+struct TextRead {
+    using clk = std::chrono::steady_clock;
+    const std::string who;      // the entry's name in the error texts
+    std::unique_ptr<pw_edgelist_ids> res;   // the names under construction, until they are handed out (res.release())
+    uint64_t n = 0;             // bytes of text
+    bool queued = false;        // work may be in flight on the default stream
+    bool no_room = false;       // an alloc() failed: every later one is skipped, the caller returns PW_EDGELIST_NEEDS_HOST_READER
+    clk::time_point t0;
+    DevBuf<char> d_text;                        // n + 1 bytes, the last one unused
+    DevBuf<uint32_t> d_flags, d_tmp;            // [0] the word the kernels raise (sized by the reader); the scans' tile sums
+    DevBuf<uint32_t> d_table, d_slot, d_first;  // number_names: left for the reader's own numbering kernel
+
+    explicit TextRead(const char *who_) : who(who_) {}
+    TextRead(const TextRead &) = delete;
+    ~TextRead() {   // (the buffers go behind this body: nothing of the call is in flight by then)
+        if (queued) (void)hipStreamSynchronize(nullptr);
+    }
+    // scratch that does not fit is no error: the host reader still works
+    template <typename T> void alloc(DevBuf<T> &buf, uint64_t count) {
+        if (!no_room && buf.alloc(count) != hipSuccess) no_room = true;
+    }
+    // the stage clock: milliseconds since upload() began or since the last lap
+    double lap() {
+        const auto t = clk::now();
+        const double ms = std::chrono::duration<double, std::milli>(t - t0).count();
+        t0 = t;
+        return ms;
+    }
+
+    // The file at `path` -> d_text and res->text (the host's copy: the names are sliced from it), in chunks through two pinned
+    // buffers.  PW_EDGELIST_OK; PW_EDGELIST_NEEDS_HOST_READER (an empty file, one of 4 GiB or more, memory that does not fit);
+    // PW_EDGELIST_IO; PW_ERR_HIP.  Nothing is in flight when it returns.
+    int upload(const char *path, int device) {
+        t0 = clk::now();
+        res.reset(new (std::nothrow) pw_edgelist_ids());
+        if (!res) return PW_EDGELIST_NEEDS_HOST_READER;
+        // the pinned buffers and the events in front of `io`: they go after its destructor has waited for the stream
+        PinnedBuf<char> pinned[2];
+        pw::Event ev[2];
+        struct Io {
+            FILE *file = nullptr;
+            bool queued = false;
+            ~Io() {
+                if (queued) (void)hipStreamSynchronize(nullptr);
+                if (file) (void)fclose(file);
+            }
+        } io;
+        io.file = fopen(path, "rb");
+        if (!io.file) return PW_EDGELIST_IO;
+        if (fseek(io.file, 0, SEEK_END) != 0) return PW_EDGELIST_IO;
+        {
+            const long sz = ftell(io.file);
+            if (sz < 0) return PW_EDGELIST_IO;
+            n = (uint64_t)sz;
+            rewind(io.file);
         }
-    } io;
-    io.file = fopen(path, "rb");
-    if (!io.file) return PW_EDGELIST_IO;
-    uint64_t n = 0;
-    if (fseek(io.file, 0, SEEK_END) != 0) return PW_EDGELIST_IO;
-    {
-        const long sz = ftell(io.file);
-        if (sz < 0) return PW_EDGELIST_IO;
-        n = (uint64_t)sz;
-        rewind(io.file);
+        if (n == 0 || n >= (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;   // (an empty file has nothing to put on the device)
+        HIP_TRY(hipSetDevice(device));
+        res->text.reset(new (std::nothrow) char[n]);
+        if (!res->text) return PW_EDGELIST_NEEDS_HOST_READER;
+        char *const h_text = res->text.get();
+        constexpr uint64_t CHUNK = 16ull << 20;
+        if (d_text.alloc(n + 1) != hipSuccess) return PW_EDGELIST_NEEDS_HOST_READER;
+        for (auto &pb : pinned) if (pb.alloc(std::min(CHUNK, n)) != hipSuccess) return PW_EDGELIST_NEEDS_HOST_READER;
+        for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
+        io.queued = true;
+        uint64_t at = 0;
+        for (int s = 0; at < n; s ^= 1) {
+            const uint64_t want = std::min(CHUNK, n - at);
+            if (at >= 2 * CHUNK) HIP_TRY(hipEventSynchronize(ev[s]));   // this buffer's last copy has left it
+            if (fread(pinned[s].p, 1, want, io.file) != want) return PW_EDGELIST_IO;   // (short: an error, or the file changed)
+            HIP_TRY(hipMemcpyAsync(d_text.p + at, pinned[s].p, want, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipEventRecord(ev[s], nullptr));
+            memcpy(h_text + at, pinned[s].p, want);
+            at += want;
+        }
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        queued = true;   // (from here on the reader's kernels)
+        return PW_EDGELIST_OK;
     }
-    if (n == 0 || n >= (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;   // (an empty file has nothing to put on the device)
-    HIP_TRY(hipSetDevice(device));
-    res->text.reset(new (std::nothrow) char[n]);
-    if (!res->text) return PW_EDGELIST_NEEDS_HOST_READER;
-    char *const h_text = res->text.get();
-    constexpr uint64_t CHUNK = 16ull << 20;
-    if (d_text.alloc(n + 1) != hipSuccess) return PW_EDGELIST_NEEDS_HOST_READER;
-    for (auto &pb : pinned) if (pb.alloc(std::min(CHUNK, n)) != hipSuccess) return PW_EDGELIST_NEEDS_HOST_READER;
-    for (auto &e : io.ev) HIP_TRY(hipEventCreate(&e));
-    io.queued = true;
-    uint64_t at = 0;
-    for (int s = 0; at < n; s ^= 1) {
-        const uint64_t want = std::min(CHUNK, n - at);
-        if (at >= 2 * CHUNK) HIP_TRY(hipEventSynchronize(io.ev[s]));   // this buffer's last copy has left it
-        if (fread(pinned[s].p, 1, want, io.file) != want) return PW_EDGELIST_IO;   // (short: an error, or the file changed)
-        HIP_TRY(hipMemcpyAsync(d_text.p + at, pinned[s].p, want, hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipEventRecord(io.ev[s], nullptr));
-        memcpy(h_text + at, pinned[s].p, want);
-        at += want;
+    // lines of the text, given its newlines: a last line without a newline counts
+    uint64_t lines(uint32_t n_newlines) const { return (uint64_t)n_newlines + (res->text[n - 1] != '\n' ? 1 : 0); }
+
+    // The first-appearance id table over d_tok[0, n_tok), n_tok > 0: table, slot and first stay in the members for the reader's
+    // numbering kernel (el_number_kernel, cp_fill_kernel), *n_names = the distinct names (`counted`: what the reader calls them in
+    // the error text).  PW_EDGELIST_NEEDS_HOST_READER: a table
+    // beyond 2^32 slots (the edge-list reader's 2^32 - 2 tokens can ask for it; the corpus reader's 2^31 cannot), no room.
+    int number_names(const pw::ElToken *d_tok, uint64_t n_tok, const char *counted, uint32_t *n_names) {
+        uint64_t table_size = 1024;
+        while (table_size < 2 * n_tok) table_size <<= 1;   // (n_tok < 2^32 - 1: at most 2^33 slots of which half stay free)
+        if (table_size > (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;
+        alloc(d_table, table_size);
+        alloc(d_slot, n_tok);
+        alloc(d_first, n_tok + 1);
+        alloc(d_tmp, pw::scan_scratch_elems(n_tok + 1));
+        if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+        const unsigned tok_grid = (unsigned)((n_tok + 256) / 256);
+        HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(uint32_t) * table_size, nullptr));
+        hipLaunchKernelGGL(pw::el_insert_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, d_tok, n_tok, d_table.p,
+                           (uint32_t)(table_size - 1), d_slot.p);
+        hipLaunchKernelGGL(pw::el_first_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const uint32_t *)d_table.p, (const uint32_t *)d_slot.p, n_tok, d_first.p);
+        pw::exclusive_scan_inplace(nullptr, d_first.p, n_tok + 1, d_tmp.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(n_names, d_first.p + n_tok, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (*n_names == 0 || *n_names > n_tok) return fail(PW_ERR_HIP, who + ": " + counted + " count out of range (internal error)");
+        return PW_EDGELIST_OK;
     }
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    *n_out = n;
-    return PW_EDGELIST_OK;
-}
+
+    // The names' spans, which the reader's numbering kernel left in d_off / d_len, into res; the flag word that kernel raises;
+    // every span inside the n_text bytes of the text; id_bytes.  PW_EDGELIST_NEEDS_HOST_READER: no host memory for the spans.
+    int download_names(const uint32_t *d_off, const uint32_t *d_len, uint32_t n_names, uint64_t n_text) {
+        try {
+            res->off.resize(n_names);
+            res->len.resize(n_names);
+        } catch (const std::bad_alloc &) {
+            return PW_EDGELIST_NEEDS_HOST_READER;
+        }
+        if (n_names) {
+            HIP_TRY(hipMemcpy(res->off.data(), d_off, sizeof(uint32_t) * n_names, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(res->len.data(), d_len, sizeof(uint32_t) * n_names, hipMemcpyDeviceToHost));
+        }
+        uint32_t h_flags = 0;
+        HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (h_flags) return fail(PW_ERR_HIP, who + ": the id table is inconsistent (internal error)");
+        for (uint32_t v = 0; v < n_names; v++) {
+            if ((uint64_t)res->off[v] + res->len[v] > n_text) return fail(PW_ERR_HIP, who + ": a name outside the text (internal error)");
+            res->id_bytes += res->len[v];
+        }
+        return PW_EDGELIST_OK;
+    }
+};
+
+}  // namespace
 
 PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int directed, const char *delimiter, int device, uint32_t flags,
                                          pw_csr_dev **csr, pw_edgelist_ids **ids, pw_edgelist_dev_stats *stats) {
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     if (!path || !csr || !ids) return fail(PW_ERR_INVALID, "null pointer");
     *csr = nullptr;
     *ids = nullptr;
@@ -1303,133 +1396,83 @@ PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int dir
     if (dl == 0 || dl > pw::EL_MAX_DELIM) return PW_EDGELIST_NEEDS_HOST_READER;   // (str.split("") raises in Python)
     for (size_t i = 0; i < dl; i++)
         if ((unsigned char)delimiter[i] >= 0x80 || delimiter[i] == '\n' || delimiter[i] == '\r') return PW_EDGELIST_NEEDS_HOST_READER;
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
 
-    // every buffer of the call, in front of `mem`: they go after its destructor has waited for the stream
-    DevBuf<char> d_text, d_delim;
-    DevBuf<uint32_t> d_flags, d_segcnt, d_tmp, d_starts, d_table, d_slot, d_first, d_idoff, d_idlen;
+    // the buffers only this reader uses, in front of `rd`: they go after its destructor has waited for the stream
+    DevBuf<char> d_delim;
+    DevBuf<uint32_t> d_segcnt, d_starts, d_idoff, d_idlen;
     DevBuf<pw::ElToken> d_tok;
     DevBuf<double> d_w64;
     DevBuf<int64_t> d_src, d_dst;
-    // ... and beside them the id handle until it is handed out
-    struct Mem {
-        pw_edgelist_ids *res = nullptr;
-        bool queued = false;
-        ~Mem() {
-            if (queued) (void)hipStreamSynchronize(nullptr);
-            delete res;
-        }
-    } mem;
-    // scratch that does not fit is no error: the host reader still works
-    bool no_room = false;
-    auto alloc = [&](auto &buf, uint64_t n) { if (!no_room && buf.alloc(n) != hipSuccess) no_room = true; };
+    TextRead rd("pw_edgelist_read_device");
 
-    // ---- upload (upload_text_file); the host keeps the bytes for the names
-    auto t0 = clk::now();
-    mem.res = new (std::nothrow) pw_edgelist_ids();
-    if (!mem.res) return PW_EDGELIST_NEEDS_HOST_READER;
-    uint64_t n = 0;
-    {
-        const int rc = upload_text_file(path, device, d_text, mem.res, &n);
-        if (rc != PW_EDGELIST_OK) return rc;
-    }
-    mem.queued = true;
-    char *const h_text = mem.res->text.get();
-    const double upload_ms = ms_since(t0);
+    // ---- upload; the host keeps the bytes for the names
+    if (const int rc = rd.upload(path, device)) return rc;
+    const uint64_t n = rd.n;
+    const double upload_ms = rd.lap();
 
     // ---- 1. byte classes and line starts
-    t0 = clk::now();
     const uint64_t n_seg = (n + pw::EL_SEG - 1) / pw::EL_SEG;
     const unsigned seg_grid = (unsigned)((n_seg + 3) / 4);
-    alloc(d_flags, 1);
-    alloc(d_segcnt, n_seg + 1);
-    alloc(d_tmp, pw::scan_scratch_elems(n_seg + 1));
-    alloc(d_delim, pw::EL_MAX_DELIM);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), nullptr));
+    rd.alloc(rd.d_flags, 1);
+    rd.alloc(d_segcnt, n_seg + 1);
+    rd.alloc(rd.d_tmp, pw::scan_scratch_elems(n_seg + 1));
+    rd.alloc(d_delim, pw::EL_MAX_DELIM);
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    uint32_t *const d_flags = rd.d_flags.p;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), nullptr));
     HIP_TRY(hipMemsetAsync(d_segcnt.p + n_seg, 0, sizeof(uint32_t), nullptr));   // (the scan's last input: its output is the total)
     HIP_TRY(hipMemcpyAsync(d_delim.p, delimiter, dl, hipMemcpyHostToDevice, nullptr));
-    hipLaunchKernelGGL(pw::el_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, d_segcnt.p, d_flags.p);
-    pw::exclusive_scan_inplace(nullptr, d_segcnt.p, n_seg + 1, d_tmp.p);
+    hipLaunchKernelGGL(pw::el_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)rd.d_text.p, n, n_seg, d_segcnt.p, d_flags);
+    pw::exclusive_scan_inplace(nullptr, d_segcnt.p, n_seg + 1, rd.d_tmp.p);
     HIP_TRY(hipGetLastError());
     uint32_t h_flags = 0, n_newlines = 0;
     HIP_TRY(hipMemcpy(&n_newlines, d_segcnt.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h_flags, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (h_flags) return PW_EDGELIST_NEEDS_HOST_READER;
     const uint64_t n_starts = (uint64_t)n_newlines + 1;
-    const uint64_t n_lines = (uint64_t)n_newlines + (h_text[n - 1] != '\n' ? 1 : 0);   // a last line without a newline counts
+    const uint64_t n_lines = rd.lines(n_newlines);
     const uint64_t n_tok = 2 * n_lines;
     if (n_tok >= 0xffffffffull || n_lines * (directed ? 1u : 2u) >= 0xffffffffull) return PW_EDGELIST_NEEDS_HOST_READER;
-    alloc(d_starts, n_starts);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    rd.alloc(d_starts, n_starts);
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
     HIP_TRY(hipMemsetAsync(d_starts.p, 0, sizeof(uint32_t), nullptr));
-    hipLaunchKernelGGL(pw::el_starts_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, (const uint32_t *)d_segcnt.p,
+    hipLaunchKernelGGL(pw::el_starts_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)rd.d_text.p, n, n_seg, (const uint32_t *)d_segcnt.p,
                        n_starts, d_starts.p);
 
     // ---- 2. per-line records
-    alloc(d_tok, n_tok);
-    if (weighted) alloc(d_w64, n_lines);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    rd.alloc(d_tok, n_tok);
+    if (weighted) rd.alloc(d_w64, n_lines);
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
     const unsigned line_grid = (unsigned)((n_lines + 255) / 256), tok_grid = (unsigned)((n_tok + 256) / 256);
-    hipLaunchKernelGGL(pw::el_lines_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, (const uint32_t *)d_starts.p, n_starts,
-                       n_lines, (const char *)d_delim.p, (uint32_t)dl, weighted ? 1 : 0, d_tok.p, d_w64.p, d_flags.p);
+    hipLaunchKernelGGL(pw::el_lines_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const char *)rd.d_text.p, n, (const uint32_t *)d_starts.p, n_starts,
+                       n_lines, (const char *)d_delim.p, (uint32_t)dl, weighted ? 1 : 0, d_tok.p, d_w64.p, d_flags);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h_flags, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (h_flags) return PW_EDGELIST_NEEDS_HOST_READER;
     d_starts.release();
     d_segcnt.release();
-    const double scan_ms = ms_since(t0);
+    const double scan_ms = rd.lap();
 
     // ---- 3. first-appearance numbering
-    t0 = clk::now();
-    uint64_t table_size = 1024;
-    while (table_size < 2 * n_tok) table_size <<= 1;   // (n_tok < 2^32 - 1: at most 2^33 slots of which half stay free)
-    if (table_size > (1ull << 32)) return PW_EDGELIST_NEEDS_HOST_READER;
-    alloc(d_table, table_size);
-    alloc(d_slot, n_tok);
-    alloc(d_first, n_tok + 1);
-    alloc(d_tmp, pw::scan_scratch_elems(n_tok + 1));
-    alloc(d_src, n_lines);
-    alloc(d_dst, n_lines);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(uint32_t) * table_size, nullptr));
-    hipLaunchKernelGGL(pw::el_insert_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, (const pw::ElToken *)d_tok.p, n_tok, d_table.p,
-                       (uint32_t)(table_size - 1), d_slot.p);
-    hipLaunchKernelGGL(pw::el_first_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const uint32_t *)d_table.p, (const uint32_t *)d_slot.p, n_tok, d_first.p);
-    pw::exclusive_scan_inplace(nullptr, d_first.p, n_tok + 1, d_tmp.p);
-    HIP_TRY(hipGetLastError());
     uint32_t n_nodes = 0;
-    HIP_TRY(hipMemcpy(&n_nodes, d_first.p + n_tok, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n_nodes == 0 || n_nodes > n_tok) return fail(PW_ERR_HIP, "pw_edgelist_read_device: vertex count out of range (internal error)");
-    alloc(d_idoff, n_nodes);
-    alloc(d_idlen, n_nodes);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    hipLaunchKernelGGL(pw::el_number_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const pw::ElToken *)d_tok.p, (const uint32_t *)d_table.p,
-                       (const uint32_t *)d_slot.p, (const uint32_t *)d_first.p, n_tok, (uint64_t)n_nodes, d_src.p, d_dst.p, d_idoff.p, d_idlen.p, d_flags.p);
+    if (const int rc = rd.number_names(d_tok.p, n_tok, "vertex", &n_nodes)) return rc;
+    rd.alloc(d_src, n_lines);
+    rd.alloc(d_dst, n_lines);
+    rd.alloc(d_idoff, n_nodes);
+    rd.alloc(d_idlen, n_nodes);
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    hipLaunchKernelGGL(pw::el_number_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const pw::ElToken *)d_tok.p, (const uint32_t *)rd.d_table.p,
+                       (const uint32_t *)rd.d_slot.p, (const uint32_t *)rd.d_first.p, n_tok, (uint64_t)n_nodes, d_src.p, d_dst.p, d_idoff.p, d_idlen.p, d_flags);
     HIP_TRY(hipGetLastError());
-    try {
-        mem.res->off.resize(n_nodes);
-        mem.res->len.resize(n_nodes);
-    } catch (const std::bad_alloc &) {
-        return PW_EDGELIST_NEEDS_HOST_READER;
-    }
-    HIP_TRY(hipMemcpy(mem.res->off.data(), d_idoff.p, sizeof(uint32_t) * n_nodes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mem.res->len.data(), d_idlen.p, sizeof(uint32_t) * n_nodes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (h_flags) return fail(PW_ERR_HIP, "pw_edgelist_read_device: the id table is inconsistent (internal error)");
-    for (uint32_t v = 0; v < n_nodes; v++) {
-        if ((uint64_t)mem.res->off[v] + mem.res->len[v] > n) return fail(PW_ERR_HIP, "pw_edgelist_read_device: a name outside the text (internal error)");
-        mem.res->id_bytes += mem.res->len[v];
-    }
-    for (DevBuf<uint32_t> *b : {&d_table, &d_slot, &d_first, &d_idoff, &d_idlen, &d_tmp}) b->release();
+    if (const int rc = rd.download_names(d_idoff.p, d_idlen.p, n_nodes, n)) return rc;
+    // (released before the build: its scratch takes their place, the peak footprint stays that of the larger of the two)
+    for (DevBuf<uint32_t> *b : {&rd.d_table, &rd.d_slot, &rd.d_first, &d_idoff, &d_idlen, &rd.d_tmp}) b->release();
     d_tok.release();
-    d_text.release();
-    const double ids_ms = ms_since(t0);
+    rd.d_text.release();
+    const double ids_ms = rd.lap();
 
     // ---- 4. the CSR (coo_csr.hip.h), the sort carrying the line index so that the float64 weights can be compared
-    t0 = clk::now();
     pw_csr_dev *c = nullptr;
     int conflict = 0;
     const int rc = coo_to_csr_build(device, d_src.p, d_dst.p, nullptr, weighted ? d_w64.p : nullptr, n_lines, n_nodes, directed, &c, &conflict,
@@ -1438,12 +1481,11 @@ PW_EXPORT int pw_edgelist_read_device_ex(const char *path, int weighted, int dir
     if (rc) return rc;
     if (conflict || !c) return PW_EDGELIST_NEEDS_HOST_READER;   // the reference warns about the overwritten weight
     if (stats) {
-        stats->upload_ms = upload_ms; stats->scan_ms = scan_ms; stats->ids_ms = ids_ms; stats->build_ms = ms_since(t0);
+        stats->upload_ms = upload_ms; stats->scan_ms = scan_ms; stats->ids_ms = ids_ms; stats->build_ms = rd.lap();
         stats->lines = n_lines; stats->n_nodes = n_nodes; stats->file_bytes = n;
     }
     *csr = c;
-    *ids = mem.res;
-    mem.res = nullptr;
+    *ids = rd.res.release();
     return PW_EDGELIST_OK;
 }
 
@@ -1489,157 +1531,101 @@ PW_EXPORT int pw_corpus_dev_export(const pw_corpus_dev *c, uint32_t *h_out) {
 }
 
 PW_EXPORT int pw_corpus_read_device(const char *path, int device, pw_corpus_dev **out, pw_edgelist_ids **ids, pw_corpus_dev_stats *stats) {
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     if (!path || !out || !ids) return fail(PW_ERR_INVALID, "null pointer");
     *out = nullptr;
     *ids = nullptr;
     if (stats) memset(stats, 0, sizeof(*stats));
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
 
-    // every buffer of the call, in front of `mem`: they go after its destructor has waited for the stream
-    DevBuf<char> d_text;
-    DevBuf<uint32_t> d_flags, d_segnl, d_segts, d_tmp, d_tokoff, d_tokline, d_linefirst, d_table, d_slot, d_first, d_nameoff, d_namelen;
+    // the buffers only this reader uses and the matrix until it is handed out, in front of `rd`: they go after its destructor
+    // has waited for the stream
+    DevBuf<uint32_t> d_segnl, d_segts, d_tokoff, d_tokline, d_linefirst, d_nameoff, d_namelen;
     DevBuf<pw::ElToken> d_tok;
-    // ... and beside them the two handles until they are handed out
-    struct Mem {
-        pw_edgelist_ids *res = nullptr;
-        pw_corpus_dev *mat = nullptr;
-        bool queued = false;
-        ~Mem() {
-            if (queued) (void)hipStreamSynchronize(nullptr);
-            delete res;
-            delete mat;
-        }
-    } mem;
-    // scratch that does not fit is no error: the host reader still works
-    bool no_room = false;
-    auto alloc = [&](auto &buf, uint64_t n) { if (!no_room && buf.alloc(n) != hipSuccess) no_room = true; };
+    std::unique_ptr<pw_corpus_dev> mat(new (std::nothrow) pw_corpus_dev());
+    TextRead rd("pw_corpus_read_device");
 
-    // ---- upload (upload_text_file); the host keeps the bytes for the names
-    auto t0 = clk::now();
-    mem.res = new (std::nothrow) pw_edgelist_ids();
-    mem.mat = new (std::nothrow) pw_corpus_dev();
-    if (!mem.res || !mem.mat) return PW_EDGELIST_NEEDS_HOST_READER;
-    uint64_t n = 0;
-    {
-        const int rc = upload_text_file(path, device, d_text, mem.res, &n);
-        if (rc != PW_EDGELIST_OK) return rc;
-    }
-    mem.queued = true;
-    mem.mat->device = device;
-    const double upload_ms = ms_since(t0);
+    // ---- upload; the host keeps the bytes for the names
+    if (!mat) return PW_EDGELIST_NEEDS_HOST_READER;
+    if (const int rc = rd.upload(path, device)) return rc;
+    const uint64_t n = rd.n;
+    mat->device = device;
+    const double upload_ms = rd.lap();
 
     // ---- 1. + 2. byte classes; newlines and token starts counted, scanned and placed; the width
-    t0 = clk::now();
     const uint64_t n_seg = (n + pw::CP_SEG - 1) / pw::CP_SEG;
     const unsigned seg_grid = (unsigned)((n_seg + 3) / 4);
-    alloc(d_flags, 2);   // [0] the flags, [1] the most tokens in a line
-    alloc(d_segnl, n_seg + 1);
-    alloc(d_segts, n_seg + 1);
-    alloc(d_tmp, pw::scan_scratch_elems(n_seg + 1));
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    HIP_TRY(hipMemsetAsync(d_flags.p, 0, 2 * sizeof(uint32_t), nullptr));
+    rd.alloc(rd.d_flags, 2);   // [0] the flags, [1] the most tokens in a line
+    rd.alloc(d_segnl, n_seg + 1);
+    rd.alloc(d_segts, n_seg + 1);
+    rd.alloc(rd.d_tmp, pw::scan_scratch_elems(n_seg + 1));
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    uint32_t *const d_flags = rd.d_flags.p;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, 2 * sizeof(uint32_t), nullptr));
     HIP_TRY(hipMemsetAsync(d_segnl.p + n_seg, 0, sizeof(uint32_t), nullptr));   // (the scans' last inputs: their outputs are the totals)
     HIP_TRY(hipMemsetAsync(d_segts.p + n_seg, 0, sizeof(uint32_t), nullptr));
-    hipLaunchKernelGGL(pw::cp_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, d_segnl.p, d_segts.p, d_flags.p);
-    pw::exclusive_scan_inplace(nullptr, d_segnl.p, n_seg + 1, d_tmp.p);
-    pw::exclusive_scan_inplace(nullptr, d_segts.p, n_seg + 1, d_tmp.p);
+    hipLaunchKernelGGL(pw::cp_count_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)rd.d_text.p, n, n_seg, d_segnl.p, d_segts.p, d_flags);
+    pw::exclusive_scan_inplace(nullptr, d_segnl.p, n_seg + 1, rd.d_tmp.p);
+    pw::exclusive_scan_inplace(nullptr, d_segts.p, n_seg + 1, rd.d_tmp.p);
     HIP_TRY(hipGetLastError());
     uint32_t h_flags = 0, n_newlines = 0, n_tok32 = 0;
     HIP_TRY(hipMemcpy(&n_newlines, d_segnl.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&n_tok32, d_segts.p + n_seg, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h_flags, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (h_flags) return PW_EDGELIST_NEEDS_HOST_READER;
     const uint64_t n_tok = n_tok32;   // (at most half the bytes and one: below 2^31 + 1)
-    const uint64_t n_lines = (uint64_t)n_newlines + (mem.res->text[n - 1] != '\n' ? 1 : 0);   // a last line without a newline counts
-    alloc(d_tokoff, n_tok);
-    alloc(d_tokline, n_tok);
-    alloc(d_linefirst, (uint64_t)n_newlines + 2);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    hipLaunchKernelGGL(pw::cp_place_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, n_seg, (const uint32_t *)d_segnl.p,
+    const uint64_t n_lines = rd.lines(n_newlines);
+    rd.alloc(d_tokoff, n_tok);
+    rd.alloc(d_tokline, n_tok);
+    rd.alloc(d_linefirst, (uint64_t)n_newlines + 2);
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    hipLaunchKernelGGL(pw::cp_place_kernel, dim3(seg_grid), dim3(256), 0, nullptr, (const char *)rd.d_text.p, n, n_seg, (const uint32_t *)d_segnl.p,
                        (const uint32_t *)d_segts.p, (uint64_t)n_newlines, n_tok, d_tokoff.p, d_tokline.p, d_linefirst.p);
     const unsigned line_grid = (unsigned)((n_lines + 255) / 256), tok_grid = (unsigned)((n_tok + 256) / 256);
-    hipLaunchKernelGGL(pw::cp_width_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const uint32_t *)d_linefirst.p, n_lines, d_flags.p + 1);
+    hipLaunchKernelGGL(pw::cp_width_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const uint32_t *)d_linefirst.p, n_lines, d_flags + 1);
     HIP_TRY(hipGetLastError());
     uint32_t max_len = 0;
-    HIP_TRY(hipMemcpy(&max_len, d_flags.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&max_len, d_flags + 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (max_len > n_tok) return fail(PW_ERR_HIP, "pw_corpus_read_device: line length out of range (internal error)");
     const uint64_t width = (uint64_t)(max_len ? max_len : 1u) + 1;
     d_segnl.release();
     d_segts.release();
-    const double scan_ms = ms_since(t0);
+    const double scan_ms = rd.lap();
 
-    // ---- 3. token records, first-appearance numbering (the edge-list reader's id table)
-    t0 = clk::now();
+    // ---- 3. token records, first-appearance numbering (a file without tokens: no table, no names)
     uint32_t n_names = 0;
     if (n_tok) {
-        uint64_t table_size = 1024;
-        while (table_size < 2 * n_tok) table_size <<= 1;
-        alloc(d_tok, n_tok);
-        alloc(d_table, table_size);
-        alloc(d_slot, n_tok);
-        alloc(d_first, n_tok + 1);
-        alloc(d_tmp, pw::scan_scratch_elems(n_tok + 1));
-        if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-        HIP_TRY(hipMemsetAsync(d_table.p, 0xff, sizeof(uint32_t) * table_size, nullptr));
-        hipLaunchKernelGGL(pw::cp_tokens_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, n, (const uint32_t *)d_tokoff.p, n_tok,
+        rd.alloc(d_tok, n_tok);
+        if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+        hipLaunchKernelGGL(pw::cp_tokens_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)rd.d_text.p, n, (const uint32_t *)d_tokoff.p, n_tok,
                            d_tok.p);
-        hipLaunchKernelGGL(pw::el_insert_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const char *)d_text.p, (const pw::ElToken *)d_tok.p, n_tok,
-                           d_table.p, (uint32_t)(table_size - 1), d_slot.p);
-        hipLaunchKernelGGL(pw::el_first_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const uint32_t *)d_table.p, (const uint32_t *)d_slot.p, n_tok,
-                           d_first.p);
-        pw::exclusive_scan_inplace(nullptr, d_first.p, n_tok + 1, d_tmp.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(&n_names, d_first.p + n_tok, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (n_names == 0 || n_names > n_tok) return fail(PW_ERR_HIP, "pw_corpus_read_device: name count out of range (internal error)");
+        if (const int rc = rd.number_names(d_tok.p, n_tok, "name", &n_names)) return rc;
     }
-    const double tokens_ms = ms_since(t0);
+    const double tokens_ms = rd.lap();
 
     // ---- 4. the matrix and the names' spans
-    t0 = clk::now();
     if (n_lines * width > (1ull << 40)) return PW_EDGELIST_NEEDS_HOST_READER;   // (4 TiB of cells: no device holds them)
-    alloc(mem.mat->d_mat, n_lines * width);
-    alloc(d_nameoff, n_names);
-    alloc(d_namelen, n_names);
-    if (no_room) return PW_EDGELIST_NEEDS_HOST_READER;
-    HIP_TRY(hipMemsetAsync(mem.mat->d_mat.p, 0, sizeof(uint32_t) * n_lines * width, nullptr));
+    rd.alloc(mat->d_mat, n_lines * width);
+    rd.alloc(d_nameoff, n_names);
+    rd.alloc(d_namelen, n_names);
+    if (rd.no_room) return PW_EDGELIST_NEEDS_HOST_READER;
+    HIP_TRY(hipMemsetAsync(mat->d_mat.p, 0, sizeof(uint32_t) * n_lines * width, nullptr));
     if (n_tok)
-        hipLaunchKernelGGL(pw::cp_fill_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const pw::ElToken *)d_tok.p, (const uint32_t *)d_table.p,
-                           (const uint32_t *)d_slot.p, (const uint32_t *)d_first.p, (const uint32_t *)d_tokline.p, (const uint32_t *)d_linefirst.p, n_tok,
-                           (uint64_t)n_names, n_lines, (uint32_t)width, mem.mat->d_mat.p, d_nameoff.p, d_namelen.p, d_flags.p);
+        hipLaunchKernelGGL(pw::cp_fill_kernel, dim3(tok_grid), dim3(256), 0, nullptr, (const pw::ElToken *)d_tok.p, (const uint32_t *)rd.d_table.p,
+                           (const uint32_t *)rd.d_slot.p, (const uint32_t *)rd.d_first.p, (const uint32_t *)d_tokline.p, (const uint32_t *)d_linefirst.p, n_tok,
+                           (uint64_t)n_names, n_lines, (uint32_t)width, mat->d_mat.p, d_nameoff.p, d_namelen.p, d_flags);
     hipLaunchKernelGGL(pw::cp_lengths_kernel, dim3(line_grid), dim3(256), 0, nullptr, (const uint32_t *)d_linefirst.p, n_lines, (uint32_t)width,
-                       mem.mat->d_mat.p);
+                       mat->d_mat.p);
     HIP_TRY(hipGetLastError());
-    try {
-        mem.res->off.resize(n_names);
-        mem.res->len.resize(n_names);
-    } catch (const std::bad_alloc &) {
-        return PW_EDGELIST_NEEDS_HOST_READER;
-    }
-    if (n_names) {
-        HIP_TRY(hipMemcpy(mem.res->off.data(), d_nameoff.p, sizeof(uint32_t) * n_names, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(mem.res->len.data(), d_namelen.p, sizeof(uint32_t) * n_names, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(hipMemcpy(&h_flags, d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (h_flags) return fail(PW_ERR_HIP, "pw_corpus_read_device: the id table is inconsistent (internal error)");
-    for (uint32_t v = 0; v < n_names; v++) {
-        if ((uint64_t)mem.res->off[v] + mem.res->len[v] > n) return fail(PW_ERR_HIP, "pw_corpus_read_device: a name outside the text (internal error)");
-        mem.res->id_bytes += mem.res->len[v];
-    }
-    mem.mat->n_rows = n_lines;
-    mem.mat->width = width;
-    mem.mat->n_tokens = n_tok;
+    if (const int rc = rd.download_names(d_nameoff.p, d_namelen.p, n_names, n)) return rc;
+    mat->n_rows = n_lines;
+    mat->width = width;
+    mat->n_tokens = n_tok;
     if (stats) {
-        stats->upload_ms = upload_ms; stats->scan_ms = scan_ms; stats->tokens_ms = tokens_ms; stats->fill_ms = ms_since(t0);
+        stats->upload_ms = upload_ms; stats->scan_ms = scan_ms; stats->tokens_ms = tokens_ms; stats->fill_ms = rd.lap();
         stats->file_bytes = n; stats->lines = n_lines; stats->tokens = n_tok; stats->names = n_names;
     }
-    *out = mem.mat;
-    *ids = mem.res;
-    mem.mat = nullptr;
-    mem.res = nullptr;
+    *out = mat.release();
+    *ids = rd.res.release();
     return PW_EDGELIST_OK;
 }
 
@@ -1736,9 +1722,10 @@ PW_EXPORT int pw_dense_create(const double *data, uint32_t n_nodes, int device, 
         }
         indptr[i + 1] = (uint32_t)nnz;
     }
-    pw_graph *g = new pw_graph();
+    GraphOwner owner(new pw_graph());   // (behind the host arrays above: every copy below is synchronous, nothing is in flight)
+    pw_graph *const g = owner.get();
     int rc = graph_common_init(g, device);
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     g->gd->kind = 1;
     g->gd->n_nodes = n_nodes;
     g->gd->nnz = (uint32_t)nnz;
@@ -1762,22 +1749,58 @@ PW_EXPORT int pw_dense_create(const double *data, uint32_t n_nodes, int device, 
         }
         rc = up(g->gd->d_deg, deg.data(), deg.size());
     }
-    if (rc) { pw_graph_destroy(g); return rc; }
-    *out = g;
+    if (rc) return rc;
+    *out = owner.release();
     return PW_OK;
 }
+
+// ---- the degrees of a dense handle; dense handles built on the device (csrc/dense_build.hip.h) -------------------------------
+namespace {
+
+// The degree-finishing pass of every dense handle whose degrees a kernel counted: the running sum of deg[0, n_nodes) with the
+// edge limit and its text -> indptr (host), max_degree and nnz.
+int dense_indptr_from_degrees(GraphData &gd, const std::vector<uint32_t> &deg, std::vector<uint32_t> &indptr) {
+    const uint64_t n = gd.n_nodes;
+    indptr.assign(n + 1, 0);
+    uint64_t nnz = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        nnz += deg[i];
+        if (nnz >= 0xffffffffull) return fail(PW_ERR_INVALID, "dense graph has more than 2^32-1 edges");
+        indptr[i + 1] = (uint32_t)nnz;
+        if (deg[i] > gd.max_degree) gd.max_degree = deg[i];
+    }
+    gd.nnz = (uint32_t)nnz;
+    return 0;
+}
+
+// what the two device builders do once adjbits, deg and the flags are on the device: degrees down, the pass above, and -- theirs
+// alone: a handle from packed bits has no values to reduce -- unit / dense_nonneg from the flag word
+int dense_finish_degrees(pw_graph *g, uint32_t flags, std::vector<uint32_t> &indptr) {
+    GraphData &gd = *g->gd;
+    std::vector<uint32_t> deg(gd.n_nodes);
+    HIP_TRY(hipMemcpy(deg.data(), gd.d_deg.p, sizeof(uint32_t) * (size_t)gd.n_nodes, hipMemcpyDeviceToHost));
+    if (int rc = dense_indptr_from_degrees(gd, deg, indptr)) return rc;
+    gd.unit = !(flags & pw::DENSE_FLAG_NOT_UNIT);
+    gd.dense_nonneg = !(flags & pw::DENSE_FLAG_NOT_NONNEG);
+    return 0;
+}
+
+unsigned dense_row_grid(uint64_t n) { return (unsigned)std::min<uint64_t>(n, 1u << 20); }   // one workgroup per row, rows strided beyond
+
+}  // namespace
 
 PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, int on_device, int device,
                                    pw_graph **out) {
     if (!adjbits || !out || n_nodes == 0) return fail(PW_ERR_INVALID, "null pointer / empty graph");
-    pw_graph *g = new pw_graph();
+    GraphOwner owner(new pw_graph());   // (in front of the host vectors; every kernel and copy below is waited for where it is issued)
+    pw_graph *const g = owner.get();
     int rc = graph_common_init(g, device);
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     const uint64_t n = n_nodes;
     const uint32_t wpr = (uint32_t)((n + 63) / 64);
     g->gd->kind = 1;
     g->gd->n_nodes = n_nodes;
-    g->gd->unit = true;
+    g->gd->unit = true;   // (and dense_nonneg stays false: pw_dense_export's flags word of such a handle is 1)
     g->gd->bits_only = true;
     g->gd->words_per_row = wpr;
     const size_t bytes = sizeof(uint64_t) * (size_t)n * wpr;
@@ -1790,59 +1813,26 @@ PW_EXPORT int pw_dense_create_bits(const uint64_t *adjbits, uint32_t n_nodes, in
         hipLaunchKernelGGL(pw::dense_degree_kernel, dim3(g->n_cu * 8), dim3(256), 0, g->stream, g->gd->d_adjbits.p, n_nodes, wpr, g->gd->d_deg.p);
         e = hipGetLastError();
     }
-    std::vector<uint32_t> deg(n), indptr(n + 1, 0);
+    std::vector<uint32_t> deg(n), indptr;
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e == hipSuccess) e = hipMemcpy(deg.data(), g->gd->d_deg.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
-    uint64_t nnz = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        nnz += deg[i];
-        if (nnz >= 0xffffffffull) { pw_graph_destroy(g); return fail(PW_ERR_INVALID, "dense graph has more than 2^32-1 edges"); }
-        indptr[i + 1] = (uint32_t)nnz;
-        if (deg[i] > g->gd->max_degree) g->gd->max_degree = deg[i];
-    }
-    g->gd->nnz = (uint32_t)nnz;
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e));
+    if ((rc = dense_indptr_from_degrees(*g->gd, deg, indptr))) return rc;
     e = g->gd->d_indptr.alloc(n + 1);   // only used for stream offsets
     if (e == hipSuccess) e = hipMemcpy(g->gd->d_indptr.p, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { pw_graph_destroy(g); return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e)); }
-    *out = g;
+    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_dense_create_bits: ") + hipGetErrorString(e));
+    *out = owner.release();
     return PW_OK;
 }
-
-// ---- dense handles built on the device (csrc/dense_build.hip.h) -------------------------------------------------------------
-namespace {
-
-// what the two device builders share once adjbits, deg and the flags are on the device: degrees down, indptr and max_degree
-// as pw_dense_create_bits computes them (same edge limit, same message), indptr up
-int dense_finish_degrees(pw_graph *g, uint32_t flags, std::vector<uint32_t> &indptr) {
-    GraphData &gd = *g->gd;
-    const uint64_t n = gd.n_nodes;
-    std::vector<uint32_t> deg(n);
-    HIP_TRY(hipMemcpy(deg.data(), gd.d_deg.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    indptr.assign(n + 1, 0);
-    uint64_t nnz = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        nnz += deg[i];
-        if (nnz >= 0xffffffffull) return fail(PW_ERR_INVALID, "dense graph has more than 2^32-1 edges");
-        indptr[i + 1] = (uint32_t)nnz;
-        if (deg[i] > gd.max_degree) gd.max_degree = deg[i];
-    }
-    gd.nnz = (uint32_t)nnz;
-    gd.unit = !(flags & pw::DENSE_FLAG_NOT_UNIT);
-    gd.dense_nonneg = !(flags & pw::DENSE_FLAG_NOT_NONNEG);
-    return 0;
-}
-
-unsigned dense_row_grid(uint64_t n) { return (unsigned)std::min<uint64_t>(n, 1u << 20); }   // one workgroup per row, rows strided beyond
-
-}  // namespace
 
 PW_EXPORT int pw_dense_create_device(int device, const void *d_data, int is_f32, uint32_t n_nodes, pw_graph **out, double *build_ms) {
     if (!d_data || !out) return fail(PW_ERR_INVALID, "null pointer");
     if (n_nodes == 0) return fail(PW_ERR_INVALID, "pw_dense_create_device: empty graph");
-    pw_graph *g = new pw_graph();
+    // the owner in front of d_flags, which kernels on g->stream write: d_flags is freed first, and hipFree waits for the device
+    GraphOwner owner(new pw_graph());
+    pw_graph *const g = owner.get();
     int rc = graph_common_init(g, device);
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     GraphData &gd = *g->gd;
     const uint64_t n = n_nodes;
     const uint32_t wpr = (uint32_t)((n + 63) / 64);
@@ -1852,61 +1842,57 @@ PW_EXPORT int pw_dense_create_device(int device, const void *d_data, int is_f32,
     DevBuf<uint32_t> d_flags;
     // the kernels run on the handle's stream between event pairs; allocations, the degree download and the indptr upload lie
     // outside the pairs (build_ms as pw_csr_dev's is defined)
-    auto body = [&]() -> int {
-        HIP_TRY(gd.d_adjbits.alloc(n * wpr));
-        HIP_TRY(gd.d_deg.alloc(n));
-        HIP_TRY(d_flags.alloc(1));
-        HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
-        HIP_TRY(hipEventRecord(g->ev[0], g->stream));
+    HIP_TRY(gd.d_adjbits.alloc(n * wpr));
+    HIP_TRY(gd.d_deg.alloc(n));
+    HIP_TRY(d_flags.alloc(1));
+    HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
+    HIP_TRY(hipEventRecord(g->ev[0], g->stream));
+    if (is_f32)
+        hipLaunchKernelGGL(pw::dense_count_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
+                           gd.d_adjbits.p, gd.d_deg.p, d_flags.p);
+    else
+        hipLaunchKernelGGL(pw::dense_count_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
+                           gd.d_adjbits.p, gd.d_deg.p, d_flags.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->ev[1], g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> indptr;
+    if ((rc = dense_finish_degrees(g, flags, indptr))) return rc;
+    const uint64_t nnz = gd.nnz;
+    HIP_TRY(gd.d_indptr.alloc(n + 1));
+    HIP_TRY(hipMemcpy(gd.d_indptr.p, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice));
+    HIP_TRY(gd.d_indices.alloc(nnz));
+    if (!gd.unit) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
+    HIP_TRY(hipEventRecord(g->ev[2], g->stream));
+    if (nnz) {
         if (is_f32)
-            hipLaunchKernelGGL(pw::dense_count_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
-                               gd.d_adjbits.p, gd.d_deg.p, d_flags.p);
+            hipLaunchKernelGGL(pw::dense_fill_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
+                               (const uint64_t *)gd.d_adjbits.p, (const uint32_t *)gd.d_indptr.p, gd.d_indices.p, (double *)gd.d_data.p);
         else
-            hipLaunchKernelGGL(pw::dense_count_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
-                               gd.d_adjbits.p, gd.d_deg.p, d_flags.p);
+            hipLaunchKernelGGL(pw::dense_fill_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
+                               (const uint64_t *)gd.d_adjbits.p, (const uint32_t *)gd.d_indptr.p, gd.d_indices.p, (double *)gd.d_data.p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(g->ev[1], g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        uint32_t flags = 0;
-        HIP_TRY(hipMemcpy(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> indptr;
-        int r = dense_finish_degrees(g, flags, indptr);
-        if (r) return r;
-        const uint64_t nnz = gd.nnz;
-        HIP_TRY(gd.d_indptr.alloc(n + 1));
-        HIP_TRY(hipMemcpy(gd.d_indptr.p, indptr.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice));
-        HIP_TRY(gd.d_indices.alloc(nnz));
-        if (!gd.unit) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
-        HIP_TRY(hipEventRecord(g->ev[2], g->stream));
-        if (nnz) {
-            if (is_f32)
-                hipLaunchKernelGGL(pw::dense_fill_kernel<float>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const float *)d_data, n_nodes, wpr,
-                                   (const uint64_t *)gd.d_adjbits.p, (const uint32_t *)gd.d_indptr.p, gd.d_indices.p, (double *)gd.d_data.p);
-            else
-                hipLaunchKernelGGL(pw::dense_fill_kernel<double>, dim3(dense_row_grid(n)), dim3(256), 0, g->stream, (const double *)d_data, n_nodes, wpr,
-                                   (const uint64_t *)gd.d_adjbits.p, (const uint32_t *)gd.d_indptr.p, gd.d_indices.p, (double *)gd.d_data.p);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(g->ev[3], g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        float ms_count = 0, ms_fill = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_count, g->ev[0], g->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_fill, g->ev[2], g->ev[3]));
-        if (build_ms) *build_ms = (double)ms_count + (double)ms_fill;
-        return 0;
-    };
-    rc = body();
-    if (rc) { pw_graph_destroy(g); return rc; }
-    *out = g;
+    }
+    HIP_TRY(hipEventRecord(g->ev[3], g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    float ms_count = 0, ms_fill = 0;
+    HIP_TRY(hipEventElapsedTime(&ms_count, g->ev[0], g->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_fill, g->ev[2], g->ev[3]));
+    if (build_ms) *build_ms = (double)ms_count + (double)ms_fill;
+    *out = owner.release();
     return PW_OK;
 }
 
 PW_EXPORT int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, double *build_ms) {
     if (!c || !out) return fail(PW_ERR_INVALID, "null pointer");
     if (c->n_nodes == 0) return fail(PW_ERR_INVALID, "pw_dense_create_from_csr: empty graph");
-    pw_graph *g = new pw_graph();
+    // the owner in front of d_flags, which kernels on g->stream write: d_flags is freed first, and hipFree waits for the device
+    GraphOwner owner(new pw_graph());
+    pw_graph *const g = owner.get();
     int rc = graph_common_init(g, c->device);
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     GraphData &gd = *g->gd;
     const uint64_t n = c->n_nodes, nnz = c->nnz;
     const uint32_t wpr = (uint32_t)((n + 63) / 64);
@@ -1914,46 +1900,40 @@ PW_EXPORT int pw_dense_create_from_csr(const pw_csr_dev *c, pw_graph **out, doub
     gd.n_nodes = (uint32_t)n;
     gd.words_per_row = wpr;
     DevBuf<uint32_t> d_flags;
-    auto body = [&]() -> int {
-        HIP_TRY(gd.d_adjbits.alloc(n * wpr));
-        HIP_TRY(gd.d_deg.alloc(n));
-        HIP_TRY(gd.d_indptr.alloc(n + 1));
-        HIP_TRY(gd.d_indices.alloc(nnz));
-        const bool weights = c->d_data64.p || c->d_data.p;
-        if (weights) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
-        HIP_TRY(d_flags.alloc(1));
-        HIP_TRY(hipEventRecord(g->ev[0], g->stream));
-        HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
-        HIP_TRY(hipMemsetAsync(gd.d_adjbits.p, 0, sizeof(uint64_t) * n * wpr, g->stream));
-        HIP_TRY(hipMemcpyAsync(gd.d_indptr.p, c->d_indptr.p, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToDevice, g->stream));
-        if (nnz) HIP_TRY(hipMemcpyAsync(gd.d_indices.p, c->d_indices.p, sizeof(uint32_t) * nnz, hipMemcpyDeviceToDevice, g->stream));
-        const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, 1u << 20);
-        if (c->d_data64.p)   // an edge-list file's float64 weights as parsed: stored as they are, the flags reduced from them
-            hipLaunchKernelGGL(pw::csr_to_dense_kernel<double>, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p,
-                               (const uint32_t *)c->d_indices.p, (const double *)c->d_data64.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p,
-                               gd.d_deg.p, d_flags.p);
-        else
-            hipLaunchKernelGGL(pw::csr_to_dense_kernel<float>, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p,
-                               (const uint32_t *)c->d_indices.p, (const float *)c->d_data.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p,
-                               gd.d_deg.p, d_flags.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(g->ev[1], g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        uint32_t flags = 0;
-        HIP_TRY(hipMemcpy(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> indptr;
-        int r = dense_finish_degrees(g, flags, indptr);
-        if (r) return r;
-        if (gd.nnz != nnz) return fail(PW_ERR_HIP, "pw_dense_create_from_csr: degrees do not add up to the CSR's entries (internal error)");
-        if (gd.unit) gd.d_data.release();   // every weight 1.0: the values are dropped, as pw_dense_create drops them
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
-        if (build_ms) *build_ms = ms;
-        return 0;
-    };
-    rc = body();
-    if (rc) { pw_graph_destroy(g); return rc; }
-    *out = g;
+    HIP_TRY(gd.d_adjbits.alloc(n * wpr));
+    HIP_TRY(gd.d_deg.alloc(n));
+    HIP_TRY(gd.d_indptr.alloc(n + 1));
+    HIP_TRY(gd.d_indices.alloc(nnz));
+    const bool weights = c->d_data64.p || c->d_data.p;
+    if (weights) HIP_TRY(gd.d_data.alloc(sizeof(double) * nnz));
+    HIP_TRY(d_flags.alloc(1));
+    HIP_TRY(hipEventRecord(g->ev[0], g->stream));
+    HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), g->stream));
+    HIP_TRY(hipMemsetAsync(gd.d_adjbits.p, 0, sizeof(uint64_t) * n * wpr, g->stream));
+    HIP_TRY(hipMemcpyAsync(gd.d_indptr.p, c->d_indptr.p, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToDevice, g->stream));
+    if (nnz) HIP_TRY(hipMemcpyAsync(gd.d_indices.p, c->d_indices.p, sizeof(uint32_t) * nnz, hipMemcpyDeviceToDevice, g->stream));
+    const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, 1u << 20);
+    if (c->d_data64.p)   // an edge-list file's float64 weights as parsed: stored as they are, the flags reduced from them
+        hipLaunchKernelGGL(pw::csr_to_dense_kernel<double>, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p,
+                           (const uint32_t *)c->d_indices.p, (const double *)c->d_data64.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p,
+                           gd.d_deg.p, d_flags.p);
+    else
+        hipLaunchKernelGGL(pw::csr_to_dense_kernel<float>, dim3(grid), dim3(256), 0, g->stream, (const uint32_t *)c->d_indptr.p,
+                           (const uint32_t *)c->d_indices.p, (const float *)c->d_data.p, (uint32_t)n, wpr, gd.d_adjbits.p, (double *)gd.d_data.p,
+                           gd.d_deg.p, d_flags.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->ev[1], g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> indptr;
+    if ((rc = dense_finish_degrees(g, flags, indptr))) return rc;
+    if (gd.nnz != nnz) return fail(PW_ERR_HIP, "pw_dense_create_from_csr: degrees do not add up to the CSR's entries (internal error)");
+    if (gd.unit) gd.d_data.release();   // every weight 1.0: the values are dropped, as pw_dense_create drops them
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+    if (build_ms) *build_ms = ms;
+    *out = owner.release();
     return PW_OK;
 }
 
@@ -2019,9 +1999,10 @@ PW_EXPORT int pw_graph_set_thresholds(pw_graph *g, const float *thr) {
 // 170 ms of index kernels + the host passes per device.  Per-(p, q) tables are built by each replica's first call.
 PW_EXPORT int pw_graph_replicate(const pw_graph *src, int device, pw_graph **out) {
     if (!src || !out) return fail(PW_ERR_INVALID, "null pointer");
-    pw_graph *g = new pw_graph();
+    GraphOwner owner(new pw_graph());   // (the only local that owns anything: the copies land in the handle's own buffers)
+    pw_graph *const g = owner.get();
     int rc = graph_common_init(g, device);
-    if (rc) { pw_graph_destroy(g); return rc; }
+    if (rc) return rc;
     static_cast<GraphDesc &>(*g->gd) = *src->gd;
     g->gd->thr_version = src->gd->d_thr.p ? 1 : 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2039,13 +2020,10 @@ PW_EXPORT int pw_graph_replicate(const pw_graph *src, int device, pw_graph **out
     copy(&GraphData::d_kf);       copy(&GraphData::d_tab_off);   copy(&GraphData::d_slots);     copy(&GraphData::d_vrec);
     copy(&GraphData::d_lines);    copy(&GraphData::d_clist);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    if (e != hipSuccess) {
-        pw_graph_destroy(g);
-        return fail(e == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("pw_graph_replicate: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PW_ERR_NOMEM : PW_ERR_HIP, std::string("pw_graph_replicate: ") + hipGetErrorString(e));
     g->gd->create_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     g->gd->index_build_ms = 0;     // (nothing was built here)
-    *out = g;
+    *out = owner.release();
     return PW_OK;
 }
 
@@ -3740,9 +3718,9 @@ static int simulate_device_impl(pw_graph *g, const LaneSwitches &sw, int mode, d
 // walks are those of one call: the second half is addressed into the stream by the draws of the first (walked again if dead
 // ends made them fewer).
 static pw_graph *make_twin(pw_graph *g) {
-    pw_graph *t = new pw_graph();
-    if (graph_common_init(t, g->device, g->gd)) { pw_graph_destroy(t); return nullptr; }
-    return t;
+    GraphOwner t(new pw_graph());   // (no other local)
+    if (graph_common_init(t.get(), g->device, g->gd)) return nullptr;
+    return t.release();
 }
 
 static void add_stats(pw_stats &total, const pw_stats &st, bool side_by_side) {
@@ -4489,9 +4467,7 @@ PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_
     const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
     if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
     const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -4814,9 +4790,7 @@ PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks,
                             float sample, uint32_t seed, uint32_t workers, float *vectors) {
     if (!walks || !vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
     if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2), vbytes = sizeof(float) * (size_t)n_nodes * dim;
     DevBuf<uint32_t> d_walks;
@@ -4850,7 +4824,7 @@ struct TextFile {
     FILE *file = nullptr;
     PinnedBuf<void> pinned[2];
     bool queued = false;   // work may be in flight on the default stream
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    pw::Event ev[8];       // count begin / end; per chunk slot: fill begin, fill end, copy end
     int n_cu = 1;
     DevBuf<uint64_t> d_row_off, d_tmp;       // uint64[n_rows + 1]: byte counts, then offsets; the scan's tile sums
     DevBuf<uint32_t> d_flags;                // one word the fill kernel raises
@@ -4865,7 +4839,6 @@ struct TextFile {
     ~TextFile() {   // (the buffers go behind this body: nothing of the call is in flight by then)
         if (queued) (void)hipStreamSynchronize(nullptr);
         if (file) (void)fclose(file);
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     }
     int write_failed() const { return fail(PW_ERR_INVALID, who + ": cannot write " + path + ": " + strerror(errno)); }
     int open(const std::string &header) {
@@ -4881,7 +4854,7 @@ struct TextFile {
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         n_cu = prop.multiProcessorCount;
         queued = true;
-        for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+        for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
         return 0;
     }
     template <typename T> int alloc(DevBuf<T> &buf, uint64_t n) {
@@ -5023,9 +4996,7 @@ PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, u
     uint64_t longest_name = 0;
     int rc;
     if ((rc = check_names(who, "row", id_chars, id_offsets, n_rows, &longest_name))) return rc;
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if ((rc = check_device(device))) return rc;
     // the byte budget of a chunk: at least what one row can take (name, dim times " " + 47 characters, newline)
     const uint64_t row_max = longest_name + (uint64_t)dim * pw::F6_SLOT + 1;
     const uint64_t budget = chunk_budget("PECANPY_AMD_EMB_CHUNK_BYTES", row_max);
@@ -5056,9 +5027,7 @@ PW_EXPORT int pw_vectors_write_text(int device, const float *vectors, uint64_t n
                                     const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
     if (!vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
     if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     const size_t vbytes = sizeof(float) * (size_t)n_rows * dim;
     DevBuf<float> d_vectors;
@@ -5084,9 +5053,7 @@ PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, ui
     if (longest_name > pw::WALK_NAME_MAX)
         return fail(PW_ERR_INVALID, "pw_walks_write_text: a name of " + std::to_string(longest_name) + " bytes (at most " +
                                         std::to_string(pw::WALK_NAME_MAX) + ")");
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if ((rc = check_device(device))) return rc;
     // the byte budget of a chunk: at least the longest possible row, walk_length + 1 times the longest name and its separator
     const uint64_t row_max = ((uint64_t)walk_length + 1) * (longest_name + 1);
     const uint64_t budget = chunk_budget("PECANPY_AMD_WALKS_CHUNK_BYTES", row_max);
@@ -5147,9 +5114,7 @@ PW_EXPORT int pw_walks_write_text(int device, const uint32_t *walks, uint64_t n_
                                   const uint64_t *id_offsets, uint64_t n_names, const char *path, pw_walks_write_stats *stats) {
     if (n_walks == 0 || !walks || walk_length >= (1u << 31))   // (nothing to upload, or refused there)
         return pw_walks_write_text_device(device, nullptr, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats);
-    const int n_dev = pw_device_count();
-    if (n_dev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n_dev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2);
     DevBuf<uint32_t> d_walks;
@@ -5176,9 +5141,7 @@ PW_EXPORT int pw_selftest_format_f6(int on_device, int device, const float *x, u
         }
         return PW_OK;
     }
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     DevBuf<float> d_x;
     DevBuf<char> d_chars;
@@ -5221,9 +5184,7 @@ template <typename T> static int selftest_exclusive_scan(T *x, uint64_t n, uint6
 
 PW_EXPORT int pw_selftest_exclusive_scan(int device, int width, void *x, uint64_t n, uint64_t *total) {
     if ((n && !x) || !total || (width != 32 && width != 64)) return fail(PW_ERR_INVALID, "bad argument");
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     return width == 32 ? selftest_exclusive_scan((uint32_t *)x, n, total) : selftest_exclusive_scan((uint64_t *)x, n, total);
 }
@@ -5471,9 +5432,7 @@ PW_EXPORT int pw_selftest_lane_floats(int on_device, int device, const uint8_t *
         }
         return PW_OK;
     }
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     DevBuf<uint8_t> d_cls;
     DevBuf<void> d_cl;
@@ -5601,9 +5560,7 @@ PW_EXPORT int pw_selftest_lane(int on_device, int device, const uint8_t *cls, ui
 #endif
         return PW_OK;
     }
-    int ndev = pw_device_count();
-    if (ndev <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(PW_ERR_INVALID, "device index out of range");
+    if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     DevBuf<uint8_t> d_cls;
     DevBuf<void> d_cl;

@@ -7,7 +7,10 @@ exposes the walk operator that replaces the reference's ``Base._random_walks`` +
 crosses PCIe).  ``simulate_sharded`` is the multi-GPU path: one process per GPU, the shuffled job
 array split into contiguous ranges, graph replicated, one gather of the walk shards at the end.
 """
+import contextlib
 import ctypes as C
+import os
+import time
 
 import numpy as np
 
@@ -123,6 +126,11 @@ def check_dense_matrix(mat, device=None):
     return int(shape[0])
 
 
+def _no_device():
+    """The one place the Python layer says that the library sees no GPU."""
+    raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+
+
 def _edge_list_to_device(lib, edge_index, edge_weight, device):
     """The device tensors ``(src, dst, w, dev, host_bytes)`` of an edge list that passed ``check_edge_index``: a CUDA tensor is
     used where it is, host input is uploaded; torch's stream is synchronised (the library works on its own streams)."""
@@ -136,7 +144,7 @@ def _edge_list_to_device(lib, edge_index, edge_weight, device):
     else:
         dev = torch.device("cuda", int(device or 0))
         if int(lib.pw_device_count()) <= 0:
-            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+            _no_device()
 
     def to_dev(x, dtype):
         nonlocal host_bytes
@@ -165,6 +173,82 @@ def _edgelist_names(lib, ids, n):
     blob = chars[:id_bytes].tobytes().decode("ascii")
     cuts = offs.tolist()
     return [blob[a:b] for a, b in zip(cuts, cuts[1:])]
+
+
+def _csr_dev_shape(lib, c):
+    """``(n_nodes, nnz, insertions, dropped, build_ms)`` of a ``pw_csr_dev``."""
+    shape = [C.c_uint64(0) for _ in range(4)]
+    ms = C.c_double(0)
+    _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
+    return tuple(int(s.value) for s in shape) + (float(ms.value),)
+
+
+@contextlib.contextmanager
+def _coo_csr_dev(lib, src, dst, w, dev, m, num_nodes, directed):
+    """``pw_coo_to_csr_device`` over the tensors of ``_edge_list_to_device``.  Yields ``(c, t_called, shape)``: the ``pw_csr_dev``,
+    destroyed when the block is left, ``time.perf_counter()`` behind the call, and ``_csr_dev_shape``'s tuple."""
+    c = C.c_void_p()
+    _lib.check(lib.pw_coo_to_csr_device(dev.index, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                        C.c_void_p(w.data_ptr() if w is not None else 0), m,
+                                        int(num_nodes or 0), int(bool(directed)), C.byref(c)))
+    try:
+        t_called = time.perf_counter()
+        yield c, t_called, _csr_dev_shape(lib, c)
+    finally:
+        lib.pw_csr_dev_destroy(c)
+
+
+@contextlib.contextmanager
+def _edgelist_csr_dev(lib, path, weighted, directed, delimiter, device, flags):
+    """``pw_edgelist_read_device_ex`` with ``flags``.  Yields ``None`` when the file needs the host reader (the library's two
+    decline codes, a delimiter that cannot be encoded), else ``(c, st, read_call_ms, t_called, shape, names)``: the
+    ``pw_csr_dev``, destroyed with the id handle when the block is left, the reader's statistics, the wall clock of the library
+    call alone (the device check, which may start the runtime, and the delimiter's encoding lie in front of it),
+    ``time.perf_counter()`` behind the call, ``_csr_dev_shape``'s tuple and the vertex names -- read in that order, so the
+    names fall into whatever the caller times from ``t_called`` on."""
+    if int(lib.pw_device_count()) <= 0:
+        _no_device()
+    try:
+        raw_delim = delimiter.encode("utf-8", "surrogateescape")
+    except (AttributeError, UnicodeError):
+        raw_delim = None
+    if raw_delim is None or b"\0" in raw_delim:
+        yield None
+        return
+    t0 = time.perf_counter()
+    c, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwEdgelistDevStats()
+    rc = lib.pw_edgelist_read_device_ex(os.fsencode(path), int(bool(weighted)), int(bool(directed)), raw_delim, int(device or 0),
+                                        flags, C.byref(c), C.byref(ids), C.byref(st))
+    if rc in (_lib.EDGELIST_NEEDS_HOST_READER, _lib.EDGELIST_IO):
+        yield None
+        return
+    _lib.check(rc)
+    try:
+        t_called = time.perf_counter()
+        shape = _csr_dev_shape(lib, c)
+        yield c, st, (t_called - t0) * 1e3, t_called, shape, _edgelist_names(lib, ids, shape[0])
+    finally:
+        lib.pw_csr_dev_destroy(c)
+        lib.pw_edgelist_ids_destroy(ids)
+
+
+def _csr_engine(cls, lib, c, n, nnz, device):
+    """A ``pw_csr_dev`` as a CSR engine that carries ``eng.csr``: the three arrays are exported once and
+    ``pw_csr_create_device`` reads them (no second download).  Returns ``(eng, t_exported, t_created)``:
+    ``time.perf_counter()`` behind the export and behind the handle."""
+    indptr = np.empty(n + 1, dtype=np.uint32)
+    indices = np.empty(nnz, dtype=np.uint32)
+    data = np.empty(nnz, dtype=np.float32)
+    _lib.check(lib.pw_csr_dev_export(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data)))
+    t_exported = time.perf_counter()
+    h = C.c_void_p()
+    _lib.check(lib.pw_csr_create_device(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), C.byref(h)))
+    t_created = time.perf_counter()
+    eng = cls(h, lib, "csr", n, device)
+    eng._max_degree = int(np.diff(indptr.astype(np.int64)).max()) if n else 0
+    eng._nnz = nnz
+    eng.csr = (indptr, indices, data)
+    return eng, t_exported, t_created
 
 
 class WalkEngine:
@@ -239,38 +323,14 @@ class WalkEngine:
         unweighted) and ``eng.build_stats``: ``edge_list_host_bytes`` (bytes of the edge list that crossed the host:
         0 for CUDA input), ``n_nodes``, ``nnz``, ``insertions``, ``dropped``, ``build_ms`` (device time of the CSR build)
         and the wall clock of the stages (``coo_call_ms``, ``export_ms``, ``handle_ms``)."""
-        import time
-
         m = check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
         lib = _lib.load()
         src, dst, w, dev, host_bytes = _edge_list_to_device(lib, edge_index, edge_weight, device)
         t0 = time.perf_counter()
-        c = C.c_void_p()
-        _lib.check(lib.pw_coo_to_csr_device(dev.index, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                            C.c_void_p(w.data_ptr() if w is not None else 0), m,
-                                            int(num_nodes or 0), int(bool(directed)), C.byref(c)))
-        try:
-            t1 = time.perf_counter()
-            shape = [C.c_uint64(0) for _ in range(4)]
-            ms = C.c_double(0)
-            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
-            n, nnz, insertions, dropped = (int(s.value) for s in shape)
-            indptr = np.empty(n + 1, dtype=np.uint32)
-            indices = np.empty(nnz, dtype=np.uint32)
-            data = np.empty(nnz, dtype=np.float32)
-            _lib.check(lib.pw_csr_dev_export(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data)))
-            t2 = time.perf_counter()
-            h = C.c_void_p()
-            _lib.check(lib.pw_csr_create_device(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), C.byref(h)))   # (no second download)
-            t3 = time.perf_counter()
-        finally:
-            lib.pw_csr_dev_destroy(c)
-        eng = cls(h, lib, "csr", n, dev.index)
-        eng._max_degree = int(np.diff(indptr.astype(np.int64)).max()) if n else 0
-        eng._nnz = nnz
-        eng.csr = (indptr, indices, data)
+        with _coo_csr_dev(lib, src, dst, w, dev, m, num_nodes, directed) as (c, t1, (n, nnz, insertions, dropped, build_ms)):
+            eng, t2, t3 = _csr_engine(cls, lib, c, n, nnz, dev.index)
         eng.build_stats = {"edge_list_host_bytes": int(host_bytes), "n_nodes": n, "nnz": nnz, "insertions": insertions,
-                           "dropped": dropped, "build_ms": float(ms.value), "coo_call_ms": (t1 - t0) * 1e3,
+                           "dropped": dropped, "build_ms": build_ms, "coo_call_ms": (t1 - t0) * 1e3,
                            "export_ms": (t2 - t1) * 1e3, "handle_ms": (t3 - t2) * 1e3}
         return eng
 
@@ -287,50 +347,15 @@ class WalkEngine:
         ``eng.build_stats``: the library's ``upload_ms``, ``scan_ms``, ``ids_ms``, ``build_ms`` (wall clock of the
         stages), ``lines``, ``n_nodes``, ``file_bytes``, and ``nnz``, ``insertions``, ``csr_kernels_ms`` (device time of
         the CSR build's kernels), ``read_call_ms``, ``export_ms``, ``handle_ms``."""
-        import os
-        import time
-
         lib = _lib.load()
-        if int(lib.pw_device_count()) <= 0:
-            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
-        try:
-            raw_delim = delimiter.encode("utf-8", "surrogateescape")
-        except (AttributeError, UnicodeError):
-            return None
-        if b"\0" in raw_delim:
-            return None
-        t0 = time.perf_counter()
-        c, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwEdgelistDevStats()
-        rc = lib.pw_edgelist_read_device(os.fsencode(path), int(bool(weighted)), int(bool(directed)), raw_delim, int(device or 0),
-                                         C.byref(c), C.byref(ids), C.byref(st))
-        if rc in (_lib.EDGELIST_NEEDS_HOST_READER, _lib.EDGELIST_IO):
-            return None
-        _lib.check(rc)
-        try:
-            t1 = time.perf_counter()
-            shape = [C.c_uint64(0) for _ in range(4)]
-            ms = C.c_double(0)
-            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
-            n, nnz, insertions, _ = (int(s.value) for s in shape)
-            indptr = np.empty(n + 1, dtype=np.uint32)
-            indices = np.empty(nnz, dtype=np.uint32)
-            data = np.empty(nnz, dtype=np.float32)
-            _lib.check(lib.pw_csr_dev_export(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data)))
-            names = _edgelist_names(lib, ids, n)
-            t2 = time.perf_counter()
-            h = C.c_void_p()
-            _lib.check(lib.pw_csr_create_device(c, _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), C.byref(h)))   # (no second download)
-            t3 = time.perf_counter()
-        finally:
-            lib.pw_csr_dev_destroy(c)
-            lib.pw_edgelist_ids_destroy(ids)
-        eng = cls(h, lib, "csr", n, int(device or 0))
-        eng._max_degree = int(np.diff(indptr.astype(np.int64)).max()) if n else 0
-        eng._nnz = nnz
-        eng.csr = (indptr, indices, data)
+        with _edgelist_csr_dev(lib, path, weighted, directed, delimiter, device, 0) as r:
+            if r is None:
+                return None
+            c, st, read_call_ms, t1, (n, nnz, insertions, _, csr_kernels_ms), names = r
+            eng, t2, t3 = _csr_engine(cls, lib, c, n, nnz, int(device or 0))
         eng.ids = names
-        eng.build_stats = {**st.as_dict(), "nnz": nnz, "insertions": insertions, "csr_kernels_ms": float(ms.value),
-                           "read_call_ms": (t1 - t0) * 1e3, "export_ms": (t2 - t1) * 1e3, "handle_ms": (t3 - t2) * 1e3}
+        eng.build_stats = {**st.as_dict(), "nnz": nnz, "insertions": insertions, "csr_kernels_ms": csr_kernels_ms,
+                           "read_call_ms": read_call_ms, "export_ms": (t2 - t1) * 1e3, "handle_ms": (t3 - t2) * 1e3}
         return eng
 
     @classmethod
@@ -346,8 +371,6 @@ class WalkEngine:
         ``eng.build_stats``: ``matrix_host_bytes`` (bytes of the matrix that crossed from the host: 0 for CUDA input),
         ``n_nodes``, ``nnz``, ``unit``, ``build_ms`` (device time of the build's kernels) and the wall clock of the stages
         (``upload_ms``: conversion / upload / making contiguous; ``create_call_ms``: the library call)."""
-        import time
-
         n = check_dense_matrix(mat, device)   # ValueError before the library or a device is touched
         import torch
 
@@ -358,7 +381,7 @@ class WalkEngine:
             t = mat
         else:
             if int(lib.pw_device_count()) <= 0:
-                raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+                _no_device()
             if isinstance(mat, np.ndarray):
                 if mat.dtype not in (np.float32, np.float64):
                     mat = mat.astype(np.float64)
@@ -392,31 +415,18 @@ class WalkEngine:
         (1.0 everywhere when ``edge_weight`` is ``None``).  ``eng.build_stats`` has the keys of ``from_edge_index``
         (``export_ms`` is 0: nothing is exported; ``handle_ms``: the dense handle) and ``dense_build_ms``, the device time
         of the dense build's kernels."""
-        import time
-
         m = check_edge_index(edge_index, edge_weight, num_nodes)   # ValueError before the library or a device is touched
         lib = _lib.load()
         src, dst, w, dev, host_bytes = _edge_list_to_device(lib, edge_index, edge_weight, device)
         t0 = time.perf_counter()
-        c = C.c_void_p()
-        _lib.check(lib.pw_coo_to_csr_device(dev.index, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                            C.c_void_p(w.data_ptr() if w is not None else 0), m,
-                                            int(num_nodes or 0), int(bool(directed)), C.byref(c)))
-        try:
-            t1 = time.perf_counter()
-            shape = [C.c_uint64(0) for _ in range(4)]
-            ms, dense_ms = C.c_double(0), C.c_double(0)
-            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
-            n, nnz, insertions, dropped = (int(s.value) for s in shape)
-            h = C.c_void_p()
+        with _coo_csr_dev(lib, src, dst, w, dev, m, num_nodes, directed) as (c, t1, (n, nnz, insertions, dropped, build_ms)):
+            h, dense_ms = C.c_void_p(), C.c_double(0)
             _lib.check(lib.pw_dense_create_from_csr(c, C.byref(h), C.byref(dense_ms)))
             t2 = time.perf_counter()
-        finally:
-            lib.pw_csr_dev_destroy(c)
         eng = cls(h, lib, "dense", n, dev.index)
         eng._max_degree, eng._nnz = eng._dense_shape()["max_degree"], nnz
         eng.build_stats = {"edge_list_host_bytes": int(host_bytes), "n_nodes": n, "nnz": nnz, "insertions": insertions,
-                           "dropped": dropped, "build_ms": float(ms.value), "coo_call_ms": (t1 - t0) * 1e3, "export_ms": 0.0,
+                           "dropped": dropped, "build_ms": build_ms, "coo_call_ms": (t1 - t0) * 1e3, "export_ms": 0.0,
                            "handle_ms": (t2 - t1) * 1e3, "dense_build_ms": float(dense_ms.value)}
         return eng
 
@@ -432,43 +442,19 @@ class WalkEngine:
         ``build_ms``, ``lines``, ``n_nodes``, ``file_bytes``, and ``nnz``, ``insertions``, ``csr_kernels_ms``,
         ``dense_build_ms`` (device time of the dense build's kernels), ``read_call_ms``, ``handle_ms`` (names and the dense
         handle), ``unit`` and ``matrix_host_bytes`` (0)."""
-        import os
-        import time
-
         lib = _lib.load()
-        if int(lib.pw_device_count()) <= 0:
-            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
-        try:
-            raw_delim = delimiter.encode("utf-8", "surrogateescape")
-        except (AttributeError, UnicodeError):
-            return None
-        if b"\0" in raw_delim:
-            return None
-        t0 = time.perf_counter()
-        c, ids, st = C.c_void_p(), C.c_void_p(), _lib.PwEdgelistDevStats()
-        rc = lib.pw_edgelist_read_device_ex(os.fsencode(path), int(bool(weighted)), int(bool(directed)), raw_delim, int(device or 0),
-                                            _lib.EDGELIST_KEEP_F64, C.byref(c), C.byref(ids), C.byref(st))
-        if rc in (_lib.EDGELIST_NEEDS_HOST_READER, _lib.EDGELIST_IO):
-            return None
-        _lib.check(rc)
-        try:
-            t1 = time.perf_counter()
-            shape = [C.c_uint64(0) for _ in range(4)]
-            ms, dense_ms = C.c_double(0), C.c_double(0)
-            _lib.check(lib.pw_csr_dev_shape(c, *[C.byref(s) for s in shape], C.byref(ms)))
-            n, nnz, insertions, _ = (int(s.value) for s in shape)
-            names = _edgelist_names(lib, ids, n)
-            h = C.c_void_p()
+        with _edgelist_csr_dev(lib, path, weighted, directed, delimiter, device, _lib.EDGELIST_KEEP_F64) as r:
+            if r is None:
+                return None
+            c, st, read_call_ms, t1, (n, nnz, insertions, _, csr_kernels_ms), names = r
+            h, dense_ms = C.c_void_p(), C.c_double(0)
             _lib.check(lib.pw_dense_create_from_csr(c, C.byref(h), C.byref(dense_ms)))
             t2 = time.perf_counter()
-        finally:
-            lib.pw_csr_dev_destroy(c)
-            lib.pw_edgelist_ids_destroy(ids)
         eng = cls(h, lib, "dense", n, int(device or 0))
         eng._max_degree, eng._nnz = eng._dense_shape()["max_degree"], nnz
         eng.ids = names
-        eng.build_stats = {**st.as_dict(), "nnz": nnz, "insertions": insertions, "csr_kernels_ms": float(ms.value),
-                           "dense_build_ms": float(dense_ms.value), "read_call_ms": (t1 - t0) * 1e3, "handle_ms": (t2 - t1) * 1e3,
+        eng.build_stats = {**st.as_dict(), "nnz": nnz, "insertions": insertions, "csr_kernels_ms": csr_kernels_ms,
+                           "dense_build_ms": float(dense_ms.value), "read_call_ms": read_call_ms, "handle_ms": (t2 - t1) * 1e3,
                            "unit": eng._dense_flags()[0], "matrix_host_bytes": 0}
         return eng
 
@@ -683,7 +669,7 @@ class MultiWalkEngine:
         lib = _lib.load()
         devices = visible_devices(devices)
         if not devices:
-            raise PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+            _no_device()
         indptr = np.ascontiguousarray(indptr, dtype=np.uint32)
         indices = np.ascontiguousarray(indices, dtype=np.uint32)
         if data is not None:
