@@ -545,6 +545,58 @@ int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, double *out)
  * handle's GPU), copied to the host -- lets the tests compare the device stream with pw_mt_random_sample / NumPy at
  * the offsets the last shards of a multi-GPU run start from. */
 int pw_stream_sample_device(pw_graph *g, uint32_t seed, uint64_t offset, uint64_t n, double *out);
+/* The tempered 32-bit words #offset.. of the same stream (random_sample takes them two at a time:
+ * ((w[2i] >> 5) * 2^26 + (w[2i+1] >> 6)) / 2^53; RandomState(seed).randint(0, 2**32, size=n, dtype=np.uint64) hands them
+ * out one by one), with jump-ahead: what the seeded alias / first-order modes draw from.  Host side, no GPU needed. */
+int pw_mt_words(uint32_t seed, uint64_t offset, uint64_t n, uint32_t *out);
+/* Test hook: the same words as the DEVICE expands them (jump-ahead tree + mt_words_kernel on the handle's GPU). */
+int pw_stream_words_device(pw_graph *g, uint32_t seed, uint64_t offset, uint64_t n, uint32_t *out);
+
+/* ---- seeded alias / first-order modes: the word offsets of the jobs, by speculation rounds (host form) -------------------- */
+/* With a seed PW_MODE_PRECOMP, _FIRST_ORDER_UNWEIGHTED and _PRECOMP_FIRST_ORDER reproduce the reference's ONE stream, which
+ * hands every step a variable number of words: the word offset at which a job starts depends on every earlier draw, and that
+ * one integer per job is all that is sequential.  csrc/seq_spec.h finds the offsets of many jobs per round: it walks
+ * candidate (job, offset) pairs in windows around the expected offsets, resolves the chain that starts at the round's exact
+ * base by pointer doubling and commits the jobs on it -- exact by construction, whatever the fields below say.  The rounds
+ * have a host form only (pw_selftest_seq_offsets, pw_selftest_seq_walks); on the device seeded calls of these modes walk on
+ * one lane (walk_seq_kernel). */
+typedef struct pw_seq_config {  /* 0 in a field = the default */
+    uint32_t jobs_per_round;     /* windows planned per round (default 512, at most 4096) */
+    uint32_t max_candidates;     /* cap on the candidates of a round (default 2^19); the round plans the jobs that fit */
+    uint32_t word_buffer_blocks; /* size of the word buffer in blocks of 624 words (default 65536); raised to the smallest
+                                    legal size, which holds one job of 3 * walk_length + 4096 words */
+    uint64_t min_jobs;           /* calls with fewer jobs take the plain sequential loop; UINT64_MAX: always */
+    float window_sigmas;         /* half width of a window in deviations of the words per job (default 3); negative: the
+                                    centre candidate alone, nearly every window misses (tests) */
+    float force_mean;            /* > 0: words per job the windows are centred with, in place of the running mean (tests) */
+    float force_sigma;           /* > 0: in place of the running deviation */
+} pw_seq_config;
+typedef struct pw_seq_info {
+    uint32_t path;               /* 0 sequential loop, 1 speculative, 2 speculative then fell back (a job that did not finish
+                                    inside a full word buffer starting at its own block) */
+    uint64_t rounds;             /* rounds that committed jobs */
+    uint64_t candidate_walks, committed_jobs;
+    uint64_t window_misses;      /* rounds whose chain ended at an offset outside the next window */
+    uint64_t unfinished_retries; /* rounds repeated behind a larger expansion: their first job had run out of words */
+    uint64_t words_consumed;     /* by the whole call: where job n_jobs would start */
+    uint64_t words_expanded;
+    double plan_ms;              /* host clock of the planning */
+    double candidate_ms, resolve_ms, commit_ms, expand_ms;   /* device time of the phases: 0 in the host form */
+} pw_seq_info;
+/* Test hook (host, no GPU): the plan, candidate, resolve and commit logic of the rounds for FirstOrderUnweighted on a host
+ * CSR, the same headers built for the host with the words of pw_mt_words.  offsets[i] = the word job i starts at,
+ * offsets[n_jobs] = the words consumed.  cfg->min_jobs = UINT64_MAX: a plain sequential loop instead. */
+int pw_selftest_seq_offsets(const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes, const uint32_t *starts,
+                            uint64_t n_jobs, uint32_t walk_length, uint32_t seed, const pw_seq_config *cfg, uint64_t *offsets,
+                            pw_seq_info *info);
+/* Test hook (host, no GPU): the same rounds for any of the three modes on a host CSR (data NULL: all 1.0) and, for PW_MODE_PRECOMP
+ * and PW_MODE_PRECOMP_FIRST_ORDER, caller-built alias tables in pw_precomp_export's layout (first order: alias_indptr = indptr
+ * widened).  out (optional): uint32[n_jobs][walk_length + 2], the walk matrix of pw_simulate; counts (optional): total_steps,
+ * overflow_reads, clamped_reads, dead_end_walks of pw_stats.  cfg->min_jobs = UINT64_MAX: the plain sequential loop. */
+int pw_selftest_seq_walks(int mode, const uint32_t *indptr, const uint32_t *indices, const float *data, uint32_t n_nodes,
+                          const uint64_t *alias_indptr, const uint32_t *alias_j, const float *alias_q, uint64_t n_alias,
+                          const uint32_t *starts, uint64_t n_jobs, uint32_t walk_length, uint32_t seed, const pw_seq_config *cfg,
+                          uint64_t *offsets, uint32_t *out, uint64_t *counts, pw_seq_info *info);
 
 /* ---- node2vec+ noisy-edge thresholds (host side; usable without a GPU) --------------------- */
 /* thr[i] = max(mean(row i) + gamma * std(row i), 0) exactly as the reference's NumPy expression evaluates it

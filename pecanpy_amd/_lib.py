@@ -153,6 +153,43 @@ class PwCorpusDevStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwSeqConfig(C.Structure):
+    """``pw_seq_config`` of include/pecanpy_amd.h (0 in a field = the default)."""
+    _fields_ = [
+        ("jobs_per_round", C.c_uint32),
+        ("max_candidates", C.c_uint32),
+        ("word_buffer_blocks", C.c_uint32),
+        ("min_jobs", C.c_uint64),
+        ("window_sigmas", C.c_float),
+        ("force_mean", C.c_float),
+        ("force_sigma", C.c_float),
+    ]
+
+
+class PwSeqInfo(C.Structure):
+    """``pw_seq_info`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("path", C.c_uint32),
+        ("rounds", C.c_uint64),
+        ("candidate_walks", C.c_uint64),
+        ("committed_jobs", C.c_uint64),
+        ("window_misses", C.c_uint64),
+        ("unfinished_retries", C.c_uint64),
+        ("words_consumed", C.c_uint64),
+        ("words_expanded", C.c_uint64),
+        ("plan_ms", C.c_double),
+        ("candidate_ms", C.c_double),
+        ("resolve_ms", C.c_double),
+        ("commit_ms", C.c_double),
+        ("expand_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+SEQ_ALWAYS_SEQUENTIAL = 2**64 - 1   # pw_seq_config.min_jobs: the plain sequential loop
+
 EDGELIST_OK, EDGELIST_NEEDS_HOST_READER, EDGELIST_IO = 0, 1, 2   # pw_edgelist_read_device's non-negative results (pw_corpus_read_device's too)
 EDGELIST_KEEP_F64 = 1   # pw_edgelist_read_device_ex's flag bit: the CSR keeps the float64 weights for the dense build
 ERR_UNSUPPORTED = -4    # PW_ERR_UNSUPPORTED
@@ -245,6 +282,13 @@ SYMBOLS = {
     "pw_selftest_exclusive_scan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_stream_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "pw_mt_words": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "pw_stream_words_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "pw_selftest_seq_offsets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                          C.POINTER(PwSeqConfig), C.c_void_p, C.POINTER(PwSeqInfo)]),
+    "pw_selftest_seq_walks": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(PwSeqConfig), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(PwSeqInfo)]),
     "pw_noise_thresholds_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_noise_thresholds_csr_numpy1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]),
     "pw_selftest_thresholds_row": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p]),

@@ -30,6 +30,26 @@ __device__ __forceinline__ uint32_t mt_temper_dev(uint32_t y) {
     return y;
 }
 
+// one block forward in LDS, all 256 threads of the workgroup: mt[0..624) -> the next 624 raw words, in place
+__device__ __forceinline__ void mt_twist_lds(uint32_t *mt, int t) {
+    // phase 1: i in [0, 227): needs old[i], old[i+1], old[i+397]
+    uint32_t v0 = 0, v1 = 0, v2 = 0;
+    if (t < 227) v0 = mt_mix_dev(mt[t], mt[t + 1], mt[t + 397]);
+    __syncthreads();
+    if (t < 227) mt[t] = v0;
+    __syncthreads();
+    // phase 2: i in [227, 454): needs old[i], old[i+1], new[i-227]
+    if (t < 227) v1 = mt_mix_dev(mt[t + 227], mt[t + 228], mt[t]);
+    __syncthreads();
+    if (t < 227) mt[t + 227] = v1;
+    __syncthreads();
+    // phase 3: i in [454, 624): needs old[i], old[i+1] (new[0] for i = 623), new[i-227]
+    if (t < 170) v2 = mt_mix_dev(mt[t + 454], (t + 455 < 624) ? mt[t + 455] : mt[0], mt[t + 227]);
+    __syncthreads();
+    if (t < 170) mt[t + 454] = v2;
+    __syncthreads();
+}
+
 __global__ void __launch_bounds__(256)
 mt_expand_kernel(const uint32_t *__restrict__ states_in, uint32_t *__restrict__ states_out,
                  double *__restrict__ out, uint64_t n_blocks, uint64_t total_blocks) {
@@ -42,22 +62,7 @@ mt_expand_kernel(const uint32_t *__restrict__ states_in, uint32_t *__restrict__ 
     uint64_t nb = first >= total_blocks ? 0 : (total_blocks - first < n_blocks ? total_blocks - first : n_blocks);
     double *dst = out + first * 312;
     for (uint64_t b = 0; b < nb; b++) {
-        // phase 1: i in [0, 227): needs old[i], old[i+1], old[i+397]
-        uint32_t v0 = 0, v1 = 0, v2 = 0;
-        if (t < 227) v0 = mt_mix_dev(mt[t], mt[t + 1], mt[t + 397]);
-        __syncthreads();
-        if (t < 227) mt[t] = v0;
-        __syncthreads();
-        // phase 2: i in [227, 454): needs old[i], old[i+1], new[i-227]
-        if (t < 227) v1 = mt_mix_dev(mt[t + 227], mt[t + 228], mt[t]);
-        __syncthreads();
-        if (t < 227) mt[t + 227] = v1;
-        __syncthreads();
-        // phase 3: i in [454, 624): needs old[i], old[i+1] (new[0] for i = 623), new[i-227]
-        if (t < 170) v2 = mt_mix_dev(mt[t + 454], (t + 455 < 624) ? mt[t + 455] : mt[0], mt[t + 227]);
-        __syncthreads();
-        if (t < 170) mt[t + 454] = v2;
-        __syncthreads();
+        mt_twist_lds(mt, t);
         for (int i = t; i < 312; i += 256) {
             uint32_t a = mt_temper_dev(mt[2 * i]) >> 5;
             uint32_t c = mt_temper_dev(mt[2 * i + 1]) >> 6;
@@ -68,6 +73,25 @@ mt_expand_kernel(const uint32_t *__restrict__ states_in, uint32_t *__restrict__ 
     __syncthreads();
     if (states_out)
         for (int i = t; i < 624; i += 256) states_out[gen * 624 + i] = mt[i];
+}
+
+// The same expansion as raw stream words: generator `gen` writes the 624 tempered 32-bit words of each of its blocks,
+// out[(gen * n_blocks + b) * 624 + i] (the seeded alias / first-order modes consume words, one or more per draw:
+// np.random.randint's masked rejection, numba:cpython/randomimpl.py:320-387).
+__global__ void __launch_bounds__(256)
+mt_words_kernel(const uint32_t *__restrict__ states_in, uint32_t *__restrict__ out, uint64_t n_blocks, uint64_t total_blocks) {
+    __shared__ uint32_t mt[624];
+    const int t = threadIdx.x;
+    const uint64_t gen = blockIdx.x;
+    for (int i = t; i < 624; i += 256) mt[i] = states_in[gen * 624 + i];
+    __syncthreads();
+    const uint64_t first = gen * n_blocks;
+    const uint64_t nb = first >= total_blocks ? 0 : (total_blocks - first < n_blocks ? total_blocks - first : n_blocks);
+    uint32_t *dst = out + first * 624;
+    for (uint64_t b = 0; b < nb; b++) {
+        mt_twist_lds(mt, t);
+        for (int i = t; i < 624; i += 256) dst[b * 624 + i] = mt_temper_dev(mt[i]);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -270,4 +270,18 @@ inline void mt_random_sample_host(uint32_t seed, uint64_t offset, uint64_t n, do
     }
 }
 
+// the tempered 32-bit words #offset.. of the seeded stream (RandomState(seed).randint(0, 2**32, dtype=np.uint64) hands out
+// the same words one by one; random_sample takes them two at a time): pw_mt_words, and the word buffer of the host form
+// of the seeded alias / first-order modes
+inline void mt_words_host(uint32_t seed, uint64_t offset, uint64_t n, uint32_t *out) {
+    int pos = (int)(offset % MT_N);
+    uint32_t st[MT_N];
+    MtJump::instance().state_at_block(seed, offset / MT_N, st);
+    mt_twist_block(st);
+    for (uint64_t i = 0; i < n; i++) {
+        if (pos == MT_N) { mt_twist_block(st); pos = 0; }
+        out[i] = mt_temper(st[pos++]);
+    }
+}
+
 }  // namespace pw

@@ -35,6 +35,7 @@
 #include "walk_dense_w.hip.h"
 #include "walk_sparse_pp.hip.h"
 #include "walk_seq.hip.h"
+#include "seq_spec_host.hpp"
 #include "walk_sparse.hip.h"
 #include "walk_lanes.hip.h"
 #include "sgns.hip.h"
@@ -283,6 +284,7 @@ struct pw_graph {
     bool jump_table_ready = false;
     DevBuf<unsigned long long> counters;  // N_COUNTERS device counters: counters.h names the slots
     DevBuf<float> probs_scratch;
+    DevBuf<uint32_t> stream_words;   // pw_stream_words_device: raw stream words (624 per block)
     // Streams and events LAST: members go in reverse order behind the destructor's body, so the events are destroyed first, then
     // the streams, then the buffers above -- on this context's device (graph_common_init creates them; one that fails half way
     // leaves what it made to this destructor)
@@ -3216,19 +3218,23 @@ static int launch_walks(pw_graph *g, pw::WalkArgs &wa, const LaneSwitches &sw, b
 // consecutive blocks of 312 doubles; generator states come from the seed state by polynomial jump-ahead on the device
 // (binary tree of x^(624*2^m) jumps).  `cacheable`: the generator states may be taken from / kept in the handle's
 // cache (a repeated call with the same seed and shape skips the jump launches).  Events ev[0] / ev[1] bracket the
-// kernels on g->stream.
-static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t stream_skip, uint64_t total, uint64_t *rng_base) {
+// kernels on g->stream.  `words_out` (room for 624 words per block): the same blocks as raw 32-bit words into that buffer
+// instead (mt_words_kernel: what the seeded alias / first-order modes consume); g->rng and what it holds are left alone.
+static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t stream_skip, uint64_t total, uint64_t *rng_base,
+                         uint32_t *words_out = nullptr) {
     const uint64_t first_block = stream_skip / 312;
     const uint64_t n_blocks = stream_blocks_from(first_block, stream_skip, total);   // (pw_graph::set_hold: the same rounding)
-    if (g->rng_hold.valid && g->rng_hold.seed == seed && first_block >= g->rng_hold.first_block &&
+    if (!words_out && g->rng_hold.valid && g->rng_hold.seed == seed && first_block >= g->rng_hold.first_block &&
         first_block + n_blocks <= g->rng_hold.first_block + g->rng_hold.n_blocks) {
         HIP_TRY(hipEventRecord(g->ev[0], g->stream));   // (nothing to do: the callers still read the pair of events)
         HIP_TRY(hipEventRecord(g->ev[1], g->stream));
         *rng_base = g->rng_hold.first_block * 312;
         return 0;
     }
-    g->drop_hold();                 // (g->rng is about to be overwritten: whatever was held is gone)
-    if (grow(g->rng, n_blocks * 312)) return PW_ERR_NOMEM;
+    if (!words_out) {
+        g->drop_hold();             // (g->rng is about to be overwritten: whatever was held is gone)
+        if (grow(g->rng, n_blocks * 312)) return PW_ERR_NOMEM;
+    }
     uint64_t per_gen = 1;
     int per_gen_log = 0;
     // generators: each level of the jump tree is a launch or two, each generator expands its blocks one after the other --
@@ -3305,8 +3311,11 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
     //  256 lanes per generator: 8.4 / 6.9 / 6.06 ms of jump + expansion per RMAT-22 pass against 6.08-6.16: the expansion is bound
     //  neither by its barriers nor by its stores (3 TB/s; a plain fill of the 12.9 GB: 4.8 TB/s) but by the per-generator chain of LDS
     //  round trips at eight workgroups per CU)
-    hipLaunchKernelGGL(pw::mt_expand_kernel, dim3(n_gen), dim3(256), 0, g->stream, mt_states,
-                       (uint32_t *)nullptr, g->rng.p, per_gen, n_blocks);
+    if (words_out)
+        hipLaunchKernelGGL(pw::mt_words_kernel, dim3(n_gen), dim3(256), 0, g->stream, mt_states, words_out, per_gen, n_blocks);
+    else
+        hipLaunchKernelGGL(pw::mt_expand_kernel, dim3(n_gen), dim3(256), 0, g->stream, mt_states,
+                           (uint32_t *)nullptr, g->rng.p, per_gen, n_blocks);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(g->ev[1], g->stream));
     *rng_base = first_block * 312;
@@ -3345,6 +3354,21 @@ PW_EXPORT int pw_stream_sample_device(pw_graph *g, uint32_t seed, uint64_t offse
     int rc = expand_stream(g, seed, false, offset, n, &base);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, g->rng.p + (offset - base), sizeof(double) * n, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return PW_OK;
+}
+
+// Test hook: the raw words #offset .. #offset + n of the stream as the device's jump-ahead tree and mt_words_kernel expand them.
+PW_EXPORT int pw_stream_words_device(pw_graph *g, uint32_t seed, uint64_t offset, uint64_t n, uint32_t *out) {
+    if (!g || (n && !out)) return fail(PW_ERR_INVALID, "null pointer");
+    if (set_device(g)) return PW_ERR_HIP;
+    if (!n) return PW_OK;
+    const uint64_t first = offset / pw::SEQ_BLOCK, n_blocks = (offset + n + pw::SEQ_BLOCK - 1) / pw::SEQ_BLOCK - first;
+    if (grow(g->stream_words, (size_t)n_blocks * pw::SEQ_BLOCK)) return PW_ERR_NOMEM;
+    uint64_t base = 0;
+    int rc = expand_stream(g, seed, false, first * 312, n_blocks * 312, &base, g->stream_words.p);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, g->stream_words.p + (offset - first * pw::SEQ_BLOCK), sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PW_OK;
 }
@@ -4201,6 +4225,41 @@ PW_EXPORT int pw_simulate_multi(pw_graph *const *handles, int n_handles, int mod
         for (int i = 1; i < n_sh; i++) add_stats(total, sh[i].st, true);   // (the shards run side by side)
         *stats = total;
     }
+    return PW_OK;
+}
+
+PW_EXPORT int pw_mt_words(uint32_t seed, uint64_t offset, uint64_t n, uint32_t *out) {
+    if (n && !out) return fail(PW_ERR_INVALID, "null pointer");
+    pw::mt_words_host(seed, offset, n, out);
+    return PW_OK;
+}
+
+PW_EXPORT int pw_selftest_seq_offsets(const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes, const uint32_t *starts,
+                                      uint64_t n_jobs, uint32_t walk_length, uint32_t seed, const pw_seq_config *cfg, uint64_t *offsets,
+                                      pw_seq_info *info) {
+    if (!indptr || !offsets || !info || (n_jobs && !starts) || (indptr[n_nodes] && !indices)) return fail(PW_ERR_INVALID, "null pointer");
+    for (uint64_t i = 0; i < n_jobs; i++)
+        if (starts[i] >= n_nodes) return fail(PW_ERR_INVALID, "start vertex out of range");
+    if (pw::seq_host_offsets(indptr, indices, n_nodes, starts, n_jobs, walk_length, seed, cfg, offsets, info))
+        return fail(PW_ERR_INVALID, "pw_selftest_seq_offsets: a job did not finish inside a fresh word buffer");
+    return PW_OK;
+}
+
+PW_EXPORT int pw_selftest_seq_walks(int mode, const uint32_t *indptr, const uint32_t *indices, const float *data, uint32_t n_nodes,
+                                    const uint64_t *alias_indptr, const uint32_t *alias_j, const float *alias_q, uint64_t n_alias,
+                                    const uint32_t *starts, uint64_t n_jobs, uint32_t walk_length, uint32_t seed, const pw_seq_config *cfg,
+                                    uint64_t *offsets, uint32_t *out, uint64_t *counts, pw_seq_info *info) {
+    if (!indptr || !offsets || !info || (n_jobs && !starts) || (indptr[n_nodes] && !indices)) return fail(PW_ERR_INVALID, "null pointer");
+    if (!mode_sequential_stream(mode)) return fail(PW_ERR_INVALID, "pw_selftest_seq_walks: an alias / first-order mode");
+    if (mode != PW_MODE_FIRST_ORDER_UNWEIGHTED && indptr[n_nodes] && (!alias_indptr || !alias_j || !alias_q))
+        return fail(PW_ERR_INVALID, "pw_selftest_seq_walks: this mode needs its alias tables");
+    for (uint64_t i = 0; i < n_jobs; i++)
+        if (starts[i] >= n_nodes) return fail(PW_ERR_INVALID, "start vertex out of range");
+    const pw::SeqGraph g{indptr, indices, data, indptr[n_nodes], alias_indptr, alias_j, alias_q, n_alias, mode, walk_length};
+    pw::SeqCounts cn = {0, 0, 0, 0};
+    if (pw::seq_host_walks(g, starts, n_jobs, seed, cfg, offsets, out, &cn, info))
+        return fail(PW_ERR_INVALID, "pw_selftest_seq_walks: a job did not finish inside a fresh word buffer");
+    if (counts) { counts[0] = cn.steps; counts[1] = cn.over; counts[2] = cn.clamp; counts[3] = cn.dead; }
     return PW_OK;
 }
 

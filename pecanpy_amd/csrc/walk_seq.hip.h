@@ -2,11 +2,12 @@
 //
 // These reference modes draw a *variable* number of MT19937 words per step (masked rejection in
 // np.random.randint, numba:cpython/randomimpl.py:320-387; call sites src/pecanpy/pecanpy.py:307,
-// 673-674), so the stream position of walk i depends on every earlier draw: a seeded run that must
-// reproduce the reference bit for bit is inherently sequential.
-// The exact path below therefore walks all jobs in order on ONE lane with the generator state in
-// LDS.  It exists for API / CLI compatibility on the small graphs these modes are meant for
-// (reference README: PreComp for < 10k nodes); the throughput path of this engine is SparseOTF.
+// 673-674), so the word offset at which walk i starts depends on every earlier draw (SURVEY.md
+// section 0, fact 1).  That offset is the one sequential quantity of a seeded run: given it, a walk is
+// independent of the others (seq_spec.h finds the offsets of many walks per round by speculation; it
+// has a host form only).  The exact path that ships walks all jobs in order on ONE lane with the
+// generator state in LDS.  It exists for API / CLI compatibility on the small graphs these modes are
+// meant for (reference README: PreComp for < 10k nodes); the throughput path of this engine is SparseOTF.
 //
 // Alias tables are built on the device, one thread per (vertex, previous-neighbour) pair, with
 // scalar code that follows the reference statement by statement (probabilities: sparse_rw.py:51-130,

@@ -614,6 +614,13 @@ class WalkEngine:
         _lib.check(self._lib.pw_stream_sample_device(self._h, int(seed) & 0xFFFFFFFF, int(offset), int(n), _np_ptr(out)))
         return out
 
+    def stream_words(self, seed, offset, n):
+        """Test hook: the raw 32-bit words ``#offset .. #offset + n`` of the same stream as the device expands them
+        (``pw_stream_words_device``)."""
+        out = np.zeros(int(n), dtype=np.uint32)
+        _lib.check(self._lib.pw_stream_words_device(self._h, int(seed) & 0xFFFFFFFF, int(offset), int(n), _np_ptr(out)))
+        return out
+
     def stream_hold(self, seed, stream_skip, n_draws):
         """Expand the draws ``[stream_skip, stream_skip + n_draws)`` of ``seed``'s stream once; ``simulate_device`` calls inside
         that range (same seed) use them in place until ``stream_release`` -- one jump-ahead tree for a shard walked in chunks."""
