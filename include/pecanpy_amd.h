@@ -537,6 +537,57 @@ int pw_walks_write_text_device(int device, const uint32_t *d_walks, uint64_t n_w
 int pw_walks_write_text(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, const char *id_chars,
                         const uint64_t *id_offsets, uint64_t n_names, const char *path, pw_walks_write_stats *stats);
 
+/* ---- nearest neighbours of embedding vectors, exact and ordered (csrc/knn.hip.h) ---------------------------------------------
+ * What gensim's wv.most_similar answers, on the vectors where the trainer leaves them, by one written definition whose
+ * answer is unique -- the device kernels are held to it bit for bit (the full text stands at the top of csrc/knn.hip.h):
+ *   dot(a, b)  = (((0.0 + a[0] b[0]) + a[1] b[1]) + ...), k ascending, in float64 on the float32 values widened (the products
+ *                are exact, the dim additions the only roundings; fma and multiply-add give the same bits);
+ *   norm(x)    = sqrt(dot(x, x)), correctly rounded;
+ *   score      PW_KNN_DOT: dot(q, x).  PW_KNN_COSINE: dot(q, x) / (norm(q) * norm(x)), +0.0 when that product is 0;
+ *   order      descending score, equal scores by ascending row number: total, so the top topn are unique;
+ *   exclude_self   a query given as a row number leaves that one row out (a different row with the same contents stays); a
+ *                query given as a vector excludes nothing;
+ *   output     idx uint32[nq, topn], score float64[nq, topn]; slots beyond the number of candidates hold 0xFFFFFFFF / -inf.
+ * Limits: 1 <= topn <= PW_KNN_MAX_TOPN, 1 <= dim <= 4096, 1 <= n_rows < 2^32; nq = 0 is a valid call that does nothing.
+ * PW_ERR_INVALID, nothing written: a NaN or an infinity in the matrix ("row <i> ...") or in a query vector ("query <i> ..."),
+ * naming the first; a row number >= n_rows; both or neither of d_queries and d_rows; a limit exceeded.
+ *   pw_knn_create_device   COPIES the matrix (device float32[n_rows, dim], contiguous): the index is a snapshot, a session that
+ *                goes on training does not change it.  Computes the norms and refuses non-finite rows.  pw_knn_create: the same
+ *                from host memory.
+ *   pw_knn_query_device    d_queries (device float32[nq, dim]) or d_rows (device uint32[nq]) -- exactly one; d_idx, d_score on the
+ *                index's device.  Runs on the device's default stream and returns when the results are written.  stats is
+ *                optional.
+ *   pw_knn_info, pw_knn_norms_get (device float64[n_rows]), pw_knn_destroy (NULL is harmless). */
+#define PW_KNN_MAX_TOPN 128
+enum { PW_KNN_DOT = 0, PW_KNN_COSINE = 1 };
+typedef struct pw_knn pw_knn;
+typedef struct pw_knn_stats {
+    double score_ms, merge_ms;   /* HIP-event time of the score kernel and of the merge kernel, summed over the batches */
+    double total_ms;             /* host clock of the call */
+    uint32_t grid;               /* workgroups of the score kernel = row_parts * tile_parts (the first batch's) */
+    uint32_t row_parts;          /* parts the row blocks are dealt to: a query has row_parts * rows_per_block / 64 partial lists */
+    uint32_t rows_per_block, queries_per_tile, col_chunk;   /* the tile actually used (pw_knn_tiles) */
+    uint32_t batches;            /* query batches (the widened queries of a batch stay within 256 MiB) */
+} pw_knn_stats;
+typedef struct pw_knn_tiles {    /* test configuration of pw_selftest_knn; 0 in a field = the default */
+    uint32_t rows_per_block;     /* rows a workgroup stages at a time: 64, 128 or 256 (default: by nq) */
+    uint32_t queries_per_tile;   /* queries a wavefront keeps accumulators for: 1 .. 8 (default 8) */
+    uint32_t grid;               /* workgroups of the score kernel, at most 65536 (default: what the device holds at once) */
+    uint32_t col_chunk;          /* columns staged at a time: a multiple of 4, at most 32 (default 32) */
+} pw_knn_tiles;
+int pw_knn_create_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, pw_knn **out);
+int pw_knn_create(int device, const float *vectors, uint64_t n_rows, uint32_t dim, pw_knn **out);
+int pw_knn_query_device(pw_knn *k, const float *d_queries, const uint32_t *d_rows, uint64_t nq, uint32_t topn, int metric,
+                        int exclude_self, uint32_t *d_idx, double *d_score, pw_knn_stats *stats);
+int pw_knn_info(const pw_knn *k, uint64_t *n_rows, uint32_t *dim, uint64_t *bytes);
+int pw_knn_norms_get(pw_knn *k, double *d_norms);
+void pw_knn_destroy(pw_knn *k);
+/* Test hook: the whole query on HOST pointers.  on_device = 0: the host build of the definition (plain loops), usable
+ * without a GPU; otherwise upload, the kernels with the forced tiles (NULL: the defaults), download.  Same refusals. */
+int pw_selftest_knn(int on_device, int device, const float *vectors, uint64_t n, uint32_t dim, const float *queries,
+                    const uint32_t *rows, uint64_t nq, uint32_t topn, int metric, int exclude_self, const pw_knn_tiles *tiles,
+                    uint32_t *idx, double *score);
+
 /* ---- random stream service (host side; usable without a GPU) ---------------------------- */
 /* doubles #offset.. of RandomState(seed).random_sample, produced with MT19937 jump-ahead. */
 int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, double *out);

@@ -120,6 +120,40 @@ class PwWalksWriteStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PwKnnStats(C.Structure):
+    """``pw_knn_stats`` of include/pecanpy_amd.h."""
+    _fields_ = [
+        ("score_ms", C.c_double),
+        ("merge_ms", C.c_double),
+        ("total_ms", C.c_double),
+        ("grid", C.c_uint32),
+        ("row_parts", C.c_uint32),
+        ("rows_per_block", C.c_uint32),
+        ("queries_per_tile", C.c_uint32),
+        ("col_chunk", C.c_uint32),
+        ("batches", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PwKnnTiles(C.Structure):
+    """``pw_knn_tiles`` of include/pecanpy_amd.h (0 in a field = the default)."""
+    _fields_ = [
+        ("rows_per_block", C.c_uint32),
+        ("queries_per_tile", C.c_uint32),
+        ("grid", C.c_uint32),
+        ("col_chunk", C.c_uint32),
+    ]
+
+
+PW_KNN_MAX_TOPN = 128
+KNN_METRICS = {"dot": 0, "cosine": 1}   # PW_KNN_DOT, PW_KNN_COSINE
+KNN_QT = 8                              # queries a wavefront keeps accumulators for (csrc/knn.hip.h)
+ERR_INVALID = -1                        # PW_ERR_INVALID
+
+
 class PwEdgelistDevStats(C.Structure):
     """``pw_edgelist_dev_stats`` of include/pecanpy_amd.h."""
     _fields_ = [
@@ -278,6 +312,15 @@ SYMBOLS = {
                                              C.POINTER(PwWalksWriteStats)]),
     "pw_walks_write_text": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p,
                                       C.POINTER(PwWalksWriteStats)]),
+    "pw_knn_create_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "pw_knn_create": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "pw_knn_query_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.POINTER(PwKnnStats)]),
+    "pw_knn_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), _u32p, C.POINTER(C.c_uint64)]),
+    "pw_knn_norms_get": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pw_knn_destroy": (None, [C.c_void_p]),
+    "pw_selftest_knn": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                  C.c_int, C.c_int, C.POINTER(PwKnnTiles), C.c_void_p, C.c_void_p]),
     "pw_selftest_format_f6": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pw_selftest_exclusive_scan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),

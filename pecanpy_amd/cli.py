@@ -7,6 +7,7 @@ uses gensim when it is importable; without it walks and skip-gram both run on th
 walk matrix stays in device memory).  ``--task walks`` writes the walks (one per line) to ``--output`` instead of training,
 the text made in device memory; ``PECANPY_AMD_DUMP_WALKS=1`` does the same through the ID lists of ``simulate_walks``.
 ``--task train`` takes such a file as ``--input`` and trains from it on the GPU, without a graph.
+``--task neighbours`` takes an embedding file as ``--input`` and writes the nearest neighbours of its nodes (``embed.KnnIndex``).
 The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
@@ -27,10 +28,11 @@ MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "Sp
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
     ("--output", dict(required=True, help="embedding file (.npz -> IDs/data arrays, else word2vec text)")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train"),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours"),
                     help="run node2vec; only convert the edge list to CSR / dense .npz; (walks) generate the walks and "
-                         "write them, one per line, to --output, no training; or (train) train embeddings from a walk "
-                         "corpus file given as --input, no graph")),
+                         "write them, one per line, to --output, no training; (train) train embeddings from a walk "
+                         "corpus file given as --input, no graph; or (neighbours) the nearest neighbours of the nodes of an "
+                         "embedding file given as --input, no graph")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
     ("--walk-length", dict(type=int, default=80, help="steps per walk")),
@@ -60,6 +62,9 @@ _OPTIONS = (
                                                      "nodes are trained")),
     ("--walks_from", dict(default="new", choices=("new", "all"),
                           help="with --init_emb: walks start from the nodes the file does not have (new) or from every node (all)")),
+    ("--topn", dict(type=int, default=10, help="--task neighbours: neighbours per query")),
+    ("--metric", dict(default="cosine", choices=("cosine", "dot"), help="--task neighbours: the score")),
+    ("--queries", dict(default=None, metavar="FILE", help="--task neighbours: one node ID per line (default: every node)")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
     ("--implicit_ids", dict(action="store_true", help=".npz without IDs: use 0..N-1")),
 )
@@ -289,6 +294,14 @@ def _warn_init_flags_ignored(args, why):
         warnings.warn(f"--init_emb, --freeze_init and --walks_from belong to the GPU trainer on a graph; {why}", stacklevel=3)
 
 
+def _warn_graph_flags_ignored(args, task):
+    """The warnings of a task that has no graph (``train``, ``neighbours``) for the flags that need one."""
+    if args.fresh_walks or args.holdout_walks:
+        warnings.warn(f"--fresh_walks and --holdout_walks draw walks from a graph; --task {task} has none, so they are ignored",
+                      stacklevel=3)
+    _warn_init_flags_ignored(args, f"--task {task} has no graph, so they are ignored")
+
+
 def _session_workers(args):
     """``--epoch_loss`` forwards ``--workers 1`` to the GPU trainer (one wavefront, deterministic); any other value keeps the
     trainer's default."""
@@ -311,10 +324,7 @@ def train_from_corpus(args):
     memory and trained there (``embed.train_sgns_file``); the vectors are written in order of first appearance."""
     from .embed import save_word2vec_format_device, sgns_session_file, train_sgns_file
 
-    if args.fresh_walks or args.holdout_walks:
-        warnings.warn("--fresh_walks and --holdout_walks draw walks from a graph; --task train has none, so they are ignored",
-                      stacklevel=2)
-    _warn_init_flags_ignored(args, "--task train has no graph, so they are ignored")
+    _warn_graph_flags_ignored(args, "train")
 
     if args.epoch_loss:
         names, session = sgns_session_file(args.input, dim=args.dimensions, window=args.window_size, epochs=args.epochs,
@@ -333,12 +343,43 @@ def train_from_corpus(args):
         save_word2vec_format_device(args.output, names, d_vectors)
 
 
+@Timer("read embedding + nearest neighbours")
+def neighbours_from_file(args):
+    """``--task neighbours``: ``--input`` is an embedding file (``read_init_emb``: ``.npz`` with ``IDs`` / ``data``, or word2vec
+    text); ``--output`` gets one line ``query<TAB>neighbour<TAB>%.6f`` per result, the queries in the order given (``--queries``:
+    one ID per line; default every row), the neighbours in rank order (``embed.KnnIndex``: exact, ties by row number)."""
+    from . import embed
+
+    _warn_graph_flags_ignored(args, "neighbours")
+    ids, data = read_init_emb(args.input)
+    if args.queries:
+        row_of = {name: i for i, name in enumerate(ids)}
+        with open(args.queries, encoding="utf-8") as f:
+            asked = [line.strip() for line in f if line.strip()]
+        for name in asked:
+            if name not in row_of:
+                raise ValueError(f"{args.queries}: unknown node ID {name!r}")
+        rows = np.array([row_of[name] for name in asked], dtype=np.int64)
+    else:
+        rows = np.arange(len(ids), dtype=np.int64)
+    with embed.KnnIndex(data, node_ids=ids) as index:
+        idx, score = index.query(rows=rows, topn=args.topn, metric=args.metric)
+    idx, score = idx.cpu().numpy(), score.cpu().numpy()
+    with open(args.output, "w", encoding="utf-8", newline="\n") as f:
+        for r, ri, rs in zip(rows, idx, score):
+            f.write("".join("%s\t%s\t%.6f\n" % (ids[r], ids[i], s) for i, s in zip(ri, rs) if i >= 0))
+
+
 def main(argv=None):
-    """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings."""
+    """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings; ``--task
+    neighbours``: embedding file -> nearest neighbours."""
     args = parse_args(argv)
     args.cli_workers = args.workers   # (as given: below, 0 becomes the host's thread count for gensim)
     if args.task == "train":   # no graph: the graph flags are ignored
         train_from_corpus(args)
+        return
+    if args.task == "neighbours":
+        neighbours_from_file(args)
         return
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)

@@ -18,6 +18,10 @@ CPU restatement of the algorithm instead (tests/test_gpu_sgns.py, tests/test_gpu
 matrices, a checkpoint file, a new schedule on trained vectors (tests/test_gpu_sgns_session.py); ``sgns_session_file`` opens
 one on a corpus file.  ``SgnsSession.evaluate`` scores any walk matrix with the vectors as they are, by a read-only kernel, and
 ``SgnsSession.set_walks`` puts another corpus of the same shape under the session (tests/test_gpu_sgns_eval.py).
+
+``KnnIndex`` answers nearest-neighbour queries on the vectors in device memory (``pw_knn``, csrc/knn.hip.h): exact float64
+scores by one written definition, ties ordered by row number, bit for bit what ``knn_host`` states in NumPy
+(tests/test_knn_host.py, tests/test_gpu_knn.py); ``SgnsSession.most_similar`` / ``knn_index`` query a session's vectors.
 """
 import ctypes as C
 
@@ -26,7 +30,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["train_sgns", "train_sgns_device", "train_sgns_file", "save_word2vec_format", "save_word2vec_format_device",
-           "SgnsSession", "sgns_session_file"]
+           "SgnsSession", "sgns_session_file", "KnnIndex", "knn_host"]
 
 
 def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
@@ -452,6 +456,29 @@ class SgnsSession:
         for which, m in staged:
             _lib.check(_lib.load().pw_sgns_vectors_set(handle, which, C.c_void_p(m.data_ptr())))
 
+    # ---- nearest neighbours
+    def knn_index(self, against="vectors"):
+        """A ``KnnIndex`` on a snapshot of ``vectors()`` (``against="vectors"``) or of ``context_vectors()``
+        (``against="context"``) as they are now: training on does not change it.  For callers who query more than once."""
+        if against not in ("vectors", "context"):
+            raise ValueError(f"against must be 'vectors' or 'context', not {against!r}")
+        return KnnIndex(self.vectors() if against == "vectors" else self.context_vectors())
+
+    def most_similar(self, rows, topn=10, metric="cosine", against="vectors"):
+        """``(idx, score)`` tensors of the ``topn`` nearest rows to each of ``rows`` among the current ``vectors()`` (the row
+        itself left out) or, with ``against="context"``, among ``context_vectors()`` (nothing left out).  The query vectors
+        always come from ``vectors()``: ``metric="dot"`` with ``against="context"`` is the model's own score of a (centre,
+        context) pair, the link score SGNS trains.  The definition is ``KnnIndex``'s."""
+        with self.knn_index(against) as index:
+            if against == "vectors":
+                return index.query(rows=rows, topn=topn, metric=metric)
+            import torch
+
+            n = self.num_nodes
+            r = _knn_rows(rows, n)
+            return index.query(vectors=self.vectors()[torch.from_numpy(r.astype(np.int64)).to(self.d_walks.device)].contiguous(), topn=topn,
+                               metric=metric)
+
     # ---- checkpoints
     def save(self, path):
         """An ``.npz`` with both matrices, the state, the constructor's parameters and ``(n_walks, walk_length,
@@ -554,3 +581,258 @@ def save_word2vec_format_device(path, node_ids, d_vectors):
 
 
 save_word2vec_format_device.last_stats = None
+
+
+# ---- nearest neighbours of embedding vectors, exact and ordered (csrc/knn.hip.h) ----------------------------------------------
+def _check_value(rc):
+    """``_lib.check`` with PW_ERR_INVALID as a ``ValueError``."""
+    if rc == _lib.ERR_INVALID:
+        msg = _lib.load().pw_last_error()
+        raise ValueError(msg.decode() if msg else "invalid argument")
+    _lib.check(rc)
+
+
+def _knn_args(queries, rows, topn, metric, exclude_self):
+    """The checks every form of the query shares: ``(topn, metric id, exclude_self)``."""
+    if (queries is None) == (rows is None):
+        raise ValueError("exactly one of vectors (queries) and rows must be given")
+    topn = int(topn)
+    if not 1 <= topn <= _lib.PW_KNN_MAX_TOPN:
+        raise ValueError(f"topn = {topn} outside 1..{_lib.PW_KNN_MAX_TOPN}")
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+    if exclude_self is None:
+        exclude_self = rows is not None
+    return topn, _lib.KNN_METRICS[metric], bool(exclude_self)
+
+
+def _knn_rows(rows, n):
+    """Row numbers -- a list, an array or a tensor of integers -- as a uint32 array; one outside ``0..n-1`` is a ``ValueError``."""
+    if hasattr(rows, "detach"):
+        rows = rows.detach().cpu().numpy()
+    rows = np.asarray(rows)
+    if rows.dtype == object or rows.dtype.kind not in "iu" or rows.ndim != 1:
+        raise ValueError("rows must be a one-dimensional array of integers")
+    if rows.size:
+        lo, hi = int(rows.min()), int(rows.max())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"row number {lo if lo < 0 else hi} is outside the {n} rows")
+    return np.ascontiguousarray(rows, dtype=np.uint32)
+
+
+def knn_host(vectors, queries=None, rows=None, topn=10, metric="cosine", exclude_self=None):
+    """The NumPy statement of the nearest-neighbour definition (csrc/knn.hip.h), what ``KnnIndex`` is held to bit
+    for bit: ``(idx int64[nq, topn], score float64[nq, topn])``, padded with -1 / -inf beyond the number of candidates.
+
+    ``dot`` sums the float64 products of the float32 values with k ascending from +0.0; ``norm = sqrt(dot(x, x))``;
+    ``cosine = dot(q, x) / (norm(q) * norm(x))``, +0.0 where that product is 0; rows rank by descending score, ties by
+    ascending row number; with ``exclude_self`` (the default for ``rows``) a query given as a row number leaves that row out."""
+    X = np.asarray(vectors)
+    if X.dtype != np.float32 or X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("vectors must be float32[n, dim]")
+    topn, metric_id, exclude_self = _knn_args(queries, rows, topn, metric, exclude_self)
+    n, dim = X.shape
+    if rows is not None:
+        rows = _knn_rows(rows, n)
+        Q = X[rows]
+    else:
+        Q = np.asarray(queries)
+        if Q.dtype != np.float32 or Q.ndim != 2 or Q.shape[1] != dim:
+            raise ValueError(f"queries must be float32[nq, {dim}]")
+    nq = Q.shape[0]
+
+    def dots(A, B):   # [len(A), len(B)]: k ascending, one rounding per addition
+        acc = np.zeros((A.shape[0], B.shape[0]))
+        tmp = np.empty_like(acc)
+        A64, B64 = A.astype(np.float64), np.ascontiguousarray(B.astype(np.float64).T)
+        for k in range(dim):
+            np.multiply(A64[:, k, None], B64[k][None, :], out=tmp)
+            acc += tmp
+        return acc
+
+    def self_dots(A):
+        acc = np.zeros(A.shape[0])
+        A64 = A.astype(np.float64)
+        for k in range(dim):
+            acc += A64[:, k] * A64[:, k]
+        return acc
+
+    with np.errstate(all="ignore"):
+        xx, qq = self_dots(X), self_dots(Q)
+        for what, d in (("row", xx), ("query", qq)):
+            bad = np.flatnonzero(~np.isfinite(d))
+            if bad.size and (what == "row" or rows is None):
+                raise ValueError(f"{what} {int(bad[0])} holds a NaN or an infinity")
+        xn, qn = np.sqrt(xx), np.sqrt(qq)
+        idx = np.full((nq, topn), -1, dtype=np.int64)
+        score = np.full((nq, topn), -np.inf)
+        block = 4096   # rows at a time: the running sums stay in cache
+        for q in range(0, nq, 64):
+            qs = slice(q, min(nq, q + 64))
+            s = np.concatenate([dots(Q[qs], X[b:b + block]) for b in range(0, n, block)], axis=1)
+            if metric_id == _lib.KNN_METRICS["cosine"]:
+                den = qn[qs, None] * xn[None, :]
+                s = np.where(den == 0.0, 0.0, s / np.where(den == 0.0, 1.0, den))
+            for i in range(s.shape[0]):
+                si = s[i]
+                cand = np.arange(n)
+                if exclude_self and rows is not None:
+                    cand = cand[cand != rows[q + i]]
+                if cand.size > topn:   # only what reaches the topn-th score can rank (ties included)
+                    cand = cand[si[cand] >= np.partition(si[cand], cand.size - topn)[cand.size - topn]]
+                order = cand[np.lexsort((cand, -si[cand]))][:topn]
+                idx[q + i, :order.size] = order
+                score[q + i, :order.size] = si[order]
+    return idx, score
+
+
+class KnnIndex:
+    """Nearest neighbours of embedding vectors on the GPU, exact and ordered (``pw_knn``, csrc/knn.hip.h): what gensim's
+    ``wv.most_similar`` answers, by the definition ``knn_host`` states in NumPy, bit for bit.
+
+    ``vectors``: a CUDA tensor, a CPU tensor or a NumPy array, float32 ``[n, dim]`` and contiguous (``1 <= dim <= 4096``);
+    anything else is a ``ValueError`` before any device work.  The index COPIES the matrix: a snapshot.  A NaN or an infinity
+    in it is a ``ValueError`` that names the first such row.  ``node_ids``: the ``n`` names ``most_similar`` speaks in.
+    A context manager; after ``close`` every use is a ``ValueError``."""
+
+    def __init__(self, vectors, node_ids=None, device=None):
+        self._handle = None
+        self.last_stats = None
+        kind = "numpy"
+        if hasattr(vectors, "is_cuda"):   # a torch tensor
+            import torch
+
+            kind = "cuda" if vectors.is_cuda else "cpu"
+            if vectors.device.type not in ("cpu", "cuda"):
+                raise ValueError(f"vectors must be on the host or on a GPU, not on {vectors.device}")
+            if vectors.dtype != torch.float32:
+                raise ValueError(f"vectors must be float32, not {vectors.dtype}")
+            shape, contiguous = tuple(vectors.shape), vectors.is_contiguous()
+        elif isinstance(vectors, np.ndarray):
+            if vectors.dtype != np.float32:
+                raise ValueError(f"vectors must be float32, not {vectors.dtype}")
+            shape, contiguous = vectors.shape, vectors.flags["C_CONTIGUOUS"]
+        else:
+            raise ValueError(f"vectors must be a torch tensor or a NumPy array, got {type(vectors).__name__}")
+        if len(shape) != 2 or shape[0] < 1 or not 1 <= shape[1] <= 4096:
+            raise ValueError(f"vectors must be float32[n, dim] with n >= 1 and 1 <= dim <= 4096, not {list(shape)}")
+        if not contiguous:
+            raise ValueError("vectors must be contiguous (row-major, dense)")
+        if shape[0] >= 2 ** 32:
+            raise ValueError("vectors must have fewer than 2^32 rows")
+        if node_ids is not None and len(node_ids) != shape[0]:
+            raise ValueError(f"{len(node_ids)} node names for {shape[0]} rows")
+        self.n, self.dim = int(shape[0]), int(shape[1])
+        self.node_ids = list(node_ids) if node_ids is not None else None
+        self._row_of = {name: i for i, name in enumerate(self.node_ids)} if node_ids is not None else None
+        self.device = vectors.device.index if kind == "cuda" else int(device or 0)
+
+        lib = _lib.load()
+        handle = C.c_void_p()
+        if kind == "cuda":
+            import torch
+
+            torch.cuda.current_stream(vectors.device).synchronize()   # the vectors were produced on torch's stream
+            rc = lib.pw_knn_create_device(self.device, C.c_void_p(vectors.data_ptr()), self.n, self.dim, C.byref(handle))
+        else:
+            host = vectors.numpy() if kind == "cpu" else vectors
+            rc = lib.pw_knn_create(self.device, C.c_void_p(host.ctypes.data), self.n, self.dim, C.byref(handle))
+        _check_value(rc)
+        self._handle = handle
+
+    def close(self):
+        """Free the index.  Closing twice is harmless."""
+        if self._handle is not None:
+            _lib.load().pw_knn_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown)
+            pass
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the index is closed")
+        return self._handle
+
+    def _torch_device(self):
+        import torch
+
+        return torch.device("cuda", self.device)
+
+    def norms(self):
+        """A new float64 ``[n]`` CUDA tensor: ``sqrt(dot(x, x))`` of every row, by the definition."""
+        import torch
+
+        handle = self._open()
+        out = torch.empty(self.n, dtype=torch.float64, device=self._torch_device())
+        _check_value(_lib.load().pw_knn_norms_get(handle, C.c_void_p(out.data_ptr())))
+        return out
+
+    def query(self, vectors=None, rows=None, topn=10, metric="cosine", exclude_self=None):
+        """``(idx, score)`` CUDA tensors, int64 ``[nq, topn]`` padded with -1 and float64 padded with -inf: the ``topn``
+        nearest rows to each query, given as ``vectors`` (float32 ``[nq, dim]``: a CUDA tensor on the index's device, a CPU
+        tensor or a NumPy array) or as ``rows`` (row numbers).  ``exclude_self`` defaults to True for ``rows`` -- that one
+        row is left out -- and means nothing for ``vectors``.  ``self.last_stats``: ``pw_knn_stats``."""
+        import torch
+
+        handle = self._open()
+        topn, metric_id, exclude_self = _knn_args(vectors, rows, topn, metric, exclude_self)
+        dev = self._torch_device()
+        d_q = d_r = None
+        if rows is not None:
+            d_r = torch.from_numpy(_knn_rows(rows, self.n).view(np.int32)).to(dev)
+            nq = d_r.numel()
+        else:
+            q = vectors
+            if isinstance(q, np.ndarray):
+                if q.dtype != np.float32:
+                    raise ValueError(f"query vectors must be float32, not {q.dtype}")
+                q = torch.from_numpy(np.ascontiguousarray(q))
+            elif not isinstance(q, torch.Tensor):
+                raise ValueError(f"query vectors must be a torch tensor or a NumPy array, got {type(q).__name__}")
+            if q.dtype != torch.float32:
+                raise ValueError(f"query vectors must be float32, not {q.dtype}")
+            if q.dim() != 2 or q.shape[1] != self.dim:
+                raise ValueError(f"query vectors must be float32[nq, {self.dim}], not {list(q.shape)}")
+            if q.is_cuda and q.device != dev:
+                raise ValueError(f"query vectors must be on the host or on {dev}, not on {q.device}")
+            d_q = q.to(dev).contiguous()
+            nq = d_q.shape[0]
+        idx = torch.empty((nq, topn), dtype=torch.int32, device=dev)
+        score = torch.empty((nq, topn), dtype=torch.float64, device=dev)
+        st = _lib.PwKnnStats()
+        torch.cuda.current_stream(dev).synchronize()   # the queries were produced on torch's stream
+        _check_value(_lib.load().pw_knn_query_device(handle, C.c_void_p(d_q.data_ptr()) if d_q is not None else None,
+                                                     C.c_void_p(d_r.data_ptr()) if d_r is not None else None, nq, topn, metric_id,
+                                                     int(exclude_self), C.c_void_p(idx.data_ptr()), C.c_void_p(score.data_ptr()), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return idx.to(torch.int64), score   # (0xFFFFFFFF, the padding, is -1 as an int32)
+
+    def _row(self, node):
+        if self._row_of is None:
+            return int(node)
+        if node in self._row_of:
+            return self._row_of[node]
+        if str(node) in self._row_of:
+            return self._row_of[str(node)]
+        raise ValueError(f"unknown node ID {node!r}")
+
+    def most_similar(self, node, topn=10, metric="cosine"):
+        """gensim's shape: ``[(id, score), ...]`` in rank order for one ``node`` -- an ID of ``node_ids``, or a row number when
+        there are none -- with the padding trimmed; a list of such lists for a list of nodes.  The node itself is left out."""
+        many = isinstance(node, (list, tuple, np.ndarray))
+        rows = [self._row(x) for x in (node if many else [node])]
+        idx, score = self.query(rows=np.asarray(rows, dtype=np.int64), topn=topn, metric=metric)
+        idx, score = idx.cpu().numpy(), score.cpu().numpy()
+        name = (lambda i: self.node_ids[i]) if self.node_ids is not None else int
+        out = [[(name(int(i)), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+        return out if many else out[0]
