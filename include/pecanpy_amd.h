@@ -588,6 +588,40 @@ int pw_selftest_knn(int on_device, int device, const float *vectors, uint64_t n,
                     const uint32_t *rows, uint64_t nq, uint32_t topn, int metric, int exclude_self, const pw_knn_tiles *tiles,
                     uint32_t *idx, double *score);
 
+/* ---- link prediction in device memory: pair scores, exact AUC, non-edges from the seeded stream --------------------------
+ * The three definitions are written at the top of csrc/linkpred.hip.h (DESIGN.md 4.9 repeats them); host and device answer
+ * them identically, whatever the grid, the tiling or the batch size.  Refusals: PW_ERR_INVALID with a message that names the
+ * first offending element, nothing written.
+ *   pw_knn_score_pairs_device   d_score[i] = the score (pw_knn's dot / norm / score, the stored norms) of row d_u[i] of `a` and row
+ *                d_v[i] of `b` (NULL: of `a`).  `b` must have a's dim and device; row numbers are checked against each index's
+ *                n_rows.  m = 0 is a valid call that does nothing; u[i] == v[i] and repeated pairs are allowed.  d_u, d_v
+ *                (uint32[m]) and d_score (float64[m]) on the indexes' device.
+ *   pw_auc_device   out[0] = wins = #{(i, j): pos[i] > neg[j]}, out[1] = ties = #{(i, j): pos[i] == neg[j]}, IEEE comparison
+ *                (-0.0 == +0.0, infinities ordinary); the AUC is (2 wins + ties) / (2 m n).  d_pos float64[m], d_neg float64[n]
+ *                on `device`; m, n >= 1, m * n < 2^62, n < 2^32.  A NaN in either array is refused ("pos[i]" before "neg[j]").
+ *   pw_sample_non_edges_device   candidate c, counted from first_candidate, of the words w of RandomState(seed) (pw_mt_words):
+ *                u = (w[2c] * n_nodes) >> 32, v = (w[2c+1] * n_nodes) >> 32, accepted when u != v and v is not in row u.  d_u,
+ *                d_v (device uint32[m]) receive the first m accepted candidates in candidate order (pairs may repeat);
+ *                *candidates_used = one past the last candidate examined, minus first_candidate: a call at first_candidate +
+ *                *candidates_used continues the sequence.  PW_ERR_UNSUPPORTED on dense handles; refused when the graph has no
+ *                off-diagonal non-edge, and once 16 * ceil(m * n_nodes^2 / acceptable pairs) + 64 candidates have been examined
+ *                (the message names the count).  m < 2^32.
+ * Test hooks on HOST pointers (on_device = 0: the host build of the definitions, plain loops, usable without a GPU; otherwise
+ * upload, the kernels, download): pw_selftest_score_pairs (b == NULL: a against itself; dim_b: b's row length),
+ * pw_selftest_auc, pw_selftest_sample_non_edges (the CSR as host arrays, rows ascending; batch: candidates per batch of the
+ * device form, 0 = the default). */
+int pw_knn_score_pairs_device(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint32_t *d_v, uint64_t m, int metric,
+                              double *d_score);
+int pw_auc_device(int device, const double *d_pos, uint64_t m, const double *d_neg, uint64_t n, uint64_t out[2]);
+int pw_sample_non_edges_device(pw_graph *g, uint32_t seed, uint64_t first_candidate, uint64_t m, uint32_t *d_u, uint32_t *d_v,
+                               uint64_t *candidates_used);
+int pw_selftest_score_pairs(int on_device, int device, const float *a, uint64_t na, const float *b, uint64_t nb, uint32_t dim,
+                            uint32_t dim_b, const uint32_t *u, const uint32_t *v, uint64_t m, int metric, double *score);
+int pw_selftest_auc(int on_device, int device, const double *pos, uint64_t m, const double *neg, uint64_t n, uint64_t out[2]);
+int pw_selftest_sample_non_edges(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes,
+                                 uint32_t seed, uint64_t first_candidate, uint64_t m, uint64_t batch, uint32_t *u, uint32_t *v,
+                                 uint64_t *candidates_used);
+
 /* ---- random stream service (host side; usable without a GPU) ---------------------------- */
 /* doubles #offset.. of RandomState(seed).random_sample, produced with MT19937 jump-ahead. */
 int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, double *out);

@@ -321,6 +321,14 @@ SYMBOLS = {
     "pw_knn_destroy": (None, [C.c_void_p]),
     "pw_selftest_knn": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                   C.c_int, C.c_int, C.POINTER(PwKnnTiles), C.c_void_p, C.c_void_p]),
+    "pw_knn_score_pairs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "pw_auc_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pw_sample_non_edges_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "pw_selftest_score_pairs": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "pw_selftest_auc": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pw_selftest_sample_non_edges": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                               C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "pw_selftest_format_f6": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pw_selftest_exclusive_scan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),

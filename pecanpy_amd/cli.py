@@ -8,6 +8,8 @@ walk matrix stays in device memory).  ``--task walks`` writes the walks (one per
 the text made in device memory; ``PECANPY_AMD_DUMP_WALKS=1`` does the same through the ID lists of ``simulate_walks``.
 ``--task train`` takes such a file as ``--input`` and trains from it on the GPU, without a graph.
 ``--task neighbours`` takes an embedding file as ``--input`` and writes the nearest neighbours of its nodes (``embed.KnnIndex``).
+``--task score`` takes an embedding file as ``--input`` and writes the score of every pair of ``--pairs``; with ``--neg_pairs`` it
+also prints the exact AUC of the two sets of scores (``linkpred``).
 The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
@@ -28,10 +30,11 @@ MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "Sp
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
     ("--output", dict(required=True, help="embedding file (.npz -> IDs/data arrays, else word2vec text)")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours"),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score"),
                     help="run node2vec; only convert the edge list to CSR / dense .npz; (walks) generate the walks and "
                          "write them, one per line, to --output, no training; (train) train embeddings from a walk "
                          "corpus file given as --input, no graph; or (neighbours) the nearest neighbours of the nodes of an "
+                         "embedding file given as --input, no graph; or (score) the score of every node pair of --pairs by an "
                          "embedding file given as --input, no graph")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
@@ -63,8 +66,11 @@ _OPTIONS = (
     ("--walks_from", dict(default="new", choices=("new", "all"),
                           help="with --init_emb: walks start from the nodes the file does not have (new) or from every node (all)")),
     ("--topn", dict(type=int, default=10, help="--task neighbours: neighbours per query")),
-    ("--metric", dict(default="cosine", choices=("cosine", "dot"), help="--task neighbours: the score")),
+    ("--metric", dict(default="cosine", choices=("cosine", "dot"), help="--task neighbours / score: the score")),
     ("--queries", dict(default=None, metavar="FILE", help="--task neighbours: one node ID per line (default: every node)")),
+    ("--pairs", dict(default=None, metavar="FILE", help="--task score: two node IDs per line, separated by --delimiter")),
+    ("--neg_pairs", dict(default=None, metavar="FILE",
+                         help="--task score: negative pairs in the same form; prints 'auc wins ties m n' of --pairs against them")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
     ("--implicit_ids", dict(action="store_true", help=".npz without IDs: use 0..N-1")),
 )
@@ -78,7 +84,10 @@ def parse_args(argv=None):
         formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     for flag, kw in _OPTIONS:
         parser.add_argument(flag, **kw)
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.task == "score" and not args.pairs:
+        parser.error("--task score needs --pairs")
+    return args
 
 
 def _advise(better, current, why):
@@ -370,6 +379,51 @@ def neighbours_from_file(args):
             f.write("".join("%s\t%s\t%.6f\n" % (ids[r], ids[i], s) for i, s in zip(ri, rs) if i >= 0))
 
 
+def _read_pairs(path, delimiter, row_of):
+    """``(names_u, names_v, rows_u, rows_v)`` of a pair file: two node IDs per line, separated by ``delimiter``; an unknown ID
+    or another number of fields is a ``ValueError`` naming the line."""
+    nu, nv = [], []
+    with open(path, encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            terms = line.split(delimiter)
+            if len(terms) != 2:
+                raise ValueError(f"{path}, line {no}: expected two node IDs, found {len(terms)} fields")
+            for name in terms:
+                if name not in row_of:
+                    raise ValueError(f"{path}, line {no}: unknown node ID {name!r}")
+            nu.append(terms[0])
+            nv.append(terms[1])
+    rows = [np.array([row_of[x] for x in names], dtype=np.int64) for names in (nu, nv)]
+    return nu, nv, rows[0], rows[1]
+
+
+@Timer("read embedding + score pairs")
+def score_from_file(args):
+    """``--task score``: ``--input`` is an embedding file (``read_init_emb``), ``--pairs`` a file of node pairs; ``--output`` gets
+    one line ``id_u<delimiter>id_v<delimiter>score`` per pair, the score as ``repr(float)`` (``KnnIndex.score_pairs``: exact).  With
+    ``--neg_pairs`` the line ``auc wins ties m n`` of the pairs' scores against those pairs' scores goes to stdout
+    (``linkpred.auc``: exact integers, one rounding)."""
+    from . import embed, linkpred
+
+    _warn_graph_flags_ignored(args, "score")
+    ids, data = read_init_emb(args.input)
+    row_of = {name: i for i, name in enumerate(ids)}
+    nu, nv, ru, rv = _read_pairs(args.pairs, args.delimiter, row_of)
+    neg = _read_pairs(args.neg_pairs, args.delimiter, row_of) if args.neg_pairs else None
+    with embed.KnnIndex(data, node_ids=ids) as index:
+        d_pos = index.score_pairs(ru, rv, metric=args.metric)
+        d_neg = index.score_pairs(neg[2], neg[3], metric=args.metric) if neg else None
+        result = linkpred.auc(d_pos, d_neg) if neg else None
+    d = args.delimiter
+    with open(args.output, "w", encoding="utf-8", newline="\n") as f:
+        f.write("".join(f"{a}{d}{b}{d}{float(s)!r}\n" for a, b, s in zip(nu, nv, d_pos.cpu().numpy())))
+    if result:
+        print(f"{result[0]!r} {result[1]} {result[2]} {len(nu)} {len(neg[0])}")
+
+
 def main(argv=None):
     """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings; ``--task
     neighbours``: embedding file -> nearest neighbours."""
@@ -380,6 +434,9 @@ def main(argv=None):
         return
     if args.task == "neighbours":
         neighbours_from_file(args)
+        return
+    if args.task == "score":
+        score_from_file(args)
         return
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)

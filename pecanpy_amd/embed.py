@@ -22,15 +22,19 @@ one on a corpus file.  ``SgnsSession.evaluate`` scores any walk matrix with the 
 ``KnnIndex`` answers nearest-neighbour queries on the vectors in device memory (``pw_knn``, csrc/knn.hip.h): exact float64
 scores by one written definition, ties ordered by row number, bit for bit what ``knn_host`` states in NumPy
 (tests/test_knn_host.py, tests/test_gpu_knn.py); ``SgnsSession.most_similar`` / ``knn_index`` query a session's vectors.
+``KnnIndex.score_pairs`` / ``SgnsSession.score_pairs`` score given pairs of rows by the same definition; ``auc``, ``link_auc``
+and the host statements of link prediction live in ``linkpred.py`` and are re-exported here.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from .linkpred import auc, auc_host, link_auc, sample_non_edges_host, score_pairs_host   # noqa: F401  (link prediction: linkpred.py)
 
 __all__ = ["train_sgns", "train_sgns_device", "train_sgns_file", "save_word2vec_format", "save_word2vec_format_device",
-           "SgnsSession", "sgns_session_file", "KnnIndex", "knn_host"]
+           "SgnsSession", "sgns_session_file", "KnnIndex", "knn_host", "auc", "auc_host", "link_auc", "sample_non_edges_host",
+           "score_pairs_host"]
 
 
 def train_sgns(walk_matrix, num_nodes, dim=128, window=10, epochs=1, negative=5, alpha=0.025, min_alpha=1e-4,
@@ -479,6 +483,18 @@ class SgnsSession:
             return index.query(vectors=self.vectors()[torch.from_numpy(r.astype(np.int64)).to(self.d_walks.device)].contiguous(), topn=topn,
                                metric=metric)
 
+    def score_pairs(self, u, v, metric="dot", against="context"):
+        """A float64 ``[m]`` CUDA tensor: the score of ``vectors()[u[i]]`` against ``context_vectors()[v[i]]``
+        (``against="context"``: with ``metric="dot"`` the model's own link score, what ``most_similar`` ranks by) or against
+        ``vectors()[v[i]]`` (``against="vectors"``), as they are now.  The definition is ``KnnIndex.score_pairs``'s."""
+        if against not in ("vectors", "context"):
+            raise ValueError(f"against must be 'vectors' or 'context', not {against!r}")
+        with self.knn_index("vectors") as a:
+            if against == "vectors":
+                return a.score_pairs(u, v, metric=metric)
+            with self.knn_index("context") as b:
+                return a.score_pairs(u, v, metric=metric, other=b)
+
     # ---- checkpoints
     def save(self, path):
         """An ``.npz`` with both matrices, the state, the constructor's parameters and ``(n_walks, walk_length,
@@ -816,6 +832,15 @@ class KnnIndex:
                                                      int(exclude_self), C.c_void_p(idx.data_ptr()), C.c_void_p(score.data_ptr()), C.byref(st)))
         self.last_stats = st.as_dict()
         return idx.to(torch.int64), score   # (0xFFFFFFFF, the padding, is -1 as an int32)
+
+    def score_pairs(self, u, v, metric="cosine", other=None):
+        """A float64 ``[m]`` CUDA tensor: the score of row ``u[i]`` against row ``v[i]`` -- of ``other``, another ``KnnIndex``
+        of the same ``dim`` on the same device, when one is given -- by the definition of ``query`` (``linkpred.score_pairs``;
+        ``linkpred.score_pairs_host`` states it in NumPy).  ``u`` / ``v``: row numbers, torch or NumPy integer arrays, on the
+        GPU or not."""
+        from . import linkpred
+
+        return linkpred.score_pairs(self, u, v, metric=metric, other=other)
 
     def _row(self, node):
         if self._row_of is None:

@@ -1,0 +1,293 @@
+"""Link prediction in device memory (csrc/linkpred.hip.h): the score of given pairs of rows, the exact AUC of two sets of
+scores, and non-edges of a sparse graph drawn from the seeded stream -- each by one written definition that host and device
+answer identically, bit for bit and integer for integer.
+
+    with embed.KnnIndex(vectors) as index:
+        pos = index.score_pairs(eu, ev, metric="dot")            # float64 tensor on the index's device
+        nu, nv, used = g.sample_non_edges(len(eu), seed=7)       # g: SparseOTF / PreComp / ...
+        value, wins, ties = linkpred.auc(pos, index.score_pairs(nu, nv, metric="dot"))
+
+``score_pairs_host``, ``auc_host`` and ``sample_non_edges_host`` state the three definitions in NumPy, to be checked by eye;
+tests/test_linkpred_host.py and tests/test_gpu_linkpred.py hold the library to them.  There is no CPU fallback: without a GPU
+the device entry points raise ``PwError`` as every other one does."""
+import ctypes as C
+from fractions import Fraction
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["score_pairs", "auc", "sample_non_edges", "link_auc", "score_pairs_host", "auc_host", "sample_non_edges_host",
+           "candidate_cap"]
+
+
+def _check_value(rc):
+    """``_lib.check`` with PW_ERR_INVALID as a ``ValueError`` and PW_ERR_UNSUPPORTED as a ``NotImplementedError``."""
+    if rc in (_lib.ERR_INVALID, _lib.ERR_UNSUPPORTED):
+        msg = _lib.load().pw_last_error()
+        raise (ValueError if rc == _lib.ERR_INVALID else NotImplementedError)(msg.decode() if msg else "invalid argument")
+    _lib.check(rc)
+
+
+def _need_device(lib):
+    if int(lib.pw_device_count()) <= 0:
+        raise _lib.PwError("no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)")
+
+
+def _metric_id(metric):
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+    return _lib.KNN_METRICS[metric]
+
+
+def _rows_host(x, name):
+    """Row numbers on the host -- a list, an array or a CPU tensor of integers -- as a uint32 array."""
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.dtype == object or x.dtype.kind not in "iu" or x.ndim != 1:
+        raise ValueError(f"{name} must be a one-dimensional array of integers")
+    if x.size and (int(x.min()) < 0 or int(x.max()) >= 2 ** 32):
+        bad = int(np.flatnonzero((x < 0) | (x >= 2 ** 32))[0])
+        raise ValueError(f"row number {name}[{bad}] = {int(x[bad])} is no row number")
+    return np.ascontiguousarray(x, dtype=np.uint32)
+
+
+def _rows_device(x, name, dev):
+    """Row numbers as an int32 tensor on ``dev`` holding the uint32 bits; a CUDA tensor stays on the device."""
+    import torch
+
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        if x.device != dev:
+            raise ValueError(f"{name} must be on the host or on {dev}, not on {x.device}")
+        if x.dtype not in (torch.int32, torch.int64, torch.uint8, torch.int16, torch.int8) or x.dim() != 1:
+            raise ValueError(f"{name} must be a one-dimensional tensor of integers")
+        if x.numel():
+            lo, hi = int(x.min()), int(x.max())
+            if lo < 0 or hi >= 2 ** 32:
+                raise ValueError(f"row number {lo if lo < 0 else hi} in {name} is no row number")
+        return x.to(torch.int64).to(torch.int32).contiguous()   # (the low 32 bits: uint32 as the library reads them)
+    return torch.from_numpy(_rows_host(x, name).view(np.int32)).to(dev)
+
+
+# ---- the three definitions in NumPy ------------------------------------------------------------------------------------
+def _dots(A, B):
+    """``dot(A[i], B[i])`` for every i: float64 products of the float32 values, k ascending from +0.0, one rounding per
+    addition (``knn_host``'s ``dots`` order)."""
+    acc = np.zeros(A.shape[0])
+    A64, B64 = A.astype(np.float64), B.astype(np.float64)
+    for k in range(A.shape[1]):
+        acc += A64[:, k] * B64[:, k]
+    return acc
+
+
+def score_pairs_host(vectors, u, v, metric="cosine", other=None):
+    """The NumPy statement of the pair score: ``score[i] = score(A[u[i]], B[v[i]])`` with ``A = vectors`` and ``B = other``
+    (default ``A``), float64 ``[m]``.  ``dot`` sums the float64 products of the float32 values with k ascending from +0.0;
+    ``norm = sqrt(dot(x, x))``; ``cosine = dot / (norm(a) * norm(b))``, +0.0 where that product is 0.  A row number outside
+    its matrix is a ``ValueError`` naming the first position (``u`` before ``v``)."""
+    A = np.asarray(vectors)
+    B = A if other is None else np.asarray(other)
+    for X in (A, B):
+        if X.dtype != np.float32 or X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("vectors must be float32[n, dim]")
+    if A.shape[1] != B.shape[1]:
+        raise ValueError(f"the two matrices have dim {A.shape[1]} and {B.shape[1]}")
+    metric_id = _metric_id(metric)
+    u, v = _rows_host(u, "u"), _rows_host(v, "v")
+    if u.shape != v.shape:
+        raise ValueError(f"u and v must have one length, not {u.size} and {v.size}")
+    bad = np.flatnonzero((u >= A.shape[0]) | (v >= B.shape[0]))
+    if bad.size:
+        i = int(bad[0])
+        which, row, n = ("u", u[i], A.shape[0]) if u[i] >= A.shape[0] else ("v", v[i], B.shape[0])
+        raise ValueError(f"row number {which}[{i}] = {int(row)} is outside the {n} rows")
+    with np.errstate(all="ignore"):
+        s = _dots(A[u], B[v])
+        if metric_id == _lib.KNN_METRICS["cosine"]:
+            den = np.sqrt(_dots(A[u], A[u])) * np.sqrt(_dots(B[v], B[v]))
+            s = np.where(den == 0.0, 0.0, s / np.where(den == 0.0, 1.0, den))
+    return s
+
+
+def _auc_value(wins, ties, m, n):
+    return float(Fraction(2 * wins + ties, 2 * m * n))
+
+
+def auc_host(pos, neg):
+    """The NumPy statement of the exact AUC: ``(auc, wins, ties)`` with ``wins = #{(i, j): pos[i] > neg[j]}`` and ``ties =
+    #{(i, j): pos[i] == neg[j]}`` as Python integers (IEEE comparison: ``-0.0 == +0.0``, infinities are ordinary values) and
+    ``auc = float(Fraction(2 wins + ties, 2 m n))``: one rounding, so a function of the inputs alone.  A NaN is a
+    ``ValueError`` naming the first (``pos`` before ``neg``)."""
+    pos, neg = np.asarray(pos, dtype=np.float64).ravel(), np.asarray(neg, dtype=np.float64).ravel()
+    m, n = pos.size, neg.size
+    if m < 1 or n < 1:
+        raise ValueError("both arrays need at least one score")
+    for name, x in (("pos", pos), ("neg", neg)):
+        bad = np.flatnonzero(np.isnan(x))
+        if bad.size:
+            raise ValueError(f"{name}[{int(bad[0])}] is a NaN")
+    s = np.sort(neg + 0.0)   # (-0.0 + 0.0 = +0.0: one zero, as the comparison sees them)
+    lb = np.searchsorted(s, pos + 0.0, side="left")
+    ub = np.searchsorted(s, pos + 0.0, side="right")
+    wins = sum(int(x) for x in lb)
+    ties = sum(int(x) for x in ub) - wins
+    return _auc_value(wins, ties, m, n), wins, ties
+
+
+def candidate_cap(m, n_nodes, acceptable):
+    """The most candidates a call for ``m`` non-edges examines: ``16 * ceil(m N^2 / A) + 64``, at most ``2^62``."""
+    need = -(-(m * n_nodes * n_nodes) // acceptable)
+    return 2 ** 62 if need >= 2 ** 57 else 16 * need + 64
+
+
+def sample_non_edges_host(indptr, indices, m, seed, first_candidate=0):
+    """The plain-loop statement of the non-edge sampler: ``(u, v, candidates_used)``.  With ``w`` the tempered words of
+    ``RandomState(seed)`` (``pw_mt_words``) candidate ``c``, counted from ``first_candidate``, is ``u = (w[2c] * N) >> 32``,
+    ``v = (w[2c+1] * N) >> 32``; it is accepted when ``u != v`` and ``v`` is not in row ``u``.  The first ``m`` accepted
+    candidates, in order -- pairs may repeat -- and one past the last candidate examined, minus ``first_candidate``.  A graph
+    without an off-diagonal non-edge and a call that would pass ``candidate_cap`` are ``ValueError``s."""
+    indptr, indices = np.asarray(indptr).astype(np.int64), np.asarray(indices).astype(np.int64)
+    n = indptr.size - 1
+    rows = [set(indices[indptr[r]:indptr[r + 1]].tolist()) for r in range(n)]
+    loops = sum(1 for r in range(n) if r in rows[r])
+    acceptable = n * (n - 1) - (int(indptr[n]) - loops)
+    if acceptable == 0:
+        raise ValueError(f"the graph of {n} vertices has no off-diagonal non-edge")
+    m = int(m)
+    if m == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, np.uint32), 0
+    cap = candidate_cap(m, n, acceptable)
+    lib = _lib.load()
+    us, vs, c = [], [], 0
+    words, have0 = np.zeros(0, np.uint32), 0
+    while len(us) < m:
+        if c >= cap:
+            raise ValueError(f"{cap} candidates examined (the cap) gave {len(us)} of the {m} non-edges asked for")
+        if c >= have0 + words.size // 2:
+            have0, words = c, np.zeros(2 * min(1 << 14, cap - c), dtype=np.uint32)
+            _lib.check(lib.pw_mt_words(int(seed) & 0xFFFFFFFF, 2 * (int(first_candidate) + c), words.size, C.c_void_p(words.ctypes.data)))
+        cu = (int(words[2 * (c - have0)]) * n) >> 32
+        cv = (int(words[2 * (c - have0) + 1]) * n) >> 32
+        if cu != cv and cv not in rows[cu]:
+            us.append(cu)
+            vs.append(cv)
+        c += 1
+    return np.array(us, dtype=np.uint32), np.array(vs, dtype=np.uint32), c
+
+
+# ---- the device entry points -------------------------------------------------------------------------------------------
+def score_pairs(index, u, v, metric="cosine", other=None):
+    """``KnnIndex.score_pairs``: a float64 ``[m]`` tensor on the index's device, ``score(A[u[i]], B[v[i]])`` with ``A`` the index's
+    rows and ``B`` those of ``other`` (another ``KnnIndex`` of the same ``dim`` on the same device; default: the index
+    itself).  ``u`` / ``v``: row numbers, torch or NumPy integer arrays, on the GPU or not.  ``u[i] == v[i]`` and repeated
+    pairs are pairs like any other."""
+    import torch
+
+    handle = index._open()
+    metric_id = _metric_id(metric)
+    if other is not None and other.dim != index.dim:
+        raise ValueError(f"the two indexes have dim {index.dim} and {other.dim}")
+    if other is not None and other.device != index.device:
+        raise ValueError(f"the two indexes are on devices {index.device} and {other.device}")
+    dev = index._torch_device()
+    d_u, d_v = _rows_device(u, "u", dev), _rows_device(v, "v", dev)
+    if d_u.shape != d_v.shape:
+        raise ValueError(f"u and v must have one length, not {d_u.numel()} and {d_v.numel()}")
+    score = torch.empty(d_u.numel(), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()   # the row numbers were produced on torch's stream
+    _check_value(_lib.load().pw_knn_score_pairs_device(handle, other._open() if other is not None else None, C.c_void_p(d_u.data_ptr()),
+                                                       C.c_void_p(d_v.data_ptr()), d_u.numel(), metric_id, C.c_void_p(score.data_ptr())))
+    return score
+
+
+def _scores_device(x, name, dev):
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        if x.is_cuda and dev is not None and x.device != dev:
+            raise ValueError(f"{name} must be on the host or on {dev}, not on {x.device}")
+        if not x.dtype.is_floating_point:
+            raise ValueError(f"{name} must hold floating-point scores, not {x.dtype}")
+        t = x
+    else:
+        a = np.asarray(x)
+        if a.dtype.kind != "f":
+            raise ValueError(f"{name} must hold floating-point scores, not {a.dtype}")
+        t = torch.from_numpy(np.array(a, dtype=np.float64, order="C"))   # (a copy: torch wants a writable array)
+    return t.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+
+
+def auc(pos, neg, device=None):
+    """``(auc, wins, ties)`` of the positives' and the negatives' scores, counted on the GPU (``pw_auc_device``): ``wins =
+    #{pos[i] > neg[j]}``, ``ties = #{pos[i] == neg[j]}`` as Python integers, ``auc = float(Fraction(2 wins + ties, 2 m n))``.
+    Inputs already on the device stay there; host arrays are uploaded (to ``device``, default that of a CUDA input, else 0).
+    A NaN is a ``ValueError`` naming the first."""
+    import torch
+
+    lib = _lib.load()
+    _need_device(lib)
+    dev = next((x.device for x in (pos, neg) if isinstance(x, torch.Tensor) and x.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", int(device or 0))
+    elif device is not None and int(device) != dev.index:
+        raise ValueError(f"the scores live on {dev}, the call was asked for device {int(device)}")
+    d_pos, d_neg = _scores_device(pos, "pos", dev), _scores_device(neg, "neg", dev)
+    m, n = d_pos.numel(), d_neg.numel()
+    out = (C.c_uint64 * 2)()
+    torch.cuda.current_stream(dev).synchronize()   # the scores were produced on torch's stream
+    _check_value(lib.pw_auc_device(dev.index, C.c_void_p(d_pos.data_ptr()), m, C.c_void_p(d_neg.data_ptr()), n, out))
+    wins, ties = int(out[0]), int(out[1])
+    return _auc_value(wins, ties, m, n), wins, ties
+
+
+def sample_non_edges(graph, m, seed, first_candidate=0):
+    """``Base.sample_non_edges``: ``(u, v, candidates_used)`` -- two int64 ``[m]`` tensors on the graph's device and a Python
+    integer -- the first ``m`` candidates of ``seed``'s stream from ``first_candidate`` on that are neither a loop nor an edge
+    (``sample_non_edges_host`` states the rule).  The draws are independent, so accepted pairs MAY REPEAT.  A second call with
+    ``first_candidate`` advanced by ``candidates_used`` continues the sequence.  Dense graphs: ``NotImplementedError``."""
+    import torch
+
+    eng = graph._get_engine()
+    if eng.kind != "csr":
+        raise NotImplementedError("sample_non_edges needs a sparse (CSR) graph")
+    m = int(m)
+    if not 0 <= m < 2 ** 32:
+        raise ValueError(f"m = {m} outside 0 .. 2^32 - 1")
+    dev = torch.device("cuda", eng.device)
+    d_u = torch.empty(m, dtype=torch.int32, device=dev)
+    d_v = torch.empty(m, dtype=torch.int32, device=dev)
+    used = C.c_uint64(0)
+    torch.cuda.current_stream(dev).synchronize()
+    _check_value(_lib.load().pw_sample_non_edges_device(eng._h, int(seed) & 0xFFFFFFFF, int(first_candidate), m, C.c_void_p(d_u.data_ptr()),
+                                                        C.c_void_p(d_v.data_ptr()), C.byref(used)))
+    return d_u.to(torch.int64) & 0xFFFFFFFF, d_v.to(torch.int64) & 0xFFFFFFFF, int(used.value)
+
+
+def _pairs(p, name):
+    if isinstance(p, (tuple, list)) and len(p) == 2:
+        return p[0], p[1]
+    if hasattr(p, "shape") and len(p.shape) == 2 and p.shape[1] == 2:
+        return p[:, 0], p[:, 1]
+    if hasattr(p, "shape") and len(p.shape) == 2 and p.shape[0] == 2:
+        return p[0], p[1]
+    raise ValueError(f"{name} must be (u, v) or an integer array of shape [m, 2] or [2, m]")
+
+
+def link_auc(index_or_session, pos_pairs, neg_pairs, metric="dot", against="context"):
+    """``(auc, wins, ties)`` of the scores of ``pos_pairs`` against those of ``neg_pairs`` -- each ``(u, v)`` or an integer
+    array ``[m, 2]`` / ``[2, m]`` -- scored by a ``KnnIndex`` (``against`` is ignored) or an ``SgnsSession`` (``against`` as
+    ``SgnsSession.score_pairs``): ``score_pairs`` twice, then ``auc``."""
+    from . import embed
+
+    if isinstance(index_or_session, embed.KnnIndex):
+        def score(u, v):
+            return index_or_session.score_pairs(u, v, metric=metric)
+    else:
+        def score(u, v):
+            return index_or_session.score_pairs(u, v, metric=metric, against=against)
+    if not isinstance(index_or_session, embed.KnnIndex) and against == "context":
+        with index_or_session.knn_index("vectors") as a, index_or_session.knn_index("context") as b:   # one snapshot for both calls
+            return auc(a.score_pairs(*_pairs(pos_pairs, "pos_pairs"), metric=metric, other=b),
+                       a.score_pairs(*_pairs(neg_pairs, "neg_pairs"), metric=metric, other=b))
+    return auc(score(*_pairs(pos_pairs, "pos_pairs")), score(*_pairs(neg_pairs, "neg_pairs")))

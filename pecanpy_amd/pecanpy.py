@@ -657,6 +657,17 @@ class Base(BaseGraph):
         self.last_corpus_stats = {"walk_matrix_host_bytes": 0, "walk_ms": (t1 - t0) * 1e3,
                                   "write_call_ms": (time.perf_counter() - t1) * 1e3, **save_walks_device.last_stats}
 
+    def sample_non_edges(self, m, seed, first_candidate=0):
+        """``(u, v, candidates_used)``: ``m`` pairs of node indices that are neither a loop nor an edge of this graph, drawn
+        on the GPU from ``seed``'s stream (``linkpred.sample_non_edges``; ``linkpred.sample_non_edges_host`` states the rule):
+        negatives for link prediction.  Accepted pairs may repeat.  ``candidates_used`` added to ``first_candidate``
+        continues the sequence in a later call.  Sparse classes only: a dense one raises ``NotImplementedError``."""
+        if not isinstance(self, SparseGraph):
+            raise NotImplementedError("sample_non_edges needs a sparse (CSR) graph")
+        from . import linkpred
+
+        return linkpred.sample_non_edges(self, m, seed, first_candidate)
+
     def embed(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, verbose=False):
         """``simulate_walks`` + skip-gram (pecanpy.py:240-290): returns ``float32[num_nodes, dim]`` in node order.
 
