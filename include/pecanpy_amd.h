@@ -622,6 +622,39 @@ int pw_selftest_sample_non_edges(int on_device, int device, const uint32_t *indp
                                  uint32_t seed, uint64_t first_candidate, uint64_t m, uint64_t batch, uint32_t *u, uint32_t *v,
                                  uint64_t *candidates_used);
 
+/* ---- edges held out by the seeded stream: the train graph and the held-out pairs, in device memory ----------------------
+ * The definition is written at the top of csrc/holdout.hip.h (DESIGN.md 4.10 repeats it); host and device answer it
+ * identically, whatever the grid or the batch of words expanded at a time.
+ *   pw_holdout_edges_device   g: a CSR handle (dense: PW_ERR_UNSUPPORTED), not modified.  w = the words of RandomState(seed)
+ *                (pw_mt_words).  directed = 1: every entry r -> c, r != c, is a unit; directed = 0: the CSR must be symmetric
+ *                (the first entry position without its mate c -> r is refused with PW_ERR_INVALID naming it, nothing written
+ *                or allocated), a unit is an entry with r < c and its mate shares its fate.  Self loops always stay.  With
+ *                protect = 1 the unit at the first non-loop entry of a row -- for an undirected unit, of either of its two
+ *                rows -- is protected: every row that had a non-loop entry keeps one.  The unit at entry position e is held
+ *                out iff w[first_word + e] < threshold and it is not protected; first_word < 2^60.
+ *                *train = the CSR of the entries not held out, in order, data carried over (pw_csr_dev_shape / _export /
+ *                pw_csr_create_device / pw_csr_dev_destroy apply; insertions, dropped and build_ms are 0); *held = the held-out
+ *                list in ascending unit position.  A later call at first_word + nnz draws an independent split.  stage_ms
+ *                (may be NULL; its synchronisations make the call a little slower): the wall clock of the word expansion, the
+ *                flag kernels, and the scans with the compactions, in ms.
+ *   pw_holdout_dev_shape    held units, units, protected units (any may be NULL)
+ *   pw_holdout_dev_fill     u, v (u < v when undirected, (r, c) when directed) and weight (the float32 of the unit's own entry,
+ *                1.0 for a graph without data) into device arrays of the handle's device with room for `held` elements
+ * Test hook on HOST pointers: pw_selftest_holdout_edges (on_device = 0: the host build of the definition, plain loops, usable
+ * without a GPU; otherwise upload, the kernels with `batch` words per expansion -- 0 = the default --, download).  data may be
+ * NULL (every weight 1.0).  out_indptr: n_nodes + 1 cells; out_indices, out_data (may be NULL), u, v, weight: room for nnz.
+ * counts = {train entries, held units, units, protected units}. */
+typedef struct pw_holdout_dev pw_holdout_dev;
+int pw_holdout_edges_device(pw_graph *g, int directed, uint32_t seed, uint64_t first_word, uint32_t threshold, int protect,
+                            pw_csr_dev **train, pw_holdout_dev **held, double stage_ms[3]);
+int pw_holdout_dev_shape(const pw_holdout_dev *h, uint64_t *held, uint64_t *units, uint64_t *protected_units);
+int pw_holdout_dev_fill(const pw_holdout_dev *h, uint32_t *d_u, uint32_t *d_v, float *d_weight);
+void pw_holdout_dev_destroy(pw_holdout_dev *h);
+int pw_selftest_holdout_edges(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, const float *data,
+                              uint32_t n_nodes, int directed, uint32_t seed, uint64_t first_word, uint32_t threshold, int protect,
+                              uint64_t batch, uint32_t *out_indptr, uint32_t *out_indices, float *out_data, uint32_t *u,
+                              uint32_t *v, float *weight, uint64_t counts[4]);
+
 /* ---- random stream service (host side; usable without a GPU) ---------------------------- */
 /* doubles #offset.. of RandomState(seed).random_sample, produced with MT19937 jump-ahead. */
 int pw_mt_random_sample(uint32_t seed, uint64_t offset, uint64_t n, double *out);

@@ -329,7 +329,14 @@ SYMBOLS = {
     "pw_selftest_auc": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pw_selftest_sample_non_edges": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                                C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
-    "pw_selftest_format_f6": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pw_holdout_edges_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), _f64p]),
+    "pw_holdout_dev_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3),
+    "pw_holdout_dev_fill": (C.c_int, [C.c_void_p] * 4),
+    "pw_holdout_dev_destroy": (None, [C.c_void_p]),
+    "pw_selftest_holdout_edges": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64,
+                                            C.c_uint32, C.c_int, C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]),
+    "pw_selftest_format_f6":(C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pw_selftest_exclusive_scan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pw_mt_random_sample": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pw_stream_sample_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -10,6 +10,9 @@ the text made in device memory; ``PECANPY_AMD_DUMP_WALKS=1`` does the same throu
 ``--task neighbours`` takes an embedding file as ``--input`` and writes the nearest neighbours of its nodes (``embed.KnnIndex``).
 ``--task score`` takes an embedding file as ``--input`` and writes the score of every pair of ``--pairs``; with ``--neg_pairs`` it
 also prints the exact AUC of the two sets of scores (``linkpred``).
+``--task split`` holds out a seeded share of the graph's edges on the GPU (``Base.holdout_edges``): the train graph goes to
+``--output`` as a CSR ``.npz``, the held-out pairs to ``--pairs`` and, with ``--neg_pairs``, as many non-edges of the original graph
+there -- the files ``--task score`` reads.  ``split``, a normal run on the train ``.npz``, ``score``: the link-prediction protocol.
 The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
@@ -30,12 +33,13 @@ MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "Sp
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
     ("--output", dict(required=True, help="embedding file (.npz -> IDs/data arrays, else word2vec text)")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score"),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score", "split"),
                     help="run node2vec; only convert the edge list to CSR / dense .npz; (walks) generate the walks and "
                          "write them, one per line, to --output, no training; (train) train embeddings from a walk "
                          "corpus file given as --input, no graph; or (neighbours) the nearest neighbours of the nodes of an "
                          "embedding file given as --input, no graph; or (score) the score of every node pair of --pairs by an "
-                         "embedding file given as --input, no graph")),
+                         "embedding file given as --input, no graph; or (split) hold out --holdout_fraction of the edges of the "
+                         "graph: the train graph as a CSR .npz to --output, the held-out pairs to --pairs")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
     ("--walk-length", dict(type=int, default=80, help="steps per walk")),
@@ -68,9 +72,13 @@ _OPTIONS = (
     ("--topn", dict(type=int, default=10, help="--task neighbours: neighbours per query")),
     ("--metric", dict(default="cosine", choices=("cosine", "dot"), help="--task neighbours / score: the score")),
     ("--queries", dict(default=None, metavar="FILE", help="--task neighbours: one node ID per line (default: every node)")),
-    ("--pairs", dict(default=None, metavar="FILE", help="--task score: two node IDs per line, separated by --delimiter")),
+    ("--pairs", dict(default=None, metavar="FILE", help="--task score: two node IDs per line, separated by --delimiter; "
+                                                        "--task split: receives the held-out pairs in that form")),
     ("--neg_pairs", dict(default=None, metavar="FILE",
-                         help="--task score: negative pairs in the same form; prints 'auc wins ties m n' of --pairs against them")),
+                         help="--task score: negative pairs in the same form; prints 'auc wins ties m n' of --pairs against them; "
+                              "--task split: receives as many non-edges of the original graph as there are held-out pairs")),
+    ("--holdout_fraction", dict(type=float, default=0.5, help="--task split: the share of the edges to hold out, in [0, 1)")),
+    ("--no_protect", dict(action="store_true", help="--task split: do not keep the first edge of every node in the train graph")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
     ("--implicit_ids", dict(action="store_true", help=".npz without IDs: use 0..N-1")),
 )
@@ -85,8 +93,8 @@ def parse_args(argv=None):
     for flag, kw in _OPTIONS:
         parser.add_argument(flag, **kw)
     args = parser.parse_args(argv)
-    if args.task == "score" and not args.pairs:
-        parser.error("--task score needs --pairs")
+    if args.task in ("score", "split") and not args.pairs:
+        parser.error(f"--task {args.task} needs --pairs")
     return args
 
 
@@ -424,6 +432,30 @@ def score_from_file(args):
         print(f"{result[0]!r} {result[1]} {result[2]} {len(nu)} {len(neg[0])}")
 
 
+def _write_pairs(path, delimiter, ids, u, v):
+    with open(path, "w", encoding="utf-8", newline="\n") as f:
+        f.write("".join(f"{ids[a]}{delimiter}{ids[b]}\n" for a, b in zip(u.cpu().tolist(), v.cpu().tolist())))
+
+
+@Timer("hold out edges + write the train graph and the pairs")
+def split_to_files(args, g):
+    """``--task split``: ``Base.holdout_edges`` with ``--holdout_fraction``, the seed ``--random_state`` (0 when not given), each
+    entry a unit with ``--directed``, no protection with ``--no_protect``.  ``--output`` gets the train graph as ``tocsr`` writes a
+    CSR (``IDs`` / ``data`` / ``indptr`` / ``indices``), ``--pairs`` the held-out pairs as node IDs, one pair per line with
+    ``--delimiter``, and ``--neg_pairs`` equally many non-edges of the ORIGINAL graph from the same seed
+    (``Base.sample_non_edges``): what ``--task score`` reads."""
+    seed = args.random_state or 0
+    train, (u, v, _), _ = g.holdout_edges(args.holdout_fraction, seed, directed=args.directed, protect=not args.no_protect)
+    train.save(args.output)
+    _write_pairs(args.pairs, args.delimiter, g.nodes, u, v)
+    if args.neg_pairs:
+        nu, nv, _ = g.sample_non_edges(int(u.numel()), seed)
+        _write_pairs(args.neg_pairs, args.delimiter, g.nodes, nu, nv)
+    if args.verbose:
+        print(f"held out {g.last_holdout_stats['held']} of {g.last_holdout_stats['units']} edges "
+              f"({g.last_holdout_stats['protected']} protected)")
+
+
 def main(argv=None):
     """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings; ``--task
     neighbours``: embedding file -> nearest neighbours."""
@@ -440,6 +472,9 @@ def main(argv=None):
         return
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)
+    if args.task == "split":
+        split_to_files(args, g)
+        return
     preprocess(g)
     if args.task == "walks":
         walks_to_file(args, g)

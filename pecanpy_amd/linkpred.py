@@ -7,8 +7,16 @@ answer identically, bit for bit and integer for integer.
         nu, nv, used = g.sample_non_edges(len(eu), seed=7)       # g: SparseOTF / PreComp / ...
         value, wins, ties = linkpred.auc(pos, index.score_pairs(nu, nv, metric="dot"))
 
-``score_pairs_host``, ``auc_host`` and ``sample_non_edges_host`` state the three definitions in NumPy, to be checked by eye;
-tests/test_linkpred_host.py and tests/test_gpu_linkpred.py hold the library to them.  There is no CPU fallback: without a GPU
+``holdout_edges`` (csrc/holdout.hip.h) is the stage in front of them: a seeded split of a sparse graph into a train graph and
+held-out pairs, in device memory, so that graph -> split -> walks -> vectors -> scores -> AUC is a function of ``(graph, seed,
+fraction)``:
+
+        train, (eu, ev, ew), used = g.holdout_edges(0.5, seed=7)    # train: a graph of g's class, its walk handle installed
+        nu, nv, _ = g.sample_non_edges(len(eu), seed=7, ...)        # negatives from the ORIGINAL graph g, not from train
+
+``score_pairs_host``, ``auc_host``, ``sample_non_edges_host`` and ``holdout_edges_host`` state the definitions in NumPy, to be
+checked by eye; tests/test_linkpred_host.py, tests/test_gpu_linkpred.py, tests/test_holdout_host.py and
+tests/test_gpu_holdout.py hold the library to them.  There is no CPU fallback: without a GPU
 the device entry points raise ``PwError`` as every other one does."""
 import ctypes as C
 from fractions import Fraction
@@ -18,7 +26,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["score_pairs", "auc", "sample_non_edges", "link_auc", "score_pairs_host", "auc_host", "sample_non_edges_host",
-           "candidate_cap"]
+           "candidate_cap", "holdout_edges", "holdout_edges_host", "holdout_threshold"]
 
 
 def _check_value(rc):
@@ -176,6 +184,74 @@ def sample_non_edges_host(indptr, indices, m, seed, first_candidate=0):
     return np.array(us, dtype=np.uint32), np.array(vs, dtype=np.uint32), c
 
 
+def holdout_threshold(fraction):
+    """``int(Fraction(fraction) * 2**32)`` for ``0 <= fraction < 1``: the uint32 a stream word is compared with.  Exact integer
+    arithmetic (a float is taken for the binary fraction it is), no float multiply."""
+    f = Fraction(fraction)
+    if not 0 <= f < 1:
+        raise ValueError(f"fraction must lie in [0, 1), not {fraction!r}")
+    return int(f * 2 ** 32)
+
+
+def holdout_edges_host(indptr, indices, data, fraction, seed, directed=False, protect=True, first_word=0):
+    """The plain-loop statement of the edge hold-out: ``((train_indptr, train_indices, train_data), (u, v, weight),
+    words_used)``.  ``data`` may be ``None`` (every weight 1.0).
+
+    With ``w`` the tempered words of ``RandomState(seed)`` (``pw_mt_words``) and ``threshold = holdout_threshold(fraction)``:
+    a UNIT is an entry ``r -> c`` with ``r != c`` of a directed graph, and an entry with ``r < c`` of an undirected one, whose
+    mate ``c -> r`` must exist (``ValueError`` naming the first entry position without one) and shares its fate.  Self loops
+    stay.  With ``protect`` a unit is protected when it sits at the first non-loop entry of its row -- for an undirected unit:
+    of either of its two rows, the mate's position counting for the lower one -- so every row that had a non-loop entry keeps
+    one.  The unit at entry position ``e`` is held out iff ``w[first_word + e] < threshold`` and it is not protected.  The
+    train CSR keeps every other entry in order; the list has the held units in ascending position, ``weight`` the unit's own
+    entry's; ``words_used = nnz``.  ``holdout_edges_host.last_stats``: ``units`` and ``protected`` of the last call."""
+    indptr, indices = np.asarray(indptr).astype(np.int64), np.asarray(indices).astype(np.int64)
+    n = indptr.size - 1
+    nnz = int(indptr[n])
+    weights = np.ones(nnz, dtype=np.float32) if data is None else np.asarray(data, dtype=np.float32)
+    threshold = holdout_threshold(fraction)
+    words = np.zeros(nnz, dtype=np.uint32)
+    if nnz:
+        _lib.check(_lib.load().pw_mt_words(int(seed) & 0xFFFFFFFF, int(first_word), nnz, C.c_void_p(words.ctypes.data)))
+    row_of = np.repeat(np.arange(n), np.diff(indptr))
+    position = {(int(row_of[e]), int(indices[e])): e for e in range(nnz)}
+
+    def first(r):   # the position of the first non-loop entry of row r, None when there is none
+        s = int(indptr[r])
+        if s < indptr[r + 1] and indices[s] == r:
+            s += 1
+        return s if s < indptr[r + 1] else None
+
+    keep, held, units, protected = np.ones(nnz, dtype=bool), [], 0, 0
+    for e in range(nnz):
+        r, c = int(row_of[e]), int(indices[e])
+        if r == c:
+            continue
+        if directed:
+            mate, safe = None, e == first(r)
+        else:
+            mate = position.get((c, r))
+            if mate is None:
+                raise ValueError(f"the CSR is not symmetric: the entry at position {e} has no mate")
+            if r > c:
+                continue
+            safe = e == first(r) or mate == first(c)
+        safe = bool(protect) and safe
+        units += 1
+        protected += int(safe)
+        if int(words[e]) < threshold and not safe:
+            held.append(e)
+            keep[e] = False
+            if mate is not None:
+                keep[mate] = False
+    train_indptr = np.zeros(n + 1, dtype=np.uint32)
+    train_indptr[1:] = np.cumsum(np.bincount(row_of[keep], minlength=n)) if nnz else 0
+    held = np.array(held, dtype=np.int64)
+    holdout_edges_host.last_stats = {"units": units, "protected": protected}
+    return ((train_indptr, indices[keep].astype(np.uint32), weights[keep]),
+            (row_of[held].astype(np.uint32), indices[held].astype(np.uint32), weights[held]), nnz)
+
+
 # ---- the device entry points -------------------------------------------------------------------------------------------
 def score_pairs(index, u, v, metric="cosine", other=None):
     """``KnnIndex.score_pairs``: a float64 ``[m]`` tensor on the index's device, ``score(A[u[i]], B[v[i]])`` with ``A`` the index's
@@ -262,6 +338,67 @@ def sample_non_edges(graph, m, seed, first_candidate=0):
     _check_value(_lib.load().pw_sample_non_edges_device(eng._h, int(seed) & 0xFFFFFFFF, int(first_candidate), m, C.c_void_p(d_u.data_ptr()),
                                                         C.c_void_p(d_v.data_ptr()), C.byref(used)))
     return d_u.to(torch.int64) & 0xFFFFFFFF, d_v.to(torch.int64) & 0xFFFFFFFF, int(used.value)
+
+
+def holdout_edges(graph, fraction, seed, directed=False, protect=True, first_word=0):
+    """``Base.holdout_edges``: ``(train_graph, (u, v, weight), words_used)`` -- a seeded split of a sparse graph's edges on the GPU
+    (``pw_holdout_edges_device``; ``holdout_edges_host`` states the rule).  Each edge -- each undirected edge once, both of its
+    entries together; ``directed=True``: each entry -- is held out when its word of ``seed``'s stream lies below ``fraction``,
+    unless ``protect`` keeps it as the first non-loop entry of a row: no vertex that had an edge loses all of them.
+
+    ``train_graph`` is an object of ``graph``'s class with the same ``p``, ``q``, ``workers``, ``extend``, ``gamma``,
+    ``random_state``, device and node IDs, its host ``indptr`` / ``indices`` / ``data`` filled from the device CSR and the walk
+    handle installed: its first ``simulate_walks`` uploads nothing.  ``u``, ``v`` (int64; ``u < v`` unless ``directed``) and
+    ``weight`` (float32) are tensors on the graph's device in ascending entry position, directly what ``score_pairs`` takes.
+    ``words_used`` added to ``first_word`` draws an independent split in a later call.  ``graph`` is not modified;
+    ``graph.last_holdout_stats`` records the counts and the stage times.
+
+    NEGATIVES come from ``sample_non_edges`` of the ORIGINAL graph: the train graph's non-edges include the held-out edges.
+    Dense graphs: ``NotImplementedError``; an undirected call on a CSR that is not symmetric: ``ValueError``."""
+    import time
+
+    import torch
+
+    from .engine import WalkEngine, _csr_dev_shape, _csr_engine
+
+    eng = graph._get_engine()
+    if eng.kind != "csr":
+        raise NotImplementedError("holdout_edges needs a sparse (CSR) graph")
+    threshold = holdout_threshold(fraction)
+    words_used = int(graph.indptr[-1])
+    lib = _lib.load()
+    dev = torch.device("cuda", eng.device)
+    c, h = C.c_void_p(), C.c_void_p()
+    stage = (C.c_double * 3)()
+    t0 = time.perf_counter()
+    _check_value(lib.pw_holdout_edges_device(eng._h, int(bool(directed)), int(seed) & 0xFFFFFFFF, int(first_word), threshold, int(bool(protect)),
+                                             C.byref(c), C.byref(h), stage))
+    t1 = time.perf_counter()
+    try:
+        counts = [C.c_uint64(0) for _ in range(3)]
+        _lib.check(lib.pw_holdout_dev_shape(h, *[C.byref(x) for x in counts]))
+        held, units, protected = (int(x.value) for x in counts)
+        d_u = torch.empty(held, dtype=torch.int32, device=dev)
+        d_v = torch.empty(held, dtype=torch.int32, device=dev)
+        d_w = torch.empty(held, dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(lib.pw_holdout_dev_fill(h, C.c_void_p(d_u.data_ptr()), C.c_void_p(d_v.data_ptr()), C.c_void_p(d_w.data_ptr())))
+        n, nnz = _csr_dev_shape(lib, c)[:2]
+        t2 = time.perf_counter()
+        train_eng, _, _ = _csr_engine(WalkEngine, lib, c, n, nnz, eng.device)
+    finally:
+        lib.pw_holdout_dev_destroy(h)
+        lib.pw_csr_dev_destroy(c)
+    train = type(graph)(graph.p, graph.q, graph.workers, graph.verbose, graph.extend, graph.gamma, graph.random_state)
+    train.device = graph.device
+    train.indptr, train.indices, train.data = train_eng.csr
+    train.set_node_ids(graph.nodes)
+    train._engine = train_eng
+    train._engine_key = (train._graph_key(), train._device_index())
+    graph.last_holdout_stats = {"held": held, "units": units, "protected": protected, "train_nnz": nnz, "words_used": words_used,
+                                "expand_ms": stage[0], "flag_ms": stage[1], "scan_compact_ms": stage[2], "split_call_ms": (t1 - t0) * 1e3,
+                                "handle_ms": (time.perf_counter() - t2) * 1e3}
+    return train, (d_u.to(torch.int64) & 0xFFFFFFFF, d_v.to(torch.int64) & 0xFFFFFFFF, d_w), words_used
 
 
 def _pairs(p, name):

@@ -129,6 +129,7 @@ class Base(BaseGraph):
         self.last_embed_stats = None
         self.last_corpus_stats = None   # walks_to_file: what the call did
         self.last_build_stats = None   # from_edge_index / from_tensor: what the device build of the graph did
+        self.last_holdout_stats = None   # holdout_edges: the counts and stage times of the last split of this graph
         # the library's one-time start-up (~140 ms for the first stream it creates) runs on a helper thread beside what comes
         # next in the reference's flow -- reading the graph (cli.py:328-337) -- instead of in front of the first walk
         import os
@@ -667,6 +668,19 @@ class Base(BaseGraph):
         from . import linkpred
 
         return linkpred.sample_non_edges(self, m, seed, first_candidate)
+
+    def holdout_edges(self, fraction, seed, directed=False, protect=True, first_word=0):
+        """``(train_graph, (u, v, weight), words_used)``: a seeded split of this graph's edges on the GPU into a train graph --
+        an object of this class with the same parameters, device and node IDs, its walk handle installed -- and the held-out
+        pairs as tensors on the graph's device (``linkpred.holdout_edges``; ``linkpred.holdout_edges_host`` states the rule).
+        With ``protect`` no vertex that had an edge loses all of them.  Negatives for the held-out pairs come from
+        ``sample_non_edges`` of THIS graph, the original: the train graph's non-edges include the held-out edges.  Sparse
+        classes only: a dense one raises ``NotImplementedError``."""
+        if not isinstance(self, SparseGraph):
+            raise NotImplementedError("holdout_edges needs a sparse (CSR) graph")
+        from . import linkpred
+
+        return linkpred.holdout_edges(self, fraction, seed, directed, protect, first_word)
 
     def embed(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, verbose=False):
         """``simulate_walks`` + skip-gram (pecanpy.py:240-290): returns ``float32[num_nodes, dim]`` in node order.
