@@ -3,27 +3,15 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared
 // (-ffp-contract=off is mandatory: the reference's Numba code never fuses a*b+c, and the
 // bit-exact float chain depends on separately rounded operations.)
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <unistd.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <new>
-#include <random>
-#include <algorithm>
-#include <cerrno>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <future>
-#include <memory>
-#include <mutex>
-#include <cmath>
-#include <string>
-#include <thread>
-#include <vector>
-
+//
+// The library is this ONE translation unit.  The host driver is this file and the drv_*.hip.h pieces it includes, one topic
+// each ("Where the host code lives"): drv_core, which everything stands on, and the topics that need drv_core
+// alone.  A piece is included at its place in the text, not at the end by habit: template kernels are instantiated, and
+// drv_selftest's own kernels emitted, in the order of the text.  Every piece includes the kernel headers it uses and passes
+// `hipcc -fsyntax-only -x hip drv_X.hip.h` by itself.
+//
+// The kernel headers, in the order that fixes the order of the device code in the code object (the pieces include the ones
+// they use again: no-ops here):
 #include "../../include/pecanpy_amd.h"
 #include "aux_kernels.hip.h"
 #include "devmem.hpp"
@@ -50,373 +38,8 @@
 #include "linkpred.hip.h"
 #include "holdout.hip.h"
 
-#define PW_EXPORT extern "C" __attribute__((visibility("default")))
-
-namespace {
-
-thread_local std::string g_err;
-
-using pw::N_COUNTERS;   // (pw_graph::counters: counters.h)
-
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-
-// opt-in switches documented as NAME=1: on when set to a non-zero number (NAME=0 and an empty value leave them off)
-bool env_on(const char *name) {
-    const char *v = getenv(name);
-    return v != nullptr && atoi(v) != 0;
-}
-
-// Behaviour switches of the lane path and the call driver.  read_lane_switches() is the one place that reads them, once at
-// the top of a call (pw_simulate_device; pw_csr_create for NO_LANES) -- never kept across calls: tests set and clear them
-// between the calls of one process -- and the struct is passed down.
-struct LaneSwitches {
-    bool has_chain_tail; uint64_t chain_tail;   // PECANPY_AMD_CHAIN_TAIL=<walks>: set at all, its number
-    bool no_chain_queue;                     // PECANPY_AMD_NO_CHAIN_QUEUE (set at all)
-    int lane_chains;                         // PECANPY_AMD_LANE_CHAINS=0/1: -1 when unset
-    uint64_t late_chains;                    // PECANPY_AMD_LATE_CHAINS=<resumed walks per resident lane> (default 16; 0: never)
-    bool verify_tight, verify_tight_poison;  // PECANPY_AMD_VERIFY_TIGHT (set at all), =poison
-    uint32_t verify_sample;                  // PECANPY_AMD_VERIFY_SAMPLE=N as given (default 1024; 0: off)
-    bool verify_sample_poison;               // PECANPY_AMD_VERIFY_SAMPLE_POISON (set at all)
-    bool has_verify_cap; uint64_t verify_cap;   // PECANPY_AMD_VERIFY_CAP=<records>: set at all, its number
-    bool no_lanes, no_wlanes, no_twin, force_tot;   // PECANPY_AMD_NO_LANES / _NO_WLANES / _NO_TWIN / _FORCE_TOT (set at all)
-    bool debug_rounds;                       // PW_DEBUG_ROUNDS (set at all)
-};
-
-LaneSwitches read_lane_switches() {
-    const char *tail = getenv("PECANPY_AMD_CHAIN_TAIL"), *chains = getenv("PECANPY_AMD_LANE_CHAINS"), *late = getenv("PECANPY_AMD_LATE_CHAINS");
-    const char *tight = getenv("PECANPY_AMD_VERIFY_TIGHT"), *sample = getenv("PECANPY_AMD_VERIFY_SAMPLE"), *cap = getenv("PECANPY_AMD_VERIFY_CAP");
-    LaneSwitches sw;
-    sw.has_chain_tail = tail != nullptr;   sw.chain_tail = tail ? (uint64_t)strtoull(tail, nullptr, 10) : 0;
-    sw.no_chain_queue = getenv("PECANPY_AMD_NO_CHAIN_QUEUE") != nullptr;
-    sw.lane_chains = chains ? (atoi(chains) != 0 ? 1 : 0) : -1;
-    sw.late_chains = late ? (uint64_t)strtoull(late, nullptr, 10) : 16ull;
-    sw.verify_tight = tight != nullptr;    sw.verify_tight_poison = tight && strcmp(tight, "poison") == 0;
-    sw.verify_sample = sample ? (uint32_t)strtoul(sample, nullptr, 10) : 1024u;
-    sw.verify_sample_poison = getenv("PECANPY_AMD_VERIFY_SAMPLE_POISON") != nullptr;
-    sw.has_verify_cap = cap != nullptr;    sw.verify_cap = cap ? (uint64_t)strtoull(cap, nullptr, 10) : 0;
-    sw.no_lanes = getenv("PECANPY_AMD_NO_LANES") != nullptr;   sw.no_wlanes = getenv("PECANPY_AMD_NO_WLANES") != nullptr;
-    sw.no_twin = getenv("PECANPY_AMD_NO_TWIN") != nullptr;     sw.force_tot = getenv("PECANPY_AMD_FORCE_TOT") != nullptr;
-    sw.debug_rounds = getenv("PW_DEBUG_ROUNDS") != nullptr;
-    return sw;
-}
-
-// The weighted lane form takes a job array only when its rounds have a queue -- the in-place form can do nothing with a
-// step it cannot decide (first steps included) but hand the walk to walk_kernel: more walks than the tail at which its
-// rounds stop queueing (PECANPY_AMD_CHAIN_TAIL, or WLANES_TAIL: plan_lane_call), and not with PECANPY_AMD_NO_CHAIN_QUEUE.
-constexpr uint64_t WLANES_TAIL = 8192;
-bool wlanes_worth(const LaneSwitches &sw, uint64_t n_jobs) {
-    return n_jobs > (sw.has_chain_tail ? sw.chain_tail : WLANES_TAIL) && !sw.no_chain_queue;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess)                                                                  \
-            return fail(PW_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
-    } while (0)
-
-using pw::DevBuf;      // (devmem.hpp: every device allocation of this file lives in one, pinned host memory in a PinnedBuf)
-using pw::PinnedBuf;
-
-// scratch that is reused across calls: grown on demand, PW_ERR_NOMEM when the device has no room for it
-template <typename T> int grow(DevBuf<T> &b, size_t n) {
-    const hipError_t e = b.ensure(n);
-    return e == hipSuccess ? 0 : fail(PW_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-}
-
-// the one device check of every entry that takes a device index
-int check_device(int device) {
-    const int n = pw_device_count();
-    if (n <= 0) return fail(PW_ERR_NO_DEVICE, "no HIP device visible (libpecanpy_amd needs a GPU; there is no CPU fallback)");
-    if (device < 0 || device >= n) return fail(PW_ERR_INVALID, "device index out of range");
-    return 0;
-}
-
-}  // namespace
-
-// The scalar description of a graph: pw_graph_replicate copies it in one assignment.
-struct GraphDesc {
-    int kind = 0;  // 0 = CSR, 1 = dense
-    uint32_t n_nodes = 0, nnz = 0;
-    bool unit = false;  // all weights are 1.0f (data not stored)
-    uint32_t max_degree = 0;
-    bool bits_only = false;          // dense graph created from packed bits: no compressed rows
-    bool dense_nonneg = false;       // weighted dense graph: every stored value is finite and > 0 (walk_dense_w.hip.h)
-    uint32_t words_per_row = 0;
-    bool has_loop = false;                              // the CSR has a self loop (unit graphs: lists fixed up, wave kernel's lazy step off)
-    bool lanes_off = false;                             // PECANPY_AMD_NO_LANES was set when the handle was created: the index is
-                                                        // built (the wave kernel's lazy step reads it) but the lane kernel is not used
-    bool vlines = false;                                // lines[nnz + v]: the line of vertex v's mirrored overflow read
-    uint64_t clist_bytes = 0, line_bytes = 0;
-    uint64_t n_clist = 0;
-    uint32_t list_max_len = 0xffffffffu;                // partial index: lists longer than this were left out (EL_NO_LIST)
-    uint64_t index_bytes = 0;                           // device bytes of the membership / lane index
-};
-
-// A graph on one device: its arrays, index and per-(p, q) tables, shared by the call contexts (pw_graph) that walk it.
-// Written only by handle creation (pw_csr_create, pw_dense_create*, pw_graph_replicate), pw_graph_set_thresholds,
-// pw_precomp_build and the lazy builders -- d_hasnbr in compute_offsets, ensure_tot_table, ensure_unit_tot,
-// ensure_wlane_tables, spp_check -- each of which writes nothing when its keys already match.  A twin context reads it
-// from another thread while the primary walks: its calls use the primary's (p, q, extend) and thresholds, so they find
-// every table in place -- or build, under those keys, one that the primary's smaller half declined and does not read.
-// Every table that reads the thresholds records the upload it was built from (*_thr_version against thr_version).
-struct GraphData : GraphDesc {
-    int device = 0;
-    DevBuf<uint32_t> d_indptr, d_indices;
-    DevBuf<uint32_t> d_hasnbr;                          // bit v: vertex v has neighbours (stream offsets; built by the first call)
-    DevBuf<void> d_data;             // float32 (CSR graphs) or float64 (dense graphs); null when unit
-    DevBuf<float> d_thr;
-    DevBuf<uint64_t> d_adjbits;      // dense graphs: bit-packed adjacency rows
-    DevBuf<uint32_t> d_deg;          // dense graphs: row degrees
-    DevBuf<uint32_t> d_foff;         // CSR graphs: per-row membership filters (offsets, bits)
-    DevBuf<uint64_t> d_fbits;
-    DevBuf<uint2> d_kf;              // CSR graphs: (neighbour id, filter word) per CSR entry
-    DevBuf<uint64_t> d_tab_off, d_slots;                // CSR graphs: adjacency index (exact lookups)
-    DevBuf<uint4> d_vrec;                               // CSR graphs: per-vertex record (row start, degree, filter, index)
-    DevBuf<pw::ELine> d_lines;                          // lane index (walk_lanes.hip.h): 64-byte edge line per CSR entry; its first 16 bytes
-                                                        // {neighbour, common-neighbour count, reverse position, degree} also serve walk_kernel's lazy step
-    DevBuf<uint8_t> d_clist;                            // lane index: the lists too long for their edge line
-    double index_build_ms = 0;                          // device time of all index KERNELS of pw_csr_create (event pairs around them)
-    double create_wall_ms = 0;                          // wall clock of pw_csr_create: runtime start-up, host passes, H2D, allocations, kernels
-    uint64_t thr_version = 0;                           // thresholds uploaded (pw_graph_set_thresholds calls)
-    DevBuf<float> d_tot_e, d_tot_v;                     // weighted CSR graphs: per-edge / per-vertex normalisers
-    double tot_p = 0, tot_q = 0;                        // ... built for these parameters
-    int tot_extend = -1;                                // -1: none yet
-    uint64_t tot_thr_version = 0;                       // thresholds uploaded since the table was built?
-    bool tot_failed = false;
-    double tot_build_ms = 0;
-    DevBuf<float> d_utot;                               // unit graphs, 1/p or 1/q not a power of two: row total per arriving line
-    float utot_wo = 0, utot_wp = 0;                     // ... built for these biases (0: none)
-    bool utot_failed = false;
-    // weighted lane form (walk_lanes.hip.h: WEIGHTED): base values, their per-row float64 prefix sums, per-entry delta prefix sums
-    DevBuf<float> d_wb;
-    DevBuf<pw::PrefixPair> d_wpq;
-    DevBuf<double> d_wdl, d_wl_dprev;
-    DevBuf<unsigned long long> d_wl_off;
-    DevBuf<uint32_t> d_wedge_row;                       // ... source vertex of every CSR entry
-    DevBuf<pw::PrefixPair> d_wp1;                       // ... per-row prefix sums of the raw weights (first steps; graph-static)
-    DevBuf<unsigned long long> d_wck_off;               // ... recorded chain values (wckpt_kernel): first record of entry e
-    DevBuf<float> d_wck;
-    double wl_p = 0, wl_q = 0;
-    int wl_extend = -1;
-    uint64_t wl_thr_version = 0;
-    bool wl_failed = false;
-    int spp_zero = -1;                                  // CSR: some stored weight is 0.0f (-1: not checked yet)
-    // alias tables (PreComp modes)
-    DevBuf<uint64_t> alias_indptr;
-    DevBuf<uint32_t> alias_j, alias_s, alias_l, edge_row;
-    DevBuf<float> alias_q;
-    uint64_t n_alias = 0;
-    int alias_kind = -1;  // -1 none, 0 second order, 1 first order
-    double alias_p = 0, alias_q_param = 0;
-    int alias_extend = 0;
-    uint64_t alias_thr_version = 0;                     // ... from this threshold upload (read by the extend tables only)
-
-    explicit GraphData(int dev) : device(dev) {}
-    GraphData(const GraphData &) = delete;
-    GraphData &operator=(const GraphData &) = delete;
-    ~GraphData() { (void)hipSetDevice(device); }   // (the members free themselves behind this body: on their own device)
-};
-
-// blocks of 312 draws from `first_block` on that cover the draws up to stream_skip + total (at least one): the one rounding
-// of expand_stream's range and of the range a hold keeps
-static uint64_t stream_blocks_from(uint64_t first_block, uint64_t stream_skip, uint64_t total) {
-    const uint64_t end_block = (stream_skip + total + 311) / 312;
-    return end_block > first_block ? end_block - first_block : 1;
-}
-
-// A call context over a graph: streams, events, counters, random stream and scratch buffers, and the state of the
-// current call.  The graph itself (gd) may be shared with a twin context.
-struct pw_graph {
-    int device = 0;
-    std::shared_ptr<GraphData> gd;
-    // TWIN (round 6): a second call context on the SAME device over the same GraphData (own streams, counters, queues, stream
-    // buffers): the weighted lane form walks the two halves of a job array on the two contexts side by side, so that one half's
-    // eager kernel runs beside the other half's lane round (simulate_twin)
-    pw_graph *twin = nullptr;
-    // INPUTS of a call, set around it by simulate_twin: not part of `call`, the driver's reset leaves them alone
-    bool twin_active = false;                           // the current call runs on both contexts: each takes a share of the GPU
-    std::function<void()> on_tables_ready;              // simulate_twin: called once the call's per-(p, q) tables are in place
-    // What one call of the driver (simulate_device_impl) keeps for its launchers and its statistics: reset by ONE assignment
-    // there, behind the validation, and read and written through this name only.
-    struct Call {
-        bool n2vpp = false;                             // the current call walks node2vec++ (walk_dense_w.hip.h)
-        bool spp = false;                               // ... node2vec++ on this CSR handle (walk_sparse_pp.hip.h)
-        bool wl_active = false;                         // the current call may run the weighted lane form (tables are there)
-        bool wl_used = false;                           // ... and did
-        double param_ms = 0;                            // (p, q)-dependent index time of the current call
-        double lane_ms = 0;                             // lane kernel time of the current call
-        uint32_t lane_rounds = 0;                       // lane kernel launches of the current call
-        uint64_t runnable = 0;                          // whole-array call: jobs whose start has neighbours (the stream's nominal draws / walk_length)
-        uint64_t ver_checked = 0, ver_mismatch = 0, ver_dropped = 0, ver_ties = 0;   // verification counts of the current call
-    } call;
-    // pw_simulate() walks a large job array in parts: the stream of the WHOLE array is expanded once, and while this is
-    // set expand_stream() serves the parts' sub-ranges from g->rng as it stands (never kept across API calls)
-    struct { bool valid = false, user = false; uint32_t seed = 0; uint64_t first_block = 0, n_blocks = 0; } rng_hold;   // (user: pw_stream_hold)
-    void drop_hold() { rng_hold.valid = false; rng_hold.user = false; }
-    // g->rng holds the draws [stream_skip, stream_skip + n_draws) of `seed`, expanded from draw `base` (expand_stream's *rng_base) on
-    void set_hold(uint32_t seed, uint64_t base, uint64_t stream_skip, uint64_t n_draws, bool user) {
-        rng_hold.valid = true;
-        rng_hold.user = user;
-        rng_hold.seed = seed;
-        rng_hold.first_block = base / 312;
-        rng_hold.n_blocks = stream_blocks_from(base / 312, stream_skip, n_draws);
-    }
-    static constexpr int N_STAGE = 12;
-    PinnedBuf<void> stage[N_STAGE];        // pinned staging buffers of pw_simulate's copy out
-    PinnedBuf<uint32_t> seed_state;        // pinned: the seed's MT19937 state on its way to the device
-    int n_cu = 0;
-    // scratch reused across calls
-    DevBuf<uint64_t> stream_off, tile_sums;
-    DevBuf<double> rng;
-    DevBuf<uint32_t> mt_state, changed, redo;
-    DevBuf<pw::SuspRec> susp[2];      // lane kernel: walks parked for the float chain (two queues, swapped per round)
-    // generator states of recent calls, keyed by (seed, first block, blocks per generator, generators): a repeated
-    // call (every pass of a benchmark, every chunk of a sharded run) skips the ~20 sequential jump-ahead launches
-    struct MtCache { bool valid = false; uint32_t seed = 0, n_gen = 0; uint64_t first_block = 0; int per_gen_log = 0; uint64_t stamp = 0;
-                     DevBuf<uint32_t> states; } mt_cache[8];
-    uint64_t mt_stamp = 0;
-    // verification mode of the lane kernel (PECANPY_AMD_VERIFY_TIGHT=1): steps the interval decision settled
-    DevBuf<pw::VerRec> ver, ver_bad;
-    DevBuf<uint32_t> ver_jobs;        // sampled verification (production): walks of mismatching records, redone by walk_kernel
-    DevBuf<uint64_t> jump_table;  // MtJump::pow2_table() on the device
-    DevBuf<uint32_t> jump_tmp;    // partial results of jumps whose taps are split over several workgroups (kept zeroed)
-    bool jump_table_ready = false;
-    DevBuf<unsigned long long> counters;  // N_COUNTERS device counters: counters.h names the slots
-    DevBuf<float> probs_scratch;
-    DevBuf<uint32_t> stream_words;   // pw_stream_words_device: raw stream words (624 per block)
-    // Streams and events LAST: members go in reverse order behind the destructor's body, so the events are destroyed first, then
-    // the streams, then the buffers above -- on this context's device (graph_common_init creates them; one that fails half way
-    // leaves what it made to this destructor)
-    pw::Stream stream;
-    pw::Stream stream2;              // side stream: the zero-fill of the walk matrix runs under the stream expansion
-    pw::Stream copy_stream;          // pw_simulate: the D2H of one part of the walk matrix runs here, under the walks of the next
-    pw::Event ev_copy[N_STAGE];
-    pw::Event ev_side;
-    std::vector<pw::Event> round_ev;       // lane rounds: a pair of events per round, read once behind the last round (no sync per round)
-    pw::Event ev[8];
-
-    ~pw_graph() { (void)hipSetDevice(device); }   // (the members release themselves behind this body: on their own device)
-};
-
-namespace {
-
-// The owner of a call context under construction: every way out of a creator but the release() into *out destroys it (a twin
-// with it).  A creator's locals go in reverse order of declaration, so where the owner stands among them decides what the
-// handle outlives: each creator says so where it declares it.
-struct GraphDeleter { void operator()(pw_graph *g) const { pw_graph_destroy(g); } };
-using GraphOwner = std::unique_ptr<pw_graph, GraphDeleter>;
-
-int set_device(const pw_graph *g) {
-    HIP_TRY(hipSetDevice(g->device));
-    return 0;
-}
-
-uint32_t os_seed() {
-    std::random_device rd;
-    return (uint32_t)rd();
-}
-
-// host emulation of seq_scan (walk_sparse.hip.h) used by the self test: identical arithmetic,
-// `chunk` elements per pass instead of one wavefront pass.
-template <typename T>
-uint32_t seqscan_emulate(const T *x, uint32_t n, double r, bool use_target, uint32_t chunk, T *sum) {
-    using B = pw::Binade<T>;
-    using U = typename B::UInt;
-    T c = (T)0;
-    uint32_t k = 0;
-    std::vector<pw::Inc<T>> f(chunk);
-    while (k < n) {
-        const int eb = B::eb_of(c);
-        const U C = B::sig_of(c);
-        const U Tt = use_target ? B::threshold(r, eb) : B::TOP;
-        uint32_t m = n - k < chunk ? n - k : chunk;
-        pw::Inc<T> run = {0, 0};
-        uint32_t first = m;
-        U Cprev = C, Cn = C;
-        for (uint32_t l = 0; l < m; l++) {
-            f[l] = B::quantize(x[k + l], eb);
-            pw::Inc<T> incl = l ? B::compose(run, f[l]) : f[l];
-            U Ci = B::apply(C, incl);
-            if (Ci >= Tt) { first = l; Cn = Ci; break; }
-            Cprev = Ci;
-            run = incl;
-        }
-        if (first == m) {
-            c = B::make(Cprev, eb);
-            k += m;
-            continue;
-        }
-        uint32_t kf = k + first;
-        if (Cn < B::TOP) { c = B::make(Cn, eb); *sum = c; return kf; }
-        c = B::make(Cprev, eb) + x[kf];
-        if (use_target && (double)c >= r) { *sum = c; return kf; }
-        k = kf + 1;
-    }
-    *sum = c;
-    return n;
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------
-PW_EXPORT const char *pw_version(void) { return "pecanpy_amd 0.1.0 (gfx950)"; }
-PW_EXPORT const char *pw_last_error(void) { return g_err.c_str(); }
-
-PW_EXPORT int pw_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-PW_EXPORT int pw_warmup(int device, double *ms) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_TRY(hipStreamDestroy(s));
-    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PW_OK;
-}
-
-PW_EXPORT void pw_graph_destroy(pw_graph *g) {
-    if (!g) return;
-    if (g->twin) { pw_graph_destroy(g->twin); g->twin = nullptr; }
-    delete g;        // (its events, streams and buffers with it, and the graph with the last context that walks it)
-}
-
-// a call context on `device` over `gd` (a twin's: the primary's graph) or over a new, empty graph
-static int graph_common_init(pw_graph *g, int device, std::shared_ptr<GraphData> gd = nullptr) {
-    const bool dbg = getenv("PECANPY_AMD_CREATE_DEBUG") != nullptr;
-    auto nowms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = nowms();
-    auto lap = [&](const char *what) { if (dbg) { const double t = nowms(); fprintf(stderr, "[create]   init: %-28s %8.2f ms\n", what, t - t0); t0 = t; } };
-    if (int rc = check_device(device)) return rc;
-    g->device = device;
-    g->gd = gd ? std::move(gd) : std::make_shared<GraphData>(device);
-    HIP_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    g->n_cu = prop.multiProcessorCount;
-    lap("device count / properties");
-    HIP_TRY(g->stream.create(hipStreamNonBlocking));
-    lap("stream");
-    HIP_TRY(g->stream2.create(hipStreamNonBlocking));
-    lap("stream2");
-    HIP_TRY(g->ev_side.create(hipEventDisableTiming));
-    for (auto &e : g->ev) HIP_TRY(e.create(hipEventDefault));
-    lap("events");
-    HIP_TRY(g->copy_stream.create(hipStreamNonBlocking));
-    for (auto &e : g->ev_copy) HIP_TRY(e.create(hipEventDisableTiming));
-    lap("copy stream + events");
-    return 0;
-}
-
-static pw::CsrDev csr_dev(const pw_graph *g);
+// the system includes, PW_EXPORT, fail / HIP_TRY, LaneSwitches, the handle structs, GraphOwner, csr_dev, graph_common_init
+#include "drv_core.hip.h"
 
 // Lane-kernel index (walk_lanes.hip.h): one 64-byte edge line per CSR entry (the record of the edge + its list of
 // common-neighbour positions when that is short) and the overflow array of the longer lists.  One set intersection per
@@ -2137,28 +1760,6 @@ PW_EXPORT int pw_count_stream_draws(pw_graph *g, const uint32_t *starts, uint64_
     if (!rc && n_jobs) rc = compute_offsets(g, d_starts.p, nullptr, walk_length, n_jobs, 0, false, &tot, nullptr);
     *out_draws = tot;
     return rc;
-}
-
-static pw::CsrDev csr_dev(const pw_graph *g) {
-    pw::CsrDev c;
-    c.indptr = g->gd->d_indptr.p;
-    c.indices = g->gd->d_indices.p;
-    c.data = g->gd->d_data.p;
-    c.thr = g->gd->d_thr.p;
-    c.adjbits = g->gd->d_adjbits.p;
-    c.foff = g->gd->d_foff.p;
-    c.fbits = g->gd->d_fbits.p;
-    c.kf = g->gd->d_kf.p;
-    c.tab_off = g->gd->d_tab_off.p;
-    c.slots = g->gd->d_slots.p;
-    c.tri = (const uint4 *)g->gd->d_lines.p;   // (stride: one 64-byte line per CSR entry)
-    c.clist = g->gd->d_clist.p;
-    c.step_edge = 0xffffffffu;
-    c.vrec = g->gd->d_vrec.p;
-    c.words_per_row = g->gd->words_per_row;
-    c.n_nodes = g->gd->n_nodes;
-    c.nnz = g->gd->nnz;
-    return c;
 }
 
 PW_EXPORT int pw_precomp_build(pw_graph *g, double p, double q, int extend, int first_order) {
@@ -4392,1116 +3993,9 @@ PW_EXPORT int pw_probs(pw_graph *g, int mode, double p, double q, int extend, ui
     return PW_OK;
 }
 
-// ---- skip-gram with negative sampling over a walk matrix (sgns.hip.h) -------------------------
-template <int PER, bool LOSS, bool LOCK>
-static void sgns_launch(unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
-    if constexpr (LOCK)
-        hipLaunchKernelGGL((pw::sgns_walk_kernel<PER, LOSS, true, uint32_t, uint32_t>), dim3(blocks), dim3(threads), lds, 0, a, a.walks,
-                           a.table, a.keep, a.lock0, a.lock1);
-    else
-        hipLaunchKernelGGL((pw::sgns_walk_kernel<PER, LOSS>), dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep);
-}
-template <bool LOSS, bool LOCK>
-static void sgns_launch_per(int per, unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
-    switch (per) {   // one instance per count of components per lane: only the last component needs a lane guard
-    case 1: sgns_launch<1, LOSS, LOCK>(blocks, threads, lds, a); break;
-    case 2: sgns_launch<2, LOSS, LOCK>(blocks, threads, lds, a); break;
-    case 3: sgns_launch<3, LOSS, LOCK>(blocks, threads, lds, a); break;
-    case 4: sgns_launch<4, LOSS, LOCK>(blocks, threads, lds, a); break;
-    case 5: sgns_launch<5, LOSS, LOCK>(blocks, threads, lds, a); break;
-    case 6: sgns_launch<6, LOSS, LOCK>(blocks, threads, lds, a); break;
-    case 7: sgns_launch<7, LOSS, LOCK>(blocks, threads, lds, a); break;
-    default: sgns_launch<8, LOSS, LOCK>(blocks, threads, lds, a); break;
-    }
-}
-// (the LOCK instances only when a row of either matrix is frozen: without locks a run is the LOCK = false kernel)
-template <bool LOSS>
-static void sgns_launch_lock(bool lock, int per, unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
-    if (lock) sgns_launch_per<LOSS, true>(per, blocks, threads, lds, a);
-    else sgns_launch_per<LOSS, false>(per, blocks, threads, lds, a);
-}
-
-// A trainer between launches: the two matrices, the tables of the vocabulary stage, the launch geometry, and where the run
-// stands (pw_sgns_state).  The walk matrix is the caller's.
-struct pw_sgns {
-    int device = 0;
-    pw::SgnsArgs a;                          // everything of a launch but item_base / lr_base / lr_total / alpha / min_alpha / counters
-    uint64_t n_items = 0;                    // n_walks * (walk_length + 1): the items of one epoch
-    uint32_t n_nodes = 0;
-    bool loss = false;
-    unsigned blocks = 1, threads = 64;
-    size_t lds = 0;
-    pw_sgns_state st;
-    double vocab_ms = 0, init_ms = 0;
-    DevBuf<float> syn0, syn1, keep;
-    DevBuf<uint32_t> table;
-    DevBuf<pw_sgns_epoch> epoch_out;         // what the launches of one pw_sgns_run leave, one cell per epoch
-    DevBuf<double> walk_loss, block_loss;    // PW_SGNS_LOSS: per walk, per SGNS_LOSS_CHUNK walks
-    DevBuf<unsigned long long> walk_evals, block_evals;
-    pw::Event ev0, ev1;                      // the pair around the training launches of a run
-    float sample = 0;                        // of the create call: what PW_SGNS_RECOUNT rebuilds the keep probabilities with
-    unsigned n_cus = 1;
-    // pw_sgns_evaluate: its own per-walk and per-block cells (sized by the matrix it scores) and its record
-    DevBuf<double> eval_walk_loss, eval_block_loss;
-    DevBuf<unsigned long long> eval_walk_evals, eval_block_evals;
-    DevBuf<pw_sgns_epoch> eval_out;
-    // pw_sgns_set_locks: the frozen rows of syn0 / syn1 as bits (a.lock0 / a.lock1 point here); not allocated = no row frozen
-    DevBuf<uint32_t> lock0, lock1;
-    uint64_t n_locked[2] = {0, 0};
-    bool ran_locked = false;                 // the last pw_sgns_run launched the LOCK instances
-};
-static_assert(offsetof(pw_sgns_epoch, kept_occurrences) + sizeof(uint64_t) == offsetof(pw_sgns_epoch, trained_pairs),
-              "the kernel's two counters are consecutive cells of an epoch's record");
-
-// The vocabulary stage of a walk matrix.  The device check first: a node id >= n_nodes or a length cell > walk_length + 1 is
-// PW_ERR_INVALID with the text every entry that takes a matrix shares.  With `out`, word2vec's unigram^0.75 table and the
-// subsampling probabilities from the word counts of that pass, uploaded; without it the check alone.
-struct SgnsVocab {
-    DevBuf<uint32_t> table;
-    DevBuf<float> keep;                      // (not allocated with sample = 0)
-    uint32_t table_size = 0;
-};
-static int sgns_vocabulary(const uint32_t *d_walks, uint64_t n_walks, uint32_t L, uint32_t n_nodes, float sample, SgnsVocab *out) {
-    DevBuf<unsigned long long> cnt_buf;
-    // d_cnt: [0, n_nodes) word counts, [n_nodes] first bad walk
-    hipError_t e = cnt_buf.alloc((size_t)n_nodes + 1);
-    unsigned long long *const d_cnt = cnt_buf.p;
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(unsigned long long) * (size_t)n_nodes);
-    if (e == hipSuccess) e = hipMemset(d_cnt + n_nodes, 0xff, sizeof(unsigned long long));
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    // vocabulary statistics (and the check that the matrix only names nodes of the vocabulary)
-    const uint64_t n_items = n_walks * (uint64_t)(L + 1);
-    hipLaunchKernelGGL(pw::sgns_count_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, 0, d_walks, n_walks, L, n_nodes, d_cnt,
-                       d_cnt + n_nodes);
-    std::vector<unsigned long long> cnt((size_t)n_nodes + 1);
-    const size_t first = out ? 0 : n_nodes;   // (the check alone: only its cell comes down)
-    e = hipMemcpy(cnt.data() + first, d_cnt + first, sizeof(unsigned long long) * ((size_t)n_nodes + 1 - first), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    if (cnt[n_nodes] != ~0ull)
-        return fail(PW_ERR_INVALID, "walk " + std::to_string(cnt[n_nodes]) + ": node id >= n_nodes or length cell > walk_length + 1");
-    if (!out) return PW_OK;
-    double total = 0, pow_total = 0;
-    for (uint32_t i = 0; i < n_nodes; i++) { total += (double)cnt[i]; pow_total += std::pow((double)cnt[i], 0.75); }
-    if (!(total > 0)) return fail(PW_ERR_INVALID, "the walk matrix holds no nodes");
-    // word2vec's unigram^0.75 table (a word that never occurs owns no slot) and subsampling probabilities
-    const uint32_t table_size = (uint32_t)std::min<uint64_t>(1ull << 26, std::max<uint64_t>(1ull << 16, 16ull * n_nodes));
-    std::vector<uint32_t> table(table_size);
-    {
-        uint32_t t = 0, last = 0;
-        double cum = 0;
-        for (uint32_t w = 0; w < n_nodes; w++) {
-            if (!cnt[w]) continue;
-            last = w;
-            cum += std::pow((double)cnt[w], 0.75) / pow_total;
-            while (t < table_size && (double)(t + 1) / table_size <= cum) table[t++] = w;
-        }
-        while (t < table_size) table[t++] = last;   // (rounding of the last share)
-    }
-    std::vector<float> keep;
-    if (sample > 0) {
-        keep.resize(n_nodes);
-        const double thr = (double)sample * total;
-        for (uint32_t i = 0; i < n_nodes; i++)
-            keep[i] = cnt[i] ? (float)std::min(1.0, (std::sqrt((double)cnt[i] / thr) + 1.0) * thr / (double)cnt[i]) : 1.0f;
-    }
-    e = out->table.alloc(table_size);
-    if (e == hipSuccess) e = hipMemcpy(out->table.p, table.data(), sizeof(uint32_t) * (size_t)table_size, hipMemcpyHostToDevice);
-    if (e == hipSuccess && sample > 0) {
-        e = out->keep.alloc(n_nodes);
-        if (e == hipSuccess) e = hipMemcpy(out->keep.p, keep.data(), sizeof(float) * (size_t)n_nodes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    out->table_size = table_size;
-    return PW_OK;
-}
-
-PW_EXPORT int pw_sgns_create_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
-                                    uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
-                                    float sample, uint32_t seed, uint32_t workers, uint32_t flags, pw_sgns **out) {
-    if (!out) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    *out = nullptr;
-    if (!d_walks || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
-    if (window == 0 || epochs == 0) return fail(PW_ERR_INVALID, "window and epochs must be positive");
-    if (flags & ~(uint32_t)PW_SGNS_LOSS) return fail(PW_ERR_INVALID, "unknown flag");
-    const uint32_t L = walk_length;
-    // the survivors of a walk live in the wavefront's LDS: four wavefronts to a workgroup while that fits, else one
-    const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
-    if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
-    const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-    const size_t vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    std::unique_ptr<pw_sgns> s(new pw_sgns);
-    s->device = device; s->n_nodes = n_nodes; s->loss = (flags & PW_SGNS_LOSS) != 0; s->sample = sample;
-    auto t_vocab = clk::now();
-    hipError_t e = s->syn0.alloc((size_t)n_nodes * dim);
-    if (e == hipSuccess) e = s->syn1.alloc((size_t)n_nodes * dim);
-    if (e == hipSuccess) e = hipMemset(s->syn1.p, 0, vbytes);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    const uint64_t n_items = n_walks * (uint64_t)(L + 1);
-    SgnsVocab vocab;
-    if (int rc = sgns_vocabulary(d_walks, n_walks, L, n_nodes, sample, &vocab)) return rc;
-    const uint32_t table_size = vocab.table_size;
-    s->table = std::move(vocab.table);
-    s->keep = std::move(vocab.keep);
-    s->vocab_ms = ms_since(t_vocab);
-    // syn0 ~ U(-0.5, 0.5) / dim (word2vec.c), seeded
-    auto t_init = clk::now();
-    {
-        std::vector<float> init((size_t)n_nodes * dim);
-        uint64_t x = 0x9E3779B97F4A7C15ull ^ ((uint64_t)seed << 17);
-        for (auto &f : init) {
-            x = x * 6364136223846793005ull + 1442695040888963407ull;
-            f = (((float)((x >> 40) & 0xffffff) / 16777216.0f) - 0.5f) / (float)dim;
-        }
-        e = hipMemcpy(s->syn0.p, init.data(), vbytes, hipMemcpyHostToDevice);
-    }
-    hipDeviceProp_t prop;
-    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = s->ev0.create(hipEventDefault);
-    if (e == hipSuccess) e = s->ev1.create(hipEventDefault);
-    if (e == hipSuccess && s->loss) {
-        const size_t n_blocks = (size_t)((n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
-        e = s->walk_loss.alloc(n_walks);
-        if (e == hipSuccess) e = s->walk_evals.alloc(n_walks);
-        if (e == hipSuccess) e = s->block_loss.alloc(n_blocks);
-        if (e == hipSuccess) e = s->block_evals.alloc(n_blocks);
-    }
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    s->init_ms = ms_since(t_init);
-    pw::SgnsArgs &a = s->a;
-    a.walks = d_walks; a.n_walks = n_walks; a.L = L; a.dim = dim; a.window = window; a.negative = negative;
-    a.syn0 = s->syn0.p; a.syn1 = s->syn1.p; a.table = s->table.p; a.table_size = table_size; a.keep = s->keep.p;
-    a.alpha = alpha; a.min_alpha = min_alpha; a.item_base = 0; a.lr_base = 0; a.lr_total = n_items * epochs; a.seed = seed;
-    a.counters = nullptr; a.walk_loss = s->walk_loss.p; a.walk_evals = s->walk_evals.p;
-    a.lock0 = a.lock1 = nullptr;
-    s->n_items = n_items;
-    s->st.epoch = 0; s->st.sched_pos = 0; s->st.sched_total = epochs; s->st.alpha = alpha; s->st.min_alpha = min_alpha;
-    // concurrency.  workers == 1: ONE wavefront takes the walks in order (deterministic: the run gensim's workers=1
-    // corresponds to; compared with oracle/sgns_ref.c).  workers == 0: as many wavefronts as keep hogwild collisions
-    // rare -- far more wavefronts than vocabulary rows in flight would overwrite most updates of a small graph.  The rule
-    // "at least ~256 items per wavefront, at most 8 workgroups per CU" is now counted in walks: a wavefront owns at least
-    // ceil(256 / (L + 1)) walks (4 for the default 80-step walks), and the cap is 32 wavefronts per CU whatever the
-    // workgroup size.  workers > 1: that many wavefronts (rounded up to whole workgroups).
-    unsigned blocks, threads = 64 * waves_per_block;
-    if (workers == 1) { blocks = 1; threads = 64; }
-    else if (workers > 1) blocks = (workers + waves_per_block - 1) / waves_per_block;
-    else {
-        const uint64_t walks_per_wave = (256 + (uint64_t)L) / ((uint64_t)L + 1);
-        const uint64_t want_waves = (n_walks + walks_per_wave - 1) / walks_per_wave;
-        const uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>(want_waves, (uint64_t)prop.multiProcessorCount * 32));
-        blocks = (unsigned)((waves + waves_per_block - 1) / waves_per_block);
-    }
-    s->blocks = blocks; s->threads = threads; s->n_cus = (unsigned)std::max(1, prop.multiProcessorCount);
-    s->lds = lds_wave * (threads / 64);
-    a.n_waves = blocks * (threads / 64);
-    *out = s.release();
-    return PW_OK;
-}
-
-PW_EXPORT int pw_sgns_run(pw_sgns *s, uint32_t n_epochs, pw_sgns_epoch *per_epoch, pw_sgns_stats *stats) {
-    if (!s) return fail(PW_ERR_INVALID, "null pointer");
-    if (n_epochs == 0) return fail(PW_ERR_INVALID, "n_epochs must be positive");
-    if (s->st.sched_pos + n_epochs > s->st.sched_total)   // (before any launch)
-        return fail(PW_ERR_INVALID, "the schedule has " + std::to_string(s->st.sched_total - s->st.sched_pos) + " of " +
-                                        std::to_string(s->st.sched_total) + " epochs left, " + std::to_string(n_epochs) + " asked for");
-    HIP_TRY(hipSetDevice(s->device));
-    hipError_t e = s->epoch_out.ensure(n_epochs);
-    if (e == hipSuccess) e = hipMemset(s->epoch_out.p, 0, sizeof(pw_sgns_epoch) * (size_t)n_epochs);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    pw::SgnsArgs a = s->a;
-    a.alpha = s->st.alpha; a.min_alpha = s->st.min_alpha; a.lr_total = s->n_items * s->st.sched_total;
-    const int per = (int)((a.dim + 63) / 64);
-    const unsigned n_blocks = (unsigned)((a.n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
-    const bool lock = a.lock0 || a.lock1;
-    s->ran_locked = lock;
-    (void)hipEventRecord(s->ev0, 0);
-    for (uint32_t i = 0; i < n_epochs; i++) {
-        a.item_base = s->n_items * (s->st.epoch + i);
-        a.lr_base = s->n_items * (s->st.sched_pos + i);
-        pw_sgns_epoch *cell = s->epoch_out.p + i;
-        a.counters = (unsigned long long *)&cell->kept_occurrences;
-        if (!s->loss) sgns_launch_lock<false>(lock, per, s->blocks, s->threads, s->lds, a);
-        else {
-            sgns_launch_lock<true>(lock, per, s->blocks, s->threads, s->lds, a);
-            hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(n_blocks), dim3(256), 0, 0, s->walk_loss.p, s->walk_evals.p, a.n_walks,
-                               (uint64_t)pw::SGNS_LOSS_CHUNK, s->block_loss.p, s->block_evals.p);
-            hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(1), dim3(256), 0, 0, s->block_loss.p, s->block_evals.p, (uint64_t)n_blocks,
-                               (uint64_t)n_blocks, &cell->loss, (unsigned long long *)&cell->evaluations);
-        }
-    }
-    (void)hipEventRecord(s->ev1, 0);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    // (the launches were queued: whatever the outcome, the vectors have moved on by what ran)
-    s->st.epoch += n_epochs; s->st.sched_pos += n_epochs;
-    float train_ms = 0;
-    std::vector<pw_sgns_epoch> got(n_epochs);
-    if (e == hipSuccess) e = hipEventElapsedTime(&train_ms, s->ev0, s->ev1);
-    if (e == hipSuccess) e = hipMemcpy(got.data(), s->epoch_out.p, sizeof(pw_sgns_epoch) * (size_t)n_epochs, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    if (per_epoch) std::copy(got.begin(), got.end(), per_epoch);
-    if (stats) {
-        stats->vocab_ms = s->vocab_ms; stats->init_ms = s->init_ms; stats->train_ms = train_ms;
-        stats->kept_occurrences = stats->trained_pairs = 0;
-        for (const pw_sgns_epoch &g : got) { stats->kept_occurrences += g.kept_occurrences; stats->trained_pairs += g.trained_pairs; }
-        stats->wavefronts = (uint64_t)s->blocks * (s->threads / 64);
-    }
-    return PW_OK;
-}
-
-template <int PER>
-static void sgns_eval_launch(unsigned blocks, unsigned threads, size_t lds, const pw::SgnsArgs &a) {
-    hipLaunchKernelGGL((pw::sgns_eval_kernel<PER>), dim3(blocks), dim3(threads), lds, 0, a, a.walks, a.table, a.keep, a.syn0, a.syn1);
-}
-
-// Scores a walk matrix with the vectors as they are (sgns.hip.h: sgns_eval_kernel); nothing of the session changes.
-PW_EXPORT int pw_sgns_evaluate(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint64_t epoch,
-                               pw_sgns_epoch *out) {
-    if (!s || !out) return fail(PW_ERR_INVALID, "null pointer");
-    const bool own = d_walks == nullptr;
-    if (own) { d_walks = s->a.walks; n_walks = s->a.n_walks; walk_length = s->a.L; }
-    if (!n_walks) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    const uint32_t L = walk_length;
-    const size_t lds_limit = 64 << 10, lds_wave = pw::sgns_lds_bytes_per_wave(L);
-    if (lds_wave > lds_limit) return fail(PW_ERR_INVALID, "walk_length must be below 8192");
-    const unsigned waves_per_block = 4 * lds_wave <= lds_limit ? 4 : 1;
-    // (the kernel counts items in 64 bits: n_items * epoch must fit)
-    const uint64_t n_items = n_walks * (uint64_t)(L + 1);
-    if (epoch >= ~0ull / n_items) return fail(PW_ERR_INVALID, "epoch index out of range");
-    HIP_TRY(hipSetDevice(s->device));
-    if (!own)   // (the session's own matrix passed these checks when it was taken)
-        if (int rc = sgns_vocabulary(d_walks, n_walks, L, s->n_nodes, s->sample, nullptr)) return rc;
-    const unsigned n_blocks = (unsigned)((n_walks + pw::SGNS_LOSS_CHUNK - 1) / pw::SGNS_LOSS_CHUNK);
-    hipError_t e = s->eval_walk_loss.ensure(n_walks);
-    if (e == hipSuccess) e = s->eval_walk_evals.ensure(n_walks);
-    if (e == hipSuccess) e = s->eval_block_loss.ensure(n_blocks);
-    if (e == hipSuccess) e = s->eval_block_evals.ensure(n_blocks);
-    if (e == hipSuccess) e = s->eval_out.ensure(1);
-    if (e == hipSuccess) e = hipMemset(s->eval_out.p, 0, sizeof(pw_sgns_epoch));
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_evaluate: ") + hipGetErrorString(e));
-    pw::SgnsArgs a = s->a;
-    a.walks = d_walks; a.n_walks = n_walks; a.L = L;
-    a.item_base = n_items * epoch;
-    a.counters = (unsigned long long *)&s->eval_out.p->kept_occurrences;
-    a.walk_loss = s->eval_walk_loss.p; a.walk_evals = s->eval_walk_evals.p;
-    // nothing is written, so nothing races: a wavefront per walk up to what the device holds at once, whatever `workers` is
-    const uint64_t waves = std::min<uint64_t>(n_walks, (uint64_t)s->n_cus * 32);
-    const unsigned blocks = (unsigned)((waves + waves_per_block - 1) / waves_per_block), threads = 64 * waves_per_block;
-    a.n_waves = blocks * waves_per_block;
-    const size_t lds = lds_wave * waves_per_block;
-    switch ((a.dim + 63) / 64) {   // (as sgns_launch_per)
-    case 1: sgns_eval_launch<1>(blocks, threads, lds, a); break;
-    case 2: sgns_eval_launch<2>(blocks, threads, lds, a); break;
-    case 3: sgns_eval_launch<3>(blocks, threads, lds, a); break;
-    case 4: sgns_eval_launch<4>(blocks, threads, lds, a); break;
-    case 5: sgns_eval_launch<5>(blocks, threads, lds, a); break;
-    case 6: sgns_eval_launch<6>(blocks, threads, lds, a); break;
-    case 7: sgns_eval_launch<7>(blocks, threads, lds, a); break;
-    default: sgns_eval_launch<8>(blocks, threads, lds, a); break;
-    }
-    hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(n_blocks), dim3(256), 0, 0, a.walk_loss, a.walk_evals, n_walks,
-                       (uint64_t)pw::SGNS_LOSS_CHUNK, s->eval_block_loss.p, s->eval_block_evals.p);
-    hipLaunchKernelGGL(pw::sgns_loss_reduce_kernel, dim3(1), dim3(256), 0, 0, s->eval_block_loss.p, s->eval_block_evals.p, (uint64_t)n_blocks,
-                       (uint64_t)n_blocks, &s->eval_out.p->loss, (unsigned long long *)&s->eval_out.p->evaluations);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, s->eval_out.p, sizeof(pw_sgns_epoch), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_evaluate: ") + hipGetErrorString(e));
-    return PW_OK;
-}
-
-// Another matrix of the same shape under the session: the schedule arithmetic (n_items) stays, the state and both matrices
-// are not touched.  Everything that can fail comes before the first assignment.
-PW_EXPORT int pw_sgns_set_walks(pw_sgns *s, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t flags) {
-    if (!s || !d_walks) return fail(PW_ERR_INVALID, "null pointer");
-    if (flags & ~(uint32_t)PW_SGNS_RECOUNT) return fail(PW_ERR_INVALID, "unknown flag");
-    if (n_walks != s->a.n_walks || walk_length != s->a.L)
-        return fail(PW_ERR_INVALID, "the session was created on " + std::to_string(s->a.n_walks) + " walks of length " + std::to_string(s->a.L) +
-                                        ": a matrix of " + std::to_string(n_walks) + " walks of length " + std::to_string(walk_length) +
-                                        " needs a session of its own");
-    HIP_TRY(hipSetDevice(s->device));
-    SgnsVocab vocab;
-    const bool recount = (flags & PW_SGNS_RECOUNT) != 0;
-    if (int rc = sgns_vocabulary(d_walks, n_walks, walk_length, s->n_nodes, s->sample, recount ? &vocab : nullptr)) return rc;
-    s->a.walks = d_walks;
-    if (recount) {
-        s->table = std::move(vocab.table);
-        s->keep = std::move(vocab.keep);
-        s->a.table = s->table.p; s->a.table_size = vocab.table_size; s->a.keep = s->keep.p;
-    }
-    return PW_OK;
-}
-
-PW_EXPORT int pw_sgns_get_state(const pw_sgns *s, pw_sgns_state *st) {
-    if (!s || !st) return fail(PW_ERR_INVALID, "null pointer");
-    *st = s->st;
-    return PW_OK;
-}
-
-PW_EXPORT int pw_sgns_set_state(pw_sgns *s, const pw_sgns_state *st) {
-    if (!s || !st) return fail(PW_ERR_INVALID, "null pointer");
-    if (st->sched_total == 0 || st->sched_pos > st->sched_total) return fail(PW_ERR_INVALID, "schedule position beyond its length");
-    // (the kernel counts items in 64 bits: n_items * epoch must fit)
-    const uint64_t most = ~0ull / s->n_items;
-    if (st->epoch >= most || st->sched_total >= most) return fail(PW_ERR_INVALID, "epoch index out of range");
-    if (!std::isfinite(st->alpha) || !std::isfinite(st->min_alpha)) return fail(PW_ERR_INVALID, "alpha and min_alpha must be finite");
-    s->st = *st;
-    return PW_OK;
-}
-
-static int sgns_vectors_copy(pw_sgns *s, int which, float *d_ptr, bool out) {
-    if (!s || !d_ptr) return fail(PW_ERR_INVALID, "null pointer");
-    if (which != 0 && which != 1) return fail(PW_ERR_INVALID, "which must be 0 (syn0) or 1 (syn1)");
-    HIP_TRY(hipSetDevice(s->device));
-    float *mine = which ? s->syn1.p : s->syn0.p;
-    const hipError_t e = hipMemcpy(out ? d_ptr : mine, out ? mine : d_ptr, sizeof(float) * (size_t)s->n_nodes * s->a.dim, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_vectors: ") + hipGetErrorString(e));
-    return PW_OK;
-}
-PW_EXPORT int pw_sgns_vectors_get(pw_sgns *s, int which, float *d_ptr) { return sgns_vectors_copy(s, which, d_ptr, true); }
-PW_EXPORT int pw_sgns_vectors_set(pw_sgns *s, int which, const float *d_ptr) { return sgns_vectors_copy(s, which, (float *)d_ptr, false); }
-
-// The byte mask of one matrix packed into bits; `words` is left unallocated when no byte is set.
-static int sgns_pack_locks(uint32_t n_nodes, const uint8_t *d_mask, DevBuf<unsigned long long> &n_set, DevBuf<uint32_t> *words,
-                           uint64_t *count) {
-    *count = 0;
-    if (!d_mask) return PW_OK;
-    hipError_t e = words->alloc(pw::sgns_lock_words(n_nodes));
-    if (e == hipSuccess) e = hipMemset(n_set.p, 0, sizeof(unsigned long long));
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_set_locks: ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(pw::sgns_lock_pack_kernel, dim3(pw::sgns_lock_blocks(n_nodes)), dim3(pw::SGNS_LOCK_THREADS), 0, 0, d_mask, n_nodes,
-                       words->p, n_set.p);
-    unsigned long long n = 0;
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(&n, n_set.p, sizeof(n), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_set_locks: ") + hipGetErrorString(e));
-    if (!n) words->release();   // (a mask without a non-zero byte is "none")
-    *count = n;
-    return PW_OK;
-}
-
-// Everything that can fail comes before the first assignment: on an error the session keeps the locks it had.
-PW_EXPORT int pw_sgns_set_locks(pw_sgns *s, const uint8_t *d_lock0, const uint8_t *d_lock1) {
-    if (!s) return fail(PW_ERR_INVALID, "null pointer");
-    HIP_TRY(hipSetDevice(s->device));
-    DevBuf<unsigned long long> n_set;
-    if (hipError_t e = n_set.alloc(1)) return fail(PW_ERR_HIP, std::string("pw_sgns_set_locks: ") + hipGetErrorString(e));
-    DevBuf<uint32_t> w0, w1;
-    uint64_t n0 = 0, n1 = 0;
-    if (int rc = sgns_pack_locks(s->n_nodes, d_lock0, n_set, &w0, &n0)) return rc;
-    if (int rc = sgns_pack_locks(s->n_nodes, d_lock1, n_set, &w1, &n1)) return rc;
-    s->lock0 = std::move(w0); s->lock1 = std::move(w1);
-    s->a.lock0 = s->lock0.p; s->a.lock1 = s->lock1.p;
-    s->n_locked[0] = n0; s->n_locked[1] = n1;
-    return PW_OK;
-}
-
-PW_EXPORT int pw_sgns_get_locks(const pw_sgns *s, uint8_t *d_lock0, uint8_t *d_lock1) {
-    if (!s) return fail(PW_ERR_INVALID, "null pointer");
-    HIP_TRY(hipSetDevice(s->device));
-    const uint32_t *words[2] = {s->lock0.p, s->lock1.p};
-    uint8_t *outs[2] = {d_lock0, d_lock1};
-    hipError_t e = hipSuccess;
-    for (int m = 0; m < 2 && e == hipSuccess; m++) {
-        if (!outs[m]) continue;
-        if (!words[m]) e = hipMemset(outs[m], 0, s->n_nodes);
-        else
-            hipLaunchKernelGGL(pw::sgns_lock_unpack_kernel, dim3(pw::sgns_lock_blocks(s->n_nodes)), dim3(pw::SGNS_LOCK_THREADS), 0, 0, words[m],
-                               s->n_nodes, outs[m]);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_get_locks: ") + hipGetErrorString(e));
-    return PW_OK;
-}
-
-PW_EXPORT int pw_sgns_lock_info(const pw_sgns *s, uint64_t out[3]) {
-    if (!s || !out) return fail(PW_ERR_INVALID, "null pointer");
-    out[0] = s->n_locked[0]; out[1] = s->n_locked[1]; out[2] = s->ran_locked ? 1 : 0;
-    return PW_OK;
-}
-
-PW_EXPORT void pw_sgns_destroy(pw_sgns *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
-
-// the one-shot entry: a session that runs its whole schedule and leaves syn0 in the caller's buffer
-PW_EXPORT int pw_sgns_train_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
-                                   uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
-                                   float sample, uint32_t seed, uint32_t workers, float *d_vectors, pw_sgns_stats *stats) {
-    if (!d_walks || !d_vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    pw_sgns *raw = nullptr;
-    int rc = pw_sgns_create_device(device, d_walks, n_walks, walk_length, n_nodes, dim, window, negative, epochs, alpha, min_alpha, sample,
-                                   seed, workers, 0, &raw);
-    if (rc != PW_OK) return rc;
-    std::unique_ptr<pw_sgns, void (*)(pw_sgns *)> s(raw, pw_sgns_destroy);
-    rc = pw_sgns_run(s.get(), epochs, nullptr, stats);
-    if (rc != PW_OK) return rc;
-    return pw_sgns_vectors_get(s.get(), 0, d_vectors);
-}
-
-// host-matrix entry: upload, the device entry, download
-PW_EXPORT int pw_sgns_train(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, uint32_t n_nodes,
-                            uint32_t dim, uint32_t window, uint32_t negative, uint32_t epochs, float alpha, float min_alpha,
-                            float sample, uint32_t seed, uint32_t workers, float *vectors) {
-    if (!walks || !vectors || !n_walks || !n_nodes) return fail(PW_ERR_INVALID, "null pointer / empty corpus");
-    if (dim == 0 || dim > 64 * pw::SGNS_MAX_PER_LANE) return fail(PW_ERR_INVALID, "dim must be in 1..512");
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2), vbytes = sizeof(float) * (size_t)n_nodes * dim;
-    DevBuf<uint32_t> d_walks;
-    DevBuf<float> d_vectors;
-    hipError_t e = d_walks.alloc((size_t)n_walks * ((size_t)walk_length + 2));
-    if (e == hipSuccess) e = d_vectors.alloc((size_t)n_nodes * dim);
-    if (e == hipSuccess) e = hipMemcpy(d_walks.p, walks, wbytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    int rc = pw_sgns_train_device(device, d_walks.p, n_walks, walk_length, n_nodes, dim, window, negative, epochs, alpha, min_alpha,
-                                  sample, seed, workers, d_vectors.p, nullptr);
-    if (rc == PW_OK) {
-        e = hipMemcpy(vectors, d_vectors.p, vbytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(PW_ERR_HIP, std::string("pw_sgns_train: ") + hipGetErrorString(e));
-    }
-    return rc;
-}
-
-// ---- the word2vec text file written from device memory (csrc/emb_text.hip.h) -------------------------------------------------
-namespace {
-
-constexpr uint64_t EMB_CHUNK_DEFAULT = 32ull << 20;   // bytes of text per chunk: PECANPY_AMD_EMB_CHUNK_BYTES overrides
-
-// What a call that writes a text file from device memory owns -- released on every way out -- and the part the embedding
-// writer and the walk writer share: the scan of the row byte counts, then consecutive rows in chunks that fit a byte budget,
-// through one device buffer and two pinned host buffers.  A writer opens the file (with its header line, if it has one),
-// allocates and uploads what its kernels read, launches its count kernel between count_begin and count_end, and hands
-// write_chunks a callable that launches its fill kernel for rows [lo, hi).
-struct TextFile {
-    const std::string who;   // the entry's name in the error texts
-    const std::string path;
-    FILE *file = nullptr;
-    PinnedBuf<void> pinned[2];
-    bool queued = false;   // work may be in flight on the default stream
-    pw::Event ev[8];       // count begin / end; per chunk slot: fill begin, fill end, copy end
-    int n_cu = 1;
-    DevBuf<uint64_t> d_row_off, d_tmp;       // uint64[n_rows + 1]: byte counts, then offsets; the scan's tile sums
-    DevBuf<uint32_t> d_flags;                // one word the fill kernel raises
-    DevBuf<char> d_ids, d_buf;               // the names' characters; the text of one chunk
-    DevBuf<uint64_t> d_id_off;               // the names' offsets
-    std::vector<uint64_t> row_off;                     // host copy: row_off[i] = offset of row i behind the header, [n_rows] = total
-    double format_ms = 0, copy_ms = 0, write_ms = 0;
-    uint64_t header_bytes = 0, n_chunks = 0;
-
-    TextFile(const char *who_, const char *path_) : who(who_), path(path_) {}
-    TextFile(const TextFile &) = delete;
-    ~TextFile() {   // (the buffers go behind this body: nothing of the call is in flight by then)
-        if (queued) (void)hipStreamSynchronize(nullptr);
-        if (file) (void)fclose(file);
-    }
-    int write_failed() const { return fail(PW_ERR_INVALID, who + ": cannot write " + path + ": " + strerror(errno)); }
-    int open(const std::string &header) {
-        file = fopen(path.c_str(), "wb");
-        if (!file) return fail(PW_ERR_INVALID, who + ": cannot open " + path + ": " + strerror(errno));
-        if (fwrite(header.data(), 1, header.size(), file) != header.size()) return write_failed();
-        header_bytes = header.size();
-        return 0;
-    }
-    int begin(int device) {
-        HIP_TRY(hipSetDevice(device));
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        n_cu = prop.multiProcessorCount;
-        queued = true;
-        for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
-        return 0;
-    }
-    template <typename T> int alloc(DevBuf<T> &buf, uint64_t n) {
-        const hipError_t e = buf.alloc(n);
-        if (e == hipSuccess) return 0;
-        return fail(PW_ERR_NOMEM, who + ": " + std::to_string(n * sizeof(T)) + " bytes do not fit in device memory: " + hipGetErrorString(e));
-    }
-    // the names of the call on the device, and the per-row buffers of the count pass
-    int alloc_rows(uint64_t n_rows, const char *id_chars, const uint64_t *id_offsets, uint64_t n_names) {
-        int rc;
-        if ((rc = alloc(d_ids, id_offsets[n_names])) || (rc = alloc(d_id_off, n_names + 1)) || (rc = alloc(d_row_off, n_rows + 1)) ||
-            (rc = alloc(d_tmp, pw::scan_scratch_elems(n_rows + 1))) || (rc = alloc(d_flags, 1)))
-            return rc;
-        if (id_offsets[n_names]) HIP_TRY(hipMemcpyAsync(d_ids.p, id_chars, id_offsets[n_names], hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(d_id_off.p, id_offsets, sizeof(uint64_t) * (n_names + 1), hipMemcpyHostToDevice, nullptr));
-        HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), nullptr));
-        HIP_TRY(hipMemsetAsync(d_row_off.p + n_rows, 0, sizeof(uint64_t), nullptr));   // (the scan's last input: its output is the total)
-        return 0;
-    }
-    // blocks of four wavefronts for one wavefront per row, rows strided over the grid
-    unsigned grid(uint64_t rows) const { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((rows + 3) / 4, (uint64_t)n_cu * 16)); }
-
-    // count pass and scan: the writer's count kernel, launched between the two, leaves row i's byte count in d_row_off[i]
-    int count_begin() {
-        HIP_TRY(hipEventRecord(ev[0], nullptr));
-        return 0;
-    }
-    int count_end(uint64_t n_rows) {
-        pw::exclusive_scan_inplace(nullptr, d_row_off.p, n_rows + 1, d_tmp.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[1], nullptr));
-        row_off.resize(n_rows + 1);
-        HIP_TRY(hipMemcpyAsync(row_off.data(), d_row_off.p, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        format_ms = ms;
-        return 0;
-    }
-    uint64_t bytes() const { return header_bytes + row_off.back(); }
-
-    // fill(lo, hi, blocks, d_buf) launches the fill kernel for rows [lo, hi) on the default stream: their text at
-    // d_buf[row_off[row] - row_off[lo]].  budget >= row_max >= the bytes of any one row.  Closes the file.
-    template <typename Fill> int write_chunks(uint64_t budget, uint64_t row_max, Fill fill) {
-        const uint64_t n_rows = row_off.size() - 1, total = row_off[n_rows];
-        for (uint64_t i = 0; i < n_rows; i++)   // (what the fill pass is bounded by: checked before anything is written through it)
-            if (row_off[i + 1] < row_off[i] || row_off[i + 1] - row_off[i] > row_max)
-                return fail(PW_ERR_HIP, who + ": row byte counts out of range (internal error)");
-
-        // chunks: consecutive rows while their text fits the budget (one row always does)
-        const uint64_t buf_bytes = std::min(budget, total);
-        int rc;
-        if ((rc = alloc(d_buf, buf_bytes))) return rc;
-        for (auto &p : pinned) {
-            const hipError_t e = p.alloc(buf_bytes);
-            if (e != hipSuccess) return fail(PW_ERR_NOMEM, who + ": pinned host buffer: " + hipGetErrorString(e));
-        }
-        struct Chunk { uint64_t lo, hi; };
-        auto next_chunk = [&](uint64_t lo) {
-            // the last row whose end lies within the budget from row lo's start
-            const uint64_t limit = row_off[lo] + buf_bytes;
-            const uint64_t hi = (uint64_t)(std::upper_bound(row_off.begin() + lo + 1, row_off.end(), limit) - row_off.begin()) - 1;
-            return Chunk{lo, hi};
-        };
-        // slot s = chunk index & 1: events 2 + 3 s .. 4 + 3 s = fill begin, fill end, copy end
-        auto issue = [&](const Chunk &c, int s) -> int {
-            HIP_TRY(hipEventRecord(ev[2 + 3 * s], nullptr));
-            fill(c.lo, c.hi, grid(c.hi - c.lo), d_buf.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ev[3 + 3 * s], nullptr));
-            HIP_TRY(hipMemcpyAsync(pinned[s].p, d_buf.p, row_off[c.hi] - row_off[c.lo], hipMemcpyDeviceToHost, nullptr));
-            HIP_TRY(hipEventRecord(ev[4 + 3 * s], nullptr));
-            return 0;
-        };
-        using clk = std::chrono::steady_clock;
-        Chunk cur = next_chunk(0);
-        if ((rc = issue(cur, 0))) return rc;
-        while (true) {
-            const int s = (int)(n_chunks & 1);
-            Chunk nxt{cur.hi, cur.hi};
-            if (cur.hi < n_rows) {   // the copy of the next chunk runs beside this chunk's fwrite
-                nxt = next_chunk(cur.hi);
-                if ((rc = issue(nxt, s ^ 1))) return rc;
-            }
-            HIP_TRY(hipEventSynchronize(ev[4 + 3 * s]));
-            float ms_fill = 0, ms_copy = 0;
-            HIP_TRY(hipEventElapsedTime(&ms_fill, ev[2 + 3 * s], ev[3 + 3 * s]));
-            HIP_TRY(hipEventElapsedTime(&ms_copy, ev[3 + 3 * s], ev[4 + 3 * s]));
-            format_ms += ms_fill;
-            copy_ms += ms_copy;
-            const uint64_t bytes = row_off[cur.hi] - row_off[cur.lo];
-            const auto t0 = clk::now();
-            if (fwrite(pinned[s].p, 1, bytes, file) != bytes) return write_failed();
-            write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-            n_chunks++;
-            if (cur.hi >= n_rows) break;
-            cur = nxt;
-        }
-        uint32_t flags = 0;
-        HIP_TRY(hipMemcpyAsync(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (flags) return fail(PW_ERR_HIP, who + ": the fill pass disagreed with the count pass (internal error)");
-        const auto t0 = clk::now();
-        FILE *f = file;
-        file = nullptr;
-        if (fclose(f) != 0) return write_failed();
-        write_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-        return 0;
-    }
-};
-
-// the names of a writer call: offsets that ascend, the longest name; `what` is what one name belongs to in the error text
-int check_names(const char *who, const char *what, const char *id_chars, const uint64_t *id_offsets, uint64_t n_names,
-                uint64_t *longest_name) {
-    *longest_name = 0;
-    for (uint64_t i = 0; i < n_names; i++) {
-        if (id_offsets[i + 1] < id_offsets[i])
-            return fail(PW_ERR_INVALID, std::string(who) + ": id_offsets do not ascend at " + what + " " + std::to_string(i));
-        *longest_name = std::max(*longest_name, id_offsets[i + 1] - id_offsets[i]);
-    }
-    if (id_offsets[n_names] && !id_chars) return fail(PW_ERR_INVALID, "null pointer");
-    return 0;
-}
-
-uint64_t chunk_budget(const char *env_name, uint64_t row_max) {   // bytes of text per chunk: at least what one row can take
-    uint64_t budget = EMB_CHUNK_DEFAULT;
-    if (const char *v = getenv(env_name))
-        if (*v) budget = (uint64_t)strtoull(v, nullptr, 10);
-    return std::max(budget, row_max);
-}
-
-}  // namespace
-
-PW_EXPORT int pw_vectors_write_text_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
-                                           const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
-    const char *who = "pw_vectors_write_text";
-    if (!d_vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
-    if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
-    uint64_t longest_name = 0;
-    int rc;
-    if ((rc = check_names(who, "row", id_chars, id_offsets, n_rows, &longest_name))) return rc;
-    if ((rc = check_device(device))) return rc;
-    // the byte budget of a chunk: at least what one row can take (name, dim times " " + 47 characters, newline)
-    const uint64_t row_max = longest_name + (uint64_t)dim * pw::F6_SLOT + 1;
-    const uint64_t budget = chunk_budget("PECANPY_AMD_EMB_CHUNK_BYTES", row_max);
-
-    TextFile out(who, path);
-    if ((rc = out.open(std::to_string(n_rows) + " " + std::to_string(dim) + "\n")) || (rc = out.begin(device))) return rc;
-    if ((rc = out.alloc_rows(n_rows, id_chars, id_offsets, n_rows))) return rc;
-
-    if ((rc = out.count_begin())) return rc;
-    hipLaunchKernelGGL(pw::emb_count_kernel, dim3(out.grid(n_rows)), dim3(256), 0, nullptr, d_vectors, n_rows, dim, (const uint64_t *)out.d_id_off.p,
-                       out.d_row_off.p);
-    if ((rc = out.count_end(n_rows))) return rc;
-    rc = out.write_chunks(budget, row_max, [&](uint64_t lo, uint64_t hi, unsigned blocks, char *d_buf) {
-        hipLaunchKernelGGL(pw::emb_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_vectors, lo, hi, dim, (const char *)out.d_ids.p,
-                           (const uint64_t *)out.d_id_off.p, (const uint64_t *)out.d_row_off.p, d_buf, out.d_flags.p);
-    });
-    if (rc) return rc;
-    if (stats) {
-        stats->format_ms = out.format_ms; stats->copy_ms = out.copy_ms; stats->write_ms = out.write_ms;
-        stats->bytes = out.bytes();
-        stats->chunks = out.n_chunks;
-    }
-    return PW_OK;
-}
-
-// host-matrix entry: upload, then the device entry
-PW_EXPORT int pw_vectors_write_text(int device, const float *vectors, uint64_t n_rows, uint32_t dim, const char *id_chars,
-                                    const uint64_t *id_offsets, const char *path, pw_emb_write_stats *stats) {
-    if (!vectors || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
-    if (n_rows == 0 || dim == 0) return fail(PW_ERR_INVALID, "pw_vectors_write_text: n_rows and dim must be positive");
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t vbytes = sizeof(float) * (size_t)n_rows * dim;
-    DevBuf<float> d_vectors;
-    hipError_t e = d_vectors.alloc((size_t)n_rows * dim);
-    if (e != hipSuccess)
-        return fail(PW_ERR_NOMEM, std::string("pw_vectors_write_text: the matrix does not fit in device memory: ") + hipGetErrorString(e));
-    e = hipMemcpy(d_vectors.p, vectors, vbytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? pw_vectors_write_text_device(device, d_vectors.p, n_rows, dim, id_chars, id_offsets, path, stats)
-                             : fail(PW_ERR_HIP, std::string("pw_vectors_write_text: ") + hipGetErrorString(e));
-    return rc;
-}
-
-// ---- the walk corpus file written from device memory (csrc/walk_text.hip.h) ---------------------------------------------------
-PW_EXPORT int pw_walks_write_text_device(int device, const uint32_t *d_walks, uint64_t n_walks, uint32_t walk_length,
-                                         const char *id_chars, const uint64_t *id_offsets, uint64_t n_names, const char *path,
-                                         pw_walks_write_stats *stats) {
-    const char *who = "pw_walks_write_text";
-    if ((n_walks && !d_walks) || !id_offsets || !path) return fail(PW_ERR_INVALID, "null pointer");
-    if (walk_length >= (1u << 31)) return fail(PW_ERR_INVALID, "pw_walks_write_text: walk_length must be below 2^31");
-    uint64_t longest_name = 0;
-    int rc;
-    if ((rc = check_names(who, "name", id_chars, id_offsets, n_names, &longest_name))) return rc;
-    if (longest_name > pw::WALK_NAME_MAX)
-        return fail(PW_ERR_INVALID, "pw_walks_write_text: a name of " + std::to_string(longest_name) + " bytes (at most " +
-                                        std::to_string(pw::WALK_NAME_MAX) + ")");
-    if ((rc = check_device(device))) return rc;
-    // the byte budget of a chunk: at least the longest possible row, walk_length + 1 times the longest name and its separator
-    const uint64_t row_max = ((uint64_t)walk_length + 1) * (longest_name + 1);
-    const uint64_t budget = chunk_budget("PECANPY_AMD_WALKS_CHUNK_BYTES", row_max);
-
-    DevBuf<unsigned long long> d_found;   // the count kernel's findings: lowest row with a bad length, with a bad token; tokens
-                                          // (declared before `out`: it goes after ~TextFile has waited for the stream)
-    TextFile out(who, path);
-    if ((rc = out.open(""))) return rc;
-    if (stats) *stats = pw_walks_write_stats{0, 0, 0, 0, 0, 0, 0};
-    if (n_walks == 0) {   // the empty file
-        FILE *f = out.file;
-        out.file = nullptr;
-        return fclose(f) == 0 ? PW_OK : out.write_failed();
-    }
-    if ((rc = out.begin(device))) return rc;
-    if ((rc = out.alloc_rows(n_walks, id_chars, id_offsets, n_names)) || (rc = out.alloc(d_found, 3))) return rc;
-    HIP_TRY(hipMemsetAsync(d_found.p, 0xff, sizeof(unsigned long long) * 2, nullptr));
-    HIP_TRY(hipMemsetAsync(d_found.p + 2, 0, sizeof(unsigned long long), nullptr));
-
-    if ((rc = out.count_begin())) return rc;
-    hipLaunchKernelGGL(pw::walk_text_count_kernel, dim3(out.grid(n_walks)), dim3(256), 0, nullptr, d_walks, n_walks, walk_length,
-                       (const uint64_t *)out.d_id_off.p, n_names, out.d_row_off.p, d_found.p);
-    if ((rc = out.count_end(n_walks))) return rc;
-    unsigned long long found[3];
-    HIP_TRY(hipMemcpy(found, d_found.p, sizeof(found), hipMemcpyDeviceToHost));
-    const uint64_t width = (uint64_t)walk_length + 2;
-    if (found[0] != ~0ull) {   // nothing of the matrix was looked up, and no fill pass runs: the file stays empty
-        uint32_t len = 0;
-        HIP_TRY(hipMemcpy(&len, d_walks + found[0] * width + walk_length + 1, sizeof(len), hipMemcpyDeviceToHost));
-        return fail(PW_ERR_INVALID, "pw_walks_write_text: row length " + std::to_string(len) + " in row " + std::to_string(found[0]) +
-                                        " exceeds walk_length + 1 = " + std::to_string((uint64_t)walk_length + 1));
-    }
-    if (found[1] != ~0ull) {
-        std::vector<uint32_t> row(width);
-        HIP_TRY(hipMemcpy(row.data(), d_walks + found[1] * width, sizeof(uint32_t) * width, hipMemcpyDeviceToHost));
-        uint64_t c = 0;
-        while (c < row[walk_length + 1] && row[c] < n_names) c++;
-        return fail(PW_ERR_INVALID, "pw_walks_write_text: node index " + std::to_string(row[c]) + " at position " + std::to_string(c) +
-                                        " of row " + std::to_string(found[1]) + " outside the " + std::to_string(n_names) + " names");
-    }
-    rc = out.write_chunks(budget, row_max, [&](uint64_t lo, uint64_t hi, unsigned blocks, char *d_buf) {
-        hipLaunchKernelGGL(pw::walk_text_fill_kernel, dim3(blocks), dim3(256), 0, nullptr, d_walks, lo, hi, walk_length, (const char *)out.d_ids.p,
-                           (const uint64_t *)out.d_id_off.p, n_names, (const uint64_t *)out.d_row_off.p, d_buf, out.d_flags.p);
-    });
-    if (rc) return rc;
-    if (stats) {
-        stats->format_ms = out.format_ms; stats->copy_ms = out.copy_ms; stats->write_ms = out.write_ms;
-        stats->bytes = out.bytes();
-        stats->chunks = out.n_chunks;
-        stats->rows = n_walks;
-        stats->tokens = found[2];
-    }
-    return PW_OK;
-}
-
-// host-matrix entry: upload, then the device entry
-PW_EXPORT int pw_walks_write_text(int device, const uint32_t *walks, uint64_t n_walks, uint32_t walk_length, const char *id_chars,
-                                  const uint64_t *id_offsets, uint64_t n_names, const char *path, pw_walks_write_stats *stats) {
-    if (n_walks == 0 || !walks || walk_length >= (1u << 31))   // (nothing to upload, or refused there)
-        return pw_walks_write_text_device(device, nullptr, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats);
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t wbytes = sizeof(uint32_t) * (size_t)n_walks * ((size_t)walk_length + 2);
-    DevBuf<uint32_t> d_walks;
-    hipError_t e = d_walks.alloc((size_t)n_walks * ((size_t)walk_length + 2));
-    if (e != hipSuccess)
-        return fail(PW_ERR_NOMEM, std::string("pw_walks_write_text: the matrix does not fit in device memory: ") + hipGetErrorString(e));
-    e = hipMemcpy(d_walks.p, walks, wbytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? pw_walks_write_text_device(device, d_walks.p, n_walks, walk_length, id_chars, id_offsets, n_names, path, stats)
-                             : fail(PW_ERR_HIP, std::string("pw_walks_write_text: ") + hipGetErrorString(e));
-    return rc;
-}
-
-// x[i] formatted into chars[48 i ..) (the rest of the slot zero), lens[i] = the count.  on_device = 0: the host build of
-// format_f6; on_device = 1: one GPU thread per value.
-PW_EXPORT int pw_selftest_format_f6(int on_device, int device, const float *x, uint64_t n, char *chars, uint32_t *lens) {
-    if (n && (!x || !chars || !lens)) return fail(PW_ERR_INVALID, "null pointer");
-    if (n == 0) return PW_OK;
-    if (!on_device) {
-        memset(chars, 0, (size_t)n * pw::F6_SLOT);
-        for (uint64_t i = 0; i < n; i++) {
-            const pw::F6 f = pw::f6_decompose(x[i]);
-            const uint32_t len = pw::f6_emit(f, chars + i * pw::F6_SLOT);
-            lens[i] = len == pw::f6_len(f) ? len : 0xffffffffu;
-        }
-        return PW_OK;
-    }
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<float> d_x;
-    DevBuf<char> d_chars;
-    DevBuf<uint32_t> d_lens;
-    const size_t cbytes = (size_t)n * pw::F6_SLOT;
-    hipError_t e = d_x.alloc(n);
-    if (e == hipSuccess) e = d_chars.alloc(cbytes);
-    if (e == hipSuccess) e = d_lens.alloc(n);
-    if (e == hipSuccess) e = hipMemcpy(d_x.p, x, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_chars.p, 0, cbytes);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pw::f6_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)d_x.p, n, d_chars.p, d_lens.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(chars, d_chars.p, cbytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(lens, d_lens.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_format_f6: ") + hipGetErrorString(e));
-    return PW_OK;
-}
-
-// x[0, n) of uint32 (width 32) or uint64 (width 64) in host memory -> its exclusive scan in place, *total = the sum, through
-// scan.hip.h's entry on the null stream
-template <typename T> static int selftest_exclusive_scan(T *x, uint64_t n, uint64_t *total) {
-    DevBuf<T> d_x, d_scratch;
-    T sum = 0;
-    hipError_t e = d_x.alloc(n + 1);
-    if (e == hipSuccess) e = d_scratch.alloc(pw::scan_scratch_elems(n));
-    if (e == hipSuccess && n) e = hipMemcpy(d_x.p, x, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        pw::exclusive_scan_inplace(nullptr, d_x.p, n, d_scratch.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && n) e = hipMemcpy(x, d_x.p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&sum, d_scratch.p, sizeof(T), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_exclusive_scan: ") + hipGetErrorString(e));
-    *total = sum;
-    return PW_OK;
-}
-
-PW_EXPORT int pw_selftest_exclusive_scan(int device, int width, void *x, uint64_t n, uint64_t *total) {
-    if ((n && !x) || !total || (width != 32 && width != 64)) return fail(PW_ERR_INVALID, "bad argument");
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    return width == 32 ? selftest_exclusive_scan((uint32_t *)x, n, total) : selftest_exclusive_scan((uint64_t *)x, n, total);
-}
-
-// ---- nearest neighbours of embedding vectors, exact and ordered (csrc/knn.hip.h) --------------------------------------------
-struct pw_knn {
-    int device = 0, n_cu = 1;
-    uint64_t n = 0;
-    uint32_t dim = 0;
-    DevBuf<float> X;         // the snapshot: float32[n, dim]
-    DevBuf<double> norms;    // float64[n]
-};
-
-namespace {
-
-constexpr uint64_t KNN_QD_BUDGET = 256ull << 20;   // bytes of widened queries per batch
-
-int knn_check_call(const void *queries, const void *rows, uint32_t topn, int metric, const pw_knn_tiles *tiles) {
-    if ((queries != nullptr) == (rows != nullptr)) return fail(PW_ERR_INVALID, "pw_knn_query: exactly one of queries and rows must be given");
-    if (topn < 1 || topn > PW_KNN_MAX_TOPN)
-        return fail(PW_ERR_INVALID, "pw_knn_query: topn = " + std::to_string(topn) + " outside 1.." + std::to_string(PW_KNN_MAX_TOPN));
-    if (metric != PW_KNN_DOT && metric != PW_KNN_COSINE) return fail(PW_ERR_INVALID, "pw_knn_query: metric must be PW_KNN_DOT or PW_KNN_COSINE");
-    if (tiles) {
-        const uint32_t r = tiles->rows_per_block, c = tiles->col_chunk;
-        if ((r != 0 && r != 64 && r != 128 && r != 256) || tiles->queries_per_tile > pw::KNN_QT || tiles->grid > 65536 || (c & 3u) || c > pw::KNN_KC)
-            return fail(PW_ERR_INVALID, "pw_knn_tiles: rows_per_block 64 / 128 / 256, queries_per_tile <= 8, grid <= 65536, col_chunk a multiple of 4 <= 32");
-    }
-    return 0;
-}
-
-int knn_check_shape(uint64_t n_rows, uint32_t dim) {
-    if (n_rows < 1 || n_rows >= (1ull << 32)) return fail(PW_ERR_INVALID, "pw_knn: n_rows must be in 1 .. 2^32 - 1");
-    if (dim < 1 || dim > pw::KNN_MAX_DIM) return fail(PW_ERR_INVALID, "pw_knn: dim must be in 1.." + std::to_string(pw::KNN_MAX_DIM));
-    return 0;
-}
-
-int knn_bad_row(uint64_t row) { return fail(PW_ERR_INVALID, "pw_knn: row " + std::to_string(row) + " of the matrix holds a NaN or an infinity"); }
-int knn_bad_query(uint64_t q) { return fail(PW_ERR_INVALID, "pw_knn_query: query " + std::to_string(q) + " holds a NaN or an infinity"); }
-int knn_row_range(uint64_t q, uint32_t row, uint64_t n) {
-    return fail(PW_ERR_INVALID, "pw_knn_query: row number " + std::to_string(row) + " at position " + std::to_string(q) + " is outside the " +
-                                    std::to_string(n) + " rows");
-}
-
-template <typename T> int knn_alloc(DevBuf<T> &b, size_t n) {
-    const hipError_t e = b.alloc(n);
-    return e == hipSuccess ? 0 : fail(PW_ERR_NOMEM, "pw_knn: " + std::to_string(n * sizeof(T)) + " bytes do not fit in device memory: " + hipGetErrorString(e));
-}
-
-// the index from a matrix in device or host memory: the copy, the norms, the refusal of non-finite rows
-int knn_create_impl(int device, const float *vectors, hipMemcpyKind kind, uint64_t n_rows, uint32_t dim, pw_knn **out) {
-    if (!vectors || !out) return fail(PW_ERR_INVALID, "null pointer");
-    *out = nullptr;
-    int rc;
-    if ((rc = knn_check_shape(n_rows, dim)) || (rc = check_device(device))) return rc;
-    HIP_TRY(hipSetDevice(device));
-    std::unique_ptr<pw_knn> k(new (std::nothrow) pw_knn());
-    if (!k) return fail(PW_ERR_NOMEM, "pw_knn: out of host memory");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    k->device = device;
-    k->n_cu = std::max(1, prop.multiProcessorCount);
-    k->n = n_rows;
-    k->dim = dim;
-    DevBuf<pw::KnnFound> found;
-    if ((rc = knn_alloc(k->X, (size_t)n_rows * dim)) || (rc = knn_alloc(k->norms, n_rows)) || (rc = knn_alloc(found, 1))) return rc;
-    HIP_TRY(hipMemcpy(k->X.p, vectors, sizeof(float) * (size_t)n_rows * dim, kind));
-    HIP_TRY(hipMemset(found.p, 0xff, sizeof(pw::KnnFound)));
-    const unsigned blocks = (unsigned)std::min<uint64_t>((n_rows + 255) / 256, (uint64_t)k->n_cu * 16);
-    hipLaunchKernelGGL(pw::knn_norms_kernel, dim3(blocks), dim3(256), 0, nullptr, (const float *)k->X.p, n_rows, dim, k->norms.p, found.p);
-    HIP_TRY(hipGetLastError());
-    pw::KnnFound h;
-    HIP_TRY(hipMemcpy(&h, found.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (h.first_bad != ~0ull) return knn_bad_row(h.first_bad);
-    *out = k.release();
-    return PW_OK;
-}
-
-// the query of pw_knn_query_device and of pw_selftest_knn (tiles: forced, or nullptr)
-int knn_query_impl(pw_knn *k, const float *d_queries, const uint32_t *d_rows, uint64_t nq, uint32_t topn, int metric, int exclude_self,
-                   uint32_t *d_idx, double *d_score, const pw_knn_tiles *tiles, pw_knn_stats *stats) {
-    using clk = std::chrono::steady_clock;
-    const auto t_begin = clk::now();
-    if (!k) return fail(PW_ERR_INVALID, "null pointer");
-    if (int rc = knn_check_call(d_queries, d_rows, topn, metric, tiles)) return rc;
-    if (stats) *stats = pw_knn_stats{0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (nq == 0) return PW_OK;
-    if (!d_idx || !d_score) return fail(PW_ERR_INVALID, "null pointer");
-    HIP_TRY(hipSetDevice(k->device));
-
-    // the queries' norms; a row number out of range and a non-finite query are refused before anything is written
-    DevBuf<double> qnorms, qd, part_sc;
-    DevBuf<uint32_t> part_ix;
-    DevBuf<pw::KnnFound> found;
-    int rc;
-    if ((rc = knn_alloc(qnorms, nq)) || (rc = knn_alloc(found, 1))) return rc;
-    HIP_TRY(hipMemsetAsync(found.p, 0xff, sizeof(pw::KnnFound), nullptr));
-    hipLaunchKernelGGL(pw::knn_query_norms_kernel, dim3((unsigned)std::min<uint64_t>((nq + 255) / 256, (uint64_t)k->n_cu * 16)), dim3(256), 0, nullptr,
-                       d_queries, d_rows, nq, k->n, k->dim, (const double *)k->norms.p, qnorms.p, found.p);
-    HIP_TRY(hipGetLastError());
-    pw::KnnFound h;
-    HIP_TRY(hipMemcpy(&h, found.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (h.first_range != ~0ull) {
-        uint32_t row = 0;
-        HIP_TRY(hipMemcpy(&row, d_rows + h.first_range, sizeof(row), hipMemcpyDeviceToHost));
-        return knn_row_range(h.first_range, row, k->n);
-    }
-    if (h.first_bad != ~0ull) return knn_bad_query(h.first_bad);
-
-    // the tile: row groups x query groups of the 8 wavefronts.  Few queries: more row groups, so that no wavefront idles
-    const uint32_t rg = tiles && tiles->rows_per_block ? tiles->rows_per_block / 64 : (nq <= 16 ? 4u : nq <= 32 ? 2u : 1u);
-    const uint32_t qt = tiles && tiles->queries_per_tile ? tiles->queries_per_tile : pw::KNN_QT;
-    const uint32_t kc = tiles && tiles->col_chunk ? tiles->col_chunk : pw::KNN_KC;
-    const uint32_t qg = pw::KNN_WAVES / rg, tile_q = qg * qt, R = 64 * rg, dimp = (k->dim + 3u) & ~3u;
-    const uint64_t n_blocks = (k->n + R - 1) / R;
-    const size_t lds = pw::knn_score_lds_bytes(rg, topn);
-    HIP_TRY(hipFuncSetAttribute((const void *)pw::knn_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    uint64_t grid = tiles ? tiles->grid : 0;
-    if (grid == 0) {   // what the device holds at once
-        int occ = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::knn_score_kernel, (int)pw::KNN_THREADS, lds));
-        grid = (uint64_t)std::max(1, occ) * k->n_cu;
-    }
-    // a batch: whole tiles whose widened queries stay within the budget (one tile always fits)
-    const uint64_t tiles_max = std::max<uint64_t>(1, KNN_QD_BUDGET / ((uint64_t)dimp * pw::KNN_QT * sizeof(double) * qg));
-    const uint64_t batch = std::min<uint64_t>(nq, std::min<uint64_t>(tiles_max, (1u << 20)) * tile_q);
-
-    pw::Event ev[3];
-    for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
-    double score_ms = 0, merge_ms = 0;
-    uint32_t n_batches = 0, first_grid = 0, first_parts = 0;
-    for (uint64_t q0 = 0; q0 < nq; q0 += batch, n_batches++) {
-        const uint32_t nqb = (uint32_t)std::min<uint64_t>(batch, nq - q0);
-        const uint32_t n_tiles = (nqb + tile_q - 1) / tile_q, n_slots = n_tiles * qg;
-        const uint32_t row_parts = (uint32_t)std::min<uint64_t>(n_blocks, std::max<uint64_t>(1, (grid + n_tiles - 1) / n_tiles));
-        const uint32_t tile_parts = (uint32_t)std::min<uint64_t>(n_tiles, std::max<uint64_t>(1, grid / row_parts));
-        const uint32_t n_lists = row_parts * rg;
-        const size_t part_elems = (size_t)n_lists * nqb * topn;
-        if ((rc = grow(qd, (size_t)n_slots * dimp * pw::KNN_QT)) || (rc = grow(part_sc, part_elems)) || (rc = grow(part_ix, part_elems))) return rc;
-        hipLaunchKernelGGL(pw::knn_stage_queries_kernel, dim3((unsigned)(((uint64_t)n_slots * pw::KNN_QT + 255) / 256)), dim3(256), 0, nullptr,
-                           (const float *)k->X.p, d_queries, d_rows, q0, nqb, qt, n_slots, k->dim, dimp, qd.p);
-        pw::KnnScoreArgs a;
-        a.X = k->X.p; a.xnorms = k->norms.p; a.qd = qd.p; a.qnorms = qnorms.p + q0;
-        a.qself = (d_rows && exclude_self) ? d_rows + q0 : nullptr;
-        a.part_sc = part_sc.p; a.part_ix = part_ix.p;
-        a.n = k->n; a.n_blocks = n_blocks;
-        a.dim = k->dim; a.dimp = dimp; a.nqb = nqb; a.qt = qt; a.topn = topn; a.metric = (uint32_t)metric;
-        a.rg = rg; a.kc = kc; a.row_parts = row_parts; a.tile_parts = tile_parts; a.n_tiles = n_tiles;
-        HIP_TRY(hipEventRecord(ev[0], nullptr));
-        hipLaunchKernelGGL(pw::knn_score_kernel, dim3(row_parts * tile_parts), dim3(pw::KNN_THREADS), lds, nullptr, a);
-        HIP_TRY(hipEventRecord(ev[1], nullptr));
-        hipLaunchKernelGGL(pw::knn_merge_kernel, dim3((nqb + 3) / 4), dim3(256), 0, nullptr, (const double *)part_sc.p, (const uint32_t *)part_ix.p,
-                           n_lists, nqb, topn, d_idx + q0 * topn, d_score + q0 * topn);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[2], nullptr));
-        HIP_TRY(hipEventSynchronize(ev[2]));   // (the next batch may grow the buffers this one reads)
-        float ms_score = 0, ms_merge = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_score, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_merge, ev[1], ev[2]));
-        score_ms += ms_score;
-        merge_ms += ms_merge;
-        if (q0 == 0) { first_grid = row_parts * tile_parts; first_parts = row_parts; }
-    }
-    if (stats) {
-        stats->score_ms = score_ms; stats->merge_ms = merge_ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
-        stats->grid = first_grid; stats->row_parts = first_parts;
-        stats->rows_per_block = R; stats->queries_per_tile = qt; stats->col_chunk = kc;
-        stats->batches = n_batches;
-    }
-    return PW_OK;
-}
-
-}  // namespace
-
-PW_EXPORT int pw_knn_create_device(int device, const float *d_vectors, uint64_t n_rows, uint32_t dim, pw_knn **out) {
-    return knn_create_impl(device, d_vectors, hipMemcpyDeviceToDevice, n_rows, dim, out);
-}
-
-PW_EXPORT int pw_knn_create(int device, const float *vectors, uint64_t n_rows, uint32_t dim, pw_knn **out) {
-    return knn_create_impl(device, vectors, hipMemcpyHostToDevice, n_rows, dim, out);
-}
-
-PW_EXPORT int pw_knn_query_device(pw_knn *k, const float *d_queries, const uint32_t *d_rows, uint64_t nq, uint32_t topn, int metric,
-                                  int exclude_self, uint32_t *d_idx, double *d_score, pw_knn_stats *stats) {
-    return knn_query_impl(k, d_queries, d_rows, nq, topn, metric, exclude_self, d_idx, d_score, nullptr, stats);
-}
-
-PW_EXPORT int pw_knn_info(const pw_knn *k, uint64_t *n_rows, uint32_t *dim, uint64_t *bytes) {
-    if (!k) return fail(PW_ERR_INVALID, "null pointer");
-    if (n_rows) *n_rows = k->n;
-    if (dim) *dim = k->dim;
-    if (bytes) *bytes = k->X.bytes() + k->norms.bytes();
-    return PW_OK;
-}
-
-PW_EXPORT int pw_knn_norms_get(pw_knn *k, double *d_norms) {
-    if (!k || !d_norms) return fail(PW_ERR_INVALID, "null pointer");
-    HIP_TRY(hipSetDevice(k->device));
-    HIP_TRY(hipMemcpy(d_norms, k->norms.p, sizeof(double) * (size_t)k->n, hipMemcpyDeviceToDevice));
-    return PW_OK;
-}
-
-PW_EXPORT void pw_knn_destroy(pw_knn *k) {
-    if (!k) return;
-    (void)hipSetDevice(k->device);
-    delete k;
-}
-
-PW_EXPORT int pw_selftest_knn(int on_device, int device, const float *vectors, uint64_t n, uint32_t dim, const float *queries,
-                              const uint32_t *rows, uint64_t nq, uint32_t topn, int metric, int exclude_self, const pw_knn_tiles *tiles,
-                              uint32_t *idx, double *score) {
-    if (!vectors || (nq && (!idx || !score))) return fail(PW_ERR_INVALID, "null pointer");
-    int rc;
-    if ((rc = knn_check_shape(n, dim)) || (rc = knn_check_call(queries, rows, topn, metric, tiles))) return rc;
-    if (!on_device) {
-        std::vector<double> norms(n), qnorms(nq);
-        std::vector<uint32_t> ix((size_t)nq * topn);
-        std::vector<double> sc((size_t)nq * topn);
-        uint64_t where = 0;
-        switch (pw::knn_host_query(vectors, n, dim, queries, rows, nq, topn, metric, exclude_self, ix.data(), sc.data(), norms.data(),
-                                   qnorms.data(), &where)) {
-            case pw::KNN_HOST_BAD_ROW: return knn_bad_row(where);
-            case pw::KNN_HOST_BAD_QUERY: return knn_bad_query(where);
-            case pw::KNN_HOST_ROW_RANGE: return knn_row_range(where, rows[where], n);
-            default: break;
-        }
-        if (nq) {
-            memcpy(idx, ix.data(), sizeof(uint32_t) * ix.size());
-            memcpy(score, sc.data(), sizeof(double) * sc.size());
-        }
-        return PW_OK;
-    }
-    pw_knn *raw = nullptr;
-    if ((rc = pw_knn_create(device, vectors, n, dim, &raw))) return rc;
-    struct Closer { void operator()(pw_knn *k) const { pw_knn_destroy(k); } };
-    std::unique_ptr<pw_knn, Closer> k(raw);
-    if (nq == 0) return PW_OK;
-    DevBuf<float> d_q;
-    DevBuf<uint32_t> d_r, d_idx;
-    DevBuf<double> d_score;
-    if ((rc = knn_alloc(d_idx, (size_t)nq * topn)) || (rc = knn_alloc(d_score, (size_t)nq * topn))) return rc;
-    if (queries) {
-        if ((rc = knn_alloc(d_q, (size_t)nq * dim))) return rc;
-        HIP_TRY(hipMemcpy(d_q.p, queries, sizeof(float) * (size_t)nq * dim, hipMemcpyHostToDevice));
-    } else {
-        if ((rc = knn_alloc(d_r, nq))) return rc;
-        HIP_TRY(hipMemcpy(d_r.p, rows, sizeof(uint32_t) * (size_t)nq, hipMemcpyHostToDevice));
-    }
-    if ((rc = knn_query_impl(k.get(), queries ? d_q.p : nullptr, rows ? d_r.p : nullptr, nq, topn, metric, exclude_self, d_idx.p, d_score.p, tiles,
-                             nullptr)))
-        return rc;
-    HIP_TRY(hipMemcpy(idx, d_idx.p, sizeof(uint32_t) * (size_t)nq * topn, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(score, d_score.p, sizeof(double) * (size_t)nq * topn, hipMemcpyDeviceToHost));
-    return PW_OK;
-}
+#include "drv_sgns.hip.h"
+#include "drv_text_write.hip.h"
+#include "drv_knn.hip.h"
 
 // ---- link prediction: pair scores, exact AUC, non-edges from the seeded stream (csrc/linkpred.hip.h) ---------------------------
 namespace {
@@ -6005,559 +4499,5 @@ PW_EXPORT int pw_selftest_holdout_edges(int on_device, int device, const uint32_
     return PW_OK;
 }
 
-// ---- host self test of the exact-arithmetic decision ---------------------------------------------------
-PW_EXPORT int pw_selftest_exact_decision(const uint8_t *cls, uint32_t n, float w_out, float w_prev, const double *r,
-                                         uint32_t n_r, uint32_t *chain, uint32_t *exact) {
-    if (!cls || !r || !chain || !exact || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    auto pow2 = [](float w) { int e = 0; return std::frexp(w, &e) == 0.5f; };
-    if (!pow2(w_out) || !pow2(w_prev)) return fail(PW_ERR_UNSUPPORTED, "biases must be powers of two");
-    uint32_t cnt[3] = {0, 0, 0};
-    for (uint32_t k = 0; k < n; k++) {
-        if (cls[k] > 2) return fail(PW_ERR_INVALID, "class must be 0 (out), 1 (common) or 2 (prev)");
-        cnt[cls[k]]++;
-    }
-    if (cnt[2] > 1) return fail(PW_ERR_INVALID, "at most one prev");
-    // same set-up as sample_step_unit_lazy (walk_sparse.hip.h)
-    float u = 1.0f;
-    if (cnt[0] && w_out < u) u = w_out;
-    if (cnt[2] && w_prev < u) u = w_prev;
-    const double td = (double)cnt[1] + (double)cnt[0] * (double)w_out + (double)cnt[2] * (double)w_prev;
-    if (!(td <= 16777216.0 * (double)u)) return fail(PW_ERR_UNSUPPORTED, "row total not exact in float32");
-    const float tot = (float)td;
-    const float x_in = 1.0f / tot, x_out = x_in * w_out, x_prev = x_in * w_prev;
-    const double units = td / (double)u;
-    const uint32_t w_units[3] = {cnt[0] ? (uint32_t)(w_out / u) : 1u, (uint32_t)(1.0f / u), cnt[2] ? (uint32_t)(w_prev / u) : 1u};
-    const uint32_t wmax = std::max(w_units[0], std::max(w_units[1], w_units[2]));
-    std::vector<uint32_t> E(n);
-    uint32_t acc = 0;
-    for (uint32_t k = 0; k < n; k++) { acc += w_units[cls[k]]; E[k] = acc; }
-    for (uint32_t i = 0; i < n_r; i++) {
-        // the reference: np.searchsorted(np.cumsum(float32 values), r), sequential float32 additions
-        float c = 0.0f;
-        uint32_t kc = n;
-        for (uint32_t k = 0; k < n; k++) {
-            c = c + (cls[k] == 1 ? x_in : (cls[k] == 0 ? x_out : x_prev));
-            if ((double)c >= r[i]) { kc = k; break; }
-        }
-        chain[i] = kc;
-        const pw::ExactThresholds th = pw::exact_thresholds_f32(r[i] * units, n, wmax);
-        const uint32_t k1 = (uint32_t)(std::lower_bound(E.begin(), E.end(), th.lo) - E.begin());
-        exact[i] = (k1 < n && E[k1] >= th.hi) ? k1 : 0xffffffffu;
-    }
-    return PW_OK;
-}
-
-PW_EXPORT int pw_selftest_exact_decision_f64(const uint8_t *cls, uint32_t n, double w_out, double w_prev,
-                                             const double *r, uint32_t n_r, uint32_t *chain, uint32_t *exact) {
-    if (!cls || !r || !chain || !exact || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    auto pow2 = [](double w) { int e = 0; return std::frexp(w, &e) == 0.5; };
-    if (!pow2(w_out) || !pow2(w_prev)) return fail(PW_ERR_UNSUPPORTED, "biases must be powers of two");
-    uint64_t cnt[3] = {0, 0, 0};
-    for (uint32_t k = 0; k < n; k++) {
-        if (cls[k] > 2) return fail(PW_ERR_INVALID, "class must be 0 (out), 1 (common) or 2 (prev)");
-        cnt[cls[k]]++;
-    }
-    if (cnt[2] > 1) return fail(PW_ERR_INVALID, "at most one prev");
-    // same set-up as walk_dense_bits_kernel (walk_dense.hip.h)
-    double u = 1.0;
-    if (cnt[0] && w_out < u) u = w_out;
-    if (cnt[2] && w_prev < u) u = w_prev;
-    const double tot = (double)cnt[1] + (double)cnt[0] * w_out + (double)cnt[2] * w_prev;
-    const double S = tot / u, wi = 1.0 / u, wo = w_out / u, wp = w_prev / u;
-    const double wmax = std::max(wi, std::max(wo, wp));
-    if (!(S <= 1099511627776.0 && wmax + 2.0 <= 1048576.0)) return fail(PW_ERR_UNSUPPORTED, "row outside the exact range");
-    const double x[3] = {w_out / tot, 1.0 / tot, w_prev / tot};
-    const uint64_t w_units[3] = {(uint64_t)wo, (uint64_t)wi, (uint64_t)wp};
-    std::vector<uint64_t> E(n);
-    uint64_t acc = 0;
-    for (uint32_t k = 0; k < n; k++) { acc += w_units[cls[k]]; E[k] = acc; }
-    for (uint32_t i = 0; i < n_r; i++) {
-        double c = 0.0;
-        uint32_t kc = n;
-        for (uint32_t k = 0; k < n; k++) {
-            c = c + x[cls[k]];
-            if (c >= r[i]) { kc = k; break; }
-        }
-        chain[i] = kc;
-        const pw::ExactThresholds64 th = pw::exact_thresholds_f64(r[i] * S, (double)n, wmax);
-        const uint32_t k1 = (uint32_t)(std::lower_bound(E.begin(), E.end(), th.lo) - E.begin());
-        exact[i] = (k1 < n && E[k1] >= th.hi) ? k1 : 0xffffffffu;
-    }
-    return PW_OK;
-}
-
-// ---- self tests of the lane kernel's per-thread routines (seqscan.h: lane_decide, lane_tight, lane_chain) ----------
-// One row given by its classes (0 out, 1 common, 2 prev), many targets.  The same routine runs on the host and -- in
-// lane_selftest_kernel, one thread per target -- on the DEVICE, where the compiler's code generation and the hardware's
-// arithmetic (v_rcp_f32 in lane_tight, -ffp-contract=off adds) are what the walk kernels actually execute.
-namespace {
-
-struct LaneRow {
-    std::vector<uint16_t> cl16;
-    std::vector<uint32_t> cl32;
-    uint32_t n_cl = 0, pp = 0xffffffffu, wide = 0;
-    uint32_t piv_off = 0;   // element offset of the list's pivots inside cl16 / cl32 (0: none) -- as the index build lays them out
-    float tot = 0, x_in = 0, x_out = 0, x_prev = 0;
-    pw::ListView view() const { return pw::list_view_of(wide ? (const void *)cl32.data() : (const void *)cl16.data(), wide, n_cl, piv_off); }
-};
-
-int lane_row_setup(const uint8_t *cls, uint32_t n, float w_out, float w_prev, LaneRow &row, bool need_pow2 = true) {
-    auto pow2 = [](float w) { int e = 0; return std::frexp(w, &e) == 0.5f; };
-    if (need_pow2 && (!pow2(w_out) || !pow2(w_prev))) return fail(PW_ERR_UNSUPPORTED, "biases must be powers of two");
-    if (!(w_out > 0.0f) || !(w_prev > 0.0f)) return fail(PW_ERR_INVALID, "biases must be positive");
-    uint32_t cnt[3] = {0, 0, 0};
-    row.wide = n > 65536u ? 1u : 0u;   // positions of rows up to 65536 entries are uint16 (walk_lanes.hip.h)
-    for (uint32_t k = 0; k < n; k++) {
-        if (cls[k] > 2) return fail(PW_ERR_INVALID, "class must be 0 (out), 1 (common) or 2 (prev)");
-        cnt[cls[k]]++;
-        if (cls[k] == 1) { if (row.wide) row.cl32.push_back(k); else row.cl16.push_back((uint16_t)k); }
-        if (cls[k] == 2) row.pp = k;
-    }
-    if (cnt[2] > 1) return fail(PW_ERR_INVALID, "at most one prev");
-    row.n_cl = cnt[1];
-    row.cl16.resize(row.cl16.size() + 8, 0xffffu);       // a list window may read past the end of the list
-    row.cl32.resize(row.cl32.size() + 8, 0xffffffffu);
-    if (pw::list_has_pivots(row.wide, row.n_cl) && !getenv("PW_SELFTEST_NO_PIVOTS")) {   // pivots, as eline_pivots_kernel writes them
-        const uint32_t np = pw::list_pivot_count(row.wide), step = pw::list_pivot_step(row.wide, row.n_cl);
-        row.piv_off = (uint32_t)(row.wide ? row.cl32.size() : row.cl16.size());
-        for (uint32_t k = 0; k < np; k++) {
-            if (row.wide) row.cl32.push_back(row.cl32[(size_t)(k + 1) * step]);
-            else row.cl16.push_back(row.cl16[(size_t)(k + 1) * step]);
-        }
-    }
-    row.tot = (float)((double)cnt[1] + (double)cnt[0] * (double)w_out + (double)cnt[2] * (double)w_prev);
-    row.x_in = 1.0f / row.tot;
-    row.x_out = row.x_in * w_out;
-    row.x_prev = row.x_in * w_prev;
-    return 0;
-}
-
-}  // namespace
-
-namespace pw {
-// lane_decide -> lane_tight -> lane_chain for one target; out = { lane, kmax, tight, chain_lane }
-PW_HD void lane_selftest_one(uint32_t n, const ListView &cl, uint32_t n_cl, uint32_t pp, float w_out, float w_prev, double r,
-                             uint32_t *out) {
-    LaneStep ls{0.0f, 0u, 0u, 0u, 0u, 0u, 0u};
-    const uint32_t lane = lane_decide(n, n_cl, pp, r, w_out, w_prev, cl, ls);
-    out[0] = lane;
-    out[1] = lane == LANE_AMBIGUOUS ? ls.kmax : 0u;
-    out[2] = lane == LANE_AMBIGUOUS ? lane_tight(n, pp, r, w_out, w_prev, ls) : lane;
-    // the per-thread float chain: over the ambiguous prefix, or the whole row when decided
-    if (lane == LANE_REDO) { out[3] = LANE_REDO; return; }
-    const uint32_t kend = lane == LANE_AMBIGUOUS ? ls.kmax : n;
-    const float x_in = 1.0f / ls.tot;
-    uint32_t reads = 0;
-    out[3] = lane_chain(kend, n_cl, pp, r, x_in, x_in * w_out, x_in * w_prev, cl, reads);
-}
-
-__global__ void __launch_bounds__(256)
-lane_selftest_kernel(const uint8_t *cls, uint32_t n, const void *cl, uint32_t wide, uint32_t piv_off, uint32_t n_cl, uint32_t pp, float w_out,
-                     float w_prev, const double *r, uint32_t n_r, uint32_t *chain, uint32_t *out4) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_r) return;
-    // the reference: sequential float32 cumsum + searchsorted (pecanpy.py:556-557), by this thread
-    uint32_t cnt_in = 0, cnt_out = 0, cnt_pv = 0;
-    for (uint32_t k = 0; k < n; k++) { const uint8_t c = cls[k]; cnt_in += c == 1; cnt_out += c == 0; cnt_pv += c == 2; }
-    const float tot = (float)((double)cnt_in + (double)cnt_out * (double)w_out + (double)cnt_pv * (double)w_prev);
-    const float x_in = 1.0f / tot, x_out = x_in * w_out, x_prev = x_in * w_prev;
-    float c = 0.0f;
-    uint32_t kc = n;
-    for (uint32_t k = 0; k < n; k++) {
-        c = c + (cls[k] == 1 ? x_in : (cls[k] == 0 ? x_out : x_prev));
-        if ((double)c >= r[i]) { kc = k; break; }
-    }
-    chain[i] = kc;
-    uint32_t o[4];
-    lane_selftest_one(n, list_view_of(cl, wide, n_cl, piv_off), n_cl, pp, w_out, w_prev, r[i], o);
-    out4[4 * i] = o[0]; out4[4 * i + 1] = o[1]; out4[4 * i + 2] = o[2]; out4[4 * i + 3] = o[3];
-}
-}  // namespace pw
-
-namespace pw {
-// the FLOATS form of the lane kernel for one target: row total by lane_chain(r = +inf), then the search over w / tot
-PW_HD void lane_floats_one(uint32_t n, const ListView &cl, uint32_t n_cl, uint32_t pp, float w_out, float w_prev, double r,
-                           uint32_t *choice, float *tot) {
-    uint32_t reads = 0;
-    float rowsum = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double inf = __longlong_as_double(0x7ff0000000000000ll);
-#else
-    const double inf = INFINITY;
-#endif
-    uint32_t res = lane_chain<true>(n, n_cl, pp, inf, 1.0f, w_out, w_prev, cl, reads, &rowsum);
-    *tot = rowsum;
-    if (res != LANE_CHAIN_END) { *choice = res; return; }   // (LANE_TIE)
-    // round 5: the float64-bounded decision first (what the kernel does with the total from its table), the chain over
-    // w / tot only where that leaves the step open
-    uint32_t probes = 0, ks = 0;
-    const uint32_t b = lane_decide_unit_bounded(n, n_cl, pp, r, rowsum, w_out, w_prev, cl, probes, ks);
-    if (b <= n) { *choice = b == n ? LANE_CHAIN_END : b; return; }
-    *choice = lane_chain<true>(n, n_cl, pp, r, 1.0f / rowsum, w_out / rowsum, w_prev / rowsum, cl, reads);
-}
-
-__global__ void __launch_bounds__(256)
-lane_floats_selftest_kernel(const uint8_t *cls, uint32_t n, const void *cl, uint32_t wide, uint32_t piv_off, uint32_t n_cl, uint32_t pp, float w_out,
-                            float w_prev, const double *r, uint32_t n_r, uint32_t *chain, uint32_t *lane, float *tots) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_r) return;
-    float tot = 0.0f;   // the reference: sequential float32 w.sum(), w / tot, cumsum, searchsorted -- by this thread
-    for (uint32_t k = 0; k < n; k++) tot = tot + (cls[k] == 1 ? 1.0f : (cls[k] == 0 ? w_out : w_prev));
-    const float x_in = 1.0f / tot, x_out = w_out / tot, x_prev = w_prev / tot;
-    float c = 0.0f;
-    uint32_t kc = n;
-    for (uint32_t k = 0; k < n; k++) {
-        c = c + (cls[k] == 1 ? x_in : (cls[k] == 0 ? x_out : x_prev));
-        if ((double)c >= r[i]) { kc = k; break; }
-    }
-    chain[i] = kc;
-    float tl = 0.0f;
-    uint32_t ch = 0;
-    lane_floats_one(n, list_view_of(cl, wide, n_cl, piv_off), n_cl, pp, w_out, w_prev, r[i], &ch, &tl);
-    lane[i] = ch;
-    tots[2 * i] = tot;
-    tots[2 * i + 1] = tl;
-}
-}  // namespace pw
-
-// The FLOATS form of a lane-kernel step (1/p or 1/q not a power of two: arbitrary float32 row values): chain[i] = the
-// reference's position for draw r[i] (sequential float32 w.sum(), w / tot, cumsum, searchsorted), lane[i] = the same by
-// two closed-form chains of one thread (0xfffffffb: never reached, 0xfffffffa: tie budget), tots[2 i], tots[2 i + 1] =
-// the sequential row total and the thread's.  on_device: one GPU thread per target.
-PW_EXPORT int pw_selftest_lane_floats(int on_device, int device, const uint8_t *cls, uint32_t n, float w_out, float w_prev,
-                                      const double *r, uint32_t n_r, uint32_t *chain, uint32_t *lane, float *tots) {
-    if (!cls || !r || !chain || !lane || !tots || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    LaneRow row;
-    int rc = lane_row_setup(cls, n, w_out, w_prev, row, false);
-    if (rc) return rc;
-    if (!on_device) {
-        float tot = 0.0f;
-        for (uint32_t k = 0; k < n; k++) tot = tot + (cls[k] == 1 ? 1.0f : (cls[k] == 0 ? w_out : w_prev));
-        const float x_in = 1.0f / tot, x_out = w_out / tot, x_prev = w_prev / tot;
-        std::vector<float> c(n);
-        float acc = 0.0f;
-        for (uint32_t k = 0; k < n; k++) { acc = acc + (cls[k] == 1 ? x_in : (cls[k] == 0 ? x_out : x_prev)); c[k] = acc; }
-        for (uint32_t i = 0; i < n_r; i++) {
-            uint32_t lo = 0, hi = n;
-            while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((double)c[mid] >= r[i]) hi = mid; else lo = mid + 1; }
-            chain[i] = lo;
-            float tl = 0.0f;
-            pw::lane_floats_one(n, row.view(), row.n_cl, row.pp, w_out, w_prev, r[i], &lane[i], &tl);
-            tots[2 * (size_t)i] = tot;
-            tots[2 * (size_t)i + 1] = tl;
-        }
-        return PW_OK;
-    }
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<uint8_t> d_cls;
-    DevBuf<void> d_cl;
-    DevBuf<double> d_r;
-    DevBuf<uint32_t> d_chain, d_lane;
-    DevBuf<float> d_tots;
-    const size_t cl_bytes = row.wide ? row.cl32.size() * sizeof(uint32_t) : row.cl16.size() * sizeof(uint16_t);
-    const void *cl_host = row.wide ? (const void *)row.cl32.data() : (const void *)row.cl16.data();
-    const size_t nr = n_r ? n_r : 1;
-    hipError_t e = d_cls.alloc(n);
-    if (e == hipSuccess) e = d_cl.alloc(cl_bytes);
-    if (e == hipSuccess) e = d_r.alloc(nr);
-    if (e == hipSuccess) e = d_chain.alloc(nr);
-    if (e == hipSuccess) e = d_lane.alloc(nr);
-    if (e == hipSuccess) e = d_tots.alloc(2 * nr);
-    if (e == hipSuccess) e = hipMemcpy(d_cls.p, cls, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cl.p, cl_host, cl_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_r) e = hipMemcpy(d_r.p, r, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_r) {
-        hipLaunchKernelGGL(pw::lane_floats_selftest_kernel, dim3((n_r + 255) / 256), dim3(256), 0, 0, d_cls.p, n, d_cl.p, row.wide, row.piv_off, row.n_cl,
-                           row.pp, w_out, w_prev, d_r.p, n_r, d_chain.p, d_lane.p, d_tots.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(chain, d_chain.p, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(lane, d_lane.p, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(tots, d_tots.p, sizeof(float) * 2 * (size_t)n_r, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_lane_floats: ") + hipGetErrorString(e));
-    return PW_OK;
-}
-
-// The bounded decision of the FLOATS form alone (host): lane[i] = lane_decide_unit_bounded's verdict for draw r[i] given the
-// row's sequential float32 total -- the position, n (never reached) or 0xfffffffd (left open) -- and chain[i] = the
-// reference's position (sequential float32 w.sum(), w / tot, cumsum, searchsorted; n: never reached).
-PW_EXPORT int pw_selftest_lane_unit_bounded(const uint8_t *cls, uint32_t n, float w_out, float w_prev, const double *r, uint32_t n_r,
-                                            uint32_t *chain, uint32_t *lane) {
-    if (!cls || !r || !chain || !lane || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    LaneRow row;
-    int rc = lane_row_setup(cls, n, w_out, w_prev, row, false);
-    if (rc) return rc;
-    float tot = 0.0f;
-    for (uint32_t k = 0; k < n; k++) tot = tot + (cls[k] == 1 ? 1.0f : (cls[k] == 0 ? w_out : w_prev));
-    const float x_in = 1.0f / tot, x_out = w_out / tot, x_prev = w_prev / tot;
-    std::vector<float> c(n);
-    float acc = 0.0f;
-    for (uint32_t k = 0; k < n; k++) { acc = acc + (cls[k] == 1 ? x_in : (cls[k] == 0 ? x_out : x_prev)); c[k] = acc; }
-    for (uint32_t i = 0; i < n_r; i++) {
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((double)c[mid] >= r[i]) hi = mid; else lo = mid + 1; }
-        chain[i] = lo;
-        uint32_t probes = 0, ks = 0;
-        lane[i] = pw::lane_decide_unit_bounded(n, row.n_cl, row.pp, r[i], tot, w_out, w_prev, row.view(), probes, ks);
-        if (lane[i] > n && lane[i] != pw::LANE_AMBIGUOUS) return fail(PW_ERR_INVALID, "unexpected verdict");
-        if (ks > lo) return fail(PW_ERR_INVALID, "k_safe beyond the reference's position");
-    }
-    return PW_OK;
-}
-
-// The FLOATS step with the interval decision in front of the chain (round 6): lane[i] = lane_decide_unit_bounded's verdict,
-// tight[i] = that verdict when it is one, else lane_tight_values' (position, or 0xfffffffd: left to the float chain).
-PW_EXPORT int pw_selftest_lane_unit_tight(const uint8_t *cls, uint32_t n, float w_out, float w_prev, const double *r, uint32_t n_r,
-                                          uint32_t *chain, uint32_t *lane, uint32_t *tight) {
-    if (!cls || !r || !chain || !lane || !tight || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    LaneRow row;
-    int rc = lane_row_setup(cls, n, w_out, w_prev, row, false);
-    if (rc) return rc;
-    float tot = 0.0f;
-    for (uint32_t k = 0; k < n; k++) tot = tot + (cls[k] == 1 ? 1.0f : (cls[k] == 0 ? w_out : w_prev));
-    const float x_in = 1.0f / tot, x_out = w_out / tot, x_prev = w_prev / tot;
-    std::vector<float> c(n);
-    float acc = 0.0f;
-    for (uint32_t k = 0; k < n; k++) { acc = acc + (cls[k] == 1 ? x_in : (cls[k] == 0 ? x_out : x_prev)); c[k] = acc; }
-    for (uint32_t i = 0; i < n_r; i++) {
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((double)c[mid] >= r[i]) hi = mid; else lo = mid + 1; }
-        chain[i] = lo;
-        uint32_t probes = 0, ks = 0;
-        pw::BoundedAmb amb;
-        lane[i] = pw::lane_decide_unit_bounded(n, row.n_cl, row.pp, r[i], tot, w_out, w_prev, row.view(), probes, ks, &amb);
-        if (lane[i] > n && lane[i] != pw::LANE_AMBIGUOUS) return fail(PW_ERR_INVALID, "unexpected verdict");
-        if (ks > lo) return fail(PW_ERR_INVALID, "k_safe beyond the reference's position");
-        tight[i] = lane[i];
-        if (lane[i] == pw::LANE_AMBIGUOUS && ks > 0) tight[i] = pw::lane_tight_values(n, row.pp, r[i], x_in, x_out, x_prev, ks, amb.f, amb.p_next, amb.z_abs);
-    }
-#if !defined(__HIP_DEVICE_COMPILE__)
-    if (getenv("PW_TIGHT_STATS")) {
-        fprintf(stderr, "tight bail reasons:");
-        for (int k = 1; k < 24; k++) if (pw::g_tight_reason[k]) fprintf(stderr, " [%d]=%llu", k, (unsigned long long)pw::g_tight_reason[k]);
-        fprintf(stderr, "\n");
-    }
-#endif
-    return PW_OK;
-}
-
-PW_EXPORT int pw_selftest_lane(int on_device, int device, const uint8_t *cls, uint32_t n, float w_out, float w_prev, const double *r,
-                               uint32_t n_r, uint32_t *chain, uint32_t *lane, uint32_t *kmax, uint32_t *tight,
-                               uint32_t *chain_lane) {
-    if (!cls || !r || !chain || !lane || !kmax || !tight || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    LaneRow row;
-    int rc = lane_row_setup(cls, n, w_out, w_prev, row);
-    if (rc) return rc;
-    if (!on_device) {
-        // the chain once: prefix sums, then one binary search per draw (the sums are non-decreasing)
-        std::vector<float> c(n);
-        float acc = 0.0f;
-        for (uint32_t k = 0; k < n; k++) {
-            acc = acc + (cls[k] == 1 ? row.x_in : (cls[k] == 0 ? row.x_out : row.x_prev));
-            c[k] = acc;
-        }
-        for (uint32_t i = 0; i < n_r; i++) {
-            uint32_t lo = 0, hi = n;
-            while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((double)c[mid] >= r[i]) hi = mid; else lo = mid + 1; }
-            chain[i] = lo;
-            uint32_t o[4];
-            pw::lane_selftest_one(n, row.view(), row.n_cl, row.pp, w_out, w_prev, r[i], o);
-            lane[i] = o[0]; kmax[i] = o[1]; tight[i] = o[2];
-            if (chain_lane) chain_lane[i] = o[3];
-        }
-#if !defined(__HIP_DEVICE_COMPILE__)
-        if (getenv("PW_TIGHT_STATS")) {
-            fprintf(stderr, "tight bail reasons:");
-            for (int k = 1; k < 24; k++) if (pw::g_tight_reason[k]) fprintf(stderr, " [%d]=%llu", k, (unsigned long long)pw::g_tight_reason[k]);
-            fprintf(stderr, "\n");
-        }
-#endif
-        return PW_OK;
-    }
-    if (int rc = check_device(device)) return rc;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<uint8_t> d_cls;
-    DevBuf<void> d_cl;
-    DevBuf<double> d_r;
-    DevBuf<uint32_t> d_chain, d_out;
-    const size_t cl_bytes = row.wide ? row.cl32.size() * sizeof(uint32_t) : row.cl16.size() * sizeof(uint16_t);
-    const void *cl_host = row.wide ? (const void *)row.cl32.data() : (const void *)row.cl16.data();
-    hipError_t e = d_cls.alloc(n);
-    if (e == hipSuccess) e = d_cl.alloc(cl_bytes);
-    if (e == hipSuccess) e = d_r.alloc(n_r);
-    if (e == hipSuccess) e = d_chain.alloc(n_r);
-    if (e == hipSuccess) e = d_out.alloc(4 * (size_t)n_r);
-    if (e == hipSuccess) e = hipMemcpy(d_cls.p, cls, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cl.p, cl_host, cl_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_r) e = hipMemcpy(d_r.p, r, sizeof(double) * (size_t)n_r, hipMemcpyHostToDevice);
-    std::vector<uint32_t> out4((size_t)4 * n_r);
-    if (e == hipSuccess && n_r) {
-        hipLaunchKernelGGL(pw::lane_selftest_kernel, dim3((n_r + 255) / 256), dim3(256), 0, 0, d_cls.p, n, d_cl.p, row.wide, row.piv_off, row.n_cl, row.pp,
-                           w_out, w_prev, d_r.p, n_r, d_chain.p, d_out.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(chain, d_chain.p, sizeof(uint32_t) * (size_t)n_r, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out4.data(), d_out.p, sizeof(uint32_t) * 4 * (size_t)n_r, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) return fail(PW_ERR_HIP, std::string("pw_selftest_lane: ") + hipGetErrorString(e));
-    for (uint32_t i = 0; i < n_r; i++) {
-        lane[i] = out4[4 * (size_t)i]; kmax[i] = out4[4 * (size_t)i + 1]; tight[i] = out4[4 * (size_t)i + 2];
-        if (chain_lane) chain_lane[i] = out4[4 * (size_t)i + 3];
-    }
-    return PW_OK;
-}
-
-// The weighted-row decision of the lane kernel (seqscan.h: lane_decide_weighted) on a host row, beside the reference's
-// sequential float32 chain.  vals[k] = the step's value of neighbour k before normalisation, base[k] = its base value
-// (what it would be as a plain "out" neighbour), cls[k] = 0 other (vals == base) / 1 common neighbour / 2 prev.
-PW_EXPORT int pw_selftest_lane_weighted(const float *vals, const float *base, const uint8_t *cls, uint32_t n, const double *r,
-                                        uint32_t n_r, uint32_t *chain, uint32_t *lane) {
-    if (!vals || !base || !cls || !r || !chain || !lane || n == 0) return fail(PW_ERR_INVALID, "bad argument");
-    float tot = 0.0f;
-    for (uint32_t k = 0; k < n; k++) tot = tot + vals[k];                     // sequential float32 w.sum()
-    std::vector<float> c(n);
-    float acc = 0.0f;
-    for (uint32_t k = 0; k < n; k++) { acc = acc + vals[k] / tot; c[k] = acc; }   // cumsum of fl32(w / tot)
-    std::vector<pw::PrefixPair> pq(n);
-    std::vector<double> dl;
-    double trun = 0.0;
-    bool any_pos = false, any_neg = false;
-    std::vector<uint16_t> cl16;
-    std::vector<uint32_t> cl32;
-    const uint32_t wide = n > 65536u ? 1u : 0u;
-    double run = 0.0, drun = 0.0, dprev = 0.0;
-    uint32_t pp = 0xffffffffu;
-    for (uint32_t k = 0; k < n; k++) {
-        run += (double)base[k];
-        trun += run;
-        pq[k] = pw::PrefixPair{run, trun};
-        if (cls[k] == 1) {
-            if (vals[k] > base[k]) any_pos = true;
-            if (vals[k] < base[k]) any_neg = true;
-            drun += (double)vals[k] - (double)base[k];
-            dl.push_back(drun);
-            if (wide) cl32.push_back(k); else cl16.push_back((uint16_t)k);
-        } else if (cls[k] == 2) {
-            if (pp != 0xffffffffu) return fail(PW_ERR_INVALID, "at most one prev");
-            pp = k;
-            dprev = (double)vals[k] - (double)base[k];
-        } else if (cls[k] != 0 || vals[k] != base[k]) return fail(PW_ERR_INVALID, "class 0 elements carry their base value");
-    }
-    const uint32_t n_cl = (uint32_t)dl.size();
-    cl16.resize(cl16.size() + 8, 0xffffu);
-    cl32.resize(cl32.size() + 8, 0xffffffffu);
-    uint32_t piv_off = 0;
-    if (pw::list_has_pivots(wide, n_cl)) {
-        const uint32_t np = pw::list_pivot_count(wide), step = pw::list_pivot_step(wide, n_cl);
-        piv_off = (uint32_t)(wide ? cl32.size() : cl16.size());
-        for (uint32_t k = 0; k < np; k++) { if (wide) cl32.push_back(cl32[(size_t)(k + 1) * step]); else cl16.push_back(cl16[(size_t)(k + 1) * step]); }
-    }
-    dl.push_back(0.0);
-    const pw::ListView view = pw::list_view_of(wide ? (const void *)cl32.data() : (const void *)cl16.data(), wide, n_cl, piv_off);
-    if (any_pos && any_neg) return fail(PW_ERR_INVALID, "the common neighbours' differences must share one sign (that of q - 1)");
-    const pw::WeightedRow wr{pq.data(), dl.data(), dprev, !any_neg};
-    for (uint32_t i = 0; i < n_r; i++) {
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((double)c[mid] >= r[i]) hi = mid; else lo = mid + 1; }
-        chain[i] = lo;
-        uint32_t probes = 0, k_safe = 0;
-        lane[i] = pw::lane_decide_weighted(n, n_cl, pp, r[i], tot, wr, view, probes, k_safe);
-        if (k_safe > chain[i]) return fail(PW_ERR_INVALID, "lane_decide_weighted: k_safe beyond the chain's position");
-    }
-    return PW_OK;
-}
-
-// ---- node2vec+ thresholds (host only) -----------------------------------------------------------------
-PW_EXPORT int pw_noise_thresholds_csr(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr) {
-    if (!indptr || !thr || (!data && indptr[n_nodes] != 0)) return fail(PW_ERR_INVALID, "null pointer");
-    pw::noise_thresholds_csr(indptr, data, n_nodes, gamma, thr);
-    return PW_OK;
-}
-
-PW_EXPORT int pw_noise_thresholds_csr_numpy1(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr) {
-    if (!indptr || !thr || (!data && indptr[n_nodes] != 0)) return fail(PW_ERR_INVALID, "null pointer");
-    pw::noise_thresholds_csr(indptr, data, n_nodes, gamma, thr, true);
-    return PW_OK;
-}
-
-PW_EXPORT int pw_noise_thresholds_csr_f64(const uint32_t *indptr, const float *data, uint32_t n_nodes, double gamma, float *thr) {
-    if (!indptr || !thr) return fail(PW_ERR_INVALID, "null pointer");
-    pw::noise_thresholds_csr_f64(indptr, data, n_nodes, gamma, thr);
-    return PW_OK;
-}
-
-PW_EXPORT int pw_noise_thresholds_dense(const double *data, uint32_t n_nodes, double gamma, float *thr) {
-    if (!data || !thr) return fail(PW_ERR_INVALID, "null pointer");
-    pw::noise_thresholds_dense(data, n_nodes, gamma, thr);
-    return PW_OK;
-}
-
-// ---- edge-list ingestion (host only) ----------------------------------------------------------------
-PW_EXPORT int pw_selftest_thresholds_row(const double *row, uint64_t n, double gamma, float *thr) {
-    if ((n && !row) || !thr) return fail(PW_ERR_INVALID, "null pointer");
-    *thr = pw::threshold_row([row](uint64_t i) { return row[i]; }, n, gamma);
-    return PW_OK;
-}
-
-struct pw_edgelist {
-    pw::EdgeList el;
-};
-
-PW_EXPORT int pw_edgelist_read(const char *path, int weighted, int directed, const char *delimiter, pw_edgelist **out) {
-    if (!path || !out) return fail(PW_ERR_INVALID, "null pointer");
-    *out = nullptr;
-    pw_edgelist *h = new (std::nothrow) pw_edgelist();
-    if (!h) return fail(PW_ERR_NOMEM, "out of host memory");
-    int st;
-    try {
-        st = pw::read_edgelist(path, weighted != 0, directed != 0, delimiter, h->el);
-    } catch (const std::bad_alloc &) {
-        delete h;
-        return fail(PW_ERR_NOMEM, "out of host memory while reading the edge list");
-    }
-    if (st == pw::EL_OK) { *out = h; return PW_OK; }
-    delete h;
-    if (st == pw::EL_IO_ERROR) return fail(PW_ERR_INVALID, std::string("cannot read ") + path);
-    return fail(PW_ERR_UNSUPPORTED, "edge list needs the statement-by-statement reader");
-}
-
-PW_EXPORT int pw_edgelist_shape(const pw_edgelist *e, uint64_t *n_nodes, uint64_t *nnz, uint64_t *insertions,
-                                uint64_t *id_bytes) {
-    if (!e) return fail(PW_ERR_INVALID, "null pointer");
-    if (n_nodes) *n_nodes = e->el.indptr.size() - 1;
-    if (nnz) *nnz = e->el.indices.size();
-    if (insertions) *insertions = e->el.insertions;
-    if (id_bytes) *id_bytes = e->el.id_chars.size();
-    return PW_OK;
-}
-
-PW_EXPORT int pw_edgelist_export(const pw_edgelist *e, uint32_t *indptr, uint32_t *indices, float *data,
-                                 double *data64, uint64_t *id_offsets, char *id_chars) {
-    if (!e) return fail(PW_ERR_INVALID, "null pointer");
-    const pw::EdgeList &el = e->el;
-    if (indptr) memcpy(indptr, el.indptr.data(), sizeof(uint32_t) * el.indptr.size());
-    if (indices && !el.indices.empty()) memcpy(indices, el.indices.data(), sizeof(uint32_t) * el.indices.size());
-    if (data && !el.data.empty()) memcpy(data, el.data.data(), sizeof(float) * el.data.size());
-    if (data64 && !el.data64.empty()) memcpy(data64, el.data64.data(), sizeof(double) * el.data64.size());
-    if (id_offsets) memcpy(id_offsets, el.id_off.data(), sizeof(uint64_t) * el.id_off.size());
-    if (id_chars && !el.id_chars.empty()) memcpy(id_chars, el.id_chars.data(), el.id_chars.size());
-    return PW_OK;
-}
-
-PW_EXPORT void pw_edgelist_destroy(pw_edgelist *e) { delete e; }
-
-PW_EXPORT int pw_selftest_seqscan_f32(const float *x, uint32_t n, double r, int use_target, uint32_t chunk,
-                                      uint32_t *index, float *sum) {
-    if (!x || !index || !sum || chunk == 0) return fail(PW_ERR_INVALID, "bad argument");
-    *index = seqscan_emulate<float>(x, n, r, use_target != 0, chunk, sum);
-    return PW_OK;
-}
-
-PW_EXPORT int pw_selftest_seqscan_f64(const double *x, uint32_t n, double r, int use_target, uint32_t chunk,
-                                      uint32_t *index, double *sum) {
-    if (!x || !index || !sum || chunk == 0) return fail(PW_ERR_INVALID, "bad argument");
-    *index = seqscan_emulate<double>(x, n, r, use_target != 0, chunk, sum);
-    return PW_OK;
-}
+#include "drv_selftest.hip.h"
+#include "drv_ingest_host.hip.h"
