@@ -622,6 +622,42 @@ int pw_selftest_sample_non_edges(int on_device, int device, const uint32_t *indp
                                  uint32_t seed, uint64_t first_candidate, uint64_t m, uint64_t batch, uint32_t *u, uint32_t *v,
                                  uint64_t *candidates_used);
 
+/* ---- neighbourhood link-prediction baselines in device memory: common neighbours, Jaccard, preferential attachment, table sums ----
+ * The definition is written at the top of csrc/nbr_scores.hip.h (DESIGN.md 4.11 repeats it); host and device answer it
+ * identically, whatever the grid, the tile or the cut between the kernel's two forms.  N(x) = the entries of row x other than x
+ * itself (weights are not looked at; a directed graph's out-row), d(x) = |N(x)|, C(u, v) = N(u) n N(v), cn = |C|.  Refusals:
+ * PW_ERR_INVALID with a message that names the first offending element, nothing written; dense handles: PW_ERR_UNSUPPORTED.
+ *   pw_nbr_degrees_device   d_deg (device uint32[n_nodes]) receives d(x).
+ *   pw_nbr_scores_device    d_score[i] (device float64[m]) = the score of the pair (d_u[i], d_v[i]) (device uint32[m]) by `kind`:
+ *                PW_NBR_COMMON    double(cn)
+ *                PW_NBR_JACCARD   double(cn) / double(d(u) + d(v) - cn): one IEEE division, +0.0 when the denominator is 0
+ *                PW_NBR_PREF      double(uint64(d(u)) * uint64(d(v))): the product exact, one rounding in the conversion
+ *                PW_NBR_WEIGHTED  (((+0.0 + t[z0]) + t[z1]) + ...) over z in C ascending, one rounding per addition; t = d_table,
+ *                                 device float64[n_nodes], a NaN or an infinity in it an ordinary value.  Adamic-Adar and
+ *                                 resource allocation are this kind with t[z] = 1 / ln d(z) and 1 / d(z) (0.0 for d(z) < 2),
+ *                                 a table the caller builds: the library evaluates no log.
+ *                d_table is read by PW_NBR_WEIGHTED only (NULL there: refused) and may be NULL otherwise.  u[i] == v[i], repeated
+ *                pairs and pairs that are edges are pairs like any other; m = 0 is a valid call that does nothing.  A row number
+ *                >= n_nodes is refused ("u[i]" before "v[i]" at one position); an unknown kind is refused.
+ * Test hooks on HOST pointers (the CSR as host arrays, rows ascending and duplicate-free; on_device = 0: the host build of the
+ * definition, plain loops, usable without a GPU; otherwise upload, the kernels, download): pw_selftest_nbr_degrees and
+ * pw_selftest_nbr_scores.  short_max forces the cut between the kernel's forms: a pair whose shorter row has at most short_max
+ * entries is settled by one lane, the others by the whole wavefront -- 0 sends every pair to the wavefront, 0xFFFFFFFF leaves
+ * every pair with its lane, -1 selects the library's default.  No result depends on it.
+ * pw_nbr_scores_device_cut is pw_nbr_scores_device with that cut forced and, when kernel_ms is not NULL, the device time of the
+ * score kernel alone (two events around it) in ms: the measurement hook of tools/nbr_bench.py. */
+enum { PW_NBR_COMMON = 0, PW_NBR_JACCARD = 1, PW_NBR_PREF = 2, PW_NBR_WEIGHTED = 3 };
+int pw_nbr_degrees_device(pw_graph *g, uint32_t *d_deg);
+int pw_nbr_scores_device(pw_graph *g, const uint32_t *d_u, const uint32_t *d_v, uint64_t m, int kind, const double *d_table,
+                         double *d_score);
+int pw_nbr_scores_device_cut(pw_graph *g, const uint32_t *d_u, const uint32_t *d_v, uint64_t m, int kind, const double *d_table,
+                             double *d_score, int64_t short_max, float *kernel_ms);
+int pw_selftest_nbr_scores(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes,
+                           const uint32_t *u, const uint32_t *v, uint64_t m, int kind, const double *table, int64_t short_max,
+                           double *score);
+int pw_selftest_nbr_degrees(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes,
+                            uint32_t *deg);
+
 /* ---- edges held out by the seeded stream: the train graph and the held-out pairs, in device memory ----------------------
  * The definition is written at the top of csrc/holdout.hip.h (DESIGN.md 4.10 repeats it); host and device answer it
  * identically, whatever the grid or the batch of words expanded at a time.

@@ -151,6 +151,8 @@ class PwKnnTiles(C.Structure):
 PW_KNN_MAX_TOPN = 128
 KNN_METRICS = {"dot": 0, "cosine": 1}   # PW_KNN_DOT, PW_KNN_COSINE
 KNN_QT = 8                              # queries a wavefront keeps accumulators for (csrc/knn.hip.h)
+NBR_KINDS = {"common_neighbours": 0, "jaccard": 1, "preferential_attachment": 2, "weighted": 3}   # PW_NBR_* (csrc/nbr_scores.hip.h)
+NBR_ALL_LANE = 0xFFFFFFFF               # short_max of pw_selftest_nbr_scores: every pair stays with its lane; -1: the default
 ERR_INVALID = -1                        # PW_ERR_INVALID
 
 
@@ -329,6 +331,13 @@ SYMBOLS = {
     "pw_selftest_auc": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pw_selftest_sample_non_edges": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                                C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "pw_nbr_degrees_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pw_nbr_scores_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "pw_nbr_scores_device_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.POINTER(C.c_float)]),
+    "pw_selftest_nbr_scores": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                         C.c_void_p, C.c_int64, C.c_void_p]),
+    "pw_selftest_nbr_degrees": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "pw_holdout_edges_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_void_p),
                                           C.POINTER(C.c_void_p), _f64p]),
     "pw_holdout_dev_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3),

@@ -13,6 +13,10 @@ also prints the exact AUC of the two sets of scores (``linkpred``).
 ``--task split`` holds out a seeded share of the graph's edges on the GPU (``Base.holdout_edges``): the train graph goes to
 ``--output`` as a CSR ``.npz``, the held-out pairs to ``--pairs`` and, with ``--neg_pairs``, as many non-edges of the original graph
 there -- the files ``--task score`` reads.  ``split``, a normal run on the train ``.npz``, ``score``: the link-prediction protocol.
+``--task baseline`` scores the pairs of ``--pairs`` by a neighbourhood heuristic of the graph given as ``--input`` (``--heuristic``:
+common neighbours, Jaccard, Adamic-Adar, resource allocation, preferential attachment; ``Base.neighbour_scores``) and, with
+``--neg_pairs``, prints the same ``auc wins ties m n`` line: the protocol's baseline rows.  The protocol's baseline is computed on the
+TRAIN graph (``--input train.npz``, what ``--task split`` wrote), not on the original, whose edges include the answers.
 The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
@@ -28,18 +32,24 @@ from . import pecanpy
 from .wrappers import Timer
 
 MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "SparseOTF")
+HEURISTICS = ("common_neighbours", "jaccard", "adamic_adar", "resource_allocation", "preferential_attachment")   # --task baseline
 
 # (flag, argparse keywords) -- one table instead of twenty add_argument calls
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
-    ("--output", dict(required=True, help="embedding file (.npz -> IDs/data arrays, else word2vec text)")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score", "split"),
+    ("--output", dict(default=None, help="embedding file (.npz -> IDs/data arrays, else word2vec text); required by every task but "
+                                         "baseline")),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score", "split", "baseline"),
                     help="run node2vec; only convert the edge list to CSR / dense .npz; (walks) generate the walks and "
                          "write them, one per line, to --output, no training; (train) train embeddings from a walk "
                          "corpus file given as --input, no graph; or (neighbours) the nearest neighbours of the nodes of an "
                          "embedding file given as --input, no graph; or (score) the score of every node pair of --pairs by an "
                          "embedding file given as --input, no graph; or (split) hold out --holdout_fraction of the edges of the "
-                         "graph: the train graph as a CSR .npz to --output, the held-out pairs to --pairs")),
+                         "graph: the train graph as a CSR .npz to --output, the held-out pairs to --pairs; or (baseline) the "
+                         "score of every node pair of --pairs by the neighbourhood heuristic --heuristic of the graph given as "
+                         "--input (a sparse --mode), written to --output when given.  The link-prediction protocol computes its "
+                         "baseline on the TRAIN graph (--input train.npz from --task split), not on the original graph, whose "
+                         "edges include the answers")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
     ("--walk-length", dict(type=int, default=80, help="steps per walk")),
@@ -72,11 +82,14 @@ _OPTIONS = (
     ("--topn", dict(type=int, default=10, help="--task neighbours: neighbours per query")),
     ("--metric", dict(default="cosine", choices=("cosine", "dot"), help="--task neighbours / score: the score")),
     ("--queries", dict(default=None, metavar="FILE", help="--task neighbours: one node ID per line (default: every node)")),
-    ("--pairs", dict(default=None, metavar="FILE", help="--task score: two node IDs per line, separated by --delimiter; "
+    ("--pairs", dict(default=None, metavar="FILE", help="--task score / baseline: two node IDs per line, separated by --delimiter; "
                                                         "--task split: receives the held-out pairs in that form")),
     ("--neg_pairs", dict(default=None, metavar="FILE",
-                         help="--task score: negative pairs in the same form; prints 'auc wins ties m n' of --pairs against them; "
+                         help="--task score / baseline: negative pairs in the same form; prints 'auc wins ties m n' of --pairs "
+                              "against them; "
                               "--task split: receives as many non-edges of the original graph as there are held-out pairs")),
+    ("--heuristic", dict(default=None, choices=HEURISTICS, metavar="KIND",
+                         help="--task baseline: the neighbourhood heuristic, one of " + ", ".join(HEURISTICS))),
     ("--holdout_fraction", dict(type=float, default=0.5, help="--task split: the share of the edges to hold out, in [0, 1)")),
     ("--no_protect", dict(action="store_true", help="--task split: do not keep the first edge of every node in the train graph")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
@@ -93,8 +106,17 @@ def parse_args(argv=None):
     for flag, kw in _OPTIONS:
         parser.add_argument(flag, **kw)
     args = parser.parse_args(argv)
-    if args.task in ("score", "split") and not args.pairs:
+    if args.task != "baseline" and args.output is None:
+        parser.error("the following arguments are required: --output")
+    if args.task in ("score", "split", "baseline") and not args.pairs:
         parser.error(f"--task {args.task} needs --pairs")
+    if args.task == "baseline":
+        if not args.heuristic:
+            parser.error("--task baseline needs --heuristic")
+        if args.mode == "DenseOTF":
+            parser.error("--task baseline needs a sparse --mode, not DenseOTF")
+        if not args.output and not args.neg_pairs:
+            parser.error("--task baseline needs --output, --neg_pairs or both: there is nothing to write otherwise")
     return args
 
 
@@ -456,6 +478,28 @@ def split_to_files(args, g):
               f"({g.last_holdout_stats['protected']} protected)")
 
 
+@Timer("score pairs by a neighbourhood heuristic")
+def baseline_from_graph(args, g):
+    """``--task baseline``: ``--input`` is a graph, read as ``--task split`` reads it (a sparse ``--mode``); in the link-prediction
+    protocol it is the TRAIN graph that ``--task split`` wrote, not the original, whose edges include the answers.  ``--pairs`` is a
+    file of node pairs, mapped to rows as ``--task score`` maps them; ``--output``, when given, gets one line
+    ``id_u<delimiter>id_v<delimiter>score`` per pair, the score as ``repr(float)`` (``Base.neighbour_scores``: exact).  With
+    ``--neg_pairs`` the line ``auc wins ties m n`` goes to stdout (``linkpred.auc``)."""
+    from . import linkpred
+
+    row_of = {name: i for i, name in enumerate(g.nodes)}
+    nu, nv, ru, rv = _read_pairs(args.pairs, args.delimiter, row_of)
+    neg = _read_pairs(args.neg_pairs, args.delimiter, row_of) if args.neg_pairs else None
+    d_pos = g.neighbour_scores(ru, rv, args.heuristic)
+    result = linkpred.auc(d_pos, g.neighbour_scores(neg[2], neg[3], args.heuristic)) if neg else None
+    d = args.delimiter
+    if args.output:
+        with open(args.output, "w", encoding="utf-8", newline="\n") as f:
+            f.write("".join(f"{a}{d}{b}{d}{float(s)!r}\n" for a, b, s in zip(nu, nv, d_pos.cpu().numpy())))
+    if result:
+        print(f"{result[0]!r} {result[1]} {result[2]} {len(nu)} {len(neg[0])}")
+
+
 def main(argv=None):
     """read graph -> preprocess -> walks (GPU) -> embeddings; ``--task train``: corpus file -> embeddings; ``--task
     neighbours``: embedding file -> nearest neighbours."""
@@ -474,6 +518,9 @@ def main(argv=None):
     g = read_graph(args)
     if args.task == "split":
         split_to_files(args, g)
+        return
+    if args.task == "baseline":
+        baseline_from_graph(args, g)
         return
     preprocess(g)
     if args.task == "walks":

@@ -4302,6 +4302,8 @@ PW_EXPORT int pw_selftest_sample_non_edges(int on_device, int device, const uint
     return PW_OK;
 }
 
+#include "drv_nbr.hip.h"
+
 // ---- edges held out by the seeded stream: the train CSR and the held-out pairs (csrc/holdout.hip.h) ---------------------------
 struct pw_holdout_dev {
     int device = 0;

@@ -14,9 +14,15 @@ fraction)``:
         train, (eu, ev, ew), used = g.holdout_edges(0.5, seed=7)    # train: a graph of g's class, its walk handle installed
         nu, nv, _ = g.sample_non_edges(len(eu), seed=7, ...)        # negatives from the ORIGINAL graph g, not from train
 
-``score_pairs_host``, ``auc_host``, ``sample_non_edges_host`` and ``holdout_edges_host`` state the definitions in NumPy, to be
-checked by eye; tests/test_linkpred_host.py, tests/test_gpu_linkpred.py, tests/test_holdout_host.py and
-tests/test_gpu_holdout.py hold the library to them.  There is no CPU fallback: without a GPU
+``neighbour_scores`` (csrc/nbr_scores.hip.h) scores pairs by the graph alone -- common neighbours, Jaccard's coefficient,
+Adamic-Adar, resource allocation, preferential attachment: the baseline rows of the protocol's table -- and ``baseline_auc`` is
+their AUC.  In the protocol they are computed on the TRAIN graph: the original's edges include the answers.
+
+        value, wins, ties = linkpred.baseline_auc(train, (eu, ev), (nu, nv), "adamic_adar")
+
+``score_pairs_host``, ``auc_host``, ``sample_non_edges_host``, ``holdout_edges_host`` and ``neighbour_scores_host`` state the
+definitions in NumPy, to be checked by eye; tests/test_linkpred_host.py, tests/test_gpu_linkpred.py, tests/test_holdout_host.py,
+tests/test_gpu_holdout.py, tests/test_nbr_host.py and tests/test_gpu_nbr.py hold the library to them.  There is no CPU fallback: without a GPU
 the device entry points raise ``PwError`` as every other one does."""
 import ctypes as C
 from fractions import Fraction
@@ -26,7 +32,11 @@ import numpy as np
 from . import _lib
 
 __all__ = ["score_pairs", "auc", "sample_non_edges", "link_auc", "score_pairs_host", "auc_host", "sample_non_edges_host",
-           "candidate_cap", "holdout_edges", "holdout_edges_host", "holdout_threshold"]
+           "candidate_cap", "holdout_edges", "holdout_edges_host", "holdout_threshold", "neighbour_scores", "neighbour_degrees",
+           "degree_table", "neighbour_scores_host", "neighbour_degrees_host", "degree_table_host", "baseline_auc", "HEURISTICS"]
+
+# the kinds of ``neighbour_scores``; the two after the first three are ``weighted`` with a table of the degrees
+HEURISTICS = ("common_neighbours", "jaccard", "preferential_attachment", "adamic_adar", "resource_allocation", "weighted")
 
 
 def _check_value(rc):
@@ -252,6 +262,97 @@ def holdout_edges_host(indptr, indices, data, fraction, seed, directed=False, pr
             (row_of[held].astype(np.uint32), indices[held].astype(np.uint32), weights[held]), nnz)
 
 
+# ---- the neighbourhood heuristics, stated plainly (csrc/nbr_scores.hip.h) ---------------------------------------------------------
+def _degree_function(kind, degrees):
+    """``f(d)`` of the DISTINCT degrees ``d >= 2`` given, in NumPy on the host: ``1 / ln d`` (Adamic-Adar) or ``1 / d`` (resource
+    allocation), float64.  The one place either function is evaluated, for the device path and the statement alike."""
+    x = np.asarray(degrees).astype(np.float64)
+    if kind == "adamic_adar":
+        return 1.0 / np.log(x)
+    if kind == "resource_allocation":
+        return 1.0 / x
+    raise ValueError(f"a degree table is 'adamic_adar' or 'resource_allocation', not {kind!r}")
+
+
+def _check_heuristic(kind, table):
+    if kind not in HEURISTICS:
+        raise ValueError(f"kind must be one of {', '.join(HEURISTICS)}, not {kind!r}")
+    if kind == "weighted" and table is None:
+        raise ValueError("kind 'weighted' needs table=, a float64 value per vertex")
+    if kind != "weighted" and table is not None:
+        raise ValueError(f"table= belongs to kind 'weighted'; {kind!r} builds its own")
+
+
+def _neighbour_sets(indptr, indices):
+    indptr, indices = np.asarray(indptr).astype(np.int64), np.asarray(indices).astype(np.int64)
+    n = indptr.size - 1
+    return [set(indices[indptr[x]:indptr[x + 1]].tolist()) - {x} for x in range(n)]
+
+
+def neighbour_degrees_host(indptr, indices):
+    """``d(x) = |N(x)|`` as uint32 ``[N]``: the entries of row ``x`` other than ``x`` itself."""
+    return np.array([len(s) for s in _neighbour_sets(indptr, indices)], dtype=np.uint32)
+
+
+def degree_table_host(indptr, indices, kind):
+    """The statement of ``degree_table``: float64 ``[N]``, ``t[z] = f(d(z))`` -- ``1 / ln d`` (``adamic_adar``) or ``1 / d``
+    (``resource_allocation``), NumPy's value on the distinct degrees -- and ``0.0`` where ``d(z) < 2``."""
+    deg = neighbour_degrees_host(indptr, indices)
+    distinct = np.unique(deg)
+    distinct = distinct[distinct >= 2]
+    value = dict(zip(distinct.tolist(), _degree_function(kind, distinct).tolist()))
+    return np.array([value.get(int(d), 0.0) for d in deg], dtype=np.float64)
+
+
+def neighbour_scores_host(indptr, indices, u, v, kind, table=None):
+    """The plain-loop statement of the neighbourhood heuristics: float64 ``[m]``.  ``N(x)`` = the entries of row ``x`` other
+    than ``x`` itself (a Python set; weights are not looked at; a directed graph's out-row), ``d(x) = |N(x)|``, ``C = N(u) & N(v)``,
+    ``cn = |C|``:
+
+    ``common_neighbours``         ``float(cn)``
+    ``jaccard``                   ``cn / (d(u) + d(v) - cn)``, one division; ``0.0`` when the denominator is 0
+    ``preferential_attachment``   ``float(d(u) * d(v))``: the integer product, one rounding
+    ``weighted``                  ``s = 0.0; for z in sorted(C): s = s + table[z]`` -- ascending, one rounding per addition
+    ``adamic_adar`` / ``resource_allocation``   ``weighted`` with ``degree_table_host``
+
+    ``u[i] == v[i]``, repeated pairs and edges are pairs like any other.  A row number outside the graph is a ``ValueError`` naming
+    the first position (``u`` before ``v``)."""
+    _check_heuristic(kind, table)
+    nbrs = _neighbour_sets(indptr, indices)
+    n = len(nbrs)
+    u, v = _rows_host(u, "u"), _rows_host(v, "v")
+    if u.shape != v.shape:
+        raise ValueError(f"u and v must have one length, not {u.size} and {v.size}")
+    bad = np.flatnonzero((u >= n) | (v >= n))
+    if bad.size:
+        i = int(bad[0])
+        which, row = ("u", u[i]) if u[i] >= n else ("v", v[i])
+        raise ValueError(f"row number {which}[{i}] = {int(row)} is outside the {n} rows")
+    if kind in ("adamic_adar", "resource_allocation"):
+        table = degree_table_host(indptr, indices, kind)
+    if table is not None:
+        table = np.asarray(table, dtype=np.float64)
+        if table.shape != (n,):
+            raise ValueError(f"table must hold one float64 per vertex ({n}), not shape {list(table.shape)}")
+    score = np.zeros(u.size, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for i, (a, b) in enumerate(zip(u.tolist(), v.tolist())):
+            common = nbrs[a] & nbrs[b]
+            cn, da, db = len(common), len(nbrs[a]), len(nbrs[b])
+            if kind == "common_neighbours":
+                score[i] = float(cn)
+            elif kind == "jaccard":
+                score[i] = cn / (da + db - cn) if da + db - cn else 0.0
+            elif kind == "preferential_attachment":
+                score[i] = float(da * db)
+            else:
+                s = np.float64(0.0)
+                for z in sorted(common):
+                    s = s + table[z]
+                score[i] = s
+    return score
+
+
 # ---- the device entry points -------------------------------------------------------------------------------------------
 def score_pairs(index, u, v, metric="cosine", other=None):
     """``KnnIndex.score_pairs``: a float64 ``[m]`` tensor on the index's device, ``score(A[u[i]], B[v[i]])`` with ``A`` the index's
@@ -401,6 +502,74 @@ def holdout_edges(graph, fraction, seed, directed=False, protect=True, first_wor
     return train, (d_u.to(torch.int64) & 0xFFFFFFFF, d_v.to(torch.int64) & 0xFFFFFFFF, d_w), words_used
 
 
+def _csr_engine_of(graph, what):
+    eng = graph._get_engine()
+    if eng.kind != "csr":
+        raise NotImplementedError(f"{what} needs a sparse (CSR) graph")
+    return eng
+
+
+def neighbour_degrees(graph):
+    """``d(x) = |N(x)|`` -- the entries of row ``x`` other than ``x`` itself -- as an int64 ``[N]`` tensor on the graph's device
+    (``pw_nbr_degrees_device``).  Dense graphs: ``NotImplementedError``."""
+    import torch
+
+    eng = _csr_engine_of(graph, "neighbour_degrees")
+    dev = torch.device("cuda", eng.device)
+    d_deg = torch.empty(eng.n_nodes, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    _check_value(_lib.load().pw_nbr_degrees_device(eng._h, C.c_void_p(d_deg.data_ptr())))
+    return d_deg.to(torch.int64) & 0xFFFFFFFF
+
+
+def degree_table(graph, kind):
+    """The table of ``adamic_adar`` (``1 / ln d(z)``) or ``resource_allocation`` (``1 / d(z)``), ``0.0`` where ``d(z) < 2``: a
+    float64 ``[N]`` tensor on the graph's device.  The degrees are counted and reduced to their distinct values on the device
+    (``neighbour_degrees``, ``torch.unique``); those few values cross to the host, where NumPy evaluates the function -- the
+    device's ``log`` is no part of any result -- and the values go back and are gathered there."""
+    import torch
+
+    _degree_function(kind, [2])   # (an unknown kind is refused before anything runs)
+    deg = neighbour_degrees(graph)
+    distinct, inverse = torch.unique(deg, return_inverse=True)
+    d_host = distinct.cpu().numpy()
+    value = np.zeros(d_host.size, dtype=np.float64)
+    value[d_host >= 2] = _degree_function(kind, d_host[d_host >= 2])
+    return torch.from_numpy(value).to(deg.device)[inverse].contiguous()
+
+
+def neighbour_scores(graph, u, v, kind, table=None):
+    """``Base.neighbour_scores``: the neighbourhood heuristic ``kind`` of every pair ``(u[i], v[i])`` as a float64 ``[m]`` tensor
+    on the graph's device -- what ``auc`` takes (``pw_nbr_scores_device``; ``neighbour_scores_host`` states the rule).  ``kind``:
+    ``common_neighbours``, ``jaccard``, ``preferential_attachment``, ``adamic_adar``, ``resource_allocation``, or ``weighted`` with
+    ``table=``, a float64 value per vertex (a tensor on the graph's device stays there), summed over the common neighbours in
+    ascending order.  ``u`` / ``v``: row numbers as ``score_pairs`` takes them.  Stored weights are not looked at; a self loop is no
+    neighbour.  In the link-prediction protocol call it on the TRAIN graph of ``holdout_edges``, not on the original.  Dense
+    graphs: ``NotImplementedError``; a row number outside the graph: ``ValueError`` naming the position."""
+    import torch
+
+    _check_heuristic(kind, table)
+    eng = _csr_engine_of(graph, "neighbour_scores")
+    dev = torch.device("cuda", eng.device)
+    d_table = None
+    if kind in ("adamic_adar", "resource_allocation"):
+        d_table = degree_table(graph, kind)
+    elif kind == "weighted":
+        d_table = _scores_device(table, "table", dev)
+        if d_table.numel() != eng.n_nodes:
+            raise ValueError(f"table must hold one float64 per vertex ({eng.n_nodes}), not {d_table.numel()}")
+    d_u, d_v = _rows_device(u, "u", dev), _rows_device(v, "v", dev)
+    if d_u.shape != d_v.shape:
+        raise ValueError(f"u and v must have one length, not {d_u.numel()} and {d_v.numel()}")
+    score = torch.empty(d_u.numel(), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()   # the row numbers and the table were produced on torch's stream
+    _check_value(_lib.load().pw_nbr_scores_device(eng._h, C.c_void_p(d_u.data_ptr()), C.c_void_p(d_v.data_ptr()), d_u.numel(),
+                                                  _lib.NBR_KINDS.get(kind, _lib.NBR_KINDS["weighted"]),
+                                                  C.c_void_p(d_table.data_ptr()) if d_table is not None else None, C.c_void_p(score.data_ptr())))
+    return score
+
+
+
 def _pairs(p, name):
     if isinstance(p, (tuple, list)) and len(p) == 2:
         return p[0], p[1]
@@ -428,3 +597,11 @@ def link_auc(index_or_session, pos_pairs, neg_pairs, metric="dot", against="cont
             return auc(a.score_pairs(*_pairs(pos_pairs, "pos_pairs"), metric=metric, other=b),
                        a.score_pairs(*_pairs(neg_pairs, "neg_pairs"), metric=metric, other=b))
     return auc(score(*_pairs(pos_pairs, "pos_pairs")), score(*_pairs(neg_pairs, "neg_pairs")))
+
+
+def baseline_auc(graph, pos_pairs, neg_pairs, kind, table=None):
+    """``(auc, wins, ties)`` of the neighbourhood heuristic ``kind`` on ``graph``: ``neighbour_scores`` of ``pos_pairs`` and of
+    ``neg_pairs`` -- each ``(u, v)`` or an integer array ``[m, 2]`` / ``[2, m]`` -- then ``auc``.  ``graph`` is the TRAIN graph of
+    ``holdout_edges``; the negatives come from ``sample_non_edges`` of the original."""
+    return auc(neighbour_scores(graph, *_pairs(pos_pairs, "pos_pairs"), kind, table=table),
+               neighbour_scores(graph, *_pairs(neg_pairs, "neg_pairs"), kind, table=table))

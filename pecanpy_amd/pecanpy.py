@@ -682,6 +682,18 @@ class Base(BaseGraph):
 
         return linkpred.holdout_edges(self, fraction, seed, directed, protect, first_word)
 
+    def neighbour_scores(self, u, v, kind, table=None):
+        """The neighbourhood heuristic ``kind`` -- ``common_neighbours``, ``jaccard``, ``preferential_attachment``,
+        ``adamic_adar``, ``resource_allocation``, or ``weighted`` with ``table=`` -- of every pair ``(u[i], v[i])`` of node
+        indices, computed on the GPU: a float64 tensor on the graph's device, what ``linkpred.auc`` takes
+        (``linkpred.neighbour_scores``; ``linkpred.neighbour_scores_host`` states the rule).  The baselines of link prediction:
+        call it on the TRAIN graph of ``holdout_edges``.  Sparse classes only: a dense one raises ``NotImplementedError``."""
+        if not isinstance(self, SparseGraph):
+            raise NotImplementedError("neighbour_scores needs a sparse (CSR) graph")
+        from . import linkpred
+
+        return linkpred.neighbour_scores(self, u, v, kind, table=table)
+
     def embed(self, dim=128, num_walks=10, walk_length=80, window_size=10, epochs=1, verbose=False):
         """``simulate_walks`` + skip-gram (pecanpy.py:240-290): returns ``float32[num_nodes, dim]`` in node order.
 
