@@ -658,6 +658,44 @@ int pw_selftest_nbr_scores(int on_device, int device, const uint32_t *indptr, co
 int pw_selftest_nbr_degrees(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes,
                             uint32_t *deg);
 
+/* ---- exact binary logistic regression on embedding rows and pair operators: one evaluation, in device memory ------------
+ * The definition is written at the top of csrc/logit.hip.h (DESIGN.md 4.12 repeats it); host and device answer it identically,
+ * bit for bit, whatever the grid.  a, b: two pw_knn indexes of one dim <= 512 on one device (b == NULL: a against itself).
+ * Sample i has the feature f = feat(op, a[d_u[i]], b[d_v[i]]) in float64:
+ *                PW_LOGIT_ROW       a's row as it is (d_v is not read and may be NULL): node classification
+ *                PW_LOGIT_AVERAGE   (a + b) * 0.5
+ *                PW_LOGIT_HADAMARD  a * b
+ *                PW_LOGIT_L1        fabs(a - b)
+ *                PW_LOGIT_L2        (a - b) * (a - b)
+ * and the decision value z[i] = (((bias + w[0] f[0]) + w[1] f[1]) + ...), theta = (w[0] .. w[dim - 1], bias) float64[dim + 1] in
+ * HOST memory, every product and sum rounded on its own.
+ *   pw_logit_eval_device   d_u, d_v device uint32[m], d_y device uint8[m] of 0 / 1, 1 <= m < 2^40, l2 finite and >= 0.
+ *                *loss = mean log-loss + (0.5 l2) |w|^2 and grad[dim + 1] (HOST memory) = its gradient (the bias is not
+ *                penalised), summed in the definition's order: 1024-sample chunks, ascending.  d_z (device float64[m], may be
+ *                NULL) receives the decision values.  With d_y == NULL the call computes d_z alone (loss and grad are not
+ *                touched): scoring with a trained model.  The library evaluates no libm exp or log: the definition carries its
+ *                own two functions, built from + - * / alone.
+ *                Refused with PW_ERR_INVALID and a message naming the first offending element, NOTHING written: an unknown op,
+ *                dims or devices of a and b that differ, m out of range, l2 negative / NaN / infinite, a non-finite theta entry,
+ *                a row number out of range ("u[i]" before "v[i]" at one position), a label other than 0 / 1, a z that is not
+ *                finite.  dim > 512: PW_ERR_UNSUPPORTED.
+ *   pw_logit_eval_device_grid   the same with the grid of both kernels forced to `blocks` workgroups (-1: the default) and, when
+ *                kernel_ms is not NULL, the device time of the kernels (two events around them) in ms: the hook of the tests
+ *                and of tools/logit_bench.py.  No result depends on blocks.
+ * Test hooks on HOST pointers: pw_selftest_logit (a float32[na, dim], b float32[nb, dim] or NULL; y == NULL: z alone; on_device = 0:
+ * the host build of the definition, plain loops, usable without a GPU; otherwise upload, the kernels, download) and
+ * pw_selftest_logit_math (the host build of the definition's lg_exp (which = 0) or lg_log1p (which = 1) on an array). */
+enum { PW_LOGIT_ROW = 0, PW_LOGIT_AVERAGE = 1, PW_LOGIT_HADAMARD = 2, PW_LOGIT_L1 = 3, PW_LOGIT_L2 = 4 };
+int pw_logit_eval_device(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint32_t *d_v, const uint8_t *d_y, uint64_t m, int op,
+                         const double *theta, double l2, double *loss, double *grad, double *d_z);
+int pw_logit_eval_device_grid(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint32_t *d_v, const uint8_t *d_y, uint64_t m,
+                              int op, const double *theta, double l2, double *loss, double *grad, double *d_z, int blocks,
+                              float *kernel_ms);
+int pw_selftest_logit(int on_device, int device, const float *a, uint64_t na, const float *b, uint64_t nb, uint32_t dim,
+                      const uint32_t *u, const uint32_t *v, const uint8_t *y, uint64_t m, int op, const double *theta, double l2,
+                      int blocks, double *loss, double *grad, double *z);
+int pw_selftest_logit_math(int which, const double *x, uint64_t n, double *out);
+
 /* ---- edges held out by the seeded stream: the train graph and the held-out pairs, in device memory ----------------------
  * The definition is written at the top of csrc/holdout.hip.h (DESIGN.md 4.10 repeats it); host and device answer it
  * identically, whatever the grid or the batch of words expanded at a time.

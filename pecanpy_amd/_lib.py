@@ -152,6 +152,9 @@ PW_KNN_MAX_TOPN = 128
 KNN_METRICS = {"dot": 0, "cosine": 1}   # PW_KNN_DOT, PW_KNN_COSINE
 KNN_QT = 8                              # queries a wavefront keeps accumulators for (csrc/knn.hip.h)
 NBR_KINDS = {"common_neighbours": 0, "jaccard": 1, "preferential_attachment": 2, "weighted": 3}   # PW_NBR_* (csrc/nbr_scores.hip.h)
+LOGIT_OPS = {"row": 0, "average": 1, "hadamard": 2, "l1": 3, "l2": 4}   # PW_LOGIT_* (csrc/logit.hip.h)
+LOGIT_MAX_DIM = 512                     # the trainer's cap (LG_MAX_DIM)
+LOGIT_CHUNK = 1024                      # LG_CHUNK: part of the definition
 NBR_ALL_LANE = 0xFFFFFFFF               # short_max of pw_selftest_nbr_scores: every pair stays with its lane; -1: the default
 ERR_INVALID = -1                        # PW_ERR_INVALID
 
@@ -338,6 +341,12 @@ SYMBOLS = {
     "pw_selftest_nbr_scores": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                          C.c_void_p, C.c_int64, C.c_void_p]),
     "pw_selftest_nbr_degrees": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "pw_logit_eval_device": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_void_p, C.c_double, _f64p, C.c_void_p, C.c_void_p]),
+    "pw_logit_eval_device_grid": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_void_p, C.c_double, _f64p, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.POINTER(C.c_float)]),
+    "pw_selftest_logit": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.c_int, C.c_void_p, C.c_double, C.c_int, _f64p, C.c_void_p, C.c_void_p]),
+    "pw_selftest_logit_math": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pw_holdout_edges_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_void_p),
                                           C.POINTER(C.c_void_p), _f64p]),
     "pw_holdout_dev_shape": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3),

@@ -17,6 +17,13 @@ there -- the files ``--task score`` reads.  ``split``, a normal run on the train
 common neighbours, Jaccard, Adamic-Adar, resource allocation, preferential attachment; ``Base.neighbour_scores``) and, with
 ``--neg_pairs``, prints the same ``auc wins ties m n`` line: the protocol's baseline rows.  The protocol's baseline is computed on the
 TRAIN graph (``--input train.npz``, what ``--task split`` wrote), not on the original, whose edges include the answers.
+``--task fit`` trains an exact logistic regression on the GPU (``classify.fit``) and writes the model to ``--output``: with
+``--pairs POS --neg_pairs NEG --operator {average,hadamard,l1,l2} [--l2_penalty X]`` the link classifier of the node2vec paper on
+the vectors of the embedding file ``--input`` -- label 1 for the pairs of ``--pairs``, 0 for those of ``--neg_pairs``, positives
+first; with ``--labels FILE`` (lines ``node<delimiter>0|1``) a node classifier on the rows themselves (operator ``row``).
+``--task score --model model.tsv`` writes the model's decision value of every pair instead of the metric (and, with
+``--neg_pairs``, the AUC of the decision values).  ``--operator``, ``--l2_penalty`` and ``--labels`` with another task, ``--model``
+with a task other than ``score``, ``--metric`` beside ``--model`` and ``--operator`` beside ``--labels`` are ignored with a warning.
 The sparse modes parse an ``.edg`` input on the GPU (``read_edg_device``); ``PECANPY_AMD_HOST_READER=1`` keeps the host reader.
 
     pecanpy --input demo/karate.edg --output karate.emb --mode SparseOTF --p 0.5 --q 2
@@ -33,13 +40,14 @@ from .wrappers import Timer
 
 MODES = ("DenseOTF", "FirstOrderUnweighted", "PreComp", "PreCompFirstOrder", "SparseOTF")
 HEURISTICS = ("common_neighbours", "jaccard", "adamic_adar", "resource_allocation", "preferential_attachment")   # --task baseline
+OPERATORS = ("average", "hadamard", "l1", "l2")   # --task fit with pairs
 
 # (flag, argparse keywords) -- one table instead of twenty add_argument calls
 _OPTIONS = (
     ("--input", dict(required=True, help="graph file: .edg edge list or .npz (CSR / dense)")),
     ("--output", dict(default=None, help="embedding file (.npz -> IDs/data arrays, else word2vec text); required by every task but "
                                          "baseline")),
-    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score", "split", "baseline"),
+    ("--task", dict(default="pecanpy", choices=("pecanpy", "tocsr", "todense", "walks", "train", "neighbours", "score", "split", "baseline", "fit"),
                     help="run node2vec; only convert the edge list to CSR / dense .npz; (walks) generate the walks and "
                          "write them, one per line, to --output, no training; (train) train embeddings from a walk "
                          "corpus file given as --input, no graph; or (neighbours) the nearest neighbours of the nodes of an "
@@ -49,7 +57,9 @@ _OPTIONS = (
                          "score of every node pair of --pairs by the neighbourhood heuristic --heuristic of the graph given as "
                          "--input (a sparse --mode), written to --output when given.  The link-prediction protocol computes its "
                          "baseline on the TRAIN graph (--input train.npz from --task split), not on the original graph, whose "
-                         "edges include the answers")),
+                         "edges include the answers; or (fit) train a logistic regression on the vectors of an embedding file given as "
+                         "--input -- on --operator of the pairs of --pairs (label 1) and --neg_pairs (label 0), or on the rows of "
+                         "the nodes of --labels -- and write the model to --output")),
     ("--mode", dict(default="SparseOTF", choices=MODES, help="walk engine variant")),
     ("--dimensions", dict(type=int, default=128, help="embedding size")),
     ("--walk-length", dict(type=int, default=80, help="steps per walk")),
@@ -90,6 +100,10 @@ _OPTIONS = (
                               "--task split: receives as many non-edges of the original graph as there are held-out pairs")),
     ("--heuristic", dict(default=None, choices=HEURISTICS, metavar="KIND",
                          help="--task baseline: the neighbourhood heuristic, one of " + ", ".join(HEURISTICS))),
+    ("--operator", dict(default="hadamard", choices=OPERATORS, help="--task fit with pairs: the binary operator on the two vectors")),
+    ("--l2_penalty", dict(type=float, default=1e-3, help="--task fit: the weight of |w|^2 / 2 beside the mean log-loss")),
+    ("--labels", dict(default=None, metavar="FILE", help="--task fit: one 'node<delimiter>0|1' line per labelled node (operator row)")),
+    ("--model", dict(default=None, metavar="FILE", help="--task score: a model file of --task fit; the score is its decision value")),
     ("--holdout_fraction", dict(type=float, default=0.5, help="--task split: the share of the edges to hold out, in [0, 1)")),
     ("--no_protect", dict(action="store_true", help="--task split: do not keep the first edge of every node in the train graph")),
     ("--delimiter", dict(type=str, default="\t", help="column separator of the edge list")),
@@ -110,6 +124,19 @@ def parse_args(argv=None):
         parser.error("the following arguments are required: --output")
     if args.task in ("score", "split", "baseline") and not args.pairs:
         parser.error(f"--task {args.task} needs --pairs")
+    fit_flags = [f for f, given in (("--operator", args.operator != parser.get_default("operator")), ("--labels", bool(args.labels)),
+                                    ("--l2_penalty", args.l2_penalty != parser.get_default("l2_penalty"))) if given]
+    if args.task != "fit" and fit_flags:
+        warnings.warn(f"{', '.join(fit_flags)} belong to --task fit; --task {args.task} ignores them", stacklevel=2)
+    if args.task == "fit" and args.labels and "--operator" in fit_flags:
+        warnings.warn("--task fit with --labels trains on the rows themselves (operator row); --operator is ignored", stacklevel=2)
+    if args.model and args.task != "score":
+        warnings.warn(f"--model belongs to --task score; --task {args.task} ignores it", stacklevel=2)
+    if args.model and args.task == "score" and args.metric != parser.get_default("metric"):
+        warnings.warn("--task score with --model writes the model's decision value; --metric is ignored", stacklevel=2)
+    if args.task == "fit":
+        if bool(args.labels) == bool(args.pairs or args.neg_pairs) or (not args.labels and not (args.pairs and args.neg_pairs)):
+            parser.error("--task fit needs either --labels, or --pairs together with --neg_pairs (and --operator)")
     if args.task == "baseline":
         if not args.heuristic:
             parser.error("--task baseline needs --heuristic")
@@ -436,7 +463,7 @@ def score_from_file(args):
     one line ``id_u<delimiter>id_v<delimiter>score`` per pair, the score as ``repr(float)`` (``KnnIndex.score_pairs``: exact).  With
     ``--neg_pairs`` the line ``auc wins ties m n`` of the pairs' scores against those pairs' scores goes to stdout
     (``linkpred.auc``: exact integers, one rounding)."""
-    from . import embed, linkpred
+    from . import classify, embed, linkpred
 
     _warn_graph_flags_ignored(args, "score")
     ids, data = read_init_emb(args.input)
@@ -444,14 +471,60 @@ def score_from_file(args):
     nu, nv, ru, rv = _read_pairs(args.pairs, args.delimiter, row_of)
     neg = _read_pairs(args.neg_pairs, args.delimiter, row_of) if args.neg_pairs else None
     with embed.KnnIndex(data, node_ids=ids) as index:
-        d_pos = index.score_pairs(ru, rv, metric=args.metric)
-        d_neg = index.score_pairs(neg[2], neg[3], metric=args.metric) if neg else None
+        if args.model:   # the decision value of a fitted model instead of the metric
+            model = classify.LogisticModel.load(args.model)
+            d_pos = model.decision_function(index, ru, rv)
+            d_neg = model.decision_function(index, neg[2], neg[3]) if neg else None
+        else:
+            d_pos = index.score_pairs(ru, rv, metric=args.metric)
+            d_neg = index.score_pairs(neg[2], neg[3], metric=args.metric) if neg else None
         result = linkpred.auc(d_pos, d_neg) if neg else None
     d = args.delimiter
     with open(args.output, "w", encoding="utf-8", newline="\n") as f:
         f.write("".join(f"{a}{d}{b}{d}{float(s)!r}\n" for a, b, s in zip(nu, nv, d_pos.cpu().numpy())))
     if result:
         print(f"{result[0]!r} {result[1]} {result[2]} {len(nu)} {len(neg[0])}")
+
+
+def _read_labels(path, delimiter, row_of):
+    """``(rows, labels)`` of a label file: ``node<delimiter>0|1`` per line; anything else is a ``ValueError`` naming the line."""
+    rows, labels = [], []
+    with open(path, encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            terms = line.split(delimiter)
+            if len(terms) != 2 or terms[1] not in ("0", "1"):
+                raise ValueError(f"{path}, line {no}: expected a node ID and a label 0 or 1")
+            if terms[0] not in row_of:
+                raise ValueError(f"{path}, line {no}: unknown node ID {terms[0]!r}")
+            rows.append(row_of[terms[0]])
+            labels.append(int(terms[1]))
+    return np.array(rows, dtype=np.int64), np.array(labels, dtype=np.uint8)
+
+
+@Timer("read embedding + fit a logistic regression")
+def fit_from_file(args):
+    """``--task fit``: ``--input`` is an embedding file (``read_init_emb``).  With ``--pairs`` and ``--neg_pairs``: ``classify.fit``
+    on ``--operator`` of the pairs, label 1 for ``--pairs`` and 0 for ``--neg_pairs``, positives first; with ``--labels``: on the
+    rows of the labelled nodes (operator ``row``).  ``--output`` gets the model (``LogisticModel.save``); stdout the line
+    ``loss n_iter n_eval converged``."""
+    from . import classify, embed
+
+    _warn_graph_flags_ignored(args, "fit")
+    ids, data = read_init_emb(args.input)
+    row_of = {name: i for i, name in enumerate(ids)}
+    with embed.KnnIndex(data, node_ids=ids) as index:
+        if args.labels:
+            rows, y = _read_labels(args.labels, args.delimiter, row_of)
+            model = classify.fit(index, rows, None, y, "row", l2=args.l2_penalty)
+        else:
+            pos, neg = _read_pairs(args.pairs, args.delimiter, row_of), _read_pairs(args.neg_pairs, args.delimiter, row_of)
+            y = np.concatenate([np.ones(len(pos[0]), dtype=np.uint8), np.zeros(len(neg[0]), dtype=np.uint8)])
+            model = classify.fit(index, np.concatenate([pos[2], neg[2]]), np.concatenate([pos[3], neg[3]]), y, args.operator, l2=args.l2_penalty)
+    model.save(args.output)
+    print(f"{model.loss!r} {model.n_iter} {model.n_eval} {int(model.converged)}")
 
 
 def _write_pairs(path, delimiter, ids, u, v):
@@ -513,6 +586,9 @@ def main(argv=None):
         return
     if args.task == "score":
         score_from_file(args)
+        return
+    if args.task == "fit":
+        fit_from_file(args)
         return
     args.workers = args.workers or (os.cpu_count() or 1)
     g = read_graph(args)

@@ -4303,6 +4303,7 @@ PW_EXPORT int pw_selftest_sample_non_edges(int on_device, int device, const uint
 }
 
 #include "drv_nbr.hip.h"
+#include "drv_logit.hip.h"
 
 // ---- edges held out by the seeded stream: the train CSR and the held-out pairs (csrc/holdout.hip.h) ---------------------------
 struct pw_holdout_dev {

@@ -495,6 +495,17 @@ class SgnsSession:
             with self.knn_index("context") as b:
                 return a.score_pairs(u, v, metric=metric, other=b)
 
+    def fit_pairs(self, u, v, y, op, l2=1e-3, against="context", max_iter=200, gtol=1e-8):
+        """``KnnIndex.fit_pairs`` on ``vectors()[u[i]]`` and ``context_vectors()[v[i]]`` (``against="context"``) or
+        ``vectors()[v[i]]`` (``against="vectors"``), as they are now."""
+        if against not in ("vectors", "context"):
+            raise ValueError(f"against must be 'vectors' or 'context', not {against!r}")
+        with self.knn_index("vectors") as a:
+            if against == "vectors":
+                return a.fit_pairs(u, v, y, op, l2=l2, max_iter=max_iter, gtol=gtol)
+            with self.knn_index("context") as b:
+                return a.fit_pairs(u, v, y, op, l2=l2, other=b, max_iter=max_iter, gtol=gtol)
+
     # ---- checkpoints
     def save(self, path):
         """An ``.npz`` with both matrices, the state, the constructor's parameters and ``(n_walks, walk_length,
@@ -841,6 +852,13 @@ class KnnIndex:
         from . import linkpred
 
         return linkpred.score_pairs(self, u, v, metric=metric, other=other)
+
+    def fit_pairs(self, u, v, y, op, l2=1e-3, other=None, max_iter=200, gtol=1e-8):
+        """A ``classify.LogisticModel``: the exact logistic regression of the labels ``y`` (0 / 1) on ``op`` (``average``,
+        ``hadamard``, ``l1``, ``l2``; ``row``: the rows ``u`` themselves) of the rows ``u[i]`` and ``v[i]`` (``classify.fit``)."""
+        from . import classify
+
+        return classify.fit(self, u, v, y, op, l2=l2, other=other, max_iter=max_iter, gtol=gtol)
 
     def _row(self, node):
         if self._row_of is None:

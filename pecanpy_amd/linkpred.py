@@ -33,7 +33,7 @@ from . import _lib
 
 __all__ = ["score_pairs", "auc", "sample_non_edges", "link_auc", "score_pairs_host", "auc_host", "sample_non_edges_host",
            "candidate_cap", "holdout_edges", "holdout_edges_host", "holdout_threshold", "neighbour_scores", "neighbour_degrees",
-           "degree_table", "neighbour_scores_host", "neighbour_degrees_host", "degree_table_host", "baseline_auc", "HEURISTICS"]
+           "degree_table", "neighbour_scores_host", "neighbour_degrees_host", "degree_table_host", "baseline_auc", "classifier_auc", "HEURISTICS"]
 
 # the kinds of ``neighbour_scores``; the two after the first three are ``weighted`` with a table of the degrees
 HEURISTICS = ("common_neighbours", "jaccard", "preferential_attachment", "adamic_adar", "resource_allocation", "weighted")
@@ -605,3 +605,26 @@ def baseline_auc(graph, pos_pairs, neg_pairs, kind, table=None):
     ``holdout_edges``; the negatives come from ``sample_non_edges`` of the original."""
     return auc(neighbour_scores(graph, *_pairs(pos_pairs, "pos_pairs"), kind, table=table),
                neighbour_scores(graph, *_pairs(neg_pairs, "neg_pairs"), kind, table=table))
+
+
+def _pair_rows(p, name, dev):
+    u, v = _pairs(p, name)
+    return _rows_device(u, f"{name}.u", dev), _rows_device(v, f"{name}.v", dev)
+
+
+def classifier_auc(index, train_pos, train_neg, test_pos, test_neg, op, l2, other=None):
+    """``(auc, wins, ties, model)``: the classifier row of the protocol's table.  ``classify.fit`` on ``op`` of the train pairs --
+    label 1 for ``train_pos``, 0 for ``train_neg``, concatenated positives first -- then the model's decision values of
+    ``test_pos`` against those of ``test_neg`` through ``auc``.  Each pair set is ``(u, v)`` or an integer array ``[m, 2]`` /
+    ``[2, m]``, on the GPU or not; ``index`` is a ``KnnIndex`` (``other``: a second one for ``v``'s rows)."""
+    import torch
+
+    from . import classify
+
+    dev = index._torch_device()
+    (pu, pv), (nu, nv) = _pair_rows(train_pos, "train_pos", dev), _pair_rows(train_neg, "train_neg", dev)
+    y = torch.cat([torch.ones(pu.numel(), dtype=torch.uint8, device=dev), torch.zeros(nu.numel(), dtype=torch.uint8, device=dev)])
+    model = classify.fit(index, torch.cat([pu, nu]), torch.cat([pv, nv]), y, op, l2=l2, other=other)
+    value, wins, ties = auc(model.decision_function(index, *_pair_rows(test_pos, "test_pos", dev), other=other),
+                            model.decision_function(index, *_pair_rows(test_neg, "test_neg", dev), other=other))
+    return value, wins, ties, model
