@@ -1,6 +1,7 @@
 #pragma once
 // Host driver, core: what every other piece stands on -- PW_EXPORT, the error text (fail, HIP_TRY), the switches of a call
-// (LaneSwitches), grow, check_device, the handle (GraphDesc / GraphData / pw_graph, GraphOwner), csr_dev, graph_common_init.
+// (LaneSwitches), grow, check_device, the evaluation drivers' helpers (dev_alloc .. download), the handles (GraphDesc / GraphData /
+// pw_graph, pw_csr_dev) and their owners, csr_dev, graph_common_init, the declaration of stream_words_window (pecanpy_amd.hip).
 // Exports pw_version, pw_last_error, pw_device_count, pw_warmup, pw_graph_destroy.  The system includes of the whole driver
 // are here and nowhere else.
 #include <hip/hip_runtime.h>
@@ -115,6 +116,39 @@ int check_device(int device) {
     if (device < 0 || device >= n) return fail(PW_ERR_INVALID, "device index out of range");
     return 0;
 }
+
+// ---- what the evaluation drivers (drv_knn, drv_linkpred, drv_nbr, drv_logit, drv_holdout) share --------------------------------
+// a fresh allocation of a call.  ("pw_knn:" whichever family asks: where the function began; a known wart)
+template <typename T> int dev_alloc(DevBuf<T> &b, size_t n) {
+    const hipError_t e = b.alloc(n);
+    return e == hipSuccess ? 0 : fail(PW_ERR_NOMEM, "pw_knn: " + std::to_string(n * sizeof(T)) + " bytes do not fit in device memory: " + hipGetErrorString(e));
+}
+
+// the grid of a 256-thread kernel whose threads stride over n items: a thread per item up to 16 workgroups per CU
+unsigned strided_grid(uint64_t n, int n_cu) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, n_cu) * 16)); }
+
+// the grid of a persistent kernel whose wavefronts take tiles from a counter: what the device holds at once, no idle workgroup
+int persistent_tile_grid(const void *kernel, int threads, uint32_t waves, uint64_t n_tiles, int n_cu, size_t lds, uint64_t *blocks) {
+    int occ = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds));
+    *blocks = std::min<uint64_t>((n_tiles + waves - 1) / waves, (uint64_t)std::max(1, occ) * std::max(1, n_cu));
+    return 0;
+}
+
+// the total of an exclusive scan launched on `stream`, behind it (scan.hip.h: [0] = the total of its scratch array)
+int scan_total(hipStream_t stream, const uint32_t *scan_tmp, uint32_t *total) {
+    HIP_TRY(hipMemcpyAsync(total, scan_tmp, sizeof(*total), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// the self tests' staging: a host array into a fresh device buffer, and a device buffer back into a host array
+template <typename T> int upload(DevBuf<T> &b, const T *host, size_t n) {
+    if (int rc = dev_alloc(b, n)) return rc;
+    HIP_TRY(hipMemcpy(b.p, host, sizeof(T) * n, hipMemcpyHostToDevice));
+    return 0;
+}
+template <typename T> int download(T *host, const DevBuf<T> &b, size_t n) { HIP_TRY(hipMemcpy(host, b.p, sizeof(T) * n, hipMemcpyDeviceToHost)); return 0; }
 
 }  // namespace
 
@@ -283,13 +317,24 @@ struct pw_graph {
     ~pw_graph() { (void)hipSetDevice(device); }   // (the members release themselves behind this body: on their own device)
 };
 
+// A CSR in device memory (pw_coo_to_csr_device, the edge-list reader, pw_holdout_edges): handles are made from it.
+struct pw_csr_dev {
+    int device = 0;
+    uint64_t n_nodes = 0, nnz = 0, insertions = 0, dropped = 0;
+    double build_ms = 0;
+    DevBuf<uint32_t> d_indptr, d_indices;
+    DevBuf<float> d_data;      // empty: no weights were given (every weight 1.0)
+    DevBuf<double> d_data64;   // the edge-list reader with PW_EDGELIST_KEEP_F64: every entry's weight as parsed; empty otherwise
+};
+
 namespace {
 
 // The owner of a call context under construction: every way out of a creator but the release() into *out destroys it (a twin
 // with it).  A creator's locals go in reverse order of declaration, so where the owner stands among them decides what the
 // handle outlives: each creator says so where it declares it.
-struct GraphDeleter { void operator()(pw_graph *g) const { pw_graph_destroy(g); } };
-using GraphOwner = std::unique_ptr<pw_graph, GraphDeleter>;
+template <typename T, void (*Destroy)(T *)> struct Closes { void operator()(T *p) const { Destroy(p); } };   // (KnnOwner, HoldoutOwner too)
+using GraphOwner = std::unique_ptr<pw_graph, Closes<pw_graph, pw_graph_destroy>>;
+using CsrDevOwner = std::unique_ptr<pw_csr_dev, Closes<pw_csr_dev, pw_csr_dev_destroy>>;
 
 int set_device(const pw_graph *g) {
     HIP_TRY(hipSetDevice(g->device));
@@ -396,6 +441,9 @@ static int graph_common_init(pw_graph *g, int device, std::shared_ptr<GraphData>
     lap("copy stream + events");
     return 0;
 }
+
+// Defined in pecanpy_amd.hip beside expand_stream, declared here for drv_linkpred and drv_holdout: *words = word w0 of [w0, w0 + n)
+static int stream_words_window(pw_graph *g, uint32_t seed, uint64_t w0, uint64_t n, const uint32_t **words);
 
 static pw::CsrDev csr_dev(const pw_graph *g) {
     pw::CsrDev c;

@@ -43,9 +43,13 @@ int knn_row_range(uint64_t q, uint32_t row, uint64_t n) {
                                     std::to_string(n) + " rows");
 }
 
-template <typename T> int knn_alloc(DevBuf<T> &b, size_t n) {
-    const hipError_t e = b.alloc(n);
-    return e == hipSuccess ? 0 : fail(PW_ERR_NOMEM, "pw_knn: " + std::to_string(n * sizeof(T)) + " bytes do not fit in device memory: " + hipGetErrorString(e));
+// an index of a self test, here and in every piece that makes one
+using KnnOwner = std::unique_ptr<pw_knn, Closes<pw_knn, pw_knn_destroy>>;
+int knn_own(int device, const float *vectors, uint64_t n_rows, uint32_t dim, KnnOwner &k) {
+    pw_knn *raw = nullptr;
+    const int rc = pw_knn_create(device, vectors, n_rows, dim, &raw);
+    k.reset(raw);
+    return rc;
 }
 
 // the index from a matrix in device or host memory: the copy, the norms, the refusal of non-finite rows
@@ -64,11 +68,10 @@ int knn_create_impl(int device, const float *vectors, hipMemcpyKind kind, uint64
     k->n = n_rows;
     k->dim = dim;
     DevBuf<pw::KnnFound> found;
-    if ((rc = knn_alloc(k->X, (size_t)n_rows * dim)) || (rc = knn_alloc(k->norms, n_rows)) || (rc = knn_alloc(found, 1))) return rc;
+    if ((rc = dev_alloc(k->X, (size_t)n_rows * dim)) || (rc = dev_alloc(k->norms, n_rows)) || (rc = dev_alloc(found, 1))) return rc;
     HIP_TRY(hipMemcpy(k->X.p, vectors, sizeof(float) * (size_t)n_rows * dim, kind));
     HIP_TRY(hipMemset(found.p, 0xff, sizeof(pw::KnnFound)));
-    const unsigned blocks = (unsigned)std::min<uint64_t>((n_rows + 255) / 256, (uint64_t)k->n_cu * 16);
-    hipLaunchKernelGGL(pw::knn_norms_kernel, dim3(blocks), dim3(256), 0, nullptr, (const float *)k->X.p, n_rows, dim, k->norms.p, found.p);
+    hipLaunchKernelGGL(pw::knn_norms_kernel, dim3(strided_grid(n_rows, k->n_cu)), dim3(256), 0, nullptr, (const float *)k->X.p, n_rows, dim, k->norms.p, found.p);
     HIP_TRY(hipGetLastError());
     pw::KnnFound h;
     HIP_TRY(hipMemcpy(&h, found.p, sizeof(h), hipMemcpyDeviceToHost));
@@ -94,10 +97,10 @@ int knn_query_impl(pw_knn *k, const float *d_queries, const uint32_t *d_rows, ui
     DevBuf<uint32_t> part_ix;
     DevBuf<pw::KnnFound> found;
     int rc;
-    if ((rc = knn_alloc(qnorms, nq)) || (rc = knn_alloc(found, 1))) return rc;
+    if ((rc = dev_alloc(qnorms, nq)) || (rc = dev_alloc(found, 1))) return rc;
     HIP_TRY(hipMemsetAsync(found.p, 0xff, sizeof(pw::KnnFound), nullptr));
-    hipLaunchKernelGGL(pw::knn_query_norms_kernel, dim3((unsigned)std::min<uint64_t>((nq + 255) / 256, (uint64_t)k->n_cu * 16)), dim3(256), 0, nullptr,
-                       d_queries, d_rows, nq, k->n, k->dim, (const double *)k->norms.p, qnorms.p, found.p);
+    hipLaunchKernelGGL(pw::knn_query_norms_kernel, dim3(strided_grid(nq, k->n_cu)), dim3(256), 0, nullptr, d_queries, d_rows, nq, k->n, k->dim,
+                       (const double *)k->norms.p, qnorms.p, found.p);
     HIP_TRY(hipGetLastError());
     pw::KnnFound h;
     HIP_TRY(hipMemcpy(&h, found.p, sizeof(h), hipMemcpyDeviceToHost));
@@ -232,26 +235,17 @@ PW_EXPORT int pw_selftest_knn(int on_device, int device, const float *vectors, u
         }
         return PW_OK;
     }
-    pw_knn *raw = nullptr;
-    if ((rc = pw_knn_create(device, vectors, n, dim, &raw))) return rc;
-    struct Closer { void operator()(pw_knn *k) const { pw_knn_destroy(k); } };
-    std::unique_ptr<pw_knn, Closer> k(raw);
+    KnnOwner k;
+    if ((rc = knn_own(device, vectors, n, dim, k))) return rc;
     if (nq == 0) return PW_OK;
     DevBuf<float> d_q;
     DevBuf<uint32_t> d_r, d_idx;
     DevBuf<double> d_score;
-    if ((rc = knn_alloc(d_idx, (size_t)nq * topn)) || (rc = knn_alloc(d_score, (size_t)nq * topn))) return rc;
-    if (queries) {
-        if ((rc = knn_alloc(d_q, (size_t)nq * dim))) return rc;
-        HIP_TRY(hipMemcpy(d_q.p, queries, sizeof(float) * (size_t)nq * dim, hipMemcpyHostToDevice));
-    } else {
-        if ((rc = knn_alloc(d_r, nq))) return rc;
-        HIP_TRY(hipMemcpy(d_r.p, rows, sizeof(uint32_t) * (size_t)nq, hipMemcpyHostToDevice));
-    }
+    if ((rc = dev_alloc(d_idx, (size_t)nq * topn)) || (rc = dev_alloc(d_score, (size_t)nq * topn))) return rc;
+    if ((rc = queries ? upload(d_q, queries, (size_t)nq * dim) : upload(d_r, rows, nq))) return rc;
     if ((rc = knn_query_impl(k.get(), queries ? d_q.p : nullptr, rows ? d_r.p : nullptr, nq, topn, metric, exclude_self, d_idx.p, d_score.p, tiles,
                              nullptr)))
         return rc;
-    HIP_TRY(hipMemcpy(idx, d_idx.p, sizeof(uint32_t) * (size_t)nq * topn, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(score, d_score.p, sizeof(double) * (size_t)nq * topn, hipMemcpyDeviceToHost));
+    if ((rc = download(idx, d_idx, (size_t)nq * topn)) || (rc = download(score, d_score, (size_t)nq * topn))) return rc;
     return PW_OK;
 }

@@ -1,19 +1,16 @@
 #pragma once
 // Host driver, exact logistic regression on embedding rows and pair operators (logit.hip.h): one evaluation of the loss, the
 // gradient and the decision values over two pw_knn indexes.  Exports pw_logit_eval_device, pw_logit_eval_device_grid,
-// pw_selftest_logit, pw_selftest_logit_math.  Stands on the core and on drv_knn (pw_knn, knn_alloc, knn_check_shape).
+// pw_selftest_logit, pw_selftest_logit_math.  Stands on the core, drv_knn (pw_knn, KnnOwner, knn_check_shape) and drv_pairs (pair_range).
 #include "drv_core.hip.h"
 #include "drv_knn.hip.h"
+#include "drv_pairs.hip.h"
 #include "logit.hip.h"
 
 namespace {
 
 constexpr int LG_MAX_BLOCKS = 65536;
 
-int lg_pair_range(const char *which, uint64_t i, uint32_t row, uint64_t n) {
-    return fail(PW_ERR_INVALID, std::string("pw_logit_eval: row number ") + which + "[" + std::to_string(i) + "] = " + std::to_string(row) +
-                                    " is outside the " + std::to_string(n) + " rows");
-}
 int lg_bad_label(uint64_t i, uint32_t y) {
     return fail(PW_ERR_INVALID, "pw_logit_eval: label y[" + std::to_string(i) + "] = " + std::to_string(y) + " is neither 0 nor 1");
 }
@@ -80,23 +77,22 @@ int logit_eval_impl(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint3
 
     DevBuf<pw::LgFound> found;
     DevBuf<double> theta_dev, z_tmp, r_tmp, l_tmp, part, totals;
-    if ((rc = knn_alloc(found, 1)) || (rc = knn_alloc(theta_dev, dim + 1)) || (d_z && (rc = knn_alloc(z_tmp, m)))) return rc;
-    if (d_y && ((rc = knn_alloc(r_tmp, m)) || (rc = knn_alloc(l_tmp, m)) || (rc = knn_alloc(part, (size_t)n_chunks * n_cols)) ||
-                (rc = knn_alloc(totals, n_cols))))
+    if ((rc = dev_alloc(found, 1)) || (rc = dev_alloc(theta_dev, dim + 1)) || (d_z && (rc = dev_alloc(z_tmp, m)))) return rc;
+    if (d_y && ((rc = dev_alloc(r_tmp, m)) || (rc = dev_alloc(l_tmp, m)) || (rc = dev_alloc(part, (size_t)n_chunks * n_cols)) ||
+                (rc = dev_alloc(totals, n_cols))))
         return rc;
     HIP_TRY(hipMemsetAsync(found.p, 0xff, sizeof(pw::LgFound), nullptr));
     HIP_TRY(hipMemcpyAsync(theta_dev.p, theta, sizeof(double) * (dim + 1), hipMemcpyHostToDevice, nullptr));
-    const unsigned check_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)a->n_cu * 16));
-    hipLaunchKernelGGL(pw::lg_check_kernel, dim3(check_grid), dim3(256), 0, nullptr, d_u, d_v, d_y, m, a->n, b->n, op, found.p);
+    hipLaunchKernelGGL(pw::lg_check_kernel, dim3(strided_grid(m, a->n_cu)), dim3(256), 0, nullptr, d_u, d_v, d_y, m, a->n, b->n, op, found.p);
     HIP_TRY(hipGetLastError());
     pw::LgFound h;
     HIP_TRY(hipMemcpy(&h, found.p, sizeof(h), hipMemcpyDeviceToHost));
     if (h.row != ~0ull) {
         uint32_t ru = 0, rv = 0;
         HIP_TRY(hipMemcpy(&ru, d_u + h.row, sizeof(ru), hipMemcpyDeviceToHost));
-        if (ru >= a->n) return lg_pair_range("u", h.row, ru, a->n);
+        if (ru >= a->n) return pair_range("pw_logit_eval", "u", h.row, ru, a->n);
         HIP_TRY(hipMemcpy(&rv, d_v + h.row, sizeof(rv), hipMemcpyDeviceToHost));
-        return lg_pair_range("v", h.row, rv, b->n);
+        return pair_range("pw_logit_eval", "v", h.row, rv, b->n);
     }
     if (h.label != ~0ull) {
         uint8_t y = 0;
@@ -109,10 +105,9 @@ int logit_eval_impl(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint3
     f.z = z_tmp.p; f.r = r_tmp.p; f.ell = l_tmp.p; f.found = found.p;
     f.m = m; f.n_tiles = (m + 63) / 64; f.dim = dim;
     const void *fwd = lg_forward_fn(op);
-    int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fwd, (int)pw::LG_FWD_THREADS, 0));
-    const uint64_t fwd_blocks = blocks > 0 ? (uint64_t)blocks
-                                           : std::min<uint64_t>((f.n_tiles + pw::LG_FWD_WAVES - 1) / pw::LG_FWD_WAVES, (uint64_t)std::max(1, occ) * a->n_cu);
+    uint64_t fwd_blocks = 0, grad_blocks = 0;   // (the occupancy is asked for with a forced grid too, as it always was)
+    if ((rc = persistent_tile_grid(fwd, (int)pw::LG_FWD_THREADS, pw::LG_FWD_WAVES, f.n_tiles, a->n_cu, 0, &fwd_blocks))) return rc;
+    if (blocks > 0) fwd_blocks = (uint64_t)blocks;
     pw::Event ev[2];
     if (kernel_ms) {
         for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
@@ -127,9 +122,8 @@ int logit_eval_impl(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint3
         g.A = a->X.p; g.B = b->X.p; g.u = d_u; g.v = d_v; g.r = r_tmp.p; g.ell = l_tmp.p; g.part = part.p;
         g.m = m; g.n_chunks = n_chunks; g.dim = dim;
         const void *gk = lg_grad_fn(op, (dim + pw::LG_COLS - 1) / pw::LG_COLS);
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gk, (int)pw::LG_GRAD_THREADS, 0));
-        const uint64_t grad_blocks =
-            blocks > 0 ? (uint64_t)blocks : std::min<uint64_t>((n_chunks + pw::LG_GRAD_WAVES - 1) / pw::LG_GRAD_WAVES, (uint64_t)std::max(1, occ) * a->n_cu);
+        if ((rc = persistent_tile_grid(gk, (int)pw::LG_GRAD_THREADS, pw::LG_GRAD_WAVES, n_chunks, a->n_cu, 0, &grad_blocks))) return rc;
+        if (blocks > 0) grad_blocks = (uint64_t)blocks;
         void *args[] = {(void *)&g};
         HIP_TRY(hipLaunchKernel(gk, dim3((unsigned)grad_blocks), dim3(pw::LG_GRAD_THREADS), args, 0, nullptr));
         hipLaunchKernelGGL(pw::lg_reduce_kernel, dim3((n_cols + 63) / 64), dim3(64), 0, nullptr, (const double *)part.p, n_chunks, n_cols, totals.p);
@@ -177,32 +171,22 @@ PW_EXPORT int pw_selftest_logit(int on_device, int device, const float *a, uint6
         if (pw::knn_host_norms(a, na, dim, norms.data(), &where) || (b && pw::knn_host_norms(b, nb, dim, norms.data(), &where))) return knn_bad_row(where);
         const uint64_t rows_b = b ? nb : na;
         switch (pw::lg_host_eval(a, na, b ? b : a, rows_b, dim, u, v, y, m, op, theta, l2, loss, grad, z, &where)) {
-            case pw::LG_HOST_U_RANGE: return lg_pair_range("u", where, u[where], na);
-            case pw::LG_HOST_V_RANGE: return lg_pair_range("v", where, v[where], rows_b);
+            case pw::LG_HOST_U_RANGE: return pair_range("pw_logit_eval", "u", where, u[where], na);
+            case pw::LG_HOST_V_RANGE: return pair_range("pw_logit_eval", "v", where, v[where], rows_b);
             case pw::LG_HOST_LABEL: return lg_bad_label(where, y[where]);
             case pw::LG_HOST_Z: return lg_bad_z(where);
             default: break;
         }
         return PW_OK;
     }
-    struct Closer { void operator()(pw_knn *k) const { pw_knn_destroy(k); } };
-    pw_knn *raw = nullptr;
-    if ((rc = pw_knn_create(device, a, na, dim, &raw))) return rc;
-    std::unique_ptr<pw_knn, Closer> ka(raw), kb;
-    if (b) {
-        if ((rc = pw_knn_create(device, b, nb, dim, &raw))) return rc;
-        kb.reset(raw);
-    }
+    KnnOwner ka, kb;
+    if ((rc = knn_own(device, a, na, dim, ka)) || (b && (rc = knn_own(device, b, nb, dim, kb)))) return rc;
     DevBuf<uint32_t> d_u, d_v;
     DevBuf<uint8_t> d_y;
     DevBuf<double> d_z;
-    if ((rc = knn_alloc(d_u, m)) || (v && (rc = knn_alloc(d_v, m))) || (y && (rc = knn_alloc(d_y, m))) || (z && (rc = knn_alloc(d_z, m)))) return rc;
-    HIP_TRY(hipMemcpy(d_u.p, u, sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-    if (v) HIP_TRY(hipMemcpy(d_v.p, v, sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-    if (y) HIP_TRY(hipMemcpy(d_y.p, y, m, hipMemcpyHostToDevice));
+    if ((rc = upload(d_u, u, m)) || (v && (rc = upload(d_v, v, m))) || (y && (rc = upload(d_y, y, m))) || (z && (rc = dev_alloc(d_z, m)))) return rc;
     if ((rc = logit_eval_impl(ka.get(), kb.get(), d_u.p, d_v.p, d_y.p, m, op, theta, l2, loss, grad, d_z.p, blocks, nullptr))) return rc;
-    if (z) HIP_TRY(hipMemcpy(z, d_z.p, sizeof(double) * m, hipMemcpyDeviceToHost));
-    return PW_OK;
+    return z ? download(z, d_z, m) : PW_OK;
 }
 
 PW_EXPORT int pw_selftest_logit_math(int which, const double *x, uint64_t n, double *out) {

@@ -1,24 +1,18 @@
 #pragma once
 // Host driver, neighbourhood link-prediction baselines (nbr_scores.hip.h): the degrees without the loop and the scores of given
 // pairs on a CSR handle.  Exports pw_nbr_degrees_device, pw_nbr_scores_device, pw_nbr_scores_device_cut, pw_selftest_nbr_scores, pw_selftest_nbr_degrees.
-// Stands on the core, on drv_knn (knn_alloc) and on the public pw_csr_create alone.
+// Stands on the core, on drv_pairs (the range check of the pairs) and on the public pw_csr_create alone.
 #include "drv_core.hip.h"
-#include "drv_knn.hip.h"
+#include "drv_pairs.hip.h"
 #include "nbr_scores.hip.h"
 
 namespace {
-
-unsigned nbr_grid(uint64_t n, int n_cu) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, n_cu) * 16)); }
 
 int nbr_check_kind(int kind, const void *table) {
     if (kind < 0 || kind >= pw::NBR_KINDS)
         return fail(PW_ERR_INVALID, "pw_nbr_scores: kind " + std::to_string(kind) + " is none of PW_NBR_COMMON, PW_NBR_JACCARD, PW_NBR_PREF, PW_NBR_WEIGHTED");
     if (kind == pw::NBR_WEIGHTED && !table) return fail(PW_ERR_INVALID, "pw_nbr_scores: PW_NBR_WEIGHTED needs a table");
     return 0;
-}
-int nbr_pair_range(const char *which, uint64_t i, uint32_t row, uint64_t n) {
-    return fail(PW_ERR_INVALID, std::string("pw_nbr_scores: row number ") + which + "[" + std::to_string(i) + "] = " + std::to_string(row) +
-                                    " is outside the " + std::to_string(n) + " rows");
 }
 int nbr_need_csr(const pw_graph *g, const char *what) {
     return g->gd->kind != 0 ? fail(PW_ERR_UNSUPPORTED, std::string(what) + " needs a CSR graph handle") : 0;
@@ -29,7 +23,7 @@ int nbr_degrees_impl(pw_graph *g, uint32_t *d_deg) {
     if (int rc = nbr_need_csr(g, "pw_nbr_degrees")) return rc;
     if (set_device(g)) return PW_ERR_HIP;
     const uint32_t n_nodes = g->gd->n_nodes;
-    hipLaunchKernelGGL(pw::nbr_degrees_kernel, dim3(nbr_grid(n_nodes, g->n_cu)), dim3(256), 0, g->stream, (const uint32_t *)g->gd->d_indptr.p,
+    hipLaunchKernelGGL(pw::nbr_degrees_kernel, dim3(strided_grid(n_nodes, g->n_cu)), dim3(256), 0, g->stream, (const uint32_t *)g->gd->d_indptr.p,
                        (const uint32_t *)g->gd->d_indices.p, n_nodes, d_deg);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -52,30 +46,15 @@ int nbr_scores_impl(pw_graph *g, const uint32_t *d_u, const uint32_t *d_v, uint6
     if (!d_u || !d_v || !d_score) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
     const uint32_t n_nodes = g->gd->n_nodes;
-    DevBuf<pw::LpFound> found;
-    if ((rc = knn_alloc(found, 1))) return rc;
-    HIP_TRY(hipMemsetAsync(found.p, 0xff, sizeof(pw::LpFound), g->stream));
-    hipLaunchKernelGGL(pw::lp_check_pairs_kernel, dim3(nbr_grid(m, g->n_cu)), dim3(256), 0, g->stream, d_u, d_v, m, (uint64_t)n_nodes, (uint64_t)n_nodes,
-                       found.p);
-    HIP_TRY(hipGetLastError());
-    pw::LpFound h;
-    HIP_TRY(hipMemcpyAsync(&h, found.p, sizeof(h), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (h.first != ~0ull) {
-        uint32_t ru = 0, rv = 0;
-        HIP_TRY(hipMemcpy(&ru, d_u + h.first, sizeof(ru), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&rv, d_v + h.first, sizeof(rv), hipMemcpyDeviceToHost));
-        return ru >= n_nodes ? nbr_pair_range("u", h.first, ru, n_nodes) : nbr_pair_range("v", h.first, rv, n_nodes);
-    }
+    if ((rc = check_pairs(g->stream, g->n_cu, d_u, d_v, m, n_nodes, n_nodes, "pw_nbr_scores"))) return rc;
     pw::NbrArgs a;
     a.indptr = g->gd->d_indptr.p; a.indices = g->gd->d_indices.p;
     a.table = kind == pw::NBR_WEIGHTED ? d_table : nullptr;
     a.u = d_u; a.v = d_v; a.score = d_score;
     a.m = m; a.n_tiles = (m + 63) / 64;
     a.kind = (uint32_t)kind; a.short_max = short_max < 0 ? pw::NBR_SHORT_MAX : (uint32_t)short_max;
-    int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::nbr_scores_kernel, (int)pw::NBR_THREADS, 0));
-    const uint64_t blocks = std::min<uint64_t>((a.n_tiles + pw::NBR_WAVES - 1) / pw::NBR_WAVES, (uint64_t)std::max(1, occ) * std::max(1, g->n_cu));
+    uint64_t blocks = 0;
+    if ((rc = persistent_tile_grid((const void *)pw::nbr_scores_kernel, (int)pw::NBR_THREADS, pw::NBR_WAVES, a.n_tiles, g->n_cu, 0, &blocks))) return rc;
     pw::Event ev[2];
     if (kernel_ms) {
         for (auto &e : ev) HIP_TRY(e.create(hipEventDefault));
@@ -119,9 +98,8 @@ PW_EXPORT int pw_selftest_nbr_degrees(int on_device, int device, const uint32_t 
     if ((rc = pw_csr_create(indptr, indices, nullptr, n_nodes, indptr[n_nodes], device, &raw))) return rc;
     GraphOwner g(raw);   // (declared before the buffer: it goes first)
     DevBuf<uint32_t> d_deg;
-    if ((rc = knn_alloc(d_deg, n_nodes)) || (rc = nbr_degrees_impl(g.get(), d_deg.p))) return rc;
-    HIP_TRY(hipMemcpy(deg, d_deg.p, sizeof(uint32_t) * (size_t)n_nodes, hipMemcpyDeviceToHost));
-    return PW_OK;
+    if ((rc = dev_alloc(d_deg, n_nodes)) || (rc = nbr_degrees_impl(g.get(), d_deg.p))) return rc;
+    return download(deg, d_deg, n_nodes);
 }
 
 PW_EXPORT int pw_selftest_nbr_scores(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes, const uint32_t *u,
@@ -135,8 +113,8 @@ PW_EXPORT int pw_selftest_nbr_scores(int on_device, int device, const uint32_t *
         std::vector<double> sc(m);   // (a refused call writes nothing)
         uint64_t where = 0;
         switch (pw::nbr_host_scores(indptr, indices, n_nodes, u, v, m, kind, table, sc.data(), &where)) {
-            case pw::LP_HOST_U_RANGE: return nbr_pair_range("u", where, u[where], n_nodes);
-            case pw::LP_HOST_V_RANGE: return nbr_pair_range("v", where, v[where], n_nodes);
+            case pw::LP_HOST_U_RANGE: return pair_range("pw_nbr_scores", "u", where, u[where], n_nodes);
+            case pw::LP_HOST_V_RANGE: return pair_range("pw_nbr_scores", "v", where, v[where], n_nodes);
             default: break;
         }
         if (m) memcpy(score, sc.data(), sizeof(double) * m);
@@ -148,14 +126,8 @@ PW_EXPORT int pw_selftest_nbr_scores(int on_device, int device, const uint32_t *
     if (m == 0) return PW_OK;
     DevBuf<uint32_t> d_u, d_v;
     DevBuf<double> d_table, d_score;
-    if ((rc = knn_alloc(d_u, m)) || (rc = knn_alloc(d_v, m)) || (rc = knn_alloc(d_score, m))) return rc;
-    HIP_TRY(hipMemcpy(d_u.p, u, sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_v.p, v, sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-    if (kind == pw::NBR_WEIGHTED) {
-        if ((rc = knn_alloc(d_table, n_nodes))) return rc;
-        HIP_TRY(hipMemcpy(d_table.p, table, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice));
-    }
+    if ((rc = upload(d_u, u, m)) || (rc = upload(d_v, v, m)) || (rc = dev_alloc(d_score, m))) return rc;
+    if (kind == pw::NBR_WEIGHTED && (rc = upload(d_table, table, n_nodes))) return rc;
     if ((rc = nbr_scores_impl(g.get(), d_u.p, d_v.p, m, kind, d_table.p, d_score.p, short_max, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(score, d_score.p, sizeof(double) * m, hipMemcpyDeviceToHost));
-    return PW_OK;
+    return download(score, d_score, m);
 }

@@ -5,10 +5,10 @@
 // bit-exact float chain depends on separately rounded operations.)
 //
 // The library is this ONE translation unit.  The host driver is this file and the drv_*.hip.h pieces it includes, one topic
-// each ("Where the host code lives"): drv_core, which everything stands on, and the topics that need drv_core
-// alone.  A piece is included at its place in the text, not at the end by habit: template kernels are instantiated, and
-// drv_selftest's own kernels emitted, in the order of the text.  Every piece includes the kernel headers it uses and passes
-// `hipcc -fsyntax-only -x hip drv_X.hip.h` by itself.
+// each ("Where the host code lives"): drv_core, which everything stands on, and the leaf topics.  This file keeps the
+// walk core; the leaves call into it through the public API and stream_words_window alone, which drv_core declares.  A piece is
+// included at its place in the text, not at the end by habit: template kernels are instantiated, and drv_selftest's own kernels
+// emitted, in the order of the text.  Every piece includes what it uses and passes `hipcc -fsyntax-only -x hip drv_X.hip.h` by itself.
 //
 // The kernel headers, in the order that fixes the order of the device code in the code object (the pieces include the ones
 // they use again: no-ops here):
@@ -38,7 +38,7 @@
 #include "linkpred.hip.h"
 #include "holdout.hip.h"
 
-// the system includes, PW_EXPORT, fail / HIP_TRY, LaneSwitches, the handle structs, GraphOwner, csr_dev, graph_common_init
+// the system includes, PW_EXPORT, fail / HIP_TRY, LaneSwitches, the handle structs and owners, csr_dev, graph_common_init, the shared helpers
 #include "drv_core.hip.h"
 
 // Lane-kernel index (walk_lanes.hip.h): one 64-byte edge line per CSR entry (the record of the edge + its list of
@@ -595,15 +595,6 @@ PW_EXPORT int pw_csr_create(const uint32_t *indptr, const uint32_t *indices, con
 }
 
 // ---- CSR from an edge list in device memory (csrc/coo_csr.hip.h) -----------------------------------------------------------------
-struct pw_csr_dev {
-    int device = 0;
-    uint64_t n_nodes = 0, nnz = 0, insertions = 0, dropped = 0;
-    double build_ms = 0;
-    DevBuf<uint32_t> d_indptr, d_indices;
-    DevBuf<float> d_data;      // empty: no weights were given (every weight 1.0)
-    DevBuf<double> d_data64;   // the edge-list reader with PW_EDGELIST_KEEP_F64: every entry's weight as parsed; empty otherwise
-};
-
 PW_EXPORT void pw_csr_dev_destroy(pw_csr_dev *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -624,7 +615,7 @@ static int coo_to_csr_build(int device, const int64_t *d_src, const int64_t *d_d
     HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
-    const unsigned stride_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)prop.multiProcessorCount * 16));
+    const unsigned stride_grid = strided_grid(m, prop.multiProcessorCount);
 
     // what the call holds beside its scratch buffers: the result until it is handed out, and the events of the three kernel
     // spans (begin / end)
@@ -2926,6 +2917,17 @@ static int expand_stream(pw_graph *g, uint32_t seed, bool cacheable, uint64_t st
     return 0;
 }
 
+// The raw words [w0, w0 + n) of `seed`'s stream (624 per block of 312 draws), expanded in whole blocks into g->stream_words on g->stream:
+// *words points at word w0, until the next call that expands words on this context.  (Declared in drv_core.hip.h for the leaf pieces.)
+static int stream_words_window(pw_graph *g, uint32_t seed, uint64_t w0, uint64_t n, const uint32_t **words) {
+    const uint64_t first = w0 / pw::SEQ_BLOCK, n_blocks = (w0 + n + pw::SEQ_BLOCK - 1) / pw::SEQ_BLOCK - first;
+    if (grow(g->stream_words, (size_t)n_blocks * pw::SEQ_BLOCK)) return PW_ERR_NOMEM;
+    uint64_t base = 0;
+    if (int rc = expand_stream(g, seed, false, first * 312, n_blocks * 312, &base, g->stream_words.p)) return rc;
+    *words = g->stream_words.p + (w0 - first * pw::SEQ_BLOCK);
+    return 0;
+}
+
 // The draws [stream_skip, stream_skip + n_draws) of `seed`'s stream expanded ONCE and kept: pw_simulate_device calls with that
 // seed whose range lies inside find their draws in place (no jump-ahead tree, no expansion) until pw_stream_release or the
 // next pw_stream_hold -- for a shard walked in chunks (every chunk would pay ~3 ms of sequential jump launches otherwise).
@@ -2967,12 +2969,9 @@ PW_EXPORT int pw_stream_words_device(pw_graph *g, uint32_t seed, uint64_t offset
     if (!g || (n && !out)) return fail(PW_ERR_INVALID, "null pointer");
     if (set_device(g)) return PW_ERR_HIP;
     if (!n) return PW_OK;
-    const uint64_t first = offset / pw::SEQ_BLOCK, n_blocks = (offset + n + pw::SEQ_BLOCK - 1) / pw::SEQ_BLOCK - first;
-    if (grow(g->stream_words, (size_t)n_blocks * pw::SEQ_BLOCK)) return PW_ERR_NOMEM;
-    uint64_t base = 0;
-    int rc = expand_stream(g, seed, false, first * 312, n_blocks * 312, &base, g->stream_words.p);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, g->stream_words.p + (offset - first * pw::SEQ_BLOCK), sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g->stream));
+    const uint32_t *words = nullptr;
+    if (int rc = stream_words_window(g, seed, offset, n, &words)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, words, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PW_OK;
 }
@@ -3996,511 +3995,9 @@ PW_EXPORT int pw_probs(pw_graph *g, int mode, double p, double q, int extend, ui
 #include "drv_sgns.hip.h"
 #include "drv_text_write.hip.h"
 #include "drv_knn.hip.h"
-
-// ---- link prediction: pair scores, exact AUC, non-edges from the seeded stream (csrc/linkpred.hip.h) ---------------------------
-namespace {
-
-constexpr uint64_t LP_BATCH_MIN = 1ull << 16, LP_BATCH_MAX = 1ull << 24;   // candidates per batch of the sampler (default form)
-
-unsigned lp_grid(uint64_t n, int n_cu) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(1, n_cu) * 16)); }
-
-int lp_check_metric(int metric) {
-    return metric == PW_KNN_DOT || metric == PW_KNN_COSINE ? 0 : fail(PW_ERR_INVALID, "pw_knn_score_pairs: metric must be PW_KNN_DOT or PW_KNN_COSINE");
-}
-int lp_pair_range(const char *which, uint64_t i, uint32_t row, uint64_t n) {
-    return fail(PW_ERR_INVALID, std::string("pw_knn_score_pairs: row number ") + which + "[" + std::to_string(i) + "] = " + std::to_string(row) +
-                                    " is outside the " + std::to_string(n) + " rows");
-}
-int lp_dim_mismatch(uint32_t da, uint32_t db) {
-    return fail(PW_ERR_INVALID, "pw_knn_score_pairs: the two indexes have dim " + std::to_string(da) + " and " + std::to_string(db));
-}
-int auc_check_sizes(uint64_t m, uint64_t n) {
-    if (m < 1 || n < 1) return fail(PW_ERR_INVALID, "pw_auc: both arrays need at least one score");
-    if (n >= (1ull << 32)) return fail(PW_ERR_INVALID, "pw_auc: n must be below 2^32");
-    if ((unsigned __int128)m * n >= ((unsigned __int128)1 << 62)) return fail(PW_ERR_INVALID, "pw_auc: m * n must be below 2^62");
-    return 0;
-}
-int auc_nan(const char *which, uint64_t i) { return fail(PW_ERR_INVALID, std::string("pw_auc: ") + which + "[" + std::to_string(i) + "] is a NaN"); }
-int lp_no_non_edge(uint64_t n_nodes) {
-    return fail(PW_ERR_INVALID, "pw_sample_non_edges: the graph of " + std::to_string(n_nodes) + " vertices has no off-diagonal non-edge");
-}
-int lp_cap_passed(uint64_t cap, uint64_t got, uint64_t m) {
-    return fail(PW_ERR_INVALID, "pw_sample_non_edges: " + std::to_string(cap) + " candidates examined (the cap) gave " + std::to_string(got) + " of the " +
-                                    std::to_string(m) + " non-edges asked for");
-}
-
-int score_pairs_impl(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint32_t *d_v, uint64_t m, int metric, double *d_score) {
-    if (!a) return fail(PW_ERR_INVALID, "null pointer");
-    if (!b) b = a;
-    if (int rc = lp_check_metric(metric)) return rc;
-    if (a->dim != b->dim) return lp_dim_mismatch(a->dim, b->dim);
-    if (a->device != b->device) return fail(PW_ERR_INVALID, "pw_knn_score_pairs: the two indexes are on different devices");
-    if (m == 0) return PW_OK;
-    if (!d_u || !d_v || !d_score) return fail(PW_ERR_INVALID, "null pointer");
-    HIP_TRY(hipSetDevice(a->device));
-    DevBuf<pw::LpFound> found;
-    if (int rc = knn_alloc(found, 1)) return rc;
-    HIP_TRY(hipMemsetAsync(found.p, 0xff, sizeof(pw::LpFound), nullptr));
-    hipLaunchKernelGGL(pw::lp_check_pairs_kernel, dim3(lp_grid(m, a->n_cu)), dim3(256), 0, nullptr, d_u, d_v, m, a->n, b->n, found.p);
-    HIP_TRY(hipGetLastError());
-    pw::LpFound h;
-    HIP_TRY(hipMemcpy(&h, found.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (h.first != ~0ull) {
-        uint32_t ru = 0, rv = 0;
-        HIP_TRY(hipMemcpy(&ru, d_u + h.first, sizeof(ru), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&rv, d_v + h.first, sizeof(rv), hipMemcpyDeviceToHost));
-        return ru >= a->n ? lp_pair_range("u", h.first, ru, a->n) : lp_pair_range("v", h.first, rv, b->n);
-    }
-    pw::LpScoreArgs s;
-    s.A = a->X.p; s.B = b->X.p; s.anorms = a->norms.p; s.bnorms = b->norms.p;
-    s.u = d_u; s.v = d_v; s.score = d_score;
-    s.m = m; s.n_tiles = (m + 63) / 64;
-    s.dim = a->dim; s.metric = (uint32_t)metric;
-    int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)pw::lp_score_pairs_kernel, (int)pw::LP_THREADS, 0));
-    const uint64_t blocks = std::min<uint64_t>((s.n_tiles + pw::LP_WAVES - 1) / pw::LP_WAVES, (uint64_t)std::max(1, occ) * a->n_cu);
-    hipLaunchKernelGGL(pw::lp_score_pairs_kernel, dim3((unsigned)blocks), dim3(pw::LP_THREADS), 0, nullptr, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return PW_OK;
-}
-
-int auc_impl(int device, const double *d_pos, uint64_t m, const double *d_neg, uint64_t n, uint64_t out[2]) {
-    if (!out) return fail(PW_ERR_INVALID, "null pointer");
-    int rc;
-    if ((rc = auc_check_sizes(m, n))) return rc;
-    if (!d_pos || !d_neg) return fail(PW_ERR_INVALID, "null pointer");
-    if ((rc = check_device(device))) return rc;
-    HIP_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    const int n_cu = std::max(1, prop.multiProcessorCount);
-    const uint64_t n_waves = (n + pw::RADIX_SUB - 1) / pw::RADIX_SUB, hist_elems = (uint64_t)pw::RADIX_BINS * n_waves;
-    DevBuf<uint64_t> pos_keys, neg_keys[2];
-    DevBuf<uint32_t> hist, tmp;
-    DevBuf<unsigned long long> cells;   // [0] first NaN of pos, [1] of neg, [2] wins, [3] ties
-    if ((rc = knn_alloc(pos_keys, m)) || (rc = knn_alloc(neg_keys[0], n)) || (rc = knn_alloc(neg_keys[1], n)) || (rc = knn_alloc(hist, hist_elems)) ||
-        (rc = knn_alloc(tmp, pw::scan_scratch_elems(hist_elems))) || (rc = knn_alloc(cells, 4)))
-        return rc;
-    HIP_TRY(hipMemsetAsync(cells.p, 0xff, 2 * sizeof(unsigned long long), nullptr));
-    HIP_TRY(hipMemsetAsync(cells.p + 2, 0, 2 * sizeof(unsigned long long), nullptr));
-    hipLaunchKernelGGL(pw::auc_keys_kernel, dim3(lp_grid(m, n_cu)), dim3(256), 0, nullptr, d_pos, m, pos_keys.p, (pw::LpFound *)(cells.p + 0));
-    hipLaunchKernelGGL(pw::auc_keys_kernel, dim3(lp_grid(n, n_cu)), dim3(256), 0, nullptr, d_neg, n, neg_keys[0].p, (pw::LpFound *)(cells.p + 1));
-    HIP_TRY(hipGetLastError());
-    unsigned long long h[4];
-    HIP_TRY(hipMemcpy(h, cells.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (h[0] != ~0ull) return auc_nan("pos", h[0]);
-    if (h[1] != ~0ull) return auc_nan("neg", h[1]);
-    uint64_t *keys[2] = {neg_keys[0].p, neg_keys[1].p};   // (the sort swaps the two views; the owners stay put)
-    const unsigned wave_grid = (unsigned)((n_waves + 3) / 4);
-    for (int shift = 0; shift < 64; shift += pw::RADIX_BITS) {
-        hipLaunchKernelGGL(pw::radix_hist_kernel, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)keys[0], n, shift, hist.p, n_waves);
-        pw::exclusive_scan_inplace(nullptr, hist.p, hist_elems, tmp.p);
-        hipLaunchKernelGGL(pw::radix_scatter_kernel<false>, dim3(wave_grid), dim3(256), 0, nullptr, (const uint64_t *)keys[0], (const uint32_t *)nullptr, keys[1],
-                           (uint32_t *)nullptr, n, shift, (const uint32_t *)hist.p, n_waves);
-        std::swap(keys[0], keys[1]);
-    }
-    hipLaunchKernelGGL(pw::auc_count_kernel, dim3(lp_grid(m, n_cu)), dim3(256), 0, nullptr, (const uint64_t *)pos_keys.p, m, (const uint64_t *)keys[0], n,
-                       cells.p + 2);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(h + 2, cells.p + 2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    out[0] = h[2];
-    out[1] = h[3];
-    return PW_OK;
-}
-
-// batch: candidates per batch; 0 = by m and the share of acceptable candidates.  The output does not depend on it.
-int sample_non_edges_impl(pw_graph *g, uint32_t seed, uint64_t first_candidate, uint64_t m, uint32_t *d_u, uint32_t *d_v, uint64_t *candidates_used,
-                          uint64_t batch) {
-    if (!g || !candidates_used || (m && (!d_u || !d_v))) return fail(PW_ERR_INVALID, "null pointer");
-    if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "pw_sample_non_edges needs a CSR graph handle");
-    if (m >= (1ull << 32)) return fail(PW_ERR_INVALID, "pw_sample_non_edges: m must be below 2^32");
-    if (first_candidate >= (1ull << 60)) return fail(PW_ERR_INVALID, "pw_sample_non_edges: first_candidate must be below 2^60");
-    if (set_device(g)) return PW_ERR_HIP;
-    const uint32_t n_nodes = g->gd->n_nodes;
-    const uint32_t *indptr = g->gd->d_indptr.p, *indices = g->gd->d_indices.p;
-    DevBuf<unsigned long long> cells;   // [0] self loops, [1] the index of the batch's last wanted candidate
-    int rc;
-    if ((rc = knn_alloc(cells, 2))) return rc;
-    HIP_TRY(hipMemsetAsync(cells.p, 0, 2 * sizeof(unsigned long long), g->stream));
-    hipLaunchKernelGGL(pw::lp_loops_kernel, dim3(lp_grid(n_nodes, g->n_cu)), dim3(256), 0, g->stream, indptr, indices, n_nodes, cells.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long loops = 0;
-    HIP_TRY(hipMemcpyAsync(&loops, cells.p, sizeof(loops), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    const uint64_t acceptable = pw::lp_acceptable(n_nodes, g->gd->nnz, loops);
-    if (acceptable == 0) return lp_no_non_edge(n_nodes);
-    if (m == 0) { *candidates_used = 0; return PW_OK; }
-    const uint64_t cap = pw::lp_candidate_cap(m, n_nodes, acceptable);
-    if (batch == 0) {   // what the call is expected to need and an eighth more, within the bounds
-        const uint64_t expect = (cap - 64) / 16;
-        batch = std::min(LP_BATCH_MAX, std::max(LP_BATCH_MIN, expect + expect / 8));
-    }
-    DevBuf<uint32_t> out_u, out_v, flag, tmp;   // (the outputs are written behind the last batch: a refused call writes nothing)
-    if ((rc = knn_alloc(out_u, m)) || (rc = knn_alloc(out_v, m))) return rc;
-    uint64_t got = 0, c0 = 0, used = 0;
-    while (got < m) {
-        if (c0 >= cap) return lp_cap_passed(cap, got, m);
-        const uint64_t nb = std::min(batch, cap - c0);
-        // the batch's words: candidates first_candidate + c0 .. + nb, two words each, in whole blocks of the stream
-        const uint64_t w0 = 2 * (first_candidate + c0), first = w0 / pw::SEQ_BLOCK, n_blocks = (w0 + 2 * nb + pw::SEQ_BLOCK - 1) / pw::SEQ_BLOCK - first;
-        if (grow(g->stream_words, (size_t)n_blocks * pw::SEQ_BLOCK) || grow(flag, nb + 1) || grow(tmp, pw::scan_scratch_elems(nb + 1))) return PW_ERR_NOMEM;
-        uint64_t base = 0;
-        if ((rc = expand_stream(g, seed, false, first * 312, n_blocks * 312, &base, g->stream_words.p))) return rc;
-        const uint32_t *words = g->stream_words.p + (w0 - first * pw::SEQ_BLOCK);
-        hipLaunchKernelGGL(pw::lp_flag_kernel, dim3(lp_grid(nb + 1, g->n_cu)), dim3(256), 0, g->stream, indptr, indices, n_nodes, words, nb, flag.p);
-        pw::exclusive_scan_inplace(g->stream, flag.p, nb + 1, tmp.p);
-        const uint64_t want = m - got;
-        hipLaunchKernelGGL(pw::lp_compact_kernel, dim3(lp_grid(nb, g->n_cu)), dim3(256), 0, g->stream, words, (const uint32_t *)flag.p, nb, n_nodes, want,
-                           out_u.p + got, out_v.p + got, cells.p + 1);
-        HIP_TRY(hipGetLastError());
-        uint32_t total = 0;
-        unsigned long long last = 0;
-        HIP_TRY(hipMemcpyAsync(&total, tmp.p, sizeof(total), hipMemcpyDeviceToHost, g->stream));   // (scan.hip.h: [0] = the total)
-        HIP_TRY(hipMemcpyAsync(&last, cells.p + 1, sizeof(last), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (total >= want) {   // the final batch, cut where acceptance number m falls
-            used = c0 + last + 1;
-            got = m;
-        } else {
-            got += total;
-            c0 += nb;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(d_u, out_u.p, sizeof(uint32_t) * m, hipMemcpyDeviceToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(d_v, out_v.p, sizeof(uint32_t) * m, hipMemcpyDeviceToDevice, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    *candidates_used = used;
-    return PW_OK;
-}
-
-}  // namespace
-
-PW_EXPORT int pw_knn_score_pairs_device(pw_knn *a, const pw_knn *b, const uint32_t *d_u, const uint32_t *d_v, uint64_t m, int metric, double *d_score) {
-    return score_pairs_impl(a, b, d_u, d_v, m, metric, d_score);
-}
-
-PW_EXPORT int pw_auc_device(int device, const double *d_pos, uint64_t m, const double *d_neg, uint64_t n, uint64_t out[2]) {
-    return auc_impl(device, d_pos, m, d_neg, n, out);
-}
-
-PW_EXPORT int pw_sample_non_edges_device(pw_graph *g, uint32_t seed, uint64_t first_candidate, uint64_t m, uint32_t *d_u, uint32_t *d_v,
-                                         uint64_t *candidates_used) {
-    return sample_non_edges_impl(g, seed, first_candidate, m, d_u, d_v, candidates_used, 0);
-}
-
-PW_EXPORT int pw_selftest_score_pairs(int on_device, int device, const float *a, uint64_t na, const float *b, uint64_t nb, uint32_t dim, uint32_t dim_b,
-                                      const uint32_t *u, const uint32_t *v, uint64_t m, int metric, double *score) {
-    if (!a || (m && (!u || !v || !score))) return fail(PW_ERR_INVALID, "null pointer");
-    int rc;
-    if ((rc = knn_check_shape(na, dim)) || (b && (rc = knn_check_shape(nb, dim_b))) || (rc = lp_check_metric(metric))) return rc;
-    if (!on_device) {
-        std::vector<double> an(na), bn(b ? nb : 0);
-        uint64_t where = 0;
-        if (pw::knn_host_norms(a, na, dim, an.data(), &where) || (b && pw::knn_host_norms(b, nb, dim_b, bn.data(), &where))) return knn_bad_row(where);
-        if (b && dim_b != dim) return lp_dim_mismatch(dim, dim_b);
-        std::vector<double> sc(m);
-        const uint64_t rows_b = b ? nb : na;
-        switch (pw::lp_host_score_pairs(a, an.data(), na, b ? b : a, b ? bn.data() : an.data(), rows_b, dim, u, v, m, metric, sc.data(), &where)) {
-            case pw::LP_HOST_U_RANGE: return lp_pair_range("u", where, u[where], na);
-            case pw::LP_HOST_V_RANGE: return lp_pair_range("v", where, v[where], rows_b);
-            default: break;
-        }
-        if (m) memcpy(score, sc.data(), sizeof(double) * m);
-        return PW_OK;
-    }
-    struct Closer { void operator()(pw_knn *k) const { pw_knn_destroy(k); } };
-    pw_knn *raw = nullptr;
-    if ((rc = pw_knn_create(device, a, na, dim, &raw))) return rc;
-    std::unique_ptr<pw_knn, Closer> ka(raw), kb;
-    if (b) {
-        if ((rc = pw_knn_create(device, b, nb, dim_b, &raw))) return rc;
-        kb.reset(raw);
-    }
-    DevBuf<uint32_t> d_u, d_v;
-    DevBuf<double> d_score;
-    if (m) {
-        if ((rc = knn_alloc(d_u, m)) || (rc = knn_alloc(d_v, m)) || (rc = knn_alloc(d_score, m))) return rc;
-        HIP_TRY(hipMemcpy(d_u.p, u, sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_v.p, v, sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-    }
-    if ((rc = score_pairs_impl(ka.get(), kb.get(), d_u.p, d_v.p, m, metric, d_score.p))) return rc;
-    if (m) HIP_TRY(hipMemcpy(score, d_score.p, sizeof(double) * m, hipMemcpyDeviceToHost));
-    return PW_OK;
-}
-
-PW_EXPORT int pw_selftest_auc(int on_device, int device, const double *pos, uint64_t m, const double *neg, uint64_t n, uint64_t out[2]) {
-    if (!out) return fail(PW_ERR_INVALID, "null pointer");
-    int rc;
-    if ((rc = auc_check_sizes(m, n))) return rc;
-    if (!pos || !neg) return fail(PW_ERR_INVALID, "null pointer");
-    if (!on_device) {
-        std::vector<uint64_t> keys(std::max(m, n));
-        uint64_t where = 0;
-        if (pw::auc_host_keys(pos, m, keys.data(), &where)) return auc_nan("pos", where);
-        if (pw::auc_host_keys(neg, n, keys.data(), &where)) return auc_nan("neg", where);
-        std::sort(keys.begin(), keys.begin() + n);
-        pw::auc_host_count(pos, m, keys.data(), n, out);
-        return PW_OK;
-    }
-    if ((rc = check_device(device))) return rc;
-    HIP_TRY(hipSetDevice(device));
-    DevBuf<double> d_pos, d_neg;
-    if ((rc = knn_alloc(d_pos, m)) || (rc = knn_alloc(d_neg, n))) return rc;
-    HIP_TRY(hipMemcpy(d_pos.p, pos, sizeof(double) * m, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_neg.p, neg, sizeof(double) * n, hipMemcpyHostToDevice));
-    return auc_impl(device, d_pos.p, m, d_neg.p, n, out);
-}
-
-PW_EXPORT int pw_selftest_sample_non_edges(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, uint32_t n_nodes, uint32_t seed,
-                                           uint64_t first_candidate, uint64_t m, uint64_t batch, uint32_t *u, uint32_t *v, uint64_t *candidates_used) {
-    if (!indptr || !candidates_used || (m && (!u || !v)) || n_nodes == 0 || (indptr[n_nodes] && !indices)) return fail(PW_ERR_INVALID, "null pointer");
-    if (m >= (1ull << 32)) return fail(PW_ERR_INVALID, "pw_sample_non_edges: m must be below 2^32");
-    if (first_candidate >= (1ull << 60)) return fail(PW_ERR_INVALID, "pw_sample_non_edges: first_candidate must be below 2^60");
-    if (!on_device) {
-        const uint64_t acceptable = pw::lp_acceptable(n_nodes, indptr[n_nodes], pw::lp_host_loops(indptr, indices, n_nodes));
-        if (acceptable == 0) return lp_no_non_edge(n_nodes);
-        if (m == 0) { *candidates_used = 0; return PW_OK; }
-        const uint64_t cap = pw::lp_candidate_cap(m, n_nodes, acceptable);
-        std::vector<uint32_t> hu(m), hv(m), words;
-        uint64_t have0 = 0;   // words holds the words of the candidates have0 .. have0 + words.size() / 2
-        auto more = [&](uint64_t c) {
-            if (c >= have0 + words.size() / 2) {
-                have0 = c;
-                words.resize(2 * std::min<uint64_t>(1u << 16, cap - c));
-                pw::mt_words_host(seed, 2 * (first_candidate + c), words.size(), words.data());
-            }
-            return words.data() + 2 * (c - have0);
-        };
-        uint64_t used = 0;
-        if (pw::lp_host_sample(indptr, indices, n_nodes, m, cap, more, hu.data(), hv.data(), &used) == pw::LP_HOST_CAP) {
-            uint64_t got = 0;   // (counted again for the message: the refused call's arrays are not the caller's)
-            for (uint64_t c = 0; c < cap; c++) {
-                const uint32_t *w = more(c);
-                got += pw::lp_accept(indptr, indices, pw::lp_candidate(w[0], n_nodes), pw::lp_candidate(w[1], n_nodes)) ? 1 : 0;
-            }
-            return lp_cap_passed(cap, got, m);
-        }
-        memcpy(u, hu.data(), sizeof(uint32_t) * m);
-        memcpy(v, hv.data(), sizeof(uint32_t) * m);
-        *candidates_used = used;
-        return PW_OK;
-    }
-    pw_graph *raw = nullptr;
-    int rc;
-    if ((rc = pw_csr_create(indptr, indices, nullptr, n_nodes, indptr[n_nodes], device, &raw))) return rc;
-    GraphOwner g(raw);   // (declared before the buffers: they go first)
-    DevBuf<uint32_t> d_u, d_v;
-    if (m && ((rc = knn_alloc(d_u, m)) || (rc = knn_alloc(d_v, m)))) return rc;
-    uint64_t used = 0;
-    if ((rc = sample_non_edges_impl(g.get(), seed, first_candidate, m, d_u.p, d_v.p, &used, batch))) return rc;
-    if (m) {
-        HIP_TRY(hipMemcpy(u, d_u.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(v, d_v.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-    }
-    *candidates_used = used;
-    return PW_OK;
-}
-
+#include "drv_linkpred.hip.h"
 #include "drv_nbr.hip.h"
 #include "drv_logit.hip.h"
-
-// ---- edges held out by the seeded stream: the train CSR and the held-out pairs (csrc/holdout.hip.h) ---------------------------
-struct pw_holdout_dev {
-    int device = 0;
-    uint64_t held = 0, units = 0, protected_units = 0;
-    DevBuf<uint32_t> d_u, d_v;
-    DevBuf<float> d_w;
-};
-
-PW_EXPORT void pw_holdout_dev_destroy(pw_holdout_dev *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    delete h;
-}
-
-namespace {
-
-constexpr uint64_t HO_BATCH = 1ull << 24;   // words expanded at a time (default form): 64 MiB of stream words
-
-struct CsrDevDeleter { void operator()(pw_csr_dev *c) const { pw_csr_dev_destroy(c); } };
-struct HoldoutDeleter { void operator()(pw_holdout_dev *h) const { pw_holdout_dev_destroy(h); } };
-
-int ho_missing_mate(uint64_t e) {
-    return fail(PW_ERR_INVALID, "pw_holdout_edges: the CSR is not symmetric: the entry at position " + std::to_string(e) +
-                                    " has no mate (pass directed = 1 for a directed graph)");
-}
-int ho_check_args(uint64_t first_word) {
-    return first_word >= (1ull << 60) ? fail(PW_ERR_INVALID, "pw_holdout_edges: first_word must be below 2^60") : 0;
-}
-
-// batch: words expanded at a time; 0 = HO_BATCH.  The outputs do not depend on it.  stage_ms (may be NULL): the wall clock of
-// the word expansion, the flag kernels, the scans with the compaction -- each ended by a stream synchronise, for tools/holdout_bench.py
-int holdout_edges_impl(pw_graph *g, int directed, uint32_t seed, uint64_t first_word, uint32_t threshold, int protect, uint64_t batch,
-                       pw_csr_dev **train, pw_holdout_dev **held, double *stage_ms) {
-    if (!g || !train || !held) return fail(PW_ERR_INVALID, "null pointer");
-    if (g->gd->kind != 0) return fail(PW_ERR_UNSUPPORTED, "pw_holdout_edges needs a CSR graph handle");
-    int rc;
-    if ((rc = ho_check_args(first_word))) return rc;
-    if (set_device(g)) return PW_ERR_HIP;
-    const uint32_t n_nodes = g->gd->n_nodes, nnz = g->gd->nnz;
-    const uint32_t *indptr = g->gd->d_indptr.p, *indices = g->gd->d_indices.p;
-    const float *data = (const float *)g->gd->d_data.p;
-    if (batch == 0) batch = HO_BATCH;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double ms[3] = {0, 0, 0};
-
-    DevBuf<uint8_t> flags;
-    DevBuf<uint32_t> pos, tmp;
-    DevBuf<pw::HoCells> cells;
-    if ((rc = knn_alloc(flags, (size_t)nnz + 1)) || (rc = knn_alloc(cells, 1))) return rc;
-    HIP_TRY(hipMemsetAsync(flags.p, 0, (size_t)nnz + 1, g->stream));
-    HIP_TRY(hipMemsetAsync(cells.p, 0xff, sizeof(unsigned long long), g->stream));
-    HIP_TRY(hipMemsetAsync(&cells.p->units, 0, 2 * sizeof(unsigned long long), g->stream));
-    for (uint64_t e0 = 0; e0 < nnz; e0 += batch) {
-        const uint64_t nb = std::min<uint64_t>(batch, nnz - e0);
-        // the batch's words: w[first_word + e0 .. + nb), in whole blocks of the stream
-        const uint64_t w0 = first_word + e0, first = w0 / pw::SEQ_BLOCK, n_blocks = (w0 + nb + pw::SEQ_BLOCK - 1) / pw::SEQ_BLOCK - first;
-        if (grow(g->stream_words, (size_t)n_blocks * pw::SEQ_BLOCK)) return PW_ERR_NOMEM;
-        double t0 = now();
-        uint64_t base = 0;
-        if ((rc = expand_stream(g, seed, false, first * 312, n_blocks * 312, &base, g->stream_words.p))) return rc;
-        if (stage_ms) { HIP_TRY(hipStreamSynchronize(g->stream)); ms[0] += (now() - t0) * 1e3; t0 = now(); }
-        hipLaunchKernelGGL(pw::ho_flag_kernel, dim3(lp_grid(nb, g->n_cu)), dim3(256), 0, g->stream, indptr, indices, n_nodes, directed ? 1 : 0,
-                           protect ? 1 : 0, threshold, (const uint32_t *)(g->stream_words.p + (w0 - first * pw::SEQ_BLOCK)), (uint32_t)e0, (uint32_t)nb,
-                           flags.p, cells.p);
-        HIP_TRY(hipGetLastError());
-        if (stage_ms) { HIP_TRY(hipStreamSynchronize(g->stream)); ms[1] += (now() - t0) * 1e3; }
-    }
-    pw::HoCells h;
-    HIP_TRY(hipMemcpyAsync(&h, cells.p, sizeof(h), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (h.missing != ~0ull) return ho_missing_mate(h.missing);
-
-    const double t0 = now();
-    std::unique_ptr<pw_csr_dev, CsrDevDeleter> c(new pw_csr_dev());
-    std::unique_ptr<pw_holdout_dev, HoldoutDeleter> ho(new pw_holdout_dev());
-    c->device = ho->device = g->device;
-    c->n_nodes = n_nodes;
-    ho->units = h.units;
-    ho->protected_units = h.prot;
-    if ((rc = knn_alloc(c->d_indptr, (size_t)n_nodes + 1))) return rc;
-    if (nnz == 0) {   // (no entry: no scan to launch)
-        HIP_TRY(hipMemsetAsync(c->d_indptr.p, 0, sizeof(uint32_t) * ((size_t)n_nodes + 1), g->stream));
-        if ((rc = knn_alloc(c->d_indices, 0)) || (rc = knn_alloc(ho->d_u, 0)) || (rc = knn_alloc(ho->d_v, 0)) || (rc = knn_alloc(ho->d_w, 0))) return rc;
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        *train = c.release();
-        *held = ho.release();
-        return PW_OK;
-    }
-    const uint64_t cells_n = (uint64_t)nnz + 1;
-    if ((rc = knn_alloc(pos, cells_n)) || (rc = knn_alloc(tmp, pw::scan_scratch_elems(cells_n)))) return rc;
-    uint32_t total = 0;
-    pw::exclusive_scan(g->stream, cells_n, pw::HoBitCount{flags.p, nnz, pw::HO_KEEP}, pw::ScanStore<uint32_t>{pos.p}, tmp.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&total, tmp.p, sizeof(total), hipMemcpyDeviceToHost, g->stream));   // (scan.hip.h: [0] = the total)
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    c->nnz = total;
-    if ((rc = knn_alloc(c->d_indices, total)) || (data && (rc = knn_alloc(c->d_data, total)))) return rc;
-    hipLaunchKernelGGL(pw::ho_compact_kernel, dim3(lp_grid(nnz, g->n_cu)), dim3(256), 0, g->stream, indices, data, (const uint8_t *)flags.p,
-                       (const uint32_t *)pos.p, nnz, c->d_indices.p, c->d_data.p);
-    hipLaunchKernelGGL(pw::ho_indptr_kernel, dim3(lp_grid((uint64_t)n_nodes + 1, g->n_cu)), dim3(256), 0, g->stream, indptr, (const uint32_t *)pos.p, n_nodes,
-                       c->d_indptr.p);
-    pw::exclusive_scan(g->stream, cells_n, pw::HoBitCount{flags.p, nnz, pw::HO_HELD}, pw::ScanStore<uint32_t>{pos.p}, tmp.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&total, tmp.p, sizeof(total), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    ho->held = total;
-    if ((rc = knn_alloc(ho->d_u, total)) || (rc = knn_alloc(ho->d_v, total)) || (rc = knn_alloc(ho->d_w, total))) return rc;
-    hipLaunchKernelGGL(pw::ho_held_kernel, dim3(lp_grid(nnz, g->n_cu)), dim3(256), 0, g->stream, indptr, indices, data, n_nodes, (const uint8_t *)flags.p,
-                       (const uint32_t *)pos.p, nnz, ho->d_u.p, ho->d_v.p, ho->d_w.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    ms[2] = (now() - t0) * 1e3;
-    if (stage_ms) { stage_ms[0] = ms[0]; stage_ms[1] = ms[1]; stage_ms[2] = ms[2]; }
-    *train = c.release();
-    *held = ho.release();
-    return PW_OK;
-}
-
-}  // namespace
-
-PW_EXPORT int pw_holdout_edges_device(pw_graph *g, int directed, uint32_t seed, uint64_t first_word, uint32_t threshold, int protect,
-                                      pw_csr_dev **train, pw_holdout_dev **held, double stage_ms[3]) {
-    return holdout_edges_impl(g, directed, seed, first_word, threshold, protect, 0, train, held, stage_ms);
-}
-
-PW_EXPORT int pw_holdout_dev_shape(const pw_holdout_dev *h, uint64_t *held, uint64_t *units, uint64_t *protected_units) {
-    if (!h) return fail(PW_ERR_INVALID, "null pointer");
-    if (held) *held = h->held;
-    if (units) *units = h->units;
-    if (protected_units) *protected_units = h->protected_units;
-    return PW_OK;
-}
-
-PW_EXPORT int pw_holdout_dev_fill(const pw_holdout_dev *h, uint32_t *d_u, uint32_t *d_v, float *d_weight) {
-    if (!h || (h->held && (!d_u || !d_v || !d_weight))) return fail(PW_ERR_INVALID, "null pointer");
-    if (!h->held) return PW_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpy(d_u, h->d_u.p, sizeof(uint32_t) * h->held, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(d_v, h->d_v.p, sizeof(uint32_t) * h->held, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(d_weight, h->d_w.p, sizeof(float) * h->held, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    return PW_OK;
-}
-
-PW_EXPORT int pw_selftest_holdout_edges(int on_device, int device, const uint32_t *indptr, const uint32_t *indices, const float *data, uint32_t n_nodes,
-                                        int directed, uint32_t seed, uint64_t first_word, uint32_t threshold, int protect, uint64_t batch,
-                                        uint32_t *out_indptr, uint32_t *out_indices, float *out_data, uint32_t *u, uint32_t *v, float *weight,
-                                        uint64_t counts[4]) {
-    if (!indptr || !out_indptr || !counts || n_nodes == 0) return fail(PW_ERR_INVALID, "null pointer");
-    const uint32_t nnz = indptr[n_nodes];
-    if (nnz && (!indices || !out_indices || !u || !v || !weight)) return fail(PW_ERR_INVALID, "null pointer");
-    int rc;
-    if ((rc = ho_check_args(first_word))) return rc;
-    if (!on_device) {
-        if (indptr[0] != 0) return fail(PW_ERR_INVALID, "indptr[0] != 0");
-        for (uint32_t r = 0; r < n_nodes; r++)
-            if (indptr[r + 1] < indptr[r]) return fail(PW_ERR_INVALID, "indptr not monotone");
-        for (uint32_t r = 0; r < n_nodes; r++)
-            for (uint32_t e = indptr[r]; e < indptr[r + 1]; e++)
-                if (indices[e] >= n_nodes || (e > indptr[r] && indices[e] <= indices[e - 1]))
-                    return fail(PW_ERR_INVALID, "pw_holdout_edges: column indices must be below n_nodes and strictly ascending within a row");
-        std::vector<uint32_t> words(nnz), t_indptr((size_t)n_nodes + 1), t_indices(nnz), hu(nnz), hv(nnz);
-        std::vector<float> t_data(nnz), hw(nnz);
-        if (nnz) pw::mt_words_host(seed, first_word, nnz, words.data());
-        uint64_t where = 0, cnt[4];
-        if (pw::ho_host_split(indptr, indices, data, n_nodes, directed, protect, threshold, [&](uint32_t e) { return words[e]; }, t_indptr.data(),
-                              t_indices.data(), t_data.data(), hu.data(), hv.data(), hw.data(), cnt, &where) == pw::HO_HOST_MISSING)
-            return ho_missing_mate(where);
-        memcpy(out_indptr, t_indptr.data(), sizeof(uint32_t) * ((size_t)n_nodes + 1));
-        if (cnt[0]) memcpy(out_indices, t_indices.data(), sizeof(uint32_t) * cnt[0]);
-        if (cnt[0] && out_data) memcpy(out_data, t_data.data(), sizeof(float) * cnt[0]);
-        if (cnt[1]) {
-            memcpy(u, hu.data(), sizeof(uint32_t) * cnt[1]);
-            memcpy(v, hv.data(), sizeof(uint32_t) * cnt[1]);
-            memcpy(weight, hw.data(), sizeof(float) * cnt[1]);
-        }
-        memcpy(counts, cnt, sizeof(cnt));
-        return PW_OK;
-    }
-    pw_graph *raw = nullptr;
-    if ((rc = pw_csr_create(indptr, indices, data, n_nodes, nnz, device, &raw))) return rc;
-    GraphOwner g(raw);   // (declared before the results: they go first)
-    pw_csr_dev *c_raw = nullptr;
-    pw_holdout_dev *h_raw = nullptr;
-    if ((rc = holdout_edges_impl(g.get(), directed, seed, first_word, threshold, protect, batch, &c_raw, &h_raw, nullptr))) return rc;
-    std::unique_ptr<pw_csr_dev, CsrDevDeleter> c(c_raw);
-    std::unique_ptr<pw_holdout_dev, HoldoutDeleter> ho(h_raw);
-    if ((rc = pw_csr_dev_export(c.get(), out_indptr, out_indices, out_data))) return rc;
-    if (ho->held) {
-        HIP_TRY(hipMemcpy(u, ho->d_u.p, sizeof(uint32_t) * ho->held, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(v, ho->d_v.p, sizeof(uint32_t) * ho->held, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(weight, ho->d_w.p, sizeof(float) * ho->held, hipMemcpyDeviceToHost));
-    }
-    counts[0] = c->nnz; counts[1] = ho->held; counts[2] = ho->units; counts[3] = ho->protected_units;
-    return PW_OK;
-}
-
+#include "drv_holdout.hip.h"
 #include "drv_selftest.hip.h"
 #include "drv_ingest_host.hip.h"
